@@ -2,6 +2,7 @@
 """bench.py -- denoised states/sec of the 18-step EDM Heun sampler (35 U-Net evaluations per state).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s128|s32|ref128|s128l3] [--batch B]
+                    [--dump-outputs DIR] [--full]
 
 `--gpus N` (N > 1) works as typed: before anything touches the GPU the process starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
@@ -15,10 +16,20 @@ scaling is weak: per-GPU batch is fixed.  Rank 0 prints ONE JSON line.
 What is timed, and how:
   * headline `value`: K sampler calls between barrier + synchronize brackets, profiler OFF, the whole call replayed
     from one HIP graph (mcedm_amd.lib.GraphedSampler; `--no-graph` launches the ~4000 kernels eagerly instead);
-  * `roofline` / `kernels`: a SEPARATE pass of `--profile-steps` eager calls with HIP event pairs around every launch
+    `ms_per_step` is the wall time of one of those K calls.  A plain run does only this: set-up, W warm-up calls, the K
+    timed calls, the optional output dump, and the line.
+  * `--full` adds, after the timed calls (none of it changes `value`):
+    `roofline` / `kernels`: a SEPARATE pass of `--profile-steps` eager calls with HIP event pairs around every launch
     on the launch stream (mcedm_prof_enable): per-kernel average duration against algorithmic flops / bytes;
-  * `cpu_baseline`: the oracle (CPU restatement of the reference) on a bounded sample, 1 warm-up + median of 3, on all
-    usable physical cores (host cores capped by the container's CPU quota) and on one thread.
+    `unet_fwd_ms` and the roofline fractions; the training step (`--no-train` skips it); the `secondary` workloads
+    (`--no-secondary`); and `cpu_baseline` (`--no-cpu-baseline`): the oracle (CPU restatement of the reference) on a
+    bounded sample, 1 warm-up + median of 3, on all usable physical cores (host cores capped by the container's CPU
+    quota) and on one thread.
+
+`--dump-outputs DIR` writes what the last timed call returned -- the final sampler state, float64 [B, 1, H, W, C] --
+to DIR/samples.npy (DIR/samples_rank<r>.npy on each rank when N > 1).  Weights, inputs and churn seeds depend only on
+the arguments, so two builds run with the same arguments can be compared output for output.  An output larger than
+its share of DUMP_BYTES is written as the flattened values at a fixed, seeded set of positions (sorted).
 
 Workloads (BASELINE.json `configs`):
   s128    SWE-periodic 128x128, EDM U-Net ch=128, ch_mult [1,1,1,1], attention at 16^2, 32 states / GPU  (config 3; default,
@@ -29,7 +40,8 @@ Workloads (BASELINE.json `configs`):
   darcy128  the single-task conditional EDM (1 + 1 -> 1 channels, ch=128) on 128x128 Darcy-sized fields, 32 states / GPU (config 4)
   repaint128  RePaint-style EDM sampling of the DDPM U-Net, 18 steps x 32 resampling loops, 32 states / GPU       (config 5)
   ref_default  ref128's network with the reference's SHIPPED sampler config (50 steps, S_churn 15, n_samples 5): 99 evaluations / state
-The default run also reports s32 / ref128 / s128l3 / darcy128 / ref_default / repaint128 as `secondary` entries.
+`--full` on the default workload also reports s32 / ref128 / s128l3 / darcy128 / ref_default / repaint128 as `secondary`
+entries.
 """
 import argparse
 import hashlib
@@ -82,21 +94,28 @@ TRAIN_LEG_TIMEOUT_S = 300      # watchdog of the multi-rank training leg (an unt
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_HBM_GBPS = 8000.0
 STEPS = 18                      # Heun steps -> 2*18 - 1 = 35 U-Net evaluations per state
+DUMP_BYTES = 64 * 10**6         # --dump-outputs: bytes written at most, over all ranks
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed sampler calls (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="s128", choices=sorted(WORKLOADS) + ["repaint128"])
     ap.add_argument("--batch", type=int, default=0, help="states per GPU (default: the workload's)")
     ap.add_argument("--no-graph", action="store_true", help="launch the sampler's kernels eagerly instead of one HIP graph")
-    ap.add_argument("--profile-steps", type=int, default=1, help="sampler calls in the separate event-timed pass")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the (untimed) training-step measurement")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of the other workloads")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed call's output to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="after the timed calls, also measure the profiled pass, the U-Net "
+                    "forward, the training step, the secondary workloads and the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=1, help="sampler calls in the separate event-timed pass (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (--full)")
+    ap.add_argument("--no-train", action="store_true", help="skip the (untimed) training-step measurement (--full)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of the other workloads (--full)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -221,6 +240,19 @@ def csrc_digest():
         if f.endswith((".hip", ".hpp")):
             h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(dirname, name, out, budget):
+    """`out` (a tensor) -> dirname/name.npy as float64 (float32 if it is no float64), whole if it fits `budget` bytes, else
+    its flattened values at the sorted positions of a seeded draw without replacement (the same for every run of a shape)."""
+    import numpy as np
+    a = out.detach().cpu().numpy()
+    a = a if a.dtype == np.float64 else a.astype(np.float32)
+    if a.nbytes > budget:
+        n = max(1, budget // a.itemsize)
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def committed_traffic(kernel_name):
@@ -492,13 +524,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-
-    prof = run.profile(args.profile_steps) if rank == 0 else []
-    fwd_ms = run.fwd_ms()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "samples" if world == 1 else f"samples_rank{rank}", out, DUMP_BYTES // world)
 
     def headline_line(train_ms_):
         states = B * world * args.steps
-        return {
+        line = {
             "metric": "denoised_states_per_sec_18step_edm_heun", "value": states / elapsed, "unit": "states/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -508,12 +539,26 @@ def main():
                                   "EDM Heun, 18 steps, 35 NFE/state, S_churn=0, w=0, fp64 state / fp32 net",
                        "parallelism": f"batch-sharded x{world}, no data-path collective",
                        "launch": "eager" if args.no_graph else "one HIP graph per sampler call"},
-            "timed_with_profiler": False, "unet_fwd_ms": fwd_ms, "unet_fwd_batch": B, "train_step_ms": train_ms_,
-            "train_samples_per_sec": (B * world / (train_ms_ * 1e-3)) if train_ms_ else None,
-            "roofline": roofline_of(prof), "kernels": kernel_table(prof)[:8], "hbm_bound_kernels": hbm_bound_rows(prof),
-            "csrc_digest": csrc_digest(),
-            **(fractions(args.workload, states / elapsed / world, fwd_ms, B) if not repaint else {}),
+            "timed_with_profiler": False, "csrc_digest": csrc_digest(),
         }
+        if args.full:
+            line.update({
+                "unet_fwd_ms": fwd_ms, "unet_fwd_batch": B, "train_step_ms": train_ms_,
+                "train_samples_per_sec": (B * world / (train_ms_ * 1e-3)) if train_ms_ else None,
+                "roofline": roofline_of(prof), "kernels": kernel_table(prof)[:8], "hbm_bound_kernels": hbm_bound_rows(prof),
+                **(fractions(args.workload, states / elapsed / world, fwd_ms, B) if not repaint else {}),
+            })
+        return line
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(headline_line(None), status="ok")), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    prof = run.profile(args.profile_steps) if rank == 0 else []
+    fwd_ms = run.fwd_ms()
 
     # one data-parallel training step (models/mcedm.py:254-281 + clip/Adam/EMA), outside the timed region:
     # noise -> denoise(training) -> loss -> backward -> gradient all-reduce -> fused clip+Adam+EMA

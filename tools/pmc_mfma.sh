@@ -11,7 +11,7 @@ cd /tmp
 for wl in s128 s32; do
   for pmc in MfmaUtil "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
     name=${tag}_pmc_${wl}_$(echo $pmc | cut -d' ' -f1)
-    timeout -k 10 400 rocprofv3 --pmc $pmc -d $out/$name -o pmc -- python3 $root/bench.py --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-train --no-graph --profile-steps 0 > $out/$name.log 2>&1 || { echo "$name failed"; tail -5 $out/$name.log; exit 1; }
+    timeout -k 10 400 rocprofv3 --pmc $pmc -d $out/$name -o pmc -- python3 $root/bench.py --full --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-train --no-graph --profile-steps 0 > $out/$name.log 2>&1 || { echo "$name failed"; tail -5 $out/$name.log; exit 1; }
     echo "$name done"
   done
 done

@@ -11,7 +11,7 @@ what=${2:-all}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp
 out=$root/gpurun_out
-common="--no-cpu-baseline --no-secondary --no-train --no-graph"
+common="--full --no-cpu-baseline --no-secondary --no-train --no-graph"
 cd /tmp
 trace() {   # name, seconds, program args...
   local name=$1 secs=$2; shift 2
