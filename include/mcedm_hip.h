@@ -269,6 +269,68 @@ int mcedm_adam_ema_step(float* param, const float* grad, float* exp_avg, float* 
                         const double* sqnorm, double max_norm, double grad_scale, double ema_beta,
                         int64_t step, void* stream);
 
+/* ---- epsilon-prediction (DDPM) training and VP sampling of the ADM U-Net: PlCondDdim, models/ddim.py:1053-1605 ----------
+ * Self-conditioning (hparams.model.self_cond, adm_blocks.py:227-238, 318-338) needs no plan of its own: conv_in reads
+ * cat(cond, x_self_cond, x), which is the cat_cond network with cond_channels' = cond_channels + in_channels fed
+ * cond' = cat(cond or 0, x_self_cond or 0) -- the same parameter table, conv_in's weight [ch, cond + 2 in, 3, 3] included.
+ * The entries below write cond' into a caller buffer [B, cond_channels + in_channels, H, W] instead of a torch.cat. */
+
+/* x_noise = x * sqrt_ab[t_b] + noise * sqrt_1mab[t_b] and labels[b] = (float)t_b  (PlDdim.forward, models/ddim.py:195-197;
+ * the labels are t.float(), :206, 209).  sqrt_ab / sqrt_1mab: n_table fp32 values on the device, (1 - betas).cumprod(0).sqrt()
+ * and (1 - that).sqrt() formed by the caller with the reference's expression; t: B int64 device values in [0, n_table). */
+int mcedm_eps_noise_inputs(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
+                           int n_table, int B, int C, int H, int W, float* x_noise, float* labels, void* stream);
+/* Self-conditioning input cond' [B, cond_channels + in_channels, H, W]: channels [0, cond_channels) = cond (NULL: zeros, the
+ * conditioning switched off, models/ddim.py:202-203), channels [cond_channels, +in_channels) = the self-conditioning estimate
+ * x_sc = (x_noise - F0 * sqrt_1mab[t_b]) / sqrt_ab[t_b] of the no-grad pre-pass F0 = model(x_noise, t, cond)
+ * (models/ddim.py:205-210); F0 == NULL: zeros (no pre-pass this batch; x_noise, t and the tables may then be NULL too). */
+int mcedm_eps_self_cond(const float* x_noise, const float* F0, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
+                        int n_table, const float* cond, int cond_channels, int in_channels, int B, int H, int W,
+                        float* cond_out, void* stream);
+/* NoiseEstimationLoss (models/losses.py:39-59): loss = mean_b sum_chw (F - eps)^2 and dF = 2 (F - eps) / B (NULL: not written).
+ * loss_out: 1 fp32 (device).  scratch as for mcedm_edm_loss: the same fixed-order, atomic-free sum (bitwise reproducible). */
+int mcedm_eps_loss(const float* F, const float* eps, int B, int C, int H, int W, float* loss_out, float* dF_out, void* scratch,
+                   size_t scratch_bytes, void* stream);
+/* Backward of mcedm_unet_forward(..., training = 1) through the U-Net from dF = dLoss/d out (the EDM entries start from dD and
+ * scale it by c_out first).  x, cond, x_scale, noise_labels, n_noise: the arguments of that forward, whose activations
+ * `workspace` still holds (mcedm_unet_workspace_bytes(training = 1)).  grads[i] receives dLoss/dparam_i (overwritten).  The
+ * _bucketed form records bucket_events as mcedm_edm_denoise_backward_bucketed does. */
+int mcedm_unet_backward(const mcedm_plan* plan, const void* packed, const float* const* params, const float* x,
+                        const float* cond, const float* x_scale, const float* noise_labels, int n_noise, const float* dF,
+                        float* const* grads, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+int mcedm_unet_backward_bucketed(const mcedm_plan* plan, const void* packed, const float* const* params, const float* x,
+                                 const float* cond, const float* x_scale, const float* noise_labels, int n_noise,
+                                 const float* dF, float* const* grads, void* workspace, size_t workspace_bytes, int B, int H,
+                                 int W, int n_buckets, const int32_t* bucket_first_param, void* const* bucket_events,
+                                 void* stream);
+
+/* VP-preconditioned Heun sampler of an epsilon network (PlCondDdim.sample_edm, models/ddim.py:1532-1601, around get_denoised
+ * :915-947): D = x + (-sigma) F(c_in x, c_noise, c_in cond), c_in = 1 / sqrt(sigma^2 + 1) in fp32, state fp64.  The host
+ * rounds the schedule onto edm_steps (round_sigma, :949-957) and passes the result; the evaluation at t_hat[i] uses
+ * c_noise[2 i], the correction at t_steps[i + 1] c_noise[2 i + 1] (the last step has none).  cond carries the first
+ * cond_channels channels of the plan's conditioning input; the rest (self-conditioning, get_self_cond_edm returns None,
+ * :1603-1605) read zeros.  |w| >= 1e-3 with cond given: F = (w + 1) F(cond) - w F(no cond) (:941-942).  All host arrays are
+ * read during the call only. */
+typedef struct {
+  int32_t timesteps;         /* N */
+  int32_t cond_channels;     /* channels of `cond`; <= the plan's cond_channels */
+  const double* t_steps;     /* N + 1 host values, rounded, t_steps[N] = 0 */
+  const double* t_hat;       /* N host values, round_sigma(t_cur + gamma t_cur) */
+  const float* c_noise;      /* 2 N host values, num_timesteps - 1 - index(round_sigma(sigma)) */
+  double S_noise;
+  double w;
+} mcedm_vp_sampler_desc;
+int mcedm_vp_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes);
+/* init_noise [B, in, H, W] fp32 (x_0 = init_noise * t_steps[0] in fp64); step_noise [N, B, in, H, W] fp64, step i's
+ * randn_like(x_cur) (NULL only when t_hat[i] == t_steps[i] for every i); out fp64 [B, 1 or N + 1, H, W, in]. */
+int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                         const float* init_noise, const double* step_noise, double* out, int return_last, void* workspace,
+                         size_t workspace_bytes, int B, int H, int W, void* stream);
+/* The same with the churn noise generated on the device, as mcedm_heun_sample_rng does (draw = step index). */
+int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                             const float* init_noise, const uint64_t* rng_seed, double* out, int return_last, void* workspace,
+                             size_t workspace_bytes, int B, int H, int W, void* stream);
+
 /* ---- kernel-level entry points ----------------------------------------------------------
  * The building blocks the schedules above are made of, exported so that each kernel can be
  * parity-tested against the oracle and timed on its own (bench.py roofline leg). */

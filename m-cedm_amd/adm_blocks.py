@@ -7,8 +7,9 @@ The sub-modules below only OWN parameters (initialised with the reference's dist
 models/adm_blocks.py:10-15,221-222); the network is executed as one fused schedule by the C library,
 not module by module.  ``dx_cond`` (the network conditioned on the PDE-residual gradient, models/adm_blocks.py:233-280,
 334-362) is built in both of the reference's forms: ``cat_dx=True`` (dx concatenated to conv_in's input) and
-``cat_dx=False`` (``dx_enc`` = Conv3x3 -> GELU -> Conv3x3 and ``combine_enc``).  Configurations outside the hot path
-(cond_enc / self-conditioning / class or augment labels / dropout) raise NotImplementedError instead of silently computing
+``cat_dx=False`` (``dx_enc`` = Conv3x3 -> GELU -> Conv3x3 and ``combine_enc``).  ``self_cond`` (adm_blocks.py:227-238,
+318-331) runs as the cat_cond network whose conditioning input is cat(cond, x_self_cond).  Configurations outside the hot path
+(cond_enc / class or augment labels / dropout) raise NotImplementedError instead of silently computing
 something else.  There is no PyTorch fallback: without the HIP library or on a CPU tensor, forward raises.
 """
 from __future__ import annotations
@@ -96,8 +97,7 @@ class DhariwalUNet(nn.Module):
         super().__init__()
         m = hparams.model
         unsupported = []
-        if _get(m, "self_cond", False):
-            unsupported.append("self_cond")
+        self_cond = bool(_get(m, "self_cond", False))
         if m.augment_dim or m.label_dim:
             unsupported.append("augment_dim/label_dim")
         if m.dropout:
@@ -105,6 +105,8 @@ class DhariwalUNet(nn.Module):
         cond_channels = _get(m, "cond_channels", 0)
         if cond_channels > 0 and not _get(m, "cat_cond", False):
             unsupported.append("cond_enc (cat_cond=False)")
+        if self_cond and _get(m, "dx_cond", False):
+            unsupported.append("self_cond with dx_cond")
         ch, mult = m.ch, tuple(m.ch_mult)
         # attention widths: the bottleneck 'in0' block always, plus every level named in attn_resolutions; the
         # kernels are built for head_dim 64, the reference's head_dim is C / (C // 64) (adm_blocks.py:135,175)
@@ -118,15 +120,18 @@ class DhariwalUNet(nn.Module):
         self.dx_cond = bool(_get(m, "dx_cond", False))
         self.cat_dx = bool(_get(m, "cat_dx", False))
         dx_mode = _lib.DX_NONE if not self.dx_cond else (_lib.DX_CAT if self.cat_dx else _lib.DX_ENC)
-        # adm_blocks.py:236-238: cond and (cat_dx) dx are stacked to the input
-        self.in_channels = m.in_channels + cond_channels + (m.in_channels if dx_mode == _lib.DX_CAT else 0)
+        # adm_blocks.py:236-238: cond, (self_cond) x_self_cond and (cat_dx) dx are stacked to the input
+        self.in_channels = m.in_channels * (2 if self_cond else 1) + cond_channels + (m.in_channels if dx_mode == _lib.DX_CAT else 0)
         self.cond_channels = cond_channels
         self.state_channels = m.in_channels
         self.out_channels = m.out_ch
         self.cat_condition = True
-        self.self_condition = False
+        self.self_condition = self_cond
         self.label_dropout = m.label_dropout
-        self._arch = dict(in_channels=m.in_channels, cond_channels=cond_channels, out_channels=m.out_ch, ch=ch,
+        # conv_in reads cat(cond, x_self_cond, x) (adm_blocks.py:318-331): to the HIP plan that is the cat_cond network with
+        # cond' = cat(cond, x_self_cond), cond_channels + in_channels wide -- the same parameter table
+        self.plan_cond_channels = cond_channels + (m.in_channels if self_cond else 0)
+        self._arch = dict(in_channels=m.in_channels, cond_channels=self.plan_cond_channels, out_channels=m.out_ch, ch=ch,
                           ch_mult=mult, num_res_blocks=m.num_res_blocks, attn_resolutions=tuple(m.attn_resolutions),
                           resolution=m.resolution, dx_channels=m.in_channels if self.dx_cond else 0, dx_mode=dx_mode)
         self.map_noise = PositionalEmbedding(ch)
@@ -211,8 +216,10 @@ class DhariwalUNet(nn.Module):
         return self._packed
 
     def _check_extra(self, x_self_cond, dx, class_labels, augment_labels):
-        if x_self_cond is not None or class_labels is not None or augment_labels is not None:
-            raise NotImplementedError("x_self_cond / class_labels / augment_labels are outside the hot path")
+        if class_labels is not None or augment_labels is not None:
+            raise NotImplementedError("class_labels / augment_labels are outside the hot path")
+        if x_self_cond is not None and not self.self_condition:
+            raise NotImplementedError("x_self_cond given to a network built with self_cond=False (the reference ignores it silently)")
         if dx is not None and not self.dx_cond:
             raise NotImplementedError("dx given to a network built with dx_cond=False (the reference ignores it silently)")
 
@@ -225,7 +232,26 @@ class DhariwalUNet(nn.Module):
         labels = noise_labels.to(torch.float32).reshape(-1).contiguous()
         cond = cond.to(torch.float32).contiguous() if cond is not None else None
         dx = dx.to(torch.float32).contiguous() if dx is not None else None
+        if self.self_condition:
+            cond = self.stage_self_cond(cond, None if x_self_cond is None else x_self_cond.to(torch.float32).contiguous(), x)
         return self.plan.forward(self.packed_weights(), x, labels, cond=cond, ws=self._ws, dx=dx)
+
+    def stage_self_cond(self, cond, x_self_cond, x, out=None):
+        """cond' = cat(cond or 0, x_self_cond or 0) for the plan's widened conditioning input (mcedm_eps_self_cond); None
+        when both are None (the plan then reads zeros)."""
+        if cond is None and x_self_cond is None:
+            return None
+        B, _, H, W = x.shape
+        if out is None:
+            out = torch.empty((B, self.plan_cond_channels, H, W), dtype=torch.float32, device=x.device)
+        # x_self_cond enters as F0 with t = 0 and the table (1, 0): (x_sc - F0 * 0) / 1 = x_sc bit for bit
+        if x_self_cond is not None:
+            one = torch.ones(1, dtype=torch.float32, device=x.device)
+            zero = torch.zeros(1, dtype=torch.float32, device=x.device)
+            t0 = torch.zeros(B, dtype=torch.int64, device=x.device)
+            return _lib.eps_self_cond(out, cond, self.cond_channels, self.state_channels, x_noise=x_self_cond, F0=x_self_cond,
+                                      t=t0, sqrt_ab=one, sqrt_1mab=zero)
+        return _lib.eps_self_cond(out, cond, self.cond_channels, self.state_channels)
 
 
 class EmaModel(nn.Module):

@@ -308,12 +308,22 @@ extern "C" int mcedm_unet_grad_buckets(const mcedm_plan* plan, int max_buckets, 
   return MCEDM_OK;
 }
 
+// Where the backward starts: the EDM entries hand in dD and the preconditioning the forward kept in the workspace header
+// (c_out, c_noise, the c_in rows of conv_in); the plain U-Net backward (mcedm_unet_backward) hands in dF and the forward's own
+// noise labels / x_scale.
+struct BwdFrom {
+  const float* dF;            // != NULL: dLoss/dF given, no c_out scaling
+  const float* noise_labels;  // the forward's labels (dF mode)
+  const float* x_scale;       // the forward's x_scale (dF mode), NULL = 1
+};
+
 static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, const float* const* params,
                                  const float* x, const float* dx, int n_sigma, const float* cond,
                                  const float* dD, float* const* grads, void* workspace, size_t workspace_bytes,
                                  int B, int H, int W, int n_buckets, const int32_t* bucket_first,
-                                 void* const* bucket_events, void* stream) {
-  MCEDM_REQUIRE(plan && packed && params && x && dD && grads && workspace, "denoise_backward: null argument");
+                                 void* const* bucket_events, void* stream, const BwdFrom& from = BwdFrom{}) {
+  MCEDM_REQUIRE(plan && packed && params && x && (dD || from.dF) && grads && workspace, "denoise_backward: null argument");
+  MCEDM_REQUIRE(!from.dF || from.noise_labels, "unet_backward: null noise_labels");
   const mcedm_plan& P = *plan;
   MCEDM_REQUIRE(dx == nullptr || P.desc.dx_mode != MCEDM_DX_NONE, "denoise_backward: dx given to a plan without dx_cond");
   if (n_buckets > 0) {
@@ -355,7 +365,8 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   float* pe = c.X(S.pe); float* u1 = c.X(S.u1); float* u2 = c.X(S.u2);
   float* t1 = c.X(S.t1); float* t2 = c.X(S.t2); float* t3 = c.X(S.t3);
   float* emb = c.X(S.emb);
-  hipLaunchKernelGGL(emb_save_kernel, dim3(n), dim3(256), 2 * ch * sizeof(float), s, at<float>(workspace, hd.c_noise),
+  hipLaunchKernelGGL(emb_save_kernel, dim3(n), dim3(256), 2 * ch * sizeof(float), s,
+                     from.dF ? from.noise_labels : at<float>(workspace, hd.c_noise),
                      pk + P.freqs, pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1, ch, pe, u1, u2);
   MCEDM_LAUNCH_CHECK("emb_save_kernel");
   const size_t ne = (size_t)n * ch;
@@ -364,16 +375,20 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   MCEDM_LAUNCH_CHECK("silu_map_kernel");
   c.emb = emb;
 
-  // dF = c_out * dD
-  hipLaunchKernelGGL(scale_by_cout_kernel, dim3(grid_for(per * B)), dim3(256), 0, s, dD, at<float>(workspace, hd.coefs4),
-                     n_sigma, per, per * B, c.X(S.gF));
-  MCEDM_LAUNCH_CHECK("scale_by_cout_kernel");
+  // dF = c_out * dD (EDM entries) or given
+  const float* gF = from.dF;
+  if (!gF) {
+    hipLaunchKernelGGL(scale_by_cout_kernel, dim3(grid_for(per * B)), dim3(256), 0, s, dD, at<float>(workspace, hd.coefs4),
+                       n_sigma, per, per * B, c.X(S.gF));
+    MCEDM_LAUNCH_CHECK("scale_by_cout_kernel");
+    gF = c.X(S.gF);
+  }
   // out = out_conv(silu(out_norm(last)))
   const TRef& last = L.t[L.last];
-  WgradArgs wo{c.X(S.gF), c.T(L.last), nullptr, last.C, 0, c.CF(L.coef_out), 1, 1, RS_NONE, H, W, H, W,
+  WgradArgs wo{gF, c.T(L.last), nullptr, last.C, 0, c.CF(L.coef_out), 1, 1, RS_NONE, H, W, H, W,
                P.desc.out_channels, B, c.X(S.wg), nullptr};
   if ((rc = launch_wgrad(wo, 9, grads[P.conv_out.w], grads[P.conv_out.b], 0, c.X(c.S.xact), s))) return rc;
-  if ((rc = dgrad(c, P.conv_out, c.X(S.gF), H, W, c.X(S.dact)))) return rc;
+  if ((rc = dgrad(c, P.conv_out, gF, H, W, c.X(S.dact)))) return rc;
   GnBwdArgs go{c.X(S.dact), RS_NONE, c.T(L.last), nullptr, last.C, 0, H, W, B, P.out_norm.groups, c.CF(L.coef_out),
                c.T(L.stats_out), pk + P.out_norm.gamma, nullptr, 0, 0, 1, c.G(L.last), nullptr, 0, nullptr, 0, 0, c.X(S.ab)};
   if ((rc = launch_gn_bwd(with_sync(c, go), s))) return rc;
@@ -415,8 +430,9 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   }
   // conv_in: weight / bias gradient only (its inputs carry no gradient)
   const bool catdx = P.desc.dx_mode == MCEDM_DX_CAT;
+  const Coef* coef_in = (from.dF && !from.x_scale) ? nullptr : at<Coef>(workspace, hd.coef_in);   // the forward's conv_in rows
   WgradArgs wi{dy_in, cond, catdx ? c.T(L.xdx) : x, P.desc.cond_channels, P.desc.in_channels + (catdx ? P.desc.dx_channels : 0),
-               at<Coef>(workspace, hd.coef_in), n_sigma > 1 ? 1 : 0, 0, RS_NONE, H, W, H, W, P.conv_in.cout, B, c.X(S.wg), nullptr};
+               coef_in, n_sigma > 1 ? 1 : 0, 0, RS_NONE, H, W, H, W, P.conv_in.cout, B, c.X(S.wg), nullptr};
   if ((rc = launch_wgrad(wi, 9, grads[P.conv_in.w], grads[P.conv_in.b], 0, c.X(c.S.xact), s))) return rc;
 
   // mapping MLP: film = emb Waff^T + baff, emb = silu(u2), u2 = W1 silu(u1) + b1, u1 = W0 pe + b0
@@ -469,4 +485,27 @@ extern "C" int mcedm_edm_denoise_backward_bucketed(const mcedm_plan* plan, const
   MCEDM_REQUIRE(n_buckets >= 1, "denoise_backward_bucketed: n_buckets must be >= 1");
   return denoise_backward_impl(plan, packed, params, x, nullptr, n_sigma, cond, dD, grads, workspace, workspace_bytes, B, H, W,
                                n_buckets, bucket_first_param, bucket_events, stream);
+}
+
+// the network backward from dF (PlCondDdim.training_step's epsilon loss, models/ddim.py:1118-1152): denoise_backward_impl
+// without the c_out scaling, on the activations of mcedm_unet_forward(..., training = 1)
+extern "C" int mcedm_unet_backward_bucketed(const mcedm_plan* plan, const void* packed, const float* const* params,
+                                            const float* x, const float* cond, const float* x_scale, const float* noise_labels,
+                                            int n_noise, const float* dF, float* const* grads, void* workspace,
+                                            size_t workspace_bytes, int B, int H, int W, int n_buckets,
+                                            const int32_t* bucket_first_param, void* const* bucket_events, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(dF != nullptr, "unet_backward: null dF");
+  MCEDM_REQUIRE(n_buckets >= 0, "unet_backward: n_buckets must be >= 0");
+  MCEDM_REQUIRE(plan == nullptr || plan->desc.dx_mode == MCEDM_DX_NONE, "unet_backward: dx_cond plans go through mcedm_edm_denoise_backward_dx");
+  return denoise_backward_impl(plan, packed, params, x, nullptr, n_noise, cond, nullptr, grads, workspace, workspace_bytes, B, H, W,
+                               n_buckets, bucket_first_param, bucket_events, stream, BwdFrom{dF, noise_labels, x_scale});
+}
+
+extern "C" int mcedm_unet_backward(const mcedm_plan* plan, const void* packed, const float* const* params, const float* x,
+                                   const float* cond, const float* x_scale, const float* noise_labels, int n_noise,
+                                   const float* dF, float* const* grads, void* workspace, size_t workspace_bytes, int B, int H,
+                                   int W, void* stream) {
+  return mcedm_unet_backward_bucketed(plan, packed, params, x, cond, x_scale, noise_labels, n_noise, dF, grads, workspace,
+                                      workspace_bytes, B, H, W, 0, nullptr, nullptr, stream);
 }

@@ -271,6 +271,36 @@ int launch_vp_coef(float c_in, int n_self, int n_in, Coef* out, hipStream_t s) {
   return MCEDM_OK;
 }
 
+// VP sampler of the ADM U-Net (PlCondDdim.sample_edm, models/ddim.py:1532-1601): one row set of conv_in transforms for
+// cat(cond', x), every channel scaled by c_in (get_denoised scales x, cond and x_self_cond, :921-935), and the network's
+// noise label c_noise written where the forward reads it
+__global__ void vp_prepare_kernel(float c_in, int n_rows, float c_noise, Coef* __restrict__ coef, float* __restrict__ label) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n_rows) coef[c] = Coef{0.f, c_in, 0.f, 0.f};
+  if (c == 0) *label = c_noise;
+}
+int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* label, hipStream_t s) {
+  hipLaunchKernelGGL(vp_prepare_kernel, dim3(ceil_div(n_rows, 64)), dim3(64), 0, s, c_in, n_rows, c_noise, coef, label);
+  MCEDM_LAUNCH_CHECK("vp_prepare_kernel");
+  return MCEDM_OK;
+}
+// D = 1 * x + c_out * F, F = (w + 1) * F - w * F_uncond when Fu != NULL   (models/ddim.py:940-945)
+__global__ void vp_cfg_finish_kernel(const float* __restrict__ x, const float* __restrict__ F, const float* __restrict__ Fu,
+                                     float w1, float w, float c_out, size_t total, float* __restrict__ D) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    float f = F[i];
+    if (Fu) f = w1 * f - w * Fu[i];
+    D[i] = 1.0f * x[i] + c_out * f;
+  }
+}
+int launch_vp_cfg_finish(const float* x, const float* F, const float* Fu, double w, float sigma, size_t total, float* D,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(vp_cfg_finish_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, F, Fu, (float)(w + 1.0), (float)w, -sigma,
+                     total, D);
+  MCEDM_LAUNCH_CHECK("vp_cfg_finish_kernel");
+  return MCEDM_OK;
+}
+
 __global__ void repaint_init_kernel(const float* __restrict__ hu, const float* __restrict__ noise,
                                     const float* __restrict__ mask, float sa, float sb, double t0, size_t total,
                                     double* __restrict__ x, float* __restrict__ x32) {
@@ -383,6 +413,42 @@ __global__ void noise_inputs_kernel(const float* __restrict__ x, const float* __
   }
 }
 
+// ---- epsilon-prediction training (PlCondDdim, models/ddim.py:195-226, 1118-1152) ------------------------------------
+// x_noise = x * sqrt(a_t) + noise * sqrt(1 - a_t), labels = t.float()   (models/ddim.py:195-197, 209)
+__global__ void eps_noise_inputs_kernel(const float* __restrict__ x, const float* __restrict__ noise,
+                                        const int64_t* __restrict__ t, const float* __restrict__ sqrt_ab,
+                                        const float* __restrict__ sqrt_1mab, int n_table, size_t per_sample, size_t total,
+                                        float* __restrict__ x_noise, float* __restrict__ labels) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / per_sample;
+    int64_t tb = t[b];
+    tb = tb < 0 ? 0 : (tb >= n_table ? n_table - 1 : tb);           // the host checks the range; never read out of the table
+    if (i % per_sample == 0) labels[b] = (float)t[b];
+    x_noise[i] = x[i] * sqrt_ab[tb] + noise[i] * sqrt_1mab[tb];
+  }
+}
+
+// cond' = cat(cond or 0, x_sc or 0), x_sc = (x_noise - F0 * sqrt(1 - a_t)) / sqrt(a_t)   (models/ddim.py:205-210)
+__global__ void eps_self_cond_kernel(const float* __restrict__ x_noise, const float* __restrict__ F0,
+                                     const int64_t* __restrict__ t, const float* __restrict__ sqrt_ab,
+                                     const float* __restrict__ sqrt_1mab, int n_table, const float* __restrict__ cond,
+                                     int cond_ch, int in_ch, size_t hw, size_t total, float* __restrict__ out) {
+  const int Ct = cond_ch + in_ch;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t p = i % hw, c = (i / hw) % Ct, b = i / (hw * Ct);
+    float v = 0.0f;
+    if ((int)c < cond_ch) {
+      if (cond) v = cond[(b * cond_ch + c) * hw + p];
+    } else if (F0) {
+      int64_t tb = t[b];
+      tb = tb < 0 ? 0 : (tb >= n_table ? n_table - 1 : tb);
+      const size_t j = (b * in_ch + (c - cond_ch)) * hw + p;
+      v = (x_noise[j] - F0[j] * sqrt_1mab[tb]) / sqrt_ab[tb];
+    }
+    out[i] = v;
+  }
+}
+
 // ---- deterministic grid-wide sums (loss, gradient norm) ---------------------------------------------------------
 // Every block stores its partial sum (fp64) in a slot of a scratch array, takes a ticket, and the block that draws the LAST
 // ticket adds the slots in index order: the value does not depend on the order the blocks ran in (an atomicAdd of the
@@ -439,6 +505,30 @@ __global__ __launch_bounds__(256) void edm_loss_kernel(const float* __restrict__
     const float diff = D[base + i] * m - x[base + i] * m;
     acc += wgt * (diff * diff);
     if (dD) dD[base + i] = (2.0f * wgt / (float)B) * diff * m;
+  }
+  double t = acc;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  double total;
+  if (grid_sum_fixed_order(rs, (red[0] + red[1]) + (red[2] + red[3]), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, &total) &&
+      threadIdx.x == 0)
+    *loss = (float)(total / (double)B);
+}
+
+// NoiseEstimationLoss: loss = mean_b sum_chw (F - eps)^2 ; dF = (2 / B) (F - eps)   (models/losses.py:39-59)
+__global__ __launch_bounds__(256) void eps_loss_kernel(const float* __restrict__ F, const float* __restrict__ eps, int B,
+                                                       size_t per_sample, float* __restrict__ loss, float* __restrict__ dF,
+                                                       RedScratch rs) {
+  const int b = blockIdx.y;
+  const size_t base = (size_t)b * per_sample;
+  float acc = 0.f;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < per_sample; i += (size_t)gridDim.x * blockDim.x) {
+    const float diff = F[base + i] - eps[base + i];
+    acc += diff * diff;
+    if (dF) dF[base + i] = (2.0f / (float)B) * diff;
   }
   double t = acc;
 #pragma unroll
@@ -531,6 +621,49 @@ extern "C" int mcedm_edm_loss(const float* D, const float* x, const float* mask,
   hipLaunchKernelGGL(edm_loss_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, D, x, mask, sigma,
                      (float)sigma_data, B, per, loss_out, dD_out, rs);
   MCEDM_LAUNCH_CHECK("edm_loss_kernel");
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_eps_noise_inputs(const float* x, const float* noise, const int64_t* t, const float* sqrt_ab,
+                                      const float* sqrt_1mab, int n_table, int B, int C, int H, int W, float* x_noise,
+                                      float* labels, void* stream) {
+  MCEDM_REQUIRE(x && noise && t && sqrt_ab && sqrt_1mab && x_noise && labels, "eps_noise_inputs: null pointer");
+  MCEDM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && n_table > 0, "eps_noise_inputs: empty shape");
+  const size_t per = (size_t)C * H * W, total = per * B;
+  hipLaunchKernelGGL(eps_noise_inputs_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, noise, t, sqrt_ab,
+                     sqrt_1mab, n_table, per, total, x_noise, labels);
+  MCEDM_LAUNCH_CHECK("eps_noise_inputs_kernel");
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_eps_self_cond(const float* x_noise, const float* F0, const int64_t* t, const float* sqrt_ab,
+                                   const float* sqrt_1mab, int n_table, const float* cond, int cond_channels, int in_channels,
+                                   int B, int H, int W, float* cond_out, void* stream) {
+  MCEDM_REQUIRE(cond_out, "eps_self_cond: null output");
+  MCEDM_REQUIRE(!F0 || (x_noise && t && sqrt_ab && sqrt_1mab && n_table > 0), "eps_self_cond: F0 needs x_noise, t and the tables");
+  MCEDM_REQUIRE(B > 0 && H > 0 && W > 0 && cond_channels >= 0 && in_channels >= 0 && cond_channels + in_channels > 0, "eps_self_cond: bad shape");
+  const size_t hw = (size_t)H * W, total = (size_t)B * (cond_channels + in_channels) * hw;
+  hipLaunchKernelGGL(eps_self_cond_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x_noise, F0, t, sqrt_ab,
+                     sqrt_1mab, n_table, cond, cond_channels, in_channels, hw, total, cond_out);
+  MCEDM_LAUNCH_CHECK("eps_self_cond_kernel");
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_eps_loss(const float* F, const float* eps, int B, int C, int H, int W, float* loss_out, float* dF_out,
+                              void* scratch, size_t scratch_bytes, void* stream) {
+  MCEDM_REQUIRE(F && eps && loss_out, "eps_loss: null pointer");
+  MCEDM_REQUIRE(scratch && scratch_bytes >= MCEDM_REDUCE_SCRATCH_BYTES && ((size_t)scratch & 7) == 0,
+                "eps_loss: needs %d bytes of 8-byte aligned device scratch (MCEDM_REDUCE_SCRATCH_BYTES)", MCEDM_REDUCE_SCRATCH_BYTES);
+  MCEDM_REQUIRE(B > 0 && B <= 65535 && C > 0 && H > 0 && W > 0, "eps_loss: bad shape");
+  MCEDM_REQUIRE(B <= RED_MAX, "eps_loss: batch %d exceeds the reduction table (%d)", B, RED_MAX);
+  const size_t per = (size_t)C * H * W;
+  int gx = (int)((per + 255) / 256);                 // the same grid as mcedm_edm_loss
+  if (gx > 64) gx = 64;
+  if (gx > RED_MAX / B) gx = RED_MAX / B;
+  const RedScratch rs = red_scratch(scratch);
+  MCEDM_HIP_TRY(hipMemsetAsync(rs.ticket, 0, sizeof(unsigned), (hipStream_t)stream));
+  hipLaunchKernelGGL(eps_loss_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, F, eps, B, per, loss_out, dF_out, rs);
+  MCEDM_LAUNCH_CHECK("eps_loss_kernel");
   return MCEDM_OK;
 }
 

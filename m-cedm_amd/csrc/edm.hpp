@@ -47,6 +47,12 @@ int launch_darcy_guidance(const GuideIO& io, float* scratch, int B, int S, float
 int launch_vp_finish(const float* x, const float* F, float sigma, size_t total, float* D, hipStream_t s);
 // conv_in transform rows of the VP network input: n_self zero/self-conditioning channels pass, the state is scaled by c_in
 int launch_vp_coef(float c_in, int n_self, int n_in, Coef* out, hipStream_t s);
+// ---- VP sampler of the ADM U-Net (PlCondDdim.sample_edm, models/ddim.py:1532-1601)
+// conv_in rows: all n_rows channels of cat(cond', x) scaled by c_in; *label = c_noise
+int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* label, hipStream_t s);
+// D = x + (-sigma) * F with F = (w + 1) F - w Fu when Fu != NULL                  (get_denoised, ddim.py:940-945)
+int launch_vp_cfg_finish(const float* x, const float* F, const float* Fu, double w, float sigma, size_t total, float* D,
+                         hipStream_t s);
 // x0 = ((hu*sa + nz*sb)*m + nz*(1-m)) [fp32] -> fp64, times t0        (ddim.py:989-994), m = 1 marks KNOWN entries
 int launch_repaint_init(const float* hu, const float* noise, const float* mask, float sa, float sb, double t0, size_t total,
                         double* x, float* x32, hipStream_t s);

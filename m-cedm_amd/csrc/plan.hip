@@ -1098,3 +1098,142 @@ static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mc
   return MCEDM_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// VP-preconditioned Heun sampler of an epsilon network (PlCondDdim.sample_edm, models/ddim.py:1532-1601)
+// ------------------------------------------------------------------------------------------
+namespace mcedm {
+struct VpBufs { size_t x, xn, d, x32, D, condp, total; };
+static VpBufs vp_bufs(const mcedm_plan& P, int B, int H, int W) {
+  VpBufs v;
+  size_t cur = 0;
+  auto take = [&](size_t bytes) { size_t o = cur; cur += align_up(bytes, 256); return o; };
+  const size_t n = (size_t)B * P.desc.in_channels * H * W;
+  v.x = take(n * 8); v.xn = take(n * 8); v.d = take(n * 8); v.x32 = take(n * 4); v.D = take(n * 4);
+  v.condp = take((size_t)B * P.desc.cond_channels * H * W * 4);      // cond' = cat(cond, zeros) of a self-conditioning plan
+  v.total = cur;
+  return v;
+}
+
+// get_denoised (models/ddim.py:915-947) at one noise level: D = x + (-sigma) F(c_in cat(cond', x), c_noise)
+static int vp_denoise(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x32, const float* condp,
+                      double sigma_d, float c_noise, double w, float* D, void* ws, int B, int H, int W, hipStream_t s) {
+  int rc;
+  const float sigma = (float)sigma_d;                                   // t.to(torch.float32)
+  const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                // 1 / (sigma ** 2 + 1).sqrt(), fp32
+  Coef* coef_in = at<Coef>(ws, hd.coef_in);
+  float* label = at<float>(ws, hd.c_noise);
+  float* F = at<float>(ws, hd.F);
+  void* act = at<char>(ws, hd.total);
+  if ((rc = launch_vp_prepare(c_in, P.desc.cond_channels + P.desc.in_channels, c_noise, coef_in, label, s))) return rc;
+  if ((rc = forward_impl(P, L, pk, x32, nullptr, condp, coef_in, 0, label, 1, F, act, B, H, W, s))) return rc;
+  const float* Fu = nullptr;
+  if (std::fabs(w) >= 0.001 && condp != nullptr) {                     // :938-942, the second evaluation without cond
+    float* Fub = at<float>(ws, hd.Fu);
+    if ((rc = forward_impl(P, L, pk, x32, nullptr, nullptr, coef_in, 0, label, 1, Fub, act, B, H, W, s))) return rc;
+    Fu = Fub;
+  }
+  return launch_vp_cfg_finish(x32, F, Fu, w, sigma, (size_t)B * P.desc.out_channels * H * W, D, s);
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_vp_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "vp_sampler_workspace_bytes: null argument");
+  size_t u = 0;
+  int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, &u);
+  if (rc) return rc;
+  *bytes = vp_bufs(*plan, B, H, W).total + u;
+  return MCEDM_OK;
+}
+
+static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                          const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
+                          int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "vp_heun_sample: null argument");
+  MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "vp_heun_sample: null schedule array");
+  const mcedm_plan& P = *plan;
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "vp_heun_sample: in_channels != out_channels");
+  MCEDM_REQUIRE(P.desc.dx_mode == MCEDM_DX_NONE, "vp_heun_sample: dx_cond plans are not supported");
+  MCEDM_REQUIRE(sp->cond_channels >= 0 && sp->cond_channels <= P.desc.cond_channels,
+                "vp_heun_sample: cond_channels %d outside [0, %d]", sp->cond_channels, P.desc.cond_channels);
+  MCEDM_REQUIRE(cond == nullptr || sp->cond_channels > 0, "vp_heun_sample: cond given with cond_channels 0");
+  MCEDM_REQUIRE(sp->timesteps >= 1 && sp->timesteps <= 4096, "vp_heun_sample: timesteps=%d out of range", sp->timesteps);
+  const int N = sp->timesteps;
+  const double* t = sp->t_steps;
+  for (int i = 0; i < N; ++i) {
+    MCEDM_REQUIRE(sp->t_hat[i] >= t[i] && t[i] > 0.0, "vp_heun_sample: step %d: t_hat %g < t_cur %g or t_cur <= 0", i, sp->t_hat[i], t[i]);
+    MCEDM_REQUIRE(sp->t_hat[i] == t[i] || step_noise != nullptr || rng_seed != nullptr,
+                  "vp_heun_sample: step %d churns (t_hat > t_cur) and needs step_noise (or mcedm_vp_heun_sample_rng)", i);
+  }
+  int rc;
+  Layout L;
+  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
+  const Header hd = header_for(P, B, H, W);
+  const VpBufs vb = vp_bufs(P, B, H, W);
+  if (vb.total + hd.total + L.total_bytes > workspace_bytes) {
+    set_error("vp_heun_sample: workspace too small (%zu < %zu bytes)", workspace_bytes, vb.total + hd.total + L.total_bytes);
+    return MCEDM_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  double* x = at<double>(workspace, vb.x);
+  double* xn = at<double>(workspace, vb.xn);
+  double* dcur = at<double>(workspace, vb.d);
+  float* x32 = at<float>(workspace, vb.x32);
+  float* D = at<float>(workspace, vb.D);
+  void* uws = at<char>(workspace, vb.total);
+  const int C = P.desc.in_channels;
+  const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
+  const int Tout = return_last ? 1 : N + 1;
+  // cond' once per call: cond in its channels, zeros in the self-conditioning ones (get_self_cond_edm returns None)
+  const float* condp = cond;
+  if (cond && sp->cond_channels < P.desc.cond_channels) {
+    float* st = at<float>(workspace, vb.condp);
+    if ((rc = mcedm_eps_self_cond(nullptr, nullptr, nullptr, nullptr, nullptr, 0, cond, sp->cond_channels,
+                                  P.desc.cond_channels - sp->cond_channels, B, H, W, st, stream))) return rc;
+    condp = st;
+  }
+  // x = u_noise.to(float64) * t_steps[0]   (:1556)
+  if ((rc = launch_heun_init(nullptr, 0, C, hw, nullptr, init_noise, t[0], total, x, x32, s))) return rc;
+  if (!return_last && (rc = launch_heun_store(x, C, hw, 0, Tout, total, out, s))) return rc;
+  for (int i = 0; i < N; ++i) {
+    const double t_cur = t[i], t_next = t[i + 1], t_hat = sp->t_hat[i];
+    if (t_hat != t_cur) {                 // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) * S_noise * eps (:1567); + 0 * eps otherwise
+      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
+      if (step_noise) rc = launch_heun_churn(x, step_noise + (size_t)i * total, nullptr, c, total, x32, s);
+      else rc = launch_heun_churn_rng(x, reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, c, total, x32, s);
+      if (rc) return rc;
+    }
+    // Euler step (:1570-1580)
+    if ((rc = vp_denoise(P, L, hd, pk, x32, condp, t_hat, sp->c_noise[2 * i], sp->w, D, uws, B, H, W, s))) return rc;
+    if ((rc = launch_heun_euler(x, D, nullptr, t_hat, t_next - t_hat, total, dcur, xn, x32, s))) return rc;
+    // 2nd-order correction (:1583-1593)
+    if (i < N - 1) {
+      if ((rc = vp_denoise(P, L, hd, pk, x32, condp, t_next, sp->c_noise[2 * i + 1], sp->w, D, uws, B, H, W, s))) return rc;
+      if ((rc = launch_heun_correct(x, dcur, D, nullptr, t_next, t_next - t_hat, total, xn, x32, s))) return rc;
+    }
+    std::swap(x, xn);
+    if (!return_last && (rc = launch_heun_store(x, C, hw, i + 1, Tout, total, out, s))) return rc;
+  }
+  if (return_last && (rc = launch_heun_store(x, C, hw, 0, 1, total, out, s))) return rc;
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                                    const float* init_noise, const double* step_noise, double* out, int return_last,
+                                    void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return vp_sample_impl(plan, packed, sp, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B, H,
+                        W, stream);
+}
+
+extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                        const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
+                                        int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                        void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return vp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, H,
+                        W, stream);
+}

@@ -14,6 +14,9 @@ the loss and of the Heun sampler (``mask = NULL`` in the C ABI).  Constructor, a
 DDPM-schedule buffers ``betas`` / ``logvar`` that ``PlDdim.__init__`` registers, models/ddim.py:22-30) and method
 signatures follow the reference (incl. PDE guidance, ``dx_cond``, the ``node_type`` channel and the ``cond_p`` drop); DDIM
 sampling of the single-task model and self-conditioning are outside the hot path and raise.
+
+``PlCondDdim`` (bottom of this file) for ``models/ddim.py:1053-1605``: the single-task conditional DDPM on the ADM U-Net with
+self-conditioning -- epsilon-prediction ``training_step`` and the VP-preconditioned ``sample_edm`` in the HIP library.
 """
 from __future__ import annotations
 
@@ -759,3 +762,269 @@ class PlDdim(_EvalMetrics, _Base):
     def training_step(self, *a, **k):
         raise NotImplementedError("DDPM (epsilon-prediction) training is not built: SURVEY.md section 8 f1 covers EDM sampling "
                                   "of a trained DDPM checkpoint")
+
+
+class _EpsTrainLoss(torch.autograd.Function):
+    """NoiseEstimationLoss of PlCondDdim.training_step (models/ddim.py:1118-1152, models/losses.py:39-59):
+    loss = mean_b sum_chw (F - noise)^2 with F = model(x_noise, t.float(), cond').  Forward and backward run in the HIP library
+    (mcedm_unet_forward, mcedm_eps_loss, mcedm_unet_backward); modelled on mcedm._EdmTrainLoss."""
+
+    @staticmethod
+    def forward(ctx, module, x_noise, labels, cond, noise, *params):
+        net: DhariwalUNet = module.model
+        plan, packed = net.plan, net.packed_weights()
+        F = plan.forward(packed, x_noise, labels, cond=cond, ws=module._train_ws, training=True)
+        loss, dF = _lib.eps_loss(F, noise, want_grad=True)
+        module._train_generation += 1
+        ctx.module, ctx.saved, ctx.generation = module, (x_noise, labels, cond, dF), module._train_generation
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        module = ctx.module
+        net: DhariwalUNet = module.model
+        if ctx.generation != module._train_generation:
+            raise RuntimeError("training_step: another training forward overwrote this one's activations before its "
+                               "backward ran (one outstanding forward per module; run backward before the next forward)")
+        x_noise, labels, cond, dF = ctx.saved
+        params = list(net.parameters())
+        grads = module._grad_views(params)
+        net.plan.unet_backward(net.packed_weights(), net.named_param_dict(), x_noise, labels, cond, dF, grads, ws=module._train_ws)
+        flat = module._grad_buf * g.to(torch.float32)
+        out, off = [], 0
+        for p in params:
+            out.append(flat[off:off + p.numel()].view(p.shape))
+            off += p.numel()
+        return (None, None, None, None, None) + tuple(out)
+
+
+class PlCondDdim(_EvalMetrics, _Base):
+    """models/ddim.py:1053-1605: the single-task conditional DDPM (epsilon prediction) on the ADM U-Net
+    (configs/model/adm_cond_h_res32.yaml: ``name: adm_cond_h``, ``self_cond: True``, ``cond_p: 1.``), trained with the noise
+    estimation loss and sampled with the EDM Heun sampler around VP preconditioning (``get_denoised``, :915-947).
+
+    Constructor, buffers (``betas``, ``logvar``), state_dict keys and method signatures follow the reference.  The training
+    step runs in the HIP library: noising (mcedm_eps_noise_inputs), the self-conditioning pre-pass and its estimate written into
+    the network's widened conditioning input (mcedm_eps_self_cond), forward, loss (mcedm_eps_loss) and backward from dF
+    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample.  The DDPM U-Net (``name: ddim*``), the PDE loss term,
+    ``guide_dx``, ``dx_cond`` and the DDIM ``sample`` loop raise."""
+
+    def __init__(self, hparams):
+        super().__init__()
+        self.save_hyperparameters()
+        m, o, d, df = hparams.model, hparams.optimization, hparams.data, hparams.diffusion
+        if not str(hparams.name).startswith("adm"):
+            raise NotImplementedError("PlCondDdim with the DDPM U-Net (models/ddim.py:43-46, Model) has no backward here; only "
+                                      "the ADM U-Net (hparams.name = 'adm*') trains")
+        if _opt(m, "dx_cond", False):
+            raise NotImplementedError("dx_cond (models/ddim.py:33-35, 199-204) is not built for PlCondDdim")
+        if _opt(o, "pde_loss_lambda", 0.0):
+            raise NotImplementedError("pde_loss_lambda > 0 (models/ddim.py:1144-1150) is not built")
+        self.dx_norm, self.dx_detach, self.dx_cond = _opt(m, "dx_norm", "l2"), _opt(m, "dx_detach", False), False
+        self.node_type = bool(_opt(m, "node_type", False))
+        if self.node_type:
+            m.cond_channels = m.cond_channels + 1
+        betas = _beta_schedule(df.beta_schedule, df.beta_start, df.beta_end, df.num_diffusion_timesteps)
+        acp = (1.0 - betas).cumprod(dim=0)
+        post_var = betas * (1.0 - torch.cat([torch.ones(1), acp[:-1]])) / (1.0 - acp)
+        self.model_var_type = m.var_type
+        self.register_buffer("betas", betas)
+        self.num_timesteps = betas.shape[0]
+        if m.var_type == "fixedlarge":
+            self.register_buffer("logvar", betas.log())
+        elif m.var_type == "fixedsmall":
+            self.register_buffer("logvar", post_var.clamp(min=1e-20).log())
+        self.model = DhariwalUNet(hparams)
+        self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
+        self.cond_p = m.cond_p if hasattr(m, "cond_p") else 0.8                       # models/ddim.py:1058
+        self.normalization, self.rescaled = d.normalization, d.rescaled
+        self.uniform_dequantization, self.gaussian_dequantization = d.uniform_dequantization, d.gaussian_dequantization
+        self.normalizer_input = Normalizer((m.in_channels,) if m.in_channels > 1 else ())
+        self.normalizer_target = Normalizer((m.out_ch,) if m.out_ch > 1 else ())
+        self.optimizer, self.lr, self.weight_decay = o.optimizer, o.lr, o.weight_decay
+        self.beta1, self.amsgrad, self.eps = o.beta1, o.amsgrad, o.eps
+        self.factor, self.step_size, self.loss = _opt(o, "factor", 0.3), _opt(o, "step_size", 50), _opt(o, "loss", "l2")
+        self.pde_loss_lambda = 0.0
+        from .pde_loss import get_pde_loss_function
+        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system="swe", flip_xy=False)    # models/ddim.py:76-78
+        self.sparams = hparams.sampler if hparams.get("sampler", None) is not None else \
+            DotDict(type="ddim", timesteps=50, skip_type="uniform", eta=0.0, n_samples=1, n_repeat=5, n_time_h=128, n_time_u=0)
+        self.test_sparams = self.sparams
+        self.edm_steps = None
+        self.sigma_min = self.sigma_max = None
+        self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
+        self._train_ws, self._grad_buf, self._train_generation = _lib.Workspace(), None, 0
+        self._sample_ws = _lib.Workspace()
+        self._tables = None
+        self._stage = None
+
+    # ---- shared with PlCondEdm: identical in the reference (PlCondEdm inherits them from PlCondDdim) -----------------
+    setup = PlCondEdm.setup
+    set_pde_loss_function = PlCondEdm.set_pde_loss_function
+    inverse_data_transform_u = PlCondEdm.inverse_data_transform_u
+    get_cond_in = PlCondEdm.get_cond_in
+    get_pde_loss = PlCondEdm.get_pde_loss
+    validation_step = PlCondEdm.validation_step
+    test_step = PlCondEdm.test_step
+    _net = PlCondEdm._net
+    _grad_views = PlCondEdm._grad_views
+
+    # ---- optimiser: the fused clip + Adam + EMA seam of PlMcedm (m-cedm_amd/optim.py) -----------------------------
+    from .mcedm import PlMcedm as _PlMcedm
+    configure_optimizers = _PlMcedm.configure_optimizers
+    configure_gradient_clipping = _PlMcedm.configure_gradient_clipping
+    del _PlMcedm
+
+    def optimizer_step(self, *args, **kwargs):
+        """models/ddim.py:228-233: Lightning's step, then EmaModel.update (already done by the fused optimiser's kernel)."""
+        super().optimizer_step(*args, **kwargs)
+        if self.ema_model is not None and getattr(self, "_fused_opt", None) is None:
+            self.ema_model.update(self.model)
+
+    # ---- schedule (host side, the reference's own expressions) ------------------------------------------------------
+    set_test_sampler_params = PlDdim.set_test_sampler_params
+    get_edm_steps = PlDdim.get_edm_steps
+    round_sigma = PlDdim.round_sigma
+
+    def _noise_tables(self, device):
+        """sqrt(a) and sqrt(1 - a), a = (1 - betas).cumprod(0), on the module's device (models/ddim.py:195-197)."""
+        if self._tables is None or self._tables[0].device != torch.device(device):
+            a = (1 - self.betas.to(device)).cumprod(dim=0)
+            self._tables = (a.sqrt().contiguous(), (1.0 - a).sqrt().contiguous())
+        return self._tables
+
+    # ---- epsilon-prediction forward (models/ddim.py:195-226) --------------------------------------------------------------
+    def _noised_inputs(self, x, t, noise, cond, ws):
+        """x_noise, labels and the network's conditioning input of one forward, consuming torch's generator as the reference
+        does: the cond_p draw (:202), then the self-conditioning draw (:205) whose pre-pass runs in `ws` before anything
+        else uses it."""
+        net = self.model
+        x = x.to(torch.float32).contiguous()
+        noise = noise.to(torch.float32).contiguous()
+        t = torch.as_tensor(t).to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+        sa, sb = self._noise_tables(x.device)
+        x_noise, labels = _lib.eps_noise_inputs(x, noise, t, sa, sb)
+        if torch.rand(1) >= self.cond_p:
+            cond = None                                    # the conditioning switched off for this batch
+        cond = None if cond is None else cond.to(torch.float32).contiguous()
+        if not net.self_condition:
+            return x_noise, labels, cond, t
+        B, _, H, W = x.shape
+        shape = (B, net.plan_cond_channels, H, W)
+        if self._stage is None or tuple(self._stage.shape) != shape or self._stage.device != x.device:
+            self._stage = torch.empty(shape, dtype=torch.float32, device=x.device)
+        stage = self._stage
+        if torch.rand(1) < 0.5:                            # no-grad pre-pass: F0 = model(x_noise, t, cond)
+            pk = net.packed_weights()
+            pre_cond = _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels) if cond is not None else None
+            F0 = net.plan.forward(pk, x_noise, labels, cond=pre_cond, ws=ws)
+            _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels, x_noise=x_noise, F0=F0, t=t, sqrt_ab=sa,
+                               sqrt_1mab=sb)
+            return x_noise, labels, stage, t
+        if cond is None:
+            return x_noise, labels, None, t
+        return x_noise, labels, _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels), t
+
+    def forward(self, x, t, noise, cond=None):
+        """models/ddim.py:195-226 without gradients: (output, x0_t)."""
+        net = self.model
+        with torch.no_grad():
+            x_noise, labels, condp, t = self._noised_inputs(x, t, noise, cond, net._ws)
+            output = net.plan.forward(net.packed_weights(), x_noise, labels, cond=condp, ws=net._ws)
+            sa, sb = self._noise_tables(x.device)
+            x0_t = torch.empty_like(output)
+            _lib.eps_self_cond(x0_t, None, 0, output.shape[1], x_noise=x_noise, F0=output, t=t, sqrt_ab=sa, sqrt_1mab=sb)
+        return output, x0_t
+
+    def training_step(self, train_batch, batch_idx):
+        h_unnorm, dx, dt, u_unnorm = train_batch
+        self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
+        x = self.data_transform(h_unnorm, u_unnorm)
+        n = x.size(0)
+        h, u = x[..., 0:h_ch], x[..., h_ch:h_ch + u_ch]
+        cond_in = _nchw(self.get_cond_in(h, u, dx, dt)).float()
+        u = _nchw(u).float()
+        noise = torch.randn_like(u)
+        t = torch.randint(low=0, high=self.num_timesteps, size=(n // 2 + 1,))       # antithetic sampling (:1134-1137)
+        t = t.to(x.device).long()
+        t = torch.cat([t, self.num_timesteps - t - 1], dim=0)[:n]
+        x_noise, labels, condp, _ = self._noised_inputs(u, t, noise, cond_in, self._train_ws)
+        loss = _EpsTrainLoss.apply(self, x_noise, labels, condp, noise.contiguous(), *self.model.parameters())
+        self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
+        return loss
+
+    # ---- sampling (models/ddim.py:915-957, 1532-1605) ---------------------------------------------------------------------
+    def get_self_cond_edm(self, denoised):
+        return None                                        # :1603-1605
+
+    def _c_noise(self, sigma):
+        return float(self.num_timesteps - 1 - self.round_sigma(torch.tensor([float(sigma)], dtype=torch.float32),
+                                                               return_index=True).to(torch.float32)[0])
+
+    def get_denoised(self, model, xt, t, cond=None, x_self_cond=None, dx=None, w=None):
+        """models/ddim.py:915-947 at one noise level (the sampler's case): one VP-preconditioned Heun step's denoiser call,
+        run as a single-step mcedm_vp_heun_sample would; here through the network directly: D = x - sigma F(c_in x, c_noise,
+        c_in cond)."""
+        if dx is not None:
+            raise NotImplementedError("dx_cond is not built for PlCondDdim (models/ddim.py:933-934)")
+        if self.edm_steps is None:
+            raise RuntimeError("call set_test_sampler_params(params) with params.type == 'edm' first (models/ddim.py:122-129)")
+        net = self._net(model)
+        sig = torch.as_tensor(t).reshape(-1)
+        if sig.numel() != 1:
+            raise NotImplementedError("one noise level for the whole batch (what sample_edm evaluates)")
+        s32 = float(sig.to(torch.float32)[0])
+        c_in = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(s32 * s32 + 1.0, dtype=torch.float32).sqrt()
+        c_in_dev = c_in.reshape(1).to(xt.device)
+        labels = torch.full((1,), self._c_noise(s32), dtype=torch.float32, device=xt.device)
+        xt = xt.to(torch.float32).contiguous()
+        B, _, H, W = xt.shape
+        with torch.no_grad():
+            pk = net.packed_weights()
+
+            def evaluate(c, sc):
+                # the conv_in rows scale every input channel by c_in: x, cond and x_self_cond (:921-935)
+                cp = net.stage_self_cond(None if c is None else (c_in_dev * c).contiguous(),
+                                         None if sc is None else (c_in_dev * sc).contiguous(), xt) \
+                    if net.self_condition else (None if c is None else (c_in_dev * c).contiguous())
+                return net.plan.forward(pk, (c_in_dev * xt).contiguous(), labels, cond=cp, ws=net._ws)
+            c32 = None if cond is None else cond.to(torch.float32)
+            F = evaluate(c32, x_self_cond)
+            if not (w is None or abs(w) < 0.001 or cond is None):
+                F = (w + 1) * F - w * evaluate(None, x_self_cond)
+            D = xt + (-c_in.new_tensor(s32).to(xt.device)) * F
+        return D, F
+
+    def sample_edm(self, h, u_noise, sparams, return_last=True, guide_dx=False):
+        """models/ddim.py:1532-1601; h, u_noise in the reference's 'b h w c' layout; returns [b, t, h, w, c] float64.  The
+        schedule is rounded on the host (round_sigma, :1553, 1566); the loop runs in mcedm_vp_heun_sample with the per-step
+        randn_like(x_cur) of :1567 drawn up front as one [N, B, C, H, W] float64 tensor."""
+        if guide_dx:
+            raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1577-1579) is not built for PlCondDdim")
+        if self.edm_steps is None:
+            self.set_test_sampler_params(sparams)
+        net = self._net(self.ema_model if self.ema_model is not None else self.model)
+        h, init = _nchw(h).float().contiguous(), _nchw(u_noise).float().contiguous()
+        smin = max(float(sparams.sigma_min), self.sigma_min)
+        smax = min(float(sparams.sigma_max), self.sigma_max)
+        N, rho = int(sparams.timesteps), float(sparams.rho)
+        idx = torch.arange(N, dtype=torch.float64)
+        t_steps = (smax ** (1 / rho) + idx / (N - 1) * (smin ** (1 / rho) - smax ** (1 / rho))) ** rho
+        t_steps = torch.cat([self.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
+        S_min, S_max = float(sparams.S_min), float(sparams.S_max)
+        t_hat, c_noise = [], []
+        for i in range(N):
+            t_cur = t_steps[i]
+            gamma = min(float(sparams.S_churn) / N, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
+            th = self.round_sigma(t_cur + gamma * t_cur)
+            t_hat.append(float(th))
+            c_noise += [self._c_noise(float(th)), self._c_noise(float(t_steps[i + 1])) if i < N - 1 else 0.0]
+        vd = _lib.vp_sampler_desc(N, net.cond_channels, t_steps.tolist(), t_hat, c_noise, float(sparams.S_noise), float(sparams.w))
+        step_noise = torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device)
+        with torch.no_grad():
+            return net.plan.vp_sample(net.packed_weights(), vd, h if net.cond_channels > 0 else None, init, step_noise,
+                                      return_last=return_last, ws=self._sample_ws)
+
+    def sample(self, *a, **k):
+        raise NotImplementedError("the DDIM sampling loop of PlCondDdim (models/ddim.py:1452-1531) is not built; "
+                                  "set the sampler type to 'edm' (sample_edm)")

@@ -32,6 +32,8 @@ EXPORTS = [
     "mcedm_ddim_repaint_sample", "mcedm_ddim_timesteps",
     "mcedm_unet_forward_dx", "mcedm_edm_denoise_dx", "mcedm_edm_denoise_backward_dx", "mcedm_heun_sample_dxcond",
     "mcedm_unet_plan_set_variant", "mcedm_ddpm_plan_set_variant", "mcedm_heun_sample_rng",
+    "mcedm_eps_noise_inputs", "mcedm_eps_self_cond", "mcedm_eps_loss", "mcedm_unet_backward", "mcedm_unet_backward_bucketed",
+    "mcedm_vp_sampler_workspace_bytes", "mcedm_vp_heun_sample", "mcedm_vp_heun_sample_rng",
 ]
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
@@ -82,6 +84,12 @@ class DdimDesc(C.Structure):
     _fields_ = [("timesteps", C.c_int32), ("skip_type", C.c_int32), ("eta", C.c_double), ("n_repeat", C.c_int32),
                 ("n_time_h", C.c_int32), ("n_time_u", C.c_int32), ("h_ch", C.c_int32), ("u_ch", C.c_int32),
                 ("num_diffusion_timesteps", C.c_int32), ("self_cond", C.c_int32), ("alphas_cumprod_ext", C.POINTER(C.c_float))]
+
+
+class VpSamplerDesc(C.Structure):
+    """mcedm_vp_sampler_desc: the host arrays are kept alive by the Python object that built the struct (vp_sampler_desc)."""
+    _fields_ = [("timesteps", C.c_int32), ("cond_channels", C.c_int32), ("t_steps", C.POINTER(C.c_double)),
+                ("t_hat", C.POINTER(C.c_double)), ("c_noise", C.POINTER(C.c_float)), ("S_noise", C.c_double), ("w", C.c_double)]
 
 
 _lib = None
@@ -170,6 +178,18 @@ def load() -> C.CDLL:
     lib.mcedm_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
     lib.mcedm_ddim_repaint_sample.argtypes = [vp, vp, C.POINTER(DdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
     lib.mcedm_ddim_timesteps.argtypes = [i32, i32, i32, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
+    lib.mcedm_eps_noise_inputs.argtypes = [f32p, f32p, vp, f32p, f32p, i32, i32, i32, i32, i32, f32p, f32p, vp]
+    lib.mcedm_eps_self_cond.argtypes = [f32p, f32p, vp, f32p, f32p, i32, f32p, i32, i32, i32, i32, i32, f32p, vp]
+    lib.mcedm_eps_loss.argtypes = [f32p, f32p, i32, i32, i32, i32, f32p, f32p, vp, sz, vp]
+    lib.mcedm_unet_backward.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, f32p, f32p, i32, f32p, C.POINTER(vp), vp, sz, i32,
+                                        i32, i32, vp]
+    lib.mcedm_unet_backward_bucketed.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, f32p, f32p, i32, f32p, C.POINTER(vp), vp,
+                                                 sz, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(vp), vp]
+    lib.mcedm_vp_sampler_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.mcedm_vp_heun_sample.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, f64p, f64p, i32, vp, sz, i32, i32, i32,
+                                         vp]
+    lib.mcedm_vp_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, i32,
+                                             i32, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)          # AttributeError here == header/library drift
         if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
@@ -379,6 +399,54 @@ class Plan:
                                                       sigma.numel(), _ptr(cond), _ptr(dD), garr, buf.data_ptr(),
                                                       buf.numel(), B, H, W, float(sigma_data), nb, firsts, evs,
                                                       _stream()), "edm_denoise_backward_dx")
+
+    def unet_backward(self, packed, params: Dict[str, torch.Tensor], x, noise_labels, cond, dF, grads: Sequence[torch.Tensor],
+                      ws: Workspace, bucket_first: Optional[Sequence[int]] = None,
+                      bucket_events: Optional[Sequence[torch.cuda.Event]] = None) -> None:
+        """Backward of forward(..., training=True) (x_scale None) on the SAME workspace, from dF = dLoss/d out:
+        grads[i] <- dLoss/dparam_i (overwritten); bucket events as in denoise_backward."""
+        B, _, H, W = x.shape
+        buf = ws.get(self.workspace_bytes(B, H, W, True), x.device)
+        parr = (C.c_void_p * len(self.param_names))(*[_ptr(params[n].detach()) for n in self.param_names])
+        garr = (C.c_void_p * len(self.param_names))(*[_ptr(g) for g in grads])
+        nb, firsts, evs = 0, None, None
+        if bucket_first is not None:
+            nb = len(bucket_first)
+            firsts = (C.c_int32 * nb)(*[int(f) for f in bucket_first])
+            handles = [int(e.cuda_event) for e in bucket_events]
+            if len(handles) != nb or not all(handles):
+                raise RuntimeError("unet_backward: one created (recorded at least once) torch.cuda.Event per bucket is needed")
+            evs = (C.c_void_p * nb)(*handles)
+        check(self._lib.mcedm_unet_backward_bucketed(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(cond), None,
+                                                     _ptr(noise_labels), noise_labels.numel(), _ptr(dF), garr, buf.data_ptr(),
+                                                     buf.numel(), B, H, W, nb, firsts, evs, _stream()), "unet_backward")
+
+    def vp_sampler_workspace_bytes(self, B: int, H: int, W: int) -> int:
+        sz = C.c_size_t()
+        check(self._lib.mcedm_vp_sampler_workspace_bytes(self._h, B, H, W, C.byref(sz)), "vp_sampler_workspace_bytes")
+        return sz.value
+
+    def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
+                  ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcedm_vp_heun_sample (rng_seed None) / mcedm_vp_heun_sample_rng; returns [B, 1 or N+1, H, W, in] float64."""
+        B, _, H, W = init_noise.shape
+        ws = ws or Workspace()
+        buf = ws.get(self.vp_sampler_workspace_bytes(B, H, W), init_noise.device)
+        T = 1 if return_last else vd.timesteps + 1
+        out = torch.empty((B, T, H, W, self.in_channels), dtype=torch.float64, device=init_noise.device)
+        if rng_seed is not None:
+            if step_noise is not None:
+                raise RuntimeError("vp_sample: give step_noise or rng_seed, not both")
+            if rng_seed.dtype != torch.int64 or rng_seed.numel() != 1 or rng_seed.device != init_noise.device:
+                raise RuntimeError("vp_sample: rng_seed must be a one-element int64 tensor on the sampler's device")
+            check(self._lib.mcedm_vp_heun_sample_rng(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
+                                                     rng_seed.data_ptr(), _ptr(out, torch.float64), int(return_last),
+                                                     buf.data_ptr(), buf.numel(), B, H, W, _stream()), "vp_heun_sample_rng")
+            return out
+        check(self._lib.mcedm_vp_heun_sample(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
+                                             _ptr(step_noise, torch.float64), _ptr(out, torch.float64), int(return_last),
+                                             buf.data_ptr(), buf.numel(), B, H, W, _stream()), "vp_heun_sample")
+        return out
 
     def sample(self, packed, sd: SamplerDesc, cond, mask, init_noise, step_noise=None, return_last: bool = True,
                ws: Optional[Workspace] = None, out: Optional[torch.Tensor] = None,
@@ -773,6 +841,50 @@ def edm_noise_inputs(x, mask, noise, rnd_normal, P_mean=-1.2, P_std=1.2):
     check(load().mcedm_edm_noise_inputs(_ptr(x), _ptr(mask), _ptr(noise), _ptr(rnd_normal), B, Cc, H, W, P_mean, P_std,
                                         _ptr(x_noise), _ptr(sigma), _stream()), "edm_noise_inputs")
     return x_noise, sigma
+
+
+def eps_noise_inputs(x, noise, t, sqrt_ab, sqrt_1mab):
+    """x_noise = x sqrt(a_t) + noise sqrt(1 - a_t) and the labels t.float() (mcedm_eps_noise_inputs); t int64 on the device."""
+    B, Cc, H, W = x.shape
+    if t.dtype != torch.int64 or t.numel() != B or not t.is_contiguous():
+        raise RuntimeError("eps_noise_inputs: t must be a contiguous int64 tensor of B timesteps")
+    n = sqrt_ab.numel()
+    if int(t.min()) < 0 or int(t.max()) >= n:
+        raise RuntimeError(f"eps_noise_inputs: timesteps outside [0, {n})")
+    x_noise = torch.empty_like(x)
+    labels = torch.empty(B, dtype=torch.float32, device=x.device)
+    check(load().mcedm_eps_noise_inputs(_ptr(x), _ptr(noise), _ptr(t, torch.int64), _ptr(sqrt_ab), _ptr(sqrt_1mab), n, B, Cc, H,
+                                        W, _ptr(x_noise), _ptr(labels), _stream()), "eps_noise_inputs")
+    return x_noise, labels
+
+
+def eps_self_cond(out, cond, cond_channels, in_channels, x_noise=None, F0=None, t=None, sqrt_ab=None, sqrt_1mab=None):
+    """out [B, cond_channels + in_channels, H, W] <- cat(cond or 0, x_sc or 0) (mcedm_eps_self_cond)."""
+    B, _, H, W = out.shape
+    n = 0 if sqrt_ab is None else sqrt_ab.numel()
+    check(load().mcedm_eps_self_cond(_ptr(x_noise), _ptr(F0), _ptr(t, torch.int64), _ptr(sqrt_ab), _ptr(sqrt_1mab), n, _ptr(cond),
+                                     cond_channels, in_channels, B, H, W, _ptr(out), _stream()), "eps_self_cond")
+    return out
+
+
+def eps_loss(F, eps, want_grad=True, scratch: Optional[torch.Tensor] = None):
+    B, Cc, H, W = F.shape
+    loss = torch.empty(1, dtype=torch.float32, device=F.device)
+    dF = torch.empty_like(F) if want_grad else None
+    scratch = reduce_scratch(F.device) if scratch is None else scratch
+    check(load().mcedm_eps_loss(_ptr(F), _ptr(eps), B, Cc, H, W, _ptr(loss), _ptr(dF), scratch.data_ptr(),
+                                scratch.numel() * scratch.element_size(), _stream()), "eps_loss")
+    return loss, dF
+
+
+def vp_sampler_desc(timesteps, cond_channels, t_steps, t_hat, c_noise, S_noise, w) -> VpSamplerDesc:
+    """The struct with its host arrays attached (they must outlive every call that reads it)."""
+    ts = (C.c_double * (timesteps + 1))(*[float(v) for v in t_steps])
+    th = (C.c_double * timesteps)(*[float(v) for v in t_hat])
+    cn = (C.c_float * (2 * timesteps))(*[float(v) for v in c_noise])
+    d = VpSamplerDesc(int(timesteps), int(cond_channels), ts, th, cn, float(S_noise), float(w))
+    d._keep = (ts, th, cn)
+    return d
 
 
 _RED_SCRATCH = {}

@@ -145,6 +145,8 @@ class PlMcedm(_Base):
         if not str(hparams.name).startswith("adm"):
             raise NotImplementedError("only the ADM/EDM U-Net (hparams.name = 'adm*') is on the hot path")
         self.dx_cond = False
+        if getattr(m, "self_cond", False) if hasattr(m, "self_cond") else False:
+            raise NotImplementedError("hparams.model.self_cond=True is outside the MI355X hot path for PlMcedm")
         # models/mcedm.py:25-34: the two optional widenings of the conditioning input.  Like the reference, the constructor
         # rewrites hparams.model.cond_channels before the network is built (the C ABI takes any cond_channels).
         self.add_cond_mask = bool(m.add_cond_mask) if hasattr(m, "add_cond_mask") else False
