@@ -1,6 +1,9 @@
-"""Drop-ins for the reference's ``models/ddim.py``:
+"""Drop-ins for the reference's ``models/ddim.py``.  What they share with each other and with ``PlMcedm`` lives in
+``m-cedm_amd/pl_base.py`` (``_PlBase``); this file adds ``_SingleTask`` (conditioning input and evaluation loops of the two
+single-task models) and the mixin ``_DdpmSchedule`` (the DDPM schedule as EDM sigmas), like the reference's hierarchy
+PlDdim -> PlCondDdim -> PlCondEdm.
 
-``PlDdim`` (bottom of this file): the joint DDPM baseline sampled with the EDM Heun sampler and
+``PlDdim``: the joint DDPM baseline sampled with the EDM Heun sampler and
 RePaint-style resampling -- ``sample_edm`` (models/ddim.py:959-1051), ``get_denoised`` (:915-947), ``round_sigma``
 (:949-957), ``compute_alpha`` (:700-704) on the DDPM U-Net of ``m-cedm_amd/ddim_blocks.py``; the loop runs in
 ``mcedm_repaint_sample`` (csrc/ddpm.hip).
@@ -13,218 +16,29 @@ It runs on the same HIP path as ``PlMcedm``: the same ``DhariwalUNet`` (``in_cha
 the loss and of the Heun sampler (``mask = NULL`` in the C ABI).  Constructor, attributes, state_dict keys (incl. the
 DDPM-schedule buffers ``betas`` / ``logvar`` that ``PlDdim.__init__`` registers, models/ddim.py:22-30) and method
 signatures follow the reference (incl. PDE guidance, ``dx_cond``, the ``node_type`` channel and the ``cond_p`` drop); DDIM
-sampling of the single-task model and self-conditioning are outside the hot path and raise.
+sampling of the single-task model is outside the hot path and raises, and so does ``self_cond`` for ``PlCondEdm`` (its sampler
+would feed ``denoised`` back).
 
 ``PlCondDdim`` (bottom of this file) for ``models/ddim.py:1053-1605``: the single-task conditional DDPM on the ADM U-Net with
-self-conditioning -- epsilon-prediction ``training_step`` and the VP-preconditioned ``sample_edm`` in the HIP library.
+self-conditioning (which it runs) -- epsilon-prediction ``training_step`` and the VP-preconditioned ``sample_edm`` in the HIP
+library.
 """
 from __future__ import annotations
-
-import math
-import os
 
 import numpy as np
 import torch
 
 from . import lib as _lib
 from .adm_blocks import DhariwalUNet, EmaModel
-from .mcedm import DotDict, Normalizer, _Base, _EdmTrainLoss, _nchw
+from .mcedm import _edm_train_loss
+from .pl_base import DotDict, _PlBase, _TrainLoss, _nchw, _opt, correlation, l1, masked_l1
 
 
-def _opt(cfg, name, default):
-    """cfg.<name> if present (DictConfig, attribute dicts whose __getattr__ raises KeyError, plain objects)."""
-    try:
-        return getattr(cfg, name)
-    except (AttributeError, KeyError):
-        return default
+class _SingleTask(_PlBase):
+    """What the single-task models (h given, u generated) share -- in the reference PlCondEdm inherits it from PlCondDdim
+    (models/ddim.py:1053-1319): the conditioning input, the u-only inverse transform, the PDE residual of (h, u) and the
+    evaluation loops around ``sample_edm``."""
 
-
-def _beta_schedule(kind, beta_start, beta_end, n):
-    """models/ddim_blocks.py:473-505."""
-    if kind == "quad":
-        b = np.linspace(beta_start ** 0.5, beta_end ** 0.5, n, dtype=np.float64) ** 2
-    elif kind == "linear":
-        b = np.linspace(beta_start, beta_end, n, dtype=np.float64)
-    elif kind == "const":
-        b = beta_end * np.ones(n, dtype=np.float64)
-    elif kind == "jsd":
-        b = 1.0 / np.linspace(n, 1, n, dtype=np.float64)
-    elif kind == "sigmoid":
-        b = 1 / (np.exp(-np.linspace(-6, 6, n)) + 1) * (beta_end - beta_start) + beta_start
-    else:
-        raise NotImplementedError(kind)
-    return torch.from_numpy(b).float()
-
-def _l1(a, b):
-    """nn.L1Loss() (mean); an empty slice gives nan like the reference's own call does."""
-    return (a - b).abs().mean()
-
-
-def _masked_l1(pred, target, mask):
-    """MaskedLoss('l1'), models/losses.py:62-78."""
-    return (pred * mask - target * mask).abs().sum() / mask.sum()
-
-
-def _correlation(pred, target):
-    """CorrelationLoss(reduction='none'), models/losses.py:93-124: per-channel Pearson correlation over the grid, averaged
-    over the batch."""
-    p = pred.reshape(pred.shape[0], -1, pred.shape[-1])
-    t = target.reshape(target.shape[0], -1, target.shape[-1])
-    pc, tc = p - p.mean(dim=1, keepdim=True), t - t.mean(dim=1, keepdim=True)
-    den = ((pc * pc).sum(dim=1) * (tc * tc).sum(dim=1)).sqrt()
-    den = den + (den == 0) * 1e-7
-    return ((tc * pc).sum(dim=1) / den).mean(dim=0)
-
-
-class _EvalMetrics:
-    """Host-side bookkeeping both reference evaluation loops share (models/ddim.py:235-262, 652-698)."""
-
-    def data_transform(self, h, u):
-        x = torch.cat([self.normalizer_input(h), self.normalizer_target(u)], dim=-1)
-        if self.uniform_dequantization:
-            x = x / 256.0 * 255.0 + torch.rand_like(x) / 256.0
-        if self.gaussian_dequantization:
-            x = x + torch.randn_like(x) * 0.01
-        return 2 * x - 1.0 if self.rescaled else x
-
-    def inverse_data_transform(self, h, u):
-        if self.rescaled:
-            h, u = (h + 1.0) / 2.0, (u + 1.0) / 2.0
-        if self.normalization == "min_max":
-            h, u = torch.clamp(h, 0.0, 1.0), torch.clamp(u, 0.0, 1.0)
-        return self.normalizer_input(h, inverse=True), self.normalizer_target(u, inverse=True)
-
-    @staticmethod
-    def scale_each_min_max(state, return_min_max=False):
-        """Per (sample, channel) min-max scaling of a 'b h w c' field to [0, 1] (models/ddim.py:689-698)."""
-        b, hh, ww, c = state.shape
-        flat = state.permute(0, 3, 1, 2).reshape(b, c, hh * ww)
-        lo, hi = flat.min(dim=2, keepdim=True)[0], flat.max(dim=2, keepdim=True)[0]
-        scaled = ((flat - lo) / (hi - lo)).reshape(b, c, hh, ww).permute(0, 2, 3, 1)
-        return (scaled, lo, hi) if return_min_max else scaled
-
-    @staticmethod
-    def scale_back_min_max(state_scaled, state_min, state_max):
-        b, hh, ww, c = state_scaled.shape
-        flat = state_scaled.permute(0, 3, 1, 2).reshape(b, c, hh * ww) * (state_max - state_min) + state_min
-        return flat.reshape(b, c, hh, ww).permute(0, 2, 3, 1)
-
-    def recover_correct_scale(self, gt, xs_scaled_mean):
-        _, lo, hi = self.scale_each_min_max(gt, return_min_max=True)
-        return self.scale_back_min_max(xs_scaled_mean, lo, hi)
-
-    def get_best_by_pde_error(self, gt, xs_scaled, n_samples, use_gt=True):
-        """models/ddim.py:652-674: per input the sample (re-scaled to the ground truth's range) with the smallest mean PDE
-        residual; returns (indices [b, 1], the selected scaled samples [b, h, w, c])."""
-        gt_rep = gt.repeat(n_samples, 1, 1, 1)
-        _, lo, hi = self.scale_each_min_max(gt_rep, return_min_max=True)
-        xs_gt = self.scale_back_min_max(xs_scaled, lo, hi)
-        err = self.pde_loss(xs_gt, gt_rep if use_gt else xs_gt, self.normalizer_input, self.normalizer_target)
-        nb = err.shape[0] // n_samples
-        err = err.reshape(n_samples, nb, -1).permute(1, 0, 2).mean(dim=2)                 # '(n b) ... -> b n (...)'
-        indices = err.min(dim=1, keepdim=True)[1]
-        per_b = xs_scaled.reshape(n_samples, nb, *xs_scaled.shape[1:]).transpose(0, 1)    # b n h w c
-        return indices, per_b[torch.arange(nb, device=indices.device), indices[:, 0]]
-
-    def _log(self, name, value):
-        self.log(name, value, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
-
-
-class PlCondEdm(_EvalMetrics, _Base):
-    def __init__(self, hparams):
-        super().__init__()
-        self.save_hyperparameters()
-        m, o, d, df = hparams.model, hparams.optimization, hparams.data, hparams.diffusion
-        if hasattr(m, "self_cond") and m.self_cond:
-            raise NotImplementedError("hparams.model.self_cond=True is outside the MI355X hot path")
-        # models/ddim.py:36-38: a boundary / interior flag per grid point rides along as one more conditioning channel
-        self.node_type = bool(m.node_type) if hasattr(m, "node_type") else False
-        if self.node_type:
-            m.cond_channels = m.cond_channels + 1
-        # dx_cond (models/ddim.py:33-35): the network also sees the PDE-residual gradient at its input state.  For the
-        # single-task model only dx_norm == 'prob' can run in the reference -- get_dx_pde (:1424-1450) returns a 3-D tensor
-        # with calc_prob=False and get_dx_input (:601-639) fails to unpack it (pinned: tests/golden/dxcond.npz
-        # 'dx_norm_l2_raises') -- so the other normalisations raise here as well
-        self.dx_cond = bool(m.dx_cond) if hasattr(m, "dx_cond") else False
-        self.dx_norm = m.dx_norm if hasattr(m, "dx_norm") else "l2"
-        self.dx_detach = m.dx_detach if hasattr(m, "dx_detach") else False
-        if self.dx_cond and self.dx_norm != "prob":
-            raise NotImplementedError(f"dx_cond with dx_norm={self.dx_norm!r}: PlCondEdm.get_dx_input raises in the reference for "
-                                      "every dx_norm other than 'prob' (models/ddim.py:608-611, 1445-1448)")
-        if not str(hparams.name).startswith("adm"):
-            raise NotImplementedError("only the ADM/EDM U-Net (hparams.name = 'adm*') is on the hot path")
-        # DDPM schedule buffers of PlDdim (kept for checkpoint compatibility; the EDM path never reads them)
-        betas = _beta_schedule(df.beta_schedule, df.beta_start, df.beta_end, df.num_diffusion_timesteps)
-        acp = (1.0 - betas).cumprod(dim=0)
-        post_var = betas * (1.0 - torch.cat([torch.ones(1), acp[:-1]])) / (1.0 - acp)
-        self.model_var_type = m.var_type
-        self.register_buffer("betas", betas)
-        self.num_timesteps = betas.shape[0]
-        if m.var_type == "fixedlarge":
-            self.register_buffer("logvar", betas.log())
-        elif m.var_type == "fixedsmall":
-            self.register_buffer("logvar", post_var.clamp(min=1e-20).log())
-        self.cond_p = m.cond_p if hasattr(m, "cond_p") else 0.8
-        self.model = DhariwalUNet(hparams)
-        self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
-        self.normalization, self.rescaled = d.normalization, d.rescaled
-        self.uniform_dequantization, self.gaussian_dequantization = d.uniform_dequantization, d.gaussian_dequantization
-        self.normalizer_input = Normalizer((m.in_channels,) if m.in_channels > 1 else ())
-        self.normalizer_target = Normalizer((m.out_ch,) if m.out_ch > 1 else ())
-        self.optimizer, self.lr, self.weight_decay = o.optimizer, o.lr, o.weight_decay
-        self.beta1, self.amsgrad, self.eps = o.beta1, o.amsgrad, o.eps
-        if hasattr(o, "pde_loss_lambda") and o.pde_loss_lambda:
-            raise NotImplementedError("pde_loss_lambda != 0 is outside the hot path")
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system="swe", flip_xy=False)    # models/ddim.py:76-78
-        self.P_mean, self.P_std, self.sigma_data = -1.2, 1.2, 1.0
-        self.sigma_min, self.sigma_max = 0.002, 80
-        self.sparams = hparams.sampler if hparams.get("sampler", None) is not None else self.get_edm_sampler_params()
-        self.test_sparams = self.sparams
-        # a default until the first batch sets the widths (the reference has none: models/ddim.py:1120-1121 are its first
-        # assignments); the node_type channel added above is not part of the known state
-        self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
-        self._train_ws, self._sample_ws, self._grad_buf = _lib.Workspace(), _lib.Workspace(), None
-        self._train_generation = 0
-        self._graphs = {}
-
-    # ---- configuration ----------------------------------------------------------------------------------
-    @staticmethod
-    def get_edm_sampler_params():
-        return DotDict(name="edm", type="edm", timesteps=50, sigma_min=0.002, sigma_max=80, rho=7, S_churn=15.0, S_min=0,
-                       S_max="inf", S_noise=1, n_samples=5, n_repeat=2, n_time_h=128, n_time_u=0, return_last=True,
-                       select_by_pde=False, use_gt_pde_select=True, guide_dx=False, w=0.0, plot_scaled=False)
-
-    def set_test_sampler_params(self, params):
-        if params.type != "edm":
-            print("Model with EDM preconditioning supports only EDM sampler ")
-            params = self.get_edm_sampler_params()
-        self.test_sparams = params
-
-    def set_pde_loss_function(self, system, flip_xy):
-        """models/ddim.py:97-101; the residuals and their guidance gradients run on the device (m-cedm_amd/pde_loss.py)."""
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system, flip_xy)
-
-    def setup(self, stage: str = None) -> None:
-        if stage == "fit":
-            st = self.trainer.datamodule.get_norm_stats()
-            key = ("min", "min_max") if self.normalization == "min_max" else ("mean", "std")
-            self.normalizer_input.set_stats(st[f"input_{key[0]}"], st[f"input_{key[1]}"])
-            self.normalizer_target.set_stats(st[f"target_{key[0]}"], st[f"target_{key[1]}"])
-
-    def configure_optimizers(self):
-        if self.optimizer != "Adam":
-            raise NotImplementedError(f"Optimizer {self.optimizer} not understood.")
-        return {"optimizer": torch.optim.Adam(self.model.parameters(), lr=self.lr, weight_decay=self.weight_decay,
-                                              betas=(self.beta1, 0.999), amsgrad=self.amsgrad, eps=self.eps)}
-
-    def optimizer_step(self, *args, **kwargs):
-        super().optimizer_step(*args, **kwargs)
-        if self.ema_model is not None:
-            self.ema_model.update(self.model)
-
-    # ---- data ------------------------------------------------------------------------------------------------
     def inverse_data_transform_u(self, u):
         if self.rescaled:
             u = (u + 1.0) / 2.0
@@ -257,23 +71,183 @@ class PlCondEdm(_EvalMetrics, _Base):
             cond_in = torch.cat([cond_in, node], dim=-1)
         return cond_in
 
+    # ---- evaluation loops (models/ddim.py:1154-1319): sampling on the device, metric bookkeeping on the host ----------
+    def get_pde_loss(self, cond, x_denoised, x_gt_unnorm=None, noise_level=None, clamp_loss=True, do_rearrange=True,
+                     reduce=True):
+        """models/ddim.py:1388-1422: residual of (h = the first h_ch conditioning channels, u = x_denoised)."""
+        h, u = cond[..., :self.h_ch].to(torch.float32), x_denoised.to(torch.float32)
+        if do_rearrange:
+            h, u = h.permute(0, 2, 3, 1), u.permute(0, 2, 3, 1)
+        x_un = torch.cat(self.inverse_data_transform(h, u), dim=-1)
+        err = self.pde_loss(x_un, x_un if x_gt_unnorm is None else x_gt_unnorm, self.normalizer_input, self.normalizer_target,
+                            return_d=False, calc_prob=False, clamp_loss=clamp_loss)
+        if err.dim() > 3:
+            err = err.sum(dim=-1)
+        if noise_level is not None:
+            err = err / (noise_level.reshape(-1, 1, 1, 1) + 1.0)
+        return err.sum() if reduce else err
+
+    def validation_step(self, val_batch, batch_idx):
+        if (self.current_epoch + 1) % 100 != 0 and self.current_epoch != 0:
+            return {"epoch": self.current_epoch}
+        h_unnorm, dx, dt, u_unnorm = val_batch
+        self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
+        state_gt = self.data_transform(h_unnorm, u_unnorm)
+        h, u = state_gt[..., :h_ch], state_gt[..., h_ch:h_ch + u_ch]
+        u_noise = torch.randn_like(u)
+        sp = self.sparams
+        if sp.type != "edm":
+            raise NotImplementedError("only the EDM sampler is built (models/ddim.py:1172-1175)")
+        xs = self.sample_edm(self.get_cond_in(h, u, dx, dt), u_noise, sp, return_last=True, guide_dx=sp.guide_dx)
+        last = xs[:, -1]
+        loss_u = l1(last[..., :u_ch], u)
+        loss_u_un = l1(self.inverse_data_transform_u(last[..., :u_ch]), u_unnorm)
+        gt_scaled, xs_scaled = self.scale_each_min_max(state_gt), self.scale_each_min_max(last)
+        loss_u_scaled = l1(xs_scaled, gt_scaled[..., h_ch:h_ch + u_ch])
+        self._log("val_mae_u", loss_u)
+        self._log("val_mae_u_un", loss_u_un)
+        self._log("val_mae_u_scaled", loss_u_scaled)
+        self._log("val_corr_u", correlation(last, u).mean())
+        self._log("val_pde_loss", self.get_pde_loss(h, last, clamp_loss=False, do_rearrange=False) / len(h_unnorm))
+        traj, gt = (xs_scaled, gt_scaled[..., h_ch:h_ch + u_ch]) if sp.plot_scaled else (last, u)
+        return {"epoch": self.current_epoch, "loss": loss_u, "loss_u_un": loss_u_un, "val_loss_u_scaled": loss_u_scaled,
+                "traj": traj.unsqueeze(1), "gt": gt}
+
+    def test_step(self, test_batch, test_idx):
+        h_unnorm, dx, dt, u_unnorm = test_batch
+        self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
+        state_gt = self.data_transform(h_unnorm, u_unnorm)
+        h, u = state_gt[..., :h_ch], state_gt[..., h_ch:h_ch + u_ch]
+        sp = self.test_sparams
+        n, nb = sp.n_samples, len(h_unnorm)
+        cond_rep = self.get_cond_in(h, u, dx, dt).repeat(n, 1, 1, 1)
+        u_noise = torch.randn_like(u.repeat(n, 1, 1, 1))
+        if sp.type != "edm":
+            raise NotImplementedError("only the EDM sampler is built (models/ddim.py:1239-1242)")
+        xs = self.sample_edm(cond_rep, u_noise, sp, return_last=sp.return_last, guide_dx=sp.guide_dx)
+        xs_mean = xs.reshape(n, nb, *xs.shape[1:]).mean(dim=0)               # '(n b) t h w c -> n b t h w c', mean over n
+        u_last = xs_mean[:, -1, :, :, :u_ch]
+        loss_u = l1(u_last, u)
+        loss_u_un = l1(self.inverse_data_transform_u(u_last), u_unnorm)
+        gt_scaled, xs_scaled = self.scale_each_min_max(state_gt), self.scale_each_min_max(xs[:, -1])
+        if sp.select_by_pde:                                                 # best sample by PDE error instead of the mean
+            print("Use the best sample determined by PDE error")
+            h_rep_scaled = self.scale_each_min_max(h.repeat(n, 1, 1, 1).unsqueeze(-1))
+            indices, best = self.get_best_by_pde_error(torch.cat([h_unnorm, u_unnorm], dim=-1),
+                                                       torch.cat([h_rep_scaled, xs_scaled], dim=-1), n, sp.use_gt_pde_select)
+            xs_scaled_mean = best[..., -1:]
+            per_b = xs.reshape(n, nb, *xs.shape[1:]).transpose(0, 1)
+            xs_mean = per_b[torch.arange(nb, device=indices.device), indices[:, 0]]
+        else:
+            xs_scaled_mean = xs_scaled.reshape(n, nb, *xs_scaled.shape[1:]).mean(dim=0)
+        loss_u_scaled = l1(xs_scaled_mean, gt_scaled[..., h_ch:h_ch + u_ch])
+        self._log("test_corr_u", correlation(xs_mean[:, -1], u).mean())
+        print(f"\nLoss u {loss_u}, loss u un {loss_u_un}\nLoss u scaled {loss_u_scaled}")
+        self._log("test_mae_u", loss_u)
+        self._log("test_mae_u_un", loss_u_un)
+        self._log("test_mae_u_scaled", loss_u_scaled)
+        pde = self.get_pde_loss(state_gt.repeat(n, 1, 1, 1)[..., :h_ch], xs[:, -1], clamp_loss=False, do_rearrange=False) / n / nb
+        self._log("test_pde_loss", pde)
+        pde_gt = self.get_pde_loss(h, u, clamp_loss=False, do_rearrange=False) / nb
+        self._log("test_pde_loss_gt", pde_gt)
+        print(f"Pde loss is {pde}\nPde loss gt is {pde_gt}")
+        shown = xs_scaled if sp.plot_scaled else xs[:, -1]
+        traj = shown.reshape(n, nb, *shown.shape[1:]).permute(1, 2, 3, 0, 4).unsqueeze(1)      # '(n b) h w c -> b 1 h w n c'
+        return {"loss": loss_u, "loss_u_un": loss_u_un, "test_mae_u_scaled": loss_u_scaled, "traj": traj,
+                "gt": gt_scaled[..., h_ch:h_ch + u_ch] if sp.plot_scaled else u}
+
+
+class _DdpmSchedule:
+    """The DDPM noise schedule as EDM sigmas (models/ddim.py:122-137, 949-957), host side: the reference's own expressions on
+    CPU tensors.  Mixed into the modules that sample a DDPM network with the EDM sampler (PlDdim, PlCondDdim)."""
+
+    def set_test_sampler_params(self, params):
+        self.test_sparams = params
+        if params.type == "edm":                                   # models/ddim.py:125-129
+            self.edm_steps = self.get_edm_steps()
+            self.sigma_min = float(self.edm_steps[self.num_timesteps - 1])
+            self.sigma_max = float(self.edm_steps[0])
+
+    def get_edm_steps(self):
+        """models/ddim.py:131-137, evaluated on the CPU like the schedule buffers themselves."""
+        b = self.betas.detach().cpu()
+        alphas_bar = (1.0 - b).cumprod(dim=0)
+        return ((1 - alphas_bar) / alphas_bar).sqrt().flip(dims=(0,))
+
+    def _alphas_ext(self):
+        b = self.betas.detach().cpu()
+        return (1 - torch.cat([torch.zeros(1), b], dim=0)).cumprod(dim=0)
+
+    def round_sigma(self, sigma, return_index=False):
+        """models/ddim.py:949-957 (host tensors: the schedule is scalar work)."""
+        if self.edm_steps is None:
+            raise RuntimeError("call set_test_sampler_params(params) with params.type == 'edm' first (models/ddim.py:122-129)")
+        sigma = torch.as_tensor(sigma)
+        s32 = sigma.detach().cpu().to(torch.float32)
+        index = torch.cdist(s32.reshape(1, -1, 1), self.edm_steps.reshape(1, -1, 1)).argmin(2)
+        result = index if return_index else self.edm_steps[index.flatten()]
+        return result.to(device=sigma.device).type_as(sigma).reshape(sigma.shape)
+
+
+class PlCondEdm(_SingleTask):
+    def __init__(self, hparams):
+        super().__init__()
+        self.save_hyperparameters()
+        m, o = hparams.model, hparams.optimization
+        if _opt(m, "self_cond", False):
+            raise NotImplementedError("hparams.model.self_cond=True is outside the MI355X hot path")
+        # models/ddim.py:36-38: a boundary / interior flag per grid point rides along as one more conditioning channel
+        self.node_type = bool(_opt(m, "node_type", False))
+        if self.node_type:
+            m.cond_channels = m.cond_channels + 1
+        # dx_cond (models/ddim.py:33-35): the network also sees the PDE-residual gradient at its input state.  For the
+        # single-task model only dx_norm == 'prob' can run in the reference -- get_dx_pde (:1424-1450) returns a 3-D tensor
+        # with calc_prob=False and get_dx_input (:601-639) fails to unpack it (pinned: tests/golden/dxcond.npz
+        # 'dx_norm_l2_raises') -- so the other normalisations raise here as well
+        self.dx_cond = bool(_opt(m, "dx_cond", False))
+        self.dx_norm, self.dx_detach = _opt(m, "dx_norm", "l2"), _opt(m, "dx_detach", False)
+        if self.dx_cond and self.dx_norm != "prob":
+            raise NotImplementedError(f"dx_cond with dx_norm={self.dx_norm!r}: PlCondEdm.get_dx_input raises in the reference for "
+                                      "every dx_norm other than 'prob' (models/ddim.py:608-611, 1445-1448)")
+        if not str(hparams.name).startswith("adm"):
+            raise NotImplementedError("only the ADM/EDM U-Net (hparams.name = 'adm*') is on the hot path")
+        # DDPM schedule buffers of PlDdim (kept for checkpoint compatibility; the EDM path never reads them)
+        self._register_schedule(hparams)
+        self.cond_p = _opt(m, "cond_p", 0.8)
+        self.model = DhariwalUNet(hparams)
+        self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
+        if _opt(o, "pde_loss_lambda", 0.0):
+            raise NotImplementedError("pde_loss_lambda != 0 is outside the hot path")
+        self._init_common(hparams, m.in_channels, m.out_ch, default_sampler=self.get_edm_sampler_params)
+        self.P_mean, self.P_std, self.sigma_data = -1.2, 1.2, 1.0
+        self.sigma_min, self.sigma_max = 0.002, 80
+        # a default until the first batch sets the widths (the reference has none: models/ddim.py:1120-1121 are its first
+        # assignments); the node_type channel added above is not part of the known state
+        self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
+
+    # ---- configuration ----------------------------------------------------------------------------------
+    @staticmethod
+    def get_edm_sampler_params():
+        return DotDict(name="edm", type="edm", timesteps=50, sigma_min=0.002, sigma_max=80, rho=7, S_churn=15.0, S_min=0,
+                       S_max="inf", S_noise=1, n_samples=5, n_repeat=2, n_time_h=128, n_time_u=0, return_last=True,
+                       select_by_pde=False, use_gt_pde_select=True, guide_dx=False, w=0.0, plot_scaled=False)
+
+    def set_test_sampler_params(self, params):
+        if params.type != "edm":
+            print("Model with EDM preconditioning supports only EDM sampler ")
+            params = self.get_edm_sampler_params()
+        self.test_sparams = params
+
+    def configure_optimizers(self):
+        if self.optimizer != "Adam":
+            raise NotImplementedError(f"Optimizer {self.optimizer} not understood.")
+        return {"optimizer": torch.optim.Adam(self.model.parameters(), lr=self.lr, weight_decay=self.weight_decay,
+                                              betas=(self.beta1, 0.999), amsgrad=self.amsgrad, eps=self.eps)}
+
     def get_loss_weight(self, sigma):
         return (sigma ** 2 + self.sigma_data ** 2) / (sigma * self.sigma_data) ** 2
 
     # ---- HIP path -------------------------------------------------------------------------------------------
-    def _net(self, model):
-        return model.ma_model if isinstance(model, EmaModel) else model
-
-    def _grad_views(self, params):
-        n = sum(p.numel() for p in params)
-        if self._grad_buf is None or self._grad_buf.numel() != n or self._grad_buf.device != params[0].device:
-            self._grad_buf = torch.empty(n, dtype=torch.float32, device=params[0].device)
-        views, off = [], 0
-        for p in params:
-            views.append(self._grad_buf[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        return views
-
     def _dx_arg(self, net, dx):
         if dx is None:
             return None
@@ -305,10 +279,7 @@ class PlCondEdm(_EvalMetrics, _Base):
             # models/ddim.py:1755-1760: the branch is taken when cond OR dx is given; its second evaluation drops both
             if not (w is None or abs(w) < 0.001 or (cond is None and dx is None)):
                 _, Fu = net.plan.denoise(pk, xt, sigma, cond=None, ws=net._ws, sigma_data=self.sigma_data, want_F=True)
-                F = (w + 1) * F - w * Fu
-                s = sigma.reshape(-1, 1, 1, 1)
-                D = self.sigma_data ** 2 / (s ** 2 + self.sigma_data ** 2) * xt + \
-                    s * self.sigma_data / (s ** 2 + self.sigma_data ** 2).sqrt() * F
+                D, F = self._cfg_blend(xt, sigma, F, Fu, w)
         return D, F
 
     def training_step(self, train_batch, batch_idx):
@@ -326,7 +297,7 @@ class PlCondEdm(_EvalMetrics, _Base):
             dx = self.get_dx_input(cond_in[:, 0:self.h_ch], u_noise)     # on the NOISED target; carries no gradient
         if torch.rand(1) >= self.cond_p:                         # models/ddim.py:1683-1684: conditioning off for this batch
             cond_in = None                                       # (the network then reads zeros, adm_blocks.py:328-331)
-        loss = _EdmTrainLoss.apply(self, u, u_noise, sigma, cond_in, None, dx, *self.model.parameters())
+        loss = _edm_train_loss(self, u, u_noise, sigma, cond_in, None, dx)
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
         return loss
 
@@ -371,114 +342,24 @@ class PlCondEdm(_EvalMetrics, _Base):
         net = self._net(self.ema_model if self.ema_model is not None else self.model)
         h, init = _nchw(h).float(), _nchw(u_noise).float()
         sd = _lib.sampler_desc(sparams, self.sigma_data, self.sigma_min, self.sigma_max)
-        N, t = sd.timesteps, _lib.edm_t_steps(sd)
-        churn = any((min(sd.S_churn / N, math.sqrt(2) - 1) if sd.S_min <= t[i] <= sd.S_max else 0) > 0 for i in range(N))
+        N, churn = sd.timesteps, self._churns(sd)
         step_noise = torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device) if churn else None
         with torch.no_grad():
             packed = net.packed_weights()
             eager = lambda c, m_, i, sn: net.plan.sample(packed, sd, c, None, i, sn, return_last=return_last, ws=self._sample_ws,
                                                          guidance=guidance, dx_input=dx_input)
-            if os.environ.get("MCEDM_HIP_GRAPH", "1") == "0":
-                return eager(h, None, init, step_noise)
             # the call replays from one HIP graph, like PlMcedm.sample_edm (the evaluation loops repeat it); the residual
             # descriptions of guide_dx / dx_cond are host-side structs, so they are part of the key and of the capture
             B, _, H, W = init.shape
             dkey = lambda d: None if d is None else tuple(getattr(d, f) for f, _ in d._fields_)      # noqa: E731
             key = (B, H, W, bool(return_last), churn, packed.data_ptr(), init.device.index,
                    tuple(getattr(sd, f) for f, _ in sd._fields_), dkey(guidance), dkey(dx_input))
-            fn = _lib.graphed_or_eager(self._graphs, key, lambda: _lib.GraphedSampler(
+            return self._replay(key, lambda: _lib.GraphedSampler(
                 net.plan, packed, sd, B, H, W, masked=False, has_cond=True, churn=churn, return_last=return_last,
-                ws=self._sample_ws, guidance=guidance, dx_input=dx_input), eager)
-            out = fn(h, None, init, step_noise)
-            return out.clone() if fn is not eager else out
-
-    # ---- evaluation loops (models/ddim.py:1154-1319): sampling on the device, metric bookkeeping on the host ----------
-    def get_pde_loss(self, cond, x_denoised, x_gt_unnorm=None, noise_level=None, clamp_loss=True, do_rearrange=True,
-                     reduce=True):
-        """models/ddim.py:1388-1422: residual of (h = the first h_ch conditioning channels, u = x_denoised)."""
-        h, u = cond[..., :self.h_ch].to(torch.float32), x_denoised.to(torch.float32)
-        if do_rearrange:
-            h, u = h.permute(0, 2, 3, 1), u.permute(0, 2, 3, 1)
-        x_un = torch.cat(self.inverse_data_transform(h, u), dim=-1)
-        err = self.pde_loss(x_un, x_un if x_gt_unnorm is None else x_gt_unnorm, self.normalizer_input, self.normalizer_target,
-                            return_d=False, calc_prob=False, clamp_loss=clamp_loss)
-        if err.dim() > 3:
-            err = err.sum(dim=-1)
-        if noise_level is not None:
-            err = err / (noise_level.reshape(-1, 1, 1, 1) + 1.0)
-        return err.sum() if reduce else err
-
-    def validation_step(self, val_batch, batch_idx):
-        if (self.current_epoch + 1) % 100 != 0 and self.current_epoch != 0:
-            return {"epoch": self.current_epoch}
-        h_unnorm, dx, dt, u_unnorm = val_batch
-        self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
-        state_gt = self.data_transform(h_unnorm, u_unnorm)
-        h, u = state_gt[..., :h_ch], state_gt[..., h_ch:h_ch + u_ch]
-        u_noise = torch.randn_like(u)
-        sp = self.sparams
-        if sp.type != "edm":
-            raise NotImplementedError("only the EDM sampler is built (models/ddim.py:1172-1175)")
-        xs = self.sample_edm(self.get_cond_in(h, u, dx, dt), u_noise, sp, return_last=True, guide_dx=sp.guide_dx)
-        last = xs[:, -1]
-        loss_u = _l1(last[..., :u_ch], u)
-        loss_u_un = _l1(self.inverse_data_transform_u(last[..., :u_ch]), u_unnorm)
-        gt_scaled, xs_scaled = self.scale_each_min_max(state_gt), self.scale_each_min_max(last)
-        loss_u_scaled = _l1(xs_scaled, gt_scaled[..., h_ch:h_ch + u_ch])
-        self._log("val_mae_u", loss_u)
-        self._log("val_mae_u_un", loss_u_un)
-        self._log("val_mae_u_scaled", loss_u_scaled)
-        self._log("val_corr_u", _correlation(last, u).mean())
-        self._log("val_pde_loss", self.get_pde_loss(h, last, clamp_loss=False, do_rearrange=False) / len(h_unnorm))
-        traj, gt = (xs_scaled, gt_scaled[..., h_ch:h_ch + u_ch]) if sp.plot_scaled else (last, u)
-        return {"epoch": self.current_epoch, "loss": loss_u, "loss_u_un": loss_u_un, "val_loss_u_scaled": loss_u_scaled,
-                "traj": traj.unsqueeze(1), "gt": gt}
-
-    def test_step(self, test_batch, test_idx):
-        h_unnorm, dx, dt, u_unnorm = test_batch
-        self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
-        state_gt = self.data_transform(h_unnorm, u_unnorm)
-        h, u = state_gt[..., :h_ch], state_gt[..., h_ch:h_ch + u_ch]
-        sp = self.test_sparams
-        n, nb = sp.n_samples, len(h_unnorm)
-        cond_rep = self.get_cond_in(h, u, dx, dt).repeat(n, 1, 1, 1)
-        u_noise = torch.randn_like(u.repeat(n, 1, 1, 1))
-        if sp.type != "edm":
-            raise NotImplementedError("only the EDM sampler is built (models/ddim.py:1239-1242)")
-        xs = self.sample_edm(cond_rep, u_noise, sp, return_last=sp.return_last, guide_dx=sp.guide_dx)
-        xs_mean = xs.reshape(n, nb, *xs.shape[1:]).mean(dim=0)               # '(n b) t h w c -> n b t h w c', mean over n
-        u_last = xs_mean[:, -1, :, :, :u_ch]
-        loss_u = _l1(u_last, u)
-        loss_u_un = _l1(self.inverse_data_transform_u(u_last), u_unnorm)
-        gt_scaled, xs_scaled = self.scale_each_min_max(state_gt), self.scale_each_min_max(xs[:, -1])
-        if sp.select_by_pde:                                                 # best sample by PDE error instead of the mean
-            print("Use the best sample determined by PDE error")
-            h_rep_scaled = self.scale_each_min_max(h.repeat(n, 1, 1, 1).unsqueeze(-1))
-            indices, best = self.get_best_by_pde_error(torch.cat([h_unnorm, u_unnorm], dim=-1),
-                                                       torch.cat([h_rep_scaled, xs_scaled], dim=-1), n, sp.use_gt_pde_select)
-            xs_scaled_mean = best[..., -1:]
-            per_b = xs.reshape(n, nb, *xs.shape[1:]).transpose(0, 1)
-            xs_mean = per_b[torch.arange(nb, device=indices.device), indices[:, 0]]
-        else:
-            xs_scaled_mean = xs_scaled.reshape(n, nb, *xs_scaled.shape[1:]).mean(dim=0)
-        loss_u_scaled = _l1(xs_scaled_mean, gt_scaled[..., h_ch:h_ch + u_ch])
-        self._log("test_corr_u", _correlation(xs_mean[:, -1], u).mean())
-        print(f"\nLoss u {loss_u}, loss u un {loss_u_un}\nLoss u scaled {loss_u_scaled}")
-        self._log("test_mae_u", loss_u)
-        self._log("test_mae_u_un", loss_u_un)
-        self._log("test_mae_u_scaled", loss_u_scaled)
-        pde = self.get_pde_loss(state_gt.repeat(n, 1, 1, 1)[..., :h_ch], xs[:, -1], clamp_loss=False, do_rearrange=False) / n / nb
-        self._log("test_pde_loss", pde)
-        pde_gt = self.get_pde_loss(h, u, clamp_loss=False, do_rearrange=False) / nb
-        self._log("test_pde_loss_gt", pde_gt)
-        print(f"Pde loss is {pde}\nPde loss gt is {pde_gt}")
-        shown = xs_scaled if sp.plot_scaled else xs[:, -1]
-        traj = shown.reshape(n, nb, *shown.shape[1:]).permute(1, 2, 3, 0, 4).unsqueeze(1)      # '(n b) h w c -> b 1 h w n c'
-        return {"loss": loss_u, "loss_u_un": loss_u_un, "test_mae_u_scaled": loss_u_scaled, "traj": traj,
-                "gt": gt_scaled[..., h_ch:h_ch + u_ch] if sp.plot_scaled else u}
+                ws=self._sample_ws, guidance=guidance, dx_input=dx_input), eager, h, None, init, step_noise)
 
 
-class PlDdim(_EvalMetrics, _Base):
+class PlDdim(_DdpmSchedule, _PlBase):
     """models/ddim.py:16-1051, the part BASELINE config 5 exercises: EDM / RePaint sampling of the joint (h, u) DDPM.
     Constructor, buffers (``betas``, ``logvar``), attributes and the signatures of ``set_test_sampler_params``,
     ``get_edm_steps``, ``compute_alpha``, ``round_sigma``, ``get_denoised`` and ``sample_edm`` follow the reference.
@@ -488,84 +369,25 @@ class PlDdim(_EvalMetrics, _Base):
     def __init__(self, hparams):
         super().__init__()
         self.save_hyperparameters()
-        m, o, d, df = hparams.model, hparams.optimization, hparams.data, hparams.diffusion
+        m = hparams.model
         for flag in ("dx_cond", "node_type"):
             if _opt(m, flag, False):
                 raise NotImplementedError(f"hparams.model.{flag}=True is outside the built path")
         if str(hparams.name).startswith("adm"):
             raise NotImplementedError("PlDdim with the ADM U-Net is not built; use PlMcedm / PlCondEdm for ADM networks")
         from .ddim_blocks import Model
-        betas = _beta_schedule(df.beta_schedule, df.beta_start, df.beta_end, df.num_diffusion_timesteps)
-        acp = (1.0 - betas).cumprod(dim=0)
-        post_var = betas * (1.0 - torch.cat([torch.ones(1), acp[:-1]])) / (1.0 - acp)
-        self.model_var_type = m.var_type
-        self.register_buffer("betas", betas)
-        self.num_timesteps = betas.shape[0]
-        if m.var_type == "fixedlarge":
-            self.register_buffer("logvar", betas.log())
-        elif m.var_type == "fixedsmall":
-            self.register_buffer("logvar", post_var.clamp(min=1e-20).log())
+        self._register_schedule(hparams)
         self.cond_p = 0.0
         self.dx_cond = self.node_type = False
         self.model = Model(hparams)
         self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
-        self.normalization, self.rescaled = d.normalization, d.rescaled
-        self.uniform_dequantization, self.gaussian_dequantization = d.uniform_dequantization, d.gaussian_dequantization
-        n_state = m.out_ch // 2
-        self.normalizer_input = Normalizer((n_state,) if n_state > 1 else ())
-        self.normalizer_target = Normalizer((n_state,) if n_state > 1 else ())
-        self.optimizer, self.lr, self.weight_decay = o.optimizer, o.lr, o.weight_decay
-        self.beta1, self.amsgrad, self.eps = o.beta1, o.amsgrad, o.eps
-        self.sparams = hparams.sampler if hparams.get("sampler", None) is not None else \
-            DotDict(type="ddim", timesteps=50, skip_type="uniform", eta=0.0, n_samples=1, n_repeat=5, n_time_h=128, n_time_u=0)
-        self.test_sparams = self.sparams
-        self.h_ch = self.u_ch = n_state
-        self.edm_steps = None
-        self.sigma_min = self.sigma_max = None
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system="swe", flip_xy=False)    # models/ddim.py:76-78
-        self._sample_ws = _lib.Workspace()
-        self._graphs = {}
-
-    def set_pde_loss_function(self, system, flip_xy):
-        """models/ddim.py:97-101; the residual metric runs on the device (m-cedm_amd/pde_loss.py)."""
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system, flip_xy)
-
-    # ---- schedule (host side, the reference's own expressions on CPU tensors) ----------------------------------
-    def set_test_sampler_params(self, params):
-        self.test_sparams = params
-        if params.type == "edm":                                   # models/ddim.py:125-129
-            self.edm_steps = self.get_edm_steps()
-            self.sigma_min = float(self.edm_steps[self.num_timesteps - 1])
-            self.sigma_max = float(self.edm_steps[0])
-
-    def get_edm_steps(self):
-        """models/ddim.py:131-137, evaluated on the CPU like the schedule buffers themselves."""
-        b = self.betas.detach().cpu()
-        alphas_bar = (1.0 - b).cumprod(dim=0)
-        return ((1 - alphas_bar) / alphas_bar).sqrt().flip(dims=(0,))
-
-    def _alphas_ext(self):
-        b = self.betas.detach().cpu()
-        return (1 - torch.cat([torch.zeros(1), b], dim=0)).cumprod(dim=0)
+        self.h_ch = self.u_ch = m.out_ch // 2
+        self._init_common(hparams, self.h_ch, self.u_ch)
+        self.edm_steps = self.sigma_min = self.sigma_max = None
 
     def compute_alpha(self, t):
         """models/ddim.py:700-704."""
         return self._alphas_ext().index_select(0, torch.as_tensor(t).cpu().reshape(-1) + 1).view(-1, 1, 1, 1)
-
-    def round_sigma(self, sigma, return_index=False):
-        """models/ddim.py:949-957 (host tensors: the schedule is scalar work)."""
-        if self.edm_steps is None:
-            raise RuntimeError("call set_test_sampler_params(params) with params.type == 'edm' first (models/ddim.py:122-129)")
-        sigma = torch.as_tensor(sigma)
-        s32 = sigma.detach().cpu().to(torch.float32)
-        index = torch.cdist(s32.reshape(1, -1, 1), self.edm_steps.reshape(1, -1, 1)).argmin(2)
-        result = index if return_index else self.edm_steps[index.flatten()]
-        return result.to(device=sigma.device).type_as(sigma).reshape(sigma.shape)
-
-    def _net(self, model):
-        return model.ma_model if isinstance(model, EmaModel) else model
 
     def get_denoised(self, model, xt, t, cond=None, x_self_cond=None, dx=None, w=None):
         """models/ddim.py:915-947 at one noise level: VP preconditioning around the DDPM network."""
@@ -611,30 +433,17 @@ class PlDdim(_EvalMetrics, _Base):
             seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64)          # CPU generator: torch.manual_seed reproduces
             eager = lambda x, nz, sd: net.plan.repaint_sample(packed, rd, x, nz, return_last=return_last, ws=self._sample_ws,
                                                               rng_seed=sd.to(x.device))
-            if os.environ.get("MCEDM_HIP_GRAPH", "1") == "0":
-                return eager(hu, hu_noise, seed)
             B = hu.shape[0]
             key = (B, bool(return_last), packed.data_ptr(), hu.device.index, float(self.edm_steps[0]),
                    tuple(getattr(rd, f) for f, _ in rd._fields_ if f not in ("edm_steps", "alphas_cumprod_ext")))
-            fn = _lib.graphed_or_eager(self._graphs, key, lambda: _lib.GraphedRepaint(net.plan, packed, rd, keep, B, return_last,
-                                                                                     ws=self._sample_ws), eager)
-            out = fn(hu, hu_noise, seed)
-            return out.clone() if fn is not eager else out
+            return self._replay(key, lambda: _lib.GraphedRepaint(net.plan, packed, rd, keep, B, return_last, ws=self._sample_ws),
+                                eager, hu, hu_noise, seed)
 
     # ---- evaluation loops (models/ddim.py:294-533): BASELINE config 5 is run through trainer.test -> test_step ------------
     def get_pde_loss(self, cond, x_denoised, x_gt_unnorm=None, noise_level=None, clamp_loss=True, do_rearrange=True,
                      reduce=True):
         """models/ddim.py:535-565: residual of the joint (h, u) state."""
-        if do_rearrange:
-            x_denoised = x_denoised.permute(0, 2, 3, 1)
-        h = x_denoised[..., :self.h_ch].to(torch.float32)
-        u = x_denoised[..., self.h_ch:self.h_ch + self.u_ch].to(torch.float32)
-        x_un = torch.cat(self.inverse_data_transform(h, u), dim=-1)
-        err = self.pde_loss(x_un, x_un if x_gt_unnorm is None else x_gt_unnorm, self.normalizer_input, self.normalizer_target,
-                            return_d=False, calc_prob=False, clamp_loss=clamp_loss)
-        if noise_level is not None:
-            err = err / (noise_level.reshape(-1, 1, 1, 1) + 1.0)
-        return err.sum() if reduce else err
+        return self._joint_pde_loss(x_denoised, x_gt_unnorm, noise_level, clamp_loss, do_rearrange, reduce)
 
     def _sample_eval(self, h, u, sp, return_last):
         """models/ddim.py:309-312, 391-394: the EDM / RePaint sampler for type 'edm', the DDIM RePaint sampler otherwise."""
@@ -654,16 +463,16 @@ class PlDdim(_EvalMetrics, _Base):
         xs = self._sample_eval(h, torch.randn_like(u), sp, True)
         last = xs[:, -1]
         h_last, u_last = last[..., :h_ch], last[..., h_ch:h_ch + u_ch]
-        loss_h, loss_u = _l1(h_last, h), _l1(u_last, u)
+        loss_h, loss_u = l1(h_last, h), l1(u_last, u)
         h_un, u_un = self.inverse_data_transform(h_last, u_last)
-        loss_h_un, loss_u_un = _l1(h_un, h_unnorm), _l1(u_un, u_unnorm)
+        loss_h_un, loss_u_un = l1(h_un, h_unnorm), l1(u_un, u_unnorm)
         gt_scaled, xs_scaled = self.scale_each_min_max(state_gt), self.scale_each_min_max(last)
-        loss_h_scaled = _l1(xs_scaled[..., :h_ch], gt_scaled[..., :h_ch])
-        loss_u_scaled = _l1(xs_scaled[..., h_ch:h_ch + u_ch], gt_scaled[..., h_ch:h_ch + u_ch])
+        loss_h_scaled = l1(xs_scaled[..., :h_ch], gt_scaled[..., :h_ch])
+        loss_u_scaled = l1(xs_scaled[..., h_ch:h_ch + u_ch], gt_scaled[..., h_ch:h_ch + u_ch])
         for name, v in (("val_mae_h", loss_h), ("val_mae_u", loss_u), ("val_mae_h_un", loss_h_un), ("val_mae_u_un", loss_u_un),
                         ("val_mae_h_scaled", loss_h_scaled), ("val_mae_u_scaled", loss_u_scaled)):
             self._log(name, v)
-        corr = _correlation(last, state_gt)
+        corr = correlation(last, state_gt)
         self._log("val_corr_h", corr[:h_ch].mean())
         self._log("val_corr_u", corr[h_ch:h_ch + u_ch].mean())
         self._log("val_pde_loss", self.get_pde_loss(None, last, clamp_loss=False, do_rearrange=False) / len(h_unnorm))
@@ -684,16 +493,16 @@ class PlDdim(_EvalMetrics, _Base):
         xs = self._sample_eval(rep[..., hs], rep[..., us], sp, sp.return_last)
         xs_mean = xs.reshape(n, nb, *xs.shape[1:]).mean(dim=0)               # '(n b) t h w c -> n b t h w c', mean over n
         h_last, u_last = xs_mean[:, -1, :, :, hs], xs_mean[:, -1, :, :, us]
-        loss_h, loss_u = _l1(h_last, h), _l1(u_last, u)
+        loss_h, loss_u = l1(h_last, h), l1(u_last, u)
         h_un, u_un = self.inverse_data_transform(h_last, u_last)
-        loss_h_un, loss_u_un = _l1(h_un, h_unnorm), _l1(u_un, u_unnorm)
+        loss_h_un, loss_u_un = l1(h_un, h_unnorm), l1(u_un, u_unnorm)
         hu_un, gt_un = torch.cat([h_un, u_un], dim=-1), torch.cat([h_unnorm, u_unnorm], dim=-1)
         unknown = torch.ones_like(hu_un)                                     # 1 = generated entries (:419-424)
         if n_time_h > 0:
             unknown[:, :n_time_h, :, hs] = 0.0
         if n_time_u > 0:
             unknown[:, :n_time_u, :, us] = 0.0
-        loss_hu_un = _masked_l1(hu_un, gt_un, unknown)
+        loss_hu_un = masked_l1(hu_un, gt_un, unknown)
         gt_scaled, xs_scaled = self.scale_each_min_max(state_gt), self.scale_each_min_max(xs[:, -1])
         if sp.select_by_pde:
             print("Use the best sample determined by PDE error")
@@ -702,17 +511,17 @@ class PlDdim(_EvalMetrics, _Base):
             xs_mean = per_b[torch.arange(nb, device=indices.device), indices[:, 0]]
         else:
             xs_scaled_mean = xs_scaled.reshape(n, nb, *xs_scaled.shape[1:]).mean(dim=0)
-        loss_h_scaled = _l1(xs_scaled_mean[..., hs], gt_scaled[..., hs])
-        loss_u_scaled = _l1(xs_scaled_mean[..., us], gt_scaled[..., us])
-        corr = _correlation(xs_mean[:, -1], state_gt)
+        loss_h_scaled = l1(xs_scaled_mean[..., hs], gt_scaled[..., hs])
+        loss_u_scaled = l1(xs_scaled_mean[..., us], gt_scaled[..., us])
+        corr = correlation(xs_mean[:, -1], state_gt)
         self._log("test_corr_h", corr[hs].mean())
         self._log("test_corr_u", corr[us].mean())
         for tag, ch, last, ref, k, on in (("h", hs, h_last, h, n_time_h, n_time_h < n_all),
                                           ("u", us, u_last, u, n_time_u, n_all > n_time_u > 0)):
             if on:      # error on the rows handed in (0 by construction) and scaled error on / off them (:460-482)
-                self._log(f"test_{tag}_known", _l1(last[:, :k], ref[:, :k]))
-                self._log(f"test_{tag}_kn_scaled", _l1(xs_scaled_mean[:, :k, :, ch], gt_scaled[:, :k, :, ch]))
-                self._log(f"test_{tag}_unkn_scaled", _l1(xs_scaled_mean[:, k:, :, ch], gt_scaled[:, k:, :, ch]))
+                self._log(f"test_{tag}_known", l1(last[:, :k], ref[:, :k]))
+                self._log(f"test_{tag}_kn_scaled", l1(xs_scaled_mean[:, :k, :, ch], gt_scaled[:, :k, :, ch]))
+                self._log(f"test_{tag}_unkn_scaled", l1(xs_scaled_mean[:, k:, :, ch], gt_scaled[:, k:, :, ch]))
         print(f"\nLoss h {loss_h}, loss h un {loss_h_un}\nLoss u {loss_u}, loss u un {loss_u_un}\nLoss hu un {loss_hu_un}\n"
               f"Loss h scaled {loss_h_scaled}, loss u scaled {loss_u_scaled}")
         for name, v in (("test_mae_h", loss_h), ("test_mae_u", loss_u), ("test_mae_h_un", loss_h_un), ("test_mae_u_un", loss_u_un),
@@ -764,41 +573,21 @@ class PlDdim(_EvalMetrics, _Base):
                                   "of a trained DDPM checkpoint")
 
 
-class _EpsTrainLoss(torch.autograd.Function):
+def _eps_train_loss(module, x_noise, labels, cond, noise):
     """NoiseEstimationLoss of PlCondDdim.training_step (models/ddim.py:1118-1152, models/losses.py:39-59):
     loss = mean_b sum_chw (F - noise)^2 with F = model(x_noise, t.float(), cond').  Forward and backward run in the HIP library
-    (mcedm_unet_forward, mcedm_eps_loss, mcedm_unet_backward); modelled on mcedm._EdmTrainLoss."""
+    (mcedm_unet_forward, mcedm_eps_loss, mcedm_unet_backward)."""
+    net: DhariwalUNet = module.model
 
-    @staticmethod
-    def forward(ctx, module, x_noise, labels, cond, noise, *params):
-        net: DhariwalUNet = module.model
-        plan, packed = net.plan, net.packed_weights()
-        F = plan.forward(packed, x_noise, labels, cond=cond, ws=module._train_ws, training=True)
+    def run():
+        F = net.plan.forward(net.packed_weights(), x_noise, labels, cond=cond, ws=module._train_ws, training=True)
         loss, dF = _lib.eps_loss(F, noise, want_grad=True)
-        module._train_generation += 1
-        ctx.module, ctx.saved, ctx.generation = module, (x_noise, labels, cond, dF), module._train_generation
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        module = ctx.module
-        net: DhariwalUNet = module.model
-        if ctx.generation != module._train_generation:
-            raise RuntimeError("training_step: another training forward overwrote this one's activations before its "
-                               "backward ran (one outstanding forward per module; run backward before the next forward)")
-        x_noise, labels, cond, dF = ctx.saved
-        params = list(net.parameters())
-        grads = module._grad_views(params)
-        net.plan.unet_backward(net.packed_weights(), net.named_param_dict(), x_noise, labels, cond, dF, grads, ws=module._train_ws)
-        flat = module._grad_buf * g.to(torch.float32)
-        out, off = [], 0
-        for p in params:
-            out.append(flat[off:off + p.numel()].view(p.shape))
-            off += p.numel()
-        return (None, None, None, None, None) + tuple(out)
+        return loss, lambda grads: net.plan.unet_backward(net.packed_weights(), net.named_param_dict(), x_noise, labels, cond, dF,
+                                                          grads, ws=module._train_ws)
+    return _TrainLoss.apply(module, run, *net.parameters())
 
 
-class PlCondDdim(_EvalMetrics, _Base):
+class PlCondDdim(_DdpmSchedule, _SingleTask):
     """models/ddim.py:1053-1605: the single-task conditional DDPM (epsilon prediction) on the ADM U-Net
     (configs/model/adm_cond_h_res32.yaml: ``name: adm_cond_h``, ``self_cond: True``, ``cond_p: 1.``), trained with the noise
     estimation loss and sampled with the EDM Heun sampler around VP preconditioning (``get_denoised``, :915-947).
@@ -812,7 +601,7 @@ class PlCondDdim(_EvalMetrics, _Base):
     def __init__(self, hparams):
         super().__init__()
         self.save_hyperparameters()
-        m, o, d, df = hparams.model, hparams.optimization, hparams.data, hparams.diffusion
+        m, o = hparams.model, hparams.optimization
         if not str(hparams.name).startswith("adm"):
             raise NotImplementedError("PlCondDdim with the DDPM U-Net (models/ddim.py:43-46, Model) has no backward here; only "
                                       "the ADM U-Net (hparams.name = 'adm*') trains")
@@ -824,67 +613,17 @@ class PlCondDdim(_EvalMetrics, _Base):
         self.node_type = bool(_opt(m, "node_type", False))
         if self.node_type:
             m.cond_channels = m.cond_channels + 1
-        betas = _beta_schedule(df.beta_schedule, df.beta_start, df.beta_end, df.num_diffusion_timesteps)
-        acp = (1.0 - betas).cumprod(dim=0)
-        post_var = betas * (1.0 - torch.cat([torch.ones(1), acp[:-1]])) / (1.0 - acp)
-        self.model_var_type = m.var_type
-        self.register_buffer("betas", betas)
-        self.num_timesteps = betas.shape[0]
-        if m.var_type == "fixedlarge":
-            self.register_buffer("logvar", betas.log())
-        elif m.var_type == "fixedsmall":
-            self.register_buffer("logvar", post_var.clamp(min=1e-20).log())
+        self._register_schedule(hparams)
         self.model = DhariwalUNet(hparams)
         self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
-        self.cond_p = m.cond_p if hasattr(m, "cond_p") else 0.8                       # models/ddim.py:1058
-        self.normalization, self.rescaled = d.normalization, d.rescaled
-        self.uniform_dequantization, self.gaussian_dequantization = d.uniform_dequantization, d.gaussian_dequantization
-        self.normalizer_input = Normalizer((m.in_channels,) if m.in_channels > 1 else ())
-        self.normalizer_target = Normalizer((m.out_ch,) if m.out_ch > 1 else ())
-        self.optimizer, self.lr, self.weight_decay = o.optimizer, o.lr, o.weight_decay
-        self.beta1, self.amsgrad, self.eps = o.beta1, o.amsgrad, o.eps
+        self.cond_p = _opt(m, "cond_p", 0.8)                                           # models/ddim.py:1058
+        self._init_common(hparams, m.in_channels, m.out_ch)
         self.factor, self.step_size, self.loss = _opt(o, "factor", 0.3), _opt(o, "step_size", 50), _opt(o, "loss", "l2")
         self.pde_loss_lambda = 0.0
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system="swe", flip_xy=False)    # models/ddim.py:76-78
-        self.sparams = hparams.sampler if hparams.get("sampler", None) is not None else \
-            DotDict(type="ddim", timesteps=50, skip_type="uniform", eta=0.0, n_samples=1, n_repeat=5, n_time_h=128, n_time_u=0)
-        self.test_sparams = self.sparams
-        self.edm_steps = None
-        self.sigma_min = self.sigma_max = None
+        self.edm_steps = self.sigma_min = self.sigma_max = None
         self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
-        self._train_ws, self._grad_buf, self._train_generation = _lib.Workspace(), None, 0
-        self._sample_ws = _lib.Workspace()
         self._tables = None
         self._stage = None
-
-    # ---- shared with PlCondEdm: identical in the reference (PlCondEdm inherits them from PlCondDdim) -----------------
-    setup = PlCondEdm.setup
-    set_pde_loss_function = PlCondEdm.set_pde_loss_function
-    inverse_data_transform_u = PlCondEdm.inverse_data_transform_u
-    get_cond_in = PlCondEdm.get_cond_in
-    get_pde_loss = PlCondEdm.get_pde_loss
-    validation_step = PlCondEdm.validation_step
-    test_step = PlCondEdm.test_step
-    _net = PlCondEdm._net
-    _grad_views = PlCondEdm._grad_views
-
-    # ---- optimiser: the fused clip + Adam + EMA seam of PlMcedm (m-cedm_amd/optim.py) -----------------------------
-    from .mcedm import PlMcedm as _PlMcedm
-    configure_optimizers = _PlMcedm.configure_optimizers
-    configure_gradient_clipping = _PlMcedm.configure_gradient_clipping
-    del _PlMcedm
-
-    def optimizer_step(self, *args, **kwargs):
-        """models/ddim.py:228-233: Lightning's step, then EmaModel.update (already done by the fused optimiser's kernel)."""
-        super().optimizer_step(*args, **kwargs)
-        if self.ema_model is not None and getattr(self, "_fused_opt", None) is None:
-            self.ema_model.update(self.model)
-
-    # ---- schedule (host side, the reference's own expressions) ------------------------------------------------------
-    set_test_sampler_params = PlDdim.set_test_sampler_params
-    get_edm_steps = PlDdim.get_edm_steps
-    round_sigma = PlDdim.round_sigma
 
     def _noise_tables(self, device):
         """sqrt(a) and sqrt(1 - a), a = (1 - betas).cumprod(0), on the module's device (models/ddim.py:195-197)."""
@@ -949,7 +688,7 @@ class PlCondDdim(_EvalMetrics, _Base):
         t = t.to(x.device).long()
         t = torch.cat([t, self.num_timesteps - t - 1], dim=0)[:n]
         x_noise, labels, condp, _ = self._noised_inputs(u, t, noise, cond_in, self._train_ws)
-        loss = _EpsTrainLoss.apply(self, x_noise, labels, condp, noise.contiguous(), *self.model.parameters())
+        loss = _eps_train_loss(self, x_noise, labels, condp, noise.contiguous())
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
         return loss
 

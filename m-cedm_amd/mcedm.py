@@ -7,6 +7,9 @@ Lightning drives ``training_step`` / ``validation_step`` / ``test_step`` unchang
 libmcedm_hip.so; the metric bookkeeping around it (MAE, PDE residual, return dicts for the plotting
 callbacks) stays in Python like the reference's.
 
+``Normalizer``, ``DotDict``, ``masked_l1`` and everything else the drop-ins for ``models/ddim.py`` need as well live in
+``m-cedm_amd/pl_base.py`` and are re-exported here.
+
 Deliberate differences, all documented in INTEGRATION.md:
   * sample_edm draws the per-step churn noise only for steps with gamma > 0 (the reference draws and
     multiplies by zero otherwise, mcedm.py:608), so device RNG streams differ for S_churn = 0;
@@ -17,140 +20,49 @@ Deliberate differences, all documented in INTEGRATION.md:
 """
 from __future__ import annotations
 
-import math
 import os
-from typing import Optional
 
 import torch
-from torch import nn
 
 from . import lib as _lib
 from .adm_blocks import DhariwalUNet, EmaModel
-
-try:  # Lightning is the reference's runtime; the build/test containers do not ship it
-    import pytorch_lightning as pl
-    _Base = pl.LightningModule
-except Exception:  # pragma: no cover - exercised where Lightning is absent
-    class _Base(nn.Module):
-        """Minimal stand-in so the module is usable (and testable) without pytorch_lightning."""
-        current_epoch = 0
-
-        def save_hyperparameters(self, *a, **k):
-            pass
-
-        def log(self, *a, **k):
-            pass
-
-        # Lightning's defaults for the two hooks the drop-in overrides (pytorch_lightning/core/module.py): the optimiser step runs
-        # the closure (zero_grad + training_step + backward), gradient clipping is clip_grad_norm_ on the optimiser's parameters
-        def optimizer_step(self, epoch=None, batch_idx=None, optimizer=None, optimizer_idx=0, optimizer_closure=None, *a, **k):
-            optimizer.step(closure=optimizer_closure)
-
-        def clip_gradients(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
-            if gradient_clip_val is None or gradient_clip_val <= 0:
-                return
-            params = [p for g in optimizer.param_groups for p in g["params"]]
-            if gradient_clip_algorithm in (None, "norm"):
-                torch.nn.utils.clip_grad_norm_(params, gradient_clip_val)
-            else:
-                torch.nn.utils.clip_grad_value_(params, gradient_clip_val)
+from .pl_base import (DotDict, Normalizer, _Base, _PlBase, _TrainLoss, _ddim_sampler_params, _nchw, _opt,  # noqa: F401
+                      masked_l1)
 
 
-class DotDict(dict):
-    __getattr__ = dict.__getitem__
-    __setattr__ = dict.__setitem__
-    __delattr__ = dict.__delitem__
-
-
-class Normalizer(nn.Module):
-    """(x - subtract) / divide and its inverse; stats travel as buffers (models/normalizer.py:5-29)."""
-
-    def __init__(self, stats_shape=()):
-        super().__init__()
-        self.register_buffer("subtract", torch.zeros(stats_shape))
-        self.register_buffer("divide", torch.ones(stats_shape))
-
-    def set_stats(self, subtract, divide):
-        self.subtract = torch.as_tensor(subtract)
-        self.divide = torch.as_tensor(divide)
-
-    def forward(self, x, inverse=False):
-        if inverse:
-            return x * self.divide.to(x.device) + self.subtract.to(x.device)
-        return (x - self.subtract.to(x.device)) / self.divide.to(x.device)
-
-
-def masked_l1(pred, target, mask, loss_dim=None):
-    """MaskedLoss('l1') of models/losses.py:62-78: sum |pred*m - target*m| / sum(m)."""
-    pred, target = pred * mask, target * mask
-    if loss_dim is not None:
-        pred, target, mask = pred[..., loss_dim], target[..., loss_dim], mask[..., loss_dim]
-    return (pred - target).abs().sum() / mask.sum()
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2).contiguous()
-
-
-class _EdmTrainLoss(torch.autograd.Function):
+def _edm_train_loss(module, x, x_noise, sigma, cond, mask, dx):
     """loss = mean_b sum_chw w(sigma_b) (D*m - x*m)^2 with D = model_precond(x_noise, sigma, cond): forward and
     backward both run in the HIP library (mcedm_edm_denoise / mcedm_edm_loss / mcedm_edm_denoise_backward).
-    Parameters enter as inputs so that Lightning's automatic optimisation and DDP see ordinary .grad tensors."""
+    dx: the network's PDE-gradient input of dx_cond models (PlCondEdm.training_step) or None; no gradient flows into it."""
+    net: DhariwalUNet = module.model
 
-    @staticmethod
-    def forward(ctx, module, x, x_noise, sigma, cond, mask, dx, *params):
-        net: DhariwalUNet = module.model
-        plan, packed = net.plan, net.packed_weights()
-        B, _, H, W = x.shape
-        ws = module._train_ws
-        # dx: the network's PDE-gradient input of dx_cond models (PlCondEdm.training_step) or None; no gradient flows into it
-        D = plan.denoise(packed, x_noise, sigma, cond=cond, ws=ws, training=True, sigma_data=module.sigma_data, dx=dx)
+    def run():
+        D = net.plan.denoise(net.packed_weights(), x_noise, sigma, cond=cond, ws=module._train_ws, training=True,
+                             sigma_data=module.sigma_data, dx=dx)
         loss, dD = _lib.edm_loss(D, x, mask, sigma, sigma_data=module.sigma_data, want_grad=True)
-        # the activations of THIS forward live in the module's single training workspace until its backward runs
-        module._train_generation += 1
-        ctx.module, ctx.saved, ctx.generation = module, (x_noise, sigma, cond, dD, dx), module._train_generation
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        module = ctx.module
-        net: DhariwalUNet = module.model
-        if ctx.generation != module._train_generation:
-            raise RuntimeError("training_step: another training forward overwrote this one's activations before its "
-                               "backward ran (one outstanding forward per module; run backward before the next forward)")
-        x_noise, sigma, cond, dD, dx = ctx.saved
-        params = list(net.parameters())
-        grads = module._grad_views(params)
-        net.plan.denoise_backward(net.packed_weights(), net.named_param_dict(), x_noise, sigma, cond, dD, grads,
-                                  ws=module._train_ws, sigma_data=module.sigma_data, dx=dx)
-        # one scale of the flat buffer into a FRESH tensor (autograd may keep the returned views as .grad, so they
-        # must not alias the buffer the next backward overwrites) instead of one multiply per parameter
-        flat = module._grad_buf * g.to(torch.float32)
-        out, off = [], 0
-        for p in params:
-            out.append(flat[off:off + p.numel()].view(p.shape))
-            off += p.numel()
-        return (None, None, None, None, None, None, None) + tuple(out)
+        return loss, lambda grads: net.plan.denoise_backward(
+            net.packed_weights(), net.named_param_dict(), x_noise, sigma, cond, dD, grads, ws=module._train_ws,
+            sigma_data=module.sigma_data, dx=dx)
+    return _TrainLoss.apply(module, run, *net.parameters())
 
 
-class PlMcedm(_Base):
+class PlMcedm(_PlBase):
     def __init__(self, hparams):
         super().__init__()
         self.save_hyperparameters()
-        m, o, d = hparams.model, hparams.optimization, hparams.data
+        m, o = hparams.model, hparams.optimization
         self.cond_p = 1.0
-        if getattr(m, "dx_cond", False) if hasattr(m, "dx_cond") else False:
+        if _opt(m, "dx_cond", False):
             raise NotImplementedError("hparams.model.dx_cond=True cannot run for the joint model in the reference either "
                                       "(PlMcedm.get_dx_pde slices the wrong axis, models/mcedm.py:500-518); see DESIGN.md")
         if not str(hparams.name).startswith("adm"):
             raise NotImplementedError("only the ADM/EDM U-Net (hparams.name = 'adm*') is on the hot path")
         self.dx_cond = False
-        if getattr(m, "self_cond", False) if hasattr(m, "self_cond") else False:
+        if _opt(m, "self_cond", False):
             raise NotImplementedError("hparams.model.self_cond=True is outside the MI355X hot path for PlMcedm")
         # models/mcedm.py:25-34: the two optional widenings of the conditioning input.  Like the reference, the constructor
         # rewrites hparams.model.cond_channels before the network is built (the C ABI takes any cond_channels).
-        self.add_cond_mask = bool(m.add_cond_mask) if hasattr(m, "add_cond_mask") else False
-        self.add_xt = bool(m.add_xt) if hasattr(m, "add_xt") else False
+        self.add_cond_mask, self.add_xt = bool(_opt(m, "add_cond_mask", False)), bool(_opt(m, "add_xt", False))
         if self.add_cond_mask:
             m.cond_channels = m.cond_channels + m.in_channels          # the observation mask rides along (SSSD-S4 style)
         if self.add_xt:
@@ -160,30 +72,12 @@ class PlMcedm(_Base):
         # EDM preconditioning constants (mcedm.py:45-50)
         self.P_mean, self.P_std, self.sigma_data = -1.2, 1.2, 1.0
         self.sigma_min, self.sigma_max = 0.002, 80
-        self.normalization = d.normalization
-        self.uniform_dequantization = d.uniform_dequantization
-        self.gaussian_dequantization = d.gaussian_dequantization
-        self.rescaled = d.rescaled
-        n_state = m.out_ch // 2
-        shape = (n_state,) if n_state > 1 else ()
-        self.normalizer_input = Normalizer(shape)
-        self.normalizer_target = Normalizer(shape)
-        self.optimizer, self.lr, self.weight_decay = o.optimizer, o.lr, o.weight_decay
-        self.beta1, self.amsgrad, self.eps = o.beta1, o.amsgrad, o.eps
         self.factor, self.step_size, self.loss = o.factor, o.step_size, o.loss
-        self.pde_loss_lambda = getattr(o, "pde_loss_lambda", 0.0) if hasattr(o, "pde_loss_lambda") else 0.0
+        self.pde_loss_lambda = _opt(o, "pde_loss_lambda", 0.0)
         if self.pde_loss_lambda:
             raise NotImplementedError("pde_loss_lambda != 0 is outside the hot path")
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system="swe", flip_xy=False)   # mcedm.py:82-84
-        self.sparams = self.get_sampler_params(hparams)
-        self.test_sparams = self.sparams
-        self.h_ch = self.u_ch = n_state
-        self._train_ws = _lib.Workspace()
-        self._sample_ws = _lib.Workspace()
-        self._grad_buf = None
-        self._train_generation = 0
-        self._graphs = {}
+        self.h_ch = self.u_ch = m.out_ch // 2
+        self._init_common(hparams, self.h_ch, self.u_ch)
         # where the sampler's per-step churn noise (models/mcedm.py:608) comes from: "device" = generated inside the kernel that
         # applies it (mcedm_heun_sample_rng; keyed by a seed drawn from torch's CPU generator, so seed_everything still pins a
         # run), "torch" = torch.randn((N, B, 2, H, W), float64) materialised up front (2.1 GB at the reference's shipped
@@ -193,98 +87,10 @@ class PlMcedm(_Base):
     # ---- configuration hooks (same names as the reference) ------------------------------------------
     @staticmethod
     def get_sampler_params(params):
-        if params.get("sampler", None) is None:
-            return DotDict(type="ddim", timesteps=50, skip_type="uniform", eta=0.0, n_samples=1, n_repeat=5,
-                           n_time_h=128, n_time_u=0)
-        return params.sampler
+        return _ddim_sampler_params() if params.get("sampler", None) is None else params.sampler
 
     def set_test_sampler_params(self, params):
         self.test_sparams = params
-
-    def set_pde_loss_function(self, system, flip_xy):
-        """models/mcedm.py:100-104.  The residual metric runs on the device (m-cedm_amd/pde_loss.py ->
-        csrc/pde.hip, bit-identical to models/pde_loss.py); its guidance gradient is not built."""
-        from .pde_loss import get_pde_loss_function
-        self.pde_loss, self.pde_loss_simulator = get_pde_loss_function(system, flip_xy)
-
-    def setup(self, stage: str = None) -> None:
-        if stage == "fit":
-            st = self.trainer.datamodule.get_norm_stats()
-            if self.normalization == "min_max":
-                self.normalizer_input.set_stats(st["input_min"], st["input_min_max"])
-                self.normalizer_target.set_stats(st["target_min"], st["target_min_max"])
-            else:
-                self.normalizer_input.set_stats(st["input_mean"], st["input_std"])
-                self.normalizer_target.set_stats(st["target_mean"], st["target_std"])
-
-    def configure_optimizers(self):
-        """models/mcedm.py:139-161.  ``optimizer: Adam`` on the device returns ``optim.FusedAdamEma`` -- a torch.optim.Optimizer
-        over flat buffers whose ``step()`` is the fused clip + Adam + EMA kernels (K11), state_dict in torch.optim.Adam form;
-        ``MCEDM_FUSED_OPT=0`` (or amsgrad, or a module still on the CPU) keeps plain ``torch.optim.Adam``."""
-        self._fused_opt = None
-        if self.optimizer == "Adam":
-            p0 = next(self.model.parameters())
-            if os.environ.get("MCEDM_FUSED_OPT", "1") != "0" and p0.is_cuda and not self.amsgrad:
-                from .optim import FusedAdamEma
-                ema = self.ema_model.ma_model if self.ema_model is not None else None
-                opt = FusedAdamEma(self.model, ema, lr=self.lr, betas=(self.beta1, 0.999), eps=self.eps,
-                                   weight_decay=self.weight_decay, ema_beta=self.ema_model.beta if ema is not None else 0.999)
-                self._fused_opt = opt
-                return {"optimizer": opt}
-            opt = torch.optim.Adam(self.model.parameters(), lr=self.lr, weight_decay=self.weight_decay,
-                                   betas=(self.beta1, 0.999), amsgrad=self.amsgrad, eps=self.eps)
-        elif self.optimizer == "RMSProp":
-            opt = torch.optim.RMSprop(self.model.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-        elif self.optimizer == "SGD":
-            opt = torch.optim.SGD(self.model.parameters(), lr=self.lr, momentum=0.9)
-        else:
-            raise NotImplementedError(f"Optimizer {self.optimizer} not understood.")
-        return {"optimizer": opt}
-
-    def optimizer_step(self, *args, **kwargs):
-        """models/mcedm.py:163-168: Lightning's step, then EmaModel.update -- which the fused optimiser's kernel has already done."""
-        super().optimizer_step(*args, **kwargs)
-        if self.ema_model is not None and getattr(self, "_fused_opt", None) is None:
-            self.ema_model.update(self.model)
-
-    def configure_gradient_clipping(self, optimizer, *args, **kwargs):
-        """Lightning calls this between backward and the optimiser's update (configs/trainer/trainer_ddim.yaml:8-9:
-        gradient_clip_val 1.0, norm).  With the fused optimiser the clip is not a pass of its own: the value is handed to the
-        optimiser, whose kernel scales the gradient by min(1, max_norm / (|g| + 1e-6)) like clip_grad_norm_.  Accepts the hook's
-        signatures of pytorch_lightning 1.x (optimizer, optimizer_idx, gradient_clip_val, gradient_clip_algorithm) and 2.x."""
-        val, algo = kwargs.get("gradient_clip_val"), kwargs.get("gradient_clip_algorithm")
-        pos = list(args)
-        if len(pos) == 3:
-            pos = pos[1:]                                   # 1.x: optimizer_idx first
-        if pos and val is None:
-            val = pos[0]
-        if len(pos) > 1 and algo is None:
-            algo = pos[1]
-        algo = getattr(algo, "value", algo)                 # GradClipAlgorithmType enum -> "norm" / "value"
-        raw = getattr(optimizer, "_optimizer", optimizer)   # LightningOptimizer wrapper
-        fused = getattr(self, "_fused_opt", None)
-        if fused is not None and raw is fused and algo in (None, "norm"):
-            fused.max_norm = float(val) if val is not None and val > 0 else None
-            return
-        self.clip_gradients(optimizer, gradient_clip_val=val, gradient_clip_algorithm=algo)
-
-    # ---- data transforms (host-side elementwise, mcedm.py:170-197) --------------------------------------
-    def data_transform(self, h, u):
-        x = torch.cat([self.normalizer_input(h), self.normalizer_target(u)], dim=-1)
-        if self.uniform_dequantization:
-            x = x / 256.0 * 255.0 + torch.rand_like(x) / 256.0
-        if self.gaussian_dequantization:
-            x = x + torch.randn_like(x) * 0.01
-        if self.rescaled:
-            x = 2 * x - 1.0
-        return x
-
-    def inverse_data_transform(self, h, u):
-        if self.rescaled:
-            h, u = (h + 1.0) / 2.0, (u + 1.0) / 2.0
-        if self.normalization == "min_max":
-            h, u = torch.clamp(h, 0.0, 1.0), torch.clamp(u, 0.0, 1.0)
-        return self.normalizer_input(h, inverse=True), self.normalizer_target(u, inverse=True)
 
     def get_loss_weight(self, sigma):
         return (sigma ** 2 + self.sigma_data ** 2) / (sigma * self.sigma_data) ** 2
@@ -301,13 +107,6 @@ class PlMcedm(_Base):
         return cond_in
 
     # ---- preconditioned network (HIP) ------------------------------------------------------------------
-    def _net(self, model):
-        if isinstance(model, EmaModel):
-            return model.ma_model
-        if isinstance(model, nn.parallel.DistributedDataParallel):
-            return model.module
-        return model
-
     def model_precond(self, x_noise, sigma, cond=None, x_self_cond=None, dx=None):
         if x_self_cond is not None or dx is not None:
             raise NotImplementedError("x_self_cond / dx are outside the hot path")
@@ -330,10 +129,7 @@ class PlMcedm(_Base):
             D, F = net.plan.denoise(packed, xt, sigma, cond=cond, ws=net._ws, sigma_data=self.sigma_data, want_F=True)
             if not (w is None or abs(w) < 0.001 or cond is None):          # classifier-free blend, mcedm.py:453-458
                 _, Fu = net.plan.denoise(packed, xt, sigma, cond=None, ws=net._ws, sigma_data=self.sigma_data, want_F=True)
-                F = (w + 1) * F - w * Fu
-                s = sigma.reshape(-1, 1, 1, 1)
-                D = self.sigma_data ** 2 / (s ** 2 + self.sigma_data ** 2) * xt + \
-                    s * self.sigma_data / (s ** 2 + self.sigma_data ** 2).sqrt() * F
+                D, F = self._cfg_blend(xt, sigma, F, Fu, w)
         return D, F
 
     def round_sigma(self, sigma, return_index=False):
@@ -346,16 +142,6 @@ class PlMcedm(_Base):
         return self.model_precond(x_noise, sigma.float(), cond)
 
     # ---- training ------------------------------------------------------------------------------------
-    def _grad_views(self, params):
-        n = sum(p.numel() for p in params)
-        if self._grad_buf is None or self._grad_buf.numel() != n or self._grad_buf.device != params[0].device:
-            self._grad_buf = torch.empty(n, dtype=torch.float32, device=params[0].device)
-        views, off = [], 0
-        for p in params:
-            views.append(self._grad_buf[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        return views
-
     def training_step(self, train_batch, batch_idx):
         h_unnorm, dx, dt, u_unnorm, mask = train_batch
         self.h_ch, self.u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
@@ -367,7 +153,7 @@ class PlMcedm(_Base):
         mask_c = _nchw(mask).to(torch.float32)
         x_noise, sigma = _lib.edm_noise_inputs(x, mask_c, noise, rnd_normal.reshape(-1).contiguous(), self.P_mean, self.P_std)
         torch.rand(1)                                                      # the cond_p draw of mcedm.py:231 (cond_p = 1: never drops)
-        loss = _EdmTrainLoss.apply(self, x, x_noise, sigma, cond_in, mask_c, None, *self.model.parameters())
+        loss = _edm_train_loss(self, x, x_noise, sigma, cond_in, mask_c, None)
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
         return loss
 
@@ -387,9 +173,7 @@ class PlMcedm(_Base):
             raise RuntimeError("cond must carry the known state in its first h_ch+u_ch channels (mcedm.py:590)")
         sd = _lib.sampler_desc(sparams, self.sigma_data, self.sigma_min, self.sigma_max)
         hu_noise = torch.randn_like(hu, dtype=torch.float32)
-        N = sd.timesteps
-        t = _lib.edm_t_steps(sd)
-        churn = any((min(sd.S_churn / N, math.sqrt(2) - 1) if sd.S_min <= t[i] <= sd.S_max else 0) > 0 for i in range(N))
+        N, churn = sd.timesteps, self._churns(sd)
         if self.noise_source not in ("device", "torch"):
             raise RuntimeError(f"noise_source must be 'device' or 'torch', not {self.noise_source!r}")
         dev_noise = churn and self.noise_source == "device"
@@ -404,35 +188,20 @@ class PlMcedm(_Base):
                 rs = torch.tensor([seed], dtype=torch.int64, device=i.device) if seed is not None else None
                 return net.plan.sample(packed, sd, c, m_, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=rs)
             kw = dict(seed=seed) if dev_noise else {}
-            if os.environ.get("MCEDM_HIP_GRAPH", "1") == "0":
-                return eager(cond, hu_mask, hu_noise, step_noise, **kw)
-            # the ~4000 launches of one sampling call replayed from one HIP graph (lib.GraphedSampler); at most two
-            # instances are kept per module (the evaluation loops repeat one call; a ragged last batch is the second),
-            # they borrow this module's sampler workspace, and a failed capture falls back to the eager call
+            # the ~4000 launches of one sampling call replay from one HIP graph (lib.GraphedSampler, see _replay)
             B, _, H, W = hu_noise.shape
             key = (B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), hu_noise.device.index,
                    tuple(getattr(sd, f) for f, _ in sd._fields_))
-            fn = _lib.graphed_or_eager(self._graphs, key, lambda: _lib.GraphedSampler(
+            return self._replay(key, lambda: _lib.GraphedSampler(
                 net.plan, packed, sd, B, H, W, masked=True, has_cond=True, churn=churn, return_last=return_last,
-                ws=self._sample_ws, device_noise=dev_noise), eager)
-            out = fn(cond, hu_mask, hu_noise, step_noise, **kw)
-            return out.clone() if fn is not eager else out
+                ws=self._sample_ws, device_noise=dev_noise), eager, cond, hu_mask, hu_noise, step_noise, **kw)
 
     # ---- evaluation loops (host-side bookkeeping, mcedm.py:283-441) ----------------------------------------
     def get_pde_loss(self, x_denoised, x_gt_unnorm=None, noise_level=None, clamp_loss=True, do_rearrange=True,
                      reduce=True):
         if self.pde_loss is None:
             return None
-        if do_rearrange:
-            x_denoised = x_denoised.permute(0, 2, 3, 1)
-        h = x_denoised[..., 0:self.h_ch].to(torch.float32)
-        u = x_denoised[..., self.h_ch:self.h_ch + self.u_ch].to(torch.float32)
-        x_un = torch.cat(self.inverse_data_transform(h, u), dim=-1)
-        err = self.pde_loss(x_un, x_un if x_gt_unnorm is None else x_gt_unnorm, self.normalizer_input,
-                            self.normalizer_target, return_d=False, calc_prob=False, clamp_loss=clamp_loss)
-        if noise_level is not None:
-            err = err / (noise_level.reshape(-1, 1, 1, 1) + 1.0)
-        return torch.sum(err) if reduce else err
+        return self._joint_pde_loss(x_denoised, x_gt_unnorm, noise_level, clamp_loss, do_rearrange, reduce)
 
     def _unnormalised_mae(self, hu_last, h_unnorm, u_unnorm, mask, loss_dim=None):
         h_un, u_un = self.inverse_data_transform(hu_last[..., 0:self.h_ch], hu_last[..., self.h_ch:self.h_ch + self.u_ch])
