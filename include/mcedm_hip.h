@@ -369,6 +369,11 @@ int mcedm_op_pack_conv_wino(const float* w, int Cout, int Cin, float* wino, void
 int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
                        int resample, int H, int W, const float* wino, const float* bias, const float* res, int res_mode,
                        float* out, int Cout, int B, void* stream);
+/* The Winograd table of the DATA GRADIENT of that convolution (the backward of models/adm_blocks.py:57-82: du = conv3x3 of dy
+ * with the weights transposed over the channels and mirrored over the taps).  w is the FORWARD weight [Cout][Cin][3][3]; wino
+ * holds mcedm_op_conv_wino_packed_floats(Cin, Cout) floats and is used as mcedm_op_conv_wino(dy, .., wino, NULL bias, ..,
+ * Cout = Cin of the forward conv): Cin % 64 == 0 and Cout % 8 == 0 of the forward conv are then required there. */
+int mcedm_op_pack_conv_wino_dgrad(const float* w, int Cout, int Cin, float* wino, void* stream);
 /* sigma-embedding MLP + every block's FiLM rows in one launch (models/adm_blocks.py:192-199 PositionalEmbedding,
  * :367-379 mapping MLP with SiLU, :143,163-165 per-block affine):  emb = silu(W1 silu(W0 pe(labels) + b0) + b1),
  * film[n] = Waff emb[n] + baff.  labels [n]; w0, w1 [ch][ch] (out, in); waff [rows][ch] = the blocks' affine weights

@@ -57,6 +57,11 @@ extern "C" int mcedm_op_pack_conv_wino(const float* w, int Cout, int Cin, float*
   return launch_pack_conv_wino(w, wino, Cout, Cin, 0, (hipStream_t)stream);
 }
 
+// the table backward.hip feeds into conv_wino_kernel for a 3x3 data gradient (plan.hip: the plan's dgrad tables)
+extern "C" int mcedm_op_pack_conv_wino_dgrad(const float* w, int Cout, int Cin, float* wino, void* stream) {
+  return launch_pack_conv_wino(w, wino, Cin, Cout, 1, (hipStream_t)stream);
+}
+
 extern "C" int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
                                   int act, int resample, int H, int W, const float* wino, const float* bias, const float* res,
                                   int res_mode, float* out, int Cout, int B, void* stream) {

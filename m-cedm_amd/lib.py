@@ -1000,9 +1000,11 @@ def _bind_ops():
     lib.mcedm_op_conv_wino_packed_floats.argtypes = [i32, i32]
     lib.mcedm_op_conv_wino_packed_floats.restype = sz
     lib.mcedm_op_pack_conv_wino.argtypes = [vp, i32, i32, vp, vp]
+    lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
-              "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino"):
+              "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
+              "mcedm_op_pack_conv_wino_dgrad"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1013,7 +1015,7 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_wgrad_scratch_floats", "mcedm_op_conv_wgrad", "mcedm_op_gn_bwd", "mcedm_op_attention_bwd",
               "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
-              "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync"]
+              "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1087,6 +1089,17 @@ def set_attn_fused(enable: int = -1) -> None:
     check(lib.mcedm_op_set_attn_fused(int(enable)), "set_attn_fused")
 
 
+def set_conv_debug(buf: Optional[torch.Tensor] = None) -> None:
+    """Per-workgroup debug records of the conv kernels (include/mcedm_hip.h, mcedm_op_set_conv_debug): buf is a device tensor of
+    64-bit words, 16 per blockIdx.x workgroup of the launches that follow; the Winograd kernels put their tiles per workgroup
+    into word 4.  None switches the records off.  The caller keeps buf alive, and large enough, until it has cleared the hook."""
+    lib = _bind_ops()
+    lib.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
+    if buf is not None and (not buf.is_cuda or buf.element_size() != 8 or not buf.is_contiguous() or buf.numel() % 16):
+        raise ValueError("set_conv_debug: buf must be a contiguous device tensor of 64-bit words, 16 per workgroup")
+    check(lib.mcedm_op_set_conv_debug(buf.data_ptr() if buf is not None else None), "set_conv_debug")
+
+
 RS_NONE, RS_UP, RS_DOWN, RS_S2 = 0, 1, 2, 3
 
 
@@ -1128,10 +1141,15 @@ def op_conv(xa, xb, wpk, bias_pk, Cout, k, coef=None, coef_batch=1, act=0, resam
     return out
 
 
-def op_pack_conv_wino(w: torch.Tensor) -> torch.Tensor:
-    """[Cout, Cin, 3, 3] -> the Winograd F(2x2, 3x3) weight table of mcedm_op_conv_wino."""
+def op_pack_conv_wino(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> the Winograd F(2x2, 3x3) weight table of mcedm_op_conv_wino.  dgrad: the table of the data gradient
+    instead (channels transposed, taps mirrored): op_conv_wino(dy, None, table, None, Cin) is then d/dx of the forward conv."""
     lib = _bind_ops()
     Cout, Cin = w.shape[:2]
+    if dgrad:
+        wino = torch.empty(lib.mcedm_op_conv_wino_packed_floats(Cin, Cout), dtype=torch.float32, device=w.device)
+        check(lib.mcedm_op_pack_conv_wino_dgrad(_ptr(w), Cout, Cin, _ptr(wino), _stream()), "op_pack_conv_wino_dgrad")
+        return wino
     wino = torch.empty(lib.mcedm_op_conv_wino_packed_floats(Cout, Cin), dtype=torch.float32, device=w.device)
     check(lib.mcedm_op_pack_conv_wino(_ptr(w), Cout, Cin, _ptr(wino), _stream()), "op_pack_conv_wino")
     return wino
