@@ -18,8 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "edm.hpp"
-#include "plan.hpp"
+#include "heun.hpp"
 #include "prof.hpp"
 
 namespace mcedm {
@@ -72,22 +71,14 @@ struct mcedm_ddpm_plan {
 
 namespace mcedm {
 
-static int dadd(mcedm_ddpm_plan& P, const std::string& name, std::initializer_list<int64_t> shape) {
-  ParamInfo pi;
-  pi.name = name; pi.ndim = (int)shape.size(); pi.numel = 1;
-  int i = 0;
-  for (int64_t s : shape) { pi.shape[i++] = s; pi.numel *= s; }
-  P.params.push_back(pi);
-  return (int)P.params.size() - 1;
-}
 static DNorm dnorm(mcedm_ddpm_plan& P, const std::string& k, int C) {
   DNorm n; n.C = C;
-  n.w = dadd(P, k + ".weight", {C}); n.b = dadd(P, k + ".bias", {C});
+  n.w = add_param(P.params, k + ".weight", {C}); n.b = add_param(P.params, k + ".bias", {C});
   return n;
 }
 static DConv dconv(mcedm_ddpm_plan& P, const std::string& k, int cin, int cout, int ks) {
   DConv c; c.cin = cin; c.cout = cout; c.taps = ks * ks;
-  c.w = dadd(P, k + ".weight", {cout, cin, ks, ks}); c.b = dadd(P, k + ".bias", {cout});
+  c.w = add_param(P.params, k + ".weight", {cout, cin, ks, ks}); c.b = add_param(P.params, k + ".bias", {cout});
   return c;
 }
 // registration order of ResnetBlock.__init__ (ddim_blocks.py:116-142)
@@ -96,7 +87,7 @@ static DRes dres(mcedm_ddpm_plan& P, const std::string& k, int cin, int cout) {
   DRes r; r.key = k; r.cin = cin; r.cout = cout;
   r.n1 = dnorm(P, k + ".norm1", cin);
   r.c1 = dconv(P, k + ".conv1", cin, cout, 3);
-  r.tw = dadd(P, k + ".temb_proj.weight", {cout, temb}); r.tb = dadd(P, k + ".temb_proj.bias", {cout});
+  r.tw = add_param(P.params, k + ".temb_proj.weight", {cout, temb}); r.tb = add_param(P.params, k + ".temb_proj.bias", {cout});
   r.n2 = dnorm(P, k + ".norm2", cout);
   r.c2 = dconv(P, k + ".conv2", cout, cout, 3);
   if (cin != cout) { r.has_sc = true; r.sc = dconv(P, k + ".nin_shortcut", cin, cout, 1); }
@@ -109,32 +100,24 @@ static DAttn dattn(mcedm_ddpm_plan& P, const std::string& k, int C) {
   a.n = dnorm(P, k + ".norm", C);
   const char* names[3] = {"q", "k", "v"};
   for (int i = 0; i < 3; ++i) {
-    a.qw[i] = dadd(P, k + "." + names[i] + ".weight", {C, C, 1, 1});
-    a.qb[i] = dadd(P, k + "." + names[i] + ".bias", {C});
+    a.qw[i] = add_param(P.params, k + "." + names[i] + ".weight", {C, C, 1, 1});
+    a.qb[i] = add_param(P.params, k + "." + names[i] + ".bias", {C});
   }
   a.qkv.cin = C; a.qkv.cout = 3 * C; a.qkv.taps = 1;
   a.proj = dconv(P, k + ".proj_out", C, C, 1);
   return a;
 }
-static bool dlist_has(const int32_t* v, int n, int x) {
-  for (int i = 0; i < n; ++i) if (v[i] == x) return true;
-  return false;
-}
-struct DTaker {
-  size_t cur = 0;
-  size_t take(size_t nfloats) { size_t o = cur; cur += align_up(nfloats, 64); return o; }
-};
-static void dplace(DTaker& t, DConv& c) {
+static void dplace(Taker& t, DConv& c) {
   c.wpk = t.take(conv_packed_floats(c.cout, c.cin, c.taps));
   c.bias = t.take((size_t)(c.cout + 31) / 32 * 32);
   if (c.taps == 9 && c.cout % 64 == 0 && c.cin % 8 == 0) c.wino = t.take(conv_wino_packed_floats(c.cout, c.cin));
 }
-static void dplace(DTaker& t, DNorm& n) { n.gamma = t.take(n.C); n.beta = t.take(n.C); }
-static void dplace(DTaker& t, DRes& r) {
+static void dplace(Taker& t, DNorm& n) { n.gamma = t.take(n.C); n.beta = t.take(n.C); }
+static void dplace(Taker& t, DRes& r) {
   dplace(t, r.n1); dplace(t, r.c1); dplace(t, r.n2); dplace(t, r.c2);
   if (r.has_sc) dplace(t, r.sc);
 }
-static void dplace(DTaker& t, DAttn& a) {
+static void dplace(Taker& t, DAttn& a) {
   dplace(t, a.n); dplace(t, a.qkv); dplace(t, a.proj);
   a.qkv_src = t.take((size_t)3 * a.C * a.C);
 }
@@ -157,8 +140,8 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
   const int ch = d->ch, temb = 4 * ch, L = d->n_levels;
   P.in_total = d->in_channels * (d->self_cond ? 2 : 1);
   // registration order of Model.__init__ (ddim_blocks.py:252-362)
-  P.d0w = dadd(P, "temb.dense.0.weight", {temb, ch}); P.d0b = dadd(P, "temb.dense.0.bias", {temb});
-  P.d1w = dadd(P, "temb.dense.1.weight", {temb, temb}); P.d1b = dadd(P, "temb.dense.1.bias", {temb});
+  P.d0w = add_param(P.params, "temb.dense.0.weight", {temb, ch}); P.d0b = add_param(P.params, "temb.dense.0.bias", {temb});
+  P.d1w = add_param(P.params, "temb.dense.1.weight", {temb, temb}); P.d1b = add_param(P.params, "temb.dense.1.bias", {temb});
   P.conv_in = dconv(P, "conv_in", P.in_total, ch, 3);
   int res = d->resolution, block_in = ch;
   auto in_mult = [&](int l) { return l == 0 ? 1 : d->ch_mult[l - 1]; };
@@ -172,7 +155,7 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
       lv.blocks.push_back(dres(P, k + ".block." + std::to_string(j), block_in, block_out));
       block_in = block_out;
     }
-    if (dlist_has(d->attn_resolutions, d->n_attn_resolutions, res))
+    if (in_list(d->attn_resolutions, d->n_attn_resolutions, res))
       for (int j = 0; j < d->num_res_blocks; ++j) lv.attns.push_back(dattn(P, k + ".attn." + std::to_string(j), block_in));
     if (l != L - 1) { lv.has_rs = true; lv.rs = dconv(P, k + ".downsample.conv", block_in, block_in, 3); res /= 2; }
   }
@@ -195,7 +178,7 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
       lv.blocks.push_back(dres(P, k + ".block." + std::to_string(j), block_in + skip_in, block_out));
       block_in = block_out;
     }
-    if (dlist_has(d->attn_resolutions, d->n_attn_resolutions, res))
+    if (in_list(d->attn_resolutions, d->n_attn_resolutions, res))
       for (int j = 0; j < d->num_res_blocks + 1; ++j) lv.attns.push_back(dattn(P, k + ".attn." + std::to_string(j), block_in));
     if (l != 0) { lv.has_rs = true; lv.rs = dconv(P, k + ".upsample.conv", block_in, block_in, 3); res *= 2; }
     up_params[l] = P.params;
@@ -235,7 +218,7 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
     return MCEDM_ERR_UNSUPPORTED;
   }
 
-  DTaker t;
+  Taker t;
   P.freqs = t.take(ch / 2);
   P.w0 = t.take((size_t)temb * ch); P.b0 = t.take(temb);
   P.w1 = t.take((size_t)temb * temb); P.b1 = t.take(temb);
@@ -255,29 +238,16 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
 }
 
 extern "C" int mcedm_ddpm_plan_set_variant(mcedm_ddpm_plan* plan, int which, int value) {
-  MCEDM_REQUIRE(plan, "ddpm_plan_set_variant: null plan");
-  MCEDM_REQUIRE(which >= 0 && which < KV_COUNT, "ddpm_plan_set_variant: unknown switch %d", which);
-  MCEDM_REQUIRE(value >= -1 && value <= 1, "ddpm_plan_set_variant: value must be -1 (process default), 0 or 1");
-  plan->variants.v[which] = value;
-  return MCEDM_OK;
+  return plan_set_variant(plan, "ddpm_plan_set_variant", which, value);
 }
 extern "C" void mcedm_ddpm_plan_destroy(mcedm_ddpm_plan* plan) { delete plan; }
-extern "C" int mcedm_ddpm_param_count(const mcedm_ddpm_plan* plan) { return plan ? (int)plan->params.size() : MCEDM_ERR_INVALID; }
+extern "C" int mcedm_ddpm_param_count(const mcedm_ddpm_plan* plan) { return plan_param_count(plan); }
 extern "C" int mcedm_ddpm_param_info(const mcedm_ddpm_plan* plan, int index, const char** name, int64_t* numel, int32_t* ndim,
                                      int64_t shape[4]) {
-  MCEDM_REQUIRE(plan && index >= 0 && index < (int)plan->params.size(), "ddpm_param_info: index %d out of range", index);
-  const ParamInfo& p = plan->params[index];
-  if (name) *name = p.name.c_str();
-  if (numel) *numel = p.numel;
-  if (ndim) *ndim = p.ndim;
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
-  return MCEDM_OK;
+  return plan_param_info(plan, "ddpm_param_info", index, name, numel, ndim, shape);
 }
 extern "C" int mcedm_ddpm_packed_bytes(const mcedm_ddpm_plan* plan, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "ddpm_packed_bytes: null argument");
-  *bytes = plan->packed_floats * sizeof(float);
-  return MCEDM_OK;
+  return plan_packed_bytes(plan, "ddpm_packed_bytes", bytes);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -753,13 +723,11 @@ extern "C" int mcedm_ddpm_denoise(const mcedm_ddpm_plan* plan, const void* packe
 }
 
 namespace mcedm {
-struct RBufs { size_t x, xn, d, x32, D, mask, total; };
+struct RBufs : HeunBufs { size_t mask; };
 static RBufs rbufs(const mcedm_ddpm_plan& P, int B) {
-  RBufs r; size_t cur = 0;
-  auto take = [&](size_t bytes) { size_t o = cur; cur += align_up(bytes, 256); return o; };
   const size_t n = (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
-  r.x = take(n * 8); r.xn = take(n * 8); r.d = take(n * 8); r.x32 = take(n * 4); r.D = take(n * 4); r.mask = take(n * 4);
-  r.total = cur;
+  RBufs r{heun_bufs(n), 0};
+  r.mask = heun_take(r, n * 4);
   return r;
 }
 // hu_mask: 1 = known: rows [0, n_time_h) of the h channels and [0, n_time_u) of the u channels (ddim.py:970-972)
@@ -778,11 +746,9 @@ __global__ void repaint_mask_kernel(float* __restrict__ m, int C, int H, int W, 
 extern "C" int mcedm_repaint_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && bytes, "repaint_workspace_bytes: null argument");
-  size_t u = 0;
-  int rc = mcedm_ddpm_workspace_bytes(plan, B, &u);
-  if (rc) return rc;
-  *bytes = rbufs(*plan, B).total + u;
-  return MCEDM_OK;
+  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
+  if (rc == MCEDM_OK) *bytes += rbufs(*plan, B).total;
+  return rc;
 }
 
 extern "C" int mcedm_repaint_schedule(const mcedm_repaint_desc* sp, double* t_steps) {
@@ -804,8 +770,87 @@ namespace mcedm {
 static int repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_repaint_desc* sp, const float* hu,
                         const float* init_noise, const double* step_noise, const double* repeat_noise,
                         const unsigned long long* rng_seed, double* out, int return_last, void* workspace,
-                        size_t workspace_bytes, int B, void* stream);
+                        size_t workspace_bytes, int B, void* stream) {
+  MCEDM_REQUIRE(plan && packed && sp && hu && init_noise && out && workspace, "repaint_sample: null argument");
+  const mcedm_ddpm_plan& P = *plan;
+  int rc;
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "repaint_sample: in_channels != out_channels");
+  MCEDM_REQUIRE(sp->edm_steps && sp->alphas_cumprod_ext && sp->num_diffusion_timesteps >= 2, "repaint_sample: missing schedule tables");
+  MCEDM_REQUIRE(sp->timesteps >= 2 && sp->timesteps <= 4096 && sp->n_repeat >= 1, "repaint_sample: timesteps=%d n_repeat=%d out of range", sp->timesteps, sp->n_repeat);
+  MCEDM_REQUIRE(sp->h_ch >= 0 && sp->u_ch >= 0 && sp->h_ch + sp->u_ch <= P.desc.in_channels, "repaint_sample: h_ch + u_ch exceeds the state channels");
+  MCEDM_REQUIRE(std::fabs(sp->w) < 0.001, "repaint_sample: classifier-free guidance needs a conditional network (cond is None on this path, ddim.py:935)");
+  MCEDM_REQUIRE(sp->n_repeat == 1 || repeat_noise != nullptr || rng_seed != nullptr, "repaint_sample: n_repeat > 1 needs repeat_noise");
+  const int N = sp->timesteps, R = sp->n_repeat, n = sp->num_diffusion_timesteps;
+  const int S = P.desc.resolution;
+  std::vector<double> t(N + 1);
+  if ((rc = mcedm_repaint_schedule(sp, t.data()))) return rc;
+  DHeader hd; size_t act = 0;
+  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
+  const RBufs rb = rbufs(P, B);
+  if ((rc = heun_check_workspace("repaint_sample", workspace_bytes, rb.total + hd.total + act))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  HeunState h = heun_state(workspace, rb, B, P.desc.in_channels, (size_t)S * S, N, return_last, out, s);
+  float* mask = at<float>(workspace, rb.mask);
+  void* uws = at<char>(workspace, rb.total);
+  const size_t total = h.total;
+
+  auto alpha = [&](double tt) -> float {          // compute_alpha(t.long()) (ddim.py:700-704): the SIGMA is the index
+    long idx = (long)tt + 1;
+    if (idx < 0) idx = 0;
+    if (idx > n) idx = n;
+    return sp->alphas_cumprod_ext[idx];
+  };
+  auto round_sigma = [&](double sg) -> double { return (double)sp->edm_steps[nearest_step(sp->edm_steps, n, (float)sg)]; };
+  auto denoise = [&](double sg, bool) -> int {    // get_denoised at a scalar sigma: c_noise = n - 1 - index(sigma)
+    const float s32 = (float)sg;
+    const float cn = (float)(n - 1 - nearest_step(sp->edm_steps, n, s32));
+    return ddpm_denoise_impl(P, hd, pk, h.x32, s32, cn, h.D, nullptr, uws, B, s);
+  };
+
+  hipLaunchKernelGGL(repaint_mask_kernel, dim3(2048 < (total + 255) / 256 ? 2048 : (unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                     mask, h.C, S, S, sp->h_ch, sp->u_ch, sp->n_time_h, sp->n_time_u, total);
+  MCEDM_LAUNCH_CHECK("repaint_mask_kernel");
+  {
+    const float aT = alpha(t[0]);
+    if ((rc = launch_repaint_init(hu, init_noise, mask, sqrtf(aT), sqrtf(1.0f - aT), t[0], total, h.x, h.x32, s))) return rc;
+  }
+  if ((rc = heun_store_step(h, 0))) return rc;
+  for (int i = 0; i < N; ++i) {
+    const double t_cur = t[i], t_next = t[i + 1];
+    const bool in_range = sp->S_min <= t_cur && t_cur <= sp->S_max;
+    const double gamma = in_range ? std::min(sp->S_churn / N, std::sqrt(2.0) - 1.0) : 0.0;
+    double t_hat = round_sigma(t_cur + gamma * t_cur);
+    {
+      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;          // ddim.py:1004
+      if (c != 0.0) {
+        MCEDM_REQUIRE(rng_seed != nullptr || step_noise != nullptr,
+                      "repaint_sample: step %d adds noise (t_hat > t_cur) but step_noise is NULL", i);
+        if ((rc = heun_churn(h, c, rng_seed ? nullptr : step_noise + (size_t)i * total, rng_seed, (unsigned long long)i * R,
+                             nullptr))) return rc;
+      }
+    }
+    for (int k = 0; k < R; ++k) {
+      // Euler step (ddim.py:1008-1015) and 2nd order correction (:1018-1026); x holds x_hat, then x_next
+      if ((rc = heun_update(h, i, t_hat, t_next, nullptr, denoise))) return rc;
+      // replace the known part with the data noised to t_next (:1028-1031)
+      const float at = alpha(t_next);
+      if ((rc = launch_repaint_known(h.x, hu, init_noise, mask, sqrtf(at), sqrtf(1.0f - at), 0, total, h.x32, s))) return rc;
+      if (k < R - 1) {                                                                   // back up from t_next to a new t_hat (:1033-1037)
+        t_hat = round_sigma(t_next + (std::sqrt(2.0) - 1.0) * t_next);
+        const double c = std::sqrt(t_hat * t_hat - t_next * t_next) * sp->S_noise;
+        if ((rc = heun_churn(h, c, rng_seed ? nullptr : repeat_noise + ((size_t)i * (R - 1) + k) * total, rng_seed,
+                             (unsigned long long)i * R + 1 + k, nullptr))) return rc;
+      }
+    }
+    // :1041-1043
+    if (i == N - 1 && (rc = launch_repaint_known(h.x, hu, init_noise, mask, 0.f, 0.f, 1, total, h.x32, s))) return rc;
+    if ((rc = heun_store_step(h, i + 1))) return rc;
+  }
+  return heun_store_last(h);
 }
+}  // namespace mcedm
+
 extern "C" int mcedm_repaint_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_repaint_desc* sp,
                                     const float* hu, const float* init_noise, const double* step_noise,
                                     const double* repeat_noise, double* out, int return_last, void* workspace,
@@ -827,107 +872,6 @@ extern "C" int mcedm_normal_fill(double* out, size_t n, const uint64_t* rng_seed
   if (n == 0) return MCEDM_OK;
   return launch_normal_fill(out, reinterpret_cast<const unsigned long long*>(rng_seed), draw, n, (hipStream_t)stream);
 }
-
-static int mcedm::repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_repaint_desc* sp, const float* hu,
-                               const float* init_noise, const double* step_noise, const double* repeat_noise,
-                               const unsigned long long* rng_seed, double* out, int return_last, void* workspace,
-                               size_t workspace_bytes, int B, void* stream) {
-  MCEDM_REQUIRE(plan && packed && sp && hu && init_noise && out && workspace, "repaint_sample: null argument");
-  const mcedm_ddpm_plan& P = *plan;
-  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "repaint_sample: in_channels != out_channels");
-  MCEDM_REQUIRE(sp->edm_steps && sp->alphas_cumprod_ext && sp->num_diffusion_timesteps >= 2, "repaint_sample: missing schedule tables");
-  MCEDM_REQUIRE(sp->timesteps >= 2 && sp->timesteps <= 4096 && sp->n_repeat >= 1, "repaint_sample: timesteps=%d n_repeat=%d out of range", sp->timesteps, sp->n_repeat);
-  MCEDM_REQUIRE(sp->h_ch >= 0 && sp->u_ch >= 0 && sp->h_ch + sp->u_ch <= P.desc.in_channels, "repaint_sample: h_ch + u_ch exceeds the state channels");
-  MCEDM_REQUIRE(std::fabs(sp->w) < 0.001, "repaint_sample: classifier-free guidance needs a conditional network (cond is None on this path, ddim.py:935)");
-  MCEDM_REQUIRE(sp->n_repeat == 1 || repeat_noise != nullptr || rng_seed != nullptr, "repaint_sample: n_repeat > 1 needs repeat_noise");
-  const int N = sp->timesteps, R = sp->n_repeat, n = sp->num_diffusion_timesteps;
-  const int S = P.desc.resolution, C = P.desc.in_channels;
-  std::vector<double> t(N + 1);
-  int rc = mcedm_repaint_schedule(sp, t.data());
-  if (rc) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
-  const RBufs rb = rbufs(P, B);
-  if (rb.total + hd.total + act > workspace_bytes) {
-    set_error("repaint_sample: workspace too small (%zu < %zu bytes)", workspace_bytes, rb.total + hd.total + act);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
-  double* x = at<double>(workspace, rb.x);
-  double* xn = at<double>(workspace, rb.xn);
-  double* dcur = at<double>(workspace, rb.d);
-  float* x32 = at<float>(workspace, rb.x32);
-  float* D = at<float>(workspace, rb.D);
-  float* mask = at<float>(workspace, rb.mask);
-  void* uws = at<char>(workspace, rb.total);
-  const size_t hw = (size_t)S * S, total = (size_t)B * C * hw;
-  const int Tout = return_last ? 1 : N + 1;
-
-  auto alpha = [&](double tt) -> float {          // compute_alpha(t.long()) (ddim.py:700-704): the SIGMA is the index
-    long idx = (long)tt + 1;
-    if (idx < 0) idx = 0;
-    if (idx > n) idx = n;
-    return sp->alphas_cumprod_ext[idx];
-  };
-  auto round_sigma = [&](double sg) -> double { return (double)sp->edm_steps[nearest_step(sp->edm_steps, n, (float)sg)]; };
-  auto denoise = [&](double sg) -> int {          // get_denoised at a scalar sigma: c_noise = n - 1 - index(sigma)
-    const float s32 = (float)sg;
-    const float cn = (float)(n - 1 - nearest_step(sp->edm_steps, n, s32));
-    return ddpm_denoise_impl(P, hd, pk, x32, s32, cn, D, nullptr, uws, B, s);
-  };
-
-  hipLaunchKernelGGL(repaint_mask_kernel, dim3(2048 < (total + 255) / 256 ? 2048 : (unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     mask, C, S, S, sp->h_ch, sp->u_ch, sp->n_time_h, sp->n_time_u, total);
-  MCEDM_LAUNCH_CHECK("repaint_mask_kernel");
-  {
-    const float aT = alpha(t[0]);
-    if ((rc = launch_repaint_init(hu, init_noise, mask, sqrtf(aT), sqrtf(1.0f - aT), t[0], total, x, x32, s))) return rc;
-  }
-  if (!return_last && (rc = launch_heun_store(x, C, hw, 0, Tout, total, out, s))) return rc;
-  for (int i = 0; i < N; ++i) {
-    const double t_cur = t[i], t_next = t[i + 1];
-    const bool in_range = sp->S_min <= t_cur && t_cur <= sp->S_max;
-    const double gamma = in_range ? std::min(sp->S_churn / N, std::sqrt(2.0) - 1.0) : 0.0;
-    double t_hat = round_sigma(t_cur + gamma * t_cur);
-    {
-      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;          // ddim.py:1004
-      if (c != 0.0) {
-        if (rng_seed) {
-          if ((rc = launch_heun_churn_rng(x, rng_seed, (unsigned long long)i * R, c, total, x32, s))) return rc;
-        } else {
-          MCEDM_REQUIRE(step_noise != nullptr, "repaint_sample: step %d adds noise (t_hat > t_cur) but step_noise is NULL", i);
-          if ((rc = launch_heun_churn(x, step_noise + (size_t)i * total, nullptr, c, total, x32, s))) return rc;
-        }
-      }
-    }
-    for (int k = 0; k < R; ++k) {
-      // Euler step (ddim.py:1008-1015); x holds x_hat
-      if ((rc = denoise(t_hat))) return rc;
-      if ((rc = launch_heun_euler(x, D, nullptr, t_hat, t_next - t_hat, total, dcur, xn, x32, s))) return rc;
-      if (i < N - 1) {                                                                   // 2nd order correction (:1018-1026)
-        if ((rc = denoise(t_next))) return rc;
-        if ((rc = launch_heun_correct(x, dcur, D, nullptr, t_next, t_next - t_hat, total, xn, x32, s))) return rc;
-      }
-      std::swap(x, xn);                                                                  // x = x_next
-      // replace the known part with the data noised to t_next (:1028-1031)
-      const float at = alpha(t_next);
-      if ((rc = launch_repaint_known(x, hu, init_noise, mask, sqrtf(at), sqrtf(1.0f - at), 0, total, x32, s))) return rc;
-      if (k < R - 1) {                                                                   // back up from t_next to a new t_hat (:1033-1037)
-        t_hat = round_sigma(t_next + (std::sqrt(2.0) - 1.0) * t_next);
-        const double c = std::sqrt(t_hat * t_hat - t_next * t_next) * sp->S_noise;
-        if (rng_seed) rc = launch_heun_churn_rng(x, rng_seed, (unsigned long long)i * R + 1 + k, c, total, x32, s);
-        else rc = launch_heun_churn(x, repeat_noise + ((size_t)i * (R - 1) + k) * total, nullptr, c, total, x32, s);
-        if (rc) return rc;
-      }
-    }
-    if (i == N - 1 && (rc = launch_repaint_known(x, hu, init_noise, mask, 0.f, 0.f, 1, total, x32, s))) return rc;   // :1041-1043
-    if (!return_last && (rc = launch_heun_store(x, C, hw, i + 1, Tout, total, out, s))) return rc;
-  }
-  if (return_last && (rc = launch_heun_store(x, C, hw, 0, 1, total, out, s))) return rc;
-  return MCEDM_OK;
-}
-
 
 // ------------------------------------------------------------------------------------------
 // PlDdim.sample_with_repeat (models/ddim.py:808-913): DDIM steps with RePaint inner loops, fp32 throughout

@@ -1,5 +1,5 @@
 // plan.hip -- the C ABI: plan construction, weight packing, workspace layout, the U-Net forward
-// schedule, EDM denoise and the Heun sampler loop.  Host code only launches the kernels of
+// schedule and EDM denoise (the samplers on top of them: sampler.hip).  Host code only launches the kernels of
 // conv_mfma.hip / norm_emb_attn.hip / edm.hip on the caller's stream; it never allocates device
 // memory and never synchronises.
 #include <algorithm>
@@ -26,31 +26,20 @@ void set_error(const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------
 // plan construction: restates DhariwalUNet.__init__ (models/adm_blocks.py:203-317)
 // ------------------------------------------------------------------------------------------
-static int add_param(mcedm_plan& P, const std::string& name, std::initializer_list<int64_t> shape) {
-  ParamInfo pi;
-  pi.name = name;
-  pi.ndim = (int)shape.size();
-  pi.numel = 1;
-  int i = 0;
-  for (int64_t s : shape) { pi.shape[i++] = s; pi.numel *= s; }
-  P.params.push_back(pi);
-  return (int)P.params.size() - 1;
-}
-
 static NormP make_norm(mcedm_plan& P, const std::string& key, int C) {
   NormP n;
   n.C = C;
   n.groups = std::min(32, C / 4);          // adm_blocks.py:89
-  n.w = add_param(P, key + ".weight", {C});
-  n.b = add_param(P, key + ".bias", {C});
+  n.w = add_param(P.params, key + ".weight", {C});
+  n.b = add_param(P.params, key + ".bias", {C});
   return n;
 }
 
 static ConvP make_conv(mcedm_plan& P, const std::string& key, int cin, int cout, int k, int qkv_heads = 0) {
   ConvP c;
   c.cin = cin; c.cout = cout; c.taps = k * k; c.qkv_heads = qkv_heads;
-  c.w = add_param(P, key + ".weight", {cout, cin, k, k});
-  c.b = add_param(P, key + ".bias", {cout});
+  c.w = add_param(P.params, key + ".weight", {cout, cin, k, k});
+  c.b = add_param(P.params, key + ".bias", {cout});
   return c;
 }
 
@@ -62,8 +51,8 @@ static BlockP make_block(mcedm_plan& P, const std::string& key, int cin, int cou
   b.attn = b.heads > 0;
   b.norm0 = make_norm(P, key + ".norm0", cin);
   b.conv0 = make_conv(P, key + ".conv0", cin, cout, 3);
-  b.aff_w = add_param(P, key + ".affine.weight", {2 * cout, emb});
-  b.aff_b = add_param(P, key + ".affine.bias", {2 * cout});
+  b.aff_w = add_param(P.params, key + ".affine.weight", {2 * cout, emb});
+  b.aff_b = add_param(P.params, key + ".affine.bias", {2 * cout});
   b.norm1 = make_norm(P, key + ".norm1", cout);
   b.conv1 = make_conv(P, key + ".conv1", cout, cout, 3);
   b.skip_kernel = -1;
@@ -78,16 +67,6 @@ static BlockP make_block(mcedm_plan& P, const std::string& key, int cin, int cou
   }
   return b;
 }
-
-static bool in_list(const int32_t* v, int n, int x) {
-  for (int i = 0; i < n; ++i) if (v[i] == x) return true;
-  return false;
-}
-
-struct Taker {
-  size_t cur = 0;
-  size_t take(size_t nfloats) { size_t o = cur; cur += align_up(nfloats, 64); return o; }
-};
 
 static void place_conv(Taker& t, ConvP& c, bool dgrad) {
   c.wpk = t.take(conv_packed_floats(c.cout, c.cin, c.taps));
@@ -107,11 +86,7 @@ using namespace mcedm;
 extern "C" int mcedm_version(void) { return MCEDM_ABI_VERSION; }
 
 extern "C" int mcedm_unet_plan_set_variant(mcedm_plan* plan, int which, int value) {
-  MCEDM_REQUIRE(plan, "plan_set_variant: null plan");
-  MCEDM_REQUIRE(which >= 0 && which < KV_COUNT, "plan_set_variant: unknown switch %d", which);
-  MCEDM_REQUIRE(value >= -1 && value <= 1, "plan_set_variant: value must be -1 (process default), 0 or 1");
-  plan->variants.v[which] = value;
-  return MCEDM_OK;
+  return plan_set_variant(plan, "plan_set_variant", which, value);
 }
 extern "C" const char* mcedm_last_error(void) { return g_err; }
 
@@ -141,10 +116,10 @@ extern "C" int mcedm_unet_plan_create(const mcedm_unet_desc* d, mcedm_plan** out
   auto key = [&](const char* side, int res, const std::string& tail) {
     return std::string(side) + "." + std::to_string(res) + "x" + std::to_string(res) + "_" + tail;
   };
-  P.map0_w = add_param(P, "map_layer0.weight", {ch, ch});
-  P.map0_b = add_param(P, "map_layer0.bias", {ch});
-  P.map1_w = add_param(P, "map_layer1.weight", {ch, ch});
-  P.map1_b = add_param(P, "map_layer1.bias", {ch});
+  P.map0_w = add_param(P.params, "map_layer0.weight", {ch, ch});
+  P.map0_b = add_param(P.params, "map_layer0.bias", {ch});
+  P.map1_w = add_param(P.params, "map_layer1.weight", {ch, ch});
+  P.map1_b = add_param(P.params, "map_layer1.bias", {ch});
   if (d->dx_mode == MCEDM_DX_ENC) {        // registered before self.enc (adm_blocks.py:266-280): state_dict order
     const int c0 = ch * d->ch_mult[0];
     P.dx_enc0 = make_conv(P, "dx_enc.0", d->dx_channels, c0, 3);
@@ -230,24 +205,15 @@ extern "C" int mcedm_unet_plan_create(const mcedm_unet_desc* d, mcedm_plan** out
 
 extern "C" void mcedm_unet_plan_destroy(mcedm_plan* plan) { delete plan; }
 
-extern "C" int mcedm_unet_param_count(const mcedm_plan* plan) { return plan ? (int)plan->params.size() : MCEDM_ERR_INVALID; }
+extern "C" int mcedm_unet_param_count(const mcedm_plan* plan) { return plan_param_count(plan); }
 
 extern "C" int mcedm_unet_param_info(const mcedm_plan* plan, int index, const char** name, int64_t* numel, int32_t* ndim,
                                      int64_t shape[4]) {
-  MCEDM_REQUIRE(plan && index >= 0 && index < (int)plan->params.size(), "param_info: index %d out of range", index);
-  const ParamInfo& p = plan->params[index];
-  if (name) *name = p.name.c_str();
-  if (numel) *numel = p.numel;
-  if (ndim) *ndim = p.ndim;
-  if (shape) for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
-  return MCEDM_OK;
+  return plan_param_info(plan, "param_info", index, name, numel, ndim, shape);
 }
 
 extern "C" int mcedm_unet_packed_bytes(const mcedm_plan* plan, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "packed_bytes: null argument");
-  *bytes = plan->packed_floats * sizeof(float);
-  return MCEDM_OK;
+  return plan_packed_bytes(plan, "packed_bytes", bytes);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -709,9 +675,9 @@ int launch_gelu(const float* v, const float* g, float* out, size_t n, int mode, 
 }
 
 // act = start of the activation region (after the header)
-static int forward_impl(const mcedm_plan& P, const Layout& L, const float* pk, const float* x, const float* dx, const float* cond,
-                        const Coef* coef_in, int coef_batch, const float* noise_labels, int n_noise, float* out,
-                        void* act, int B, int H, int W, hipStream_t s) {
+int forward_impl(const mcedm_plan& P, const Layout& L, const float* pk, const float* x, const float* dx, const float* cond,
+                 const Coef* coef_in, int coef_batch, const float* noise_labels, int n_noise, float* out,
+                 void* act, int B, int H, int W, hipStream_t s) {
   const int ch = P.desc.ch;
   const int dxm = P.desc.dx_mode;
   int rc;
@@ -795,10 +761,10 @@ __global__ void scale_to_coef_kernel(const float* __restrict__ x_scale, int n, i
 }
 
 // D = c_skip x + c_out F(c_in x; ln(sigma)/4; cond) with sigma from the device (n_sigma rows) or from the host
-static int denoise_impl(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x, const float* dx,
-                        const float* sigma_dev, float sigma_host, int use_host, int n_sigma, const float* cond,
-                        float w, float* D_out, float* F_out, void* ws, int B, int H, int W, float sigma_data,
-                        hipStream_t s) {
+int denoise_impl(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x, const float* dx,
+                 const float* sigma_dev, float sigma_host, int use_host, int n_sigma, const float* cond,
+                 float w, float* D_out, float* F_out, void* ws, int B, int H, int W, float sigma_data,
+                 hipStream_t s) {
   int rc;
   float* coefs4 = at<float>(ws, hd.coefs4);
   float* c_noise = at<float>(ws, hd.c_noise);
@@ -897,343 +863,4 @@ extern "C" int mcedm_edm_denoise(const mcedm_plan* plan, const void* packed, con
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   return mcedm_edm_denoise_dx(plan, packed, x, nullptr, sigma, n_sigma, cond, D_out, F_out, workspace, workspace_bytes, B, H, W,
                               training, sigma_data, stream);
-}
-
-// ------------------------------------------------------------------------------------------
-// Heun sampler (models/mcedm.py:570-638)
-// ------------------------------------------------------------------------------------------
-extern "C" int mcedm_edm_t_steps(const mcedm_sampler_desc* sp, double* t) {
-  MCEDM_REQUIRE(sp && t, "t_steps: null argument");
-  MCEDM_REQUIRE(sp->timesteps >= 2, "t_steps: timesteps=%d (the reference divides by timesteps-1)", sp->timesteps);
-  const double smin = std::max(sp->sigma_min, sp->net_sigma_min);   // mcedm.py:579-580
-  const double smax = std::min(sp->sigma_max, sp->net_sigma_max);
-  const int N = sp->timesteps;
-  const double a = std::pow(smax, 1.0 / sp->rho), b = std::pow(smin, 1.0 / sp->rho) - std::pow(smax, 1.0 / sp->rho);
-  for (int i = 0; i < N; ++i) t[i] = std::pow(a + (double)i / (double)(N - 1) * b, sp->rho);
-  t[N] = 0.0;
-  return MCEDM_OK;
-}
-
-namespace mcedm {
-struct SamplerBufs { size_t x, xn, d, x32, D, dx, g, dxin, total; };
-static SamplerBufs sampler_bufs(const mcedm_plan& P, int B, int H, int W) {
-  SamplerBufs s;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) { size_t o = cur; cur += align_up(bytes, 256); return o; };
-  const size_t n = (size_t)B * P.desc.in_channels * H * W;
-  s.x = take(n * 8); s.xn = take(n * 8); s.d = take(n * 8); s.x32 = take(n * 4); s.D = take(n * 4);
-  s.dx = take(n * 4); s.g = take(n * 4);          // PDE guidance: gradient and the Darcy interior scratch
-  s.dxin = take(n * 4);                           // dx_cond: the network's dx input
-  s.total = cur;
-  return s;
-}
-}  // namespace mcedm
-
-extern "C" int mcedm_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "sampler_workspace_bytes: null argument");
-  size_t u = 0;
-  int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, &u);
-  if (rc) return rc;
-  *bytes = sampler_bufs(*plan, B, H, W).total + u;
-  return MCEDM_OK;
-}
-
-namespace mcedm {
-// dx = get_dx_log_prob(h, denoised, guide_dx) of the single-task models (models/ddim.py:641-650 -> get_dx_pde :1424-1450):
-// the residual of x_unnorm = (h from the conditioning, u = the denoised state), differentiated w.r.t. x_unnorm, then the
-// MEAN over the two field gradients (calc_prob=True) -> [B, 1, H, W]
-// (the same call on the current noisy state instead of D is get_dx_input(h, x) with dx_norm == 'prob', ddim.py:601-613)
-static int guidance_dx(const mcedm_plan& P, const mcedm_guidance_desc& g, const float* cond, const float* D, float* dx,
-                       float* scratch, int B, int H, int W, hipStream_t s) {
-  GuideIO io{};
-  const long hw = (long)H * W;
-  io.in[0] = cond; io.in[1] = D; io.gt[0] = cond; io.gt[1] = D;
-  io.in_sb[0] = (long)P.desc.cond_channels * hw; io.in_sb[1] = hw; io.st = W; io.sx = 1;
-  io.out[0] = dx; io.out[1] = nullptr; io.out_sb[0] = hw; io.out_sb[1] = 0; io.out_st = W; io.out_sx = 1;
-  io.sub[0] = g.sub_h; io.sub[1] = g.sub_u; io.div[0] = g.div_h; io.div[1] = g.div_u;
-  io.mean = 1;
-  if (g.system == 1)      // SweFvLoss: half_dt = 0.5 * Tn / n_times, dx = x[1] - x[0] of gen_x, both formed by the caller in fp32
-    return launch_swe_guidance(io, B, H, W, g.half_dt, g.dx, g.div_h * g.div_h, g.div_u * g.div_u, s);
-  MCEDM_REQUIRE(H == W && H > 4, "guidance: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)", H, W);
-  return launch_darcy_guidance(io, scratch, B, H, g.two_dx, /*calc_prob=*/1, s);
-}
-}  // namespace mcedm
-
-static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                            const float* cond, const float* mask, const float* init_noise,
-                            const double* step_noise, double* out, int return_last, void* workspace,
-                            size_t workspace_bytes, int B, int H, int W, const mcedm_guidance_desc* gd, void* stream,
-                            const mcedm_guidance_desc* dxc = nullptr, const uint64_t* rng_seed = nullptr);
-
-extern "C" int mcedm_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                                 const float* cond, const float* mask, const float* init_noise,
-                                 const double* step_noise, double* out, int return_last, void* workspace,
-                                 size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
-                          B, H, W, nullptr, stream);
-}
-
-// The churn noise of every step generated inside the kernel that applies it (Philox4x32-10 keyed by *rng_seed, draw = step
-// index): no [timesteps][B][C][H][W] fp64 tensor (2.1 GB at 50 x 160 x 2 x 128 x 128, the reference's shipped sampler config,
-// configs/diff_sampler/edm_sampler.yaml) and one HIP graph replays with fresh noise after the host bumps the seed.
-extern "C" int mcedm_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                                     const float* cond, const float* mask, const float* init_noise, const uint64_t* rng_seed,
-                                     double* out, int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
-                                     void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
-  return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, nullptr, out, return_last, workspace, workspace_bytes,
-                          B, H, W, nullptr, stream, nullptr, rng_seed);
-}
-
-extern "C" int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                                        const mcedm_guidance_desc* gd, const float* cond, const float* mask,
-                                        const float* init_noise, const double* step_noise, double* out, int return_last,
-                                        void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(gd != nullptr && (gd->system == 1 || gd->system == 2), "heun_sample_guided: guidance system must be 1 (SWE) or 2 (Darcy)");
-  MCEDM_REQUIRE(plan && plan->desc.in_channels == 1 && plan->desc.cond_channels >= 1 && cond != nullptr && mask == nullptr,
-                "heun_sample_guided: PDE guidance is defined for the single-task sampler (state u, conditioning h in cond[:, 0]; "
-                "mask NULL), models/ddim.py:1532-1601; the joint model's hook fails in the reference (models/mcedm.py:500-518)");
-  return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
-                          B, H, W, gd, stream);
-}
-
-extern "C" int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                                        const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
-                                        const float* init_noise, const double* step_noise, double* out, int return_last,
-                                        void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(dxc != nullptr && (dxc->system == 1 || dxc->system == 2), "heun_sample_dxcond: dx system must be 1 (SWE) or 2 (Darcy)");
-  MCEDM_REQUIRE(gd == nullptr || gd->system == 1 || gd->system == 2, "heun_sample_dxcond: guidance system must be 1 (SWE) or 2 (Darcy)");
-  MCEDM_REQUIRE(plan && plan->desc.dx_mode != MCEDM_DX_NONE && plan->desc.dx_channels == 1 && plan->desc.in_channels == 1 &&
-                    plan->desc.cond_channels >= 1 && cond != nullptr,
-                "heun_sample_dxcond: needs a dx_cond plan of the single-task model (state u, conditioning h in cond[:, 0], one dx "
-                "channel), models/ddim.py:1424-1450, 1532-1601");
-  return heun_sample_impl(plan, packed, sp, cond, nullptr, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
-                          B, H, W, gd, stream, dxc);
-}
-
-static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                            const float* cond, const float* mask, const float* init_noise,
-                            const double* step_noise, double* out, int return_last, void* workspace,
-                            size_t workspace_bytes, int B, int H, int W, const mcedm_guidance_desc* gd, void* stream,
-                            const mcedm_guidance_desc* dxc, const uint64_t* rng_seed) {
-  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "heun_sample: null argument");
-  const mcedm_plan& P = *plan;
-  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "heun_sample: in_channels != out_channels");
-  MCEDM_REQUIRE(mask == nullptr || (cond != nullptr && P.desc.cond_channels >= P.desc.in_channels),
-                "heun_sample: with a mask, cond must carry hu_known in its first %d channels", P.desc.in_channels);
-  MCEDM_REQUIRE(sp->timesteps >= 2 && sp->timesteps <= 4096, "heun_sample: timesteps=%d out of range", sp->timesteps);
-  const int N = sp->timesteps;
-  std::vector<double> t(N + 1);
-  int rc = mcedm_edm_t_steps(sp, t.data());
-  if (rc) return rc;
-  std::vector<double> gammas(N);
-  for (int i = 0; i < N; ++i) {
-    const bool in_range = sp->S_min <= t[i] && t[i] <= sp->S_max;                    // mcedm.py:606
-    gammas[i] = in_range ? std::min(sp->S_churn / N, std::sqrt(2.0) - 1.0) : 0.0;
-    MCEDM_REQUIRE(gammas[i] == 0.0 || step_noise != nullptr || rng_seed != nullptr, "heun_sample: S_churn > 0 needs step_noise (or mcedm_heun_sample_rng)");
-  }
-  Layout L;
-  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
-  const Header hd = header_for(P, B, H, W);
-  const SamplerBufs sb = sampler_bufs(P, B, H, W);
-  if (sb.total + hd.total + L.total_bytes > workspace_bytes) {
-    set_error("heun_sample: workspace too small (%zu < %zu bytes)", workspace_bytes, sb.total + hd.total + L.total_bytes);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
-  double* x = at<double>(workspace, sb.x);
-  double* xn = at<double>(workspace, sb.xn);
-  double* dcur = at<double>(workspace, sb.d);
-  float* x32 = at<float>(workspace, sb.x32);
-  float* D = at<float>(workspace, sb.D);
-  void* uws = at<char>(workspace, sb.total);
-  const int C = P.desc.in_channels;
-  const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
-  const int Tout = return_last ? 1 : N + 1;
-  const float w = (float)sp->w;
-  const float sd = (float)sp->sigma_data;
-
-  if ((rc = launch_heun_init(cond, P.desc.cond_channels, C, hw, mask, init_noise, t[0], total, x, x32, s))) return rc;
-  if (!return_last && (rc = launch_heun_store(x, C, hw, 0, Tout, total, out, s))) return rc;
-  for (int i = 0; i < N; ++i) {
-    const double t_cur = t[i], t_next = t[i + 1];
-    const double t_hat = t_cur + gammas[i] * t_cur;                                   // mcedm.py:607
-    if (gammas[i] != 0.0) {
-      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
-      if (step_noise) rc = launch_heun_churn(x, step_noise + (size_t)i * total, mask, c, total, x32, s);
-      else rc = launch_heun_churn_rng(x, reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, c, total, x32, s, mask);
-      if (rc) return rc;
-    }
-    // Euler step (mcedm.py:611-618); dx_cond: dx_in = get_dx_input(h, x_hat) first (ddim.py:1571)
-    float* dxin = nullptr;
-    if (dxc) {
-      dxin = at<float>(workspace, sb.dxin);
-      if ((rc = guidance_dx(P, *dxc, cond, x32, dxin, at<float>(workspace, sb.g), B, H, W, s))) return rc;
-    }
-    if ((rc = denoise_impl(P, L, hd, pk, x32, dxin, nullptr, (float)t_hat, 1, 1, cond, w, D, nullptr, uws, B, H, W, sd, s))) return rc;
-    const float* dxg = nullptr;
-    const float wgt = gd ? (float)gd->weight : 0.f;
-    if (gd) {
-      if ((rc = guidance_dx(P, *gd, cond, D, at<float>(workspace, sb.dx), at<float>(workspace, sb.g), B, H, W, s))) return rc;
-      dxg = at<float>(workspace, sb.dx);
-    }
-    if ((rc = launch_heun_euler(x, D, mask, t_hat, t_next - t_hat, total, dcur, xn, x32, s, dxg, wgt, (float)t_hat))) return rc;
-    // 2nd-order correction (mcedm.py:621-628)
-    if (i < N - 1) {
-      if (dxc && (rc = guidance_dx(P, *dxc, cond, x32, dxin, at<float>(workspace, sb.g), B, H, W, s))) return rc;   // on x_next (ddim.py:1584)
-      if ((rc = denoise_impl(P, L, hd, pk, x32, dxin, nullptr, (float)t_next, 1, 1, cond, w, D, nullptr, uws, B, H, W, sd, s))) return rc;
-      if (gd && (rc = guidance_dx(P, *gd, cond, D, at<float>(workspace, sb.dx), at<float>(workspace, sb.g), B, H, W, s))) return rc;
-      if ((rc = launch_heun_correct(x, dcur, D, mask, t_next, t_next - t_hat, total, xn, x32, s, dxg, wgt, (float)t_hat))) return rc;
-    }
-    std::swap(x, xn);
-    if (!return_last && (rc = launch_heun_store(x, C, hw, i + 1, Tout, total, out, s))) return rc;
-  }
-  if (return_last && (rc = launch_heun_store(x, C, hw, 0, 1, total, out, s))) return rc;
-  return MCEDM_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------
-// VP-preconditioned Heun sampler of an epsilon network (PlCondDdim.sample_edm, models/ddim.py:1532-1601)
-// ------------------------------------------------------------------------------------------
-namespace mcedm {
-struct VpBufs { size_t x, xn, d, x32, D, condp, total; };
-static VpBufs vp_bufs(const mcedm_plan& P, int B, int H, int W) {
-  VpBufs v;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) { size_t o = cur; cur += align_up(bytes, 256); return o; };
-  const size_t n = (size_t)B * P.desc.in_channels * H * W;
-  v.x = take(n * 8); v.xn = take(n * 8); v.d = take(n * 8); v.x32 = take(n * 4); v.D = take(n * 4);
-  v.condp = take((size_t)B * P.desc.cond_channels * H * W * 4);      // cond' = cat(cond, zeros) of a self-conditioning plan
-  v.total = cur;
-  return v;
-}
-
-// get_denoised (models/ddim.py:915-947) at one noise level: D = x + (-sigma) F(c_in cat(cond', x), c_noise)
-static int vp_denoise(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x32, const float* condp,
-                      double sigma_d, float c_noise, double w, float* D, void* ws, int B, int H, int W, hipStream_t s) {
-  int rc;
-  const float sigma = (float)sigma_d;                                   // t.to(torch.float32)
-  const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                // 1 / (sigma ** 2 + 1).sqrt(), fp32
-  Coef* coef_in = at<Coef>(ws, hd.coef_in);
-  float* label = at<float>(ws, hd.c_noise);
-  float* F = at<float>(ws, hd.F);
-  void* act = at<char>(ws, hd.total);
-  if ((rc = launch_vp_prepare(c_in, P.desc.cond_channels + P.desc.in_channels, c_noise, coef_in, label, s))) return rc;
-  if ((rc = forward_impl(P, L, pk, x32, nullptr, condp, coef_in, 0, label, 1, F, act, B, H, W, s))) return rc;
-  const float* Fu = nullptr;
-  if (std::fabs(w) >= 0.001 && condp != nullptr) {                     // :938-942, the second evaluation without cond
-    float* Fub = at<float>(ws, hd.Fu);
-    if ((rc = forward_impl(P, L, pk, x32, nullptr, nullptr, coef_in, 0, label, 1, Fub, act, B, H, W, s))) return rc;
-    Fu = Fub;
-  }
-  return launch_vp_cfg_finish(x32, F, Fu, w, sigma, (size_t)B * P.desc.out_channels * H * W, D, s);
-}
-}  // namespace mcedm
-
-extern "C" int mcedm_vp_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "vp_sampler_workspace_bytes: null argument");
-  size_t u = 0;
-  int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, &u);
-  if (rc) return rc;
-  *bytes = vp_bufs(*plan, B, H, W).total + u;
-  return MCEDM_OK;
-}
-
-static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
-                          const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
-                          int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "vp_heun_sample: null argument");
-  MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "vp_heun_sample: null schedule array");
-  const mcedm_plan& P = *plan;
-  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "vp_heun_sample: in_channels != out_channels");
-  MCEDM_REQUIRE(P.desc.dx_mode == MCEDM_DX_NONE, "vp_heun_sample: dx_cond plans are not supported");
-  MCEDM_REQUIRE(sp->cond_channels >= 0 && sp->cond_channels <= P.desc.cond_channels,
-                "vp_heun_sample: cond_channels %d outside [0, %d]", sp->cond_channels, P.desc.cond_channels);
-  MCEDM_REQUIRE(cond == nullptr || sp->cond_channels > 0, "vp_heun_sample: cond given with cond_channels 0");
-  MCEDM_REQUIRE(sp->timesteps >= 1 && sp->timesteps <= 4096, "vp_heun_sample: timesteps=%d out of range", sp->timesteps);
-  const int N = sp->timesteps;
-  const double* t = sp->t_steps;
-  for (int i = 0; i < N; ++i) {
-    MCEDM_REQUIRE(sp->t_hat[i] >= t[i] && t[i] > 0.0, "vp_heun_sample: step %d: t_hat %g < t_cur %g or t_cur <= 0", i, sp->t_hat[i], t[i]);
-    MCEDM_REQUIRE(sp->t_hat[i] == t[i] || step_noise != nullptr || rng_seed != nullptr,
-                  "vp_heun_sample: step %d churns (t_hat > t_cur) and needs step_noise (or mcedm_vp_heun_sample_rng)", i);
-  }
-  int rc;
-  Layout L;
-  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
-  const Header hd = header_for(P, B, H, W);
-  const VpBufs vb = vp_bufs(P, B, H, W);
-  if (vb.total + hd.total + L.total_bytes > workspace_bytes) {
-    set_error("vp_heun_sample: workspace too small (%zu < %zu bytes)", workspace_bytes, vb.total + hd.total + L.total_bytes);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
-  double* x = at<double>(workspace, vb.x);
-  double* xn = at<double>(workspace, vb.xn);
-  double* dcur = at<double>(workspace, vb.d);
-  float* x32 = at<float>(workspace, vb.x32);
-  float* D = at<float>(workspace, vb.D);
-  void* uws = at<char>(workspace, vb.total);
-  const int C = P.desc.in_channels;
-  const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
-  const int Tout = return_last ? 1 : N + 1;
-  // cond' once per call: cond in its channels, zeros in the self-conditioning ones (get_self_cond_edm returns None)
-  const float* condp = cond;
-  if (cond && sp->cond_channels < P.desc.cond_channels) {
-    float* st = at<float>(workspace, vb.condp);
-    if ((rc = mcedm_eps_self_cond(nullptr, nullptr, nullptr, nullptr, nullptr, 0, cond, sp->cond_channels,
-                                  P.desc.cond_channels - sp->cond_channels, B, H, W, st, stream))) return rc;
-    condp = st;
-  }
-  // x = u_noise.to(float64) * t_steps[0]   (:1556)
-  if ((rc = launch_heun_init(nullptr, 0, C, hw, nullptr, init_noise, t[0], total, x, x32, s))) return rc;
-  if (!return_last && (rc = launch_heun_store(x, C, hw, 0, Tout, total, out, s))) return rc;
-  for (int i = 0; i < N; ++i) {
-    const double t_cur = t[i], t_next = t[i + 1], t_hat = sp->t_hat[i];
-    if (t_hat != t_cur) {                 // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) * S_noise * eps (:1567); + 0 * eps otherwise
-      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
-      if (step_noise) rc = launch_heun_churn(x, step_noise + (size_t)i * total, nullptr, c, total, x32, s);
-      else rc = launch_heun_churn_rng(x, reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, c, total, x32, s);
-      if (rc) return rc;
-    }
-    // Euler step (:1570-1580)
-    if ((rc = vp_denoise(P, L, hd, pk, x32, condp, t_hat, sp->c_noise[2 * i], sp->w, D, uws, B, H, W, s))) return rc;
-    if ((rc = launch_heun_euler(x, D, nullptr, t_hat, t_next - t_hat, total, dcur, xn, x32, s))) return rc;
-    // 2nd-order correction (:1583-1593)
-    if (i < N - 1) {
-      if ((rc = vp_denoise(P, L, hd, pk, x32, condp, t_next, sp->c_noise[2 * i + 1], sp->w, D, uws, B, H, W, s))) return rc;
-      if ((rc = launch_heun_correct(x, dcur, D, nullptr, t_next, t_next - t_hat, total, xn, x32, s))) return rc;
-    }
-    std::swap(x, xn);
-    if (!return_last && (rc = launch_heun_store(x, C, hw, i + 1, Tout, total, out, s))) return rc;
-  }
-  if (return_last && (rc = launch_heun_store(x, C, hw, 0, 1, total, out, s))) return rc;
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
-                                    const float* init_noise, const double* step_noise, double* out, int return_last,
-                                    void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  return vp_sample_impl(plan, packed, sp, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B, H,
-                        W, stream);
-}
-
-extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
-                                        const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
-                                        int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
-                                        void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(rng_seed != nullptr, "vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
-  return vp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, H,
-                        W, stream);
 }

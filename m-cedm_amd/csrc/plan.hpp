@@ -2,6 +2,7 @@
 // layout) and of the activation layout inside the caller's workspace.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -48,6 +49,63 @@ struct ParamInfo {
   int64_t shape[4] = {1, 1, 1, 1};
   int64_t numel = 0;
 };
+
+// the parameter table of a plan, in state_dict order: append one entry, return its index
+static inline int add_param(std::vector<ParamInfo>& params, const std::string& name, std::initializer_list<int64_t> shape) {
+  ParamInfo pi;
+  pi.name = name;
+  pi.ndim = (int)shape.size();
+  pi.numel = 1;
+  int i = 0;
+  for (int64_t s : shape) { pi.shape[i++] = s; pi.numel *= s; }
+  params.push_back(pi);
+  return (int)params.size() - 1;
+}
+
+static inline bool in_list(const int32_t* v, int n, int x) {
+  for (int i = 0; i < n; ++i) if (v[i] == x) return true;
+  return false;
+}
+
+// cursor over the packed-weight buffer (float offsets, 64-float granules)
+struct Taker {
+  size_t cur = 0;
+  size_t take(size_t nfloats) { size_t o = cur; cur += align_up(nfloats, 64); return o; }
+};
+
+// The accessors both plan types export (mcedm_unet_* / mcedm_ddpm_*): PlanT has params, packed_floats and variants;
+// `who` is the entry's name in its error texts.
+template <class PlanT>
+int plan_param_count(const PlanT* plan) { return plan ? (int)plan->params.size() : MCEDM_ERR_INVALID; }
+
+template <class PlanT>
+int plan_param_info(const PlanT* plan, const char* who, int index, const char** name, int64_t* numel, int32_t* ndim,
+                    int64_t shape[4]) {
+  MCEDM_REQUIRE(plan && index >= 0 && index < (int)plan->params.size(), "%s: index %d out of range", who, index);
+  const ParamInfo& p = plan->params[index];
+  if (name) *name = p.name.c_str();
+  if (numel) *numel = p.numel;
+  if (ndim) *ndim = p.ndim;
+  if (shape) for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
+  return MCEDM_OK;
+}
+
+template <class PlanT>
+int plan_packed_bytes(const PlanT* plan, const char* who, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "%s: null argument", who);
+  *bytes = plan->packed_floats * sizeof(float);
+  return MCEDM_OK;
+}
+
+template <class PlanT>
+int plan_set_variant(PlanT* plan, const char* who, int which, int value) {
+  MCEDM_REQUIRE(plan, "%s: null plan", who);
+  MCEDM_REQUIRE(which >= 0 && which < KV_COUNT, "%s: unknown switch %d", who, which);
+  MCEDM_REQUIRE(value >= -1 && value <= 1, "%s: value must be -1 (process default), 0 or 1", who);
+  plan->variants.v[which] = value;
+  return MCEDM_OK;
+}
 
 struct ConvP {   // one Conv2d with weights
   int w = -1, b = -1;          // parameter indices
@@ -136,6 +194,16 @@ Header header_for(const mcedm_plan& P, int B, int H, int W);
 
 template <class T>
 static inline T* at(void* ws, size_t off) { return reinterpret_cast<T*>(reinterpret_cast<char*>(ws) + off); }
+
+// plan.hip's forward and EDM denoise, as the samplers (sampler.hip) call them.  act = start of the activation region
+// (after the header); ws = start of the header.
+int forward_impl(const mcedm_plan& P, const Layout& L, const float* pk, const float* x, const float* dx, const float* cond,
+                 const Coef* coef_in, int coef_batch, const float* noise_labels, int n_noise, float* out,
+                 void* act, int B, int H, int W, hipStream_t s);
+int denoise_impl(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x, const float* dx,
+                 const float* sigma_dev, float sigma_host, int use_host, int n_sigma, const float* cond,
+                 float w, float* D_out, float* F_out, void* ws, int B, int H, int W, float sigma_data,
+                 hipStream_t s);
 
 // bytes the backward needs behind the training-mode activations (gradient buffers + scratch)
 size_t backward_scratch_bytes(const mcedm_plan& P, const Layout& L, int B, int H, int W);

@@ -1,0 +1,296 @@
+// sampler.hip -- the Heun samplers of the ADM U-Net: the EDM sampler (with mask, PDE guidance and dx_cond) and the
+// VP-preconditioned sampler of an epsilon network.  Host code only: the schedules (fp64) and the order of the launches;
+// the loop itself is heun.hpp, the network plan.hip.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "heun.hpp"
+
+using namespace mcedm;
+
+// ------------------------------------------------------------------------------------------
+// Heun sampler (models/mcedm.py:570-638)
+// ------------------------------------------------------------------------------------------
+extern "C" int mcedm_edm_t_steps(const mcedm_sampler_desc* sp, double* t) {
+  MCEDM_REQUIRE(sp && t, "t_steps: null argument");
+  MCEDM_REQUIRE(sp->timesteps >= 2, "t_steps: timesteps=%d (the reference divides by timesteps-1)", sp->timesteps);
+  const double smin = std::max(sp->sigma_min, sp->net_sigma_min);   // mcedm.py:579-580
+  const double smax = std::min(sp->sigma_max, sp->net_sigma_max);
+  const int N = sp->timesteps;
+  const double a = std::pow(smax, 1.0 / sp->rho), b = std::pow(smin, 1.0 / sp->rho) - std::pow(smax, 1.0 / sp->rho);
+  for (int i = 0; i < N; ++i) t[i] = std::pow(a + (double)i / (double)(N - 1) * b, sp->rho);
+  t[N] = 0.0;
+  return MCEDM_OK;
+}
+
+namespace mcedm {
+struct SamplerBufs : HeunBufs { size_t dx, g, dxin; };
+static SamplerBufs sampler_bufs(const mcedm_plan& P, int B, int H, int W) {
+  const size_t n = (size_t)B * P.desc.in_channels * H * W;
+  SamplerBufs s{heun_bufs(n), 0, 0, 0};
+  s.dx = heun_take(s, n * 4); s.g = heun_take(s, n * 4);          // PDE guidance: gradient and the Darcy interior scratch
+  s.dxin = heun_take(s, n * 4);                                   // dx_cond: the network's dx input
+  return s;
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "sampler_workspace_bytes: null argument");
+  const int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, bytes);
+  if (rc == MCEDM_OK) *bytes += sampler_bufs(*plan, B, H, W).total;
+  return rc;
+}
+
+namespace mcedm {
+// dx = get_dx_log_prob(h, denoised, guide_dx) of the single-task models (models/ddim.py:641-650 -> get_dx_pde :1424-1450):
+// the residual of x_unnorm = (h from the conditioning, u = the denoised state), differentiated w.r.t. x_unnorm, then the
+// MEAN over the two field gradients (calc_prob=True) -> [B, 1, H, W]
+// (the same call on the current noisy state instead of D is get_dx_input(h, x) with dx_norm == 'prob', ddim.py:601-613)
+static int guidance_dx(const mcedm_plan& P, const mcedm_guidance_desc& g, const float* cond, const float* D, float* dx,
+                       float* scratch, int B, int H, int W, hipStream_t s) {
+  GuideIO io{};
+  const long hw = (long)H * W;
+  io.in[0] = cond; io.in[1] = D; io.gt[0] = cond; io.gt[1] = D;
+  io.in_sb[0] = (long)P.desc.cond_channels * hw; io.in_sb[1] = hw; io.st = W; io.sx = 1;
+  io.out[0] = dx; io.out[1] = nullptr; io.out_sb[0] = hw; io.out_sb[1] = 0; io.out_st = W; io.out_sx = 1;
+  io.sub[0] = g.sub_h; io.sub[1] = g.sub_u; io.div[0] = g.div_h; io.div[1] = g.div_u;
+  io.mean = 1;
+  if (g.system == 1)      // SweFvLoss: half_dt = 0.5 * Tn / n_times, dx = x[1] - x[0] of gen_x, both formed by the caller in fp32
+    return launch_swe_guidance(io, B, H, W, g.half_dt, g.dx, g.div_h * g.div_h, g.div_u * g.div_u, s);
+  MCEDM_REQUIRE(H == W && H > 4, "guidance: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)", H, W);
+  return launch_darcy_guidance(io, scratch, B, H, g.two_dx, /*calc_prob=*/1, s);
+}
+}  // namespace mcedm
+
+// gd: PDE guidance on the denoised state; dxc: the residual whose gradient at the current state is the network's dx input;
+// rng_seed: the churn draws come from the device generator instead of step_noise
+static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                            const float* cond, const float* mask, const float* init_noise,
+                            const double* step_noise, double* out, int return_last, void* workspace,
+                            size_t workspace_bytes, int B, int H, int W, const mcedm_guidance_desc* gd, void* stream,
+                            const mcedm_guidance_desc* dxc, const uint64_t* rng_seed) {
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "heun_sample: null argument");
+  const mcedm_plan& P = *plan;
+  int rc;
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "heun_sample: in_channels != out_channels");
+  MCEDM_REQUIRE(mask == nullptr || (cond != nullptr && P.desc.cond_channels >= P.desc.in_channels),
+                "heun_sample: with a mask, cond must carry hu_known in its first %d channels", P.desc.in_channels);
+  MCEDM_REQUIRE(sp->timesteps >= 2 && sp->timesteps <= 4096, "heun_sample: timesteps=%d out of range", sp->timesteps);
+  const int N = sp->timesteps;
+  std::vector<double> t(N + 1);
+  if ((rc = mcedm_edm_t_steps(sp, t.data()))) return rc;
+  std::vector<double> gammas(N);
+  for (int i = 0; i < N; ++i) {
+    const bool in_range = sp->S_min <= t[i] && t[i] <= sp->S_max;                    // mcedm.py:606
+    gammas[i] = in_range ? std::min(sp->S_churn / N, std::sqrt(2.0) - 1.0) : 0.0;
+    MCEDM_REQUIRE(gammas[i] == 0.0 || step_noise != nullptr || rng_seed != nullptr, "heun_sample: S_churn > 0 needs step_noise (or mcedm_heun_sample_rng)");
+  }
+  Layout L;
+  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
+  const Header hd = header_for(P, B, H, W);
+  const SamplerBufs sb = sampler_bufs(P, B, H, W);
+  if ((rc = heun_check_workspace("heun_sample", workspace_bytes, sb.total + hd.total + L.total_bytes))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  HeunState h = heun_state(workspace, sb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, s);
+  void* uws = at<char>(workspace, sb.total);
+  const float w = (float)sp->w;
+  const float sd = (float)sp->sigma_data;
+  float* gscratch = at<float>(workspace, sb.g);
+  float* dxin = dxc ? at<float>(workspace, sb.dxin) : nullptr;
+  float* dxg = gd ? at<float>(workspace, sb.dx) : nullptr;
+  const float wgt = gd ? (float)gd->weight : 0.f;
+  // D(x32; sigma), mcedm.py:611-618 / 621-628; dx_cond: dx_in = get_dx_input(h, x32) first (ddim.py:1571, 1584); guidance:
+  // its gradient at D afterwards
+  auto denoise = [&](double sigma, bool) -> int {
+    int e = dxc ? guidance_dx(P, *dxc, cond, h.x32, dxin, gscratch, B, H, W, s) : MCEDM_OK;
+    if (e) return e;
+    e = denoise_impl(P, L, hd, pk, h.x32, dxin, nullptr, (float)sigma, 1, 1, cond, w, h.D, nullptr, uws, B, H, W, sd, s);
+    if (e) return e;
+    return gd ? guidance_dx(P, *gd, cond, h.D, dxg, gscratch, B, H, W, s) : MCEDM_OK;
+  };
+
+  if ((rc = launch_heun_init(cond, P.desc.cond_channels, h.C, h.hw, mask, init_noise, t[0], h.total, h.x, h.x32, s))) return rc;
+  if ((rc = heun_store_step(h, 0))) return rc;
+  for (int i = 0; i < N; ++i) {
+    const double t_cur = t[i], t_next = t[i + 1];
+    const double t_hat = t_cur + gammas[i] * t_cur;                                   // mcedm.py:607
+    if (gammas[i] != 0.0) {
+      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
+      if ((rc = heun_churn(h, c, step_noise ? step_noise + (size_t)i * h.total : nullptr,
+                           reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, mask))) return rc;
+    }
+    if ((rc = heun_update(h, i, t_hat, t_next, mask, denoise, dxg, wgt, (float)t_hat))) return rc;
+    if ((rc = heun_store_step(h, i + 1))) return rc;
+  }
+  return heun_store_last(h);
+}
+
+extern "C" int mcedm_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                 const float* cond, const float* mask, const float* init_noise,
+                                 const double* step_noise, double* out, int return_last, void* workspace,
+                                 size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
+                          B, H, W, nullptr, stream, nullptr, nullptr);
+}
+
+// The churn noise of every step generated inside the kernel that applies it (Philox4x32-10 keyed by *rng_seed, draw = step
+// index): no [timesteps][B][C][H][W] fp64 tensor (2.1 GB at 50 x 160 x 2 x 128 x 128, the reference's shipped sampler config,
+// configs/diff_sampler/edm_sampler.yaml) and one HIP graph replays with fresh noise after the host bumps the seed.
+extern "C" int mcedm_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                     const float* cond, const float* mask, const float* init_noise, const uint64_t* rng_seed,
+                                     double* out, int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                     void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, nullptr, out, return_last, workspace, workspace_bytes,
+                          B, H, W, nullptr, stream, nullptr, rng_seed);
+}
+
+extern "C" int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                        const mcedm_guidance_desc* gd, const float* cond, const float* mask,
+                                        const float* init_noise, const double* step_noise, double* out, int return_last,
+                                        void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(gd != nullptr && (gd->system == 1 || gd->system == 2), "heun_sample_guided: guidance system must be 1 (SWE) or 2 (Darcy)");
+  MCEDM_REQUIRE(plan && plan->desc.in_channels == 1 && plan->desc.cond_channels >= 1 && cond != nullptr && mask == nullptr,
+                "heun_sample_guided: PDE guidance is defined for the single-task sampler (state u, conditioning h in cond[:, 0]; "
+                "mask NULL), models/ddim.py:1532-1601; the joint model's hook fails in the reference (models/mcedm.py:500-518)");
+  return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
+                          B, H, W, gd, stream, nullptr, nullptr);
+}
+
+extern "C" int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                        const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+                                        const float* init_noise, const double* step_noise, double* out, int return_last,
+                                        void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(dxc != nullptr && (dxc->system == 1 || dxc->system == 2), "heun_sample_dxcond: dx system must be 1 (SWE) or 2 (Darcy)");
+  MCEDM_REQUIRE(gd == nullptr || gd->system == 1 || gd->system == 2, "heun_sample_dxcond: guidance system must be 1 (SWE) or 2 (Darcy)");
+  MCEDM_REQUIRE(plan && plan->desc.dx_mode != MCEDM_DX_NONE && plan->desc.dx_channels == 1 && plan->desc.in_channels == 1 &&
+                    plan->desc.cond_channels >= 1 && cond != nullptr,
+                "heun_sample_dxcond: needs a dx_cond plan of the single-task model (state u, conditioning h in cond[:, 0], one dx "
+                "channel), models/ddim.py:1424-1450, 1532-1601");
+  return heun_sample_impl(plan, packed, sp, cond, nullptr, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
+                          B, H, W, gd, stream, dxc, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// VP-preconditioned Heun sampler of an epsilon network (PlCondDdim.sample_edm, models/ddim.py:1532-1601)
+// ------------------------------------------------------------------------------------------
+namespace mcedm {
+struct VpBufs : HeunBufs { size_t condp; };
+static VpBufs vp_bufs(const mcedm_plan& P, int B, int H, int W) {
+  VpBufs v{heun_bufs((size_t)B * P.desc.in_channels * H * W), 0};
+  // cond' = cat(cond, zeros) of a self-conditioning plan
+  v.condp = heun_take(v, (size_t)B * P.desc.cond_channels * H * W * 4);
+  return v;
+}
+
+// get_denoised (models/ddim.py:915-947) at one noise level: D = x + (-sigma) F(c_in cat(cond', x), c_noise)
+static int vp_denoise(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x32, const float* condp,
+                      double sigma_d, float c_noise, double w, float* D, void* ws, int B, int H, int W, hipStream_t s) {
+  int rc;
+  const float sigma = (float)sigma_d;                                   // t.to(torch.float32)
+  const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                // 1 / (sigma ** 2 + 1).sqrt(), fp32
+  Coef* coef_in = at<Coef>(ws, hd.coef_in);
+  float* label = at<float>(ws, hd.c_noise);
+  float* F = at<float>(ws, hd.F);
+  void* act = at<char>(ws, hd.total);
+  if ((rc = launch_vp_prepare(c_in, P.desc.cond_channels + P.desc.in_channels, c_noise, coef_in, label, s))) return rc;
+  if ((rc = forward_impl(P, L, pk, x32, nullptr, condp, coef_in, 0, label, 1, F, act, B, H, W, s))) return rc;
+  const float* Fu = nullptr;
+  if (std::fabs(w) >= 0.001 && condp != nullptr) {                     // :938-942, the second evaluation without cond
+    float* Fub = at<float>(ws, hd.Fu);
+    if ((rc = forward_impl(P, L, pk, x32, nullptr, nullptr, coef_in, 0, label, 1, Fub, act, B, H, W, s))) return rc;
+    Fu = Fub;
+  }
+  return launch_vp_cfg_finish(x32, F, Fu, w, sigma, (size_t)B * P.desc.out_channels * H * W, D, s);
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_vp_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "vp_sampler_workspace_bytes: null argument");
+  const int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, bytes);
+  if (rc == MCEDM_OK) *bytes += vp_bufs(*plan, B, H, W).total;
+  return rc;
+}
+
+static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                          const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
+                          int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "vp_heun_sample: null argument");
+  MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "vp_heun_sample: null schedule array");
+  const mcedm_plan& P = *plan;
+  int rc;
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "vp_heun_sample: in_channels != out_channels");
+  MCEDM_REQUIRE(P.desc.dx_mode == MCEDM_DX_NONE, "vp_heun_sample: dx_cond plans are not supported");
+  MCEDM_REQUIRE(sp->cond_channels >= 0 && sp->cond_channels <= P.desc.cond_channels,
+                "vp_heun_sample: cond_channels %d outside [0, %d]", sp->cond_channels, P.desc.cond_channels);
+  MCEDM_REQUIRE(cond == nullptr || sp->cond_channels > 0, "vp_heun_sample: cond given with cond_channels 0");
+  MCEDM_REQUIRE(sp->timesteps >= 1 && sp->timesteps <= 4096, "vp_heun_sample: timesteps=%d out of range", sp->timesteps);
+  const int N = sp->timesteps;
+  const double* t = sp->t_steps;
+  for (int i = 0; i < N; ++i) {
+    MCEDM_REQUIRE(sp->t_hat[i] >= t[i] && t[i] > 0.0, "vp_heun_sample: step %d: t_hat %g < t_cur %g or t_cur <= 0", i, sp->t_hat[i], t[i]);
+    MCEDM_REQUIRE(sp->t_hat[i] == t[i] || step_noise != nullptr || rng_seed != nullptr,
+                  "vp_heun_sample: step %d churns (t_hat > t_cur) and needs step_noise (or mcedm_vp_heun_sample_rng)", i);
+  }
+  Layout L;
+  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
+  const Header hd = header_for(P, B, H, W);
+  const VpBufs vb = vp_bufs(P, B, H, W);
+  if ((rc = heun_check_workspace("vp_heun_sample", workspace_bytes, vb.total + hd.total + L.total_bytes))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, s);
+  void* uws = at<char>(workspace, vb.total);
+  // cond' once per call: cond in its channels, zeros in the self-conditioning ones (get_self_cond_edm returns None)
+  const float* condp = cond;
+  if (cond && sp->cond_channels < P.desc.cond_channels) {
+    float* st = at<float>(workspace, vb.condp);
+    if ((rc = mcedm_eps_self_cond(nullptr, nullptr, nullptr, nullptr, nullptr, 0, cond, sp->cond_channels,
+                                  P.desc.cond_channels - sp->cond_channels, B, H, W, st, stream))) return rc;
+    condp = st;
+  }
+  // x = u_noise.to(float64) * t_steps[0]   (:1556)
+  if ((rc = launch_heun_init(nullptr, 0, h.C, h.hw, nullptr, init_noise, t[0], h.total, h.x, h.x32, s))) return rc;
+  if ((rc = heun_store_step(h, 0))) return rc;
+  for (int i = 0; i < N; ++i) {
+    const double t_cur = t[i], t_next = t[i + 1], t_hat = sp->t_hat[i];
+    if (t_hat != t_cur) {                 // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) * S_noise * eps (:1567); + 0 * eps otherwise
+      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
+      if ((rc = heun_churn(h, c, step_noise ? step_noise + (size_t)i * h.total : nullptr,
+                           reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, nullptr))) return rc;
+    }
+    // Euler step (:1570-1580) at c_noise[2 i], 2nd-order correction (:1583-1593) at c_noise[2 i + 1]
+    auto denoise = [&](double sigma, bool second) {
+      return vp_denoise(P, L, hd, pk, h.x32, condp, sigma, sp->c_noise[2 * i + (second ? 1 : 0)], sp->w, h.D, uws, B, H, W, s);
+    };
+    if ((rc = heun_update(h, i, t_hat, t_next, nullptr, denoise))) return rc;
+    if ((rc = heun_store_step(h, i + 1))) return rc;
+  }
+  return heun_store_last(h);
+}
+
+extern "C" int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                                    const float* init_noise, const double* step_noise, double* out, int return_last,
+                                    void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return vp_sample_impl(plan, packed, sp, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B, H,
+                        W, stream);
+}
+
+extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                        const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
+                                        int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                        void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return vp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, H,
+                        W, stream);
+}

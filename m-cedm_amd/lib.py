@@ -246,8 +246,73 @@ class Workspace:
         return self.buf
 
 
-class Plan:
+def _bucket_args(bucket_first, bucket_events, who: str):
+    """(nb, firsts, evs) of a bucketed backward call; (0, None, None) without buckets."""
+    if bucket_first is None:
+        return 0, None, None
+    nb = len(bucket_first)
+    firsts = (C.c_int32 * nb)(*[int(f) for f in bucket_first])
+    handles = [int(e.cuda_event) for e in bucket_events]
+    if len(handles) != nb or not all(handles):
+        raise RuntimeError(f"{who}: one created (recorded at least once) torch.cuda.Event per bucket is needed")
+    return nb, firsts, (C.c_void_p * nb)(*handles)
+
+
+def _seed_ptr(rng_seed: torch.Tensor, device, who: str) -> int:
+    if rng_seed.dtype != torch.int64 or rng_seed.numel() != 1 or rng_seed.device != device:
+        raise RuntimeError(f"{who}: rng_seed must be a one-element int64 tensor on the sampler's device")
+    return rng_seed.data_ptr()
+
+
+class _PlanBase:
+    """What the two plan handles share.  _SYM: the prefix of the plan's own symbols (mcedm_unet / mcedm_ddpm); _WHAT: the
+    prefix its entries carry in error messages ("" / "ddpm_")."""
+    _SYM = _WHAT = ""
+
+    def _adopt(self, lib, h) -> None:
+        """Take ownership of the created plan handle and read its parameter table and packed size."""
+        self._h, self._lib = h, lib
+        self.param_names: List[str] = []
+        self.param_shapes: List[tuple] = []
+        for i in range(getattr(lib, self._SYM + "_param_count")(h)):
+            name, numel, ndim, shape = C.c_char_p(), C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
+            check(getattr(lib, self._SYM + "_param_info")(h, i, C.byref(name), C.byref(numel), C.byref(ndim), C.byref(shape)))
+            self.param_names.append(name.value.decode())
+            self.param_shapes.append(tuple(shape[j] for j in range(ndim.value)))
+        self.packed_bytes = self._bytes(self._SYM + "_packed_bytes", "")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            getattr(self._lib, self._SYM + "_plan_destroy")(h)
+
+    def set_variant(self, which: str, value: int = -1) -> None:
+        """This plan's own choice for one kernel family (``VARIANTS``): 1 / 0, -1 = the process default (mcedm_op_set_* or the
+        environment).  In force whenever one of THIS plan's entry points runs; other plans are not affected.  'conv_wino'
+        also shapes the workspace layout: set it before the plan's first use."""
+        fn = getattr(self._lib, self._SYM + "_plan_set_variant")
+        check(fn(self._h, VARIANTS[which], int(value)), self._WHAT + "plan_set_variant")
+
+    def _collect(self, params: Dict[str, torch.Tensor]) -> List[torch.Tensor]:
+        """The plan's parameters out of ``params``, in table order, shapes checked."""
+        tens = []
+        for name, shape in zip(self.param_names, self.param_shapes):
+            t = params[name]
+            if tuple(t.shape) != shape:
+                raise RuntimeError(f"parameter {name}: shape {tuple(t.shape)} != {shape}")
+            tens.append(t.detach())
+        return tens
+
+    def _bytes(self, symbol: str, what: str, *args) -> int:
+        """A size query ``symbol(plan, *args, &bytes)``; ``what`` names it in the error message."""
+        sz = C.c_size_t()
+        check(getattr(self._lib, symbol)(self._h, *args, C.byref(sz)), what)
+        return sz.value
+
+
+class Plan(_PlanBase):
     """Host-side handle of one network architecture (mcedm_unet_plan_create)."""
+    _SYM, _WHAT = "mcedm_unet", ""
 
     def __init__(self, in_channels: int, cond_channels: int, out_channels: int, ch: int, ch_mult: Sequence[int],
                  num_res_blocks: int, attn_resolutions: Sequence[int], resolution: int, channels_per_head: int = 64,
@@ -270,42 +335,13 @@ class Plan:
         self.desc = d
         h = C.c_void_p()
         check(lib.mcedm_unet_plan_create(C.byref(d), C.byref(h)), "plan_create")
-        self._h = h
-        self._lib = lib
-        n = lib.mcedm_unet_param_count(h)
-        self.param_names: List[str] = []
-        self.param_shapes: List[tuple] = []
-        for i in range(n):
-            name, numel, ndim, shape = C.c_char_p(), C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
-            check(lib.mcedm_unet_param_info(h, i, C.byref(name), C.byref(numel), C.byref(ndim), C.byref(shape)))
-            self.param_names.append(name.value.decode())
-            self.param_shapes.append(tuple(shape[j] for j in range(ndim.value)))
-        sz = C.c_size_t()
-        check(lib.mcedm_unet_packed_bytes(h, C.byref(sz)))
-        self.packed_bytes = sz.value
+        self._adopt(lib, h)
         self.in_channels, self.cond_channels, self.out_channels = in_channels, cond_channels, out_channels
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.mcedm_unet_plan_destroy(h)
-
-    def set_variant(self, which: str, value: int = -1) -> None:
-        """This plan's own choice for one kernel family (``VARIANTS``): 1 / 0, -1 = the process default (mcedm_op_set_* or the
-        environment).  In force whenever one of THIS plan's entry points runs; other plans are not affected.  'conv_wino'
-        also shapes the workspace layout: set it before the plan's first use."""
-        self._lib.mcedm_unet_plan_set_variant.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        check(self._lib.mcedm_unet_plan_set_variant(self._h, VARIANTS[which], int(value)), "plan_set_variant")
 
     # ---- derived weights ---------------------------------------------------------------
     def pack(self, params: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Pack the named fp32 device parameters (keys = DhariwalUNet.state_dict() names)."""
-        tens = []
-        for name, shape in zip(self.param_names, self.param_shapes):
-            t = params[name]
-            if tuple(t.shape) != shape:
-                raise RuntimeError(f"parameter {name}: shape {tuple(t.shape)} != {shape}")
-            tens.append(t.detach())
+        tens = self._collect(params)
         dev = tens[0].device
         if packed is None:
             packed = torch.empty(self.packed_bytes, dtype=torch.uint8, device=dev)
@@ -315,14 +351,10 @@ class Plan:
 
     # ---- sizes -----------------------------------------------------------------------------
     def workspace_bytes(self, B: int, H: int, W: int, training: bool = False) -> int:
-        sz = C.c_size_t()
-        check(self._lib.mcedm_unet_workspace_bytes(self._h, B, H, W, int(training), C.byref(sz)), "workspace_bytes")
-        return sz.value
+        return self._bytes("mcedm_unet_workspace_bytes", "workspace_bytes", B, H, W, int(training))
 
     def sampler_workspace_bytes(self, B: int, H: int, W: int) -> int:
-        sz = C.c_size_t()
-        check(self._lib.mcedm_sampler_workspace_bytes(self._h, B, H, W, C.byref(sz)), "sampler_workspace_bytes")
-        return sz.value
+        return self._bytes("mcedm_sampler_workspace_bytes", "sampler_workspace_bytes", B, H, W)
 
     # ---- compute ---------------------------------------------------------------------------
     def _check_dx(self, x, dx):
@@ -378,23 +410,12 @@ class Plan:
         buf = ws.get(self.workspace_bytes(B, H, W, True), x.device)
         parr = (C.c_void_p * len(self.param_names))(*[_ptr(params[n].detach()) for n in self.param_names])
         garr = (C.c_void_p * len(self.param_names))(*[_ptr(g) for g in grads])
-        if dx is not None and bucket_first is None:
-            check(self._lib.mcedm_edm_denoise_backward_dx(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(dx), _ptr(sigma),
-                                                          sigma.numel(), _ptr(cond), _ptr(dD), garr, buf.data_ptr(), buf.numel(),
-                                                          B, H, W, float(sigma_data), 0, None, None, _stream()),
-                  "edm_denoise_backward_dx")
-            return
-        if bucket_first is None:
+        if dx is None and bucket_first is None:
             check(self._lib.mcedm_edm_denoise_backward(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(sigma), sigma.numel(),
                                                        _ptr(cond), _ptr(dD), garr, buf.data_ptr(), buf.numel(), B, H, W,
                                                        float(sigma_data), _stream()), "edm_denoise_backward")
             return
-        nb = len(bucket_first)
-        firsts = (C.c_int32 * nb)(*[int(f) for f in bucket_first])
-        handles = [int(e.cuda_event) for e in bucket_events]
-        if len(handles) != nb or not all(handles):
-            raise RuntimeError("denoise_backward: one created (recorded at least once) torch.cuda.Event per bucket is needed")
-        evs = (C.c_void_p * nb)(*handles)
+        nb, firsts, evs = _bucket_args(bucket_first, bucket_events, "denoise_backward")
         check(self._lib.mcedm_edm_denoise_backward_dx(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(dx), _ptr(sigma),
                                                       sigma.numel(), _ptr(cond), _ptr(dD), garr, buf.data_ptr(),
                                                       buf.numel(), B, H, W, float(sigma_data), nb, firsts, evs,
@@ -409,22 +430,13 @@ class Plan:
         buf = ws.get(self.workspace_bytes(B, H, W, True), x.device)
         parr = (C.c_void_p * len(self.param_names))(*[_ptr(params[n].detach()) for n in self.param_names])
         garr = (C.c_void_p * len(self.param_names))(*[_ptr(g) for g in grads])
-        nb, firsts, evs = 0, None, None
-        if bucket_first is not None:
-            nb = len(bucket_first)
-            firsts = (C.c_int32 * nb)(*[int(f) for f in bucket_first])
-            handles = [int(e.cuda_event) for e in bucket_events]
-            if len(handles) != nb or not all(handles):
-                raise RuntimeError("unet_backward: one created (recorded at least once) torch.cuda.Event per bucket is needed")
-            evs = (C.c_void_p * nb)(*handles)
+        nb, firsts, evs = _bucket_args(bucket_first, bucket_events, "unet_backward")
         check(self._lib.mcedm_unet_backward_bucketed(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(cond), None,
                                                      _ptr(noise_labels), noise_labels.numel(), _ptr(dF), garr, buf.data_ptr(),
                                                      buf.numel(), B, H, W, nb, firsts, evs, _stream()), "unet_backward")
 
     def vp_sampler_workspace_bytes(self, B: int, H: int, W: int) -> int:
-        sz = C.c_size_t()
-        check(self._lib.mcedm_vp_sampler_workspace_bytes(self._h, B, H, W, C.byref(sz)), "vp_sampler_workspace_bytes")
-        return sz.value
+        return self._bytes("mcedm_vp_sampler_workspace_bytes", "vp_sampler_workspace_bytes", B, H, W)
 
     def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
                   ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -437,10 +449,9 @@ class Plan:
         if rng_seed is not None:
             if step_noise is not None:
                 raise RuntimeError("vp_sample: give step_noise or rng_seed, not both")
-            if rng_seed.dtype != torch.int64 or rng_seed.numel() != 1 or rng_seed.device != init_noise.device:
-                raise RuntimeError("vp_sample: rng_seed must be a one-element int64 tensor on the sampler's device")
+            seed = _seed_ptr(rng_seed, init_noise.device, "vp_sample")
             check(self._lib.mcedm_vp_heun_sample_rng(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
-                                                     rng_seed.data_ptr(), _ptr(out, torch.float64), int(return_last),
+                                                     seed, _ptr(out, torch.float64), int(return_last),
                                                      buf.data_ptr(), buf.numel(), B, H, W, _stream()), "vp_heun_sample_rng")
             return out
         check(self._lib.mcedm_vp_heun_sample(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
@@ -481,10 +492,9 @@ class Plan:
         if rng_seed is not None:
             if step_noise is not None:
                 raise RuntimeError("sample: give step_noise (materialised draws) or rng_seed (device-side draws), not both")
-            if rng_seed.dtype != torch.int64 or rng_seed.numel() != 1 or rng_seed.device != init_noise.device:
-                raise RuntimeError("sample: rng_seed must be a one-element int64 tensor on the sampler's device")
+            seed = _seed_ptr(rng_seed, init_noise.device, "sample")
             check(self._lib.mcedm_heun_sample_rng(self._h, packed.data_ptr(), C.byref(sd), _ptr(cond), _ptr(mask),
-                                                  _ptr(init_noise), rng_seed.data_ptr(), _ptr(out, torch.float64),
+                                                  _ptr(init_noise), seed, _ptr(out, torch.float64),
                                                   int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
                   "heun_sample_rng")
             return out
@@ -538,8 +548,9 @@ def repaint_schedule(rd: RepaintDesc) -> List[float]:
     return list(arr)
 
 
-class DdpmPlan:
+class DdpmPlan(_PlanBase):
     """Host-side handle of one DDPM U-Net (models/ddim_blocks.py Model; mcedm_ddpm_plan_create)."""
+    _SYM, _WHAT = "mcedm_ddpm", "ddpm_"
 
     def __init__(self, in_channels: int, out_channels: int, ch: int, ch_mult: Sequence[int], num_res_blocks: int,
                  attn_resolutions: Sequence[int], resolution: int, self_cond: bool = True, eps: float = 1e-6):
@@ -557,38 +568,13 @@ class DdpmPlan:
         self.desc = d
         h = C.c_void_p()
         check(lib.mcedm_ddpm_plan_create(C.byref(d), C.byref(h)), "ddpm_plan_create")
-        self._h, self._lib = h, lib
-        self.param_names: List[str] = []
-        self.param_shapes: List[tuple] = []
-        for i in range(lib.mcedm_ddpm_param_count(h)):
-            name, numel, ndim, shape = C.c_char_p(), C.c_int64(), C.c_int32(), (C.c_int64 * 4)()
-            check(lib.mcedm_ddpm_param_info(h, i, C.byref(name), C.byref(numel), C.byref(ndim), C.byref(shape)))
-            self.param_names.append(name.value.decode())
-            self.param_shapes.append(tuple(shape[j] for j in range(ndim.value)))
-        sz = C.c_size_t()
-        check(lib.mcedm_ddpm_packed_bytes(h, C.byref(sz)))
-        self.packed_bytes = sz.value
+        self._adopt(lib, h)
         self.in_channels, self.out_channels, self.resolution, self.ch = in_channels, out_channels, resolution, ch
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.mcedm_ddpm_plan_destroy(h)
-
-    def set_variant(self, which: str, value: int = -1) -> None:
-        """As ``Plan.set_variant``: this plan's own kernel choice, -1 = the process default."""
-        self._lib.mcedm_ddpm_plan_set_variant.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        check(self._lib.mcedm_ddpm_plan_set_variant(self._h, VARIANTS[which], int(value)), "ddpm_plan_set_variant")
 
     def pack(self, params: Dict[str, torch.Tensor], temb_freqs: torch.Tensor, packed: Optional[torch.Tensor] = None):
         """params keyed like Model.state_dict(); temb_freqs [ch/2] device fp32, built by the caller exactly as
         get_timestep_embedding does (models/ddim_blocks.py:22-24)."""
-        tens = []
-        for name, shape in zip(self.param_names, self.param_shapes):
-            t = params[name]
-            if tuple(t.shape) != shape:
-                raise RuntimeError(f"parameter {name}: shape {tuple(t.shape)} != {shape}")
-            tens.append(t.detach())
+        tens = self._collect(params)
         if temb_freqs.numel() != self.ch // 2:
             raise RuntimeError("temb_freqs must have ch / 2 entries")
         if packed is None:
@@ -598,14 +584,10 @@ class DdpmPlan:
         return packed
 
     def workspace_bytes(self, B: int) -> int:
-        sz = C.c_size_t()
-        check(self._lib.mcedm_ddpm_workspace_bytes(self._h, B, C.byref(sz)), "ddpm_workspace_bytes")
-        return sz.value
+        return self._bytes("mcedm_ddpm_workspace_bytes", "ddpm_workspace_bytes", B)
 
     def repaint_workspace_bytes(self, B: int) -> int:
-        sz = C.c_size_t()
-        check(self._lib.mcedm_repaint_workspace_bytes(self._h, B, C.byref(sz)), "repaint_workspace_bytes")
-        return sz.value
+        return self._bytes("mcedm_repaint_workspace_bytes", "repaint_workspace_bytes", B)
 
     def _check_x(self, x):
         if tuple(x.shape[1:]) != (self.in_channels, self.resolution, self.resolution):
@@ -629,9 +611,7 @@ class DdpmPlan:
         return out
 
     def ddim_workspace_bytes(self, B: int) -> int:
-        sz = C.c_size_t()
-        check(self._lib.mcedm_ddim_workspace_bytes(self._h, B, C.byref(sz)), "ddim_workspace_bytes")
-        return sz.value
+        return self._bytes("mcedm_ddim_workspace_bytes", "ddim_workspace_bytes", B)
 
     def ddim_repaint_sample(self, packed, dd: "DdimDesc", hu, init_noise, eta_noise=None, return_last: bool = True,
                             ws: Optional[Workspace] = None):
