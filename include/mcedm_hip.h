@@ -331,6 +331,33 @@ int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const m
                              const float* init_noise, const uint64_t* rng_seed, double* out, int return_last, void* workspace,
                              size_t workspace_bytes, int B, int H, int W, void* stream);
 
+/* PlCondDdim.sample (models/ddim.py:1452-1530): the DDIM sampler of the single-task conditional network, guide_dx False,
+ * dx_cond False.  Everything is fp32 like the reference; one network evaluation per step, two with guidance, and one fused
+ * elementwise kernel per step.
+ *  timesteps, skip_type (0 uniform, 1 quad), eta, alphas_cumprod_ext, num_diffusion_timesteps: as in mcedm_ddim_desc; the
+ *                  sequence walked is mcedm_ddim_timesteps', last entry first, S entries (uniform: S may exceed timesteps)
+ *  w               classifier-free guidance: |w| >= 0.001 adds a second pass whose cond channels read zeros,
+ *                  et = (w + 1) F(cond) - w F(None) (:1493-1497)
+ *  cond_channels   channels of `cond`; the plan's conditioning input is cat(cond, x_self_cond)
+ *  self_cond       1: the previous step's x0 prediction is fed back as x_self_cond (zeros in the first step, :1490), which
+ *                  needs a plan with cond_channels + in_channels conditioning channels; 0: those channels stay zero
+ *  cond            [B, cond_channels, H, W] (NULL iff cond_channels == 0);  init_noise [B, in, H, W]
+ *  eta_noise       [S, B, in, H, W]: step k's torch.rand_like draw of :1512 (UNIFORM in the reference) in slice k, in the order
+ *                  the steps are walked; required exactly when |eta| > 1e-10, else ignored and may be NULL
+ *  xs_out, x0_out  fp32 'b t h w c': [B, S + 1, H, W, in] with init_noise in slot 0 and [B, S, H, W, in]; one slot each with
+ *                  return_last (the last state and the last x0 prediction)
+ * The workspace holds xt, xt_next, F, F_uncond, cond' and its zero-cond twin in front of the network's own workspace. */
+typedef struct mcedm_cond_ddim_desc {
+  int32_t timesteps, skip_type;
+  double eta, w;
+  int32_t cond_channels, self_cond, num_diffusion_timesteps;
+  const float* alphas_cumprod_ext;
+} mcedm_cond_ddim_desc;
+int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes);
+int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                           const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out, int return_last,
+                           void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+
 /* ---- kernel-level entry points ----------------------------------------------------------
  * The building blocks the schedules above are made of, exported so that each kernel can be
  * parity-tested against the oracle and timed on its own (bench.py roofline leg). */
@@ -416,6 +443,15 @@ int mcedm_op_gn_bwd_sync(const float* dact, int resample, const float* xa, const
  * lse_scratch holds B*heads*T*2 floats. */
 int mcedm_op_attention_bwd(const float* qkv, const float* a, const float* da, float* dqkv, float* lse_scratch, int B,
                            int heads, int T, void* stream);
+/* One step of mcedm_cond_ddim_sample's elementwise part on caller-owned tensors (all fp32):
+ *   et = (w + 1) F - w Fu (Fu != NULL) or F;  x0 = (xt - et * s1) / s0;  xt_next = sa_next * x0 [+ c1 * noise] + c2 * et
+ * xt, F, Fu, noise, xt_next [B, C, H, W]; x0 also goes to channels [cond_channels, cond_channels + C) of condp and condp_u
+ * ([B, plan_cond_channels, H, W], either may be NULL) and to slot t_x0 of x0s [B, T_x0, H, W, C], xt_next to slot t_xs of xs
+ * [B, T_xs, H, W, C] (either may be NULL). */
+int mcedm_op_ddim_cond_step(const float* xt, const float* F, const float* Fu, const float* noise, double w, float s0, float s1,
+                            float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u, int cond_channels,
+                            int plan_cond_channels, int B, int C, int H, int W, float* xs, int T_xs, int t_xs, float* x0s,
+                            int T_x0, int t_x0, void* stream);
 /* Test hook: force the conv tile (channel tile mt in {32,64,128}, pixel tile ph x pw in {8x32,8x16,16x16,8x8};
  * (128,16,32) = the 8-wave kernel, 3x3 only);
  * (0,0,0) restores the size heuristic.  Process-global, not thread-safe. */

@@ -898,28 +898,7 @@ extern "C" int mcedm_ddim_workspace_bytes(const mcedm_ddpm_plan* plan, int B, si
   return MCEDM_OK;
 }
 
-// The DDIM timestep sequence of PlDdim.sample_with_repeat (models/ddim.py:823-830).
-//  uniform: range(0, n, n // N) -- may hold more than N entries;
-//  quad:    [int(s) for s in np.linspace(0, sqrt(0.8 n), N) ** 2].  numpy.linspace evaluates arange(N) * step with
-//           step = stop / (N - 1) and then PINS the last sample to `stop` itself; hi * i / (N - 1) is a different rounding
-//           and lands on the other side of an integer for 85 of ~1200 (n, N) pairs (n = 1000, N = 100: first sampled step
-//           799 instead of 800), so the two operations are reproduced in numpy's order.
-static std::vector<int> ddim_timestep_seq(int n, int N, int skip_type) {
-  std::vector<int> seq;
-  if (skip_type == 0) {
-    const int skip = n / N;
-    for (int v = 0; v < n; v += skip) seq.push_back(v);
-  } else {
-    const double hi = std::sqrt(n * 0.8);
-    const double step = N > 1 ? hi / (double)(N - 1) : 0.0;
-    for (int i = 0; i < N; ++i) {
-      const double v = (N > 1 && i == N - 1) ? hi : (double)i * step;
-      seq.push_back((int)(v * v));
-    }
-  }
-  return seq;
-}
-
+// (the timestep sequence itself, ddim_timestep_seq, is shared with the conditional sampler: edm.hpp)
 extern "C" int mcedm_ddim_timesteps(int num_diffusion_timesteps, int timesteps, int skip_type, int* seq, int capacity, int* count) {
   MCEDM_REQUIRE(count && num_diffusion_timesteps >= 2 && timesteps >= 1 && timesteps <= num_diffusion_timesteps,
                 "ddim_timesteps: bad schedule (timesteps=%d of %d)", timesteps, num_diffusion_timesteps);

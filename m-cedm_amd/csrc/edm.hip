@@ -399,6 +399,86 @@ int launch_store_f32(const float* x, int C, size_t hw, int t, int T, size_t tota
   return MCEDM_OK;
 }
 
+// ---- DDIM sampler of the conditional ADM U-Net (PlCondDdim.sample, models/ddim.py:1452-1530): one pass per step --------
+// fp32 in the reference's order (:1497-1515; this file is built without fma contraction).  Pure streaming: every thread
+// takes four consecutive state elements (16-byte loads of xt / F / Fu / noise, 16-byte store of xt_next) and scatters x0
+// and xt_next to where their readers want them -- the self-conditioning channels of cond' and of its zero-cond twin
+// ([B, Cp, H, W]: the next forward's conv_in reads them there) and one slot each of the 'b t h w c' trajectories.
+__device__ __forceinline__ void ddim_cond_point(const DdimCondStep& a, float x, float f, float fu, float nz, float& x0, float& xn) {
+  const float et = a.Fu ? a.w1 * f - a.w * fu : f;                     // (w + 1) * model(cond) - w * model(None)   (:1497)
+  x0 = (x - et * a.s1) / a.s0;                                         // (xt - et * (1 - at).sqrt()) / at.sqrt()   (:1505)
+  xn = a.noise ? (a.sa * x0 + a.c1 * nz) + a.c2 * et : a.sa * x0 + a.c2 * et;        // (:1512 / :1515)
+}
+// element i of the [B, C, H, W] state -> its places in cond' / twin and in the trajectories
+__device__ __forceinline__ void ddim_cond_scatter(const DdimCondStep& a, size_t i, float x0, float xn) {
+  const size_t chw = (size_t)a.C * a.hw, b = i / chw, r = i - b * chw;
+  if (a.sc) {
+    const size_t j = (b * (size_t)a.Cp + (size_t)a.sc_off) * a.hw + r;
+    a.sc[j] = x0;
+    if (a.sc_u) a.sc_u[j] = x0;
+  }
+  if (a.xs || a.x0s) {
+    const size_t c = r / a.hw, p = r - c * a.hw;
+    if (a.xs) a.xs[((b * (size_t)a.T_xs + (size_t)a.t_xs) * a.hw + p) * (size_t)a.C + c] = xn;
+    if (a.x0s) a.x0s[((b * (size_t)a.T_x0 + (size_t)a.t_x0) * a.hw + p) * (size_t)a.C + c] = x0;
+  }
+}
+__global__ __launch_bounds__(256) void ddim_cond_step_kernel(DdimCondStep a, size_t n4, int vec_sc, int vec_tr) {
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (size_t g = tid; g < n4; g += stride) {
+    const float4 x = reinterpret_cast<const float4*>(a.xt)[g], f = reinterpret_cast<const float4*>(a.F)[g];
+    const float4 fu = a.Fu ? reinterpret_cast<const float4*>(a.Fu)[g] : zero4;
+    const float4 nz = a.noise ? reinterpret_cast<const float4*>(a.noise)[g] : zero4;
+    float4 x0, xn;
+    ddim_cond_point(a, x.x, f.x, fu.x, nz.x, x0.x, xn.x);
+    ddim_cond_point(a, x.y, f.y, fu.y, nz.y, x0.y, xn.y);
+    ddim_cond_point(a, x.z, f.z, fu.z, nz.z, x0.z, xn.z);
+    ddim_cond_point(a, x.w, f.w, fu.w, nz.w, x0.w, xn.w);
+    reinterpret_cast<float4*>(a.xt_next)[g] = xn;
+    const size_t i = 4 * g;
+    // H * W % 4 == 0: the four elements share (b, c) and every destination offset is a multiple of four
+    const size_t chw = (size_t)a.C * a.hw, b = i / chw, r = i - b * chw;
+    if (a.sc) {
+      if (vec_sc) {
+        const size_t j = (b * (size_t)a.Cp + (size_t)a.sc_off) * a.hw + r;
+        *reinterpret_cast<float4*>(a.sc + j) = x0;
+        if (a.sc_u) *reinterpret_cast<float4*>(a.sc_u + j) = x0;
+      } else {
+        DdimCondStep t = a; t.xs = nullptr; t.x0s = nullptr;
+        ddim_cond_scatter(t, i, x0.x, xn.x); ddim_cond_scatter(t, i + 1, x0.y, xn.y);
+        ddim_cond_scatter(t, i + 2, x0.z, xn.z); ddim_cond_scatter(t, i + 3, x0.w, xn.w);
+      }
+    }
+    if (a.xs || a.x0s) {
+      if (vec_tr) {                      // C == 1: a sample's slot is contiguous
+        if (a.xs) *reinterpret_cast<float4*>(a.xs + (b * (size_t)a.T_xs + (size_t)a.t_xs) * a.hw + r) = xn;
+        if (a.x0s) *reinterpret_cast<float4*>(a.x0s + (b * (size_t)a.T_x0 + (size_t)a.t_x0) * a.hw + r) = x0;
+      } else {
+        DdimCondStep t = a; t.sc = nullptr;
+        ddim_cond_scatter(t, i, x0.x, xn.x); ddim_cond_scatter(t, i + 1, x0.y, xn.y);
+        ddim_cond_scatter(t, i + 2, x0.z, xn.z); ddim_cond_scatter(t, i + 3, x0.w, xn.w);
+      }
+    }
+  }
+  for (size_t i = 4 * n4 + tid; i < a.n; i += stride) {                // scalar tail (everything, when a pointer is not 16-byte aligned)
+    float x0, xn;
+    ddim_cond_point(a, a.xt[i], a.F[i], a.Fu ? a.Fu[i] : 0.f, a.noise ? a.noise[i] : 0.f, x0, xn);
+    a.xt_next[i] = xn;
+    ddim_cond_scatter(a, i, x0, xn);
+  }
+}
+int launch_ddim_cond_step(const DdimCondStep& a, hipStream_t s) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; };
+  const bool body = al16(a.xt) && al16(a.F) && al16(a.Fu) && al16(a.noise) && al16(a.xt_next);
+  const size_t n4 = body ? a.n / 4 : 0;
+  const int vec_sc = a.hw % 4 == 0 && al16(a.sc) && al16(a.sc_u);
+  const int vec_tr = a.hw % 4 == 0 && a.C == 1 && al16(a.xs) && al16(a.x0s);
+  hipLaunchKernelGGL(ddim_cond_step_kernel, dim3(grid_for(n4 ? n4 : a.n)), dim3(256), 0, s, a, n4, vec_sc, vec_tr);
+  MCEDM_LAUNCH_CHECK("ddim_cond_step_kernel");
+  return MCEDM_OK;
+}
+
 // ---- training-side elementwise ----------------------------------------------------------------
 // sigma = exp(rnd*P_std + P_mean) (mcedm.py:271); x_noise = x + mask*noise*sigma (mcedm.py:216)
 __global__ void noise_inputs_kernel(const float* __restrict__ x, const float* __restrict__ mask,

@@ -1,5 +1,8 @@
 // edm.hpp -- launchers of the EDM preconditioning / Heun sampler kernels (edm.hip).
 #pragma once
+#include <cmath>
+#include <vector>
+
 #include "common.hpp"
 
 namespace mcedm {
@@ -71,5 +74,42 @@ int launch_ddim_next(const float* x0, const float* et, const float* hu, const fl
 int launch_ddim_init(const float* hu, const float* hn, const float* mask, float sa, float sb, size_t total, float* xt, hipStream_t s);
 // 'b c h w -> b t h w c' for one time slot, fp32
 int launch_store_f32(const float* x, int C, size_t hw, int t, int T, size_t total, float* out, hipStream_t s);
+
+// The DDIM timestep sequence of PlDdim.sample_with_repeat / PlCondDdim.sample (models/ddim.py:823-830, 1463-1470).
+//  uniform: range(0, n, n // N) -- may hold more than N entries;
+//  quad:    [int(s) for s in np.linspace(0, sqrt(0.8 n), N) ** 2].  numpy.linspace evaluates arange(N) * step with
+//           step = stop / (N - 1) and then PINS the last sample to `stop` itself; hi * i / (N - 1) is a different rounding
+//           and lands on the other side of an integer for 85 of ~1200 (n, N) pairs (n = 1000, N = 100: first sampled step
+//           799 instead of 800), so the two operations are reproduced in numpy's order.
+static inline std::vector<int> ddim_timestep_seq(int n, int N, int skip_type) {
+  std::vector<int> seq;
+  if (skip_type == 0) {
+    const int skip = n / N;
+    for (int v = 0; v < n; v += skip) seq.push_back(v);
+  } else {
+    const double hi = std::sqrt(n * 0.8);
+    const double step = N > 1 ? hi / (double)(N - 1) : 0.0;
+    for (int i = 0; i < N; ++i) {
+      const double v = (N > 1 && i == N - 1) ? hi : (double)i * step;
+      seq.push_back((int)(v * v));
+    }
+  }
+  return seq;
+}
+
+// ---- DDIM sampler of the conditional ADM U-Net (PlCondDdim.sample, models/ddim.py:1452-1530), all fp32: one step
+//   et = w1 * F - w * Fu (Fu != NULL) or F;  x0 = (xt - et * s1) / s0;  xt_next = sa * x0 [+ c1 * noise] + c2 * et   (:1497-1515)
+// in one pass that also puts x0 and xt_next where they are read next.  Every pointer but xt, F and xt_next may be NULL.
+struct DdimCondStep {
+  const float *xt, *F, *Fu, *noise;        // [B, C, H, W]
+  float w1, w, s0, s1, sa, c1, c2;
+  float* xt_next;                          // [B, C, H, W]
+  float *sc, *sc_u;                        // [B, Cp, H, W] cond' and its zero-cond twin: x0 -> channels [sc_off, sc_off + C)
+  int C, Cp, sc_off;
+  size_t hw, n;                            // H * W;  B * C * H * W
+  float *xs, *x0s;                         // 'b t h w c' trajectories: xt_next -> slot t_xs of T_xs, x0 -> slot t_x0 of T_x0
+  int T_xs, t_xs, T_x0, t_x0;
+};
+int launch_ddim_cond_step(const DdimCondStep& a, hipStream_t s);
 
 }  // namespace mcedm

@@ -1,5 +1,5 @@
-// sampler.hip -- the Heun samplers of the ADM U-Net: the EDM sampler (with mask, PDE guidance and dx_cond) and the
-// VP-preconditioned sampler of an epsilon network.  Host code only: the schedules (fp64) and the order of the launches;
+// sampler.hip -- the samplers of the ADM U-Net: the EDM Heun sampler (with mask, PDE guidance and dx_cond), the
+// VP-preconditioned Heun sampler of an epsilon network and that network's DDIM sampler.  Host code only: the schedules (fp64) and the order of the launches;
 // the loop itself is heun.hpp, the network plan.hip.
 #include <algorithm>
 #include <cmath>
@@ -293,4 +293,116 @@ extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* pack
   MCEDM_REQUIRE(rng_seed != nullptr, "vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return vp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, H,
                         W, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// DDIM sampler of the conditional epsilon network (PlCondDdim.sample, models/ddim.py:1452-1530): fp32 throughout
+// ------------------------------------------------------------------------------------------
+namespace mcedm {
+// the sampler's own buffers in front of the network's workspace, each 256-byte aligned
+struct CondDdimBufs { size_t xt, xtn, F, Fu, condp, condu, total; };
+static CondDdimBufs cond_ddim_bufs(const mcedm_plan& P, int B, int H, int W) {
+  CondDdimBufs b{};
+  auto take = [&](size_t bytes) { size_t o = b.total; b.total += align_up(bytes, 256); return o; };
+  const size_t hw = (size_t)H * W, n = (size_t)B * P.desc.in_channels * hw;
+  b.xt = take(n * 4); b.xtn = take(n * 4);
+  b.F = take((size_t)B * P.desc.out_channels * hw * 4); b.Fu = take((size_t)B * P.desc.out_channels * hw * 4);
+  // cond' = cat(cond, x0_t) and cat(0, x0_t), what the unconditional pass reads
+  b.condp = take((size_t)B * P.desc.cond_channels * hw * 4); b.condu = take((size_t)B * P.desc.cond_channels * hw * 4);
+  return b;
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "cond_ddim_workspace_bytes: null argument");
+  Layout L;                              // one noise label for the whole batch, as the sampler lays its forward out
+  const int rc = build_layout(*plan, B, H, W, 0, 1, &L);
+  if (rc == MCEDM_OK) *bytes = cond_ddim_bufs(*plan, B, H, W).total + header_for(*plan, B, H, W).total + L.total_bytes;
+  return rc;
+}
+
+extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                                      const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out,
+                                      int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                      void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && xs_out && x0_out && workspace, "cond_ddim_sample: null argument");
+  const mcedm_plan& P = *plan;
+  int rc;
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "cond_ddim_sample: in_channels != out_channels");
+  MCEDM_REQUIRE(P.desc.dx_mode == MCEDM_DX_NONE, "cond_ddim_sample: dx_cond plans are not supported");
+  const int C = P.desc.in_channels, Cp = P.desc.cond_channels, cc = sp->cond_channels;
+  MCEDM_REQUIRE(cc >= 0 && cc <= Cp, "cond_ddim_sample: cond_channels %d outside [0, %d]", cc, Cp);
+  MCEDM_REQUIRE((cond != nullptr) == (cc > 0), "cond_ddim_sample: cond goes with cond_channels > 0 (and only with it)");
+  MCEDM_REQUIRE(!sp->self_cond || cc + C <= Cp,
+                "cond_ddim_sample: self-conditioning asked of a plan whose conditioning input is not widened (%d + %d > %d channels)",
+                cc, C, Cp);
+  const int n = sp->num_diffusion_timesteps, N = sp->timesteps;
+  MCEDM_REQUIRE(sp->alphas_cumprod_ext && n >= 2 && N >= 1 && N <= n, "cond_ddim_sample: bad schedule (timesteps=%d of %d)", N, n);
+  MCEDM_REQUIRE(sp->skip_type == 0 || sp->skip_type == 1, "cond_ddim_sample: skip_type must be 0 (uniform) or 1 (quad)");
+  const bool stochastic = std::fabs(sp->eta) > 1e-10;                   // :1509
+  MCEDM_REQUIRE(!stochastic || eta_noise != nullptr, "cond_ddim_sample: eta != 0 needs eta_noise");
+  const bool guided = !(std::fabs(sp->w) < 0.001);                      // :1493
+  Layout L;
+  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
+  const Header hd = header_for(P, B, H, W);
+  const CondDdimBufs cb = cond_ddim_bufs(P, B, H, W);
+  if ((rc = heun_check_workspace("cond_ddim_sample", workspace_bytes, cb.total + hd.total + L.total_bytes))) return rc;
+  const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  void* uws = at<char>(workspace, cb.total);
+  float* label = at<float>(uws, hd.c_noise);
+  Coef* coef_in = at<Coef>(uws, hd.coef_in);
+  void* act = at<char>(uws, hd.total);
+  const std::vector<int> seq = ddim_timestep_seq(n, N, sp->skip_type);   // :1463-1470; walked from its end, seq_next = [-1] + seq[:-1]
+  const int S = (int)seq.size();
+  for (int t : seq) MCEDM_REQUIRE(t >= 0 && t < n, "cond_ddim_sample: timestep %d outside the schedule table", t);
+
+  // cond' once per call: cond in its channels, zeros in the others (x_self_cond is None in the first step); the step kernel
+  // keeps the self-conditioning channels current from then on.  Guided: the twin with zeros for cond as well.
+  float* condp = Cp > 0 ? at<float>(workspace, cb.condp) : nullptr;
+  float* condu = Cp > 0 && guided ? at<float>(workspace, cb.condu) : nullptr;
+  if (condp && (rc = mcedm_eps_self_cond(nullptr, nullptr, nullptr, nullptr, nullptr, 0, cond, cc, Cp - cc, B, H, W, condp, stream)))
+    return rc;
+  if (condu && (rc = mcedm_eps_self_cond(nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, cc, Cp - cc, B, H, W, condu, stream)))
+    return rc;
+  if (!return_last && (rc = launch_store_f32(init_noise, C, hw, 0, S + 1, total, xs_out, s))) return rc;      // xs = [x]  (:1477)
+
+  float* F = at<float>(workspace, cb.F);
+  float* Fu = guided ? at<float>(workspace, cb.Fu) : nullptr;
+  DdimCondStep k{};
+  k.F = F; k.Fu = Fu;
+  k.w1 = (float)(sp->w + 1.0); k.w = (float)sp->w;
+  k.sc = sp->self_cond ? condp : nullptr; k.sc_u = sp->self_cond ? condu : nullptr;
+  k.C = C; k.Cp = Cp; k.sc_off = cc; k.hw = hw; k.n = total;
+  k.T_xs = return_last ? 1 : S + 1; k.T_x0 = return_last ? 1 : S;
+  const float* xt = init_noise;
+  float* bufs[2] = {at<float>(workspace, cb.xtn), at<float>(workspace, cb.xt)};
+  auto alpha = [&](int t) -> float { return sp->alphas_cumprod_ext[t + 1]; };      // compute_alpha(t): index t + 1 (:700-704)
+  for (int step = 0; step < S; ++step) {
+    const int i = seq[S - 1 - step], j = (S - 1 - step) > 0 ? seq[S - 2 - step] : -1;
+    const float a_t = alpha(i), at_next = alpha(j);
+    // the network sees xt itself (no c_in on this path: conv_in rows scaled by 1) under the label t = i
+    if ((rc = launch_vp_prepare(1.0f, Cp + C, (float)i, coef_in, label, s))) return rc;
+    if ((rc = forward_impl(P, L, pk, xt, nullptr, condp, coef_in, 0, label, 1, F, act, B, H, W, s))) return rc;
+    if (guided && (rc = forward_impl(P, L, pk, xt, nullptr, condu, coef_in, 0, label, 1, Fu, act, B, H, W, s)))
+      return rc;
+    k.xt = xt; k.xt_next = bufs[step & 1];
+    k.s0 = sqrtf(a_t); k.s1 = sqrtf(1.0f - a_t); k.sa = sqrtf(at_next);
+    if (stochastic) {        // c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2), fp32 like the tensors
+      k.c1 = (float)sp->eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
+      k.c2 = sqrtf((1.0f - at_next) - k.c1 * k.c1);
+      k.noise = eta_noise + (size_t)step * total;
+    } else {
+      k.c1 = 0.f; k.c2 = sqrtf(1.0f - at_next); k.noise = nullptr;
+    }
+    const bool store = !return_last || step == S - 1;                   // return_last keeps the last state and x0 only (:1517-1522)
+    k.xs = store ? xs_out : nullptr; k.x0s = store ? x0_out : nullptr;
+    k.t_xs = return_last ? 0 : step + 1; k.t_x0 = return_last ? 0 : step;
+    if ((rc = launch_ddim_cond_step(k, s))) return rc;
+    xt = k.xt_next;
+  }
+  return MCEDM_OK;
 }

@@ -16,12 +16,12 @@ It runs on the same HIP path as ``PlMcedm``: the same ``DhariwalUNet`` (``in_cha
 the loss and of the Heun sampler (``mask = NULL`` in the C ABI).  Constructor, attributes, state_dict keys (incl. the
 DDPM-schedule buffers ``betas`` / ``logvar`` that ``PlDdim.__init__`` registers, models/ddim.py:22-30) and method
 signatures follow the reference (incl. PDE guidance, ``dx_cond``, the ``node_type`` channel and the ``cond_p`` drop); DDIM
-sampling of the single-task model is outside the hot path and raises, and so does ``self_cond`` for ``PlCondEdm`` (its sampler
+sampling of ``PlCondEdm`` raises as in the reference (models/ddim.py:1739-1740), and so does ``self_cond`` for it (its sampler
 would feed ``denoised`` back).
 
 ``PlCondDdim`` (bottom of this file) for ``models/ddim.py:1053-1605``: the single-task conditional DDPM on the ADM U-Net with
-self-conditioning (which it runs) -- epsilon-prediction ``training_step`` and the VP-preconditioned ``sample_edm`` in the HIP
-library.
+self-conditioning (which it runs) -- epsilon-prediction ``training_step``, the VP-preconditioned ``sample_edm`` and the DDIM
+``sample`` loop in the HIP library.
 """
 from __future__ import annotations
 
@@ -96,9 +96,11 @@ class _SingleTask(_PlBase):
         h, u = state_gt[..., :h_ch], state_gt[..., h_ch:h_ch + u_ch]
         u_noise = torch.randn_like(u)
         sp = self.sparams
-        if sp.type != "edm":
-            raise NotImplementedError("only the EDM sampler is built (models/ddim.py:1172-1175)")
-        xs = self.sample_edm(self.get_cond_in(h, u, dx, dt), u_noise, sp, return_last=True, guide_dx=sp.guide_dx)
+        cond_in = self.get_cond_in(h, u, dx, dt)
+        if sp.type == "edm":                                                 # models/ddim.py:1169-1172
+            xs = self.sample_edm(cond_in, u_noise, sp, return_last=True, guide_dx=sp.guide_dx)
+        else:
+            xs, _ = self.sample(cond_in, u_noise, sp, return_last=True, guide_dx=sp.guide_dx)
         last = xs[:, -1]
         loss_u = l1(last[..., :u_ch], u)
         loss_u_un = l1(self.inverse_data_transform_u(last[..., :u_ch]), u_unnorm)
@@ -122,9 +124,10 @@ class _SingleTask(_PlBase):
         n, nb = sp.n_samples, len(h_unnorm)
         cond_rep = self.get_cond_in(h, u, dx, dt).repeat(n, 1, 1, 1)
         u_noise = torch.randn_like(u.repeat(n, 1, 1, 1))
-        if sp.type != "edm":
-            raise NotImplementedError("only the EDM sampler is built (models/ddim.py:1239-1242)")
-        xs = self.sample_edm(cond_rep, u_noise, sp, return_last=sp.return_last, guide_dx=sp.guide_dx)
+        if sp.type == "edm":                                                 # models/ddim.py:1239-1242
+            xs = self.sample_edm(cond_rep, u_noise, sp, return_last=sp.return_last, guide_dx=sp.guide_dx)
+        else:
+            xs, _ = self.sample(cond_rep, u_noise, sp, return_last=sp.return_last, guide_dx=sp.guide_dx)
         xs_mean = xs.reshape(n, nb, *xs.shape[1:]).mean(dim=0)               # '(n b) t h w c -> n b t h w c', mean over n
         u_last = xs_mean[:, -1, :, :, :u_ch]
         loss_u = l1(u_last, u)
@@ -324,6 +327,9 @@ class PlCondEdm(_SingleTask):
         if not guide_dx:
             return torch.zeros_like(x_denoised)
         return self.get_dx_pde(cond, x_denoised, calc_prob=True)
+
+    def sample(self, h, u_noise, sparams, return_last=True, guide_dx=False):
+        raise NotImplementedError("Only EDM sampler is supported for the model with EDM pre-conditioning")      # models/ddim.py:1739-1740
 
     def sample_edm(self, h, u_noise, sparams, return_last=True, guide_dx=False):
         """h, u_noise in the reference's 'b h w c' layout; returns [b, t, h, w, c] float64 (models/ddim.py:1532-1601).
@@ -596,7 +602,8 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     step runs in the HIP library: noising (mcedm_eps_noise_inputs), the self-conditioning pre-pass and its estimate written into
     the network's widened conditioning input (mcedm_eps_self_cond), forward, loss (mcedm_eps_loss) and backward from dF
     (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample.  The DDPM U-Net (``name: ddim*``), the PDE loss term,
-    ``guide_dx``, ``dx_cond`` and the DDIM ``sample`` loop raise."""
+    ``guide_dx`` and ``dx_cond`` raise.  ``sample`` (the DDIM loop, :1452-1530) is
+    mcedm_cond_ddim_sample."""
 
     def __init__(self, hparams):
         super().__init__()
@@ -765,5 +772,34 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
                                       return_last=return_last, ws=self._sample_ws)
 
     def sample(self, *a, **k):
-        raise NotImplementedError("the DDIM sampling loop of PlCondDdim (models/ddim.py:1452-1531) is not built; "
-                                  "set the sampler type to 'edm' (sample_edm)")
+        """``sample(h, u_noise, sparams, return_last=True, guide_dx=False)`` of models/ddim.py:1452-1530 (the open signature is the
+        one the stub had, which tests/test_pl_layout_cpu.py pins; the arguments are bound by ``_ddim_sample``)."""
+        return self._ddim_sample(*a, **k)
+
+    def _ddim_sample(self, h, u_noise, sparams, return_last=True, guide_dx=False):
+        """models/ddim.py:1452-1530, the DDIM sampler (``type: ddim``, the reference's default sampler configuration): h, u_noise
+        in the reference's 'b h w c' layout; returns (xs, x0_preds), fp32 'b t h w c'.  The loop runs in mcedm_cond_ddim_sample:
+        per step one network pass (two with classifier-free guidance, |w| >= 0.001) and one fused kernel that also feeds the
+        x0 prediction back as the next step's x_self_cond.  With eta != 0 the per-step torch.rand_like(x) of :1512 (a UNIFORM
+        draw) is made up front as one torch.rand([S, B, C, H, W])."""
+        if guide_dx:
+            raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1501-1503) is not built for PlCondDdim")
+        if h is None:
+            raise NotImplementedError("sampling without the conditioning field h (models/ddim.py:1452-1531 hands cond=h to the "
+                                      "network in every step) is not built")
+        net =self._net(self.ema_model if self.ema_model is not None else self.model)
+        h, init = _nchw(h).float().contiguous(), _nchw(u_noise).float().contiguous()
+        dd = _lib.cond_ddim_desc(sparams, self._alphas_ext(), net.cond_channels, self._net(self.model).self_condition)
+        stochastic = abs(float(sparams.eta)) > 1e-10
+        S = len(_lib.ddim_timesteps(self.num_timesteps, dd.timesteps, dd.skip_type))
+        eta_noise = torch.rand((S,) + tuple(init.shape), dtype=torch.float32, device=init.device) if stochastic else None
+        cond = h if net.cond_channels > 0 else None
+        with torch.no_grad():
+            packed = net.packed_weights()
+            eager = lambda c, i, en: net.plan.cond_ddim_sample(packed, dd, c, i, en, return_last=return_last, ws=self._sample_ws)
+            # the evaluation loops repeat the call: it replays from one HIP graph, like sample_edm of the sibling modules
+            B, _, H, W = init.shape
+            key = ("ddim", B, H, W, bool(return_last), stochastic, packed.data_ptr(), init.device.index,
+                   tuple(getattr(dd, f) for f, _ in dd._fields_ if f != "alphas_cumprod_ext"))
+            return self._replay(key, lambda: _lib.GraphedCondDdim(net.plan, packed, dd, B, H, W, stochastic, return_last=return_last,
+                                                                  ws=self._sample_ws), eager, cond, init, eta_noise)

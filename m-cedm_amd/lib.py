@@ -34,6 +34,7 @@ EXPORTS = [
     "mcedm_unet_plan_set_variant", "mcedm_ddpm_plan_set_variant", "mcedm_heun_sample_rng",
     "mcedm_eps_noise_inputs", "mcedm_eps_self_cond", "mcedm_eps_loss", "mcedm_unet_backward", "mcedm_unet_backward_bucketed",
     "mcedm_vp_sampler_workspace_bytes", "mcedm_vp_heun_sample", "mcedm_vp_heun_sample_rng",
+    "mcedm_cond_ddim_workspace_bytes", "mcedm_cond_ddim_sample",
 ]
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
@@ -90,6 +91,13 @@ class VpSamplerDesc(C.Structure):
     """mcedm_vp_sampler_desc: the host arrays are kept alive by the Python object that built the struct (vp_sampler_desc)."""
     _fields_ = [("timesteps", C.c_int32), ("cond_channels", C.c_int32), ("t_steps", C.POINTER(C.c_double)),
                 ("t_hat", C.POINTER(C.c_double)), ("c_noise", C.POINTER(C.c_float)), ("S_noise", C.c_double), ("w", C.c_double)]
+
+
+class CondDdimDesc(C.Structure):
+    """mcedm_cond_ddim_desc: the schedule table is kept alive by the Python object that built the struct (cond_ddim_desc)."""
+    _fields_ = [("timesteps", C.c_int32), ("skip_type", C.c_int32), ("eta", C.c_double), ("w", C.c_double),
+                ("cond_channels", C.c_int32), ("self_cond", C.c_int32), ("num_diffusion_timesteps", C.c_int32),
+                ("alphas_cumprod_ext", C.POINTER(C.c_float))]
 
 
 _lib = None
@@ -190,6 +198,9 @@ def load() -> C.CDLL:
                                          vp]
     lib.mcedm_vp_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, i32,
                                              i32, vp]
+    lib.mcedm_cond_ddim_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.mcedm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, i32,
+                                           i32, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)          # AttributeError here == header/library drift
         if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
@@ -459,6 +470,29 @@ class Plan(_PlanBase):
                                              buf.data_ptr(), buf.numel(), B, H, W, _stream()), "vp_heun_sample")
         return out
 
+    def cond_ddim_workspace_bytes(self, B: int, H: int, W: int) -> int:
+        return self._bytes("mcedm_cond_ddim_workspace_bytes", "cond_ddim_workspace_bytes", B, H, W)
+
+    def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
+                         ws: Optional[Workspace] = None, out=None):
+        """mcedm_cond_ddim_sample (PlCondDdim.sample on the device) -> (xs, x0_preds), both fp32 'b t h w c': S + 1 and S
+        slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors)."""
+        B, _, H, W = init_noise.shape
+        ws = ws or Workspace()
+        buf = ws.get(self.cond_ddim_workspace_bytes(B, H, W), init_noise.device)
+        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
+        shapes = [(B, 1 if return_last else S + 1, H, W, self.in_channels), (B, 1 if return_last else S, H, W, self.in_channels)]
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=torch.float32, device=init_noise.device) for sh in shapes)
+        elif [tuple(o.shape) for o in out] != shapes:
+            raise RuntimeError(f"cond_ddim_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
+        if eta_noise is not None and tuple(eta_noise.shape) != (S,) + tuple(init_noise.shape):
+            raise RuntimeError(f"cond_ddim_sample: eta_noise must be {(S,) + tuple(init_noise.shape)}, got {tuple(eta_noise.shape)}")
+        check(self._lib.mcedm_cond_ddim_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise),
+                                               _ptr(eta_noise), _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(),
+                                               buf.numel(), B, H, W, _stream()), "cond_ddim_sample")
+        return out[0], out[1]
+
     def sample(self, packed, sd: SamplerDesc, cond, mask, init_noise, step_noise=None, return_last: bool = True,
                ws: Optional[Workspace] = None, out: Optional[torch.Tensor] = None,
                guidance: Optional["GuidanceDesc"] = None, dx_input: Optional["GuidanceDesc"] = None,
@@ -528,6 +562,20 @@ def ddim_desc(sp, alphas_ext: torch.Tensor, h_ch: int, u_ch: int, self_cond: boo
     d = DdimDesc(int(sp.timesteps), skip, float(sp.eta), int(sp.n_repeat), int(sp.n_time_h), int(sp.n_time_u), int(h_ch), int(u_ch),
                  int(ae.numel() - 1), int(bool(self_cond)), C.cast(ae.data_ptr(), C.POINTER(C.c_float)))
     return d, ae
+
+
+def cond_ddim_desc(sp, alphas_ext: torch.Tensor, cond_channels: int, self_cond: bool) -> CondDdimDesc:
+    """C description of PlCondDdim.sample's parameters (configs/diff_sampler/default.yaml, ddim_sampler*.yaml: timesteps,
+    skip_type, eta, w) with the schedule table cumprod(1 - cat(0, betas)) attached (it must outlive every call that reads it)."""
+    ae = alphas_ext.detach().to("cpu", torch.float32).contiguous()
+    skip = {"uniform": 0, "quad": 1}.get(str(sp.skip_type))
+    if skip is None:
+        raise NotImplementedError(f"skip_type {sp.skip_type}")             # models/ddim.py:1469-1470
+    w = getattr(sp, "w", None)
+    d = CondDdimDesc(int(sp.timesteps), skip, float(sp.eta), 0.0 if w is None else float(w), int(cond_channels),
+                     int(bool(self_cond)), int(ae.numel() - 1), C.cast(ae.data_ptr(), C.POINTER(C.c_float)))
+    d._keep = ae
+    return d
 
 
 def ddim_timesteps(num_diffusion_timesteps: int, timesteps: int, skip_type) -> List[int]:
@@ -792,6 +840,37 @@ class GraphedRepaint:
         return self.out
 
 
+class GraphedCondDdim:
+    """mcedm_cond_ddim_sample captured once and replayed, like GraphedSampler: the schedule is host arithmetic baked into the
+    kernel arguments, the inputs (cond, init_noise and, with eta != 0, the uniform draws of every step) are copied into static
+    buffers first.  Returns the instance's static (xs, x0_preds), overwritten by the next call."""
+
+    def __init__(self, plan: "Plan", packed: torch.Tensor, dd: CondDdimDesc, B: int, H: int, W: int, stochastic: bool,
+                 return_last: bool = True, ws: Optional[Workspace] = None):
+        dev = packed.device
+        self.plan, self.packed, self.dd, self.return_last = plan, packed, dd, return_last
+        Cc, S = plan.in_channels, len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
+        self.cond = torch.zeros((B, dd.cond_channels, H, W), device=dev) if dd.cond_channels > 0 else None
+        self.init = torch.zeros((B, Cc, H, W), device=dev)
+        self.eta_noise = torch.zeros((S, B, Cc, H, W), device=dev) if stochastic else None
+        self.out = (torch.empty((B, 1 if return_last else S + 1, H, W, Cc), device=dev),
+                    torch.empty((B, 1 if return_last else S, H, W, Cc), device=dev))
+        self.ws = _PinnedWorkspace(ws, plan.cond_ddim_workspace_bytes(B, H, W), dev)
+        self.graph = _capture(self._run, dev)
+
+    def _run(self):
+        self.plan.cond_ddim_sample(self.packed, self.dd, self.cond, self.init, self.eta_noise, self.return_last, self.ws, out=self.out)
+
+    def __call__(self, cond, init_noise, eta_noise=None):
+        for dst, src, name in ((self.cond, cond, "cond"), (self.init, init_noise, "init_noise"), (self.eta_noise, eta_noise, "eta_noise")):
+            if (dst is None) != (src is None):
+                raise RuntimeError(f"GraphedCondDdim: '{name}' presence differs from the captured call")
+            if dst is not None:
+                dst.copy_(src)
+        self.graph.replay()
+        return self.out
+
+
 def graphed_or_eager(cache: dict, key, build, eager, max_entries: int = 2):
     """Replay the cached graph for ``key`` (building it with ``build()`` on first use, at most ``max_entries`` kept, oldest
     evicted) and return ``fn`` such that fn(*args) runs the call; if the capture fails (another thread's HIP call under a
@@ -982,9 +1061,12 @@ def _bind_ops():
     lib.mcedm_op_pack_conv_wino.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
+    f32 = C.c_float
+    lib.mcedm_op_ddim_cond_step.argtypes = [vp, vp, vp, vp, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32,
+                                            i32, vp, i32, i32, vp, i32, i32, vp]
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
-              "mcedm_op_pack_conv_wino_dgrad"):
+              "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -995,7 +1077,8 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_wgrad_scratch_floats", "mcedm_op_conv_wgrad", "mcedm_op_gn_bwd", "mcedm_op_attention_bwd",
               "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
-              "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad"]
+              "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
+              "mcedm_op_ddim_cond_step"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1217,3 +1300,17 @@ def op_attention_bwd(qkv, a, da, heads):
     check(lib.mcedm_op_attention_bwd(_ptr(qkv), _ptr(a), _ptr(da), _ptr(dqkv), _ptr(lse), B, heads, H * W, _stream()),
           "op_attention_bwd")
     return dqkv
+
+
+def op_ddim_cond_step(xt, F, s0, s1, sa_next, c2, Fu=None, w=0.0, noise=None, c1=0.0, condp=None, condp_u=None, cond_channels=0,
+                      xs=None, t_xs=0, x0s=None, t_x0=0):
+    """One elementwise step of the conditional DDIM sampler (mcedm_op_ddim_cond_step) -> xt_next.  x0 is written into channels
+    [cond_channels, cond_channels + C) of condp / condp_u and into slot t_x0 of x0s, xt_next into slot t_xs of xs ('b t h w c')."""
+    lib = _bind_ops()
+    B, Cc, H, W = xt.shape
+    xt_next = torch.empty_like(xt)
+    check(lib.mcedm_op_ddim_cond_step(_ptr(xt), _ptr(F), _ptr(Fu), _ptr(noise), float(w), s0, s1, sa_next, c1, c2, _ptr(xt_next),
+                                      _ptr(condp), _ptr(condp_u), int(cond_channels), 0 if condp is None else condp.shape[1],
+                                      B, Cc, H, W, _ptr(xs), 0 if xs is None else xs.shape[1], int(t_xs), _ptr(x0s),
+                                      0 if x0s is None else x0s.shape[1], int(t_x0), _stream()), "op_ddim_cond_step")
+    return xt_next

@@ -319,12 +319,14 @@ class _PlBase(_Base):
         """One sampling call: ``eager(*args, **kw)`` with ``MCEDM_HIP_GRAPH=0``, otherwise replayed from one HIP graph
         (lib.GraphedSampler / lib.GraphedRepaint, built by ``build()`` on first use).  At most two graphs are kept per module
         (the evaluation loops repeat one call; a ragged last batch is the second), they borrow the module's sampler workspace,
-        a failed capture falls back to the eager call, and a replay's static output is cloned."""
+        a failed capture falls back to the eager call, and a replay's static output (a tensor, or a tuple of them) is cloned."""
         if os.environ.get("MCEDM_HIP_GRAPH", "1") == "0":
             return eager(*args, **kw)
         fn = _lib.graphed_or_eager(self._graphs, key, build, eager)
         out = fn(*args, **kw)
-        return out.clone() if fn is not eager else out
+        if fn is eager:
+            return out
+        return tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()
 
     # ---- evaluation bookkeeping both reference loops share (models/ddim.py:235-262, 652-698) ---------------------------
     def _joint_pde_loss(self, x_denoised, x_gt_unnorm=None, noise_level=None, clamp_loss=True, do_rearrange=True, reduce=True):
