@@ -103,6 +103,7 @@ void mcedm_unet_plan_destroy(mcedm_plan* plan);
 #define MCEDM_VARIANT_ATTN_FUSED 4      /* single-launch attention block at 8 x 8 x 64 (env MCEDM_ATTN_FUSED, default 1) */
 #define MCEDM_VARIANT_WGRAD_WINO 5      /* Winograd F(3x3, 2x2) weight gradient (env MCEDM_WGRAD_WINO, default 1) */
 #define MCEDM_VARIANT_CONV1X1_REG 6     /* register-direct GEMM for un-transformed 1x1 convs at >= 32 x 32 (env MCEDM_CONV1X1_REG, default 1) */
+#define MCEDM_VARIANT_CONV_WINO_FOLD 7  /* decoder skip projections computed in the Winograd conv1's epilogue (env MCEDM_WINO_FOLD, default 1); the workspace layout does not depend on it */
 int mcedm_unet_plan_set_variant(mcedm_plan* plan, int which, int value);
 
 /* Parameter table in DhariwalUNet.state_dict() order (parameters only, no buffers).
@@ -484,6 +485,24 @@ int mcedm_op_set_wgrad_wino(int enable);
  * default (env MCEDM_CONV1X1_REG, else on).  Results differ from conv_mfma_kernel's in the last bits only through ... nothing: both sum
  * over ci in ascending pairs; tests hold them to rtol 1e-5.  Read at every launch.  Process-global. */
 int mcedm_op_set_conv1x1_reg(int enable);
+/* The SKIP variant of the Winograd kernel (conv_wino.hip): conv1 of an un-resampled decoder block computes the block's 1x1 skip
+ * projection (Cout % 128 == 0, both sources % 16 == 0, 32 <= Cin <= 256) in its epilogue instead of reading it back from a launch
+ * of its own: 1 on, 0 off, -1 back to the default (env MCEDM_WINO_FOLD, else on).  Bit-identical results either way (the
+ * projection is summed in conv1x1_reg_kernel's order).  Read at every launch and at every forward; the workspace layout does not depend on it (the
+ * projected tensor stays reserved), so it may change between calls on one workspace.  Process-global. */
+int mcedm_op_set_conv_wino_fold(int enable);
+/* [Cout][Cin] weights of a 1x1 conv -> the MFMA-fragment order that mcedm_op_conv_skip's sk_wfrag expects;
+ * wfrag holds ((Cout + 31) / 32 * 32) * ((Cin + 7) / 8 * 8) floats, 16-byte aligned. */
+int mcedm_op_pack_conv_frag(const float* w, int Cout, int Cin, float* wfrag, void* stream);
+/* conv1 of a decoder block as a plan launches it (through the dispatcher): out[B, Cout, H, W] = conv3x3(act(coef(x))) + bias + either
+ * the residual res (same shape) or, with sk_wpk set, the folded 1x1 projection sk_bias + W * cat(sk_xa, sk_xb) (sk_wpk / sk_bias from
+ * mcedm_op_pack_conv with k = 1; sk_wfrag from mcedm_op_pack_conv_frag or NULL, without which the Winograd kernel does not take
+ * the fold).  wino: mcedm_op_pack_conv_wino's table or NULL.  gsum: NULL, or B * ceil(H / 4) * ceil(W / 8) * ceil(Cout / 4) * 2
+ * floats that receive the fused GroupNorm records of out. */
+int mcedm_op_conv_skip(const float* x, int Cin, const mcedm_coef* coef, int act, int H, int W, const float* wpk, const float* wino,
+                       const float* bias, const float* res, const float* sk_xa, const float* sk_xb, int sk_Ca, int sk_Cb,
+                       const float* sk_wpk, const float* sk_wfrag, const float* sk_bias, float* out, float* gsum, int Cout, int B,
+                       void* stream);
 /* The single-launch attention part of a UNetBlock at 8 x 8 x 64 channels (attn_fused.hip; inference only): 1 on, 0 off
  * (qkv conv + attention kernel + proj conv), -1 back to the default (env MCEDM_ATTN_FUSED, else on).  Process-global. */
 int mcedm_op_set_attn_fused(int enable);

@@ -41,8 +41,8 @@ void set_error(const char* fmt, ...);
 // (mcedm_*_plan_set_variant; a field of the plan, so two plans in one process -- on two threads or two streams -- cannot flip each
 // other's kernels), the process-wide test hooks mcedm_op_set_* (kernel-level calls have no plan), the environment.
 enum KernelVariant { KV_CONV_WINO = 0, KV_CONV_WINO1 = 1, KV_CONV_RESIDENT = 2, KV_CONV8 = 3, KV_ATTN_FUSED = 4, KV_WGRAD_WINO = 5,
-                     KV_CONV1X1_REG = 6, KV_COUNT = 7 };
-struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1}; };
+                     KV_CONV1X1_REG = 6, KV_CONV_WINO_FOLD = 7, KV_COUNT = 8 };
+struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1}; };
 const KernelVariants* current_variants();                 // of the executing plan-level call on this thread, or null
 struct VariantScope {                                      // first statement of every extern "C" function that takes a plan
   const KernelVariants* prev;
@@ -163,6 +163,10 @@ struct ConvArgs {
   GnArgs gn; int gn_on;
   int coef_rows;     // set by the launcher: 1 = coef holds Ca+Cb rows (per sample if coef_batch), 0 = a single identity row
   unsigned long long* dbg;   // diagnostics only (mcedm_op_set_conv_debug): 4 timestamps (10 ns) + CU id per workgroup
+  // optional: sk_wpk's weights once more in MFMA-fragment order (launch_pack_conv_frag).  With it the Winograd kernel serves the
+  // conv AND the projection (conv_wino.hip, the SKIP variant: the projection is computed in the epilogue); without it a conv
+  // with sk_wpk runs on the direct / resident kernels.  (Last member: the other members keep their kernel-argument offsets.)
+  const float* sk_wfrag;
 };
 
 int launch_conv(const ConvArgs& a, int taps, hipStream_t stream);
@@ -171,6 +175,11 @@ size_t conv_wino_packed_floats(int Cout, int Cin);
 int launch_pack_conv_wino(const float* w, float* dst, int Cout, int Cin, int transpose_flip, hipStream_t stream);   // w [Cout][Cin][3][3]; transpose_flip: w is [Cin][Cout][3][3], build the data-gradient weights
 bool conv_wino_applicable(const ConvArgs& a, int taps);
 bool conv_wino_shape_ok(int Cout, int Cin, int H, int W);
+// the SKIP variant: conv1 of an un-resampled block computes the block's 1x1 skip projection (sk_Ca + sk_Cb -> Cout) in its epilogue
+bool conv_wino_fold_shape_ok(int Cout, int sk_Ca, int sk_Cb, int H, int W);
+void set_conv_wino_fold(int enable);                     // 1 / 0, -1: default (env MCEDM_WINO_FOLD, else on)
+size_t conv_frag_packed_floats(int Cout, int Cin);       // a 1x1 conv's weights in MFMA-fragment order (ConvArgs::sk_wfrag)
+int launch_pack_conv_frag(const float* w, float* dst, int Cout, int Cin, hipStream_t stream);   // w [Cout][Cin]
 void set_conv_wino(int enable);                          // 1 / 0, -1: default (env MCEDM_WINOGRAD, else on)
 bool conv_wino_preferred(const ConvArgs& a);              // env MCEDM_WINOGRAD (default on), MCEDM_WINO_MIN_HW (default 32 x 32)
 int launch_conv_wino(const ConvArgs& a, hipStream_t stream);

@@ -42,6 +42,143 @@ __global__ void wino_pack_kernel(const float* __restrict__ w, float* __restrict_
   wino_pack_elem(w, dst, idx, Cout, Cin, coutp, tflip);
 }
 
+// The fragment-ordered copy of a 1x1 projection's weights that the SKIP variant reads (ConvArgs::sk_wfrag): per (8-channel
+// group, 32-channel output block, lane) the four k-steps of the A operand as ONE 16-byte load, like a single Winograd position
+// of wino_pack_elem: f32x4[((ci / 8) * (coutp / 32) + co / 32) * 64 + (co & 31) + 32 * (ci & 1)][(ci & 7) >> 1] = w[co][ci].
+__global__ void conv_frag_pack_kernel(const float* __restrict__ w, float* __restrict__ dst, int Cout, int Cin, int coutp, int cinp) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= coutp * cinp) return;
+  dst[idx] = frag_pack_value(w, idx, Cout, Cin, coutp);
+}
+
+// ---- the SKIP variant's epilogue (WinoSkipCfg): the residual of a decoder block's conv1 is the 1x1 projection of the block input,
+//   rv[co][px] = sk_bias[co] + sum_ci W[co][ci] * cat(sk_xa, sk_xb)[ci][px],
+// and a wave's share of it -- its 32 channels x (32 patches x the two pixels of the row it stores) -- has exactly the layout of two
+// 32 x 32 accumulator blocks (column = patch = lane & 31, one block per pixel of the pair), in registers that are free between the
+// output transform and init_acc().  So the wave computes it: K = 2 steps over the channel pairs (2 j, 2 j + 1), j ascending, from
+// the matrix pipe's zero, bias added afterwards -- conv1x1_reg_kernel's order, hence the bits of the tensor that kernel would have
+// stored -- while the exchange rounds of the output transform wait behind the stage barriers of this loop instead of their own.
+//   B operand: stages of 16 channels x the tile's 8 x 16 pixels = one 16-byte load per thread (thread = channel tid >> 5, row
+//   (tid & 31) >> 2, column quad tid & 3 = the pixel pairs of two neighbouring patches), committed to LDS one stage later in the
+//   order the MFMAs read it (conv_wino.hpp): four ds_read_b128 per stage and lane, one barrier per stage, two buffers.
+//   A operand: sk_wfrag, two 16-byte loads per stage and lane, one stage ahead in registers.
+template <class C, bool = C::SKIP>
+struct SkipFold {};
+template <class C>
+struct SkipFold<C, true> {
+  static constexpr int SKS = C::SKS, SKBUF = C::SKBUF, SKP = C::SKPITCH;
+  __amdgpu_buffer_rsrc_t rs_a, rs_b;                      // this sample's planes of sk_xa / sk_xb (the launcher checks < 4 GiB each)
+  unsigned voff, HW4;                                     // the staging load's lane offset; bytes per channel plane
+  int Ca, nsk;                                            // channels of sk_xa; stages
+  const f32x4* wf;
+  size_t wstride;
+  float* wr;                                              // LDS: where this thread commits its piece, where this lane's B fragments start
+  const float* rd;
+  f32x4 sld, sa[2];                                       // staged input (one stage ahead of the commit), this stage's A fragments
+
+  __device__ __forceinline__ f32x4 req(int s) const {
+    const int ci0 = SKS * s;                              // a stage lies in one source: sk_Ca % 16 == 0
+    if (ci0 < Ca) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, voff, (unsigned)ci0 * HW4, 0));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, voff, (unsigned)(ci0 - Ca) * HW4, 0));
+  }
+  __device__ __forceinline__ void commit(int buf) const {
+    float* d = wr + buf * SKBUF;
+    *reinterpret_cast<f32x2*>(d) = f32x2{sld[0], sld[1]};
+    *reinterpret_cast<f32x2*>(d + SKP) = f32x2{sld[2], sld[3]};
+  }
+  __device__ __forceinline__ void wreq(int s, f32x4 (&a)[2]) const {
+    a[0] = wf[(size_t)(2 * s) * wstride];
+    a[1] = wf[(size_t)(2 * s + 1) * wstride];
+  }
+  __device__ __forceinline__ void begin(const ConvArgs& p, float* skbuf, int n, int mblk, int mblocks, int y0, int x0, int tid, int lane, int hf) {
+    // an opaque copy of the thread index: everything below is derived from it HERE, once per tile -- hoisted out of the stream of
+    // stages these loop invariants would sit in registers through the K loop, which has none to spare (256)
+    asm volatile("" : "+v"(tid));
+    lane = tid & 63;
+    const unsigned HW = (unsigned)p.H * (unsigned)p.W;
+    HW4 = 4u * HW;
+    Ca = p.sk_Ca;
+    nsk = (p.sk_Ca + p.sk_Cb) / SKS;
+    rs_a = make_rsrc(p.sk_xa + (size_t)n * p.sk_Ca * HW, 4u * (unsigned)p.sk_Ca * HW);
+    rs_b = make_rsrc(p.sk_xb ? p.sk_xb + (size_t)n * p.sk_Cb * HW : nullptr, p.sk_xb ? 4u * (unsigned)p.sk_Cb * HW : 0u);
+    const int c16 = tid >> 5, row = (tid & 31) >> 2, q = tid & 3;
+    voff = 4u * ((unsigned)c16 * HW + (unsigned)(y0 + row) * (unsigned)p.W + (unsigned)(x0 + 4 * q));
+    wr = skbuf + ((row & 1) * 32 + (row >> 1) * WTX + 2 * q) * SKP + (c16 & 1) * 16 + 2 * (c16 >> 1);
+    rd = skbuf + (hf * 32 + (lane & 31)) * SKP + (lane >> 5) * 16;
+    wf = reinterpret_cast<const f32x4*>(p.sk_wfrag) + (size_t)mblk * 64 + lane;
+    wstride = (size_t)mblocks * 64;
+    sld = req(0);
+    wreq(0, sa);
+  }
+  // keep / send: the output transform's two pixel columns (conv_wino_kernel); v0 / v1 = keep + the partner's send + rv on return
+  __device__ __forceinline__ void run(float* xch, const float* skb, int wave, int pw, int lane, const f32x16 (&keep)[2], const f32x16 (&send)[2],
+                                      float (&v0)[16], float (&v1)[16]) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) xch[(wave * 16 + r) * 64 + lane] = send[0][r];
+    commit(0);
+    sld = req(1);                                         // nsk >= 2 (conv_wino_applicable)
+    f32x16 rv[2];
+    {
+      const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      float z = 0.f;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        asm volatile("" : "+v"(z));
+        rv[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(z, z, zero16, 0, 0, 0);
+      }
+    }
+    __syncthreads();                                      // stage 0 and round 0 of the exchange are in LDS
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v0[r] = keep[0][r] + xch[(pw * 16 + r) * 64 + lane];
+    f32x4 bq[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) bq[jj] = *reinterpret_cast<const f32x4*>(rd + 4 * jj);
+    for (int s = 0; s < nsk; ++s) {
+      f32x4 bqn[4], san[2];
+      wreq(s + 1 < nsk ? s + 1 : s, san);
+      // stage s + 1 goes to the buffer that stage s - 1 was read from (before the last barrier), stage s + 2 is requested; past the
+      // end both repeat the last stage (a buffer nobody reads, a load nobody uses): no branch
+      commit((s + 1) & 1);
+      sld = req(s + 2 < nsk ? s + 2 : nsk - 1);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) rv[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(sa[j >> 2][j & 3], bq[j >> 1][2 * (j & 1) + e], rv[e], 0, 0, 0);
+      // the stage barrier sits in the MIDDLE of the stage's MFMAs: the next stage's fragments are read right behind it and
+      // arrive under the second half (behind a barrier at the end of the stage both waves of a SIMD wait for LDS together;
+      // measured 45.8 k -> 45.1 k cycles per tile for the phase)
+      __syncthreads();
+      const float* b = rd + ((s + 1) & 1) * SKBUF;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) bqn[jj] = *reinterpret_cast<const f32x4*>(b + 4 * jj);
+      // the exchange rounds ride on these barriers: every wave read round 0 before its first MFMA, so round 1 may be written
+      // behind the first stage barrier and read behind the second
+      if (s == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xch[(wave * 16 + r) * 64 + lane] = send[1][r];
+      }
+      if (s == 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v1[r] = keep[1][r] + xch[(pw * 16 + r) * 64 + lane];
+      }
+#pragma unroll
+      for (int j = 4; j < 8; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) rv[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(sa[j >> 2][j & 3], bq[j >> 1][2 * (j & 1) + e], rv[e], 0, 0, 0);
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) bq[jj] = bqn[jj];
+      sa[0] = san[0];
+      sa[1] = san[1];
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float bs = skb[(r & 3) + 8 * (r >> 2)];
+      v0[r] = v0[r] + (rv[0][r] + bs);
+      v1[r] = v1[r] + (rv[1][r] + bs);
+    }
+  }
+};
+
 // UP: the conv input is the nearest-neighbour 2x up-sampling of the (activated) source (adm_blocks.py:69-73)
 // ACT = false: the launch has no activation (p.act == 0: the data-gradient convs of training, whose input is a raw gradient): the
 // plain variant's branch-free "evaluate SiLU and select" is compiled out -- ~20 of the ~58 vector instructions per chunk and lane,
@@ -50,6 +187,7 @@ template <class C, bool UP, bool ACT = true>
 __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(const ConvArgs p, int tiles_x, int tiles_img, int nch, int mblocks,
                                                                           int per, int mode) {
   constexpr int WSC = C::SC, VBUF = C::VBUF, RBUF = C::RBUF, MB = C::MB;
+  constexpr bool SKIP = C::SKIP;                                  // WinoSkipCfg: the epilogue computes the residual (the skip projection)
   extern __shared__ float lds[];
   const int Cin = p.Ca + p.Cb;
   float* const vbuf = lds;
@@ -58,6 +196,8 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   float* const xch = lds + C::LDS_ROWS_OFF + 4 * Cin;            // epilogue exchange (one 16-register round), then the records
   float* const red = xch + C::XCH_FLOATS;
   float* const bias_l = red + 2 * (C::MT / 2) * 3;                // this workgroup's MT bias values
+  float* const skb_l = bias_l + C::MT;                            // SKIP: the projection's MT bias values, then its two stage buffers
+  float* const skbuf = skb_l + C::MT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mb = wave % MB, hf = wave / MB;
@@ -245,6 +385,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   // ---- prologue (once per workgroup): transform rows of the sample, stages 0 .. 2 of the stream
   stage_coef_rows<C::NT>(p, n, cfl, tid);
   if (tid < C::MT) bias_l[tid] = p.bias ? p.bias[m0 + tid] : 0.f;
+  if constexpr (SKIP) { if (tid < C::MT) skb_l[tid] = p.sk_bias ? p.sk_bias[m0 + tid] : 0.f; }
   raw_load();
   __syncthreads();
   for (int sc = 0; sc < WSC; ++sc) raw_commit1(sc, rbuf);
@@ -404,8 +545,10 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     const unsigned rvoff = 4u * ((unsigned)cbase * (HWu >> 2) + (unsigned)(oy >> 1) * (p.W >> 1) + (ox >> 1));
     // A^T = [[1,1,1,0],[0,1,-1,-1]].  Over nu (register-local), then over xi across the two halves: row 0 of the patch =
     // T0 + T1 + T2, row 1 = T1 - T2 - T3 with T_xi the nu-reduced blocks; half 0 holds T0, T1, half 1 T2, T3.
-    float2 rv[16];                                        // residual: in flight during the rest of the transform and the exchange
     f32x16 keep[2], send[2];
+    float v0[16], v1[16];
+    SkipFold<C> sk;                                       // SKIP: the projection's first operands are requested here, under the transform
+    if constexpr (SKIP) sk.begin(p, skbuf, n, m0 / 32 + mb, mblocks, y0, x0, tid, lane, hf);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {                          // one pixel column at a time: fewer values live beside the accumulators
       const f32x16 t0 = j == 0 ? acc[0] + acc[1] + acc[2] : acc[1] - acc[2] - acc[3];
@@ -419,6 +562,12 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     // kernel spills 3 registers instead of 7, issues 64 fewer vector-memory instructions per tile and CU, and is 0.4 % faster.
     // Exchanging the halves through 16-byte LDS accesses, lane pitch 20 floats, measured 1.5 % slower at 128 channels.)
     __builtin_amdgcn_sched_barrier(0);                    // the accumulators are dead from here to the end of the epilogue
+    if constexpr (SKIP) {
+      WINO_EP(1)                                          // 1: output transform over nu, first projection requests
+      sk.run(xch, skb_l + 32 * mb + 4 * (lane >> 5), wave, wave ^ MB, lane, keep, send, v0, v1);
+      WINO_EP(2)                                          // 2: the projection with the two exchange rounds inside it
+    } else {
+    float2 rv[16];                                        // residual: in flight during the rest of the transform and the exchange
     if (p.res && p.res_mode == RS_DOWN) {
       // residual at double resolution: the 2x2 mean of the source (adm_blocks.py:75-77), two 16-byte loads per channel and
       // pixel pair, four channels in flight at a time (all sixteen would need 128 registers)
@@ -450,7 +599,6 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     }
     WINO_EP(1)                                            // 1: output transform over nu, weight + residual requests
     const int pw = wave ^ MB;
-    float v0[16], v1[16];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {                         // two rounds of 16 registers through the exchange area
 #pragma unroll
@@ -465,6 +613,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       if (j == 0) __syncthreads();
     }
     WINO_EP(2)                                            // 2: the two exchange rounds (incl. the wait for the residual)
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r)
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, make_float2(v0[r], v1[r])), rs_out, voff,
@@ -539,6 +688,13 @@ static int wino_env() {                                        // MCEDM_WINOGRAD
   if (env < 0) { const char* e = getenv("MCEDM_WINOGRAD"); env = e ? atoi(e) : 1; }
   return variant_choice(KV_CONV_WINO, g_wino, env);            // the executing plan's choice, the process-wide hook, the environment
 }
+static int g_wino_fold = -1; // -1: default (env MCEDM_WINO_FOLD, else on); 0 / 1: forced by mcedm_op_set_conv_wino_fold
+void set_conv_wino_fold(int enable) { g_wino_fold = enable; }
+static int wino_fold_env() {                                   // MCEDM_WINO_FOLD=0: the skip projection stays a launch of its own
+  static int env = -1;
+  if (env < 0) { const char* e = getenv("MCEDM_WINO_FOLD"); env = e ? atoi(e) : 1; }
+  return variant_choice(KV_CONV_WINO_FOLD, g_wino_fold, env);
+}
 static int wino_mode_env() {                                   // MCEDM_WINO_MODE: ablation bits of the -DMCEDM_WINO_TIMELINE build (else unused)
   static int env = -1;                                         // | 256: the interleaved, XCD-aware tile map (MCEDM_WINO_MAP, default on)
   if (env < 0) {
@@ -555,6 +711,16 @@ static int wino_min_hw_env() {                                 // MCEDM_WINO_MIN
   return env;
 }
 
+size_t conv_frag_packed_floats(int Cout, int Cin) { return (size_t)cout_padded(Cout) * (size_t)ceil_div(Cin, 8) * 8; }
+
+int launch_pack_conv_frag(const float* w, float* dst, int Cout, int Cin, hipStream_t stream) {
+  MCEDM_REQUIRE(w && dst && Cout > 0 && Cin > 0, "pack_conv_frag: bad arguments");
+  const int coutp = cout_padded(Cout), cinp = ceil_div(Cin, 8) * 8;
+  hipLaunchKernelGGL(conv_frag_pack_kernel, dim3(ceil_div(coutp * cinp, 256)), dim3(256), 0, stream, w, dst, Cout, Cin, coutp, cinp);
+  MCEDM_LAUNCH_CHECK("conv_frag_pack_kernel");
+  return MCEDM_OK;
+}
+
 size_t conv_wino_packed_floats(int Cout, int Cin) { return (size_t)16 * cout_padded(Cout) * (size_t)ceil_div(Cin, WKC) * WKC; }
 
 int launch_pack_conv_wino(const float* w, float* dst, int Cout, int Cin, int transpose_flip, hipStream_t stream) {
@@ -566,11 +732,29 @@ int launch_pack_conv_wino(const float* w, float* dst, int Cout, int Cin, int tra
   return MCEDM_OK;
 }
 
+// A folded 1x1 projection (ConvArgs::sk_*) is served by the SKIP variant of the plain, activated, 128-channel kernel: whole stages
+// of 16 channels out of either source (at least two: the exchange rounds ride on the first two stage barriers), 16-byte loads,
+// one sample of each source below the 4 GiB range of its buffer descriptor.
+static bool conv_wino_fold_ok(const ConvArgs& a) {
+  const int Csk = a.sk_Ca + a.sk_Cb;
+  const unsigned long long HW = (unsigned long long)a.H * a.W;
+  return wino_fold_env() != 0 && a.sk_wfrag && a.resample == RS_NONE && !a.res && a.act && a.Cout % 128 == 0 && a.sk_xa && a.sk_Ca > 0 &&
+         a.sk_Cb >= 0 && (a.sk_Cb > 0) == (a.sk_xb != nullptr) && a.sk_Ca % 16 == 0 && a.sk_Cb % 16 == 0 && Csk >= 32 && Csk <= 256 &&
+         (((size_t)a.sk_xa | (size_t)a.sk_xb | (size_t)a.sk_wfrag) & 15) == 0 && HW * 4ull * (unsigned long long)a.sk_Ca < (1ull << 32) &&
+         HW * 4ull * (unsigned long long)a.sk_Cb < (1ull << 32);
+}
+// plan-time question (build_layout): will conv1 of an un-resampled block (Csk -> Cout skip projection) take the fold?
+bool conv_wino_fold_shape_ok(int Cout, int sk_Ca, int sk_Cb, int H, int W) {
+  const int Csk = sk_Ca + sk_Cb;
+  return wino_fold_env() != 0 && conv_wino_shape_ok(Cout, Cout, H, W) && Cout % 128 == 0 && sk_Ca > 0 && sk_Ca % 16 == 0 && sk_Cb % 16 == 0 &&
+         Csk >= 32 && Csk <= 256 && (unsigned long long)H * W * 4ull * (unsigned long long)(sk_Ca > sk_Cb ? sk_Ca : sk_Cb) < (1ull << 32);
+}
+
 bool conv_wino_applicable(const ConvArgs& a, int taps) {
   // the plain variant stages its input with 16-byte loads (raw_load1): misaligned views take the direct kernel
   const bool aligned = a.resample != RS_NONE || (((size_t)a.xa | (size_t)a.xb) & 15) == 0;
   return taps == 9 && a.wino && (a.resample == RS_NONE || a.resample == RS_UP) && a.Cout % 64 == 0 && a.H % WPH == 0 && aligned &&
-         a.W % WPW == 0 && (a.Ca + a.Cb) % WKC == 0 && a.Ca % WKC == 0 && !a.sk_wpk && ((size_t)a.wino & 15) == 0 &&
+         a.W % WPW == 0 && (a.Ca + a.Cb) % WKC == 0 && a.Ca % WKC == 0 && (!a.sk_wpk || conv_wino_fold_ok(a)) && ((size_t)a.wino & 15) == 0 &&
          (!a.res || a.res_mode == RS_NONE || a.res_mode == RS_UP || a.res_mode == RS_DOWN) && (a.Ca + a.Cb) <= 1024;
 }
 
@@ -595,7 +779,9 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   const long long total = (long long)a.B * tiles_img;
   MCEDM_REQUIRE(total > 0 && total <= 0x7fffffffLL, "conv_wino: grid out of range");
   const int Cin = a.Ca + a.Cb, nch = Cin / WKC;
-  const int lds_bytes = (C::LDS_ROWS_OFF + 4 * Cin + C::XCH_FLOATS + C::RED_FLOATS) * 4;
+  int sk_floats = 0;
+  if constexpr (C::SKIP) sk_floats = C::SK_FLOATS;
+  const int lds_bytes = (C::LDS_ROWS_OFF + 4 * Cin + C::XCH_FLOATS + C::RED_FLOATS + sk_floats) * 4;
   MCEDM_REQUIRE(lds_bytes <= 160 * 1024 / (C::MB == 4 ? 1 : 2), "conv_wino: %d input channels exceed the LDS row table", Cin);
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> ncu[64];
@@ -607,8 +793,10 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
     MCEDM_HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     ncu[dev].store(n_cu > 0 ? n_cu : 256, std::memory_order_release);
     MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if constexpr (!C::SKIP) {                              // the SKIP variant exists in the plain, activated form only
+      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
     attr_set[dev].store(true, std::memory_order_release);
   }
   static int per_env = -1;                                 // MCEDM_WINO_PER: force the tiles per workgroup (A/B runs; must divide)
@@ -617,13 +805,17 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   if (per_env > 0 && tiles_img % per_env == 0) per = per_env;
   char name[64] = "";
   const bool noact = a.resample != RS_UP && !a.act;
-  if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<WinoCfg<%d>, %s, %s>", C::MB, a.resample == RS_UP ? "true" : "false",
+  if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<Wino%sCfg<%d>, %s, %s>", C::SKIP ? "Skip" : "", C::MB, a.resample == RS_UP ? "true" : "false",
                                noact ? "false" : "true");   // = rocprofv3's name
   const double px = (double)a.B * a.H * a.W;
+  const double skc = C::SKIP ? (double)(a.sk_Ca + a.sk_Cb) : 0.0;      // folded 1x1 projection: its own flops, input read and weights
   // algorithmic cost = the direct convolution's (2 * MAC); the kernel issues 4 / 9 of these as matrix flops
-  ProfScope ps(name, 2.0 * px * a.Cout * (double)Cin * 9,
-               4.0 * ((double)a.B * Cin * a.Hs * a.Ws + px * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * Cin * 9), stream);
-  if (a.resample == RS_UP)
+  ProfScope ps(name, 2.0 * px * a.Cout * ((double)Cin * 9 + skc),
+               4.0 * ((double)a.B * Cin * a.Hs * a.Ws + px * (a.Cout * (a.res ? 2 : 1) + skc) + (double)a.Cout * (Cin * 9 + skc)), stream);
+  if constexpr (C::SKIP)
+    hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
+                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+  else if (a.resample == RS_UP)
     hipLaunchKernelGGL((conv_wino_kernel<C, true>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
                        tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
   else if (noact)
@@ -648,6 +840,7 @@ int launch_conv_wino(const ConvArgs& a_in, hipStream_t stream) {
   { const int rc = conv_resolve_identity(a); if (rc != MCEDM_OK) return rc; }
   // 128 output channels per workgroup where they divide (fewer passes over the input), else 64; the 128-channel shape runs on
   // the one-wave-per-SIMD kernel (conv_wino1.hip) only when that is switched on (MCEDM_WINO1=1; off by default)
+  if (a.sk_wpk) return launch_wino_cfg<WinoSkipCfg<4>>(a, stream);      // the SKIP variant (conv_wino_fold_ok); never the one-wave kernel
   if (a.Cout % 128 == 0) {
     const int rc = try_launch_conv_wino1(a, stream);
     if (rc != -1) return rc;

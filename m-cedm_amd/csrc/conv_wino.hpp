@@ -21,8 +21,22 @@ struct WinoCfg {
   static constexpr int LDS_ROWS_OFF = 2 * VBUF + 2 * RBUF;              // transform rows start here (floats; 16-byte aligned)
   static constexpr int XCH_FLOATS = NW * 16 * 64;                       // epilogue exchange: one round of 16 registers x 64 lanes per wave
   static constexpr int RED_FLOATS = 2 * (MT / 2) * 3 + MT;              // statistics records of the two halves (pairs at most) + the bias row
+  static constexpr bool SKIP = false;                                   // see WinoSkipCfg
   static_assert(MB_ == 4 || MB_ == 2, "128 or 64 output channels per workgroup");
   static_assert(LDS_ROWS_OFF % 4 == 0, "LDS layout");
+};
+// The SKIP variant (ConvArgs::sk_wfrag): the epilogue COMPUTES the residual -- the decoder block's 1x1 skip projection of
+// cat(sk_xa, sk_xb), 32 channels x 64 pixels per wave -- on the matrix pipe instead of loading it.  A configuration class of its
+// own, so that it is an instantiation of its own and the other variants keep their code and their names.
+//   raw input: stages of SKS channels x the tile's 8 x 16 pixels, one 16-byte load per thread, through two LDS buffers in the
+//   B-operand order [row half][patch][channel parity][k-step][pixel of the pair]; patches SKPITCH = 36 floats apart (= 4 mod 32:
+//   the sixteen lanes of a ds_read_b128 group cover the 64 banks once)
+template <int MB_>
+struct WinoSkipCfg : WinoCfg<MB_> {
+  static constexpr bool SKIP = true;
+  static constexpr int SKS = 16, SKPITCH = 36, SKBUF = 64 * SKPITCH;
+  static constexpr int SK_FLOATS = WinoCfg<MB_>::MT + 2 * SKBUF;        // the projection's bias row, two stage buffers
+  static_assert(MB_ == 4, "the fold is built for the 128-channel workgroup (512 threads = 16 channels x 32 quads per stage)");
 };
 constexpr int RROWS = WPH + 2, RPITCH = WPW + 2; // raw tile with halo: 10 x 18
 constexpr int RPLANE = 196;                      // floats between channels of the raw tile (180 used); = 4 mod 32: hipcc merges the transform's two

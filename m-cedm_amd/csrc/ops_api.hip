@@ -79,6 +79,31 @@ extern "C" int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int 
   return launch_conv_wino(a, (hipStream_t)stream);
 }
 
+// A 1x1 conv's weights [Cout][Cin] in the MFMA-fragment order of ConvArgs::sk_wfrag (cout_padded(Cout) * ceil8(Cin) floats)
+extern "C" int mcedm_op_pack_conv_frag(const float* w, int Cout, int Cin, float* wfrag, void* stream) {
+  return launch_pack_conv_frag(w, wfrag, Cout, Cin, (hipStream_t)stream);
+}
+
+// conv1 of a decoder block as the plan launches it, through the dispatcher: out = conv3x3(silu(coef(x))) + bias + either the
+// residual `res`, or the folded 1x1 projection sk_bias + W_s * cat(sk_xa, sk_xb) (sk_wpk set; sk_wfrag: its fragment-ordered copy,
+// which lets the Winograd kernel's SKIP variant serve it), with the fused GroupNorm records in gsum (or null).
+extern "C" int mcedm_op_conv_skip(const float* x, int Cin, const mcedm_coef* coef, int act, int H, int W, const float* wpk, const float* wino,
+                                  const float* bias, const float* res, const float* sk_xa, const float* sk_xb, int sk_Ca, int sk_Cb,
+                                  const float* sk_wpk, const float* sk_wfrag, const float* sk_bias, float* out, float* gsum, int Cout,
+                                  int B, void* stream) {
+  MCEDM_REQUIRE(x && out && wpk && Cin > 0 && Cout > 0 && B > 0 && H > 0 && W > 0, "op_conv_skip: bad arguments");
+  MCEDM_REQUIRE(!(res && sk_wpk), "op_conv_skip: a residual or a folded projection, not both");
+  ConvArgs a{};
+  a.xa = x; a.Ca = Cin;
+  a.coef = reinterpret_cast<const Coef*>(coef); a.coef_batch = 1; a.act = act;
+  a.resample = RS_NONE; a.Hs = H; a.Ws = W; a.H = H; a.W = W;
+  a.wpk = wpk; a.wino = wino; a.bias = bias; a.res = res; a.res_mode = RS_NONE;
+  a.sk_xa = sk_xa; a.sk_xb = sk_xb; a.sk_Ca = sk_Ca; a.sk_Cb = sk_Cb; a.sk_wpk = sk_wpk; a.sk_wfrag = sk_wfrag; a.sk_bias = sk_bias;
+  SumTiles st;
+  a.out = out; a.Cout = Cout; a.B = B; a.gsum = gsum; a.gsum_tiles = gsum ? &st : nullptr;
+  return launch_conv(a, 9, (hipStream_t)stream);
+}
+
 // freqs[k] = (1/10000)^(k/half) exactly as the plan packs them (adm_blocks.py:193-196, endpoint=False)
 __global__ void op_freqs_kernel(float* f, int half) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -175,6 +200,11 @@ extern "C" int mcedm_op_set_conv_wino(int enable) {
 
 extern "C" int mcedm_op_set_conv_wino1(int enable) {
   set_conv_wino1(enable);
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_op_set_conv_wino_fold(int enable) {
+  set_conv_wino_fold(enable);
   return MCEDM_OK;
 }
 

@@ -40,6 +40,15 @@ __device__ __forceinline__ float pack_conv_value(const float* __restrict__ w, si
   return v;
 }
 
+// value of element i of a 1x1 conv's weights in MFMA-fragment order (ConvArgs::sk_wfrag, conv_wino.hip SkipFold):
+// dst[(((ci / 8) * (coutp / 32) + co / 32) * 64 + (co & 31) + 32 * (ci & 1)) * 4 + ((ci & 7) >> 1)] = w[co][ci], zero-padded
+__device__ __forceinline__ float frag_pack_value(const float* __restrict__ w, int i, int Cout, int Cin, int coutp) {
+  const int s = i & 3, lane = (i >> 2) & 63, blk = i >> 8;
+  const int mblocks = coutp / 32, mb = blk % mblocks, g = blk / mblocks;
+  const int co = 32 * mb + (lane & 31), ci = 8 * g + 2 * s + (lane >> 5);
+  return (co < Cout && ci < Cin) ? w[(size_t)co * Cin + ci] : 0.f;
+}
+
 // U = G g G^T for one (cout, cin) = element idx of [coutp][nch * WKC]: G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 // tflip: the data-gradient weights, w'[co][ci][a][b] = w[ci][co][2 - a][2 - b] (w is then [Cin][Cout][3][3])
 __device__ __forceinline__ void wino_pack_elem(const float* __restrict__ w, float* __restrict__ dst, int idx, int Cout, int Cin, int coutp,

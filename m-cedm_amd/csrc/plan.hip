@@ -77,6 +77,10 @@ static void place_conv(Taker& t, ConvP& c, bool dgrad) {
     if (dgrad && c.cin % 64 == 0 && c.cout % 8 == 0) c.wino_dgrad = t.take(conv_wino_packed_floats(c.cin, c.cout));
   }
 }
+// a skip projection that the Winograd kernel's SKIP variant can compute in conv1's epilogue (conv_wino.hip): fragment order
+static void place_skip_frag(Taker& t, ConvP& c) {
+  if (c.taps == 1 && c.cout % 128 == 0 && c.cin % 16 == 0 && c.cin >= 32 && c.cin <= 256) c.wfrag = t.take(conv_frag_packed_floats(c.cout, c.cin));
+}
 static void place_norm(Taker& t, NormP& n) { n.gamma = t.take(n.C); n.beta = t.take(n.C); }
 
 }  // namespace mcedm
@@ -193,7 +197,7 @@ extern "C" int mcedm_unet_plan_create(const mcedm_unet_desc* d, mcedm_plan** out
     for (BlockP& b : *v) {
       place_norm(t, b.norm0); place_conv(t, b.conv0, true);
       place_norm(t, b.norm1); place_conv(t, b.conv1, true);
-      if (b.skip_kernel == 1) place_conv(t, b.skip, true);
+      if (b.skip_kernel == 1) { place_conv(t, b.skip, true); if (!b.up && !b.down) place_skip_frag(t, b.skip); }
       if (b.attn) { place_norm(t, b.norm2); place_conv(t, b.qkv, true); place_conv(t, b.proj, true); }
     }
   place_norm(t, P.out_norm);
@@ -249,7 +253,7 @@ constexpr int PACK_MAX = 48;
 struct PackJob {
   const float* w; float* dst;
   int Cout, Cin, taps, KC, coutp, qkv_heads, tflip;
-  int kind;                     // 0: direct form (pack_conv_value), 1: Winograd F(2x2, 3x3) form (wino_pack_elem)
+  int kind;                     // 0: direct form (pack_conv_value), 1: Winograd F(2x2, 3x3) form (wino_pack_elem), 2: fragment order (frag_pack_value)
   unsigned total;               // elements to walk: packed floats (direct) or coutp * nch * WKC (Winograd)
 };
 struct PackBatch { PackJob j[PACK_MAX]; };
@@ -259,6 +263,7 @@ __global__ void pack_batch_kernel(PackBatch b) {
   const PackJob& J = b.j[blockIdx.y];
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < J.total; i += gridDim.x * blockDim.x) {
     if (J.kind == 0) J.dst[i] = pack_conv_value(J.w, i, J.Cout, J.Cin, J.taps, J.KC, J.coutp, J.qkv_heads, J.tflip);
+    else if (J.kind == 2) J.dst[i] = frag_pack_value(J.w, (int)i, J.Cout, J.Cin, J.coutp);
     else wino_pack_elem(J.w, J.dst, (int)i, J.Cout, J.Cin, J.coutp, J.tflip);
   }
 }
@@ -281,13 +286,16 @@ struct Packer {
   void add(const PackJob& j) {
     b.j[count] = j;
     // direct tables: one float read per float written; Winograd: 9 taps read, 16 positions written per (cout, cin)
-    bytes += j.kind == 0 ? 8.0 * j.total : 4.0 * (9.0 + 16.0) * j.total;
+    bytes += j.kind != 1 ? 8.0 * j.total : 4.0 * (9.0 + 16.0) * j.total;
     if (++count == PACK_MAX) flush();
   }
   void conv(const float* w, float* dst, int Cout, int Cin, int taps, int qkv_heads, int tflip) {
     const size_t total = conv_packed_floats(Cout, Cin, taps);
     if (total >= (1ull << 32)) { set_error("pack: table too large"); status = MCEDM_ERR_INVALID; return; }
     add(PackJob{w, dst, Cout, Cin, taps, conv_kc_for(taps), cout_padded(Cout), qkv_heads, tflip, 0, (unsigned)total});
+  }
+  void frag(const float* w, float* dst, int Cout, int Cin) {
+    add(PackJob{w, dst, Cout, Cin, 1, 8, cout_padded(Cout), 0, 0, 2, (unsigned)conv_frag_packed_floats(Cout, Cin)});
   }
   void wino(const float* w, float* dst, int Cout, int Cin, int tflip) {
     const int coutp = cout_padded(Cout), nch = ceil_div(Cin, WKC);
@@ -323,6 +331,7 @@ static int pack_conv(const ConvP& c, const float* const* params, float* pk, Copi
   if (c.wpk_dgrad != NONE) pp.conv(params[c.w], pk + c.wpk_dgrad, c.cin, c.cout, c.taps, c.qkv_heads, 1);
   if (c.wino != NONE) pp.wino(params[c.w], pk + c.wino, c.cout, c.cin, 0);
   if (c.wino_dgrad != NONE) pp.wino(params[c.w], pk + c.wino_dgrad, c.cin, c.cout, 1);
+  if (c.wfrag != NONE) pp.frag(params[c.w], pk + c.wfrag, c.cout, c.cin);
   return pp.status;
 }
 
@@ -473,9 +482,15 @@ int build_layout(const mcedm_plan& P, int B, int H, int W, int training, int n_n
     // ... and for blocks whose conv1 the Winograd kernel serves (conv_wino.hip): a 1x1 projection has nothing to gain
     // from that transform (it would cost 16 multiplies per output instead of 1), so it runs as its own launch there
     // and enters conv1 as a residual
-    (void)training;
+    // ... unless that kernel's SKIP variant takes the projection into conv1's epilogue (inference only: training runs as before;
+    // a choice by shape and channels, never by the batch).  The tensor stays RESERVED all the same: the workspace a caller sized
+    // is then good for either path -- the fold can be switched per call (mcedm_op_set_conv_wino_fold, MCEDM_WINO_FOLD) without
+    // laying the workspace out again -- and a plan's workspace_bytes is what it was
     const bool wino1 = b.conv1.wino != NONE && conv_wino_shape_ok(b.cout, b.cout, bl.H, bl.W);
+    const bool wfold = wino1 && !training && !b.up && !b.down && b.skip_kernel == 1 && b.skip.wfrag != NONE &&
+                       conv_wino_fold_shape_ok(b.cout, L.t[xa].C, xb >= 0 ? L.t[xb].C : 0, bl.H, bl.W);
     if (b.skip_kernel == 1 && (b.up || b.down || wino1)) bl.sk = lb.act(b.cout, bl.H, bl.W);
+    bl.wfold = wfold ? 1 : 0;
     bl.y = lb.act(b.cout, bl.H, bl.W);
     give_sums(bl.y);
     lb.drop(bl.h); lb.drop(bl.coef1); lb.drop(bl.sk);
@@ -596,7 +611,7 @@ static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl
   // skip path
   const float* res = xa;
   int res_mode = RS_NONE;
-  const bool fold_skip = b.skip_kernel == 1 && bl.sk < 0;      // see build_layout
+  const bool fold_skip = b.skip_kernel == 1 && (bl.sk < 0 || bl.wfold);      // see build_layout
   if (b.skip_kernel == 1 && !fold_skip) {
     ConvArgs cs{};
     cs.xa = xa; cs.xb = xb; cs.Ca = Ca; cs.Cb = Cb;
@@ -620,6 +635,7 @@ static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl
     c1.res = nullptr; c1.res_mode = RS_NONE;
     c1.sk_xa = xa; c1.sk_xb = xb; c1.sk_Ca = Ca; c1.sk_Cb = Cb;
     c1.sk_wpk = pk + b.skip.wpk; c1.sk_bias = pk + b.skip.bias;
+    c1.sk_wfrag = b.skip.wfrag != NONE ? pk + b.skip.wfrag : nullptr;
   }
   c1.out = T(bl.y); c1.Cout = b.cout; c1.B = B; c1.gsum = SUMS(bl.y); c1.gsum_tiles = &st[bl.y];
   if ((rc = gn_for_conv(g1, c1, false, s))) return rc;

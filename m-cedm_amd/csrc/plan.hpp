@@ -114,6 +114,7 @@ struct ConvP {   // one Conv2d with weights
   size_t wpk = NONE, bias = NONE;      // float offsets into the packed buffer
   size_t wpk_dgrad = NONE;             // transposed + mirrored weights for the data gradient
   size_t wino = NONE, wino_dgrad = NONE;   // both again in Winograd F(2x2, 3x3) form (conv_wino.hip) where that kernel can serve
+  size_t wfrag = NONE;                 // a 1x1 skip projection's weights in MFMA-fragment order (ConvArgs::sk_wfrag) where conv1 may fold it
 };
 
 struct NormP {
@@ -150,6 +151,7 @@ struct BlockLayout {
   int stats0 = -1, stats1 = -1, stats2 = -1;
   int xd = -1;                 // down blocks: the activated, 2x2-averaged input of conv0 (temporary)
   int out = -1;                // y or z
+  int wfold = 0;               // conv1 (Winograd kernel, SKIP variant) computes the 1x1 skip projection itself; `sk` stays reserved
   int Hin = 0, Win = 0, H = 0, W = 0;
 };
 

@@ -38,7 +38,8 @@ EXPORTS = [
 ]
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
-VARIANTS = {"conv_wino": 0, "conv_wino1": 1, "conv_resident": 2, "conv8": 3, "attn_fused": 4, "wgrad_wino": 5, "conv1x1_reg": 6}
+VARIANTS = {"conv_wino": 0, "conv_wino1": 1, "conv_resident": 2, "conv8": 3, "attn_fused": 4, "wgrad_wino": 5, "conv1x1_reg": 6,
+            "conv_wino_fold": 7}
 
 
 class UNetDesc(C.Structure):
@@ -1061,12 +1062,14 @@ def _bind_ops():
     lib.mcedm_op_pack_conv_wino.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
+    lib.mcedm_op_pack_conv_frag.argtypes = [vp, i32, i32, vp, vp]
+    lib.mcedm_op_conv_skip.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]
     f32 = C.c_float
     lib.mcedm_op_ddim_cond_step.argtypes = [vp, vp, vp, vp, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32,
                                             i32, vp, i32, i32, vp, i32, i32, vp]
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
-              "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step"):
+              "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1078,7 +1081,7 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
-              "mcedm_op_ddim_cond_step"]
+              "mcedm_op_ddim_cond_step", "mcedm_op_set_conv_wino_fold", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1129,6 +1132,14 @@ def set_conv1x1_reg(enable: int = -1) -> None:
     lib = _bind_ops()
     lib.mcedm_op_set_conv1x1_reg.argtypes = [C.c_int]
     check(lib.mcedm_op_set_conv1x1_reg(int(enable)), "set_conv1x1_reg")
+
+
+def set_conv_wino_fold(enable: int = -1) -> None:
+    """The Winograd conv1 of an un-resampled decoder block computes the block's 1x1 skip projection in its epilogue (conv_wino.hip,
+    the SKIP variant): 1 / 0 (a conv1x1_reg_kernel launch plus a residual read); -1 = default (on).  Same bits either way."""
+    lib = _bind_ops()
+    lib.mcedm_op_set_conv_wino_fold.argtypes = [C.c_int]
+    check(lib.mcedm_op_set_conv_wino_fold(int(enable)), "set_conv_wino_fold")
 
 
 def set_wgrad_wino(enable: int = -1) -> None:
@@ -1229,6 +1240,29 @@ def op_conv_wino(xa, xb, wino, bias, Cout, coef=None, coef_batch=1, act=0, resam
     check(lib.mcedm_op_conv_wino(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, H, W, _ptr(wino),
                                  _ptr(bias), _ptr(res), res_mode, _ptr(out), Cout, B, _stream()), "op_conv_wino")
     return out
+
+
+def op_pack_conv_frag(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 1, 1] -> the 1x1 weights in the MFMA-fragment order op_conv_skip's sk_wfrag expects."""
+    lib = _bind_ops()
+    Cout, Cin = w.shape[:2]
+    wfrag = torch.empty((Cout + 31) // 32 * 32 * ((Cin + 7) // 8 * 8), dtype=torch.float32, device=w.device)
+    check(lib.mcedm_op_pack_conv_frag(_ptr(w), Cout, Cin, _ptr(wfrag), _stream()), "op_pack_conv_frag")
+    return wfrag
+
+
+def op_conv_skip(x, wpk, wino, bias, Cout, coef=None, act=1, res=None, sk_xa=None, sk_xb=None, sk_wpk=None, sk_wfrag=None,
+                 sk_bias=None, want_sums=False):
+    """conv1 of a decoder block through the dispatcher (mcedm_op_conv_skip): 3x3 conv of act(coef(x)) plus either the residual
+    res or the folded 1x1 projection of cat(sk_xa, sk_xb).  -> out, or (out, the fused GroupNorm records) with want_sums."""
+    lib = _bind_ops()
+    B, Cin, H, W = x.shape
+    out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
+    gsum = torch.zeros(B * ((H + 3) // 4) * ((W + 7) // 8) * ((Cout + 3) // 4) * 2, dtype=torch.float32, device=x.device) if want_sums else None
+    check(lib.mcedm_op_conv_skip(_ptr(x), Cin, _ptr(coef), act, H, W, _ptr(wpk), _ptr(wino), _ptr(bias), _ptr(res), _ptr(sk_xa), _ptr(sk_xb),
+                                 sk_xa.shape[1] if sk_xa is not None else 0, sk_xb.shape[1] if sk_xb is not None else 0, _ptr(sk_wpk),
+                                 _ptr(sk_wfrag), _ptr(sk_bias), _ptr(out), _ptr(gsum), Cout, B, _stream()), "op_conv_skip")
+    return (out, gsum) if want_sums else out
 
 
 def op_embedding(labels, w0, b0, w1, b1, waff, baff):

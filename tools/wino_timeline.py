@@ -1,11 +1,15 @@
 """In-kernel timeline of the Winograd conv: per-workgroup stamps (start, prologue end, K loop end, end).
-    MCEDM_WINO_MODE=1 python tools/wino_timeline.py [B cin hw [cout]]      (cout 64: the 256-thread WinoCfg<2> variant)"""
+    MCEDM_WINO_MODE=1 python tools/wino_timeline.py [B cin hw [cout [sk]]]      (cout 64: the 256-thread WinoCfg<2> variant)
+sk > 0: conv1 of a decoder block with its 1x1 skip projection of sk channels (two sources of sk / 2) folded in -- the SKIP variant
+(MCEDM_WINO_FOLD=0: the same conv on the direct kernels) -- instead of a residual; with MCEDM_WINO_MODE=32 the second epilogue
+phase is then the projection with the exchange rounds inside it (budget: 48 k cycles per tile at 256 channels)."""
 import ctypes as C, importlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lib = importlib.import_module("m-cedm_amd.lib")
 B, cin, hw = (int(v) for v in (sys.argv[1:4] + ["32", "128", "128"][len(sys.argv) - 1:]))
 cout = int(sys.argv[4]) if len(sys.argv) > 4 else 128
+sk = int(sys.argv[5]) if len(sys.argv) > 5 else 0
 x = torch.randn(B, cin, hw, hw, device="cuda")
 w = torch.randn(cout, cin, 3, 3, device="cuda") / (cin * 9) ** 0.5
 b = torch.randn(cout, device="cuda")
@@ -14,6 +18,13 @@ coef = torch.stack([torch.zeros(B, cin), torch.ones(B, cin), torch.zeros(B, cin)
 wino = lib.op_pack_conv_wino(w)
 out = torch.empty(B, cout, hw, hw, device="cuda")
 run = lambda: lib.op_conv_wino(x, None, wino, b, cout, coef=coef, act=1, res=res, out=out)
+if sk:
+    ws = torch.randn(cout, sk, 1, 1, device="cuda") / sk ** 0.5
+    wpk, bpk = lib.op_pack_conv(w, b)
+    spk, sbias = lib.op_pack_conv(ws, b)
+    sfrag = lib.op_pack_conv_frag(ws)
+    sa, sb = torch.randn(B, sk // 2, hw, hw, device="cuda"), torch.randn(B, sk // 2, hw, hw, device="cuda")
+    run = lambda: lib.op_conv_skip(x, wpk, wino, bpk, cout, coef=coef, sk_xa=sa, sk_xb=sb, sk_wpk=spk, sk_wfrag=sfrag, sk_bias=sbias)
 for _ in range(3):
     run()
 torch.cuda.synchronize()
@@ -37,7 +48,7 @@ d = d[d[:, 0] != 0]
 per = int(d[0, 4])
 t0 = d[:, 0].min()
 st, pro, loop, end = [(d[:, i] - t0) / 100.0 for i in range(4)]
-flops = 2.0 * B * hw * hw * cout * cin * 9
+flops = 2.0 * B * hw * hw * cout * (cin * 9 + sk)
 cyc = np.median(d[:, 6] - d[:, 5]) / per
 clk = np.median((d[:, 6] - d[:, 5]) / ((d[:, 2] - d[:, 1]) * 10e-9) / 1e9)
 nch = cin // 8
@@ -53,7 +64,7 @@ elif int(os.environ.get("MCEDM_WINO_MODE", "0")) & 16:
           + "  ".join(f"s{j} {np.mean(d[:, 8 + j]) / nst / per:.0f}" for j in range(8)))
 elif int(os.environ.get("MCEDM_WINO_MODE", "0")) & 32:
     print("   wave 0 cycles per TILE in the epilogue: " + "  ".join(f"{nm} {np.mean(d[:, 8 + j]) / per:.0f}" for j, nm in enumerate(
-        ["nu-transform + requests", "exchange rounds", "stores", "statistics", "accumulator init"])))
+        ["nu-transform + requests", "projection + exchange rounds" if sk else "exchange rounds", "stores", "statistics", "accumulator init"])))
 elif d[:, 8:13].max() > 0:
     print("   wave 0 cycles per chunk: " + "  ".join(f"{nm} {np.mean(d[:, 8 + j]) / nch / per:.0f}" for j, nm in enumerate(["top", "mfma stream", "barrier", "epilogue"])))
     if d[:, 13:16].max() > 0:      # the SIMD partner of wave 0 (wave MB: the same channel block, the other row half)
