@@ -182,6 +182,13 @@ int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* packed, const m
                              const mcedm_guidance_desc* gd, const float* cond, const float* mask,
                              const float* init_noise, const double* step_noise, double* out, int return_last,
                              void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+/* mcedm_heun_sample_guided with rng_seed in place of step_noise: the churn draws are generated on the device exactly as in
+ * mcedm_heun_sample_rng (draw index = step index; mcedm_normal_fill's tensors fed to mcedm_heun_sample_guided reproduce the call
+ * bit for bit).  A NULL rng_seed is MCEDM_ERR_ARGUMENT; every other check is mcedm_heun_sample_guided's. */
+int mcedm_heun_sample_guided_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                 const mcedm_guidance_desc* gd, const float* cond, const float* mask, const float* init_noise,
+                                 const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes,
+                                 int B, int H, int W, void* stream);
 /* ---- dx_cond: the network conditioned on the PDE-residual gradient (plans with dx_mode != MCEDM_DX_NONE) ----------
  * The same three calls with the extra network input dx [B, dx_channels, H, W] (DhariwalUNet.forward(..., dx=dx),
  * adm_blocks.py:364-388; model_precond / get_denoised with dx, models/ddim.py:1661-1666, 1745-1763).  dx == NULL is the
@@ -211,6 +218,11 @@ int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* packed, const m
                              const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
                              const float* init_noise, const double* step_noise, double* out, int return_last,
                              void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+/* The same with rng_seed in place of step_noise (draw index = step index, as in mcedm_heun_sample_rng). */
+int mcedm_heun_sample_dxcond_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                 const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+                                 const float* init_noise, const uint64_t* rng_seed, double* out, int return_last, void* workspace,
+                                 size_t workspace_bytes, int B, int H, int W, void* stream);
 /* Host helper: the float64 sigma schedule of mcedm.py:584-588 (timesteps+1 values, last = 0). */
 int mcedm_edm_t_steps(const mcedm_sampler_desc* sp, double* t_steps);
 
@@ -358,6 +370,16 @@ int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, int H, int W,
 int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
                            const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out, int return_last,
                            void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+/* mcedm_cond_ddim_sample with rng_seed in place of eta_noise: the fused step kernel generates the uniform draw of step k (in the
+ * order the steps are walked) itself, as draw k of the uniform generator below (mcedm_uniform_fill) keyed by the 64-bit seed at
+ * *rng_seed in DEVICE memory, read when the kernel runs -- one Philox block per 16-byte group in registers instead of a 16-byte
+ * load, no [S, B, in, H, W] tensor, and a captured HIP graph replays with fresh noise once the host has rewritten the seed.
+ * Bit-for-bit contract: mcedm_uniform_fill(slice k of eta_noise, B * in * H * W, rng_seed, k) for every k, handed to
+ * mcedm_cond_ddim_sample, reproduces this call.  With |eta| <= 1e-10 the seed is never read.  A NULL rng_seed is
+ * MCEDM_ERR_ARGUMENT; every other check is mcedm_cond_ddim_sample's. */
+int mcedm_cond_ddim_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                               const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last,
+                               void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
 
 /* ---- kernel-level entry points ----------------------------------------------------------
  * The building blocks the schedules above are made of, exported so that each kernel can be
@@ -453,6 +475,12 @@ int mcedm_op_ddim_cond_step(const float* xt, const float* F, const float* Fu, co
                             float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u, int cond_channels,
                             int plan_cond_channels, int B, int C, int H, int W, float* xs, int T_xs, int t_xs, float* x0s,
                             int T_x0, int t_x0, void* stream);
+/* The same step with `noise` generated in the kernel: draw `draw` of mcedm_uniform_fill keyed by *rng_seed (device memory).  The
+ * value of an element depends on (seed, draw, element index) only, not on whether the 16-byte or the scalar path computed it. */
+int mcedm_op_ddim_cond_step_rng(const float* xt, const float* F, const float* Fu, const uint64_t* rng_seed, uint64_t draw, double w,
+                                float s0, float s1, float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u,
+                                int cond_channels, int plan_cond_channels, int B, int C, int H, int W, float* xs, int T_xs,
+                                int t_xs, float* x0s, int T_x0, int t_x0, void* stream);
 /* Test hook: force the conv tile (channel tile mt in {32,64,128}, pixel tile ph x pw in {8x32,8x16,16x16,8x8};
  * (128,16,32) = the 8-wave kernel, 3x3 only);
  * (0,0,0) restores the size heuristic.  Process-global, not thread-safe. */
@@ -594,6 +622,12 @@ int mcedm_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, co
                              void* workspace, size_t workspace_bytes, int B, void* stream);
 /* out[0 .. n) = the N(0, 1) values of draw `draw` of that generator (fp64). */
 int mcedm_normal_fill(double* out, size_t n, const uint64_t* rng_seed, uint64_t draw, void* stream);
+/* The UNIFORM stream of the same generator (the DDIM samplers' torch.rand_like draws): out[e], e in [0, n), is word e % 4 of the
+ * Philox4x32-10 block with key = the seed at *rng_seed and counter (lo32(e / 4), hi32(e / 4), lo32(draw), hi32(draw) | 0x80000000),
+ * as u = (word >> 8) * 2^-24 -- fp32, in [0, 1), exactly representable, torch.rand's 24-bit granularity.  The set top bit of the
+ * counter keeps these blocks disjoint from every block of the normal stream (whose draw indices stay below 2^63) under the same
+ * seed.  out needs no particular alignment. */
+int mcedm_uniform_fill(float* out, size_t n, const uint64_t* rng_seed, uint64_t draw, void* stream);
 
 /* Model.forward(x, t, x_self_cond) with the self-conditioning tensor given (ddim_blocks.py:417-420; NULL = zeros, i.e.
  * mcedm_ddpm_forward).  x_self_cond [B, in_channels, R, R]. */
@@ -622,6 +656,13 @@ int mcedm_ddim_timesteps(int num_diffusion_timesteps, int timesteps, int skip_ty
 int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp, const float* hu,
                               const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out, int return_last,
                               void* workspace, size_t workspace_bytes, int B, void* stream);
+/* The same with rng_seed in place of eta_noise: step k (in the order the steps are walked) uses draw k of mcedm_uniform_fill,
+ * generated inside the step kernel; feeding mcedm_ddim_repaint_sample the tensors mcedm_uniform_fill writes reproduces the call
+ * bit for bit.  With |eta| <= 1e-10 the seed is never read.  A NULL rng_seed is MCEDM_ERR_ARGUMENT; every other check is
+ * mcedm_ddim_repaint_sample's. */
+int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp, const float* hu,
+                                  const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
+                                  int return_last, void* workspace, size_t workspace_bytes, int B, void* stream);
 
 /* ---- PDE residuals (forward) ----------------------------------------------
  * Replace the tensor-op bodies of models/pde_loss.py; results are bit-identical to the PyTorch CPU path.

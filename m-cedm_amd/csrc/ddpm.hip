@@ -867,6 +867,11 @@ extern "C" int mcedm_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void*
   return repaint_impl(plan, packed, sp, hu, init_noise, nullptr, nullptr, reinterpret_cast<const unsigned long long*>(rng_seed),
                       out, return_last, workspace, workspace_bytes, B, stream);
 }
+extern "C" int mcedm_uniform_fill(float* out, size_t n, const uint64_t* rng_seed, uint64_t draw, void* stream) {
+  MCEDM_REQUIRE(out && rng_seed, "uniform_fill: null argument");
+  if (n == 0) return MCEDM_OK;
+  return launch_uniform_fill(out, reinterpret_cast<const unsigned long long*>(rng_seed), draw, n, (hipStream_t)stream);
+}
 extern "C" int mcedm_normal_fill(double* out, size_t n, const uint64_t* rng_seed, uint64_t draw, void* stream) {
   MCEDM_REQUIRE(out && rng_seed, "normal_fill: null argument");
   if (n == 0) return MCEDM_OK;
@@ -912,11 +917,10 @@ extern "C" int mcedm_ddim_timesteps(int num_diffusion_timesteps, int timesteps, 
   return MCEDM_OK;
 }
 
-extern "C" int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp,
-                                         const float* hu, const float* init_noise, const float* eta_noise, float* xs_out,
-                                         float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
-                                         void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+// eta_noise / rng_seed: the uniform draws of the stochastic steps, read from slice k or generated in the step kernel as draw k
+static int ddim_repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp, const float* hu,
+                             const float* init_noise, const float* eta_noise, const unsigned long long* rng_seed, float* xs_out,
+                             float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
   MCEDM_REQUIRE(plan && packed && sp && hu && init_noise && xs_out && workspace, "ddim_repaint_sample: null argument");
   const mcedm_ddpm_plan& P = *plan;
   MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "ddim_repaint_sample: in_channels != out_channels");
@@ -926,7 +930,7 @@ extern "C" int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void
   MCEDM_REQUIRE(sp->h_ch >= 0 && sp->u_ch >= 0 && sp->h_ch + sp->u_ch <= P.desc.in_channels, "ddim_repaint_sample: h_ch + u_ch exceeds the state channels");
   MCEDM_REQUIRE(!sp->self_cond || P.desc.self_cond, "ddim_repaint_sample: self-conditioning asked of a network built without it");
   const bool stochastic = std::fabs(sp->eta) > 1e-10;                   // ddim.py:884
-  MCEDM_REQUIRE(!stochastic || eta_noise != nullptr, "ddim_repaint_sample: eta != 0 needs eta_noise");
+  MCEDM_REQUIRE(!stochastic || eta_noise != nullptr || rng_seed != nullptr, "ddim_repaint_sample: eta != 0 needs eta_noise");
   // the timestep sequence (ddim.py:823-830) and its predecessor list (:845)
   std::vector<int> seq = ddim_timestep_seq(n, N, sp->skip_type);
   const int S = (int)seq.size();
@@ -976,8 +980,11 @@ extern "C" int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void
     } else {
       c2 = sqrtf(1.0f - at_next);
     }
-    if ((rc = launch_ddim_next(x0, et, hu, init_noise, mask, stochastic ? eta_noise + (size_t)step * total : nullptr, sqrtf(at_next), c1,
-                               c2, total, xt, s))) return rc;
+    if (stochastic && rng_seed) {
+      if ((rc = launch_ddim_next_rng(x0, et, hu, init_noise, mask, rng_seed, (unsigned long long)step, sqrtf(at_next), c1, c2, total,
+                                     xt, s))) return rc;
+    } else if ((rc = launch_ddim_next(x0, et, hu, init_noise, mask, stochastic ? eta_noise + (size_t)step * total : nullptr,
+                                      sqrtf(at_next), c1, c2, total, xt, s))) return rc;
     if (!return_last) {
       if ((rc = launch_store_f32(xt, C, hw, step + 1, Txs, total, xs_out, s))) return rc;
       if (x0_out && (rc = launch_store_f32(x0, C, hw, step, Tx0, total, x0_out, s))) return rc;
@@ -988,4 +995,23 @@ extern "C" int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void
     if (x0_out && (rc = launch_store_f32(x0, C, hw, 0, 1, total, x0_out, s))) return rc;
   }
   return MCEDM_OK;
+}
+
+extern "C" int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp,
+                                         const float* hu, const float* init_noise, const float* eta_noise, float* xs_out,
+                                         float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
+                                         void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return ddim_repaint_impl(plan, packed, sp, hu, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
+                           workspace_bytes, B, stream);
+}
+
+extern "C" int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp,
+                                             const float* hu, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
+                                             float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
+                                             void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "ddim_repaint_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return ddim_repaint_impl(plan, packed, sp, hu, init_noise, nullptr, reinterpret_cast<const unsigned long long*>(rng_seed), xs_out,
+                           x0_out, return_last, workspace, workspace_bytes, B, stream);
 }

@@ -248,6 +248,38 @@ int launch_normal_fill(double* out, const unsigned long long* seed_dev, unsigned
   return MCEDM_OK;
 }
 
+// ---- counter-based uniform noise (the DDIM samplers' torch.rand_like, models/ddim.py:893, 1512) ---------------------------
+// Element e of draw d is word e % 4 of the Philox4x32-10 block with counter (lo32(e / 4), hi32(e / 4), lo32(d), hi32(d) | 2^31),
+// key = the seed: the set top bit keeps these blocks apart from every block of the normal generator above, whose draw indices
+// stay below 2^63.  u = (word >> 8) * 2^-24: fp32, in [0, 1), exact, torch.rand's granularity.  One block serves a 16-byte group.
+__device__ __forceinline__ float4 uniform_group(unsigned long long seed, unsigned long long draw, size_t g) {
+  unsigned ctr[4] = {(unsigned)g, (unsigned)((unsigned long long)g >> 32), (unsigned)draw, (unsigned)(draw >> 32) | 0x80000000u};
+  philox4x32_10(ctr, (unsigned)seed, (unsigned)(seed >> 32));
+  constexpr float k = 1.0f / 16777216.0f;
+  return make_float4((float)(ctr[0] >> 8) * k, (float)(ctr[1] >> 8) * k, (float)(ctr[2] >> 8) * k, (float)(ctr[3] >> 8) * k);
+}
+// the same value for one element, whichever path asks for it (scalar tails, unaligned tensors)
+__device__ __forceinline__ float uniform_element(unsigned long long seed, unsigned long long draw, size_t e) {
+  const float4 u = uniform_group(seed, draw, e >> 2);
+  const unsigned k = (unsigned)e & 3u;
+  return k == 0 ? u.x : k == 1 ? u.y : k == 2 ? u.z : u.w;
+}
+// out[i] = U[0, 1) of draw `draw` (the generator on its own): n4 full groups stored as float4 (out 16-byte aligned), the rest
+// element by element
+__global__ void uniform_fill_kernel(float* __restrict__ out, const unsigned long long* __restrict__ seed_dev, unsigned long long draw,
+                                    size_t n4, size_t total) {
+  const unsigned long long seed = *seed_dev;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t g = tid; g < n4; g += stride) reinterpret_cast<float4*>(out)[g] = uniform_group(seed, draw, g);
+  for (size_t i = 4 * n4 + tid; i < total; i += stride) out[i] = uniform_element(seed, draw, i);
+}
+int launch_uniform_fill(float* out, const unsigned long long* seed_dev, unsigned long long draw, size_t total, hipStream_t s) {
+  const size_t n4 = (reinterpret_cast<size_t>(out) & 15) == 0 ? total / 4 : 0;
+  hipLaunchKernelGGL(uniform_fill_kernel, dim3(grid_for(n4 ? n4 : total)), dim3(256), 0, s, out, seed_dev, draw, n4, total);
+  MCEDM_LAUNCH_CHECK("uniform_fill_kernel");
+  return MCEDM_OK;
+}
+
 // ---- RePaint-style EDM sampling on the DDPM U-Net (PlDdim, models/ddim.py:915-1051) -------------------------------
 __global__ void vp_finish_kernel(const float* __restrict__ x, const float* __restrict__ F, float c_out, size_t total,
                                  float* __restrict__ D) {
@@ -375,6 +407,45 @@ int launch_ddim_next(const float* x0, const float* et, const float* hu, const fl
   MCEDM_LAUNCH_CHECK("ddim_next_kernel");
   return MCEDM_OK;
 }
+// The same step with the uniform draw generated in the kernel (launch_ddim_next_rng): every thread takes four consecutive
+// elements -- one Philox block, 16-byte loads and one 16-byte store -- for the n4 full groups (all pointers 16-byte aligned), the
+// rest element by element with the value uniform_fill_kernel writes for that element.
+__device__ __forceinline__ float ddim_next_point(float x0, float et, float hu, float hn, float m, float nz, float sa, float c1, float c2) {
+  const float v = (sa * x0 + c1 * nz) + c2 * et;
+  const float known = sa * hu + c2 * hn;
+  return known * m + v * (1.0f - m);
+}
+__global__ __launch_bounds__(256) void ddim_next_rng_kernel(const float* __restrict__ x0, const float* __restrict__ et,
+                                                            const float* __restrict__ hu, const float* __restrict__ hn,
+                                                            const float* __restrict__ mask,
+                                                            const unsigned long long* __restrict__ seed_dev, unsigned long long draw,
+                                                            float sa, float c1, float c2, size_t n4, size_t total, float* __restrict__ xt) {
+  const unsigned long long seed = *seed_dev;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t g = tid; g < n4; g += stride) {
+    const float4 a = reinterpret_cast<const float4*>(x0)[g], e = reinterpret_cast<const float4*>(et)[g];
+    const float4 h = reinterpret_cast<const float4*>(hu)[g], n = reinterpret_cast<const float4*>(hn)[g];
+    const float4 m = reinterpret_cast<const float4*>(mask)[g], u = uniform_group(seed, draw, g);
+    float4 r;
+    r.x = ddim_next_point(a.x, e.x, h.x, n.x, m.x, u.x, sa, c1, c2);
+    r.y = ddim_next_point(a.y, e.y, h.y, n.y, m.y, u.y, sa, c1, c2);
+    r.z = ddim_next_point(a.z, e.z, h.z, n.z, m.z, u.z, sa, c1, c2);
+    r.w = ddim_next_point(a.w, e.w, h.w, n.w, m.w, u.w, sa, c1, c2);
+    reinterpret_cast<float4*>(xt)[g] = r;
+  }
+  for (size_t i = 4 * n4 + tid; i < total; i += stride)
+    xt[i] = ddim_next_point(x0[i], et[i], hu[i], hn[i], mask[i], uniform_element(seed, draw, i), sa, c1, c2);
+}
+int launch_ddim_next_rng(const float* x0, const float* et, const float* hu, const float* hn, const float* mask,
+                         const unsigned long long* seed_dev, unsigned long long draw, float sa, float c1, float c2, size_t total,
+                         float* xt, hipStream_t s) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; };
+  const size_t n4 = al16(x0) && al16(et) && al16(hu) && al16(hn) && al16(mask) && al16(xt) ? total / 4 : 0;
+  hipLaunchKernelGGL(ddim_next_rng_kernel, dim3(grid_for(n4 ? n4 : total)), dim3(256), 0, s, x0, et, hu, hn, mask, seed_dev, draw, sa,
+                     c1, c2, n4, total, xt);
+  MCEDM_LAUNCH_CHECK("ddim_next_rng_kernel");
+  return MCEDM_OK;
+}
 __global__ void ddim_init_kernel(const float* __restrict__ hu, const float* __restrict__ hn, const float* __restrict__ mask,
                                  float sa, float sb, size_t total, float* __restrict__ xt) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -407,7 +478,7 @@ int launch_store_f32(const float* x, int C, size_t hw, int t, int T, size_t tota
 __device__ __forceinline__ void ddim_cond_point(const DdimCondStep& a, float x, float f, float fu, float nz, float& x0, float& xn) {
   const float et = a.Fu ? a.w1 * f - a.w * fu : f;                     // (w + 1) * model(cond) - w * model(None)   (:1497)
   x0 = (x - et * a.s1) / a.s0;                                         // (xt - et * (1 - at).sqrt()) / at.sqrt()   (:1505)
-  xn = a.noise ? (a.sa * x0 + a.c1 * nz) + a.c2 * et : a.sa * x0 + a.c2 * et;        // (:1512 / :1515)
+  xn = (a.noise || a.seed) ? (a.sa * x0 + a.c1 * nz) + a.c2 * et : a.sa * x0 + a.c2 * et;        // (:1512 / :1515)
 }
 // element i of the [B, C, H, W] state -> its places in cond' / twin and in the trajectories
 __device__ __forceinline__ void ddim_cond_scatter(const DdimCondStep& a, size_t i, float x0, float xn) {
@@ -426,10 +497,11 @@ __device__ __forceinline__ void ddim_cond_scatter(const DdimCondStep& a, size_t 
 __global__ __launch_bounds__(256) void ddim_cond_step_kernel(DdimCondStep a, size_t n4, int vec_sc, int vec_tr) {
   const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const unsigned long long seed = a.seed ? *a.seed : 0ull;             // the draws come from the generator: no noise load
   for (size_t g = tid; g < n4; g += stride) {
     const float4 x = reinterpret_cast<const float4*>(a.xt)[g], f = reinterpret_cast<const float4*>(a.F)[g];
     const float4 fu = a.Fu ? reinterpret_cast<const float4*>(a.Fu)[g] : zero4;
-    const float4 nz = a.noise ? reinterpret_cast<const float4*>(a.noise)[g] : zero4;
+    const float4 nz = a.seed ? uniform_group(seed, a.draw, g) : a.noise ? reinterpret_cast<const float4*>(a.noise)[g] : zero4;
     float4 x0, xn;
     ddim_cond_point(a, x.x, f.x, fu.x, nz.x, x0.x, xn.x);
     ddim_cond_point(a, x.y, f.y, fu.y, nz.y, x0.y, xn.y);
@@ -463,7 +535,8 @@ __global__ __launch_bounds__(256) void ddim_cond_step_kernel(DdimCondStep a, siz
   }
   for (size_t i = 4 * n4 + tid; i < a.n; i += stride) {                // scalar tail (everything, when a pointer is not 16-byte aligned)
     float x0, xn;
-    ddim_cond_point(a, a.xt[i], a.F[i], a.Fu ? a.Fu[i] : 0.f, a.noise ? a.noise[i] : 0.f, x0, xn);
+    const float nz = a.seed ? uniform_element(seed, a.draw, i) : a.noise ? a.noise[i] : 0.f;
+    ddim_cond_point(a, a.xt[i], a.F[i], a.Fu ? a.Fu[i] : 0.f, nz, x0, xn);
     a.xt_next[i] = xn;
     ddim_cond_scatter(a, i, x0, xn);
   }

@@ -21,6 +21,9 @@ int launch_heun_churn(double* x, const double* eps, const float* mask, double c,
 int launch_heun_churn_rng(double* x, const unsigned long long* seed_dev, unsigned long long draw, double c, size_t total, float* x32,
                           hipStream_t s, const float* mask = nullptr);
 int launch_normal_fill(double* out, const unsigned long long* seed_dev, unsigned long long draw, size_t total, hipStream_t s);
+// out[e] = U[0, 1) in fp32, (word >> 8) * 2^-24 with word e % 4 of the Philox block at counter (e / 4, draw | 2^63): the draws of
+// the DDIM step kernels (launch_ddim_next_rng, DdimCondStep::seed), disjoint from the normal generator's blocks
+int launch_uniform_fill(float* out, const unsigned long long* seed_dev, unsigned long long draw, size_t total, hipStream_t s);
 // dxg / wgt / gdiv: optional PDE-guidance term of the single-task sampler, d -= (double)((wgt * dxg) / gdiv) formed in fp32
 // (models/ddim.py:1577-1579, 1590-1591: `weight * dx / t_hat`, with t_hat in BOTH stages)
 int launch_heun_euler(const double* x_hat, const float* D, const float* mask, double t_hat, double dt, size_t total,
@@ -70,6 +73,10 @@ int launch_ddim_x0(float* xt, const float* et, const float* hu, const float* mas
 // xt_next = sa * x0 + [c1 * noise +] c2 * et;  xt_next = (sa * hu + c2 * hn) * m + xt_next * (1 - m)   (:884-895)
 int launch_ddim_next(const float* x0, const float* et, const float* hu, const float* hn, const float* mask, const float* noise,
                      float sa, float c1, float c2, size_t total, float* xt, hipStream_t s);
+// the stochastic step with `noise` = draw `draw` of launch_uniform_fill, generated in the kernel
+int launch_ddim_next_rng(const float* x0, const float* et, const float* hu, const float* hn, const float* mask,
+                         const unsigned long long* seed_dev, unsigned long long draw, float sa, float c1, float c2, size_t total,
+                         float* xt, hipStream_t s);
 // x = (hu * sa + hn * sb) * m + hn * (1 - m)   (:837-838)
 int launch_ddim_init(const float* hu, const float* hn, const float* mask, float sa, float sb, size_t total, float* xt, hipStream_t s);
 // 'b c h w -> b t h w c' for one time slot, fp32
@@ -100,8 +107,11 @@ static inline std::vector<int> ddim_timestep_seq(int n, int N, int skip_type) {
 // ---- DDIM sampler of the conditional ADM U-Net (PlCondDdim.sample, models/ddim.py:1452-1530), all fp32: one step
 //   et = w1 * F - w * Fu (Fu != NULL) or F;  x0 = (xt - et * s1) / s0;  xt_next = sa * x0 [+ c1 * noise] + c2 * et   (:1497-1515)
 // in one pass that also puts x0 and xt_next where they are read next.  Every pointer but xt, F and xt_next may be NULL.
+// seed != NULL (then noise is NULL): the kernel generates `noise` itself, draw `draw` of launch_uniform_fill keyed by *seed.
 struct DdimCondStep {
   const float *xt, *F, *Fu, *noise;        // [B, C, H, W]
+  const unsigned long long* seed;          // device memory, read when the kernel runs
+  unsigned long long draw;
   float w1, w, s0, s1, sa, c1, c2;
   float* xt_next;                          // [B, C, H, W]
   float *sc, *sc_u;                        // [B, Cp, H, W] cond' and its zero-cond twin: x0 -> channels [sc_off, sc_off + C)

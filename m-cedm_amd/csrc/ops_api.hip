@@ -234,10 +234,10 @@ extern "C" int mcedm_op_set_conv_debug(unsigned long long* buf) {
 }
 
 // one step of the conditional DDIM sampler (edm.hip: ddim_cond_step_kernel) on caller-owned tensors
-extern "C" int mcedm_op_ddim_cond_step(const float* xt, const float* F, const float* Fu, const float* noise, double w, float s0,
-                                       float s1, float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u,
-                                       int cond_channels, int plan_cond_channels, int B, int C, int H, int W, float* xs,
-                                       int T_xs, int t_xs, float* x0s, int T_x0, int t_x0, void* stream) {
+static int op_ddim_cond_step(const float* xt, const float* F, const float* Fu, const float* noise, const uint64_t* rng_seed,
+                             uint64_t draw, double w, float s0, float s1, float sa_next, float c1, float c2, float* xt_next,
+                             float* condp, float* condp_u, int cond_channels, int plan_cond_channels, int B, int C, int H, int W,
+                             float* xs, int T_xs, int t_xs, float* x0s, int T_x0, int t_x0, void* stream) {
   MCEDM_REQUIRE(xt && F && xt_next, "op_ddim_cond_step: null pointer");
   MCEDM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "op_ddim_cond_step: empty shape");
   MCEDM_REQUIRE(!condp_u || condp, "op_ddim_cond_step: the twin goes with cond'");
@@ -246,9 +246,27 @@ extern "C" int mcedm_op_ddim_cond_step(const float* xt, const float* F, const fl
   MCEDM_REQUIRE((!xs || (t_xs >= 0 && t_xs < T_xs)) && (!x0s || (t_x0 >= 0 && t_x0 < T_x0)), "op_ddim_cond_step: slot outside the trajectory");
   DdimCondStep k{};
   k.xt = xt; k.F = F; k.Fu = Fu; k.noise = noise;
+  k.seed = reinterpret_cast<const unsigned long long*>(rng_seed); k.draw = draw;
   k.w1 = (float)(w + 1.0); k.w = (float)w; k.s0 = s0; k.s1 = s1; k.sa = sa_next; k.c1 = c1; k.c2 = c2;
   k.xt_next = xt_next; k.sc = condp; k.sc_u = condp_u;
   k.C = C; k.Cp = plan_cond_channels; k.sc_off = cond_channels; k.hw = (size_t)H * W; k.n = (size_t)B * C * k.hw;
   k.xs = xs; k.x0s = x0s; k.T_xs = T_xs; k.t_xs = t_xs; k.T_x0 = T_x0; k.t_x0 = t_x0;
   return launch_ddim_cond_step(k, (hipStream_t)stream);
+}
+extern "C" int mcedm_op_ddim_cond_step(const float* xt, const float* F, const float* Fu, const float* noise, double w, float s0,
+                                       float s1, float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u,
+                                       int cond_channels, int plan_cond_channels, int B, int C, int H, int W, float* xs,
+                                       int T_xs, int t_xs, float* x0s, int T_x0, int t_x0, void* stream) {
+  return op_ddim_cond_step(xt, F, Fu, noise, nullptr, 0, w, s0, s1, sa_next, c1, c2, xt_next, condp, condp_u, cond_channels,
+                           plan_cond_channels, B, C, H, W, xs, T_xs, t_xs, x0s, T_x0, t_x0, stream);
+}
+// the same step with its uniform noise generated in the kernel: draw `draw` of mcedm_uniform_fill keyed by *rng_seed
+extern "C" int mcedm_op_ddim_cond_step_rng(const float* xt, const float* F, const float* Fu, const uint64_t* rng_seed, uint64_t draw,
+                                           double w, float s0, float s1, float sa_next, float c1, float c2, float* xt_next,
+                                           float* condp, float* condp_u, int cond_channels, int plan_cond_channels, int B, int C,
+                                           int H, int W, float* xs, int T_xs, int t_xs, float* x0s, int T_x0, int t_x0,
+                                           void* stream) {
+  MCEDM_REQUIRE(rng_seed != nullptr, "op_ddim_cond_step_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return op_ddim_cond_step(xt, F, Fu, nullptr, rng_seed, draw, w, s0, s1, sa_next, c1, c2, xt_next, condp, condp_u, cond_channels,
+                           plan_cond_channels, B, C, H, W, xs, T_xs, t_xs, x0s, T_x0, t_x0, stream);
 }

@@ -150,24 +150,42 @@ extern "C" int mcedm_heun_sample_rng(const mcedm_plan* plan, const void* packed,
                           B, H, W, nullptr, stream, nullptr, rng_seed);
 }
 
-extern "C" int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                                        const mcedm_guidance_desc* gd, const float* cond, const float* mask,
-                                        const float* init_noise, const double* step_noise, double* out, int return_last,
-                                        void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+// the two PDE entries, each with its draws read from step_noise or generated from rng_seed (at most one of them non-NULL)
+static int heun_guided(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp, const mcedm_guidance_desc* gd,
+                       const float* cond, const float* mask, const float* init_noise, const double* step_noise,
+                       const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes, int B, int H,
+                       int W, void* stream) {
   MCEDM_REQUIRE(gd != nullptr && (gd->system == 1 || gd->system == 2), "heun_sample_guided: guidance system must be 1 (SWE) or 2 (Darcy)");
   MCEDM_REQUIRE(plan && plan->desc.in_channels == 1 && plan->desc.cond_channels >= 1 && cond != nullptr && mask == nullptr,
                 "heun_sample_guided: PDE guidance is defined for the single-task sampler (state u, conditioning h in cond[:, 0]; "
                 "mask NULL), models/ddim.py:1532-1601; the joint model's hook fails in the reference (models/mcedm.py:500-518)");
   return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
-                          B, H, W, gd, stream, nullptr, nullptr);
+                          B, H, W, gd, stream, nullptr, rng_seed);
 }
 
-extern "C" int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
-                                        const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+extern "C" int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                        const mcedm_guidance_desc* gd, const float* cond, const float* mask,
                                         const float* init_noise, const double* step_noise, double* out, int return_last,
                                         void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return heun_guided(plan, packed, sp, gd, cond, mask, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B,
+                     H, W, stream);
+}
+
+extern "C" int mcedm_heun_sample_guided_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                            const mcedm_guidance_desc* gd, const float* cond, const float* mask,
+                                            const float* init_noise, const uint64_t* rng_seed, double* out, int return_last,
+                                            void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_guided_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return heun_guided(plan, packed, sp, gd, cond, mask, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B,
+                     H, W, stream);
+}
+
+static int heun_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp, const mcedm_guidance_desc* dxc,
+                       const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const double* step_noise,
+                       const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes, int B, int H,
+                       int W, void* stream) {
   MCEDM_REQUIRE(dxc != nullptr && (dxc->system == 1 || dxc->system == 2), "heun_sample_dxcond: dx system must be 1 (SWE) or 2 (Darcy)");
   MCEDM_REQUIRE(gd == nullptr || gd->system == 1 || gd->system == 2, "heun_sample_dxcond: guidance system must be 1 (SWE) or 2 (Darcy)");
   MCEDM_REQUIRE(plan && plan->desc.dx_mode != MCEDM_DX_NONE && plan->desc.dx_channels == 1 && plan->desc.in_channels == 1 &&
@@ -175,7 +193,26 @@ extern "C" int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* pack
                 "heun_sample_dxcond: needs a dx_cond plan of the single-task model (state u, conditioning h in cond[:, 0], one dx "
                 "channel), models/ddim.py:1424-1450, 1532-1601");
   return heun_sample_impl(plan, packed, sp, cond, nullptr, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
-                          B, H, W, gd, stream, dxc, nullptr);
+                          B, H, W, gd, stream, dxc, rng_seed);
+}
+
+extern "C" int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                        const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+                                        const float* init_noise, const double* step_noise, double* out, int return_last,
+                                        void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return heun_dxcond(plan, packed, sp, dxc, gd, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B,
+                     H, W, stream);
+}
+
+extern "C" int mcedm_heun_sample_dxcond_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
+                                            const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+                                            const float* init_noise, const uint64_t* rng_seed, double* out, int return_last,
+                                            void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_dxcond_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return heun_dxcond(plan, packed, sp, dxc, gd, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B,
+                     H, W, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -322,11 +359,10 @@ extern "C" int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, in
   return rc;
 }
 
-extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
-                                      const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out,
-                                      int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
-                                      void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+// eta_noise / rng_seed: the uniform draws of the stochastic steps, read from slice k or generated in the step kernel as draw k
+static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                          const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
+                          int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
   MCEDM_REQUIRE(plan && packed && sp && init_noise && xs_out && x0_out && workspace, "cond_ddim_sample: null argument");
   const mcedm_plan& P = *plan;
   int rc;
@@ -342,7 +378,7 @@ extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed
   MCEDM_REQUIRE(sp->alphas_cumprod_ext && n >= 2 && N >= 1 && N <= n, "cond_ddim_sample: bad schedule (timesteps=%d of %d)", N, n);
   MCEDM_REQUIRE(sp->skip_type == 0 || sp->skip_type == 1, "cond_ddim_sample: skip_type must be 0 (uniform) or 1 (quad)");
   const bool stochastic = std::fabs(sp->eta) > 1e-10;                   // :1509
-  MCEDM_REQUIRE(!stochastic || eta_noise != nullptr, "cond_ddim_sample: eta != 0 needs eta_noise");
+  MCEDM_REQUIRE(!stochastic || eta_noise != nullptr || rng_seed != nullptr, "cond_ddim_sample: eta != 0 needs eta_noise");
   const bool guided = !(std::fabs(sp->w) < 0.001);                      // :1493
   Layout L;
   if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
@@ -394,9 +430,10 @@ extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed
     if (stochastic) {        // c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2), fp32 like the tensors
       k.c1 = (float)sp->eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
       k.c2 = sqrtf((1.0f - at_next) - k.c1 * k.c1);
-      k.noise = eta_noise + (size_t)step * total;
+      k.noise = rng_seed ? nullptr : eta_noise + (size_t)step * total;
+      k.seed = reinterpret_cast<const unsigned long long*>(rng_seed); k.draw = (unsigned long long)step;
     } else {
-      k.c1 = 0.f; k.c2 = sqrtf(1.0f - at_next); k.noise = nullptr;
+      k.c1 = 0.f; k.c2 = sqrtf(1.0f - at_next); k.noise = nullptr; k.seed = nullptr;
     }
     const bool store = !return_last || step == S - 1;                   // return_last keeps the last state and x0 only (:1517-1522)
     k.xs = store ? xs_out : nullptr; k.x0s = store ? x0_out : nullptr;
@@ -405,4 +442,23 @@ extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed
     xt = k.xt_next;
   }
   return MCEDM_OK;
+}
+
+extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                                      const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out,
+                                      int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                      void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return cond_ddim_impl(plan, packed, sp, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
+                        workspace_bytes, B, H, W, stream);
+}
+
+extern "C" int mcedm_cond_ddim_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                          const float* cond, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
+                                          float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B, int H,
+                                          int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return cond_ddim_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace,
+                        workspace_bytes, B, H, W, stream);
 }

@@ -25,6 +25,8 @@ self-conditioning (which it runs) -- epsilon-prediction ``training_step``, the V
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -160,6 +162,11 @@ class _SingleTask(_PlBase):
                 "gt": gt_scaled[..., h_ch:h_ch + u_ch] if sp.plot_scaled else u}
 
 
+def _table_key(t):
+    """A host schedule table as part of a graph key: its values are baked into the captured kernel arguments."""
+    return hash(t.detach().to("cpu", torch.float32).contiguous().numpy().tobytes())
+
+
 class _DdpmSchedule:
     """The DDPM noise schedule as EDM sigmas (models/ddim.py:122-137, 949-957), host side: the reference's own expressions on
     CPU tensors.  Mixed into the modules that sample a DDPM network with the EDM sampler (PlDdim, PlCondDdim)."""
@@ -224,6 +231,7 @@ class PlCondEdm(_SingleTask):
         self._init_common(hparams, m.in_channels, m.out_ch, default_sampler=self.get_edm_sampler_params)
         self.P_mean, self.P_std, self.sigma_data = -1.2, 1.2, 1.0
         self.sigma_min, self.sigma_max = 0.002, 80
+        self.noise_source = os.environ.get("MCEDM_NOISE_SOURCE", "device")      # the sampler's churn draws, as in PlMcedm
         # a default until the first batch sets the widths (the reference has none: models/ddim.py:1120-1121 are its first
         # assignments); the node_type channel added above is not part of the known state
         self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
@@ -334,7 +342,10 @@ class PlCondEdm(_SingleTask):
     def sample_edm(self, h, u_noise, sparams, return_last=True, guide_dx=False):
         """h, u_noise in the reference's 'b h w c' layout; returns [b, t, h, w, c] float64 (models/ddim.py:1532-1601).
         guide_dx=True: after every denoiser call d -= 5 * dx / t_hat with dx the PDE-residual gradient, evaluated on the
-        device by the stencils' analytic adjoints (csrc/pde.hip) instead of torch.autograd."""
+        device by the stencils' analytic adjoints (csrc/pde.hip) instead of torch.autograd.
+        The per-step churn noise is generated inside the churn kernel from a seed drawn from torch's CPU generator
+        (``noise_source = "device"``), or drawn with torch.randn as one [N, B, C, H, W] float64 tensor (``"torch"``)."""
+        noise_source = self._noise_mode()
         guidance = dx_input = None
         if guide_dx or self.dx_cond:
             if self.pde_loss is None or not hasattr(self.pde_loss, "guidance_desc"):
@@ -349,20 +360,25 @@ class PlCondEdm(_SingleTask):
         h, init = _nchw(h).float(), _nchw(u_noise).float()
         sd = _lib.sampler_desc(sparams, self.sigma_data, self.sigma_min, self.sigma_max)
         N, churn = sd.timesteps, self._churns(sd)
-        step_noise = torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device) if churn else None
+        dev_noise = churn and noise_source == "device"
+        step_noise = (torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device)
+                      if churn and not dev_noise else None)
+        kw = dict(seed=self._draw_seed()) if dev_noise else {}
         with torch.no_grad():
             packed = net.packed_weights()
-            eager = lambda c, m_, i, sn: net.plan.sample(packed, sd, c, None, i, sn, return_last=return_last, ws=self._sample_ws,
-                                                         guidance=guidance, dx_input=dx_input)
+            eager = lambda c, m_, i, sn, seed=None: net.plan.sample(      # noqa: E731
+                packed, sd, c, None, i, sn, return_last=return_last, ws=self._sample_ws, guidance=guidance, dx_input=dx_input,
+                rng_seed=self._seed_tensor(seed, i.device))
             # the call replays from one HIP graph, like PlMcedm.sample_edm (the evaluation loops repeat it); the residual
             # descriptions of guide_dx / dx_cond are host-side structs, so they are part of the key and of the capture
             B, _, H, W = init.shape
             dkey = lambda d: None if d is None else tuple(getattr(d, f) for f, _ in d._fields_)      # noqa: E731
-            key = (B, H, W, bool(return_last), churn, packed.data_ptr(), init.device.index,
+            key = (B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), init.device.index,
                    tuple(getattr(sd, f) for f, _ in sd._fields_), dkey(guidance), dkey(dx_input))
             return self._replay(key, lambda: _lib.GraphedSampler(
                 net.plan, packed, sd, B, H, W, masked=False, has_cond=True, churn=churn, return_last=return_last,
-                ws=self._sample_ws, guidance=guidance, dx_input=dx_input), eager, h, None, init, step_noise)
+                ws=self._sample_ws, guidance=guidance, dx_input=dx_input, device_noise=dev_noise), eager, h, None, init,
+                step_noise, **kw)
 
 
 class PlDdim(_DdpmSchedule, _PlBase):
@@ -559,20 +575,35 @@ class PlDdim(_DdpmSchedule, _PlBase):
     def sample_with_repeat(self, h, u, sparams, return_last=True, guide_dx=False):
         """models/ddim.py:808-913: DDIM steps (eta, uniform / quad skipping) with n_repeat RePaint-style inner loops per step
         and the previous x0 prediction fed back as x_self_cond; the loop runs in mcedm_ddim_repaint_sample (csrc/ddpm.hip).
-        h, u: 'b h w c' normalised fields.  Returns (xs, x0_preds), fp32 'b t h w c' like the reference."""
+        h, u: 'b h w c' normalised fields.  Returns (xs, x0_preds), fp32 'b t h w c' like the reference.
+        With eta != 0 the per-step torch.rand_like of :893 (a UNIFORM draw) is generated inside the step kernel from a seed drawn
+        from torch's CPU generator (``noise_source`` "device", also when the attribute is absent), or made up front as one
+        torch.rand([S, B, C, H, W]) (``"torch"``).  Either way the call replays from one HIP graph."""
         if guide_dx:
             raise NotImplementedError("guide_dx=True (PDE guidance) is outside the built path")
+        noise_source = self._noise_mode()
         net = self._net(self.ema_model if self.ema_model is not None else self.model)
         hu = _nchw(torch.cat([h, u], dim=-1)).float()
-        dd, keep = _lib.ddim_desc(sparams, self._alphas_ext(), self.h_ch, self.u_ch, net.self_condition)
+        ae = self._alphas_ext()
+        dd, keep = _lib.ddim_desc(sparams, ae, self.h_ch, self.u_ch, net.self_condition)
         hu_noise = torch.randn_like(hu)
+        stochastic = abs(float(sparams.eta)) > 1e-10
+        dev_noise = stochastic and noise_source == "device"
         eta_noise = None
-        if abs(float(sparams.eta)) > 1e-10:        # the reference draws torch.rand_like (UNIFORM) here, models/ddim.py:893
+        if stochastic and not dev_noise:           # the reference draws torch.rand_like (UNIFORM) here, models/ddim.py:893
             S = len(range(0, self.num_timesteps, self.num_timesteps // dd.timesteps)) if dd.skip_type == 0 else dd.timesteps
             eta_noise = torch.rand((S,) + tuple(hu.shape), dtype=torch.float32, device=hu.device)
+        kw = dict(seed=self._draw_seed()) if dev_noise else {}
         with torch.no_grad():
-            return net.plan.ddim_repaint_sample(net.packed_weights(), dd, hu, hu_noise, eta_noise, return_last=return_last,
-                                                ws=self._sample_ws)
+            packed = net.packed_weights()
+            eager = lambda x, nz, en, seed=None: net.plan.ddim_repaint_sample(      # noqa: E731
+                packed, dd, x, nz, en, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, x.device))
+            B = hu.shape[0]
+            key = ("ddim", B, bool(return_last), stochastic, dev_noise, packed.data_ptr(), hu.device.index, _table_key(ae),
+                   tuple(getattr(dd, f) for f, _ in dd._fields_ if f != "alphas_cumprod_ext"))
+            return self._replay(key, lambda: _lib.GraphedDdimRepaint(net.plan, packed, dd, keep, B, stochastic, return_last,
+                                                                     ws=self._sample_ws, device_noise=dev_noise),
+                                eager, hu, hu_noise, eta_noise, **kw)
 
     def training_step(self, *a, **k):
         raise NotImplementedError("DDPM (epsilon-prediction) training is not built: SURVEY.md section 8 f1 covers EDM sampling "
@@ -601,9 +632,10 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     Constructor, buffers (``betas``, ``logvar``), state_dict keys and method signatures follow the reference.  The training
     step runs in the HIP library: noising (mcedm_eps_noise_inputs), the self-conditioning pre-pass and its estimate written into
     the network's widened conditioning input (mcedm_eps_self_cond), forward, loss (mcedm_eps_loss) and backward from dF
-    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample.  The DDPM U-Net (``name: ddim*``), the PDE loss term,
+    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The DDPM U-Net (``name: ddim*``), the PDE loss term,
     ``guide_dx`` and ``dx_cond`` raise.  ``sample`` (the DDIM loop, :1452-1530) is
-    mcedm_cond_ddim_sample."""
+    mcedm_cond_ddim_sample[_rng].  ``noise_source`` ("device" / "torch", from MCEDM_NOISE_SOURCE) says where the per-step draws of
+    the two samplers come from: the sampler's own kernels, or torch tensors drawn up front."""
 
     def __init__(self, hparams):
         super().__init__()
@@ -628,6 +660,7 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         self.factor, self.step_size, self.loss = _opt(o, "factor", 0.3), _opt(o, "step_size", 50), _opt(o, "loss", "l2")
         self.pde_loss_lambda = 0.0
         self.edm_steps = self.sigma_min = self.sigma_max = None
+        self.noise_source = os.environ.get("MCEDM_NOISE_SOURCE", "device")      # the samplers' per-step draws, as in PlMcedm
         self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
         self._tables = None
         self._stage = None
@@ -743,10 +776,13 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
 
     def sample_edm(self, h, u_noise, sparams, return_last=True, guide_dx=False):
         """models/ddim.py:1532-1601; h, u_noise in the reference's 'b h w c' layout; returns [b, t, h, w, c] float64.  The
-        schedule is rounded on the host (round_sigma, :1553, 1566); the loop runs in mcedm_vp_heun_sample with the per-step
-        randn_like(x_cur) of :1567 drawn up front as one [N, B, C, H, W] float64 tensor."""
+        schedule is rounded on the host (round_sigma, :1553, 1566); the loop runs in mcedm_vp_heun_sample_rng, whose churn kernel
+        generates the per-step randn_like(x_cur) of :1567 from a seed drawn from torch's CPU generator (``noise_source =
+        "device"``), or in mcedm_vp_heun_sample fed one torch.randn([N, B, C, H, W], float64) (``"torch"``).  Either way the call
+        replays from one HIP graph."""
         if guide_dx:
             raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1577-1579) is not built for PlCondDdim")
+        noise_source = self._noise_mode()
         if self.edm_steps is None:
             self.set_test_sampler_params(sparams)
         net = self._net(self.ema_model if self.ema_model is not None else self.model)
@@ -766,10 +802,25 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             t_hat.append(float(th))
             c_noise += [self._c_noise(float(th)), self._c_noise(float(t_steps[i + 1])) if i < N - 1 else 0.0]
         vd = _lib.vp_sampler_desc(N, net.cond_channels, t_steps.tolist(), t_hat, c_noise, float(sparams.S_noise), float(sparams.w))
-        step_noise = torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device)
+        churn = any(th != float(t_steps[i]) for i, th in enumerate(t_hat))     # the steps whose x_hat adds noise (:1567)
+        dev_noise = churn and noise_source == "device"
+        step_noise = None
+        if noise_source == "torch":                # drawn whether or not a step churns, like the reference's randn_like
+            step_noise = torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device)
+            if not churn:
+                step_noise = None                  # nothing reads it
+        kw = dict(seed=self._draw_seed()) if dev_noise else {}
+        cond = h if net.cond_channels > 0 else None
         with torch.no_grad():
-            return net.plan.vp_sample(net.packed_weights(), vd, h if net.cond_channels > 0 else None, init, step_noise,
-                                      return_last=return_last, ws=self._sample_ws)
+            packed = net.packed_weights()
+            eager = lambda c, i, sn, seed=None: net.plan.vp_sample(      # noqa: E731
+                packed, vd, c, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device))
+            B, _, H, W = init.shape
+            key = ("vp", B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), init.device.index, N, net.cond_channels,
+                   tuple(t_steps.tolist()), tuple(t_hat), tuple(c_noise), float(sparams.S_noise), float(sparams.w))
+            return self._replay(key, lambda: _lib.GraphedVpSampler(net.plan, packed, vd, B, H, W, cond is not None, churn,
+                                                                   return_last=return_last, ws=self._sample_ws,
+                                                                   device_noise=dev_noise), eager, cond, init, step_noise, **kw)
 
     def sample(self, *a, **k):
         """``sample(h, u_noise, sparams, return_last=True, guide_dx=False)`` of models/ddim.py:1452-1530 (the open signature is the
@@ -781,25 +832,33 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         in the reference's 'b h w c' layout; returns (xs, x0_preds), fp32 'b t h w c'.  The loop runs in mcedm_cond_ddim_sample:
         per step one network pass (two with classifier-free guidance, |w| >= 0.001) and one fused kernel that also feeds the
         x0 prediction back as the next step's x_self_cond.  With eta != 0 the per-step torch.rand_like(x) of :1512 (a UNIFORM
-        draw) is made up front as one torch.rand([S, B, C, H, W])."""
+        draw) is generated inside that kernel from a seed drawn from torch's CPU generator (``noise_source = "device"``), or made
+        up front as one torch.rand([S, B, C, H, W]) (``"torch"``)."""
         if guide_dx:
             raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1501-1503) is not built for PlCondDdim")
         if h is None:
             raise NotImplementedError("sampling without the conditioning field h (models/ddim.py:1452-1531 hands cond=h to the "
                                       "network in every step) is not built")
-        net =self._net(self.ema_model if self.ema_model is not None else self.model)
+        noise_source = self._noise_mode()
+        net = self._net(self.ema_model if self.ema_model is not None else self.model)
         h, init = _nchw(h).float().contiguous(), _nchw(u_noise).float().contiguous()
-        dd = _lib.cond_ddim_desc(sparams, self._alphas_ext(), net.cond_channels, self._net(self.model).self_condition)
+        ae = self._alphas_ext()
+        dd = _lib.cond_ddim_desc(sparams, ae, net.cond_channels, self._net(self.model).self_condition)
         stochastic = abs(float(sparams.eta)) > 1e-10
+        dev_noise = stochastic and noise_source == "device"
         S = len(_lib.ddim_timesteps(self.num_timesteps, dd.timesteps, dd.skip_type))
-        eta_noise = torch.rand((S,) + tuple(init.shape), dtype=torch.float32, device=init.device) if stochastic else None
+        eta_noise = (torch.rand((S,) + tuple(init.shape), dtype=torch.float32, device=init.device)
+                     if stochastic and not dev_noise else None)
+        kw = dict(seed=self._draw_seed()) if dev_noise else {}
         cond = h if net.cond_channels > 0 else None
         with torch.no_grad():
             packed = net.packed_weights()
-            eager = lambda c, i, en: net.plan.cond_ddim_sample(packed, dd, c, i, en, return_last=return_last, ws=self._sample_ws)
+            eager = lambda c, i, en, seed=None: net.plan.cond_ddim_sample(      # noqa: E731
+                packed, dd, c, i, en, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device))
             # the evaluation loops repeat the call: it replays from one HIP graph, like sample_edm of the sibling modules
             B, _, H, W = init.shape
-            key = ("ddim", B, H, W, bool(return_last), stochastic, packed.data_ptr(), init.device.index,
+            key = ("ddim", B, H, W, bool(return_last), stochastic, dev_noise, packed.data_ptr(), init.device.index, _table_key(ae),
                    tuple(getattr(dd, f) for f, _ in dd._fields_ if f != "alphas_cumprod_ext"))
             return self._replay(key, lambda: _lib.GraphedCondDdim(net.plan, packed, dd, B, H, W, stochastic, return_last=return_last,
-                                                                  ws=self._sample_ws), eager, cond, init, eta_noise)
+                                                                  ws=self._sample_ws, device_noise=dev_noise),
+                                eager, cond, init, eta_noise, **kw)

@@ -35,6 +35,8 @@ EXPORTS = [
     "mcedm_eps_noise_inputs", "mcedm_eps_self_cond", "mcedm_eps_loss", "mcedm_unet_backward", "mcedm_unet_backward_bucketed",
     "mcedm_vp_sampler_workspace_bytes", "mcedm_vp_heun_sample", "mcedm_vp_heun_sample_rng",
     "mcedm_cond_ddim_workspace_bytes", "mcedm_cond_ddim_sample",
+    "mcedm_uniform_fill", "mcedm_cond_ddim_sample_rng", "mcedm_ddim_repaint_sample_rng", "mcedm_heun_sample_guided_rng",
+    "mcedm_heun_sample_dxcond_rng",
 ]
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
@@ -167,6 +169,10 @@ def load() -> C.CDLL:
     lib.mcedm_darcy_guidance.argtypes = [f32p, f32p, f32p, i32, i32, C.c_float, i32, vp]
     lib.mcedm_heun_sample_guided.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), f32p, f32p, f32p, f64p,
                                              f64p, i32, vp, sz, i32, i32, i32, vp]
+    lib.mcedm_heun_sample_guided_rng.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), f32p, f32p, f32p, vp,
+                                                 f64p, i32, vp, sz, i32, i32, i32, vp]
+    lib.mcedm_heun_sample_dxcond_rng.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), C.POINTER(GuidanceDesc),
+                                                 f32p, f32p, vp, f64p, i32, vp, sz, i32, i32, i32, vp]
     lib.mcedm_ddpm_plan_create.argtypes = [C.POINTER(DdpmDesc), C.POINTER(vp)]
     lib.mcedm_ddpm_plan_destroy.argtypes = [vp]
     lib.mcedm_ddpm_plan_destroy.restype = None
@@ -183,9 +189,11 @@ def load() -> C.CDLL:
     lib.mcedm_repaint_sample.argtypes = [vp, vp, C.POINTER(RepaintDesc), f32p, f32p, f64p, f64p, f64p, i32, vp, sz, i32, vp]
     lib.mcedm_repaint_sample_rng.argtypes = [vp, vp, C.POINTER(RepaintDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, vp]
     lib.mcedm_normal_fill.argtypes = [f64p, sz, vp, C.c_uint64, vp]
+    lib.mcedm_uniform_fill.argtypes = [f32p, sz, vp, C.c_uint64, vp]
     lib.mcedm_ddpm_forward_sc.argtypes = [vp, vp, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
     lib.mcedm_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
     lib.mcedm_ddim_repaint_sample.argtypes = [vp, vp, C.POINTER(DdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddim_repaint_sample_rng.argtypes = [vp, vp, C.POINTER(DdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32, vp]
     lib.mcedm_ddim_timesteps.argtypes = [i32, i32, i32, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
     lib.mcedm_eps_noise_inputs.argtypes = [f32p, f32p, vp, f32p, f32p, i32, i32, i32, i32, i32, f32p, f32p, vp]
     lib.mcedm_eps_self_cond.argtypes = [f32p, f32p, vp, f32p, f32p, i32, f32p, i32, i32, i32, i32, i32, f32p, vp]
@@ -202,6 +210,8 @@ def load() -> C.CDLL:
     lib.mcedm_cond_ddim_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
     lib.mcedm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, i32,
                                            i32, vp]
+    lib.mcedm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32,
+                                               i32, i32, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)          # AttributeError here == header/library drift
         if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
@@ -451,13 +461,18 @@ class Plan(_PlanBase):
         return self._bytes("mcedm_vp_sampler_workspace_bytes", "vp_sampler_workspace_bytes", B, H, W)
 
     def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
-                  ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mcedm_vp_heun_sample (rng_seed None) / mcedm_vp_heun_sample_rng; returns [B, 1 or N+1, H, W, in] float64."""
+                  ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcedm_vp_heun_sample (rng_seed None) / mcedm_vp_heun_sample_rng; returns [B, 1 or N+1, H, W, in] float64 (``out``, when
+        given: a graphed call's static tensor)."""
         B, _, H, W = init_noise.shape
         ws = ws or Workspace()
         buf = ws.get(self.vp_sampler_workspace_bytes(B, H, W), init_noise.device)
         T = 1 if return_last else vd.timesteps + 1
-        out = torch.empty((B, T, H, W, self.in_channels), dtype=torch.float64, device=init_noise.device)
+        if out is None:
+            out = torch.empty((B, T, H, W, self.in_channels), dtype=torch.float64, device=init_noise.device)
+        elif tuple(out.shape) != (B, T, H, W, self.in_channels):
+            raise RuntimeError(f"vp_sample: out has shape {tuple(out.shape)}, expected {(B, T, H, W, self.in_channels)}")
         if rng_seed is not None:
             if step_noise is not None:
                 raise RuntimeError("vp_sample: give step_noise or rng_seed, not both")
@@ -475,9 +490,11 @@ class Plan(_PlanBase):
         return self._bytes("mcedm_cond_ddim_workspace_bytes", "cond_ddim_workspace_bytes", B, H, W)
 
     def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
-                         ws: Optional[Workspace] = None, out=None):
+                         ws: Optional[Workspace] = None, out=None, rng_seed: Optional[torch.Tensor] = None):
         """mcedm_cond_ddim_sample (PlCondDdim.sample on the device) -> (xs, x0_preds), both fp32 'b t h w c': S + 1 and S
-        slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors)."""
+        slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors).  rng_seed (int64 [1]
+        on the device): the uniform draws of the eta != 0 steps are generated inside the step kernel (mcedm_cond_ddim_sample_rng,
+        step k = draw k of uniform_fill) instead of being read from eta_noise."""
         B, _, H, W = init_noise.shape
         ws = ws or Workspace()
         buf = ws.get(self.cond_ddim_workspace_bytes(B, H, W), init_noise.device)
@@ -489,6 +506,14 @@ class Plan(_PlanBase):
             raise RuntimeError(f"cond_ddim_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
         if eta_noise is not None and tuple(eta_noise.shape) != (S,) + tuple(init_noise.shape):
             raise RuntimeError(f"cond_ddim_sample: eta_noise must be {(S,) + tuple(init_noise.shape)}, got {tuple(eta_noise.shape)}")
+        if rng_seed is not None:
+            if eta_noise is not None:
+                raise RuntimeError("cond_ddim_sample: give eta_noise (materialised draws) or rng_seed (device-side draws), not both")
+            seed = _seed_ptr(rng_seed, init_noise.device, "cond_ddim_sample")
+            check(self._lib.mcedm_cond_ddim_sample_rng(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise), seed,
+                                                       _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(), buf.numel(),
+                                                       B, H, W, _stream()), "cond_ddim_sample_rng")
+            return out[0], out[1]
         check(self._lib.mcedm_cond_ddim_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise),
                                                _ptr(eta_noise), _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(),
                                                buf.numel(), B, H, W, _stream()), "cond_ddim_sample")
@@ -500,7 +525,8 @@ class Plan(_PlanBase):
                rng_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dx_input: the residual whose gradient at the current state is the network's dx input (dx_cond plans).
         rng_seed: a one-element int64 DEVICE tensor -- the churn noise of every step is then generated inside the kernel that
-        applies it (mcedm_heun_sample_rng) instead of being read from step_noise [N, B, C, H, W] float64."""
+        applies it (mcedm_heun_sample_rng and its _guided / _dxcond forms) instead of being read from step_noise
+        [N, B, C, H, W] float64."""
         B, _, H, W = init_noise.shape
         ws = ws or Workspace()
         buf = ws.get(self.sampler_workspace_bytes(B, H, W), init_noise.device)
@@ -509,9 +535,21 @@ class Plan(_PlanBase):
             out = torch.empty((B, T, H, W, self.in_channels), dtype=torch.float64, device=init_noise.device)
         elif tuple(out.shape) != (B, T, H, W, self.in_channels):
             raise RuntimeError(f"sample: out has shape {tuple(out.shape)}, expected {(B, T, H, W, self.in_channels)}")
+        seed = None
+        if rng_seed is not None:
+            if step_noise is not None:
+                raise RuntimeError("sample: give step_noise (materialised draws) or rng_seed (device-side draws), not both")
+            seed = _seed_ptr(rng_seed, init_noise.device, "sample")
         if dx_input is not None:
             if mask is not None:
                 raise RuntimeError("sample: dx_cond sampling is the unmasked single-task sampler")
+            if seed is not None:
+                check(self._lib.mcedm_heun_sample_dxcond_rng(self._h, packed.data_ptr(), C.byref(sd), C.byref(dx_input),
+                                                             C.byref(guidance) if guidance is not None else None, _ptr(cond),
+                                                             _ptr(init_noise), seed, _ptr(out, torch.float64), int(return_last),
+                                                             buf.data_ptr(), buf.numel(), B, H, W, _stream()),
+                      "heun_sample_dxcond_rng")
+                return out
             check(self._lib.mcedm_heun_sample_dxcond(self._h, packed.data_ptr(), C.byref(sd), C.byref(dx_input),
                                                      C.byref(guidance) if guidance is not None else None, _ptr(cond),
                                                      _ptr(init_noise), _ptr(step_noise, torch.float64), _ptr(out, torch.float64),
@@ -519,15 +557,18 @@ class Plan(_PlanBase):
                   "heun_sample_dxcond")
             return out
         if guidance is not None:
+            if seed is not None:
+                check(self._lib.mcedm_heun_sample_guided_rng(self._h, packed.data_ptr(), C.byref(sd), C.byref(guidance), _ptr(cond),
+                                                             _ptr(mask), _ptr(init_noise), seed, _ptr(out, torch.float64),
+                                                             int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
+                      "heun_sample_guided_rng")
+                return out
             check(self._lib.mcedm_heun_sample_guided(self._h, packed.data_ptr(), C.byref(sd), C.byref(guidance), _ptr(cond),
                                                      _ptr(mask), _ptr(init_noise), _ptr(step_noise, torch.float64),
                                                      _ptr(out, torch.float64), int(return_last), buf.data_ptr(), buf.numel(),
                                                      B, H, W, _stream()), "heun_sample_guided")
             return out
-        if rng_seed is not None:
-            if step_noise is not None:
-                raise RuntimeError("sample: give step_noise (materialised draws) or rng_seed (device-side draws), not both")
-            seed = _seed_ptr(rng_seed, init_noise.device, "sample")
+        if seed is not None:
             check(self._lib.mcedm_heun_sample_rng(self._h, packed.data_ptr(), C.byref(sd), _ptr(cond), _ptr(mask),
                                                   _ptr(init_noise), seed, _ptr(out, torch.float64),
                                                   int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
@@ -663,8 +704,11 @@ class DdpmPlan(_PlanBase):
         return self._bytes("mcedm_ddim_workspace_bytes", "ddim_workspace_bytes", B)
 
     def ddim_repaint_sample(self, packed, dd: "DdimDesc", hu, init_noise, eta_noise=None, return_last: bool = True,
-                            ws: Optional[Workspace] = None):
-        """PlDdim.sample_with_repeat on the device -> (xs, x0_preds), both fp32 'b t h w c'."""
+                            ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None, out=None):
+        """PlDdim.sample_with_repeat on the device -> (xs, x0_preds), both fp32 'b t h w c'.  rng_seed (int64 [1] on the device):
+        the uniform draws of the eta != 0 steps are generated inside the step kernel (mcedm_ddim_repaint_sample_rng, step k =
+        draw k of uniform_fill) instead of being read from eta_noise.  out: the pair to write into (a graphed call's static
+        tensors)."""
         self._check_x(hu)
         B = hu.shape[0]
         ws = ws or Workspace()
@@ -672,8 +716,20 @@ class DdpmPlan(_PlanBase):
         n = dd.num_diffusion_timesteps
         S = len(ddim_timesteps(n, dd.timesteps, dd.skip_type))
         R = self.resolution
-        xs = torch.empty((B, 1 if return_last else S + 1, R, R, self.in_channels), dtype=torch.float32, device=hu.device)
-        x0 = torch.empty((B, 1 if return_last else S, R, R, self.in_channels), dtype=torch.float32, device=hu.device)
+        shapes = [(B, 1 if return_last else S + 1, R, R, self.in_channels), (B, 1 if return_last else S, R, R, self.in_channels)]
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=torch.float32, device=hu.device) for sh in shapes)
+        elif [tuple(o.shape) for o in out] != shapes:
+            raise RuntimeError(f"ddim_repaint_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
+        xs, x0 = out
+        if rng_seed is not None:
+            if eta_noise is not None:
+                raise RuntimeError("ddim_repaint_sample: give eta_noise (materialised draws) or rng_seed (device-side draws), not both")
+            seed = _seed_ptr(rng_seed, hu.device, "ddim_repaint_sample")
+            check(self._lib.mcedm_ddim_repaint_sample_rng(self._h, packed.data_ptr(), C.byref(dd), _ptr(hu), _ptr(init_noise), seed,
+                                                          _ptr(xs), _ptr(x0), int(return_last), buf.data_ptr(), buf.numel(), B,
+                                                          _stream()), "ddim_repaint_sample_rng")
+            return xs, x0
         check(self._lib.mcedm_ddim_repaint_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(hu), _ptr(init_noise),
                                                   _ptr(eta_noise), _ptr(xs), _ptr(x0), int(return_last), buf.data_ptr(),
                                                   buf.numel(), B, _stream()), "ddim_repaint_sample")
@@ -726,6 +782,13 @@ def normal_fill(out: torch.Tensor, rng_seed: torch.Tensor, draw: int) -> torch.T
     return out
 
 
+def uniform_fill(out: torch.Tensor, rng_seed: torch.Tensor, draw: int) -> torch.Tensor:
+    """out (fp32, contiguous) <- draw number `draw` of the device generator's UNIFORM stream keyed by rng_seed (int64 [1] on the
+    device): multiples of 2^-24 in [0, 1), what the DDIM step kernels generate for themselves (mcedm_uniform_fill)."""
+    check(load().mcedm_uniform_fill(_ptr(out), out.numel(), _ptr(rng_seed, torch.int64), int(draw), _stream()), "uniform_fill")
+    return out
+
+
 class _PinnedWorkspace:
     """Workspace view with a FIXED buffer: a captured graph bakes the pointer in, so the buffer must neither move nor be
     freed while the graph lives (the owner of the graph holds this object)."""
@@ -753,6 +816,23 @@ def _capture(run, dev) -> "torch.cuda.CUDAGraph":
     with torch.cuda.graph(graph, capture_error_mode="thread_local"):
         run()
     return graph
+
+
+def _write_seed(dst: torch.Tensor, seed) -> None:
+    """The key of a replay's device-side draws into the graph's int64 seed scalar: python int or int64 tensor."""
+    if torch.is_tensor(seed):
+        dst.copy_(seed.reshape(1))
+    else:
+        dst.fill_(int(seed))
+
+
+def _copy_static(who: str, pairs) -> None:
+    """Copy a replay's inputs into the graph's static buffers; (dst, src, name) with both None = not part of the capture."""
+    for dst, src, name in pairs:
+        if (dst is None) != (src is None):
+            raise RuntimeError(f"{who}: '{name}' presence differs from the captured call")
+        if dst is not None:
+            dst.copy_(src)
 
 
 class GraphedSampler:
@@ -793,16 +873,9 @@ class GraphedSampler:
         if (self.seed is None) != (seed is None):
             raise RuntimeError("GraphedSampler: 'seed' goes with device_noise=True instances (and only with them)")
         if seed is not None:
-            if torch.is_tensor(seed):
-                self.seed.copy_(seed.reshape(1))
-            else:
-                self.seed.fill_(int(seed))
-        for dst, src, name in ((self.cond, cond, "cond"), (self.mask, mask, "mask"), (self.init, init_noise, "init_noise"),
-                               (self.step_noise, step_noise, "step_noise")):
-            if (dst is None) != (src is None):
-                raise RuntimeError(f"GraphedSampler: '{name}' presence differs from the captured call")
-            if dst is not None:
-                dst.copy_(src)
+            _write_seed(self.seed, seed)
+        _copy_static("GraphedSampler", ((self.cond, cond, "cond"), (self.mask, mask, "mask"), (self.init, init_noise, "init_noise"),
+                                        (self.step_noise, step_noise, "step_noise")))
         self.graph.replay()
         return self.out
 
@@ -833,10 +906,7 @@ class GraphedRepaint:
         """seed: python int or int64 tensor.  Returns the instance's static output tensor."""
         self.hu.copy_(hu)
         self.init.copy_(init_noise)
-        if torch.is_tensor(seed):
-            self.seed.copy_(seed.reshape(1))
-        else:
-            self.seed.fill_(int(seed))
+        _write_seed(self.seed, seed)
         self.graph.replay()
         return self.out
 
@@ -844,30 +914,106 @@ class GraphedRepaint:
 class GraphedCondDdim:
     """mcedm_cond_ddim_sample captured once and replayed, like GraphedSampler: the schedule is host arithmetic baked into the
     kernel arguments, the inputs (cond, init_noise and, with eta != 0, the uniform draws of every step) are copied into static
-    buffers first.  Returns the instance's static (xs, x0_preds), overwritten by the next call."""
+    buffers first.  device_noise (with eta != 0): mcedm_cond_ddim_sample_rng instead -- the step kernel generates the draws from
+    ``self.seed`` (an int64 device scalar the call rewrites before each replay) and no [S, B, C, H, W] buffer exists.  Returns the
+    instance's static (xs, x0_preds), overwritten by the next call."""
 
     def __init__(self, plan: "Plan", packed: torch.Tensor, dd: CondDdimDesc, B: int, H: int, W: int, stochastic: bool,
-                 return_last: bool = True, ws: Optional[Workspace] = None):
+                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False):
         dev = packed.device
         self.plan, self.packed, self.dd, self.return_last = plan, packed, dd, return_last
         Cc, S = plan.in_channels, len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
         self.cond = torch.zeros((B, dd.cond_channels, H, W), device=dev) if dd.cond_channels > 0 else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
-        self.eta_noise = torch.zeros((S, B, Cc, H, W), device=dev) if stochastic else None
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (stochastic and device_noise) else None
+        self.eta_noise = torch.zeros((S, B, Cc, H, W), device=dev) if (stochastic and not device_noise) else None
         self.out = (torch.empty((B, 1 if return_last else S + 1, H, W, Cc), device=dev),
                     torch.empty((B, 1 if return_last else S, H, W, Cc), device=dev))
         self.ws = _PinnedWorkspace(ws, plan.cond_ddim_workspace_bytes(B, H, W), dev)
         self.graph = _capture(self._run, dev)
 
     def _run(self):
-        self.plan.cond_ddim_sample(self.packed, self.dd, self.cond, self.init, self.eta_noise, self.return_last, self.ws, out=self.out)
+        self.plan.cond_ddim_sample(self.packed, self.dd, self.cond, self.init, self.eta_noise, self.return_last, self.ws, out=self.out,
+                                   rng_seed=self.seed)
 
-    def __call__(self, cond, init_noise, eta_noise=None):
-        for dst, src, name in ((self.cond, cond, "cond"), (self.init, init_noise, "init_noise"), (self.eta_noise, eta_noise, "eta_noise")):
-            if (dst is None) != (src is None):
-                raise RuntimeError(f"GraphedCondDdim: '{name}' presence differs from the captured call")
-            if dst is not None:
-                dst.copy_(src)
+    def __call__(self, cond, init_noise, eta_noise=None, seed=None):
+        if (self.seed is None) != (seed is None):
+            raise RuntimeError("GraphedCondDdim: 'seed' goes with device_noise=True instances of a stochastic sampler (and only with them)")
+        if seed is not None:
+            _write_seed(self.seed, seed)
+        _copy_static("GraphedCondDdim", ((self.cond, cond, "cond"), (self.init, init_noise, "init_noise"),
+                                         (self.eta_noise, eta_noise, "eta_noise")))
+        self.graph.replay()
+        return self.out
+
+
+class GraphedDdimRepaint:
+    """mcedm_ddim_repaint_sample (device_noise False) or mcedm_ddim_repaint_sample_rng (True) captured once and replayed: every
+    network pass and elementwise kernel of PlDdim.sample_with_repeat is one HIP graph.  With eta != 0 the uniform draws are either
+    copied into a static [S, B, C, R, R] buffer or generated by the step kernel from ``self.seed``.  ``keep``: the host tables the
+    description points at.  Returns the instance's static (xs, x0_preds), overwritten by the next call."""
+
+    def __init__(self, plan: "DdpmPlan", packed: torch.Tensor, dd: DdimDesc, keep, B: int, stochastic: bool, return_last: bool = True,
+                 ws: Optional[Workspace] = None, device_noise: bool = False):
+        dev = packed.device
+        self.plan, self.packed, self.dd, self._keep, self.return_last = plan, packed, dd, keep, return_last
+        R, Cc = plan.resolution, plan.in_channels
+        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
+        self.hu = torch.zeros((B, Cc, R, R), device=dev)
+        self.init = torch.zeros((B, Cc, R, R), device=dev)
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (stochastic and device_noise) else None
+        self.eta_noise = torch.zeros((S, B, Cc, R, R), device=dev) if (stochastic and not device_noise) else None
+        self.out = (torch.empty((B, 1 if return_last else S + 1, R, R, Cc), device=dev),
+                    torch.empty((B, 1 if return_last else S, R, R, Cc), device=dev))
+        self.ws = _PinnedWorkspace(ws, plan.ddim_workspace_bytes(B), dev)
+        self.graph = _capture(self._run, dev)
+
+    def _run(self):
+        self.plan.ddim_repaint_sample(self.packed, self.dd, self.hu, self.init, self.eta_noise, self.return_last, self.ws,
+                                      rng_seed=self.seed, out=self.out)
+
+    def __call__(self, hu, init_noise, eta_noise=None, seed=None):
+        if (self.seed is None) != (seed is None):
+            raise RuntimeError("GraphedDdimRepaint: 'seed' goes with device_noise=True instances of a stochastic sampler (and only with them)")
+        if seed is not None:
+            _write_seed(self.seed, seed)
+        _copy_static("GraphedDdimRepaint", ((self.hu, hu, "hu"), (self.init, init_noise, "init_noise"),
+                                            (self.eta_noise, eta_noise, "eta_noise")))
+        self.graph.replay()
+        return self.out
+
+
+class GraphedVpSampler:
+    """mcedm_vp_heun_sample (device_noise False) or mcedm_vp_heun_sample_rng (True) captured once and replayed: the ~2 N network
+    evaluations and state updates of PlCondDdim.sample_edm are one HIP graph.  churn: some step of ``vd`` has t_hat > t_cur; its
+    normal draws are either copied into a static [N, B, C, H, W] float64 buffer or generated by the churn kernel from
+    ``self.seed``.  Returns the instance's static output tensor, overwritten by the next call."""
+
+    def __init__(self, plan: "Plan", packed: torch.Tensor, vd: VpSamplerDesc, B: int, H: int, W: int, has_cond: bool, churn: bool,
+                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False):
+        dev = packed.device
+        self.plan, self.packed, self.vd, self.return_last = plan, packed, vd, return_last
+        Cc = plan.in_channels
+        self.cond = torch.zeros((B, vd.cond_channels, H, W), device=dev) if has_cond else None
+        self.init = torch.zeros((B, Cc, H, W), device=dev)
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (churn and device_noise) else None
+        self.step_noise = (torch.zeros((vd.timesteps, B, Cc, H, W), dtype=torch.float64, device=dev)
+                           if churn and not device_noise else None)
+        self.out = torch.empty((B, 1 if return_last else vd.timesteps + 1, H, W, Cc), dtype=torch.float64, device=dev)
+        self.ws = _PinnedWorkspace(ws, plan.vp_sampler_workspace_bytes(B, H, W), dev)
+        self.graph = _capture(self._run, dev)
+
+    def _run(self):
+        self.plan.vp_sample(self.packed, self.vd, self.cond, self.init, self.step_noise, self.return_last, self.ws,
+                            rng_seed=self.seed, out=self.out)
+
+    def __call__(self, cond, init_noise, step_noise=None, seed=None) -> torch.Tensor:
+        if (self.seed is None) != (seed is None):
+            raise RuntimeError("GraphedVpSampler: 'seed' goes with device_noise=True instances of a churning sampler (and only with them)")
+        if seed is not None:
+            _write_seed(self.seed, seed)
+        _copy_static("GraphedVpSampler", ((self.cond, cond, "cond"), (self.init, init_noise, "init_noise"),
+                                          (self.step_noise, step_noise, "step_noise")))
         self.graph.replay()
         return self.out
 
@@ -1067,9 +1213,11 @@ def _bind_ops():
     f32 = C.c_float
     lib.mcedm_op_ddim_cond_step.argtypes = [vp, vp, vp, vp, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32,
                                             i32, vp, i32, i32, vp, i32, i32, vp]
+    lib.mcedm_op_ddim_cond_step_rng.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32,
+                                                i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
-              "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"):
+              "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1081,7 +1229,7 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
-              "mcedm_op_ddim_cond_step", "mcedm_op_set_conv_wino_fold", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"]
+              "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1337,14 +1485,21 @@ def op_attention_bwd(qkv, a, da, heads):
 
 
 def op_ddim_cond_step(xt, F, s0, s1, sa_next, c2, Fu=None, w=0.0, noise=None, c1=0.0, condp=None, condp_u=None, cond_channels=0,
-                      xs=None, t_xs=0, x0s=None, t_x0=0):
+                      xs=None, t_xs=0, x0s=None, t_x0=0, rng_seed=None, draw=0):
     """One elementwise step of the conditional DDIM sampler (mcedm_op_ddim_cond_step) -> xt_next.  x0 is written into channels
-    [cond_channels, cond_channels + C) of condp / condp_u and into slot t_x0 of x0s, xt_next into slot t_xs of xs ('b t h w c')."""
+    [cond_channels, cond_channels + C) of condp / condp_u and into slot t_x0 of x0s, xt_next into slot t_xs of xs ('b t h w c').
+    rng_seed (int64 [1] on the device) with draw: the kernel generates the uniform noise itself (mcedm_op_ddim_cond_step_rng)."""
     lib = _bind_ops()
     B, Cc, H, W = xt.shape
     xt_next = torch.empty_like(xt)
-    check(lib.mcedm_op_ddim_cond_step(_ptr(xt), _ptr(F), _ptr(Fu), _ptr(noise), float(w), s0, s1, sa_next, c1, c2, _ptr(xt_next),
-                                      _ptr(condp), _ptr(condp_u), int(cond_channels), 0 if condp is None else condp.shape[1],
-                                      B, Cc, H, W, _ptr(xs), 0 if xs is None else xs.shape[1], int(t_xs), _ptr(x0s),
-                                      0 if x0s is None else x0s.shape[1], int(t_x0), _stream()), "op_ddim_cond_step")
+    args = (float(w), s0, s1, sa_next, c1, c2, _ptr(xt_next), _ptr(condp), _ptr(condp_u), int(cond_channels),
+            0 if condp is None else condp.shape[1], B, Cc, H, W, _ptr(xs), 0 if xs is None else xs.shape[1], int(t_xs), _ptr(x0s),
+            0 if x0s is None else x0s.shape[1], int(t_x0))
+    if rng_seed is not None:
+        if noise is not None:
+            raise RuntimeError("op_ddim_cond_step: give noise or rng_seed, not both")
+        check(lib.mcedm_op_ddim_cond_step_rng(_ptr(xt), _ptr(F), _ptr(Fu), _seed_ptr(rng_seed, xt.device, "op_ddim_cond_step"),
+                                              int(draw), *args, _stream()), "op_ddim_cond_step_rng")
+        return xt_next
+    check(lib.mcedm_op_ddim_cond_step(_ptr(xt), _ptr(F), _ptr(Fu), _ptr(noise), *args, _stream()), "op_ddim_cond_step")
     return xt_next

@@ -174,19 +174,17 @@ class PlMcedm(_PlBase):
         sd = _lib.sampler_desc(sparams, self.sigma_data, self.sigma_min, self.sigma_max)
         hu_noise = torch.randn_like(hu, dtype=torch.float32)
         N, churn = sd.timesteps, self._churns(sd)
-        if self.noise_source not in ("device", "torch"):
-            raise RuntimeError(f"noise_source must be 'device' or 'torch', not {self.noise_source!r}")
-        dev_noise = churn and self.noise_source == "device"
+        dev_noise = self._noise_mode() == "device" and churn
         step_noise = (torch.randn((N,) + tuple(hu.shape), dtype=torch.float64, device=hu.device)
                       if churn and not dev_noise else None)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if dev_noise else None        # CPU generator: no device sync
+        seed = self._draw_seed() if dev_noise else None
         cond, hu_mask, hu_noise = cond.float().contiguous(), hu_mask.float().contiguous(), hu_noise.contiguous()
         with torch.no_grad():
             packed = net.packed_weights()
 
             def eager(c, m_, i, sn, seed=None):
-                rs = torch.tensor([seed], dtype=torch.int64, device=i.device) if seed is not None else None
-                return net.plan.sample(packed, sd, c, m_, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=rs)
+                return net.plan.sample(packed, sd, c, m_, i, sn, return_last=return_last, ws=self._sample_ws,
+                                       rng_seed=self._seed_tensor(seed, i.device))
             kw = dict(seed=seed) if dev_noise else {}
             # the ~4000 launches of one sampling call replay from one HIP graph (lib.GraphedSampler, see _replay)
             B, _, H, W = hu_noise.shape

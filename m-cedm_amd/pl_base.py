@@ -315,9 +315,26 @@ class _PlBase(_Base):
         N, t = sd.timesteps, _lib.edm_t_steps(sd)
         return any((min(sd.S_churn / N, math.sqrt(2) - 1) if sd.S_min <= t[i] <= sd.S_max else 0) > 0 for i in range(N))
 
+    def _noise_mode(self):
+        """``self.noise_source`` checked ('device', also when a module has no such attribute, or 'torch'): where a sampler's
+        per-step noise comes from -- generated inside its kernels from a seed, or drawn by torch into tensors."""
+        src = getattr(self, "noise_source", "device")
+        if src not in ("device", "torch"):
+            raise RuntimeError(f"noise_source must be 'device' or 'torch', not {src!r}")
+        return src
+
+    @staticmethod
+    def _draw_seed():
+        """The key of one call's device-side draws, from torch's CPU generator (no device sync): seed_everything pins a run."""
+        return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+    @staticmethod
+    def _seed_tensor(seed, device):
+        return None if seed is None else torch.tensor([seed], dtype=torch.int64, device=device)
+
     def _replay(self, key, build, eager, *args, **kw):
         """One sampling call: ``eager(*args, **kw)`` with ``MCEDM_HIP_GRAPH=0``, otherwise replayed from one HIP graph
-        (lib.GraphedSampler / lib.GraphedRepaint, built by ``build()`` on first use).  At most two graphs are kept per module
+        (one of lib's Graphed* wrappers, built by ``build()`` on first use).  At most two graphs are kept per module
         (the evaluation loops repeat one call; a ragged last batch is the second), they borrow the module's sampler workspace,
         a failed capture falls back to the eager call, and a replay's static output (a tensor, or a tuple of them) is cloned."""
         if os.environ.get("MCEDM_HIP_GRAPH", "1") == "0":
