@@ -664,6 +664,48 @@ int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packe
                                   const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
                                   int return_last, void* workspace, size_t workspace_bytes, int B, void* stream);
 
+/* ---- the conditioning head of Model (cond_enc / combine_enc, models/ddim_blocks.py:279-306, 401-421) -------------------
+ * cat_cond False, cond_channels > 0 (configs/model/ddim_cond_h_res32.yaml):
+ *   x_feat = combine_enc(cat(conv_in(cat(x_self_cond, x)), cond_enc(cond))),
+ *   cond_enc = Conv1x1(cond_channels -> ch) -> GELU (erf) -> Conv3x3(ch -> ch, circular padding), combine_enc = Conv1x1(2 ch -> ch),
+ *   cond None: ZERO features in place of cond_enc(cond).
+ * combine_enc is linear, so with Wx, Wc the two halves of its weight the plan folds, at pack time (fp64, rounded once),
+ *   x_feat = (Wx conv_in)(z) + M,   M = (Wc cond_enc.2) (*)circ GELU(cond_enc.0(cond)) + (Wx b_in + Wc b_enc2 + b_comb):
+ * the map M [B, ch, R, R] depends on cond alone (mcedm_ddpm_cond_map: one launch, a sampler runs it once per call) and the
+ * folded conv_in adds it before its GroupNorm statistics; without cond (zero features, so no b_enc2 either) conv_in adds the
+ * vector Wx b_in + b_comb and no map is read.  A network
+ * evaluation launches exactly what a plan without the head launches.  The parameter table gains cond_enc.0.*, cond_enc.2.*,
+ * combine_enc.* behind conv_in.*, as Model.state_dict() orders them.  cat_cond != 0 (the conditioning concatenated to the
+ * input of the DDPM U-Net) is not built: MCEDM_ERR_INVALID. */
+typedef struct { int32_t cond_channels; int32_t cat_cond; } mcedm_ddpm_cond_desc;
+int mcedm_ddpm_plan_create_cond(const mcedm_ddpm_desc* desc, const mcedm_ddpm_cond_desc* cond, mcedm_ddpm_plan** out);
+/* map_out [B, ch, R, R] <- M(cond), cond [B, cond_channels, R, R]; the caller owns map_out. */
+int mcedm_ddpm_cond_map(const mcedm_ddpm_plan* plan, const void* packed, const float* cond, float* map_out, int B, void* stream);
+/* Model.forward(x, t, cond, x_self_cond) with the conditioning given as its map: x_self_cond NULL = zeros, cond_map NULL = cond
+ * None.  On a plan without the head cond_map must be NULL and this is mcedm_ddpm_forward_sc. */
+int mcedm_ddpm_forward_cond(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
+                            const float* cond_map, float t, float* out, void* workspace, size_t workspace_bytes, int B, void* stream);
+/* mcedm_vp_heun_sample[_rng] on the DDPM U-Net with the head: same description, same contracts (fp64 state, the rounded schedule
+ * from the host, guidance for |w| >= 1e-3 with cond given, _rng bit-equal to the tensor-fed form on mcedm_normal_fill's draws).
+ * sp->cond_channels is the plan's cond_channels (cond given) or 0 (cond NULL); the map is computed once, inside the call;
+ * x_self_cond is None in every evaluation (get_self_cond_edm, :1603-1605).  H = W = the plan's resolution. */
+int mcedm_ddpm_vp_sampler_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes);
+int mcedm_ddpm_vp_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                              const float* init_noise, const double* step_noise, double* out, int return_last, void* workspace,
+                              size_t workspace_bytes, int B, void* stream);
+int mcedm_ddpm_vp_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                                  const float* init_noise, const uint64_t* rng_seed, double* out, int return_last, void* workspace,
+                                  size_t workspace_bytes, int B, void* stream);
+/* mcedm_cond_ddim_sample[_rng] on the DDPM U-Net with the head: the x0 prediction of a step is the next step's x_self_cond
+ * (sp->self_cond, which needs a plan built with self_cond); the guidance pass runs without the map, on the same x_self_cond. */
+int mcedm_ddpm_cond_ddim_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes);
+int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                                const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out, int return_last,
+                                void* workspace, size_t workspace_bytes, int B, void* stream);
+int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                                    const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last,
+                                    void* workspace, size_t workspace_bytes, int B, void* stream);
+
 /* ---- PDE residuals (forward) ----------------------------------------------
  * Replace the tensor-op bodies of models/pde_loss.py; results are bit-identical to the PyTorch CPU path.
  * All tensors are fp32, channel-last (b, t, x, 2) = (h, u) for SWE and (b, s, s, 2) = (a, u) for Darcy.

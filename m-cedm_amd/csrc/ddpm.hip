@@ -12,7 +12,10 @@
 //   * q, k, v are one packed [3C x C] GEMM whose output is the attention kernel's [3][64][T] layout (C == 64);
 //   * the stride-2 conv is conv_s2_mfma_kernel (4-phase LDS tile), nearest-up is the RS_UP staging mode, the channel
 //     concat of the decoder is virtual (two source pointers).
-// Only what the sampler needs is built: inference, one timestep per call, x_self_cond = None (zeros: a null source).
+// Only what the samplers need is built: inference, one timestep per call.
+//   * the conditioning head of the single-task model (cond_enc / combine_enc, ddim_blocks.py:279-306, 401-421) is folded into
+//     conv_in at pack time (combine_enc is linear); what depends on cond is one map M [B, ch, R, R], computed by
+//     ddpm_cond_map_kernel once per sampler call and added by conv_in as its residual, in front of the fused statistics.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -67,6 +70,12 @@ struct mcedm_ddpm_plan {
   size_t tproj_w = mcedm::NONE, tproj_b = mcedm::NONE, c1bias = mcedm::NONE;
   size_t packed_floats = 0;
   int in_total = 0;          // conv_in input channels (self-conditioning channels first)
+  // the cond_enc / combine_enc head (mcedm_ddpm_plan_create_cond; cond_channels 0 = none).  Packed: cond_enc.0 as it is, the
+  // folded 3x3 of the map as [tap][cin][cout], the map's bias, and the folded conv_in weight in parameter layout (the
+  // source launch_pack_conv reads; conv_in.wpk / conv_in.bias hold the folded forms, the bias that of cond = None)
+  int cond_channels = 0;
+  int e0w = -1, e0b = -1, e2w = -1, e2b = -1, cbw = -1, cbb = -1;
+  size_t enc0_w = mcedm::NONE, enc0_b = mcedm::NONE, map_w = mcedm::NONE, map_b = mcedm::NONE, in_fold = mcedm::NONE;
 };
 
 namespace mcedm {
@@ -126,7 +135,7 @@ static void dplace(Taker& t, DAttn& a) {
 
 using namespace mcedm;
 
-extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan** out) {
+static int ddpm_plan_build(const mcedm_ddpm_desc* d, int cond_channels, mcedm_ddpm_plan** out) {
   MCEDM_REQUIRE(d && out, "ddpm_plan_create: null argument");
   MCEDM_REQUIRE(d->n_levels >= 1 && d->n_levels <= MCEDM_MAX_LEVELS, "ddpm_plan_create: n_levels=%d out of range", d->n_levels);
   MCEDM_REQUIRE(d->n_attn_resolutions >= 0 && d->n_attn_resolutions <= MCEDM_MAX_LEVELS, "ddpm_plan_create: bad n_attn_resolutions");
@@ -143,6 +152,12 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
   P.d0w = add_param(P.params, "temb.dense.0.weight", {temb, ch}); P.d0b = add_param(P.params, "temb.dense.0.bias", {temb});
   P.d1w = add_param(P.params, "temb.dense.1.weight", {temb, temb}); P.d1b = add_param(P.params, "temb.dense.1.bias", {temb});
   P.conv_in = dconv(P, "conv_in", P.in_total, ch, 3);
+  P.cond_channels = cond_channels;
+  if (cond_channels > 0) {             // cond_enc = Sequential(Conv1x1, GELU, Conv3x3 circular), combine_enc (ddim_blocks.py:281-304)
+    P.e0w = add_param(P.params, "cond_enc.0.weight", {ch, cond_channels, 1, 1}); P.e0b = add_param(P.params, "cond_enc.0.bias", {ch});
+    P.e2w = add_param(P.params, "cond_enc.2.weight", {ch, ch, 3, 3}); P.e2b = add_param(P.params, "cond_enc.2.bias", {ch});
+    P.cbw = add_param(P.params, "combine_enc.weight", {ch, 2 * ch, 1, 1}); P.cbb = add_param(P.params, "combine_enc.bias", {ch});
+  }
   int res = d->resolution, block_in = ch;
   auto in_mult = [&](int l) { return l == 0 ? 1 : d->ch_mult[l - 1]; };
   P.down.resize(L);
@@ -232,9 +247,26 @@ extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan*
     }
   dplace(t, P.mid1); dplace(t, P.mid_attn); dplace(t, P.mid2);
   dplace(t, P.norm_out); dplace(t, P.conv_out);
+  if (cond_channels > 0) {             // behind everything else: the offsets of a plan without the head do not move
+    P.enc0_w = t.take((size_t)ch * cond_channels); P.enc0_b = t.take(ch);
+    P.map_w = t.take((size_t)9 * ch * ch); P.map_b = t.take(ch);
+    P.in_fold = t.take((size_t)ch * P.in_total * 9);
+  }
   P.packed_floats = t.cur;
   *out = Pp;
   return MCEDM_OK;
+}
+
+extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan** out) { return ddpm_plan_build(d, 0, out); }
+
+extern "C" int mcedm_ddpm_plan_create_cond(const mcedm_ddpm_desc* d, const mcedm_ddpm_cond_desc* cd, mcedm_ddpm_plan** out) {
+  MCEDM_REQUIRE(d && cd && out, "ddpm_plan_create_cond: null argument");
+  MCEDM_REQUIRE(cd->cond_channels >= 0 && cd->cond_channels <= 64, "ddpm_plan_create_cond: cond_channels=%d outside [0, 64]", cd->cond_channels);
+  MCEDM_REQUIRE(!(cd->cat_cond && cd->cond_channels > 0),
+                "ddpm_plan_create_cond: cat_cond (the conditioning concatenated to the input of the DDPM U-Net, ddim_blocks.py:259, "
+                "386-391) is not built; only the cond_enc head (cat_cond 0) is");
+  MCEDM_REQUIRE(cd->cond_channels == 0 || d->ch <= 512, "ddpm_plan_create_cond: ch=%d > 512 (the map kernel holds ch / 128 tiles per wave)", d->ch);
+  return ddpm_plan_build(d, cd->cond_channels, out);
 }
 
 extern "C" int mcedm_ddpm_plan_set_variant(mcedm_ddpm_plan* plan, int which, int value) {
@@ -292,6 +324,55 @@ static int dpack(const DAttn& a, const float* const* params, float* pk, hipStrea
   return dpack(a.proj, params, pk, s);
 }
 
+
+// The fold of the conditioning head, fp64 accumulation rounded once (Wx, Wc: the two halves of combine_enc.weight [ch][2 ch]):
+//   [0, n0)        in_fold[o][i][tap] = sum_m Wx[o][m] conv_in.weight[m][i][tap]
+//   [n0, n0 + n1)  map_w[tap][c][o]   = sum_m Wc[o][m] cond_enc.2.weight[m][c][tap]
+//   then ch        bias[o]            = sum_m Wx[o][m] conv_in.bias[m] + combine_enc.bias[o]      (cond None: zero features, no b_enc2)
+//                  map_b[o]           = that + sum_m Wc[o][m] cond_enc.2.bias[m]                  (what the map carries)
+__global__ __launch_bounds__(256) void ddpm_fold_kernel(const float* __restrict__ comb, const float* __restrict__ comb_b,
+                                                        const float* __restrict__ win, const float* __restrict__ bin,
+                                                        const float* __restrict__ w2, const float* __restrict__ b2, int ch, int cin,
+                                                        float* __restrict__ in_fold, float* __restrict__ map_w,
+                                                        float* __restrict__ bias, float* __restrict__ map_b) {
+  const size_t n0 = (size_t)ch * cin * 9, n1 = (size_t)9 * ch * ch, total = n0 + n1 + ch;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    double acc = 0.0;
+    if (e < n0) {
+      const int o = (int)(e / ((size_t)cin * 9)), r = (int)(e % ((size_t)cin * 9));
+      for (int m = 0; m < ch; ++m) acc += (double)comb[(size_t)o * 2 * ch + m] * (double)win[(size_t)m * cin * 9 + r];
+      in_fold[e] = (float)acc;
+    } else if (e < n0 + n1) {
+      const size_t f = e - n0;
+      const int o = (int)(f % ch), c = (int)((f / ch) % ch), tap = (int)(f / ((size_t)ch * ch));
+      for (int m = 0; m < ch; ++m) acc += (double)comb[(size_t)o * 2 * ch + ch + m] * (double)w2[((size_t)m * ch + c) * 9 + tap];
+      map_w[f] = (float)acc;
+    } else {
+      const int o = (int)(e - n0 - n1);
+      double accc = 0.0;
+      for (int m = 0; m < ch; ++m) acc += (double)comb[(size_t)o * 2 * ch + m] * (double)bin[m];
+      for (int m = 0; m < ch; ++m) accc += (double)comb[(size_t)o * 2 * ch + ch + m] * (double)b2[m];
+      bias[o] = (float)(acc + (double)comb_b[o]);
+      map_b[o] = (float)(acc + accc + (double)comb_b[o]);
+    }
+  }
+}
+
+// conv_in of a plan with the head: the folded weight and bias in conv_in's packed slots
+static int dpack_head(const mcedm_ddpm_plan& P, const float* const* params, float* pk, hipStream_t s) {
+  const int ch = P.desc.ch;
+  const DConv& c = P.conv_in;
+  const size_t total = (size_t)ch * P.in_total * 9 + (size_t)9 * ch * ch + ch;
+  hipLaunchKernelGGL(ddpm_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, params[P.cbw], params[P.cbb], params[c.w],
+                     params[c.b], params[P.e2w], params[P.e2b], ch, P.in_total, pk + P.in_fold, pk + P.map_w, pk + c.bias, pk + P.map_b);
+  MCEDM_LAUNCH_CHECK("ddpm_fold_kernel");
+  int rc;
+  if ((rc = launch_pack_conv(pk + P.in_fold, pk + c.wpk, c.cout, c.cin, c.taps, 0, 0, s))) return rc;
+  if (c.wino != NONE && (rc = launch_pack_conv_wino(pk + P.in_fold, pk + c.wino, c.cout, c.cin, 0, s))) return rc;
+  if ((rc = dcopy(pk + P.enc0_w, params[P.e0w], (size_t)ch * P.cond_channels, s))) return rc;
+  return dcopy(pk + P.enc0_b, params[P.e0b], ch, s);
+}
+
 }  // namespace mcedm
 
 extern "C" int mcedm_ddpm_pack_weights(const mcedm_ddpm_plan* plan, const float* const* params, const float* temb_freqs,
@@ -308,7 +389,7 @@ extern "C" int mcedm_ddpm_pack_weights(const mcedm_ddpm_plan* plan, const float*
   if ((rc = dcopy(pk + P.freqs, temb_freqs, ch / 2, s))) return rc;
   if ((rc = dcopy(pk + P.w0, params[P.d0w], (size_t)temb * ch, s)) || (rc = dcopy(pk + P.b0, params[P.d0b], temb, s)) ||
       (rc = dcopy(pk + P.w1, params[P.d1w], (size_t)temb * temb, s)) || (rc = dcopy(pk + P.b1, params[P.d1b], temb, s))) return rc;
-  if ((rc = dpack(P.conv_in, params, pk, s))) return rc;
+  if ((rc = P.cond_channels > 0 ? dpack_head(P, params, pk, s) : dpack(P.conv_in, params, pk, s))) return rc;
   for (auto* v : {&P.down, &P.up})
     for (const DLevel& lv : *v) {
       for (const DRes& r : lv.blocks) if ((rc = dpack(P, r, params, pk, s))) return rc;
@@ -373,6 +454,76 @@ __global__ __launch_bounds__(TEMB_NT) void ddpm_temb_kernel(float t, int ch, con
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) out[r] = (s + bp[r]) + c1b[r];
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// the conditioning map M = (Wc cond_enc.2) (*)circ GELU(cond_enc.0(cond)) + bias   [B, ch, R, R]
+// ------------------------------------------------------------------------------------------
+// An implicit GEMM on the fp32 MFMA: output channels x pixels x (ch * 9).  A workgroup owns CM_PW pixels of one image row.
+// Per chunk of CM_KC encoder channels it forms the GELU features of the three rows it reads (halo included) straight from
+// cond while staging -- wrap-around on both axes, so the ch-channel feature tensor never exists -- then runs the nine
+// taps out of LDS.  Wave w owns the 32-channel output tiles w, w + 4, ...; weights [tap][cin][cout] come from L2 (one
+// coalesced 128-byte row per half-wave).  Runs once per sampler call: 1.2 GFLOP per sample at 128^2.
+constexpr int CM_PW = 32, CM_KC = 64, CM_NT = 256, CM_TM = 4;
+__global__ __launch_bounds__(CM_NT) void ddpm_cond_map_kernel(const float* __restrict__ cond, int cc, const float* __restrict__ w0,
+                                                              const float* __restrict__ b0, const float* __restrict__ wm,
+                                                              const float* __restrict__ bias, int ch, int R,
+                                                              float* __restrict__ out) {
+  __shared__ float g[CM_KC][3][CM_PW + 2];
+  const int x0 = blockIdx.x * CM_PW, y = blockIdx.y, n = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, kh = lane >> 5;
+  const int mtiles = ch / 32;
+  f32x16 acc[CM_TM];
+#pragma unroll
+  for (int i = 0; i < CM_TM; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  const size_t plane = (size_t)R * R;
+  for (int c0 = 0; c0 < ch; c0 += CM_KC) {
+    const int kc = min(CM_KC, ch - c0);                  // a multiple of 32
+    __syncthreads();                                     // the previous chunk's readers are done
+    for (int e = tid; e < kc * 3 * (CM_PW + 2); e += CM_NT) {
+      const int c = e / (3 * (CM_PW + 2)), rem = e - c * (3 * (CM_PW + 2)), r = rem / (CM_PW + 2), cl = rem - r * (CM_PW + 2);
+      const int yy = ((y + r - 1) % R + R) % R, xx = ((x0 + cl - 1) % R + R) % R;       // padding_mode='circular'
+      float v = b0[c0 + c];
+      for (int k = 0; k < cc; ++k) v = fmaf(w0[(size_t)(c0 + c) * cc + k], cond[((size_t)n * cc + k) * plane + (size_t)yy * R + xx], v);
+      g[c][r][cl] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));              // nn.GELU(): the erf form
+    }
+    __syncthreads();
+    for (int tap = 0; tap < 9; ++tap) {
+      const int dy = tap / 3, dx = tap - 3 * dy;
+      const float* wt = wm + ((size_t)tap * ch + c0) * ch;
+      for (int k2 = 0; k2 < kc; k2 += 2) {
+        const float b = g[k2 + kh][dy][col + dx];
+#pragma unroll
+        for (int i = 0; i < CM_TM; ++i) {
+          const int mt = wave + i * (CM_NT / 64);
+          if (mt < mtiles) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wt[(size_t)(k2 + kh) * ch + mt * 32 + col], b, acc[i], 0, 0, 0);
+        }
+      }
+    }
+  }
+  const int x = x0 + col;
+  if (x >= R) return;
+#pragma unroll
+  for (int i = 0; i < CM_TM; ++i) {
+    const int mt = wave + i * (CM_NT / 64);
+    if (mt >= mtiles) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int o = mt * 32 + 4 * kh + (r & 3) + 8 * (r >> 2);
+      out[((size_t)n * ch + o) * plane + (size_t)y * R + x] = acc[i][r] + bias[o];
+    }
+  }
+}
+
+static int launch_cond_map(const mcedm_ddpm_plan& P, const float* pk, const float* cond, float* map, int B, hipStream_t s) {
+  const int R = P.desc.resolution;
+  MCEDM_REQUIRE(B > 0 && B <= 65535, "ddpm_cond_map: batch %d outside [1, 65535]", B);
+  hipLaunchKernelGGL(ddpm_cond_map_kernel, dim3(ceil_div(R, CM_PW), R, B), dim3(CM_NT), 0, s, cond, P.cond_channels, pk + P.enc0_w,
+                     pk + P.enc0_b, pk + P.map_w, pk + P.map_b, P.desc.ch, R, map);
+  MCEDM_LAUNCH_CHECK("ddpm_cond_map_kernel");
+  return MCEDM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -545,11 +696,11 @@ static DHeader dheader(const mcedm_ddpm_plan& P, int B, int H, int W) {
   return h;
 }
 
-// Model.forward (ddim_blocks.py:410-470) with cond None, dx None, x_self_cond None; x is scaled by the rows of coef_in
+// Model.forward (ddim_blocks.py:410-470) with dx None; cond enters as cond_map (null: None); x is scaled by the rows of coef_in
 // (null = identity) while conv_in stages it.  `act` = start of the activation region.  Returns the peak bytes in *peak.
 static int ddpm_forward(const mcedm_ddpm_plan& P, bool dry, const float* pk, const float* x, const Coef* coef_in, float t,
                         float* bias_table, float* out, char* act, int B, hipStream_t s, size_t* peak,
-                        const float* x_self_cond = nullptr) {
+                        const float* x_self_cond = nullptr, const float* cond_map = nullptr) {
   const mcedm_ddpm_desc& d = P.desc;
   const int R = d.resolution, L = d.n_levels;
   int rc;
@@ -573,6 +724,9 @@ static int ddpm_forward(const mcedm_ddpm_plan& P, bool dry, const float* pk, con
     ci.coef = coef_in; ci.coef_batch = 0; ci.act = 0;
     ci.Hs = R; ci.Ws = R; ci.H = R; ci.W = R;
     dst_of(E, ci, h0, P.conv_in, nullptr, true);
+    // the head: conv_in holds the folded weights; with cond the map (which carries its own bias) enters as the residual, in
+    // front of the statistics; without it (cond None: zero features, not cond_enc(0)) the folded bias Wx b_in + b_comb alone
+    if (cond_map) { ci.bias = nullptr; ci.res = cond_map; ci.res_mode = RS_NONE; }
     if ((rc = run_conv(E, ci, 9, h0))) return rc;
     hs.push_back(h0);
   }
@@ -1014,4 +1168,185 @@ extern "C" int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const 
   MCEDM_REQUIRE(rng_seed != nullptr, "ddim_repaint_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return ddim_repaint_impl(plan, packed, sp, hu, init_noise, nullptr, reinterpret_cast<const unsigned long long*>(rng_seed), xs_out,
                            x0_out, return_last, workspace, workspace_bytes, B, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// the single-task model (PlCondDdim on Model): the head's entries and the two samplers of sampler.hip on this network
+// ------------------------------------------------------------------------------------------
+extern "C" int mcedm_ddpm_cond_map(const mcedm_ddpm_plan* plan, const void* packed, const float* cond, float* map_out, int B,
+                                   void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && map_out, "ddpm_cond_map: null argument");
+  MCEDM_REQUIRE(plan->cond_channels > 0, "ddpm_cond_map: the plan was built without the cond_enc head (mcedm_ddpm_plan_create_cond)");
+  MCEDM_REQUIRE(cond != nullptr, "ddpm_cond_map: cond is null on a plan with cond_channels=%d", plan->cond_channels);
+  return launch_cond_map(*plan, (const float*)packed, cond, map_out, B, (hipStream_t)stream);
+}
+
+extern "C" int mcedm_ddpm_forward_cond(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
+                                       const float* cond_map, float t, float* out, void* workspace, size_t workspace_bytes, int B,
+                                       void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_cond: null argument");
+  MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_cond: the network was built without self-conditioning channels");
+  MCEDM_REQUIRE(!cond_map || plan->cond_channels > 0, "ddpm_forward_cond: cond_map given to a plan built without the cond_enc head");
+  DHeader hd; size_t act = 0;
+  int rc = ddpm_sizes(*plan, B, &hd, &act);
+  if (rc) return rc;
+  if ((rc = heun_check_workspace("ddpm_forward_cond", workspace_bytes, hd.total + act))) return rc;
+  return ddpm_forward(*plan, false, (const float*)packed, x, nullptr, t, at<float>(workspace, hd.bias), out,
+                      at<char>(workspace, hd.total), B, (hipStream_t)stream, nullptr, x_self_cond, cond_map);
+}
+
+namespace mcedm {
+// what both samplers check of (plan, cond) and the map they compute once per call (null: cond None)
+static int cond_sampler_check(const char* who, const mcedm_ddpm_plan& P, const float* cond, int cond_channels, int B) {
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "%s: in_channels != out_channels", who);
+  MCEDM_REQUIRE(B > 0, "%s: empty batch", who);
+  MCEDM_REQUIRE(cond_channels == 0 || cond_channels == P.cond_channels, "%s: cond_channels %d is neither 0 nor the plan's %d", who,
+                cond_channels, P.cond_channels);
+  MCEDM_REQUIRE((cond != nullptr) == (cond_channels > 0), "%s: cond goes with cond_channels > 0 (and only with it)", who);
+  return MCEDM_OK;
+}
+static size_t state_floats(const mcedm_ddpm_plan& P, int B) {
+  return (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
+}
+static size_t map_bytes(const mcedm_ddpm_plan& P, int B) {
+  return (size_t)B * P.desc.ch * P.desc.resolution * P.desc.resolution * sizeof(float);
+}
+
+struct DVpBufs : HeunBufs { size_t map, Fu; };
+static DVpBufs dvp_bufs(const mcedm_ddpm_plan& P, int B) {
+  DVpBufs v{heun_bufs(state_floats(P, B)), 0, 0};
+  v.map = heun_take(v, map_bytes(P, B));
+  v.Fu = heun_take(v, state_floats(P, B) * 4);
+  return v;
+}
+
+static int dvp_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
+                           const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
+                           int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "ddpm_vp_heun_sample: null argument");
+  MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "ddpm_vp_heun_sample: null schedule array");
+  const mcedm_ddpm_plan& P = *plan;
+  int rc;
+  if ((rc = cond_sampler_check("ddpm_vp_heun_sample", P, cond, sp->cond_channels, B))) return rc;
+  if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
+  DHeader hd; size_t act = 0;
+  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
+  const DVpBufs vb = dvp_bufs(P, B);
+  if ((rc = heun_check_workspace("ddpm_vp_heun_sample", workspace_bytes, vb.total + hd.total + act))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  const int R = P.desc.resolution;
+  HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)R * R, sp->timesteps, return_last, out, s);
+  void* uws = at<char>(workspace, vb.total);
+  float* map = cond ? at<float>(workspace, vb.map) : nullptr;
+  if (map && (rc = launch_cond_map(P, pk, cond, map, B, s))) return rc;
+  const bool guided = std::fabs(sp->w) >= 0.001 && map != nullptr;             // :937-942, the second evaluation without cond
+  float* F = at<float>(uws, hd.F);
+  float* Fu = guided ? at<float>(workspace, vb.Fu) : nullptr;
+  Coef* coef_in = at<Coef>(uws, hd.coef_in);
+  const int n_self = P.in_total - P.desc.in_channels;
+  // get_denoised (:915-947): D = x + (-sigma) F(c_in x, c_noise, cond); cond itself is NOT scaled (cat_condition False, :932),
+  // so one map serves every noise level; x_self_cond is None (get_self_cond_edm, :1603-1605)
+  return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma_d, float c_noise) -> int {
+    int e;
+    const float sigma = (float)sigma_d;                                   // t.to(torch.float32)
+    const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                // 1 / (sigma ** 2 + 1).sqrt(), fp32
+    if ((e = launch_vp_coef(c_in, n_self, P.desc.in_channels, coef_in, s))) return e;
+    if ((e = ddpm_forward(P, false, pk, h.x32, coef_in, c_noise, at<float>(uws, hd.bias), F, at<char>(uws, hd.total), B, s, nullptr,
+                          nullptr, map))) return e;
+    if (guided && (e = ddpm_forward(P, false, pk, h.x32, coef_in, c_noise, at<float>(uws, hd.bias), Fu, at<char>(uws, hd.total), B, s,
+                                    nullptr, nullptr, nullptr))) return e;
+    return launch_vp_cfg_finish(h.x32, F, Fu, sp->w, sigma, h.total, h.D, s);
+  });
+}
+
+struct DCondDdimBufs { size_t xt, xtn, F, Fu, sc, map, total; };
+static DCondDdimBufs dcond_ddim_bufs(const mcedm_ddpm_plan& P, int B) {
+  DCondDdimBufs b{};
+  auto take = [&](size_t bytes) { size_t o = b.total; b.total += align_up(bytes, 256); return o; };
+  const size_t n = state_floats(P, B);
+  b.xt = take(n * 4); b.xtn = take(n * 4); b.F = take(n * 4); b.Fu = take(n * 4); b.sc = take(n * 4);
+  b.map = take(map_bytes(P, B));
+  return b;
+}
+
+static int dcond_ddim_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
+                           const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
+                           int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && xs_out && x0_out && workspace, "ddpm_cond_ddim_sample: null argument");
+  const mcedm_ddpm_plan& P = *plan;
+  int rc;
+  if ((rc = cond_sampler_check("ddpm_cond_ddim_sample", P, cond, sp->cond_channels, B))) return rc;
+  MCEDM_REQUIRE(!sp->self_cond || P.desc.self_cond, "ddpm_cond_ddim_sample: self-conditioning asked of a network built without it");
+  if ((rc = cond_ddim_check_schedule(sp, eta_noise, rng_seed))) return rc;
+  DHeader hd; size_t act = 0;
+  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
+  const DCondDdimBufs cb = dcond_ddim_bufs(P, B);
+  if ((rc = heun_check_workspace("ddpm_cond_ddim_sample", workspace_bytes, cb.total + hd.total + act))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  void* uws = at<char>(workspace, cb.total);
+  const int R = P.desc.resolution, C = P.desc.in_channels;
+  float* map = cond ? at<float>(workspace, cb.map) : nullptr;
+  if (map && (rc = launch_cond_map(P, pk, cond, map, B, s))) return rc;
+  const bool guided = cond_ddim_guided(sp);
+  // x_self_cond of the next step = this step's x0 prediction, written by the step kernel (:1490, 1505); both passes read it
+  float* sc = sp->self_cond ? at<float>(workspace, cb.sc) : nullptr;
+  CondDdimLoop lp{C, (size_t)R * R, state_floats(P, B), at<float>(workspace, cb.xt), at<float>(workspace, cb.xtn),
+                  at<float>(workspace, cb.F), guided ? at<float>(workspace, cb.Fu) : nullptr, sc, nullptr, C, 0};
+  return cond_ddim_loop(sp, lp, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, s, [&](const float* xt, float t, int step) -> int {
+    const float* xsc = step > 0 ? sc : nullptr;                           // None in the first step: zeros
+    int e = ddpm_forward(P, false, pk, xt, nullptr, t, at<float>(uws, hd.bias), lp.F, at<char>(uws, hd.total), B, s, nullptr, xsc, map);
+    if (e || !guided) return e;
+    return ddpm_forward(P, false, pk, xt, nullptr, t, at<float>(uws, hd.bias), lp.Fu, at<char>(uws, hd.total), B, s, nullptr, xsc, nullptr);
+  });
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_ddpm_vp_sampler_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "ddpm_vp_sampler_workspace_bytes: null argument");
+  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
+  if (rc == MCEDM_OK) *bytes += dvp_bufs(*plan, B).total;
+  return rc;
+}
+extern "C" int mcedm_ddpm_vp_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                         const float* cond, const float* init_noise, const double* step_noise, double* out,
+                                         int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return dvp_sample_impl(plan, packed, sp, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B, stream);
+}
+extern "C" int mcedm_ddpm_vp_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                             const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
+                                             int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return dvp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, stream);
+}
+
+extern "C" int mcedm_ddpm_cond_ddim_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "ddpm_cond_ddim_workspace_bytes: null argument");
+  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
+  if (rc == MCEDM_OK) *bytes += dcond_ddim_bufs(*plan, B).total;
+  return rc;
+}
+extern "C" int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                           const float* cond, const float* init_noise, const float* eta_noise, float* xs_out,
+                                           float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
+                                           void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return dcond_ddim_impl(plan, packed, sp, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace, workspace_bytes,
+                         B, stream);
+}
+extern "C" int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                               const float* cond, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
+                                               float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
+                                               void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return dcond_ddim_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace, workspace_bytes,
+                         B, stream);
 }

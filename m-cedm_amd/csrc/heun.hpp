@@ -1,9 +1,12 @@
-// heun.hpp -- what the three Heun samplers share (EDM and VP on the ADM U-Net: sampler.hip; RePaint on the DDPM U-Net:
-// ddpm.hip): the five state buffers in front of the network's workspace, the trajectory stores, the churn and the
+// heun.hpp -- what the three Heun samplers share (EDM and VP on the ADM U-Net: sampler.hip; RePaint and VP on the DDPM
+// U-Net: ddpm.hip): the five state buffers in front of the network's workspace, the trajectory stores, the churn and the
 // 2nd-order update.  Each sampler keeps its own schedule arithmetic (fp64, on the host), decides itself whether a step
-// churns, and passes its network in as a callable.
+// churns, and passes its network in as a callable.  The VP Heun loop and the conditional DDIM loop, which run on either
+// network, are here whole (vp_heun_loop, cond_ddim_loop).
 #pragma once
+#include <cmath>
 #include <utility>
+#include <vector>
 
 #include "edm.hpp"
 #include "plan.hpp"
@@ -77,6 +80,108 @@ static inline int heun_update(HeunState& h, int i, double t_hat, double t_next, 
       return rc;
   }
   std::swap(h.x, h.xn);
+  return MCEDM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// PlCondDdim.sample_edm (models/ddim.py:1532-1601) on either network
+// ------------------------------------------------------------------------------------------
+// the checks of the schedule arrays; the caller has checked its plan and its pointers
+static inline int vp_check_schedule(const mcedm_vp_sampler_desc* sp, const double* step_noise, const uint64_t* rng_seed) {
+  MCEDM_REQUIRE(sp->timesteps >= 1 && sp->timesteps <= 4096, "vp_heun_sample: timesteps=%d out of range", sp->timesteps);
+  for (int i = 0; i < sp->timesteps; ++i) {
+    MCEDM_REQUIRE(sp->t_hat[i] >= sp->t_steps[i] && sp->t_steps[i] > 0.0, "vp_heun_sample: step %d: t_hat %g < t_cur %g or t_cur <= 0", i,
+                  sp->t_hat[i], sp->t_steps[i]);
+    MCEDM_REQUIRE(sp->t_hat[i] == sp->t_steps[i] || step_noise != nullptr || rng_seed != nullptr,
+                  "vp_heun_sample: step %d churns (t_hat > t_cur) and needs step_noise (or mcedm_vp_heun_sample_rng)", i);
+  }
+  return MCEDM_OK;
+}
+
+// denoise(sigma, c_noise) leaves D(h.x32; sigma) in h.D: get_denoised (:915-947) of the caller's network
+template <class Denoise>
+static inline int vp_heun_loop(HeunState& h, const mcedm_vp_sampler_desc* sp, const float* init_noise, const double* step_noise,
+                               const uint64_t* rng_seed, Denoise&& denoise) {
+  int rc;
+  const int N = sp->timesteps;
+  const double* t = sp->t_steps;
+  // x = u_noise.to(float64) * t_steps[0]   (:1556)
+  if ((rc = launch_heun_init(nullptr, 0, h.C, h.hw, nullptr, init_noise, t[0], h.total, h.x, h.x32, h.s))) return rc;
+  if ((rc = heun_store_step(h, 0))) return rc;
+  for (int i = 0; i < N; ++i) {
+    const double t_cur = t[i], t_next = t[i + 1], t_hat = sp->t_hat[i];
+    if (t_hat != t_cur) {                 // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) * S_noise * eps (:1567); + 0 * eps otherwise
+      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
+      if ((rc = heun_churn(h, c, step_noise ? step_noise + (size_t)i * h.total : nullptr,
+                           reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, nullptr))) return rc;
+    }
+    // Euler step (:1570-1580) at c_noise[2 i], 2nd-order correction (:1583-1593) at c_noise[2 i + 1]
+    auto at_level = [&](double sigma, bool second) { return denoise(sigma, sp->c_noise[2 * i + (second ? 1 : 0)]); };
+    if ((rc = heun_update(h, i, t_hat, t_next, nullptr, at_level))) return rc;
+    if ((rc = heun_store_step(h, i + 1))) return rc;
+  }
+  return heun_store_last(h);
+}
+
+// ------------------------------------------------------------------------------------------
+// PlCondDdim.sample (models/ddim.py:1452-1530) on either network: fp32 throughout
+// ------------------------------------------------------------------------------------------
+static inline int cond_ddim_check_schedule(const mcedm_cond_ddim_desc* sp, const float* eta_noise, const uint64_t* rng_seed) {
+  const int n = sp->num_diffusion_timesteps, N = sp->timesteps;
+  MCEDM_REQUIRE(sp->alphas_cumprod_ext && n >= 2 && N >= 1 && N <= n, "cond_ddim_sample: bad schedule (timesteps=%d of %d)", N, n);
+  MCEDM_REQUIRE(sp->skip_type == 0 || sp->skip_type == 1, "cond_ddim_sample: skip_type must be 0 (uniform) or 1 (quad)");
+  MCEDM_REQUIRE(!(std::fabs(sp->eta) > 1e-10) || eta_noise != nullptr || rng_seed != nullptr, "cond_ddim_sample: eta != 0 needs eta_noise");   // :1509
+  for (int t : ddim_timestep_seq(n, N, sp->skip_type))       // :1463-1470
+    MCEDM_REQUIRE(t >= 0 && t < n, "cond_ddim_sample: timestep %d outside the schedule table", t);
+  return MCEDM_OK;
+}
+static inline bool cond_ddim_guided(const mcedm_cond_ddim_desc* sp) { return !(std::fabs(sp->w) < 0.001); }      // :1493
+
+// The state and network-output buffers of the loop, and where the step kernel leaves the x0 prediction for the next
+// evaluation: channels [sc_off, sc_off + C) of sc (and of sc_u) [B, Cp, H, W]; sc null = no self-conditioning feedback.
+struct CondDdimLoop {
+  int C; size_t hw, total;
+  float *xt, *xtn, *F, *Fu;            // Fu null = no guidance pass
+  float *sc, *sc_u; int Cp, sc_off;
+};
+// net(xt, t, step) runs the network on xt under the label t into b.F (and, guided, without cond into b.Fu)
+template <class Net>
+static inline int cond_ddim_loop(const mcedm_cond_ddim_desc* sp, const CondDdimLoop& b, const float* init_noise, const float* eta_noise,
+                                 const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last, hipStream_t s, Net&& net) {
+  int rc;
+  const std::vector<int> seq = ddim_timestep_seq(sp->num_diffusion_timesteps, sp->timesteps, sp->skip_type);   // walked from its end, seq_next = [-1] + seq[:-1]
+  const int S = (int)seq.size();
+  const bool stochastic = std::fabs(sp->eta) > 1e-10;                   // :1509
+  if (!return_last && (rc = launch_store_f32(init_noise, b.C, b.hw, 0, S + 1, b.total, xs_out, s))) return rc;      // xs = [x]  (:1477)
+  DdimCondStep k{};
+  k.F = b.F; k.Fu = b.Fu;
+  k.w1 = (float)(sp->w + 1.0); k.w = (float)sp->w;
+  k.sc = b.sc; k.sc_u = b.sc_u;
+  k.C = b.C; k.Cp = b.Cp; k.sc_off = b.sc_off; k.hw = b.hw; k.n = b.total;
+  k.T_xs = return_last ? 1 : S + 1; k.T_x0 = return_last ? 1 : S;
+  const float* xt = init_noise;
+  float* bufs[2] = {b.xtn, b.xt};
+  auto alpha = [&](int t) -> float { return sp->alphas_cumprod_ext[t + 1]; };      // compute_alpha(t): index t + 1 (:700-704)
+  for (int step = 0; step < S; ++step) {
+    const int i = seq[S - 1 - step], j = (S - 1 - step) > 0 ? seq[S - 2 - step] : -1;
+    const float a_t = alpha(i), at_next = alpha(j);
+    if ((rc = net(xt, (float)i, step))) return rc;
+    k.xt = xt; k.xt_next = bufs[step & 1];
+    k.s0 = sqrtf(a_t); k.s1 = sqrtf(1.0f - a_t); k.sa = sqrtf(at_next);
+    if (stochastic) {        // c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2), fp32 like the tensors
+      k.c1 = (float)sp->eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
+      k.c2 = sqrtf((1.0f - at_next) - k.c1 * k.c1);
+      k.noise = rng_seed ? nullptr : eta_noise + (size_t)step * b.total;
+      k.seed = reinterpret_cast<const unsigned long long*>(rng_seed); k.draw = (unsigned long long)step;
+    } else {
+      k.c1 = 0.f; k.c2 = sqrtf(1.0f - at_next); k.noise = nullptr; k.seed = nullptr;
+    }
+    const bool store = !return_last || step == S - 1;                   // return_last keeps the last state and x0 only (:1517-1522)
+    k.xs = store ? xs_out : nullptr; k.x0s = store ? x0_out : nullptr;
+    k.t_xs = return_last ? 0 : step + 1; k.t_x0 = return_last ? 0 : step;
+    if ((rc = launch_ddim_cond_step(k, s))) return rc;
+    xt = k.xt_next;
+  }
   return MCEDM_OK;
 }
 

@@ -269,14 +269,8 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
   MCEDM_REQUIRE(sp->cond_channels >= 0 && sp->cond_channels <= P.desc.cond_channels,
                 "vp_heun_sample: cond_channels %d outside [0, %d]", sp->cond_channels, P.desc.cond_channels);
   MCEDM_REQUIRE(cond == nullptr || sp->cond_channels > 0, "vp_heun_sample: cond given with cond_channels 0");
-  MCEDM_REQUIRE(sp->timesteps >= 1 && sp->timesteps <= 4096, "vp_heun_sample: timesteps=%d out of range", sp->timesteps);
+  if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
   const int N = sp->timesteps;
-  const double* t = sp->t_steps;
-  for (int i = 0; i < N; ++i) {
-    MCEDM_REQUIRE(sp->t_hat[i] >= t[i] && t[i] > 0.0, "vp_heun_sample: step %d: t_hat %g < t_cur %g or t_cur <= 0", i, sp->t_hat[i], t[i]);
-    MCEDM_REQUIRE(sp->t_hat[i] == t[i] || step_noise != nullptr || rng_seed != nullptr,
-                  "vp_heun_sample: step %d churns (t_hat > t_cur) and needs step_noise (or mcedm_vp_heun_sample_rng)", i);
-  }
   Layout L;
   if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
   const Header hd = header_for(P, B, H, W);
@@ -294,24 +288,9 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
                                   P.desc.cond_channels - sp->cond_channels, B, H, W, st, stream))) return rc;
     condp = st;
   }
-  // x = u_noise.to(float64) * t_steps[0]   (:1556)
-  if ((rc = launch_heun_init(nullptr, 0, h.C, h.hw, nullptr, init_noise, t[0], h.total, h.x, h.x32, s))) return rc;
-  if ((rc = heun_store_step(h, 0))) return rc;
-  for (int i = 0; i < N; ++i) {
-    const double t_cur = t[i], t_next = t[i + 1], t_hat = sp->t_hat[i];
-    if (t_hat != t_cur) {                 // x_hat = x_cur + sqrt(t_hat^2 - t_cur^2) * S_noise * eps (:1567); + 0 * eps otherwise
-      const double c = std::sqrt(t_hat * t_hat - t_cur * t_cur) * sp->S_noise;
-      if ((rc = heun_churn(h, c, step_noise ? step_noise + (size_t)i * h.total : nullptr,
-                           reinterpret_cast<const unsigned long long*>(rng_seed), (unsigned long long)i, nullptr))) return rc;
-    }
-    // Euler step (:1570-1580) at c_noise[2 i], 2nd-order correction (:1583-1593) at c_noise[2 i + 1]
-    auto denoise = [&](double sigma, bool second) {
-      return vp_denoise(P, L, hd, pk, h.x32, condp, sigma, sp->c_noise[2 * i + (second ? 1 : 0)], sp->w, h.D, uws, B, H, W, s);
-    };
-    if ((rc = heun_update(h, i, t_hat, t_next, nullptr, denoise))) return rc;
-    if ((rc = heun_store_step(h, i + 1))) return rc;
-  }
-  return heun_store_last(h);
+  return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma, float c_noise) {
+    return vp_denoise(P, L, hd, pk, h.x32, condp, sigma, c_noise, sp->w, h.D, uws, B, H, W, s);
+  });
 }
 
 extern "C" int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
@@ -374,12 +353,8 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
   MCEDM_REQUIRE(!sp->self_cond || cc + C <= Cp,
                 "cond_ddim_sample: self-conditioning asked of a plan whose conditioning input is not widened (%d + %d > %d channels)",
                 cc, C, Cp);
-  const int n = sp->num_diffusion_timesteps, N = sp->timesteps;
-  MCEDM_REQUIRE(sp->alphas_cumprod_ext && n >= 2 && N >= 1 && N <= n, "cond_ddim_sample: bad schedule (timesteps=%d of %d)", N, n);
-  MCEDM_REQUIRE(sp->skip_type == 0 || sp->skip_type == 1, "cond_ddim_sample: skip_type must be 0 (uniform) or 1 (quad)");
-  const bool stochastic = std::fabs(sp->eta) > 1e-10;                   // :1509
-  MCEDM_REQUIRE(!stochastic || eta_noise != nullptr || rng_seed != nullptr, "cond_ddim_sample: eta != 0 needs eta_noise");
-  const bool guided = !(std::fabs(sp->w) < 0.001);                      // :1493
+  if ((rc = cond_ddim_check_schedule(sp, eta_noise, rng_seed))) return rc;
+  const bool guided = cond_ddim_guided(sp);
   Layout L;
   if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
   const Header hd = header_for(P, B, H, W);
@@ -392,10 +367,6 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
   float* label = at<float>(uws, hd.c_noise);
   Coef* coef_in = at<Coef>(uws, hd.coef_in);
   void* act = at<char>(uws, hd.total);
-  const std::vector<int> seq = ddim_timestep_seq(n, N, sp->skip_type);   // :1463-1470; walked from its end, seq_next = [-1] + seq[:-1]
-  const int S = (int)seq.size();
-  for (int t : seq) MCEDM_REQUIRE(t >= 0 && t < n, "cond_ddim_sample: timestep %d outside the schedule table", t);
-
   // cond' once per call: cond in its channels, zeros in the others (x_self_cond is None in the first step); the step kernel
   // keeps the self-conditioning channels current from then on.  Guided: the twin with zeros for cond as well.
   float* condp = Cp > 0 ? at<float>(workspace, cb.condp) : nullptr;
@@ -404,44 +375,15 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
     return rc;
   if (condu && (rc = mcedm_eps_self_cond(nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, cc, Cp - cc, B, H, W, condu, stream)))
     return rc;
-  if (!return_last && (rc = launch_store_f32(init_noise, C, hw, 0, S + 1, total, xs_out, s))) return rc;      // xs = [x]  (:1477)
-
-  float* F = at<float>(workspace, cb.F);
-  float* Fu = guided ? at<float>(workspace, cb.Fu) : nullptr;
-  DdimCondStep k{};
-  k.F = F; k.Fu = Fu;
-  k.w1 = (float)(sp->w + 1.0); k.w = (float)sp->w;
-  k.sc = sp->self_cond ? condp : nullptr; k.sc_u = sp->self_cond ? condu : nullptr;
-  k.C = C; k.Cp = Cp; k.sc_off = cc; k.hw = hw; k.n = total;
-  k.T_xs = return_last ? 1 : S + 1; k.T_x0 = return_last ? 1 : S;
-  const float* xt = init_noise;
-  float* bufs[2] = {at<float>(workspace, cb.xtn), at<float>(workspace, cb.xt)};
-  auto alpha = [&](int t) -> float { return sp->alphas_cumprod_ext[t + 1]; };      // compute_alpha(t): index t + 1 (:700-704)
-  for (int step = 0; step < S; ++step) {
-    const int i = seq[S - 1 - step], j = (S - 1 - step) > 0 ? seq[S - 2 - step] : -1;
-    const float a_t = alpha(i), at_next = alpha(j);
-    // the network sees xt itself (no c_in on this path: conv_in rows scaled by 1) under the label t = i
-    if ((rc = launch_vp_prepare(1.0f, Cp + C, (float)i, coef_in, label, s))) return rc;
-    if ((rc = forward_impl(P, L, pk, xt, nullptr, condp, coef_in, 0, label, 1, F, act, B, H, W, s))) return rc;
-    if (guided && (rc = forward_impl(P, L, pk, xt, nullptr, condu, coef_in, 0, label, 1, Fu, act, B, H, W, s)))
-      return rc;
-    k.xt = xt; k.xt_next = bufs[step & 1];
-    k.s0 = sqrtf(a_t); k.s1 = sqrtf(1.0f - a_t); k.sa = sqrtf(at_next);
-    if (stochastic) {        // c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2), fp32 like the tensors
-      k.c1 = (float)sp->eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
-      k.c2 = sqrtf((1.0f - at_next) - k.c1 * k.c1);
-      k.noise = rng_seed ? nullptr : eta_noise + (size_t)step * total;
-      k.seed = reinterpret_cast<const unsigned long long*>(rng_seed); k.draw = (unsigned long long)step;
-    } else {
-      k.c1 = 0.f; k.c2 = sqrtf(1.0f - at_next); k.noise = nullptr; k.seed = nullptr;
-    }
-    const bool store = !return_last || step == S - 1;                   // return_last keeps the last state and x0 only (:1517-1522)
-    k.xs = store ? xs_out : nullptr; k.x0s = store ? x0_out : nullptr;
-    k.t_xs = return_last ? 0 : step + 1; k.t_x0 = return_last ? 0 : step;
-    if ((rc = launch_ddim_cond_step(k, s))) return rc;
-    xt = k.xt_next;
-  }
-  return MCEDM_OK;
+  CondDdimLoop lp{C, hw, total, at<float>(workspace, cb.xt), at<float>(workspace, cb.xtn), at<float>(workspace, cb.F),
+                  guided ? at<float>(workspace, cb.Fu) : nullptr, sp->self_cond ? condp : nullptr, sp->self_cond ? condu : nullptr, Cp, cc};
+  // the network sees xt itself (no c_in on this path: conv_in rows scaled by 1) under the label t
+  return cond_ddim_loop(sp, lp, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, s, [&](const float* xt, float t, int) -> int {
+    int e;
+    if ((e = launch_vp_prepare(1.0f, Cp + C, t, coef_in, label, s))) return e;
+    if ((e = forward_impl(P, L, pk, xt, nullptr, condp, coef_in, 0, label, 1, lp.F, act, B, H, W, s))) return e;
+    return guided ? forward_impl(P, L, pk, xt, nullptr, condu, coef_in, 0, label, 1, lp.Fu, act, B, H, W, s) : MCEDM_OK;
+  });
 }
 
 extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,

@@ -632,18 +632,21 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     Constructor, buffers (``betas``, ``logvar``), state_dict keys and method signatures follow the reference.  The training
     step runs in the HIP library: noising (mcedm_eps_noise_inputs), the self-conditioning pre-pass and its estimate written into
     the network's widened conditioning input (mcedm_eps_self_cond), forward, loss (mcedm_eps_loss) and backward from dF
-    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The DDPM U-Net (``name: ddim*``), the PDE loss term,
-    ``guide_dx`` and ``dx_cond`` raise.  ``sample`` (the DDIM loop, :1452-1530) is
-    mcedm_cond_ddim_sample[_rng].  ``noise_source`` ("device" / "torch", from MCEDM_NOISE_SOURCE) says where the per-step draws of
+    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The PDE loss term, ``guide_dx`` and ``dx_cond`` raise.
+    ``sample`` (the DDIM loop, :1452-1530) is mcedm_cond_ddim_sample[_rng].
+
+    With a ``name`` that does not start with ``adm`` the network is the DDPM U-Net ``Model`` (:43-46;
+    configs/model/ddim_cond_h_res32.yaml: ``name: ddim_cond_h``, ``cat_cond: False``, ``self_cond: True``) with its cond_enc head,
+    for EVALUATION: ``get_denoised``, ``sample_edm``, ``sample``, ``validation_step`` and ``test_step`` run on it
+    (mcedm_ddpm_vp_heun_sample[_rng], mcedm_ddpm_cond_ddim_sample[_rng]); ``training_step`` and ``forward`` raise, because
+    ``Model`` has no backward here.  ``noise_source`` ("device" / "torch", from MCEDM_NOISE_SOURCE) says where the per-step draws of
     the two samplers come from: the sampler's own kernels, or torch tensors drawn up front."""
 
     def __init__(self, hparams):
         super().__init__()
         self.save_hyperparameters()
         m, o = hparams.model, hparams.optimization
-        if not str(hparams.name).startswith("adm"):
-            raise NotImplementedError("PlCondDdim with the DDPM U-Net (models/ddim.py:43-46, Model) has no backward here; only "
-                                      "the ADM U-Net (hparams.name = 'adm*') trains")
+        self._on_ddpm_unet = not str(hparams.name).startswith("adm")                    # models/ddim.py:43-46
         if _opt(m, "dx_cond", False):
             raise NotImplementedError("dx_cond (models/ddim.py:33-35, 199-204) is not built for PlCondDdim")
         if _opt(o, "pde_loss_lambda", 0.0):
@@ -653,7 +656,9 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         if self.node_type:
             m.cond_channels = m.cond_channels + 1
         self._register_schedule(hparams)
-        self.model = DhariwalUNet(hparams)
+        if self._on_ddpm_unet:
+            from .ddim_blocks import Model
+        self.model = Model(hparams) if self._on_ddpm_unet else DhariwalUNet(hparams)
         self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
         self.cond_p = _opt(m, "cond_p", 0.8)                                           # models/ddim.py:1058
         self._init_common(hparams, m.in_channels, m.out_ch)
@@ -706,6 +711,7 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
 
     def forward(self, x, t, noise, cond=None):
         """models/ddim.py:195-226 without gradients: (output, x0_t)."""
+        self._adm_only("forward (the noising pass of training)")
         net = self.model
         with torch.no_grad():
             x_noise, labels, condp, t = self._noised_inputs(x, t, noise, cond, net._ws)
@@ -715,7 +721,13 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             _lib.eps_self_cond(x0_t, None, 0, output.shape[1], x_noise=x_noise, F0=output, t=t, sqrt_ab=sa, sqrt_1mab=sb)
         return output, x0_t
 
+    def _adm_only(self, what):
+        if self._on_ddpm_unet:
+            raise NotImplementedError(f"{what} is not built on the DDPM U-Net (models/ddim.py:43-46, Model): it has no backward "
+                                      "here; only the ADM U-Net (hparams.name = 'adm*') trains")
+
     def training_step(self, train_batch, batch_idx):
+        self._adm_only("training_step")
         h_unnorm, dx, dt, u_unnorm = train_batch
         self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
         x = self.data_transform(h_unnorm, u_unnorm)
@@ -760,6 +772,15 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         B, _, H, W = xt.shape
         with torch.no_grad():
             pk = net.packed_weights()
+            if self._on_ddpm_unet:     # cond is not scaled (cat_condition False, :932): its map once, for both evaluations
+                t_lab = float(labels[0])
+                cmap = None if cond is None else net.plan.cond_map(pk, cond.to(torch.float32).contiguous())
+                x_in = (c_in_dev * xt).contiguous()
+                xsc = None if x_self_cond is None else (c_in_dev * x_self_cond.to(torch.float32)).contiguous()
+                F = net.plan.forward_cond(pk, x_in, t_lab, cond_map=cmap, x_self_cond=xsc, ws=net._ws)
+                if not (w is None or abs(w) < 0.001 or cond is None):
+                    F = (w + 1) * F - w * net.plan.forward_cond(pk, x_in, t_lab, x_self_cond=xsc, ws=net._ws)
+                return xt + (-c_in.new_tensor(s32).to(xt.device)) * F, F
 
             def evaluate(c, sc):
                 # the conv_in rows scale every input channel by c_in: x, cond and x_self_cond (:921-935)

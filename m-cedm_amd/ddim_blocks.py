@@ -4,9 +4,11 @@ Same constructor (``Model(hparams)``), the same ``state_dict`` keys / shapes (``
 ``down.0.block.0.norm1.weight``, ``mid.attn_1.q.weight``, ``up.2.upsample.conv.weight`` ...) so reference checkpoints load
 unchanged, and the same ``forward(x, t, cond=None, x_self_cond=None, dx=None)`` signature; the compute runs in
 libmcedm_hip.so (csrc/ddpm.hip).  The sub-modules only OWN parameters (plain torch layers, i.e. the reference's own
-default initialisation).  What ``PlDdim.sample_edm`` evaluates is built: inference, one timestep for the whole batch,
-``cond`` / ``x_self_cond`` / ``dx`` None.  Everything else (cond_enc, dx conditioning, a self-conditioning tensor, per-sample
-timesteps, autograd) raises instead of silently computing something else.  There is no PyTorch fallback.
+default initialisation).  What the samplers of ``PlDdim`` and ``PlCondDdim`` evaluate is built: inference, one timestep for
+the whole batch, ``x_self_cond`` given or None, and -- with ``cond_channels > 0`` and ``cat_cond: False``
+(configs/model/ddim_cond_h_res32.yaml) -- ``cond`` through the ``cond_enc`` / ``combine_enc`` head.  Everything else (cat_cond on
+this network, dx conditioning, per-sample timesteps, autograd) raises instead of silently computing something else.  There is
+no PyTorch fallback.
 """
 from __future__ import annotations
 
@@ -74,8 +76,9 @@ class Model(nn.Module):
         super().__init__()
         m = hparams.model
         unsupported = []
-        if _get(m, "cond_channels", 0) > 0:
-            unsupported.append("cond_channels > 0 (cond_enc / cat_cond)")
+        cond_channels = int(_get(m, "cond_channels", 0))
+        if cond_channels > 0 and _get(m, "cat_cond", False):
+            unsupported.append("cat_cond on the DDPM U-Net (cond concatenated to the input; only the cond_enc head is built)")
         if _get(m, "dx_cond", False):
             unsupported.append("dx_cond")
         if m.dropout:
@@ -90,15 +93,20 @@ class Model(nn.Module):
         self.ch, self.temb_ch = ch, 4 * ch
         self.num_resolutions, self.num_res_blocks, self.resolution = len(mult), m.num_res_blocks, m.resolution
         self.self_condition = bool(_get(m, "self_cond", False))
-        self.cat_condition, self.dx_cond, self.cat_dx, self.cond_channels = False, False, False, 0
+        self.cat_condition, self.dx_cond, self.cat_dx, self.cond_channels = False, False, False, cond_channels
         self.state_channels = m.in_channels
         self.in_channels = m.in_channels * (2 if self.self_condition else 1)
-        self.cond_enc = self.dx_enc = self.combine_enc = None
         self._arch = dict(in_channels=m.in_channels, out_channels=m.out_ch, ch=ch, ch_mult=mult, num_res_blocks=m.num_res_blocks,
-                          attn_resolutions=tuple(m.attn_resolutions), resolution=m.resolution, self_cond=self.self_condition)
+                          attn_resolutions=tuple(m.attn_resolutions), resolution=m.resolution, self_cond=self.self_condition,
+                          cond_channels=cond_channels)
         self.temb = nn.Module()
         self.temb.dense = nn.ModuleList([nn.Linear(ch, self.temb_ch), nn.Linear(self.temb_ch, self.temb_ch)])
         self.conv_in = nn.Conv2d(self.in_channels, ch, 3, 1, 1)
+        self.cond_enc = self.dx_enc = self.combine_enc = None
+        if cond_channels > 0:          # registered behind conv_in like the reference's (ddim_blocks.py:279-306)
+            self.cond_enc = nn.Sequential(nn.Conv2d(cond_channels, ch, 1, 1, 0), nn.GELU(),
+                                          nn.Conv2d(ch, ch, 3, 1, 1, padding_mode="circular"))
+            self.combine_enc = nn.Conv2d(2 * ch, ch, 1, 1, 0)
         curr_res, in_mult = m.resolution, (1,) + mult
         self.down = nn.ModuleList()
         block_in = ch
@@ -178,8 +186,10 @@ class Model(nn.Module):
         return self._packed
 
     def forward(self, x, t, cond=None, x_self_cond=None, dx=None):
-        if cond is not None or dx is not None:
-            raise NotImplementedError("cond / dx are outside the built path (the samplers pass None for both)")
+        if dx is not None:
+            raise NotImplementedError("dx is outside the built path (the samplers pass None)")
+        if cond is not None and self.cond_enc is None:
+            raise NotImplementedError("cond given to a network built without cond_channels (ddim_blocks.py:401-421 ignores it)")
         if x_self_cond is not None and not self.self_condition:
             raise RuntimeError("x_self_cond given to a network built with self_cond: False")
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
@@ -188,4 +198,8 @@ class Model(nn.Module):
         if t.numel() != 1 and not bool((t == t[0]).all()):
             raise NotImplementedError("one timestep for the whole batch (what the sampler evaluates)")
         sc = None if x_self_cond is None else x_self_cond.to(torch.float32).contiguous()
+        if self.cond_enc is not None:      # the conditioning as its map (None: zero features), then the folded conv_in
+            pk = self.packed_weights()
+            cmap = None if cond is None else self.plan.cond_map(pk, cond.to(torch.float32).contiguous())
+            return self.plan.forward_cond(pk, x.to(torch.float32).contiguous(), float(t[0]), cond_map=cmap, x_self_cond=sc, ws=self._ws)
         return self.plan.forward(self.packed_weights(), x.to(torch.float32).contiguous(), float(t[0]), ws=self._ws, x_self_cond=sc)

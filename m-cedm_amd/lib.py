@@ -37,6 +37,9 @@ EXPORTS = [
     "mcedm_cond_ddim_workspace_bytes", "mcedm_cond_ddim_sample",
     "mcedm_uniform_fill", "mcedm_cond_ddim_sample_rng", "mcedm_ddim_repaint_sample_rng", "mcedm_heun_sample_guided_rng",
     "mcedm_heun_sample_dxcond_rng",
+    "mcedm_ddpm_plan_create_cond", "mcedm_ddpm_cond_map", "mcedm_ddpm_forward_cond", "mcedm_ddpm_vp_sampler_workspace_bytes",
+    "mcedm_ddpm_vp_heun_sample", "mcedm_ddpm_vp_heun_sample_rng", "mcedm_ddpm_cond_ddim_workspace_bytes",
+    "mcedm_ddpm_cond_ddim_sample", "mcedm_ddpm_cond_ddim_sample_rng",
 ]
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
@@ -74,6 +77,10 @@ class DdpmDesc(C.Structure):
                 ("ch_mult", C.c_int32 * MAX_LEVELS), ("num_res_blocks", C.c_int32), ("resolution", C.c_int32),
                 ("n_attn_resolutions", C.c_int32), ("attn_resolutions", C.c_int32 * MAX_LEVELS), ("self_cond", C.c_int32),
                 ("eps", C.c_float)]
+
+
+class DdpmCondDesc(C.Structure):
+    _fields_ = [("cond_channels", C.c_int32), ("cat_cond", C.c_int32)]
 
 
 class RepaintDesc(C.Structure):
@@ -212,6 +219,15 @@ def load() -> C.CDLL:
                                            i32, vp]
     lib.mcedm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32,
                                                i32, i32, vp]
+    lib.mcedm_ddpm_plan_create_cond.argtypes = [C.POINTER(DdpmDesc), C.POINTER(DdpmCondDesc), C.POINTER(vp)]
+    lib.mcedm_ddpm_cond_map.argtypes = [vp, vp, f32p, f32p, i32, vp]
+    lib.mcedm_ddpm_forward_cond.argtypes = [vp, vp, f32p, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
+    lib.mcedm_ddpm_vp_sampler_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
+    lib.mcedm_ddpm_vp_heun_sample.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, f64p, f64p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddpm_vp_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddpm_cond_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
+    lib.mcedm_ddpm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddpm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)          # AttributeError here == header/library drift
         if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
@@ -643,7 +659,10 @@ class DdpmPlan(_PlanBase):
     _SYM, _WHAT = "mcedm_ddpm", "ddpm_"
 
     def __init__(self, in_channels: int, out_channels: int, ch: int, ch_mult: Sequence[int], num_res_blocks: int,
-                 attn_resolutions: Sequence[int], resolution: int, self_cond: bool = True, eps: float = 1e-6):
+                 attn_resolutions: Sequence[int], resolution: int, self_cond: bool = True, eps: float = 1e-6,
+                 cond_channels: int = 0, cat_cond: bool = False):
+        """cond_channels > 0 (with cat_cond False): the cond_enc / combine_enc head of the single-task model
+        (mcedm_ddpm_plan_create_cond); the parameter table then lists cond_enc.* / combine_enc.* behind conv_in.*."""
         lib = load()
         if len(ch_mult) > MAX_LEVELS or len(attn_resolutions) > MAX_LEVELS:
             raise RuntimeError("too many levels / attention resolutions")
@@ -657,9 +676,14 @@ class DdpmPlan(_PlanBase):
         d.self_cond, d.eps = int(bool(self_cond)), eps
         self.desc = d
         h = C.c_void_p()
-        check(lib.mcedm_ddpm_plan_create(C.byref(d), C.byref(h)), "ddpm_plan_create")
+        if cond_channels or cat_cond:
+            cd = DdpmCondDesc(int(cond_channels), int(bool(cat_cond)))
+            check(lib.mcedm_ddpm_plan_create_cond(C.byref(d), C.byref(cd), C.byref(h)), "ddpm_plan_create_cond")
+        else:
+            check(lib.mcedm_ddpm_plan_create(C.byref(d), C.byref(h)), "ddpm_plan_create")
         self._adopt(lib, h)
         self.in_channels, self.out_channels, self.resolution, self.ch = in_channels, out_channels, resolution, ch
+        self.cond_channels = int(cond_channels)
 
     def pack(self, params: Dict[str, torch.Tensor], temb_freqs: torch.Tensor, packed: Optional[torch.Tensor] = None):
         """params keyed like Model.state_dict(); temb_freqs [ch/2] device fp32, built by the caller exactly as
@@ -699,6 +723,100 @@ class DdpmPlan(_PlanBase):
         check(self._lib.mcedm_ddpm_forward(self._h, packed.data_ptr(), _ptr(x), float(t), _ptr(out), buf.data_ptr(),
                                            buf.numel(), B, _stream()), "ddpm_forward")
         return out
+
+    # ---- the single-task model: the cond_enc head and the two samplers of PlCondDdim --------------------------------------
+    def _check_cond(self, cond, who: str):
+        R = self.resolution
+        if cond is not None and tuple(cond.shape[1:]) != (self.cond_channels, R, R):
+            raise RuntimeError(f"{who}: cond {tuple(cond.shape)} != [B, {self.cond_channels}, {R}, {R}]")
+
+    def cond_map(self, packed, cond, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcedm_ddpm_cond_map: M(cond) [B, ch, R, R], what conv_in adds for this conditioning (once per sampler call)."""
+        self._check_cond(cond, "cond_map")
+        B, R = cond.shape[0], self.resolution
+        if out is None:
+            out = torch.empty((B, self.ch, R, R), dtype=torch.float32, device=cond.device)
+        check(self._lib.mcedm_ddpm_cond_map(self._h, packed.data_ptr(), _ptr(cond), _ptr(out), B, _stream()), "ddpm_cond_map")
+        return out
+
+    def forward_cond(self, packed, x, t: float, cond_map=None, x_self_cond=None, ws: Optional[Workspace] = None) -> torch.Tensor:
+        """mcedm_ddpm_forward_cond: Model.forward(x, t, cond, x_self_cond) with cond given as its map (None: cond None)."""
+        self._check_x(x)
+        B, R = x.shape[0], self.resolution
+        if x_self_cond is not None and tuple(x_self_cond.shape) != tuple(x.shape):
+            raise RuntimeError("x_self_cond must have the shape of x")
+        if cond_map is not None and tuple(cond_map.shape) != (B, self.ch, R, R):
+            raise RuntimeError(f"forward_cond: cond_map {tuple(cond_map.shape)} != {(B, self.ch, R, R)}")
+        ws = ws or Workspace()
+        buf = ws.get(self.workspace_bytes(B), x.device)
+        out = torch.empty((B, self.out_channels, R, R), dtype=torch.float32, device=x.device)
+        check(self._lib.mcedm_ddpm_forward_cond(self._h, packed.data_ptr(), _ptr(x), _ptr(x_self_cond), _ptr(cond_map), float(t),
+                                                _ptr(out), buf.data_ptr(), buf.numel(), B, _stream()), "ddpm_forward_cond")
+        return out
+
+    # the sampler methods keep Plan's signatures (H, W: ignored, the state has the plan's resolution): GraphedVpSampler /
+    # GraphedCondDdim and the Lightning module drive either network through them
+    def vp_sampler_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> int:
+        return self._bytes("mcedm_ddpm_vp_sampler_workspace_bytes", "ddpm_vp_sampler_workspace_bytes", B)
+
+    def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
+                  ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcedm_ddpm_vp_heun_sample (rng_seed None) / _rng; returns [B, 1 or N+1, R, R, in] float64."""
+        self._check_x(init_noise)
+        self._check_cond(cond, "vp_sample")
+        B, R = init_noise.shape[0], self.resolution
+        ws = ws or Workspace()
+        buf = ws.get(self.vp_sampler_workspace_bytes(B), init_noise.device)
+        shape = (B, 1 if return_last else vd.timesteps + 1, R, R, self.in_channels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=init_noise.device)
+        elif tuple(out.shape) != shape:
+            raise RuntimeError(f"vp_sample: out has shape {tuple(out.shape)}, expected {shape}")
+        if rng_seed is not None:
+            if step_noise is not None:
+                raise RuntimeError("vp_sample: give step_noise or rng_seed, not both")
+            seed = _seed_ptr(rng_seed, init_noise.device, "vp_sample")
+            check(self._lib.mcedm_ddpm_vp_heun_sample_rng(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise), seed,
+                                                          _ptr(out, torch.float64), int(return_last), buf.data_ptr(), buf.numel(), B,
+                                                          _stream()), "ddpm_vp_heun_sample_rng")
+            return out
+        check(self._lib.mcedm_ddpm_vp_heun_sample(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
+                                                  _ptr(step_noise, torch.float64), _ptr(out, torch.float64), int(return_last),
+                                                  buf.data_ptr(), buf.numel(), B, _stream()), "ddpm_vp_heun_sample")
+        return out
+
+    def cond_ddim_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> int:
+        return self._bytes("mcedm_ddpm_cond_ddim_workspace_bytes", "ddpm_cond_ddim_workspace_bytes", B)
+
+    def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
+                         ws: Optional[Workspace] = None, out=None, rng_seed: Optional[torch.Tensor] = None):
+        """mcedm_ddpm_cond_ddim_sample[_rng] -> (xs, x0_preds), both fp32 'b t h w c', as Plan.cond_ddim_sample returns them."""
+        self._check_x(init_noise)
+        self._check_cond(cond, "cond_ddim_sample")
+        B, R = init_noise.shape[0], self.resolution
+        ws = ws or Workspace()
+        buf = ws.get(self.cond_ddim_workspace_bytes(B), init_noise.device)
+        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
+        shapes = [(B, 1 if return_last else S + 1, R, R, self.in_channels), (B, 1 if return_last else S, R, R, self.in_channels)]
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=torch.float32, device=init_noise.device) for sh in shapes)
+        elif [tuple(o.shape) for o in out] != shapes:
+            raise RuntimeError(f"cond_ddim_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
+        if eta_noise is not None and tuple(eta_noise.shape) != (S,) + tuple(init_noise.shape):
+            raise RuntimeError(f"cond_ddim_sample: eta_noise must be {(S,) + tuple(init_noise.shape)}, got {tuple(eta_noise.shape)}")
+        if rng_seed is not None:
+            if eta_noise is not None:
+                raise RuntimeError("cond_ddim_sample: give eta_noise (materialised draws) or rng_seed (device-side draws), not both")
+            seed = _seed_ptr(rng_seed, init_noise.device, "cond_ddim_sample")
+            check(self._lib.mcedm_ddpm_cond_ddim_sample_rng(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise), seed,
+                                                            _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(), buf.numel(),
+                                                            B, _stream()), "ddpm_cond_ddim_sample_rng")
+            return out[0], out[1]
+        check(self._lib.mcedm_ddpm_cond_ddim_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise),
+                                                    _ptr(eta_noise), _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(),
+                                                    buf.numel(), B, _stream()), "ddpm_cond_ddim_sample")
+        return out[0], out[1]
 
     def ddim_workspace_bytes(self, B: int) -> int:
         return self._bytes("mcedm_ddim_workspace_bytes", "ddim_workspace_bytes", B)
