@@ -895,6 +895,14 @@ __global__ void repaint_mask_kernel(float* __restrict__ m, int C, int H, int W, 
     m[i] = v;
   }
 }
+// m [B, C, R, R] <- the known-region mask of a sampler description's (h_ch, u_ch, n_time_h, n_time_u)
+template <class Desc>
+static int launch_repaint_mask(float* m, int C, int R, const Desc* sp, size_t total, hipStream_t s) {
+  hipLaunchKernelGGL(repaint_mask_kernel, dim3(2048 < (total + 255) / 256 ? 2048 : (unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                     m, C, R, R, sp->h_ch, sp->u_ch, sp->n_time_h, sp->n_time_u, total);
+  MCEDM_LAUNCH_CHECK("repaint_mask_kernel");
+  return MCEDM_OK;
+}
 }  // namespace mcedm
 
 extern "C" int mcedm_repaint_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
@@ -962,9 +970,7 @@ static int repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, const m
     return ddpm_denoise_impl(P, hd, pk, h.x32, s32, cn, h.D, nullptr, uws, B, s);
   };
 
-  hipLaunchKernelGGL(repaint_mask_kernel, dim3(2048 < (total + 255) / 256 ? 2048 : (unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     mask, h.C, S, S, sp->h_ch, sp->u_ch, sp->n_time_h, sp->n_time_u, total);
-  MCEDM_LAUNCH_CHECK("repaint_mask_kernel");
+  if ((rc = launch_repaint_mask(mask, h.C, S, sp, total, s))) return rc;
   {
     const float aT = alpha(t[0]);
     if ((rc = launch_repaint_init(hu, init_noise, mask, sqrtf(aT), sqrtf(1.0f - aT), t[0], total, h.x, h.x32, s))) return rc;
@@ -1038,11 +1044,9 @@ extern "C" int mcedm_normal_fill(double* out, size_t n, const uint64_t* rng_seed
 namespace mcedm {
 struct DdimBufs { size_t xt, x0, et, mask, total; };
 static DdimBufs ddim_bufs(const mcedm_ddpm_plan& P, int B) {
-  DdimBufs r; size_t cur = 0;
-  auto take = [&](size_t bytes) { size_t o = cur; cur += align_up(bytes, 256); return o; };
+  DdimBufs r{};
   const size_t n = (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
-  r.xt = take(n * 4); r.x0 = take(n * 4); r.et = take(n * 4); r.mask = take(n * 4);
-  r.total = cur;
+  r.xt = heun_take(r, n * 4); r.x0 = heun_take(r, n * 4); r.et = heun_take(r, n * 4); r.mask = heun_take(r, n * 4);
   return r;
 }
 }  // namespace mcedm
@@ -1092,10 +1096,7 @@ static int ddim_repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, co
   int rc;
   if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
   const DdimBufs db = ddim_bufs(P, B);
-  if (db.total + hd.total + act > workspace_bytes) {
-    set_error("ddim_repaint_sample: workspace too small (%zu < %zu bytes)", workspace_bytes, db.total + hd.total + act);
-    return MCEDM_ERR_WORKSPACE;
-  }
+  if ((rc = heun_check_workspace("ddim_repaint_sample", workspace_bytes, db.total + hd.total + act))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float* pk = (const float*)packed;
   float* xt = at<float>(workspace, db.xt);
@@ -1108,9 +1109,7 @@ static int ddim_repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, co
   const int Txs = return_last ? 1 : S + 1, Tx0 = return_last ? 1 : S;
   auto alpha = [&](int t) -> float { return sp->alphas_cumprod_ext[t + 1]; };      // compute_alpha(t): index t + 1 (ddim.py:700-704)
 
-  hipLaunchKernelGGL(repaint_mask_kernel, dim3(2048 < (total + 255) / 256 ? 2048 : (unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     mask, C, res, res, sp->h_ch, sp->u_ch, sp->n_time_h, sp->n_time_u, total);
-  MCEDM_LAUNCH_CHECK("repaint_mask_kernel");
+  if ((rc = launch_repaint_mask(mask, C, res, sp, total, s))) return rc;
   {   // x = (hu * a[-1].sqrt() + hu_noise * (1 - a[-1]).sqrt()) * mask + hu_noise * (1 - mask)   (:837-838); a[-1] = alpha(n - 1)
     const float aT = alpha(n - 1);
     if ((rc = launch_ddim_init(hu, init_noise, mask, sqrtf(aT), sqrtf(1.0f - aT), total, xt, s))) return rc;
@@ -1127,13 +1126,8 @@ static int ddim_repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, co
       if ((rc = launch_ddim_x0(xt, et, hu, mask, s0, s1, k < R - 1 ? 1 : 0, total, x0, s))) return rc;
       have_x0 = true;
     }
-    float c1 = 0.f, c2;
-    if (stochastic) {        // c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2), fp32 like the tensors
-      c1 = (float)sp->eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
-      c2 = sqrtf((1.0f - at_next) - c1 * c1);
-    } else {
-      c2 = sqrtf(1.0f - at_next);
-    }
+    const DdimNoiseCoefs nc = ddim_noise_coefs(stochastic, sp->eta, a_t, at_next);
+    const float c1 = nc.c1, c2 = nc.c2;
     if (stochastic && rng_seed) {
       if ((rc = launch_ddim_next_rng(x0, et, hu, init_noise, mask, rng_seed, (unsigned long long)step, sqrtf(at_next), c1, c2, total,
                                      xt, s))) return rc;
@@ -1265,10 +1259,10 @@ static int dvp_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, cons
 struct DCondDdimBufs { size_t xt, xtn, F, Fu, sc, map, total; };
 static DCondDdimBufs dcond_ddim_bufs(const mcedm_ddpm_plan& P, int B) {
   DCondDdimBufs b{};
-  auto take = [&](size_t bytes) { size_t o = b.total; b.total += align_up(bytes, 256); return o; };
   const size_t n = state_floats(P, B);
-  b.xt = take(n * 4); b.xtn = take(n * 4); b.F = take(n * 4); b.Fu = take(n * 4); b.sc = take(n * 4);
-  b.map = take(map_bytes(P, B));
+  b.xt = heun_take(b, n * 4); b.xtn = heun_take(b, n * 4); b.F = heun_take(b, n * 4); b.Fu = heun_take(b, n * 4);
+  b.sc = heun_take(b, n * 4);
+  b.map = heun_take(b, map_bytes(P, B));
   return b;
 }
 

@@ -15,8 +15,9 @@ namespace mcedm {
 
 // byte offsets of the fp64 state x, the next state xn, the Euler slope d, and of the fp32 network input x32 and output D
 struct HeunBufs { size_t x, xn, d, x32, D, total; };
-// a sampler's own buffers go behind the five: each take appends one, 256-byte aligned
-static inline size_t heun_take(HeunBufs& b, size_t bytes) { size_t o = b.total; b.total += align_up(bytes, 256); return o; }
+// a sampler's own buffers go behind the five: each take appends one, 256-byte aligned (any offset table with a `total`)
+template <class Bufs>
+static inline size_t heun_take(Bufs& b, size_t bytes) { size_t o = b.total; b.total += align_up(bytes, 256); return o; }
 static inline HeunBufs heun_bufs(size_t n) {      // n = B * C * H * W state elements
   HeunBufs b{};
   b.x = heun_take(b, n * 8); b.xn = heun_take(b, n * 8); b.d = heun_take(b, n * 8);
@@ -137,6 +138,20 @@ static inline int cond_ddim_check_schedule(const mcedm_cond_ddim_desc* sp, const
 }
 static inline bool cond_ddim_guided(const mcedm_cond_ddim_desc* sp) { return !(std::fabs(sp->w) < 0.001); }      // :1493
 
+// The noise coefficients of one DDIM step (:1509-1513, and :884-894 of sample_with_repeat), fp32 like the tensors:
+// c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2); c1 = 0 when eta is
+struct DdimNoiseCoefs { float c1, c2; };
+static inline DdimNoiseCoefs ddim_noise_coefs(bool stochastic, double eta, float a_t, float at_next) {
+  DdimNoiseCoefs k{0.f, 0.f};
+  if (stochastic) {
+    k.c1 = (float)eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
+    k.c2 = sqrtf((1.0f - at_next) - k.c1 * k.c1);
+  } else {
+    k.c2 = sqrtf(1.0f - at_next);
+  }
+  return k;
+}
+
 // The state and network-output buffers of the loop, and where the step kernel leaves the x0 prediction for the next
 // evaluation: channels [sc_off, sc_off + C) of sc (and of sc_u) [B, Cp, H, W]; sc null = no self-conditioning feedback.
 struct CondDdimLoop {
@@ -168,13 +183,13 @@ static inline int cond_ddim_loop(const mcedm_cond_ddim_desc* sp, const CondDdimL
     if ((rc = net(xt, (float)i, step))) return rc;
     k.xt = xt; k.xt_next = bufs[step & 1];
     k.s0 = sqrtf(a_t); k.s1 = sqrtf(1.0f - a_t); k.sa = sqrtf(at_next);
-    if (stochastic) {        // c1 = eta * sqrt((1 - at / at_next) * (1 - at_next) / (1 - at)); c2 = sqrt((1 - at_next) - c1^2), fp32 like the tensors
-      k.c1 = (float)sp->eta * sqrtf((1.0f - a_t / at_next) * (1.0f - at_next) / (1.0f - a_t));
-      k.c2 = sqrtf((1.0f - at_next) - k.c1 * k.c1);
+    const DdimNoiseCoefs nc = ddim_noise_coefs(stochastic, sp->eta, a_t, at_next);
+    k.c1 = nc.c1; k.c2 = nc.c2;
+    if (stochastic) {
       k.noise = rng_seed ? nullptr : eta_noise + (size_t)step * b.total;
       k.seed = reinterpret_cast<const unsigned long long*>(rng_seed); k.draw = (unsigned long long)step;
     } else {
-      k.c1 = 0.f; k.c2 = sqrtf(1.0f - at_next); k.noise = nullptr; k.seed = nullptr;
+      k.noise = nullptr; k.seed = nullptr;
     }
     const bool store = !return_last || step == S - 1;                   // return_last keeps the last state and x0 only (:1517-1522)
     k.xs = store ? xs_out : nullptr; k.x0s = store ? x0_out : nullptr;

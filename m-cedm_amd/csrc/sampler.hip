@@ -319,12 +319,11 @@ namespace mcedm {
 struct CondDdimBufs { size_t xt, xtn, F, Fu, condp, condu, total; };
 static CondDdimBufs cond_ddim_bufs(const mcedm_plan& P, int B, int H, int W) {
   CondDdimBufs b{};
-  auto take = [&](size_t bytes) { size_t o = b.total; b.total += align_up(bytes, 256); return o; };
   const size_t hw = (size_t)H * W, n = (size_t)B * P.desc.in_channels * hw;
-  b.xt = take(n * 4); b.xtn = take(n * 4);
-  b.F = take((size_t)B * P.desc.out_channels * hw * 4); b.Fu = take((size_t)B * P.desc.out_channels * hw * 4);
+  b.xt = heun_take(b, n * 4); b.xtn = heun_take(b, n * 4);
+  b.F = heun_take(b, (size_t)B * P.desc.out_channels * hw * 4); b.Fu = heun_take(b, (size_t)B * P.desc.out_channels * hw * 4);
   // cond' = cat(cond, x0_t) and cat(0, x0_t), what the unconditional pass reads
-  b.condp = take((size_t)B * P.desc.cond_channels * hw * 4); b.condu = take((size_t)B * P.desc.cond_channels * hw * 4);
+  b.condp = heun_take(b, (size_t)B * P.desc.cond_channels * hw * 4); b.condu = heun_take(b, (size_t)B * P.desc.cond_channels * hw * 4);
   return b;
 }
 }  // namespace mcedm

@@ -372,9 +372,9 @@ class PlCondEdm(_SingleTask):
             # the call replays from one HIP graph, like PlMcedm.sample_edm (the evaluation loops repeat it); the residual
             # descriptions of guide_dx / dx_cond are host-side structs, so they are part of the key and of the capture
             B, _, H, W = init.shape
-            dkey = lambda d: None if d is None else tuple(getattr(d, f) for f, _ in d._fields_)      # noqa: E731
+            dkey = lambda d: None if d is None else _lib.desc_key(d)      # noqa: E731
             key = (B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), init.device.index,
-                   tuple(getattr(sd, f) for f, _ in sd._fields_), dkey(guidance), dkey(dx_input))
+                   _lib.desc_key(sd), dkey(guidance), dkey(dx_input))
             return self._replay(key, lambda: _lib.GraphedSampler(
                 net.plan, packed, sd, B, H, W, masked=False, has_cond=True, churn=churn, return_last=return_last,
                 ws=self._sample_ws, guidance=guidance, dx_input=dx_input, device_noise=dev_noise), eager, h, None, init,
@@ -457,7 +457,7 @@ class PlDdim(_DdpmSchedule, _PlBase):
                                                               rng_seed=sd.to(x.device))
             B = hu.shape[0]
             key = (B, bool(return_last), packed.data_ptr(), hu.device.index, float(self.edm_steps[0]),
-                   tuple(getattr(rd, f) for f, _ in rd._fields_ if f not in ("edm_steps", "alphas_cumprod_ext")))
+                   _lib.desc_key(rd, skip=("edm_steps", "alphas_cumprod_ext")))
             return self._replay(key, lambda: _lib.GraphedRepaint(net.plan, packed, rd, keep, B, return_last, ws=self._sample_ws),
                                 eager, hu, hu_noise, seed)
 
@@ -600,7 +600,7 @@ class PlDdim(_DdpmSchedule, _PlBase):
                 packed, dd, x, nz, en, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, x.device))
             B = hu.shape[0]
             key = ("ddim", B, bool(return_last), stochastic, dev_noise, packed.data_ptr(), hu.device.index, _table_key(ae),
-                   tuple(getattr(dd, f) for f, _ in dd._fields_ if f != "alphas_cumprod_ext"))
+                   _lib.desc_key(dd, skip=("alphas_cumprod_ext",)))
             return self._replay(key, lambda: _lib.GraphedDdimRepaint(net.plan, packed, dd, keep, B, stochastic, return_last,
                                                                      ws=self._sample_ws, device_noise=dev_noise),
                                 eager, hu, hu_noise, eta_noise, **kw)
@@ -879,7 +879,7 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             # the evaluation loops repeat the call: it replays from one HIP graph, like sample_edm of the sibling modules
             B, _, H, W = init.shape
             key = ("ddim", B, H, W, bool(return_last), stochastic, dev_noise, packed.data_ptr(), init.device.index, _table_key(ae),
-                   tuple(getattr(dd, f) for f, _ in dd._fields_ if f != "alphas_cumprod_ext"))
+                   _lib.desc_key(dd, skip=("alphas_cumprod_ext",)))
             return self._replay(key, lambda: _lib.GraphedCondDdim(net.plan, packed, dd, B, H, W, stochastic, return_last=return_last,
                                                                   ws=self._sample_ws, device_noise=dev_noise),
                                 eager, cond, init, eta_noise, **kw)

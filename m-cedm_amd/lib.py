@@ -41,6 +41,13 @@ EXPORTS = [
     "mcedm_ddpm_vp_heun_sample", "mcedm_ddpm_vp_heun_sample_rng", "mcedm_ddpm_cond_ddim_workspace_bytes",
     "mcedm_ddpm_cond_ddim_sample", "mcedm_ddpm_cond_ddim_sample_rng",
 ]
+# The sampler entries _PlanBase._sample_call drives, with the number of materialised-noise pointers each takes; every one
+# has a "_rng" twin that takes ONE seed pointer in their place.  A new sampler is a row here and a method that names it.
+SAMPLER_STEMS = {
+    "mcedm_heun_sample": 1, "mcedm_heun_sample_guided": 1, "mcedm_heun_sample_dxcond": 1,
+    "mcedm_vp_heun_sample": 1, "mcedm_ddpm_vp_heun_sample": 1, "mcedm_cond_ddim_sample": 1, "mcedm_ddpm_cond_ddim_sample": 1,
+    "mcedm_ddim_repaint_sample": 1, "mcedm_repaint_sample": 2,
+}
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
 VARIANTS = {"conv_wino": 0, "conv_wino1": 1, "conv_resident": 2, "conv8": 3, "attn_fused": 4, "wgrad_wino": 5, "conv1x1_reg": 6,
@@ -265,6 +272,12 @@ def sampler_desc(sp, sigma_data=1.0, net_sigma_min=0.002, net_sigma_max=80.0) ->
                        float(net_sigma_min), float(net_sigma_max))
 
 
+def desc_key(desc: C.Structure, skip: Sequence[str] = ()) -> tuple:
+    """The hashable tuple of a ctypes description's fields, minus the pointer fields named in ``skip`` (their tables enter a
+    cache key by value, where they can change): what tells two captured sampler calls apart."""
+    return tuple(getattr(desc, f) for f, _ in desc._fields_ if f not in skip)
+
+
 def edm_t_steps(sd: SamplerDesc) -> List[float]:
     arr = (C.c_double * (sd.timesteps + 1))()
     check(load().mcedm_edm_t_steps(C.byref(sd), arr), "edm_t_steps")
@@ -346,6 +359,70 @@ class _PlanBase:
         sz = C.c_size_t()
         check(getattr(self._lib, symbol)(self._h, *args, C.byref(sz)), what)
         return sz.value
+
+    # ---- the samplers ----------------------------------------------------------------------
+    def _sample_call(self, who: str, stem: str, packed, head: Sequence, noise: Sequence[tuple], rng_seed, out, shapes: List[tuple],
+                     dtype, return_last: bool, ws: Optional["Workspace"], nbytes: int, dims: tuple, device):
+        """The call every sampler method makes: ``stem(plan, packed, *head, <draws>, <outputs>, return_last, workspace, bytes,
+        *dims, stream)``.  noise: (name, tensor or None, dtype, shape) of each materialised draw ``stem`` takes; with rng_seed
+        (device-side draws) ``stem + "_rng"`` runs instead, the one seed pointer in their place.  shapes: of the one or two
+        ``dtype`` outputs, allocated here or checked against the caller's ``out`` (a graphed call's static tensors); returns
+        the tensor, or the pair.  Every check runs before anything is enqueued."""
+        buf = (ws or Workspace()).get(nbytes, device)
+        single = len(shapes) == 1
+        if out is None:
+            outs = [torch.empty(sh, dtype=dtype, device=device) for sh in shapes]
+        else:
+            outs = [out] if single else list(out)
+            got = [tuple(o.shape) for o in outs]
+            if got != shapes:
+                raise RuntimeError(f"{who}: out has shape {got[0]}, expected {shapes[0]}" if single else
+                                   f"{who}: out has shapes {got}, expected {shapes}")
+        assert len(noise) == SAMPLER_STEMS[stem], stem
+        for name, t, dt, shape in noise:
+            if t is not None and (t.dtype != dt or tuple(t.shape) != tuple(shape)):
+                raise RuntimeError(f"{who}: {name} must be {dt} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        if rng_seed is not None:
+            if any(t is not None for _, t, _, _ in noise):
+                raise RuntimeError(f"{who}: give {' / '.join(n[0] for n in noise)} (materialised draws) or rng_seed (device-side "
+                                   "draws), not both")
+            stem, draws = stem + "_rng", [_seed_ptr(rng_seed, device, who)]
+        else:
+            draws = [_ptr(t, dt) for _, t, dt, _ in noise]
+        check(getattr(self._lib, stem)(self._h, packed.data_ptr(), *head, *draws, *[_ptr(o, dtype) for o in outs], int(return_last),
+                                       buf.data_ptr(), buf.numel(), *dims, _stream()), stem[len("mcedm_"):])
+        return outs[0] if single else (outs[0], outs[1])
+
+    # The two samplers of the single-task model run on either network: each plan supplies its symbol prefix (_WHAT), its size
+    # queries, the trailing size arguments of its entries (_dims) and its input checks with the state's (H, W) (_state_hw).
+    def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
+                  ws: Optional["Workspace"] = None, rng_seed: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcedm_[ddpm_]vp_heun_sample (rng_seed None) / its _rng form; returns [B, 1 or N+1, H, W, in] float64 (``out``, when
+        given: a graphed call's static tensor)."""
+        H, W = self._state_hw(init_noise, cond, "vp_sample")
+        B, N = init_noise.shape[0], vd.timesteps
+        return self._sample_call("vp_sample", f"mcedm_{self._WHAT}vp_heun_sample", packed,
+                                 (C.byref(vd), _ptr(cond), _ptr(init_noise)),
+                                 [("step_noise", step_noise, torch.float64, (N,) + tuple(init_noise.shape))], rng_seed, out,
+                                 [(B, 1 if return_last else N + 1, H, W, self.in_channels)], torch.float64, return_last, ws,
+                                 self.vp_sampler_workspace_bytes(B, H, W), self._dims(B, H, W), init_noise.device)
+
+    def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
+                         ws: Optional["Workspace"] = None, out=None, rng_seed: Optional[torch.Tensor] = None):
+        """mcedm_[ddpm_]cond_ddim_sample (PlCondDdim.sample on the device) -> (xs, x0_preds), both fp32 'b t h w c': S + 1 and S
+        slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors).  rng_seed (int64 [1]
+        on the device): the uniform draws of the eta != 0 steps are generated inside the step kernel (the _rng form, step k =
+        draw k of uniform_fill) instead of being read from eta_noise [S, B, C, H, W]."""
+        H, W = self._state_hw(init_noise, cond, "cond_ddim_sample")
+        B, Cc = init_noise.shape[0], self.in_channels
+        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
+        return self._sample_call("cond_ddim_sample", f"mcedm_{self._WHAT}cond_ddim_sample", packed,
+                                 (C.byref(dd), _ptr(cond), _ptr(init_noise)),
+                                 [("eta_noise", eta_noise, torch.float32, (S,) + tuple(init_noise.shape))], rng_seed, out,
+                                 [(B, 1 if return_last else S + 1, H, W, Cc), (B, 1 if return_last else S, H, W, Cc)],
+                                 torch.float32, return_last, ws, self.cond_ddim_workspace_bytes(B, H, W), self._dims(B, H, W),
+                                 init_noise.device)
 
 
 class Plan(_PlanBase):
@@ -476,64 +553,14 @@ class Plan(_PlanBase):
     def vp_sampler_workspace_bytes(self, B: int, H: int, W: int) -> int:
         return self._bytes("mcedm_vp_sampler_workspace_bytes", "vp_sampler_workspace_bytes", B, H, W)
 
-    def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
-                  ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mcedm_vp_heun_sample (rng_seed None) / mcedm_vp_heun_sample_rng; returns [B, 1 or N+1, H, W, in] float64 (``out``, when
-        given: a graphed call's static tensor)."""
-        B, _, H, W = init_noise.shape
-        ws = ws or Workspace()
-        buf = ws.get(self.vp_sampler_workspace_bytes(B, H, W), init_noise.device)
-        T = 1 if return_last else vd.timesteps + 1
-        if out is None:
-            out = torch.empty((B, T, H, W, self.in_channels), dtype=torch.float64, device=init_noise.device)
-        elif tuple(out.shape) != (B, T, H, W, self.in_channels):
-            raise RuntimeError(f"vp_sample: out has shape {tuple(out.shape)}, expected {(B, T, H, W, self.in_channels)}")
-        if rng_seed is not None:
-            if step_noise is not None:
-                raise RuntimeError("vp_sample: give step_noise or rng_seed, not both")
-            seed = _seed_ptr(rng_seed, init_noise.device, "vp_sample")
-            check(self._lib.mcedm_vp_heun_sample_rng(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
-                                                     seed, _ptr(out, torch.float64), int(return_last),
-                                                     buf.data_ptr(), buf.numel(), B, H, W, _stream()), "vp_heun_sample_rng")
-            return out
-        check(self._lib.mcedm_vp_heun_sample(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
-                                             _ptr(step_noise, torch.float64), _ptr(out, torch.float64), int(return_last),
-                                             buf.data_ptr(), buf.numel(), B, H, W, _stream()), "vp_heun_sample")
-        return out
-
     def cond_ddim_workspace_bytes(self, B: int, H: int, W: int) -> int:
         return self._bytes("mcedm_cond_ddim_workspace_bytes", "cond_ddim_workspace_bytes", B, H, W)
 
-    def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
-                         ws: Optional[Workspace] = None, out=None, rng_seed: Optional[torch.Tensor] = None):
-        """mcedm_cond_ddim_sample (PlCondDdim.sample on the device) -> (xs, x0_preds), both fp32 'b t h w c': S + 1 and S
-        slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors).  rng_seed (int64 [1]
-        on the device): the uniform draws of the eta != 0 steps are generated inside the step kernel (mcedm_cond_ddim_sample_rng,
-        step k = draw k of uniform_fill) instead of being read from eta_noise."""
-        B, _, H, W = init_noise.shape
-        ws = ws or Workspace()
-        buf = ws.get(self.cond_ddim_workspace_bytes(B, H, W), init_noise.device)
-        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
-        shapes = [(B, 1 if return_last else S + 1, H, W, self.in_channels), (B, 1 if return_last else S, H, W, self.in_channels)]
-        if out is None:
-            out = tuple(torch.empty(sh, dtype=torch.float32, device=init_noise.device) for sh in shapes)
-        elif [tuple(o.shape) for o in out] != shapes:
-            raise RuntimeError(f"cond_ddim_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
-        if eta_noise is not None and tuple(eta_noise.shape) != (S,) + tuple(init_noise.shape):
-            raise RuntimeError(f"cond_ddim_sample: eta_noise must be {(S,) + tuple(init_noise.shape)}, got {tuple(eta_noise.shape)}")
-        if rng_seed is not None:
-            if eta_noise is not None:
-                raise RuntimeError("cond_ddim_sample: give eta_noise (materialised draws) or rng_seed (device-side draws), not both")
-            seed = _seed_ptr(rng_seed, init_noise.device, "cond_ddim_sample")
-            check(self._lib.mcedm_cond_ddim_sample_rng(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise), seed,
-                                                       _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(), buf.numel(),
-                                                       B, H, W, _stream()), "cond_ddim_sample_rng")
-            return out[0], out[1]
-        check(self._lib.mcedm_cond_ddim_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise),
-                                               _ptr(eta_noise), _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(),
-                                               buf.numel(), B, H, W, _stream()), "cond_ddim_sample")
-        return out[0], out[1]
+    def _dims(self, B: int, H: int, W: int) -> tuple:
+        return B, H, W
+
+    def _state_hw(self, x, cond, who: str):
+        return x.shape[2], x.shape[3]
 
     def sample(self, packed, sd: SamplerDesc, cond, mask, init_noise, step_noise=None, return_last: bool = True,
                ws: Optional[Workspace] = None, out: Optional[torch.Tensor] = None,
@@ -544,57 +571,20 @@ class Plan(_PlanBase):
         applies it (mcedm_heun_sample_rng and its _guided / _dxcond forms) instead of being read from step_noise
         [N, B, C, H, W] float64."""
         B, _, H, W = init_noise.shape
-        ws = ws or Workspace()
-        buf = ws.get(self.sampler_workspace_bytes(B, H, W), init_noise.device)
-        T = 1 if return_last else sd.timesteps + 1
-        if out is None:
-            out = torch.empty((B, T, H, W, self.in_channels), dtype=torch.float64, device=init_noise.device)
-        elif tuple(out.shape) != (B, T, H, W, self.in_channels):
-            raise RuntimeError(f"sample: out has shape {tuple(out.shape)}, expected {(B, T, H, W, self.in_channels)}")
-        seed = None
-        if rng_seed is not None:
-            if step_noise is not None:
-                raise RuntimeError("sample: give step_noise (materialised draws) or rng_seed (device-side draws), not both")
-            seed = _seed_ptr(rng_seed, init_noise.device, "sample")
+        N = sd.timesteps
         if dx_input is not None:
             if mask is not None:
                 raise RuntimeError("sample: dx_cond sampling is the unmasked single-task sampler")
-            if seed is not None:
-                check(self._lib.mcedm_heun_sample_dxcond_rng(self._h, packed.data_ptr(), C.byref(sd), C.byref(dx_input),
-                                                             C.byref(guidance) if guidance is not None else None, _ptr(cond),
-                                                             _ptr(init_noise), seed, _ptr(out, torch.float64), int(return_last),
-                                                             buf.data_ptr(), buf.numel(), B, H, W, _stream()),
-                      "heun_sample_dxcond_rng")
-                return out
-            check(self._lib.mcedm_heun_sample_dxcond(self._h, packed.data_ptr(), C.byref(sd), C.byref(dx_input),
-                                                     C.byref(guidance) if guidance is not None else None, _ptr(cond),
-                                                     _ptr(init_noise), _ptr(step_noise, torch.float64), _ptr(out, torch.float64),
-                                                     int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
-                  "heun_sample_dxcond")
-            return out
-        if guidance is not None:
-            if seed is not None:
-                check(self._lib.mcedm_heun_sample_guided_rng(self._h, packed.data_ptr(), C.byref(sd), C.byref(guidance), _ptr(cond),
-                                                             _ptr(mask), _ptr(init_noise), seed, _ptr(out, torch.float64),
-                                                             int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
-                      "heun_sample_guided_rng")
-                return out
-            check(self._lib.mcedm_heun_sample_guided(self._h, packed.data_ptr(), C.byref(sd), C.byref(guidance), _ptr(cond),
-                                                     _ptr(mask), _ptr(init_noise), _ptr(step_noise, torch.float64),
-                                                     _ptr(out, torch.float64), int(return_last), buf.data_ptr(), buf.numel(),
-                                                     B, H, W, _stream()), "heun_sample_guided")
-            return out
-        if seed is not None:
-            check(self._lib.mcedm_heun_sample_rng(self._h, packed.data_ptr(), C.byref(sd), _ptr(cond), _ptr(mask),
-                                                  _ptr(init_noise), seed, _ptr(out, torch.float64),
-                                                  int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
-                  "heun_sample_rng")
-            return out
-        check(self._lib.mcedm_heun_sample(self._h, packed.data_ptr(), C.byref(sd), _ptr(cond), _ptr(mask),
-                                          _ptr(init_noise), _ptr(step_noise, torch.float64), _ptr(out, torch.float64),
-                                          int(return_last), buf.data_ptr(), buf.numel(), B, H, W, _stream()),
-              "heun_sample")
-        return out
+            stem = "mcedm_heun_sample_dxcond"
+            head = (C.byref(sd), C.byref(dx_input), C.byref(guidance) if guidance is not None else None, _ptr(cond), _ptr(init_noise))
+        elif guidance is not None:
+            stem, head = "mcedm_heun_sample_guided", (C.byref(sd), C.byref(guidance), _ptr(cond), _ptr(mask), _ptr(init_noise))
+        else:
+            stem, head = "mcedm_heun_sample", (C.byref(sd), _ptr(cond), _ptr(mask), _ptr(init_noise))
+        return self._sample_call("sample", stem, packed, head,
+                                 [("step_noise", step_noise, torch.float64, (N,) + tuple(init_noise.shape))], rng_seed, out,
+                                 [(B, 1 if return_last else N + 1, H, W, self.in_channels)], torch.float64, return_last, ws,
+                                 self.sampler_workspace_bytes(B, H, W), (B, H, W), init_noise.device)
 
 
 def repaint_desc(sp, edm_steps: torch.Tensor, alphas_ext: torch.Tensor, h_ch: int, u_ch: int):
@@ -754,69 +744,21 @@ class DdpmPlan(_PlanBase):
                                                 _ptr(out), buf.data_ptr(), buf.numel(), B, _stream()), "ddpm_forward_cond")
         return out
 
-    # the sampler methods keep Plan's signatures (H, W: ignored, the state has the plan's resolution): GraphedVpSampler /
-    # GraphedCondDdim and the Lightning module drive either network through them
+    # the size queries keep Plan's signatures (H, W: ignored, the state has the plan's resolution): GraphedVpSampler /
+    # GraphedCondDdim and the Lightning module drive either network through them and through vp_sample / cond_ddim_sample
     def vp_sampler_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> int:
         return self._bytes("mcedm_ddpm_vp_sampler_workspace_bytes", "ddpm_vp_sampler_workspace_bytes", B)
-
-    def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
-                  ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mcedm_ddpm_vp_heun_sample (rng_seed None) / _rng; returns [B, 1 or N+1, R, R, in] float64."""
-        self._check_x(init_noise)
-        self._check_cond(cond, "vp_sample")
-        B, R = init_noise.shape[0], self.resolution
-        ws = ws or Workspace()
-        buf = ws.get(self.vp_sampler_workspace_bytes(B), init_noise.device)
-        shape = (B, 1 if return_last else vd.timesteps + 1, R, R, self.in_channels)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=init_noise.device)
-        elif tuple(out.shape) != shape:
-            raise RuntimeError(f"vp_sample: out has shape {tuple(out.shape)}, expected {shape}")
-        if rng_seed is not None:
-            if step_noise is not None:
-                raise RuntimeError("vp_sample: give step_noise or rng_seed, not both")
-            seed = _seed_ptr(rng_seed, init_noise.device, "vp_sample")
-            check(self._lib.mcedm_ddpm_vp_heun_sample_rng(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise), seed,
-                                                          _ptr(out, torch.float64), int(return_last), buf.data_ptr(), buf.numel(), B,
-                                                          _stream()), "ddpm_vp_heun_sample_rng")
-            return out
-        check(self._lib.mcedm_ddpm_vp_heun_sample(self._h, packed.data_ptr(), C.byref(vd), _ptr(cond), _ptr(init_noise),
-                                                  _ptr(step_noise, torch.float64), _ptr(out, torch.float64), int(return_last),
-                                                  buf.data_ptr(), buf.numel(), B, _stream()), "ddpm_vp_heun_sample")
-        return out
 
     def cond_ddim_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> int:
         return self._bytes("mcedm_ddpm_cond_ddim_workspace_bytes", "ddpm_cond_ddim_workspace_bytes", B)
 
-    def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
-                         ws: Optional[Workspace] = None, out=None, rng_seed: Optional[torch.Tensor] = None):
-        """mcedm_ddpm_cond_ddim_sample[_rng] -> (xs, x0_preds), both fp32 'b t h w c', as Plan.cond_ddim_sample returns them."""
-        self._check_x(init_noise)
-        self._check_cond(cond, "cond_ddim_sample")
-        B, R = init_noise.shape[0], self.resolution
-        ws = ws or Workspace()
-        buf = ws.get(self.cond_ddim_workspace_bytes(B), init_noise.device)
-        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
-        shapes = [(B, 1 if return_last else S + 1, R, R, self.in_channels), (B, 1 if return_last else S, R, R, self.in_channels)]
-        if out is None:
-            out = tuple(torch.empty(sh, dtype=torch.float32, device=init_noise.device) for sh in shapes)
-        elif [tuple(o.shape) for o in out] != shapes:
-            raise RuntimeError(f"cond_ddim_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
-        if eta_noise is not None and tuple(eta_noise.shape) != (S,) + tuple(init_noise.shape):
-            raise RuntimeError(f"cond_ddim_sample: eta_noise must be {(S,) + tuple(init_noise.shape)}, got {tuple(eta_noise.shape)}")
-        if rng_seed is not None:
-            if eta_noise is not None:
-                raise RuntimeError("cond_ddim_sample: give eta_noise (materialised draws) or rng_seed (device-side draws), not both")
-            seed = _seed_ptr(rng_seed, init_noise.device, "cond_ddim_sample")
-            check(self._lib.mcedm_ddpm_cond_ddim_sample_rng(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise), seed,
-                                                            _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(), buf.numel(),
-                                                            B, _stream()), "ddpm_cond_ddim_sample_rng")
-            return out[0], out[1]
-        check(self._lib.mcedm_ddpm_cond_ddim_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(cond), _ptr(init_noise),
-                                                    _ptr(eta_noise), _ptr(out[0]), _ptr(out[1]), int(return_last), buf.data_ptr(),
-                                                    buf.numel(), B, _stream()), "ddpm_cond_ddim_sample")
-        return out[0], out[1]
+    def _dims(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> tuple:
+        return (B,)
+
+    def _state_hw(self, x, cond, who: str):
+        self._check_x(x)
+        self._check_cond(cond, who)
+        return self.resolution, self.resolution
 
     def ddim_workspace_bytes(self, B: int) -> int:
         return self._bytes("mcedm_ddim_workspace_bytes", "ddim_workspace_bytes", B)
@@ -828,30 +770,13 @@ class DdpmPlan(_PlanBase):
         draw k of uniform_fill) instead of being read from eta_noise.  out: the pair to write into (a graphed call's static
         tensors)."""
         self._check_x(hu)
-        B = hu.shape[0]
-        ws = ws or Workspace()
-        buf = ws.get(self.ddim_workspace_bytes(B), hu.device)
-        n = dd.num_diffusion_timesteps
-        S = len(ddim_timesteps(n, dd.timesteps, dd.skip_type))
-        R = self.resolution
-        shapes = [(B, 1 if return_last else S + 1, R, R, self.in_channels), (B, 1 if return_last else S, R, R, self.in_channels)]
-        if out is None:
-            out = tuple(torch.empty(sh, dtype=torch.float32, device=hu.device) for sh in shapes)
-        elif [tuple(o.shape) for o in out] != shapes:
-            raise RuntimeError(f"ddim_repaint_sample: out has shapes {[tuple(o.shape) for o in out]}, expected {shapes}")
-        xs, x0 = out
-        if rng_seed is not None:
-            if eta_noise is not None:
-                raise RuntimeError("ddim_repaint_sample: give eta_noise (materialised draws) or rng_seed (device-side draws), not both")
-            seed = _seed_ptr(rng_seed, hu.device, "ddim_repaint_sample")
-            check(self._lib.mcedm_ddim_repaint_sample_rng(self._h, packed.data_ptr(), C.byref(dd), _ptr(hu), _ptr(init_noise), seed,
-                                                          _ptr(xs), _ptr(x0), int(return_last), buf.data_ptr(), buf.numel(), B,
-                                                          _stream()), "ddim_repaint_sample_rng")
-            return xs, x0
-        check(self._lib.mcedm_ddim_repaint_sample(self._h, packed.data_ptr(), C.byref(dd), _ptr(hu), _ptr(init_noise),
-                                                  _ptr(eta_noise), _ptr(xs), _ptr(x0), int(return_last), buf.data_ptr(),
-                                                  buf.numel(), B, _stream()), "ddim_repaint_sample")
-        return xs, x0
+        B, R, Cc = hu.shape[0], self.resolution, self.in_channels
+        S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
+        return self._sample_call("ddim_repaint_sample", "mcedm_ddim_repaint_sample", packed,
+                                 (C.byref(dd), _ptr(hu), _ptr(init_noise)),
+                                 [("eta_noise", eta_noise, torch.float32, (S,) + tuple(init_noise.shape))], rng_seed, out,
+                                 [(B, 1 if return_last else S + 1, R, R, Cc), (B, 1 if return_last else S, R, R, Cc)],
+                                 torch.float32, return_last, ws, self.ddim_workspace_bytes(B), (B,), hu.device)
 
     def denoise(self, packed, x, sigma: float, c_noise: float, ws: Optional[Workspace] = None, want_F: bool = False):
         self._check_x(x)
@@ -870,27 +795,12 @@ class DdpmPlan(_PlanBase):
         """rng_seed (device int64 [1]): the per-step / per-loop noise is generated on the device from that seed
         (mcedm_repaint_sample_rng) instead of being read from step_noise / repeat_noise."""
         self._check_x(hu)
-        B = hu.shape[0]
-        ws = ws or Workspace()
-        buf = ws.get(self.repaint_workspace_bytes(B), hu.device)
-        T = 1 if return_last else rd.timesteps + 1
-        shape = (B, T, self.resolution, self.resolution, self.in_channels)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=hu.device)
-        elif tuple(out.shape) != shape:
-            raise RuntimeError(f"repaint_sample: out has shape {tuple(out.shape)}, expected {shape}")
-        if rng_seed is not None:
-            if step_noise is not None or repeat_noise is not None:
-                raise RuntimeError("repaint_sample: give either noise tensors or rng_seed")
-            check(self._lib.mcedm_repaint_sample_rng(self._h, packed.data_ptr(), C.byref(rd), _ptr(hu), _ptr(init_noise),
-                                                     _ptr(rng_seed, torch.int64), _ptr(out, torch.float64), int(return_last),
-                                                     buf.data_ptr(), buf.numel(), B, _stream()), "repaint_sample_rng")
-            return out
-        check(self._lib.mcedm_repaint_sample(self._h, packed.data_ptr(), C.byref(rd), _ptr(hu), _ptr(init_noise),
-                                             _ptr(step_noise, torch.float64), _ptr(repeat_noise, torch.float64),
-                                             _ptr(out, torch.float64), int(return_last), buf.data_ptr(), buf.numel(), B,
-                                             _stream()), "repaint_sample")
-        return out
+        B, R, N = hu.shape[0], self.resolution, rd.timesteps
+        return self._sample_call("repaint_sample", "mcedm_repaint_sample", packed, (C.byref(rd), _ptr(hu), _ptr(init_noise)),
+                                 [("step_noise", step_noise, torch.float64, (N,) + tuple(hu.shape)),
+                                  ("repeat_noise", repeat_noise, torch.float64, (N, rd.n_repeat - 1) + tuple(hu.shape))],
+                                 rng_seed, out, [(B, 1 if return_last else N + 1, R, R, self.in_channels)], torch.float64,
+                                 return_last, ws, self.repaint_workspace_bytes(B), (B,), hu.device)
 
 
 def normal_fill(out: torch.Tensor, rng_seed: torch.Tensor, draw: int) -> torch.Tensor:
@@ -953,7 +863,40 @@ def _copy_static(who: str, pairs) -> None:
             dst.copy_(src)
 
 
-class GraphedSampler:
+class _GraphedCall:
+    """What the Graphed* classes share: one sampler call captured ONCE into a HIP graph and replayed.  A subclass makes its
+    static buffers (plain attributes), names the ones a replay copies into and defines ``_run``, the eager plan method on
+    exactly those buffers; ``_capture_call`` pins the workspace and captures, ``_replay`` is every ``__call__``."""
+
+    @staticmethod
+    def _draws(dev, random: bool, device_noise: bool, shape: tuple, dtype):
+        """(seed, noise) of a sampler that draws per step (``random``): the int64 device scalar that keys device-side draws
+        (rewritten before each replay), or the static buffer materialised draws are copied into; (None, None) when it does not."""
+        if not random:
+            return None, None
+        if device_noise:
+            return torch.zeros(1, dtype=torch.int64, device=dev), None
+        return None, torch.zeros(shape, dtype=dtype, device=dev)
+
+    def _capture_call(self, dev, static: Dict[str, Optional[torch.Tensor]], ws: Optional[Workspace], nbytes: int) -> None:
+        """static: the static input tensors under the names of ``__call__``'s arguments, in their order (None: not part of this
+        capture).  ``self.seed`` and ``self.out`` are set by now."""
+        self._static = static
+        self.ws = _PinnedWorkspace(ws, nbytes, dev)
+        self.graph = _capture(self._run, dev)
+
+    def _replay(self, seed, *inputs):
+        who = type(self).__name__
+        if (self.seed is None) != (seed is None):
+            raise RuntimeError(f"{who}: 'seed' goes with device_noise=True instances of a sampler that draws (and only with them)")
+        if seed is not None:
+            _write_seed(self.seed, seed)
+        _copy_static(who, [(dst, src, name) for (name, dst), src in zip(self._static.items(), inputs)])
+        self.graph.replay()
+        return self.out
+
+
+class GraphedSampler(_GraphedCall):
     """The whole Heun sampling call (every U-Net evaluation and state update of mcedm_heun_sample: ~4000 launches at
     18 steps) captured ONCE into a HIP graph and replayed.  The library never allocates or synchronises and the sigma
     schedule is host-side arithmetic baked into kernel arguments, so a replay is exact; inputs are copied into static
@@ -968,18 +911,15 @@ class GraphedSampler:
         device scalar the call rewrites before each replay) -- no [N, B, C, H, W] float64 buffer, fresh noise per replay."""
         dev = packed.device
         self.plan, self.packed, self.sd, self.return_last = plan, packed, sd, return_last
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (churn and device_noise) else None
         self.guidance, self.dx_input = guidance, dx_input      # host-side descriptions, baked into the captured kernel arguments
         C = plan.in_channels
         self.cond = torch.zeros((B, plan.cond_channels, H, W), device=dev) if has_cond else None
         self.mask = torch.zeros((B, C, H, W), device=dev) if masked else None
         self.init = torch.zeros((B, C, H, W), device=dev)
-        self.step_noise = (torch.zeros((sd.timesteps, B, C, H, W), dtype=torch.float64, device=dev)
-                           if churn and not device_noise else None)
-        T = 1 if return_last else sd.timesteps + 1
-        self.out = torch.empty((B, T, H, W, C), dtype=torch.float64, device=dev)
-        self.ws = _PinnedWorkspace(ws, plan.sampler_workspace_bytes(B, H, W), dev)
-        self.graph = _capture(self._run, dev)
+        self.seed, self.step_noise = self._draws(dev, churn, device_noise, (sd.timesteps, B, C, H, W), torch.float64)
+        self.out = torch.empty((B, 1 if return_last else sd.timesteps + 1, H, W, C), dtype=torch.float64, device=dev)
+        self._capture_call(dev, {"cond": self.cond, "mask": self.mask, "init_noise": self.init, "step_noise": self.step_noise},
+                           ws, plan.sampler_workspace_bytes(B, H, W))
 
     def _run(self):
         self.plan.sample(self.packed, self.sd, self.cond, self.mask, self.init, self.step_noise, self.return_last, self.ws,
@@ -988,17 +928,10 @@ class GraphedSampler:
     def __call__(self, cond, mask, init_noise, step_noise=None, seed=None) -> torch.Tensor:
         """Returns the instance's static output tensor (overwritten by the next call).  seed (device-noise instances): python
         int or int64 tensor, the key of this call's churn draws."""
-        if (self.seed is None) != (seed is None):
-            raise RuntimeError("GraphedSampler: 'seed' goes with device_noise=True instances (and only with them)")
-        if seed is not None:
-            _write_seed(self.seed, seed)
-        _copy_static("GraphedSampler", ((self.cond, cond, "cond"), (self.mask, mask, "mask"), (self.init, init_noise, "init_noise"),
-                                        (self.step_noise, step_noise, "step_noise")))
-        self.graph.replay()
-        return self.out
+        return self._replay(seed, cond, mask, init_noise, step_noise)
 
 
-class GraphedRepaint:
+class GraphedRepaint(_GraphedCall):
     """mcedm_repaint_sample_rng captured once and replayed: the whole RePaint call (timesteps x n_repeat Heun updates:
     ~80 000 launches at BASELINE config 5) is one HIP graph.  The noise is generated on the device from the seed in
     ``self.seed``, which the host rewrites before each replay, so every replay draws fresh noise."""
@@ -1011,10 +944,8 @@ class GraphedRepaint:
         self.hu = torch.zeros((B, Cc, S, S), device=dev)
         self.init = torch.zeros((B, Cc, S, S), device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        T = 1 if return_last else rd.timesteps + 1
-        self.out = torch.empty((B, T, S, S, Cc), dtype=torch.float64, device=dev)
-        self.ws = _PinnedWorkspace(ws, plan.repaint_workspace_bytes(B), dev)
-        self.graph = _capture(self._run, dev)
+        self.out = torch.empty((B, 1 if return_last else rd.timesteps + 1, S, S, Cc), dtype=torch.float64, device=dev)
+        self._capture_call(dev, {"hu": self.hu, "init_noise": self.init}, ws, plan.repaint_workspace_bytes(B))
 
     def _run(self):
         self.plan.repaint_sample(self.packed, self.rd, self.hu, self.init, None, None, self.return_last, self.ws, out=self.out,
@@ -1022,14 +953,10 @@ class GraphedRepaint:
 
     def __call__(self, hu, init_noise, seed) -> torch.Tensor:
         """seed: python int or int64 tensor.  Returns the instance's static output tensor."""
-        self.hu.copy_(hu)
-        self.init.copy_(init_noise)
-        _write_seed(self.seed, seed)
-        self.graph.replay()
-        return self.out
+        return self._replay(seed, hu, init_noise)
 
 
-class GraphedCondDdim:
+class GraphedCondDdim(_GraphedCall):
     """mcedm_cond_ddim_sample captured once and replayed, like GraphedSampler: the schedule is host arithmetic baked into the
     kernel arguments, the inputs (cond, init_noise and, with eta != 0, the uniform draws of every step) are copied into static
     buffers first.  device_noise (with eta != 0): mcedm_cond_ddim_sample_rng instead -- the step kernel generates the draws from
@@ -1043,29 +970,21 @@ class GraphedCondDdim:
         Cc, S = plan.in_channels, len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
         self.cond = torch.zeros((B, dd.cond_channels, H, W), device=dev) if dd.cond_channels > 0 else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (stochastic and device_noise) else None
-        self.eta_noise = torch.zeros((S, B, Cc, H, W), device=dev) if (stochastic and not device_noise) else None
+        self.seed, self.eta_noise = self._draws(dev, stochastic, device_noise, (S, B, Cc, H, W), torch.float32)
         self.out = (torch.empty((B, 1 if return_last else S + 1, H, W, Cc), device=dev),
                     torch.empty((B, 1 if return_last else S, H, W, Cc), device=dev))
-        self.ws = _PinnedWorkspace(ws, plan.cond_ddim_workspace_bytes(B, H, W), dev)
-        self.graph = _capture(self._run, dev)
+        self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "eta_noise": self.eta_noise}, ws,
+                           plan.cond_ddim_workspace_bytes(B, H, W))
 
     def _run(self):
         self.plan.cond_ddim_sample(self.packed, self.dd, self.cond, self.init, self.eta_noise, self.return_last, self.ws, out=self.out,
                                    rng_seed=self.seed)
 
     def __call__(self, cond, init_noise, eta_noise=None, seed=None):
-        if (self.seed is None) != (seed is None):
-            raise RuntimeError("GraphedCondDdim: 'seed' goes with device_noise=True instances of a stochastic sampler (and only with them)")
-        if seed is not None:
-            _write_seed(self.seed, seed)
-        _copy_static("GraphedCondDdim", ((self.cond, cond, "cond"), (self.init, init_noise, "init_noise"),
-                                         (self.eta_noise, eta_noise, "eta_noise")))
-        self.graph.replay()
-        return self.out
+        return self._replay(seed, cond, init_noise, eta_noise)
 
 
-class GraphedDdimRepaint:
+class GraphedDdimRepaint(_GraphedCall):
     """mcedm_ddim_repaint_sample (device_noise False) or mcedm_ddim_repaint_sample_rng (True) captured once and replayed: every
     network pass and elementwise kernel of PlDdim.sample_with_repeat is one HIP graph.  With eta != 0 the uniform draws are either
     copied into a static [S, B, C, R, R] buffer or generated by the step kernel from ``self.seed``.  ``keep``: the host tables the
@@ -1079,29 +998,21 @@ class GraphedDdimRepaint:
         S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
         self.hu = torch.zeros((B, Cc, R, R), device=dev)
         self.init = torch.zeros((B, Cc, R, R), device=dev)
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (stochastic and device_noise) else None
-        self.eta_noise = torch.zeros((S, B, Cc, R, R), device=dev) if (stochastic and not device_noise) else None
+        self.seed, self.eta_noise = self._draws(dev, stochastic, device_noise, (S, B, Cc, R, R), torch.float32)
         self.out = (torch.empty((B, 1 if return_last else S + 1, R, R, Cc), device=dev),
                     torch.empty((B, 1 if return_last else S, R, R, Cc), device=dev))
-        self.ws = _PinnedWorkspace(ws, plan.ddim_workspace_bytes(B), dev)
-        self.graph = _capture(self._run, dev)
+        self._capture_call(dev, {"hu": self.hu, "init_noise": self.init, "eta_noise": self.eta_noise}, ws,
+                           plan.ddim_workspace_bytes(B))
 
     def _run(self):
         self.plan.ddim_repaint_sample(self.packed, self.dd, self.hu, self.init, self.eta_noise, self.return_last, self.ws,
                                       rng_seed=self.seed, out=self.out)
 
     def __call__(self, hu, init_noise, eta_noise=None, seed=None):
-        if (self.seed is None) != (seed is None):
-            raise RuntimeError("GraphedDdimRepaint: 'seed' goes with device_noise=True instances of a stochastic sampler (and only with them)")
-        if seed is not None:
-            _write_seed(self.seed, seed)
-        _copy_static("GraphedDdimRepaint", ((self.hu, hu, "hu"), (self.init, init_noise, "init_noise"),
-                                            (self.eta_noise, eta_noise, "eta_noise")))
-        self.graph.replay()
-        return self.out
+        return self._replay(seed, hu, init_noise, eta_noise)
 
 
-class GraphedVpSampler:
+class GraphedVpSampler(_GraphedCall):
     """mcedm_vp_heun_sample (device_noise False) or mcedm_vp_heun_sample_rng (True) captured once and replayed: the ~2 N network
     evaluations and state updates of PlCondDdim.sample_edm are one HIP graph.  churn: some step of ``vd`` has t_hat > t_cur; its
     normal draws are either copied into a static [N, B, C, H, W] float64 buffer or generated by the churn kernel from
@@ -1114,26 +1025,17 @@ class GraphedVpSampler:
         Cc = plan.in_channels
         self.cond = torch.zeros((B, vd.cond_channels, H, W), device=dev) if has_cond else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev) if (churn and device_noise) else None
-        self.step_noise = (torch.zeros((vd.timesteps, B, Cc, H, W), dtype=torch.float64, device=dev)
-                           if churn and not device_noise else None)
+        self.seed, self.step_noise = self._draws(dev, churn, device_noise, (vd.timesteps, B, Cc, H, W), torch.float64)
         self.out = torch.empty((B, 1 if return_last else vd.timesteps + 1, H, W, Cc), dtype=torch.float64, device=dev)
-        self.ws = _PinnedWorkspace(ws, plan.vp_sampler_workspace_bytes(B, H, W), dev)
-        self.graph = _capture(self._run, dev)
+        self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "step_noise": self.step_noise}, ws,
+                           plan.vp_sampler_workspace_bytes(B, H, W))
 
     def _run(self):
         self.plan.vp_sample(self.packed, self.vd, self.cond, self.init, self.step_noise, self.return_last, self.ws,
                             rng_seed=self.seed, out=self.out)
 
     def __call__(self, cond, init_noise, step_noise=None, seed=None) -> torch.Tensor:
-        if (self.seed is None) != (seed is None):
-            raise RuntimeError("GraphedVpSampler: 'seed' goes with device_noise=True instances of a churning sampler (and only with them)")
-        if seed is not None:
-            _write_seed(self.seed, seed)
-        _copy_static("GraphedVpSampler", ((self.cond, cond, "cond"), (self.init, init_noise, "init_noise"),
-                                          (self.step_noise, step_noise, "step_noise")))
-        self.graph.replay()
-        return self.out
+        return self._replay(seed, cond, init_noise, step_noise)
 
 
 def graphed_or_eager(cache: dict, key, build, eager, max_entries: int = 2):

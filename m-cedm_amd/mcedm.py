@@ -189,7 +189,7 @@ class PlMcedm(_PlBase):
             # the ~4000 launches of one sampling call replay from one HIP graph (lib.GraphedSampler, see _replay)
             B, _, H, W = hu_noise.shape
             key = (B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), hu_noise.device.index,
-                   tuple(getattr(sd, f) for f, _ in sd._fields_))
+                   _lib.desc_key(sd))
             return self._replay(key, lambda: _lib.GraphedSampler(
                 net.plan, packed, sd, B, H, W, masked=True, has_cond=True, churn=churn, return_last=return_last,
                 ws=self._sample_ws, device_noise=dev_noise), eager, cond, hu_mask, hu_noise, step_noise, **kw)

@@ -149,3 +149,44 @@ def test_single_task_modules_read_the_noise_source_from_the_environment(monkeypa
     assert PlCondEdm(cond_hparams()).noise_source == PlCondDdim(ddim_hparams()).noise_source == "device"
     monkeypatch.setenv("MCEDM_NOISE_SOURCE", "torch")
     assert PlCondEdm(cond_hparams()).noise_source == PlCondDdim(ddim_hparams()).noise_source == "torch"
+
+
+def test_every_sampler_stem_has_an_rng_twin_in_header_library_and_binding():
+    """lib.SAMPLER_STEMS is what _PlanBase._sample_call dispatches on: each stem and its `_rng` twin is exported, declared and
+    bound, and the twin takes ONE seed pointer where the stem takes its materialised-noise pointers."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mcedm_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(mcedm_[a-z0-9_]+)\s*\(", src))
+    lib = L.load()
+    for stem, n_noise in L.SAMPLER_STEMS.items():
+        for name in (stem, stem + "_rng"):
+            assert name in L.EXPORTS and name in declared, name
+            assert getattr(lib, name).argtypes, name
+        assert n_noise >= 1
+        assert len(getattr(lib, stem + "_rng").argtypes) == len(getattr(lib, stem).argtypes) - (n_noise - 1), stem
+    # and the table is complete: every exported `_rng` sampler entry is the twin of a row
+    assert {n[:-len("_rng")] for n in L.EXPORTS if n.endswith("_rng")} == set(L.SAMPLER_STEMS)
+
+
+def test_desc_key():
+    sp = orc.SamplerParams(timesteps=4, S_churn=15.0)
+    a, b = L.sampler_desc(sp), L.sampler_desc(sp)
+    assert L.desc_key(a) == L.desc_key(b) and hash(L.desc_key(a)) == hash(L.desc_key(b))
+    assert len(L.desc_key(a)) == len(L.SamplerDesc._fields_)
+    b.S_churn = 14.0
+    assert L.desc_key(a) != L.desc_key(b)
+    ae = alphas_ext()
+    d = L.cond_ddim_desc(sparams(timesteps=10, eta=0.5), ae, 1, True)
+    e = L.cond_ddim_desc(sparams(timesteps=10, eta=0.5), ae.clone(), 1, True)           # another table at another address
+    key = L.desc_key(d, skip=("alphas_cumprod_ext",))
+    assert key == L.desc_key(e, skip=("alphas_cumprod_ext",)) == (10, 0, 0.5, 0.0, 1, 1, 1000)
+    assert len(key) == len(L.CondDdimDesc._fields_) - 1 and not any(isinstance(v, C._Pointer) for v in key)
+    e.eta = 0.25
+    assert L.desc_key(e, skip=("alphas_cumprod_ext",)) != key
+    from oracle import ddpm_oracle as dorc
+    rp = dorc.RepaintParams(timesteps=4, n_repeat=2, S_churn=0.0, n_time_h=0, n_time_u=16)
+    from oracle import fixtures as fx
+    betas = dorc.betas_of(fx.CFG_D)
+    rd, keep = L.repaint_desc(rp, dorc.edm_steps_of(betas), dorc.alphas_ext_of(betas), 1, 1)
+    rkey = L.desc_key(rd, skip=("edm_steps", "alphas_cumprod_ext"))
+    assert len(rkey) == len(L.RepaintDesc._fields_) - 2 and not any(isinstance(v, C._Pointer) for v in rkey)
+    hash(rkey)
