@@ -675,8 +675,10 @@ int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packe
  * folded conv_in adds it before its GroupNorm statistics; without cond (zero features, so no b_enc2 either) conv_in adds the
  * vector Wx b_in + b_comb and no map is read.  A network
  * evaluation launches exactly what a plan without the head launches.  The parameter table gains cond_enc.0.*, cond_enc.2.*,
- * combine_enc.* behind conv_in.*, as Model.state_dict() orders them.  cat_cond != 0 (the conditioning concatenated to the
- * input of the DDPM U-Net) is not built: MCEDM_ERR_INVALID. */
+ * combine_enc.* behind conv_in.*, as Model.state_dict() orders them.
+ * cat_cond != 0 with cond_channels > 0 (configs/model/edm_cond_h_res32.yaml; models/ddim_blocks.py:259, 386-391): no head; conv_in
+ * reads cat(cond, x), its weight is [ch, cond_channels + in_channels, 3, 3] and the parameter table is that of a plan without
+ * conditioning.  It needs desc->self_cond == 0; with self_cond it is not built: MCEDM_ERR_INVALID. */
 typedef struct { int32_t cond_channels; int32_t cat_cond; } mcedm_ddpm_cond_desc;
 int mcedm_ddpm_plan_create_cond(const mcedm_ddpm_desc* desc, const mcedm_ddpm_cond_desc* cond, mcedm_ddpm_plan** out);
 /* map_out [B, ch, R, R] <- M(cond), cond [B, cond_channels, R, R]; the caller owns map_out. */
@@ -705,6 +707,35 @@ int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const void* packed,
 int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
                                     const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last,
                                     void* workspace, size_t workspace_bytes, int B, void* stream);
+
+/* ---- the single-task EDM model on a cat_cond plan (PlCondEdm on Model, models/ddim.py:1608-1773) ------------------------
+ * mcedm_ddpm_forward_cat: Model.forward(x, t, cond) with cond [B, cond_channels, R, R] concatenated in front of the state by
+ * conv_in's two source pointers (no copy, no extra launch); cond NULL = cond None, which reads as zeros (:387-390).  On a plan
+ * without cat_cond channels cond must be NULL and this is mcedm_ddpm_forward.
+ * mcedm_ddpm_edm_denoise: PlCondEdm.get_denoised (:1745-1763) at one noise level, fp32:
+ *   c_skip = sd^2 / (sigma^2 + sd^2), c_out = sigma sd / sqrt(sigma^2 + sd^2), c_in = 1 / sqrt(sd^2 + sigma^2),
+ *   F = net(c_in x, c_noise, cond) -- c_in scales the state only, cond enters unscaled -- and, for |w| >= 1e-3 with cond given,
+ *   F = (1 + w) F - w net(c_in x, c_noise, None);  D = c_skip x + c_out F.
+ * c_noise is the caller's fp32 ln(sigma) / 4.  F_out (optional) receives the blended F. */
+int mcedm_ddpm_forward_cat(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float t, float* out,
+                           void* workspace, size_t workspace_bytes, int B, void* stream);
+int mcedm_ddpm_edm_denoise(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float sigma,
+                           float c_noise, double w, double sigma_data, float* D_out, float* F_out, void* workspace,
+                           size_t workspace_bytes, int B, void* stream);
+/* PlCondDdim.sample_edm as PlCondEdm inherits it (:1532-1601) around mcedm_ddpm_edm_denoise: the description is
+ * mcedm_vp_heun_sample's (t_steps, t_hat -- round_sigma is the identity here -- and c_noise = ln(sigma) / 4 at t_hat and at t_next,
+ * all from the host; cond_channels = the plan's with cond, 0 with cond NULL), the contracts too (fp64 state, materialised or
+ * device-generated churn draws, _rng bit-equal to the tensor-fed form on mcedm_normal_fill's draws, one capturable call).
+ * gd (optional): PDE guidance, after every denoiser call dx = get_dx_log_prob(h, D) with h = cond[:, 0] and
+ * d -= gd->weight * dx / t_hat in both stages (:1576-1578, 1589-1590); it needs in_channels == 1 and cond. */
+int mcedm_ddpm_edm_sampler_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes);
+int mcedm_ddpm_edm_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, double sigma_data,
+                               const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const double* step_noise,
+                               double* out, int return_last, void* workspace, size_t workspace_bytes, int B, void* stream);
+int mcedm_ddpm_edm_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                   double sigma_data, const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                   const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes,
+                                   int B, void* stream);
 
 /* ---- PDE residuals (forward) ----------------------------------------------
  * Replace the tensor-op bodies of models/pde_loss.py; results are bit-identical to the PyTorch CPU path.

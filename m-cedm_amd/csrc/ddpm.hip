@@ -16,6 +16,8 @@
 //   * the conditioning head of the single-task model (cond_enc / combine_enc, ddim_blocks.py:279-306, 401-421) is folded into
 //     conv_in at pack time (combine_enc is linear); what depends on cond is one map M [B, ch, R, R], computed by
 //     ddpm_cond_map_kernel once per sampler call and added by conv_in as its residual, in front of the fused statistics.
+//   * cat_cond (ddim_blocks.py:259, 386-391; configs/model/edm_cond_h_res32.yaml): conv_in reads cat(cond, x) through its two
+//     source pointers, cond first; a null cond source reads as zeros (cond None).  No head, no map, no extra launch.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -69,7 +71,8 @@ struct mcedm_ddpm_plan {
   size_t freqs = mcedm::NONE, w0 = mcedm::NONE, b0 = mcedm::NONE, w1 = mcedm::NONE, b1 = mcedm::NONE;
   size_t tproj_w = mcedm::NONE, tproj_b = mcedm::NONE, c1bias = mcedm::NONE;
   size_t packed_floats = 0;
-  int in_total = 0;          // conv_in input channels (self-conditioning channels first)
+  int in_total = 0;          // conv_in input channels (self-conditioning or cat_cond channels first)
+  int cat_channels = 0;      // cat_cond: the conditioning channels conv_in reads in front of the state (no head then)
   // the cond_enc / combine_enc head (mcedm_ddpm_plan_create_cond; cond_channels 0 = none).  Packed: cond_enc.0 as it is, the
   // folded 3x3 of the map as [tap][cin][cout], the map's bias, and the folded conv_in weight in parameter layout (the
   // source launch_pack_conv reads; conv_in.wpk / conv_in.bias hold the folded forms, the bias that of cond = None)
@@ -135,7 +138,8 @@ static void dplace(Taker& t, DAttn& a) {
 
 using namespace mcedm;
 
-static int ddpm_plan_build(const mcedm_ddpm_desc* d, int cond_channels, mcedm_ddpm_plan** out) {
+// cond_channels: of the cond_enc head; cat_channels: of a cat_cond input (at most one of the two is non-zero)
+static int ddpm_plan_build(const mcedm_ddpm_desc* d, int cond_channels, int cat_channels, mcedm_ddpm_plan** out) {
   MCEDM_REQUIRE(d && out, "ddpm_plan_create: null argument");
   MCEDM_REQUIRE(d->n_levels >= 1 && d->n_levels <= MCEDM_MAX_LEVELS, "ddpm_plan_create: n_levels=%d out of range", d->n_levels);
   MCEDM_REQUIRE(d->n_attn_resolutions >= 0 && d->n_attn_resolutions <= MCEDM_MAX_LEVELS, "ddpm_plan_create: bad n_attn_resolutions");
@@ -147,7 +151,8 @@ static int ddpm_plan_build(const mcedm_ddpm_desc* d, int cond_channels, mcedm_dd
   mcedm_ddpm_plan& P = *Pp;
   P.desc = *d;
   const int ch = d->ch, temb = 4 * ch, L = d->n_levels;
-  P.in_total = d->in_channels * (d->self_cond ? 2 : 1);
+  P.cat_channels = cat_channels;
+  P.in_total = cat_channels + d->in_channels * (d->self_cond ? 2 : 1);      // cat(cond, cat(x_self_cond, x)), ddim_blocks.py:258-259
   // registration order of Model.__init__ (ddim_blocks.py:252-362)
   P.d0w = add_param(P.params, "temb.dense.0.weight", {temb, ch}); P.d0b = add_param(P.params, "temb.dense.0.bias", {temb});
   P.d1w = add_param(P.params, "temb.dense.1.weight", {temb, temb}); P.d1b = add_param(P.params, "temb.dense.1.bias", {temb});
@@ -257,16 +262,20 @@ static int ddpm_plan_build(const mcedm_ddpm_desc* d, int cond_channels, mcedm_dd
   return MCEDM_OK;
 }
 
-extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan** out) { return ddpm_plan_build(d, 0, out); }
+extern "C" int mcedm_ddpm_plan_create(const mcedm_ddpm_desc* d, mcedm_ddpm_plan** out) { return ddpm_plan_build(d, 0, 0, out); }
 
 extern "C" int mcedm_ddpm_plan_create_cond(const mcedm_ddpm_desc* d, const mcedm_ddpm_cond_desc* cd, mcedm_ddpm_plan** out) {
   MCEDM_REQUIRE(d && cd && out, "ddpm_plan_create_cond: null argument");
   MCEDM_REQUIRE(cd->cond_channels >= 0 && cd->cond_channels <= 64, "ddpm_plan_create_cond: cond_channels=%d outside [0, 64]", cd->cond_channels);
-  MCEDM_REQUIRE(!(cd->cat_cond && cd->cond_channels > 0),
+  const bool cat = cd->cat_cond && cd->cond_channels > 0;
+  MCEDM_REQUIRE(!(cat && d->self_cond),
                 "ddpm_plan_create_cond: cat_cond (the conditioning concatenated to the input of the DDPM U-Net, ddim_blocks.py:259, "
-                "386-391) is not built; only the cond_enc head (cat_cond 0) is");
+                "386-391) together with self_cond is not built; cat_cond needs self_cond 0");
+  MCEDM_REQUIRE(!cat || cd->cond_channels + d->in_channels <= 64, "ddpm_plan_create_cond: cat_cond input of %d + %d channels (at most 64)",
+                cd->cond_channels, d->in_channels);
+  if (cat) return ddpm_plan_build(d, 0, cd->cond_channels, out);
   MCEDM_REQUIRE(cd->cond_channels == 0 || d->ch <= 512, "ddpm_plan_create_cond: ch=%d > 512 (the map kernel holds ch / 128 tiles per wave)", d->ch);
-  return ddpm_plan_build(d, cd->cond_channels, out);
+  return ddpm_plan_build(d, cd->cond_channels, 0, out);
 }
 
 extern "C" int mcedm_ddpm_plan_set_variant(mcedm_ddpm_plan* plan, int which, int value) {
@@ -684,7 +693,7 @@ static int attn_block(DExec& E, const DAttn& a, int x, int* out_id) {
 }
 
 // header in front of the activations
-struct DHeader { size_t bias, coef_in, F, total; };
+struct DHeader { size_t bias, coef_in, F, Fu, total; };      // Fu: the guidance pass of a cat_cond plan (NONE otherwise)
 static DHeader dheader(const mcedm_ddpm_plan& P, int B, int H, int W) {
   DHeader h;
   size_t cur = 0;
@@ -692,15 +701,17 @@ static DHeader dheader(const mcedm_ddpm_plan& P, int B, int H, int W) {
   h.bias = take((size_t)P.rows * sizeof(float));
   h.coef_in = take((size_t)P.in_total * sizeof(Coef));
   h.F = take((size_t)B * P.desc.out_channels * H * W * sizeof(float));
+  h.Fu = P.cat_channels > 0 ? take((size_t)B * P.desc.out_channels * H * W * sizeof(float)) : NONE;
   h.total = cur;
   return h;
 }
 
-// Model.forward (ddim_blocks.py:410-470) with dx None; cond enters as cond_map (null: None); x is scaled by the rows of coef_in
-// (null = identity) while conv_in stages it.  `act` = start of the activation region.  Returns the peak bytes in *peak.
+// Model.forward (ddim_blocks.py:410-470) with dx None; cond enters as cond_map (null: None) on a plan with the head, as cond_cat
+// [B, cat_channels, R, R] (null: None, zeros) on a cat_cond plan; the input is scaled by the rows of coef_in (null = identity)
+// while conv_in stages it.  `act` = start of the activation region.  Returns the peak bytes in *peak.
 static int ddpm_forward(const mcedm_ddpm_plan& P, bool dry, const float* pk, const float* x, const Coef* coef_in, float t,
                         float* bias_table, float* out, char* act, int B, hipStream_t s, size_t* peak,
-                        const float* x_self_cond = nullptr, const float* cond_map = nullptr) {
+                        const float* x_self_cond = nullptr, const float* cond_map = nullptr, const float* cond_cat = nullptr) {
   const mcedm_ddpm_desc& d = P.desc;
   const int R = d.resolution, L = d.n_levels;
   int rc;
@@ -713,13 +724,15 @@ static int ddpm_forward(const mcedm_ddpm_plan& P, bool dry, const float* pk, con
   }
   DExec E{P, dry, act, pk, s, B, Pool(), {}};
   E.t.reserve(4096);        // ConvArgs::gsum_tiles points into this vector during a launch
-  // conv_in on cat(x_self_cond = zeros, x): the self-conditioning half is a null source (reads as zeros)
+  // conv_in on cat(x_self_cond = zeros, x): the self-conditioning half is a null source (reads as zeros); on a cat_cond plan
+  // (no self-conditioning there) the first source is the conditioning instead, cat(cond, x)
   const int n_self = P.in_total - d.in_channels;
+  const float* front = P.cat_channels > 0 ? cond_cat : x_self_cond;
   std::vector<int> hs;
   {
     const int h0 = E.act(d.ch, R, R, true);
     ConvArgs ci{};
-    ci.xa = x_self_cond; ci.Ca = n_self; ci.xb = x; ci.Cb = d.in_channels;       // a null self-conditioning source reads as zeros
+    ci.xa = front; ci.Ca = n_self; ci.xb = x; ci.Cb = d.in_channels;             // a null first source reads as zeros
     if (n_self == 0) { ci.xa = x; ci.Ca = d.in_channels; ci.xb = nullptr; ci.Cb = 0; }
     ci.coef = coef_in; ci.coef_batch = 0; ci.act = 0;
     ci.Hs = R; ci.Ws = R; ci.H = R; ci.W = R;
@@ -1343,4 +1356,140 @@ extern "C" int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, cons
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return dcond_ddim_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace, workspace_bytes,
                          B, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// the single-task EDM model (PlCondEdm on Model, configs/model/edm_cond_h_res32.yaml): cat_cond input, EDM preconditioning
+// (models/ddim.py:1745-1763) and the Heun sampler (:1532-1601) with optional PDE guidance
+// ------------------------------------------------------------------------------------------
+namespace mcedm {
+// cond goes with a cat_cond plan (NULL: cond None, zeros)
+static int cat_check(const char* who, const mcedm_ddpm_plan& P, const float* cond, int B) {
+  MCEDM_REQUIRE(B > 0, "%s: empty batch", who);
+  MCEDM_REQUIRE(!cond || P.cat_channels > 0, "%s: cond given to a plan built without cat_cond channels (mcedm_ddpm_plan_create_cond)", who);
+  return MCEDM_OK;
+}
+
+// get_denoised (:1745-1763) at one noise level, fp32 like the reference: c_in scales the state rows of conv_in only (cond is
+// concatenated unscaled), F = (1 + w) F(cond) - w F(None) for |w| >= 1e-3 with cond given, D = c_skip x + c_out F
+static int dedm_denoise_impl(const mcedm_ddpm_plan& P, const DHeader& hd, const float* pk, const float* x, const float* cond,
+                             float sigma, float c_noise, double w, float sigma_data, float* D_out, float* F_out, void* ws, int B,
+                             hipStream_t s) {
+  int rc;
+  const float sd2 = sigma_data * sigma_data, s2 = sigma * sigma;
+  const float c_skip = sd2 / (s2 + sd2);
+  const float c_out = sigma * sigma_data / sqrtf(s2 + sd2);
+  const float c_in = 1.0f / sqrtf(sd2 + s2);
+  Coef* coef_in = at<Coef>(ws, hd.coef_in);
+  if ((rc = launch_vp_coef(c_in, P.in_total - P.desc.in_channels, P.desc.in_channels, coef_in, s))) return rc;
+  float* F = at<float>(ws, hd.F);
+  float* bias = at<float>(ws, hd.bias);
+  char* act = at<char>(ws, hd.total);
+  if ((rc = ddpm_forward(P, false, pk, x, coef_in, c_noise, bias, F, act, B, s, nullptr, nullptr, nullptr, cond))) return rc;
+  float* Fu = nullptr;
+  if (std::fabs(w) >= 0.001 && cond != nullptr) {
+    Fu = at<float>(ws, hd.Fu);
+    if ((rc = ddpm_forward(P, false, pk, x, coef_in, c_noise, bias, Fu, act, B, s, nullptr, nullptr, nullptr, nullptr))) return rc;
+  }
+  return launch_edm_cfg_finish(x, F, Fu, w, c_skip, c_out, state_floats(P, B), D_out, F_out, s);
+}
+
+struct DEdmBufs : HeunBufs { size_t dx, g; };
+static DEdmBufs dedm_bufs(const mcedm_ddpm_plan& P, int B) {
+  DEdmBufs v{heun_bufs(state_floats(P, B)), 0, 0};
+  v.dx = heun_take(v, state_floats(P, B) * 4); v.g = heun_take(v, state_floats(P, B) * 4);      // PDE guidance: gradient, Darcy scratch
+  return v;
+}
+
+static int dedm_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, double sigma_data,
+                            const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const double* step_noise,
+                            const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes, int B,
+                            void* stream) {
+  MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "ddpm_edm_heun_sample: null argument");
+  MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "ddpm_edm_heun_sample: null schedule array");
+  const mcedm_ddpm_plan& P = *plan;
+  int rc;
+  MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "ddpm_edm_heun_sample: in_channels != out_channels");
+  if ((rc = cat_check("ddpm_edm_heun_sample", P, cond, B))) return rc;
+  MCEDM_REQUIRE(sp->cond_channels == (cond ? P.cat_channels : 0), "ddpm_edm_heun_sample: cond_channels %d, expected %d (the plan's with cond, 0 without)",
+                sp->cond_channels, cond ? P.cat_channels : 0);
+  MCEDM_REQUIRE(sigma_data > 0.0, "ddpm_edm_heun_sample: sigma_data %g <= 0", sigma_data);
+  MCEDM_REQUIRE(gd == nullptr || gd->system == 1 || gd->system == 2, "ddpm_edm_heun_sample: guidance system must be 1 (SWE) or 2 (Darcy)");
+  MCEDM_REQUIRE(gd == nullptr || (P.desc.in_channels == 1 && cond != nullptr),
+                "ddpm_edm_heun_sample: PDE guidance is defined for the single-task sampler (state u, conditioning h in cond[:, 0]), "
+                "models/ddim.py:1532-1601");
+  if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
+  DHeader hd; size_t act = 0;
+  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
+  const DEdmBufs eb = dedm_bufs(P, B);
+  if ((rc = heun_check_workspace("ddpm_edm_heun_sample", workspace_bytes, eb.total + hd.total + act))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float* pk = (const float*)packed;
+  const int R = P.desc.resolution;
+  HeunState h = heun_state(workspace, eb, B, P.desc.in_channels, (size_t)R * R, sp->timesteps, return_last, out, s);
+  void* uws = at<char>(workspace, eb.total);
+  float* dxg = gd ? at<float>(workspace, eb.dx) : nullptr;
+  float* gscratch = at<float>(workspace, eb.g);
+  const float sd = (float)sigma_data;
+  // x_self_cond is None in every evaluation (no self-conditioning on a cat_cond plan); guidance: dx = get_dx_log_prob(h, D) after
+  // each denoiser call (:1576, 1589)
+  return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma_d, float c_noise) -> int {
+    int e = dedm_denoise_impl(P, hd, pk, h.x32, cond, (float)sigma_d, c_noise, sp->w, sd, h.D, nullptr, uws, B, s);      // t.to(torch.float32)
+    if (e || !gd) return e;
+    return guidance_dx(P.cat_channels, *gd, cond, h.D, dxg, gscratch, B, R, R, s);
+  }, dxg, gd ? (float)gd->weight : 0.f);
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_ddpm_forward_cat(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float t,
+                                      float* out, void* workspace, size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_cat: null argument");
+  int rc;
+  if ((rc = cat_check("ddpm_forward_cat", *plan, cond, B))) return rc;
+  DHeader hd; size_t act = 0;
+  if ((rc = ddpm_sizes(*plan, B, &hd, &act))) return rc;
+  if ((rc = heun_check_workspace("ddpm_forward_cat", workspace_bytes, hd.total + act))) return rc;
+  return ddpm_forward(*plan, false, (const float*)packed, x, nullptr, t, at<float>(workspace, hd.bias), out,
+                      at<char>(workspace, hd.total), B, (hipStream_t)stream, nullptr, nullptr, nullptr, cond);
+}
+
+extern "C" int mcedm_ddpm_edm_denoise(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float sigma,
+                                      float c_noise, double w, double sigma_data, float* D_out, float* F_out, void* workspace,
+                                      size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && x && D_out && workspace, "ddpm_edm_denoise: null argument");
+  MCEDM_REQUIRE(sigma > 0.f && sigma_data > 0.0, "ddpm_edm_denoise: sigma %g and sigma_data %g must be positive", (double)sigma, sigma_data);
+  int rc;
+  if ((rc = cat_check("ddpm_edm_denoise", *plan, cond, B))) return rc;
+  DHeader hd; size_t act = 0;
+  if ((rc = ddpm_sizes(*plan, B, &hd, &act))) return rc;
+  if ((rc = heun_check_workspace("ddpm_edm_denoise", workspace_bytes, hd.total + act))) return rc;
+  return dedm_denoise_impl(*plan, hd, (const float*)packed, x, cond, sigma, c_noise, w, (float)sigma_data, D_out, F_out, workspace, B,
+                           (hipStream_t)stream);
+}
+
+extern "C" int mcedm_ddpm_edm_sampler_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "ddpm_edm_sampler_workspace_bytes: null argument");
+  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
+  if (rc == MCEDM_OK) *bytes += dedm_bufs(*plan, B).total;
+  return rc;
+}
+extern "C" int mcedm_ddpm_edm_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                          double sigma_data, const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                          const double* step_noise, double* out, int return_last, void* workspace,
+                                          size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return dedm_sample_impl(plan, packed, sp, sigma_data, gd, cond, init_noise, step_noise, nullptr, out, return_last, workspace,
+                          workspace_bytes, B, stream);
+}
+extern "C" int mcedm_ddpm_edm_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                              double sigma_data, const mcedm_guidance_desc* gd, const float* cond,
+                                              const float* init_noise, const uint64_t* rng_seed, double* out, int return_last,
+                                              void* workspace, size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_edm_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
+  return dedm_sample_impl(plan, packed, sp, sigma_data, gd, cond, init_noise, nullptr, rng_seed, out, return_last, workspace,
+                          workspace_bytes, B, stream);
 }

@@ -333,6 +333,26 @@ int launch_vp_cfg_finish(const float* x, const float* F, const float* Fu, double
   return MCEDM_OK;
 }
 
+// EDM preconditioning around the DDPM U-Net (PlCondEdm.get_denoised, models/ddim.py:1745-1763) at one noise level:
+// F = (w + 1) * F - w * F_uncond when Fu != NULL, D = c_skip * x + c_out * F; the blended F also to F_out when given
+__global__ void edm_cfg_finish_kernel(const float* __restrict__ x, const float* __restrict__ F, const float* __restrict__ Fu,
+                                      float w1, float w, float c_skip, float c_out, size_t total, float* __restrict__ D,
+                                      float* __restrict__ F_out) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    float f = F[i];
+    if (Fu) f = w1 * f - w * Fu[i];
+    if (F_out) F_out[i] = f;
+    D[i] = c_skip * x[i] + c_out * f;
+  }
+}
+int launch_edm_cfg_finish(const float* x, const float* F, const float* Fu, double w, float c_skip, float c_out, size_t total,
+                          float* D, float* F_out, hipStream_t s) {
+  hipLaunchKernelGGL(edm_cfg_finish_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, F, Fu, (float)(w + 1.0), (float)w, c_skip,
+                     c_out, total, D, F_out);
+  MCEDM_LAUNCH_CHECK("edm_cfg_finish_kernel");
+  return MCEDM_OK;
+}
+
 __global__ void repaint_init_kernel(const float* __restrict__ hu, const float* __restrict__ noise,
                                     const float* __restrict__ mask, float sa, float sb, double t0, size_t total,
                                     double* __restrict__ x, float* __restrict__ x32) {

@@ -59,6 +59,10 @@ int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* 
 // D = x + (-sigma) * F with F = (w + 1) F - w Fu when Fu != NULL                  (get_denoised, ddim.py:940-945)
 int launch_vp_cfg_finish(const float* x, const float* F, const float* Fu, double w, float sigma, size_t total, float* D,
                          hipStream_t s);
+// ---- EDM sampler of the DDPM U-Net (PlCondEdm on Model, models/ddim.py:1745-1763)
+// D = c_skip * x + c_out * F with F = (w + 1) F - w Fu when Fu != NULL; F_out (optional, not F itself) <- the blended F
+int launch_edm_cfg_finish(const float* x, const float* F, const float* Fu, double w, float c_skip, float c_out, size_t total,
+                          float* D, float* F_out, hipStream_t s);
 // x0 = ((hu*sa + nz*sb)*m + nz*(1-m)) [fp32] -> fp64, times t0        (ddim.py:989-994), m = 1 marks KNOWN entries
 int launch_repaint_init(const float* hu, const float* noise, const float* mask, float sa, float sb, double t0, size_t total,
                         double* x, float* x32, hipStream_t s);

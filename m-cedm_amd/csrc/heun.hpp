@@ -1,4 +1,4 @@
-// heun.hpp -- what the three Heun samplers share (EDM and VP on the ADM U-Net: sampler.hip; RePaint and VP on the DDPM
+// heun.hpp -- what the Heun samplers share (EDM and VP on the ADM U-Net: sampler.hip; RePaint, VP and EDM on the DDPM
 // U-Net: ddpm.hip): the five state buffers in front of the network's workspace, the trajectory stores, the churn and the
 // 2nd-order update.  Each sampler keeps its own schedule arithmetic (fp64, on the host), decides itself whether a step
 // churns, and passes its network in as a callable.  The VP Heun loop and the conditional DDIM loop, which run on either
@@ -84,6 +84,26 @@ static inline int heun_update(HeunState& h, int i, double t_hat, double t_next, 
   return MCEDM_OK;
 }
 
+// dx = get_dx_log_prob(h, denoised, guide_dx) of the single-task models (models/ddim.py:641-650 -> get_dx_pde :1424-1450):
+// the residual of x_unnorm = (h from the conditioning, u = the denoised state), differentiated w.r.t. x_unnorm, then the
+// MEAN over the two field gradients (calc_prob=True) -> [B, 1, H, W].  cond [B, cond_channels, H, W] of either network: its
+// first plane is h.
+// (the same call on the current noisy state instead of D is get_dx_input(h, x) with dx_norm == 'prob', ddim.py:601-613)
+static inline int guidance_dx(int cond_channels, const mcedm_guidance_desc& g, const float* cond, const float* D, float* dx,
+                              float* scratch, int B, int H, int W, hipStream_t s) {
+  GuideIO io{};
+  const long hw = (long)H * W;
+  io.in[0] = cond; io.in[1] = D; io.gt[0] = cond; io.gt[1] = D;
+  io.in_sb[0] = (long)cond_channels * hw; io.in_sb[1] = hw; io.st = W; io.sx = 1;
+  io.out[0] = dx; io.out[1] = nullptr; io.out_sb[0] = hw; io.out_sb[1] = 0; io.out_st = W; io.out_sx = 1;
+  io.sub[0] = g.sub_h; io.sub[1] = g.sub_u; io.div[0] = g.div_h; io.div[1] = g.div_u;
+  io.mean = 1;
+  if (g.system == 1)      // SweFvLoss: half_dt = 0.5 * Tn / n_times, dx = x[1] - x[0] of gen_x, both formed by the caller in fp32
+    return launch_swe_guidance(io, B, H, W, g.half_dt, g.dx, g.div_h * g.div_h, g.div_u * g.div_u, s);
+  MCEDM_REQUIRE(H == W && H > 4, "guidance: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)", H, W);
+  return launch_darcy_guidance(io, scratch, B, H, g.two_dx, /*calc_prob=*/1, s);
+}
+
 // ------------------------------------------------------------------------------------------
 // PlCondDdim.sample_edm (models/ddim.py:1532-1601) on either network
 // ------------------------------------------------------------------------------------------
@@ -99,10 +119,12 @@ static inline int vp_check_schedule(const mcedm_vp_sampler_desc* sp, const doubl
   return MCEDM_OK;
 }
 
-// denoise(sigma, c_noise) leaves D(h.x32; sigma) in h.D: get_denoised (:915-947) of the caller's network
+// denoise(sigma, c_noise) leaves D(h.x32; sigma) in h.D: get_denoised (:915-947, PlCondEdm's :1745-1763) of the caller's
+// network.  dxg / wgt: the PDE-guidance term, d -= wgt * dxg / t_hat in both stages (:1576-1578, 1589-1590); the callable
+// leaves get_dx_log_prob(h, D) in dxg after every evaluation.
 template <class Denoise>
 static inline int vp_heun_loop(HeunState& h, const mcedm_vp_sampler_desc* sp, const float* init_noise, const double* step_noise,
-                               const uint64_t* rng_seed, Denoise&& denoise) {
+                               const uint64_t* rng_seed, Denoise&& denoise, const float* dxg = nullptr, float wgt = 0.f) {
   int rc;
   const int N = sp->timesteps;
   const double* t = sp->t_steps;
@@ -118,7 +140,7 @@ static inline int vp_heun_loop(HeunState& h, const mcedm_vp_sampler_desc* sp, co
     }
     // Euler step (:1570-1580) at c_noise[2 i], 2nd-order correction (:1583-1593) at c_noise[2 i + 1]
     auto at_level = [&](double sigma, bool second) { return denoise(sigma, sp->c_noise[2 * i + (second ? 1 : 0)]); };
-    if ((rc = heun_update(h, i, t_hat, t_next, nullptr, at_level))) return rc;
+    if ((rc = heun_update(h, i, t_hat, t_next, nullptr, at_level, dxg, wgt, dxg ? (float)t_hat : 1.f))) return rc;
     if ((rc = heun_store_step(h, i + 1))) return rc;
   }
   return heun_store_last(h);

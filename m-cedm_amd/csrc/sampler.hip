@@ -43,27 +43,6 @@ extern "C" int mcedm_sampler_workspace_bytes(const mcedm_plan* plan, int B, int 
   return rc;
 }
 
-namespace mcedm {
-// dx = get_dx_log_prob(h, denoised, guide_dx) of the single-task models (models/ddim.py:641-650 -> get_dx_pde :1424-1450):
-// the residual of x_unnorm = (h from the conditioning, u = the denoised state), differentiated w.r.t. x_unnorm, then the
-// MEAN over the two field gradients (calc_prob=True) -> [B, 1, H, W]
-// (the same call on the current noisy state instead of D is get_dx_input(h, x) with dx_norm == 'prob', ddim.py:601-613)
-static int guidance_dx(const mcedm_plan& P, const mcedm_guidance_desc& g, const float* cond, const float* D, float* dx,
-                       float* scratch, int B, int H, int W, hipStream_t s) {
-  GuideIO io{};
-  const long hw = (long)H * W;
-  io.in[0] = cond; io.in[1] = D; io.gt[0] = cond; io.gt[1] = D;
-  io.in_sb[0] = (long)P.desc.cond_channels * hw; io.in_sb[1] = hw; io.st = W; io.sx = 1;
-  io.out[0] = dx; io.out[1] = nullptr; io.out_sb[0] = hw; io.out_sb[1] = 0; io.out_st = W; io.out_sx = 1;
-  io.sub[0] = g.sub_h; io.sub[1] = g.sub_u; io.div[0] = g.div_h; io.div[1] = g.div_u;
-  io.mean = 1;
-  if (g.system == 1)      // SweFvLoss: half_dt = 0.5 * Tn / n_times, dx = x[1] - x[0] of gen_x, both formed by the caller in fp32
-    return launch_swe_guidance(io, B, H, W, g.half_dt, g.dx, g.div_h * g.div_h, g.div_u * g.div_u, s);
-  MCEDM_REQUIRE(H == W && H > 4, "guidance: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)", H, W);
-  return launch_darcy_guidance(io, scratch, B, H, g.two_dx, /*calc_prob=*/1, s);
-}
-}  // namespace mcedm
-
 // gd: PDE guidance on the denoised state; dxc: the residual whose gradient at the current state is the network's dx input;
 // rng_seed: the churn draws come from the device generator instead of step_noise
 static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
@@ -105,11 +84,11 @@ static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mc
   // D(x32; sigma), mcedm.py:611-618 / 621-628; dx_cond: dx_in = get_dx_input(h, x32) first (ddim.py:1571, 1584); guidance:
   // its gradient at D afterwards
   auto denoise = [&](double sigma, bool) -> int {
-    int e = dxc ? guidance_dx(P, *dxc, cond, h.x32, dxin, gscratch, B, H, W, s) : MCEDM_OK;
+    int e = dxc ? guidance_dx(P.desc.cond_channels, *dxc, cond, h.x32, dxin, gscratch, B, H, W, s) : MCEDM_OK;
     if (e) return e;
     e = denoise_impl(P, L, hd, pk, h.x32, dxin, nullptr, (float)sigma, 1, 1, cond, w, h.D, nullptr, uws, B, H, W, sd, s);
     if (e) return e;
-    return gd ? guidance_dx(P, *gd, cond, h.D, dxg, gscratch, B, H, W, s) : MCEDM_OK;
+    return gd ? guidance_dx(P.desc.cond_channels, *gd, cond, h.D, dxg, gscratch, B, H, W, s) : MCEDM_OK;
   };
 
   if ((rc = launch_heun_init(cond, P.desc.cond_channels, h.C, h.hw, mask, init_noise, t[0], h.total, h.x, h.x32, s))) return rc;

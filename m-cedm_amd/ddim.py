@@ -17,7 +17,11 @@ the loss and of the Heun sampler (``mask = NULL`` in the C ABI).  Constructor, a
 DDPM-schedule buffers ``betas`` / ``logvar`` that ``PlDdim.__init__`` registers, models/ddim.py:22-30) and method
 signatures follow the reference (incl. PDE guidance, ``dx_cond``, the ``node_type`` channel and the ``cond_p`` drop); DDIM
 sampling of ``PlCondEdm`` raises as in the reference (models/ddim.py:1739-1740), and so does ``self_cond`` for it (its sampler
-would feed ``denoised`` back).
+would feed ``denoised`` back).  With a ``name`` that does not start with ``adm`` (configs/model/edm_cond_h_res32.yaml: ``name:
+edm_cond_h``, ``cat_cond: True``, ``self_cond: False``) the network is the DDPM U-Net ``Model`` with the conditioning concatenated
+to its input, for EVALUATION: ``model_precond``, ``get_denoised``, ``sample_edm`` (with ``guide_dx``), ``validation_step`` and
+``test_step`` run on it (mcedm_ddpm_edm_denoise, mcedm_ddpm_edm_heun_sample[_rng]); ``training_step`` and ``forward`` raise, because
+``Model`` has no backward here, and so does ``dx_cond``.
 
 ``PlCondDdim`` (bottom of this file) for ``models/ddim.py:1053-1605``: the single-task conditional DDPM on the ADM U-Net with
 self-conditioning (which it runs) -- epsilon-prediction ``training_step``, the VP-preconditioned ``sample_edm`` and the DDIM
@@ -40,6 +44,31 @@ class _SingleTask(_PlBase):
     """What the single-task models (h given, u generated) share -- in the reference PlCondEdm inherits it from PlCondDdim
     (models/ddim.py:1053-1319): the conditioning input, the u-only inverse transform, the PDE residual of (h, u) and the
     evaluation loops around ``sample_edm``."""
+
+    def _adm_only(self, what):
+        if self._on_ddpm_unet:
+            raise NotImplementedError(f"{what} is not built on the DDPM U-Net (models/ddim.py:43-46, Model): it has no backward "
+                                      "here; only the ADM U-Net (hparams.name = 'adm*') trains")
+
+    def _edm_schedule(self, sparams, c_noise_of):
+        """The schedule of sample_edm in the reference's own expressions on the host (models/ddim.py:1543-1553, 1566-1567), rounded by
+        the module's round_sigma: (N, t_steps fp64 [N + 1], t_hat [N], c_noise [2 N]) with c_noise_of(sigma) the network's label at
+        t_hat and at t_next (0 behind the last step, which has no second evaluation)."""
+        smin = max(float(sparams.sigma_min), self.sigma_min)
+        smax = min(float(sparams.sigma_max), self.sigma_max)
+        N, rho = int(sparams.timesteps), float(sparams.rho)
+        idx = torch.arange(N, dtype=torch.float64)
+        t_steps = (smax ** (1 / rho) + idx / (N - 1) * (smin ** (1 / rho) - smax ** (1 / rho))) ** rho
+        t_steps = torch.cat([self.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
+        S_min, S_max = float(sparams.S_min), float(sparams.S_max)
+        t_hat, c_noise = [], []
+        for i in range(N):
+            t_cur = t_steps[i]
+            gamma = min(float(sparams.S_churn) / N, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
+            th = self.round_sigma(t_cur + gamma * t_cur)
+            t_hat.append(float(th))
+            c_noise += [c_noise_of(th), c_noise_of(t_steps[i + 1]) if i < N - 1 else 0.0]
+        return N, t_steps, t_hat, c_noise
 
     def inverse_data_transform_u(self, u):
         if self.rescaled:
@@ -219,12 +248,15 @@ class PlCondEdm(_SingleTask):
         if self.dx_cond and self.dx_norm != "prob":
             raise NotImplementedError(f"dx_cond with dx_norm={self.dx_norm!r}: PlCondEdm.get_dx_input raises in the reference for "
                                       "every dx_norm other than 'prob' (models/ddim.py:608-611, 1445-1448)")
-        if not str(hparams.name).startswith("adm"):
-            raise NotImplementedError("only the ADM/EDM U-Net (hparams.name = 'adm*') is on the hot path")
+        self._on_ddpm_unet = not str(hparams.name).startswith("adm")                    # models/ddim.py:43-46
+        if self._on_ddpm_unet and self.dx_cond:
+            raise NotImplementedError("dx_cond (models/ddim.py:33-35) is not built on the DDPM U-Net")
         # DDPM schedule buffers of PlDdim (kept for checkpoint compatibility; the EDM path never reads them)
         self._register_schedule(hparams)
         self.cond_p = _opt(m, "cond_p", 0.8)
-        self.model = DhariwalUNet(hparams)
+        if self._on_ddpm_unet:
+            from .ddim_blocks import Model
+        self.model = Model(hparams) if self._on_ddpm_unet else DhariwalUNet(hparams)
         self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
         if _opt(o, "pde_loss_lambda", 0.0):
             raise NotImplementedError("pde_loss_lambda != 0 is outside the hot path")
@@ -258,6 +290,15 @@ class PlCondEdm(_SingleTask):
     def get_loss_weight(self, sigma):
         return (sigma ** 2 + self.sigma_data ** 2) / (sigma * self.sigma_data) ** 2
 
+    def round_sigma(self, sigma, return_index=False):
+        """models/ddim.py:1765-1768: the EDM schedule is continuous, nothing is rounded."""
+        sigma = torch.as_tensor(sigma)
+        return 0 if return_index else sigma
+
+    def forward(self, x, sigma, noise, cond=None):
+        self._adm_only("forward (the noising pass of training)")
+        return super().forward(x, sigma, noise, cond)          # not defined for the ADM U-Net either: training_step is the entry
+
     # ---- HIP path -------------------------------------------------------------------------------------------
     def _dx_arg(self, net, dx):
         if dx is None:
@@ -266,10 +307,27 @@ class PlCondEdm(_SingleTask):
             raise NotImplementedError("dx given to a network built with dx_cond=False (the reference ignores it silently)")
         return dx.to(torch.float32).contiguous()
 
+    def _ddpm_denoise(self, net, xt, sigma, cond, dx, w):
+        """get_denoised / model_precond on the DDPM U-Net (mcedm_ddpm_edm_denoise): one noise level, c_noise = sigma.log() / 4 in
+        torch's fp32 like the reference (:1661, 1753); the conditioning is concatenated unscaled."""
+        if dx is not None:
+            raise NotImplementedError("dx_cond is not built on the DDPM U-Net")
+        sig = torch.as_tensor(sigma).detach().to("cpu", torch.float32).reshape(-1)
+        if sig.numel() != 1 and not bool((sig == sig[0]).all()):
+            raise NotImplementedError("one noise level for the whole batch (what sample_edm evaluates; per-sample levels need a "
+                                      "per-sample bias in every conv of the DDPM U-Net)")
+        c_noise = float((sig[:1].log() / 4)[0])
+        with torch.no_grad():
+            return net.plan.edm_denoise(net.packed_weights(), xt.to(torch.float32).contiguous(), float(sig[0]), c_noise,
+                                        cond=None if cond is None else cond.to(torch.float32).contiguous(),
+                                        w=0.0 if w is None else float(w), sigma_data=self.sigma_data, ws=net._ws, want_F=True)
+
     def model_precond(self, x_noise, sigma, cond=None, x_self_cond=None, dx=None):
         if x_self_cond is not None:
             raise NotImplementedError("x_self_cond is outside the hot path")
         net = self.model
+        if self._on_ddpm_unet:
+            return self._ddpm_denoise(net, x_noise, sigma, cond, dx, None)[0]
         with torch.no_grad():
             return net.plan.denoise(net.packed_weights(), x_noise.float().contiguous(),
                                     sigma.to(torch.float32).reshape(-1).contiguous(),
@@ -280,6 +338,8 @@ class PlCondEdm(_SingleTask):
         if x_self_cond is not None:
             raise NotImplementedError("x_self_cond is outside the hot path")
         net = self._net(model)
+        if self._on_ddpm_unet:
+            return self._ddpm_denoise(net, xt, t, cond, dx, w)
         xt = xt.to(torch.float32).contiguous()
         sigma = torch.as_tensor(t).to(torch.float32).reshape(-1).contiguous().to(xt.device)
         cond = None if cond is None else cond.float().contiguous()
@@ -294,6 +354,7 @@ class PlCondEdm(_SingleTask):
         return D, F
 
     def training_step(self, train_batch, batch_idx):
+        self._adm_only("training_step")
         h_unnorm, dx, dt, u_unnorm = train_batch
         self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
         x = self.data_transform(h_unnorm, u_unnorm)
@@ -357,6 +418,8 @@ class PlCondEdm(_SingleTask):
             # dx_cond: dx_in = get_dx_input(h, x) on the current noisy state before every denoiser call (:1571, :1584)
             dx_input = gdesc if self.dx_cond else None
         net = self._net(self.ema_model if self.ema_model is not None else self.model)
+        if self._on_ddpm_unet:
+            return self._ddpm_sample_edm(net, h, u_noise, sparams, return_last, guidance, noise_source)
         h, init = _nchw(h).float(), _nchw(u_noise).float()
         sd = _lib.sampler_desc(sparams, self.sigma_data, self.sigma_min, self.sigma_max)
         N, churn = sd.timesteps, self._churns(sd)
@@ -379,6 +442,35 @@ class PlCondEdm(_SingleTask):
                 net.plan, packed, sd, B, H, W, masked=False, has_cond=True, churn=churn, return_last=return_last,
                 ws=self._sample_ws, guidance=guidance, dx_input=dx_input, device_noise=dev_noise), eager, h, None, init,
                 step_noise, **kw)
+
+
+    def _ddpm_sample_edm(self, net, h, u_noise, sparams, return_last, guidance, noise_source):
+        """sample_edm on the DDPM U-Net: the schedule in the reference's own expressions on the host (:1543-1553, 1566-1567;
+        round_sigma is the identity: _edm_schedule), c_noise = ln(sigma) / 4 in torch's fp32 at t_hat and at t_next; the loop runs in
+        mcedm_ddpm_edm_heun_sample[_rng] and replays from one HIP graph."""
+        h, init = _nchw(h).float().contiguous(), _nchw(u_noise).float().contiguous()
+        N, t_steps, t_hat, c_noise = self._edm_schedule(
+            sparams, lambda t: float((t.to(torch.float32).reshape(1).log() / 4)[0]))      # (:1747-1753)
+        cond = h if net.cond_channels > 0 else None
+        vd = _lib.vp_sampler_desc(N, net.cond_channels if cond is not None else 0, t_steps.tolist(), t_hat, c_noise,
+                                  float(sparams.S_noise), float(sparams.w))
+        churn = any(th != float(t_steps[i]) for i, th in enumerate(t_hat))     # the steps whose x_hat adds noise (:1567)
+        dev_noise = churn and noise_source == "device"
+        step_noise = (torch.randn((N,) + tuple(init.shape), dtype=torch.float64, device=init.device)
+                      if churn and not dev_noise else None)
+        kw = dict(seed=self._draw_seed()) if dev_noise else {}
+        with torch.no_grad():
+            packed = net.packed_weights()
+            eager = lambda c, i, sn, seed=None: net.plan.edm_sample(      # noqa: E731
+                packed, vd, c, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device),
+                sigma_data=self.sigma_data, guidance=guidance)
+            B = init.shape[0]
+            key = ("ddpm_edm", B, bool(return_last), churn, dev_noise, packed.data_ptr(), init.device.index, N, vd.cond_channels,
+                   tuple(t_steps.tolist()), tuple(t_hat), tuple(c_noise), float(sparams.S_noise), float(sparams.w),
+                   float(self.sigma_data), None if guidance is None else _lib.desc_key(guidance))
+            return self._replay(key, lambda: _lib.GraphedDdpmEdmSampler(
+                net.plan, packed, vd, B, cond is not None, churn, return_last=return_last, ws=self._sample_ws,
+                device_noise=dev_noise, sigma_data=self.sigma_data, guidance=guidance), eager, cond, init, step_noise, **kw)
 
 
 class PlDdim(_DdpmSchedule, _PlBase):
@@ -657,6 +749,10 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             m.cond_channels = m.cond_channels + 1
         self._register_schedule(hparams)
         if self._on_ddpm_unet:
+            if _opt(m, "cat_cond", False) and _opt(m, "cond_channels", 0) > 0:
+                raise NotImplementedError("cat_cond on the DDPM U-Net (models/ddim_blocks.py:259, 386-391) is not built for PlCondDdim: "
+                                          "its VP preconditioning scales the concatenated cond (models/ddim.py:932); no shipped "
+                                          "configuration uses it (PlCondEdm runs cat_cond on this network)")
             from .ddim_blocks import Model
         self.model = Model(hparams) if self._on_ddpm_unet else DhariwalUNet(hparams)
         self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
@@ -720,11 +816,6 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             x0_t = torch.empty_like(output)
             _lib.eps_self_cond(x0_t, None, 0, output.shape[1], x_noise=x_noise, F0=output, t=t, sqrt_ab=sa, sqrt_1mab=sb)
         return output, x0_t
-
-    def _adm_only(self, what):
-        if self._on_ddpm_unet:
-            raise NotImplementedError(f"{what} is not built on the DDPM U-Net (models/ddim.py:43-46, Model): it has no backward "
-                                      "here; only the ADM U-Net (hparams.name = 'adm*') trains")
 
     def training_step(self, train_batch, batch_idx):
         self._adm_only("training_step")
@@ -808,20 +899,7 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             self.set_test_sampler_params(sparams)
         net = self._net(self.ema_model if self.ema_model is not None else self.model)
         h, init = _nchw(h).float().contiguous(), _nchw(u_noise).float().contiguous()
-        smin = max(float(sparams.sigma_min), self.sigma_min)
-        smax = min(float(sparams.sigma_max), self.sigma_max)
-        N, rho = int(sparams.timesteps), float(sparams.rho)
-        idx = torch.arange(N, dtype=torch.float64)
-        t_steps = (smax ** (1 / rho) + idx / (N - 1) * (smin ** (1 / rho) - smax ** (1 / rho))) ** rho
-        t_steps = torch.cat([self.round_sigma(t_steps), torch.zeros_like(t_steps[:1])])
-        S_min, S_max = float(sparams.S_min), float(sparams.S_max)
-        t_hat, c_noise = [], []
-        for i in range(N):
-            t_cur = t_steps[i]
-            gamma = min(float(sparams.S_churn) / N, np.sqrt(2) - 1) if S_min <= t_cur <= S_max else 0
-            th = self.round_sigma(t_cur + gamma * t_cur)
-            t_hat.append(float(th))
-            c_noise += [self._c_noise(float(th)), self._c_noise(float(t_steps[i + 1])) if i < N - 1 else 0.0]
+        N, t_steps, t_hat, c_noise = self._edm_schedule(sparams, lambda t: self._c_noise(float(t)))
         vd = _lib.vp_sampler_desc(N, net.cond_channels, t_steps.tolist(), t_hat, c_noise, float(sparams.S_noise), float(sparams.w))
         churn = any(th != float(t_steps[i]) for i, th in enumerate(t_hat))     # the steps whose x_hat adds noise (:1567)
         dev_noise = churn and noise_source == "device"

@@ -6,9 +6,10 @@ unchanged, and the same ``forward(x, t, cond=None, x_self_cond=None, dx=None)`` 
 libmcedm_hip.so (csrc/ddpm.hip).  The sub-modules only OWN parameters (plain torch layers, i.e. the reference's own
 default initialisation).  What the samplers of ``PlDdim`` and ``PlCondDdim`` evaluate is built: inference, one timestep for
 the whole batch, ``x_self_cond`` given or None, and -- with ``cond_channels > 0`` and ``cat_cond: False``
-(configs/model/ddim_cond_h_res32.yaml) -- ``cond`` through the ``cond_enc`` / ``combine_enc`` head.  Everything else (cat_cond on
-this network, dx conditioning, per-sample timesteps, autograd) raises instead of silently computing something else.  There is
-no PyTorch fallback.
+(configs/model/ddim_cond_h_res32.yaml) -- ``cond`` through the ``cond_enc`` / ``combine_enc`` head, or -- with ``cat_cond: True``
+and ``self_cond: False`` (configs/model/edm_cond_h_res32.yaml) -- ``cond`` concatenated in front of the state by ``conv_in``.
+Everything else (cat_cond together with self_cond, dx conditioning, per-sample timesteps, autograd) raises instead of silently
+computing something else.  There is no PyTorch fallback.
 """
 from __future__ import annotations
 
@@ -77,7 +78,8 @@ class Model(nn.Module):
         m = hparams.model
         unsupported = []
         cond_channels = int(_get(m, "cond_channels", 0))
-        if cond_channels > 0 and _get(m, "cat_cond", False):
+        cat_cond = cond_channels > 0 and bool(_get(m, "cat_cond", False))
+        if cat_cond and _get(m, "self_cond", False):
             unsupported.append("cat_cond on the DDPM U-Net (cond concatenated to the input; only the cond_enc head is built)")
         if _get(m, "dx_cond", False):
             unsupported.append("dx_cond")
@@ -93,17 +95,18 @@ class Model(nn.Module):
         self.ch, self.temb_ch = ch, 4 * ch
         self.num_resolutions, self.num_res_blocks, self.resolution = len(mult), m.num_res_blocks, m.resolution
         self.self_condition = bool(_get(m, "self_cond", False))
-        self.cat_condition, self.dx_cond, self.cat_dx, self.cond_channels = False, False, False, cond_channels
+        self.cat_condition, self.dx_cond, self.cat_dx, self.cond_channels = cat_cond, False, False, cond_channels
         self.state_channels = m.in_channels
-        self.in_channels = m.in_channels * (2 if self.self_condition else 1)
+        # self cond is stacked to the input, cond in front of that (ddim_blocks.py:258-259)
+        self.in_channels = m.in_channels * (2 if self.self_condition else 1) + (cond_channels if cat_cond else 0)
         self._arch = dict(in_channels=m.in_channels, out_channels=m.out_ch, ch=ch, ch_mult=mult, num_res_blocks=m.num_res_blocks,
                           attn_resolutions=tuple(m.attn_resolutions), resolution=m.resolution, self_cond=self.self_condition,
-                          cond_channels=cond_channels)
+                          cond_channels=cond_channels, cat_cond=cat_cond)
         self.temb = nn.Module()
         self.temb.dense = nn.ModuleList([nn.Linear(ch, self.temb_ch), nn.Linear(self.temb_ch, self.temb_ch)])
         self.conv_in = nn.Conv2d(self.in_channels, ch, 3, 1, 1)
         self.cond_enc = self.dx_enc = self.combine_enc = None
-        if cond_channels > 0:          # registered behind conv_in like the reference's (ddim_blocks.py:279-306)
+        if cond_channels > 0 and not cat_cond:          # registered behind conv_in like the reference's (ddim_blocks.py:279-306)
             self.cond_enc = nn.Sequential(nn.Conv2d(cond_channels, ch, 1, 1, 0), nn.GELU(),
                                           nn.Conv2d(ch, ch, 3, 1, 1, padding_mode="circular"))
             self.combine_enc = nn.Conv2d(2 * ch, ch, 1, 1, 0)
@@ -188,7 +191,7 @@ class Model(nn.Module):
     def forward(self, x, t, cond=None, x_self_cond=None, dx=None):
         if dx is not None:
             raise NotImplementedError("dx is outside the built path (the samplers pass None)")
-        if cond is not None and self.cond_enc is None:
+        if cond is not None and self.cond_enc is None and not self.cat_condition:
             raise NotImplementedError("cond given to a network built without cond_channels (ddim_blocks.py:401-421 ignores it)")
         if x_self_cond is not None and not self.self_condition:
             raise RuntimeError("x_self_cond given to a network built with self_cond: False")
@@ -198,6 +201,9 @@ class Model(nn.Module):
         if t.numel() != 1 and not bool((t == t[0]).all()):
             raise NotImplementedError("one timestep for the whole batch (what the sampler evaluates)")
         sc = None if x_self_cond is None else x_self_cond.to(torch.float32).contiguous()
+        if self.cat_condition:             # cat(cond, x) by conv_in's two sources; cond None reads as zeros (ddim_blocks.py:386-391)
+            c = None if cond is None else cond.to(torch.float32).contiguous()
+            return self.plan.forward_cat(self.packed_weights(), x.to(torch.float32).contiguous(), float(t[0]), cond=c, ws=self._ws)
         if self.cond_enc is not None:      # the conditioning as its map (None: zero features), then the folded conv_in
             pk = self.packed_weights()
             cmap = None if cond is None else self.plan.cond_map(pk, cond.to(torch.float32).contiguous())

@@ -40,13 +40,15 @@ EXPORTS = [
     "mcedm_ddpm_plan_create_cond", "mcedm_ddpm_cond_map", "mcedm_ddpm_forward_cond", "mcedm_ddpm_vp_sampler_workspace_bytes",
     "mcedm_ddpm_vp_heun_sample", "mcedm_ddpm_vp_heun_sample_rng", "mcedm_ddpm_cond_ddim_workspace_bytes",
     "mcedm_ddpm_cond_ddim_sample", "mcedm_ddpm_cond_ddim_sample_rng",
+    "mcedm_ddpm_forward_cat", "mcedm_ddpm_edm_denoise", "mcedm_ddpm_edm_sampler_workspace_bytes", "mcedm_ddpm_edm_heun_sample",
+    "mcedm_ddpm_edm_heun_sample_rng",
 ]
 # The sampler entries _PlanBase._sample_call drives, with the number of materialised-noise pointers each takes; every one
 # has a "_rng" twin that takes ONE seed pointer in their place.  A new sampler is a row here and a method that names it.
 SAMPLER_STEMS = {
     "mcedm_heun_sample": 1, "mcedm_heun_sample_guided": 1, "mcedm_heun_sample_dxcond": 1,
     "mcedm_vp_heun_sample": 1, "mcedm_ddpm_vp_heun_sample": 1, "mcedm_cond_ddim_sample": 1, "mcedm_ddpm_cond_ddim_sample": 1,
-    "mcedm_ddim_repaint_sample": 1, "mcedm_repaint_sample": 2,
+    "mcedm_ddim_repaint_sample": 1, "mcedm_repaint_sample": 2, "mcedm_ddpm_edm_heun_sample": 1,
 }
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
@@ -235,6 +237,13 @@ def load() -> C.CDLL:
     lib.mcedm_ddpm_cond_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
     lib.mcedm_ddpm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
     lib.mcedm_ddpm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddpm_forward_cat.argtypes = [vp, vp, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
+    lib.mcedm_ddpm_edm_denoise.argtypes = [vp, vp, f32p, f32p, C.c_float, C.c_float, C.c_double, C.c_double, f32p, f32p, vp, sz, i32, vp]
+    lib.mcedm_ddpm_edm_sampler_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
+    lib.mcedm_ddpm_edm_heun_sample.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), C.c_double, C.POINTER(GuidanceDesc), f32p, f32p, f64p,
+                                               f64p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddpm_edm_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), C.c_double, C.POINTER(GuidanceDesc), f32p, f32p, vp,
+                                                   f64p, i32, vp, sz, i32, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)          # AttributeError here == header/library drift
         if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
@@ -652,7 +661,9 @@ class DdpmPlan(_PlanBase):
                  attn_resolutions: Sequence[int], resolution: int, self_cond: bool = True, eps: float = 1e-6,
                  cond_channels: int = 0, cat_cond: bool = False):
         """cond_channels > 0 (with cat_cond False): the cond_enc / combine_enc head of the single-task model
-        (mcedm_ddpm_plan_create_cond); the parameter table then lists cond_enc.* / combine_enc.* behind conv_in.*."""
+        (mcedm_ddpm_plan_create_cond); the parameter table then lists cond_enc.* / combine_enc.* behind conv_in.*.
+        cond_channels > 0 with cat_cond True (needs self_cond False): no head, conv_in reads cat(cond, x) and its weight is
+        [ch, cond_channels + in_channels, 3, 3]; forward_cat / edm_denoise / edm_sample take the raw conditioning."""
         lib = load()
         if len(ch_mult) > MAX_LEVELS or len(attn_resolutions) > MAX_LEVELS:
             raise RuntimeError("too many levels / attention resolutions")
@@ -674,6 +685,7 @@ class DdpmPlan(_PlanBase):
         self._adopt(lib, h)
         self.in_channels, self.out_channels, self.resolution, self.ch = in_channels, out_channels, resolution, ch
         self.cond_channels = int(cond_channels)
+        self.cat_cond = bool(cat_cond) and self.cond_channels > 0
 
     def pack(self, params: Dict[str, torch.Tensor], temb_freqs: torch.Tensor, packed: Optional[torch.Tensor] = None):
         """params keyed like Model.state_dict(); temb_freqs [ch/2] device fp32, built by the caller exactly as
@@ -759,6 +771,50 @@ class DdpmPlan(_PlanBase):
         self._check_x(x)
         self._check_cond(cond, who)
         return self.resolution, self.resolution
+
+    # ---- the single-task EDM model on a cat_cond plan (PlCondEdm on Model) ----------------------------------------------
+    def forward_cat(self, packed, x, t: float, cond=None, ws: Optional[Workspace] = None) -> torch.Tensor:
+        """mcedm_ddpm_forward_cat: Model.forward(x, t, cond) with the raw conditioning in front of the state (None: zeros)."""
+        self._check_x(x)
+        self._check_cond(cond, "forward_cat")
+        B, R = x.shape[0], self.resolution
+        buf = (ws or Workspace()).get(self.workspace_bytes(B), x.device)
+        out = torch.empty((B, self.out_channels, R, R), dtype=torch.float32, device=x.device)
+        check(self._lib.mcedm_ddpm_forward_cat(self._h, packed.data_ptr(), _ptr(x), _ptr(cond), float(t), _ptr(out), buf.data_ptr(),
+                                               buf.numel(), B, _stream()), "ddpm_forward_cat")
+        return out
+
+    def edm_denoise(self, packed, x, sigma: float, c_noise: float, cond=None, w: float = 0.0, sigma_data: float = 1.0,
+                    ws: Optional[Workspace] = None, want_F: bool = False):
+        """mcedm_ddpm_edm_denoise: PlCondEdm.get_denoised at one noise level; c_noise is the caller's fp32 ln(sigma) / 4."""
+        self._check_x(x)
+        self._check_cond(cond, "edm_denoise")
+        B = x.shape[0]
+        buf = (ws or Workspace()).get(self.workspace_bytes(B), x.device)
+        D = torch.empty((B, self.out_channels, self.resolution, self.resolution), dtype=torch.float32, device=x.device)
+        F = torch.empty_like(D) if want_F else None
+        check(self._lib.mcedm_ddpm_edm_denoise(self._h, packed.data_ptr(), _ptr(x), _ptr(cond), float(sigma), float(c_noise), float(w),
+                                               float(sigma_data), _ptr(D), _ptr(F), buf.data_ptr(), buf.numel(), B, _stream()),
+              "ddpm_edm_denoise")
+        return (D, F) if want_F else D
+
+    def edm_sampler_workspace_bytes(self, B: int) -> int:
+        return self._bytes("mcedm_ddpm_edm_sampler_workspace_bytes", "ddpm_edm_sampler_workspace_bytes", B)
+
+    def edm_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
+                   ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   sigma_data: float = 1.0, guidance: Optional["GuidanceDesc"] = None) -> torch.Tensor:
+        """mcedm_ddpm_edm_heun_sample (rng_seed None) / its _rng form: PlCondEdm.sample_edm on the device; returns
+        [B, 1 or N+1, R, R, in] float64.  vd: vp_sampler_desc with t_hat as it is and c_noise = ln(sigma) / 4.  guidance: the PDE
+        residual whose gradient at the denoised state corrects the slope (guide_dx)."""
+        R = self._state_hw(init_noise, cond, "edm_sample")[0]
+        B, N = init_noise.shape[0], vd.timesteps
+        return self._sample_call("edm_sample", "mcedm_ddpm_edm_heun_sample", packed,
+                                 (C.byref(vd), float(sigma_data), C.byref(guidance) if guidance is not None else None, _ptr(cond),
+                                  _ptr(init_noise)),
+                                 [("step_noise", step_noise, torch.float64, (N,) + tuple(init_noise.shape))], rng_seed, out,
+                                 [(B, 1 if return_last else N + 1, R, R, self.in_channels)], torch.float64, return_last, ws,
+                                 self.edm_sampler_workspace_bytes(B), (B,), init_noise.device)
 
     def ddim_workspace_bytes(self, B: int) -> int:
         return self._bytes("mcedm_ddim_workspace_bytes", "ddim_workspace_bytes", B)
@@ -1033,6 +1089,33 @@ class GraphedVpSampler(_GraphedCall):
     def _run(self):
         self.plan.vp_sample(self.packed, self.vd, self.cond, self.init, self.step_noise, self.return_last, self.ws,
                             rng_seed=self.seed, out=self.out)
+
+    def __call__(self, cond, init_noise, step_noise=None, seed=None) -> torch.Tensor:
+        return self._replay(seed, cond, init_noise, step_noise)
+
+
+class GraphedDdpmEdmSampler(_GraphedCall):
+    """mcedm_ddpm_edm_heun_sample (device_noise False) or its _rng form (True) captured once and replayed: the ~2 N network
+    evaluations (twice that with classifier-free guidance), the PDE-guidance gradients and the state updates of PlCondEdm.sample_edm
+    on the DDPM U-Net are one HIP graph.  Returns the instance's static output tensor, overwritten by the next call."""
+
+    def __init__(self, plan: "DdpmPlan", packed: torch.Tensor, vd: VpSamplerDesc, B: int, has_cond: bool, churn: bool,
+                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False, sigma_data: float = 1.0,
+                 guidance: Optional["GuidanceDesc"] = None):
+        dev = packed.device
+        self.plan, self.packed, self.vd, self.return_last = plan, packed, vd, return_last
+        self.sigma_data, self.guidance = sigma_data, guidance      # host-side, baked into the captured kernel arguments
+        R, Cc = plan.resolution, plan.in_channels
+        self.cond = torch.zeros((B, plan.cond_channels, R, R), device=dev) if has_cond else None
+        self.init = torch.zeros((B, Cc, R, R), device=dev)
+        self.seed, self.step_noise = self._draws(dev, churn, device_noise, (vd.timesteps, B, Cc, R, R), torch.float64)
+        self.out = torch.empty((B, 1 if return_last else vd.timesteps + 1, R, R, Cc), dtype=torch.float64, device=dev)
+        self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "step_noise": self.step_noise}, ws,
+                           plan.edm_sampler_workspace_bytes(B))
+
+    def _run(self):
+        self.plan.edm_sample(self.packed, self.vd, self.cond, self.init, self.step_noise, self.return_last, self.ws,
+                             rng_seed=self.seed, out=self.out, sigma_data=self.sigma_data, guidance=self.guidance)
 
     def __call__(self, cond, init_noise, step_noise=None, seed=None) -> torch.Tensor:
         return self._replay(seed, cond, init_noise, step_noise)
