@@ -7,7 +7,10 @@ Plain-PyTorch restatement of
   * ``PlDdim.round_sigma``              models/ddim.py:949-957,  ``compute_alpha`` :700-704, ``get_edm_steps`` :131-137
   * ``PlDdim.sample_edm``               models/ddim.py:959-1051  (inner ``n_repeat`` loop, known-region re-noising)
 for the configuration of configs/model/ddim_res32.yaml (type simple, self_cond True, cond_channels 0, dx_cond False,
-dropout 0, resamp_with_conv True).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import it.
+dropout 0, resamp_with_conv True) and its variants: any ch / ch_mult / num_res_blocks / attn_resolutions, and for the network
+alone (``model_forward``) the cond_enc / combine_enc head and cat_cond (ddim_blocks.py:279-306, 378-421).  ``model_forward``
+runs in the dtype of the parameters it is given: fp32 is the reference's own arithmetic, fp64 the high-precision reference.
+Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import it.
 Pinned by tests/golden/ddpm.npz, which oracle/make_golden_ddpm.py writes by running the reference itself.
 Parameters are a flat dict keyed exactly like ``Model.state_dict()``.
 """
@@ -38,6 +41,8 @@ class DdpmConfig:
     num_timesteps: int = 1000
     beta_start: float = 1e-4
     beta_end: float = 0.02
+    cond_channels: int = 0          # > 0: the cond_enc / combine_enc head (ddim_blocks.py:279-306), or with cat_cond ...
+    cat_cond: bool = False          # ... the conditioning concatenated in front of conv_in's input (:258-259, 386-391)
 
 
 # --------------------------------------------------------------------------- #
@@ -61,13 +66,22 @@ def _attn_shapes(k, c):
     return o
 
 
+def head_shapes(ch: int, cond_channels: int) -> List[Tuple[str, Tuple[int, ...]]]:
+    """cond_enc / combine_enc as Model registers them behind conv_in (ddim_blocks.py:279-306)."""
+    return [("cond_enc.0.weight", (ch, cond_channels, 1, 1)), ("cond_enc.0.bias", (ch,)),
+            ("cond_enc.2.weight", (ch, ch, 3, 3)), ("cond_enc.2.bias", (ch,)),
+            ("combine_enc.weight", (ch, 2 * ch, 1, 1)), ("combine_enc.bias", (ch,))]
+
+
 def param_shapes(cfg: DdpmConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     ch, temb = cfg.ch, 4 * cfg.ch
     nres = len(cfg.ch_mult)
-    in_total = cfg.in_channels * (2 if cfg.self_cond else 1)
+    in_total = cfg.in_channels * (2 if cfg.self_cond else 1) + (cfg.cond_channels if cfg.cat_cond else 0)
     out = [("temb.dense.0.weight", (temb, ch)), ("temb.dense.0.bias", (temb,)),
            ("temb.dense.1.weight", (temb, temb)), ("temb.dense.1.bias", (temb,)),
            ("conv_in.weight", (ch, in_total, 3, 3)), ("conv_in.bias", (ch,))]
+    if cfg.cond_channels > 0 and not cfg.cat_cond:
+        out += head_shapes(ch, cfg.cond_channels)
     in_mult = (1,) + tuple(cfg.ch_mult)
     res = cfg.resolution
     block_in = ch
@@ -137,9 +151,11 @@ def timestep_freqs(ch: int) -> Tensor:
     return torch.exp(torch.arange(half, dtype=torch.float32) * -emb)
 
 
-def timestep_embedding(t: Tensor, ch: int) -> Tensor:
-    """get_timestep_embedding, ddim_blocks.py:12-30: [sin | cos] (sin FIRST)."""
-    e = t.float()[:, None] * timestep_freqs(ch)[None, :]
+def timestep_embedding(t: Tensor, ch: int, dtype: torch.dtype = torch.float32) -> Tensor:
+    """get_timestep_embedding, ddim_blocks.py:12-30: [sin | cos] (sin FIRST).  ``dtype``: the precision of the product and of
+    sin / cos; the frequencies are the fp32 table in either case (it is what the reference multiplies by, and an input of the
+    library's packing)."""
+    e = t.to(dtype)[:, None] * timestep_freqs(ch).to(dtype)[None, :]
     return torch.cat([torch.sin(e), torch.cos(e)], dim=1)
 
 
@@ -185,16 +201,36 @@ def upsample(P, k, x):
     return F.conv2d(F.interpolate(x, scale_factor=2.0, mode="nearest"), P[f"{k}.conv.weight"], P[f"{k}.conv.bias"], padding=1)
 
 
-def model_forward(P, cfg: DdpmConfig, x: Tensor, t: Tensor, x_self_cond: Optional[Tensor] = None) -> Tensor:
-    """Model.forward, ddim_blocks.py:410-470 with cond None, dx None."""
+def cond_enc(P, cond: Tensor) -> Tensor:
+    """Model.cond_enc, ddim_blocks.py:281-286: 1x1 conv, nn.GELU() (the erf form), 3x3 conv with circular padding."""
+    g = F.gelu(F.conv2d(cond, P["cond_enc.0.weight"], P["cond_enc.0.bias"]))
+    return F.conv2d(F.pad(g, (1, 1, 1, 1), mode="circular"), P["cond_enc.2.weight"], P["cond_enc.2.bias"])
+
+
+def model_forward(P, cfg: DdpmConfig, x: Tensor, t: Tensor, x_self_cond: Optional[Tensor] = None,
+                  cond: Optional[Tensor] = None) -> Tensor:
+    """Model.forward, ddim_blocks.py:378-470 with dx None, evaluated in the dtype of the parameters (fp32 as the reference runs
+    it; fp64 parameters give the high-precision reference of the same formula).  cfg.cat_cond: conv_in reads
+    cat(cond or zeros, x) (:386-391); cfg.cond_channels without it: the head combine_enc(cat(conv_in(x'), cond_enc(cond) or
+    zeros)) (:401-421)."""
     assert x.shape[2] == x.shape[3] == cfg.resolution
-    temb = timestep_embedding(t, cfg.ch)
+    dt = P["conv_in.weight"].dtype
+    x = x.to(dt)
+    temb = timestep_embedding(t, cfg.ch, dt)
     temb = F.linear(_swish(F.linear(temb, P["temb.dense.0.weight"], P["temb.dense.0.bias"])),
                     P["temb.dense.1.weight"], P["temb.dense.1.bias"])
     if cfg.self_cond:
-        x = torch.cat((torch.zeros_like(x) if x_self_cond is None else x_self_cond, x), dim=1)
+        x = torch.cat((torch.zeros_like(x) if x_self_cond is None else x_self_cond.to(dt), x), dim=1)
+    has_head = cfg.cond_channels > 0 and not cfg.cat_cond
+    if cfg.cond_channels > 0 and cfg.cat_cond:
+        front = torch.zeros_like(x[:, :1]).expand(-1, cfg.cond_channels, -1, -1) if cond is None else cond.to(dt)
+        x = torch.cat((front, x), dim=1)
     nres = len(cfg.ch_mult)
-    hs = [F.conv2d(x, P["conv_in.weight"], P["conv_in.bias"], padding=1)]
+    h0 = F.conv2d(x, P["conv_in.weight"], P["conv_in.bias"], padding=1)
+    if has_head:
+        feat = torch.zeros_like(h0) if cond is None else cond_enc(P, cond.to(dt))
+        h0 = F.conv2d(torch.cat([h0, feat], dim=1), P["combine_enc.weight"], P["combine_enc.bias"])
+    hs = [h0]
     for lv in range(nres):
         for j in range(cfg.num_res_blocks):
             h = resnet_block(P, f"down.{lv}.block.{j}", hs[-1], temb)

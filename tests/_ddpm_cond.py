@@ -7,6 +7,7 @@ import sys
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -30,9 +31,7 @@ EVAL_DDIM_STEPS, EVAL_N = 4, 2
 
 def head_shapes(cond_channels, ch=CFG.ch):
     """cond_enc / combine_enc as Model registers them behind conv_in (models/ddim_blocks.py:279-306)."""
-    return [("cond_enc.0.weight", (ch, cond_channels, 1, 1)), ("cond_enc.0.bias", (ch,)),
-            ("cond_enc.2.weight", (ch, ch, 3, 3)), ("cond_enc.2.bias", (ch,)),
-            ("combine_enc.weight", (ch, 2 * ch, 1, 1)), ("combine_enc.bias", (ch,))]
+    return ddo.head_shapes(ch, cond_channels)
 
 
 def param_shapes(cond_channels):
@@ -125,3 +124,30 @@ def bars_apart(a, b):
     """|a - b| in units of the comparison bar for reference b (rtol 1e-4, atol 1e-5 max|b|), per entry."""
     a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
     return (a - b).abs() / (1e-5 * float(b.abs().max()) + 1e-4 * b.abs())
+
+
+def check_cond_map(got, P, cond, what):
+    """The map kernel's output against M = (Wc cond_enc.2) (*)circ GELU(cond_enc.0(cond)) + (Wx b_in + Wc b_enc2 + b_comb), everything
+    in fp64 on the host (P: the parameters in fp64); the border ring (where the wrap-around is read), the four corners (both axes
+    wrap) and the interior are held to the bar apart."""
+    got = got.detach().cpu().double()
+    ch = P["combine_enc.bias"].numel()
+    Bc, _, R, _ = cond.shape
+    Wx, Wc = P["combine_enc.weight"][:, :ch, 0, 0], P["combine_enc.weight"][:, ch:, 0, 0]
+    g = F.gelu(F.conv2d(cond.double(), P["cond_enc.0.weight"], P["cond_enc.0.bias"]))
+    w2 = torch.einsum("om,mckl->ockl", Wc, P["cond_enc.2.weight"])
+    bias = Wx @ P["conv_in.bias"] + Wc @ P["cond_enc.2.bias"] + P["combine_enc.bias"]
+    ref = F.conv2d(F.pad(g, (1, 1, 1, 1), mode="circular"), w2, bias)
+    assert got.shape == ref.shape == (Bc, ch, R, R)
+    ring = torch.ones(R, R, dtype=torch.bool)
+    ring[1:-1, 1:-1] = False
+    corners = torch.zeros(R, R, dtype=torch.bool)
+    corners[0, 0] = corners[0, -1] = corners[-1, 0] = corners[-1, -1] = True
+    atol = 1e-5 * float(ref.abs().max())
+    for where, sel in (("interior", ~ring), ("border ring", ring & ~corners), ("corners", corners)):
+        err, lim = (got[..., sel] - ref[..., sel]).abs(), atol + 1e-4 * ref[..., sel].abs()
+        print(f"cond_map {what} {where}: worst err / bar {float((err / lim).max()):.4f}")
+        assert bool((err <= lim).all()), (where, float(err.max()))
+    # zero padding in place of circular would miss the ring by far more than the bar
+    zp = F.conv2d(g, w2, bias, padding=1)
+    assert float((bars_apart(zp[..., ring], ref[..., ring]) >= 100).double().mean()) > 0.5

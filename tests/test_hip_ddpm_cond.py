@@ -7,7 +7,6 @@ import io
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import fixtures as fx
 from tests import _ddpm_cond as D
@@ -45,27 +44,8 @@ def test_cond_map_against_the_formula_in_fp64(cc):
     net = m.model
     cond = D.fwd_inputs(cc)[1]
     with torch.no_grad():
-        got = net.plan.cond_map(net.packed_weights(), cond.cuda()).cpu().double()
-    P = {n: p.detach().cpu().double() for n, p in net.named_parameters()}
-    ch = net.ch
-    Wx, Wc = P["combine_enc.weight"][:, :ch, 0, 0], P["combine_enc.weight"][:, ch:, 0, 0]
-    g = F.gelu(F.conv2d(cond.double(), P["cond_enc.0.weight"], P["cond_enc.0.bias"]))
-    w2 = torch.einsum("om,mckl->ockl", Wc, P["cond_enc.2.weight"])
-    bias = Wx @ P["conv_in.bias"] + Wc @ P["cond_enc.2.bias"] + P["combine_enc.bias"]
-    ref = F.conv2d(F.pad(g, (1, 1, 1, 1), mode="circular"), w2, bias)
-    assert got.shape == ref.shape == (B, ch, H, W)
-    ring = torch.ones(H, W, dtype=torch.bool)
-    ring[1:-1, 1:-1] = False
-    corners = torch.zeros(H, W, dtype=torch.bool)
-    corners[0, 0] = corners[0, -1] = corners[-1, 0] = corners[-1, -1] = True
-    atol = 1e-5 * float(ref.abs().max())
-    for what, sel in (("interior", ~ring), ("border ring", ring & ~corners), ("corners", corners)):
-        err, lim = (got[..., sel] - ref[..., sel]).abs(), atol + 1e-4 * ref[..., sel].abs()
-        print(f"cond_map cc={cc} {what}: worst err / bar {float((err / lim).max()):.4f}")
-        assert bool((err <= lim).all()), (what, float(err.max()))
-    # zero padding in place of circular would miss the ring by far more than the bar
-    zp = F.conv2d(g, w2, bias, padding=1)
-    assert float((D.bars_apart(zp[..., ring], ref[..., ring]) >= 100).double().mean()) > 0.5
+        got = net.plan.cond_map(net.packed_weights(), cond.cuda())
+    D.check_cond_map(got, {n: p.detach().cpu().double() for n, p in net.named_parameters()}, cond, f"cc={cc}")
 
 
 # ---- 2. forward, get_denoised, samplers, evaluation loops against the reference ---------------------------------------------
