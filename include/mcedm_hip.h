@@ -104,6 +104,7 @@ void mcedm_unet_plan_destroy(mcedm_plan* plan);
 #define MCEDM_VARIANT_WGRAD_WINO 5      /* Winograd F(3x3, 2x2) weight gradient (env MCEDM_WGRAD_WINO, default 1) */
 #define MCEDM_VARIANT_CONV1X1_REG 6     /* register-direct GEMM for un-transformed 1x1 convs at >= 32 x 32 (env MCEDM_CONV1X1_REG, default 1) */
 #define MCEDM_VARIANT_CONV_WINO_FOLD 7  /* decoder skip projections computed in the Winograd conv1's epilogue (env MCEDM_WINO_FOLD, default 1); the workspace layout does not depend on it */
+#define MCEDM_VARIANT_CONV_WINO_UPZ 8   /* up-sampling Winograd convs skip the positions whose transformed input is exactly zero and stage their input at source resolution (env MCEDM_WINO_UPZ, default 1); bit-identical results, the workspace layout does not depend on it */
 int mcedm_unet_plan_set_variant(mcedm_plan* plan, int which, int value);
 
 /* Parameter table in DhariwalUNet.state_dict() order (parameters only, no buffers).
@@ -419,6 +420,11 @@ int mcedm_op_pack_conv_wino(const float* w, int Cout, int Cin, float* wino, void
 int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
                        int resample, int H, int W, const float* wino, const float* bias, const float* res, int res_mode,
                        float* out, int Cout, int B, void* stream);
+/* The same launch with the fused GroupNorm records of out in gsum: B * ceil(H / 4) * ceil(W / 8) * ceil(Cout / 4) * 2 floats (4-channel
+ * blocks, as a plan's convs write them; kernel-level tests compare the records of two variants of the kernel). */
+int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                            int resample, int H, int W, const float* wino, const float* bias, const float* res, int res_mode,
+                            float* out, float* gsum, int Cout, int B, void* stream);
 /* The Winograd table of the DATA GRADIENT of that convolution (the backward of models/adm_blocks.py:57-82: du = conv3x3 of dy
  * with the weights transposed over the channels and mirrored over the taps).  w is the FORWARD weight [Cout][Cin][3][3]; wino
  * holds mcedm_op_conv_wino_packed_floats(Cin, Cout) floats and is used as mcedm_op_conv_wino(dy, .., wino, NULL bias, ..,
@@ -519,6 +525,15 @@ int mcedm_op_set_conv1x1_reg(int enable);
  * projection is summed in conv1x1_reg_kernel's order).  Read at every launch and at every forward; the workspace layout does not depend on it (the
  * projected tensor stays reserved), so it may change between calls on one workspace.  Process-global. */
 int mcedm_op_set_conv_wino_fold(int enable);
+/* The zero-position variant of the up-sampling Winograd kernel (conv_wino.hip, WinoUp): the input of an RS_UP conv is the nearest
+ * 2x up-sampling of its source and every tile starts on an even pixel, so rows (and columns) 1 and 2 of every 4 x 4 input patch are
+ * equal and the transformed input is exactly +0 at the seven Winograd positions with xi = 2 or nu = 2; the variant loads no weights,
+ * reads no B fragments and issues no matrix instructions for them, and stages and transforms the tile's input at source resolution
+ * (one load and one activation per source pixel): 1 on, 0 off (all sixteen positions), 2 the positions alone on the
+ * sixteen-position kernel's staging (A/B runs; this hook and the environment only), -1 back to the default (env MCEDM_WINO_UPZ, else
+ * on).  Bit-identical results in every form for finite transformed weights (a product with an exact zero is dropped instead of
+ * yielding NaN).  Read at every launch; the workspace layout does not depend on it.  Process-global. */
+int mcedm_op_set_conv_wino_upz(int enable);
 /* [Cout][Cin] weights of a 1x1 conv -> the MFMA-fragment order that mcedm_op_conv_skip's sk_wfrag expects;
  * wfrag holds ((Cout + 31) / 32 * 32) * ((Cin + 7) / 8 * 8) floats, 16-byte aligned. */
 int mcedm_op_pack_conv_frag(const float* w, int Cout, int Cin, float* wfrag, void* stream);

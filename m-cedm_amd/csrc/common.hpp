@@ -41,8 +41,8 @@ void set_error(const char* fmt, ...);
 // (mcedm_*_plan_set_variant; a field of the plan, so two plans in one process -- on two threads or two streams -- cannot flip each
 // other's kernels), the process-wide test hooks mcedm_op_set_* (kernel-level calls have no plan), the environment.
 enum KernelVariant { KV_CONV_WINO = 0, KV_CONV_WINO1 = 1, KV_CONV_RESIDENT = 2, KV_CONV8 = 3, KV_ATTN_FUSED = 4, KV_WGRAD_WINO = 5,
-                     KV_CONV1X1_REG = 6, KV_CONV_WINO_FOLD = 7, KV_COUNT = 8 };
-struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1}; };
+                     KV_CONV1X1_REG = 6, KV_CONV_WINO_FOLD = 7, KV_CONV_WINO_UPZ = 8, KV_COUNT = 9 };
+struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1}; };
 const KernelVariants* current_variants();                 // of the executing plan-level call on this thread, or null
 struct VariantScope {                                      // first statement of every extern "C" function that takes a plan
   const KernelVariants* prev;
@@ -178,6 +178,7 @@ bool conv_wino_shape_ok(int Cout, int Cin, int H, int W);
 // the SKIP variant: conv1 of an un-resampled block computes the block's 1x1 skip projection (sk_Ca + sk_Cb -> Cout) in its epilogue
 bool conv_wino_fold_shape_ok(int Cout, int sk_Ca, int sk_Cb, int H, int W);
 void set_conv_wino_fold(int enable);                     // 1 / 0, -1: default (env MCEDM_WINO_FOLD, else on)
+void set_conv_wino_upz(int enable);                      // 1 / 0, 2: the positions alone (A/B runs), -1: default (env MCEDM_WINO_UPZ, else on)
 size_t conv_frag_packed_floats(int Cout, int Cin);       // a 1x1 conv's weights in MFMA-fragment order (ConvArgs::sk_wfrag)
 int launch_pack_conv_frag(const float* w, float* dst, int Cout, int Cin, hipStream_t stream);   // w [Cout][Cin]
 void set_conv_wino(int enable);                          // 1 / 0, -1: default (env MCEDM_WINOGRAD, else on)

@@ -23,6 +23,8 @@
 //     issued in slices between the MFMAs of the same wave (see the K loop).
 //   * epilogue: the output transform is register-local over nu; over xi the two halves exchange one 2 x 32-register
 //     partial through LDS; then bias, residual, stores (8-byte, two pixels of a row) and the fused GroupNorm statistics.
+//   * up-sampled input (UP): by default the zero-position variant WinoUp (conv_wino.hpp) -- 9 of the 16 positions, the raw tile
+//     staged and transformed at source resolution; bit-identical to the sixteen-position form, which MCEDM_WINO_UPZ=0 keeps.
 // Results differ from the direct kernel in the last bits (a different, equally long fp32 sum: measured 1.5x its error
 // against fp64, 0.1 of the rtol 1e-4 / atol 1e-5 bar); they do not depend on the batch size or the grid.
 #include <atomic>
@@ -183,11 +185,16 @@ struct SkipFold<C, true> {
 // ACT = false: the launch has no activation (p.act == 0: the data-gradient convs of training, whose input is a raw gradient): the
 // plain variant's branch-free "evaluate SiLU and select" is compiled out -- ~20 of the ~58 vector instructions per chunk and lane,
 // every one of them matrix time (round 5; the forward convs of inference all carry the activation)
-template <class C, bool UP, bool ACT = true>
+// Tag: empty, or WinoUp<SRC> (conv_wino.hpp): the zero-position variant of the up-sampling kernel
+template <class C, bool UP, bool ACT = true, class... Tag>
 __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(const ConvArgs p, int tiles_x, int tiles_img, int nch, int mblocks,
                                                                           int per, int mode) {
   constexpr int WSC = C::SC, VBUF = C::VBUF, RBUF = C::RBUF, MB = C::MB;
   constexpr bool SKIP = C::SKIP;                                  // WinoSkipCfg: the epilogue computes the residual (the skip projection)
+  constexpr bool UPZ = WinoUpTraits<Tag...>::UPZ;                 // WinoUp: nothing is done for the positions whose V is exactly +0
+  constexpr bool UPS = WinoUpTraits<Tag...>::UPS;                 // ... and the raw tile is staged and transformed at source resolution
+  static_assert(!UPS || UPZ, "source-resolution staging is part of the zero-position variant");
+  static_assert(!UPZ || (UP && !SKIP), "the zero positions belong to the up-sampled input");
   extern __shared__ float lds[];
   const int Cin = p.Ca + p.Cb;
   float* const vbuf = lds;
@@ -227,7 +234,8 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   //   up-sampled input: elements lane, lane + 64, lane + 128 of the 180, one dword load each (source pixel (y/2, x/2)).
   // Geometry (byte offsets, zero-padding masks) of the tile that is being LOADED; the masks of the tile whose registers are
   // waiting to be COMMITTED are kept beside them (the two differ for one trip at a tile boundary).
-  constexpr int NR = UP ? RSUB : 4, NG = UP ? RSUB : 1;             // raw registers / geometry entries per lane and channel
+  //   UPS: element `lane` of the 6 x 10 source patch, one dword load.
+  constexpr int NR = UPS ? 1 : UP ? RSUB : 4, NG = UPS ? 1 : UP ? RSUB : 1;   // raw registers / geometry entries per lane and channel
   unsigned roff[NG], rkeepL[NG], rkeepC[NG];
   int lofs[4];                                                      // plain input: where the quad's four elements go in the LDS patch
   if (!UP) {
@@ -240,7 +248,13 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   }
   auto set_geom = [&](int tile) {
     const int y0 = (tile / tiles_x) * WPH, x0 = (tile % tiles_x) * WPW;
-    if (UP) {
+    if (UPS) {     // zero padding = source row / column -1 or Hs / Ws (H = 2 Hs, W = 2 Ws, y0 and x0 even)
+      const int r = lane / UCOLS, c = lane - r * UCOLS;
+      const int y = (y0 >> 1) - 1 + r, x = (x0 >> 1) - 1 + c;
+      const bool inb = lane < UROWS * UCOLS && (unsigned)y < (unsigned)p.Hs && (unsigned)x < (unsigned)p.Ws;
+      rkeepL[0] = inb ? 0xffffffffu : 0u;
+      roff[0] = !inb ? 0u : 4u * (unsigned)(y * p.Ws + x);
+    } else if (UP) {
 #pragma unroll
       for (int i = 0; i < NG; ++i) {
         const int e = lane + 64 * i;
@@ -301,7 +315,11 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       const bool ok = ci < Cin && (ci < p.Ca ? p.xa : p.xb) != nullptr;
       const Coef cf = cfl[ci < Cin ? ci : Cin - 1];
       const unsigned ck = ok ? 0xffffffffu : 0u;
-      if (UP) {
+      if (UPS) {
+        float v = apply_coef(raw[sc][cw][0], cf, p.act);
+        v = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & (rkeepC[0] & ck));
+        rb[(sc * WKC + kl) * UPLANE + lane] = v;                     // lanes 60 .. 63: zeros into the plane's pad
+      } else if (UP) {
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
           float v = apply_coef(raw[sc][cw][i], cf, p.act);
@@ -313,6 +331,8 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
         // lane loads element 0 of the plane, and an Inf / NaN there (or a (v - mean) that overflows) would make the padding NaN
         // instead of 0; the up-sampling variant above masks the finished value bit-wise.  (A network whose activations are
         // not finite has no meaningful output either way; two v_and per pair here would cost ~3 % of the slice's vector work.)
+        // PRECONDITION of the zero-position variant (WinoUp, conv_wino.hpp): finite transformed WEIGHTS -- a product with an
+        // exactly zero V is dropped there, where the sixteen-position kernel would have turned 0 * Inf into NaN.
         const unsigned mk = rkeepC[0] & ck;
         const float scm = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, cf.scale) & mk);
         const float ofm = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, cf.offset) & mk);
@@ -346,7 +366,24 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   const f32x2 tpm = {1.f, -1.f};
   const int tr_dst = (8 * hf) * VPOS + (tk & 1) * VH1 + (tty * WTX + ttx) * 4 + (tk >> 1);
   f32x2 td[WSC][C::TI][3][2];                         // rows Y, Z, X; column pairs (c0, c1), (c2, c3)
+  // UPS: the same rows out of the source patch -- patch row r = source row (r + 1) >> 1: Y = ty + hf, Z = ty + 1 + hf, X = ty + 1 -- and
+  // the three source columns tx, tx + 1, tx + 2 = (c0, c1 = c2, c3)
+  const int us_yz = tk * UPLANE + (tty + hf) * UCOLS + ttx, us_x = tk * UPLANE + (tty + 1) * UCOLS + ttx;
+  float tu[WSC][C::TI][3][3];
   auto transform_read1 = [&](int sc, const float* rb) {
+    if constexpr (UPS) {
+#pragma unroll
+      for (int ti = 0; ti < C::TI; ++ti) {
+        const float* b = rb + sc * WKC * UPLANE + MB * ti * UCOLS;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          tu[sc][ti][0][c] = b[us_yz + c];
+          tu[sc][ti][1][c] = b[us_yz + UCOLS + c];
+          tu[sc][ti][2][c] = b[us_x + c];
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int ti = 0; ti < C::TI; ++ti)
 #pragma unroll
@@ -358,6 +395,26 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       }
   };
   auto transform_finish1 = [&](int sc, float* vb) {
+    if constexpr (UPS) {
+#pragma unroll
+      for (int ti = 0; ti < C::TI; ++ti) {
+        float t[2][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          t[0][c] = tu[sc][ti][0][c] - tu[sc][ti][2][c];
+          t[1][c] = tu[sc][ti][2][c] + tsgn * tu[sc][ti][1][c];
+        }
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+          if (x == 0 && hf != 0) continue;                 // xi = 2 of the hf = 1 waves is exactly +0 and nobody reads it
+          float* o = vb + sc * 16 * VPOS + tr_dst + MB * ti * WTX * 4 + 4 * x * VPOS;
+          o[0 * VPOS] = t[x][0] - t[x][1];                 // c0 - c2
+          o[1 * VPOS] = t[x][1] + 1.f * t[x][1];           // c1 + c2
+          o[3 * VPOS] = t[x][1] - t[x][2];                 // c1 - c3
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int ti = 0; ti < C::TI; ++ti) {
       f32x2 t[2][2];
@@ -374,7 +431,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
         float* o = vb + sc * 16 * VPOS + tr_dst + MB * ti * WTX * 4 + 4 * x * VPOS;
         o[0 * VPOS] = o03.x;
         o[1 * VPOS] = o12.x;
-        o[2 * VPOS] = o12.y;
+        if constexpr (!UPZ) o[2 * VPOS] = o12.y;             // UPZ: nu = 2 is exactly +0 and nobody reads it
         o[3 * VPOS] = o03.y;
       }
     }
@@ -394,10 +451,19 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   if (G > 2) raw_load();                                             // stays in registers until trip 0 commits it
   // this wave's transformed weights: 8 positions x one 16-byte load per chunk
   const size_t ustride = (size_t)mblocks * 16 * 64;                  // f32x4 per chunk
-  const f32x4* up = reinterpret_cast<const f32x4*>(p.wino) + ((size_t)(m0 / 32 + mb) * 16 + 8 * hf) * 64 + lane;
+  // UPZ: block q of the hf = 1 waves is position 12 + q (xi = 3 first; its blocks 4 .. 7, xi = 2, are never touched)
+  constexpr int PHF = UPZ ? 12 : 8;                                  // first position of the hf = 1 waves' block 0
+  const f32x4* up = reinterpret_cast<const f32x4*>(p.wino) + ((size_t)(m0 / 32 + mb) * 16 + PHF * hf) * 64 + lane;
   f32x4 ua[8];                                                       // reloaded position by position right after its last use
+  if constexpr (UPZ) {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    ua[0] = up[0 * 64]; ua[1] = up[1 * 64]; ua[3] = up[3 * 64];
+    ua[4] = zero4; ua[5] = zero4; ua[7] = zero4;
+    if (hf == 0) { ua[4] = up[4 * 64]; ua[5] = up[5 * 64]; ua[7] = up[7 * 64]; }
+  } else {
 #pragma unroll
-  for (int q = 0; q < 8; ++q) ua[q] = up[q * 64];
+    for (int q = 0; q < 8; ++q) ua[q] = up[q * 64];
+  }
   __syncthreads();
   transform_read(rbuf);
   transform_finish(vbuf);
@@ -424,7 +490,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   init_acc();
 
   // ---- the stream of stages: one trip = one stage of WSC chunks
-  const int vrd = (8 * hf) * VPOS + (lane >> 5) * VH1 + (lane & 31) * 4;
+  const int vrd = (PHF * hf) * VPOS + (lane >> 5) * VH1 + (lane & 31) * 4;
   if (p.dbg && tid == 0) { p.dbg[blockIdx.x * 16 + 1] = __builtin_amdgcn_s_memrealtime(); p.dbg[blockIdx.x * 16 + 5] = __builtin_amdgcn_s_memtime(); }
 #ifdef MCEDM_WINO_TIMELINE      // cycle sums of waves 0 and MB (lane 0): MFMA stream, barrier, epilogue -> dbg[8..12] / dbg[13..15, 7] (diagnostic builds only)
   unsigned long long ph[5] = {0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -449,6 +515,24 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   // stages of the workgroup's next tile.  Sliced like this the side work costs its issue cycles; as a phase of its own
   // (before or after the MFMAs, or ping-ponged between the two waves of a SIMD) it cost its latencies: 2400 cycles per chunk
   // and wave against 2048 of MFMAs.  Every slice touches buffers no MFMA of this trip reads: one barrier per trip.
+  // UPZ: a chunk is THREE slots of four MFMAs -- the blocks 0, 1, 3 that both halves run -- and behind them, for the hf = 0 waves
+  // only, the twelve MFMAs of blocks 4, 5, 7 with their B reads and reloads behind ONE wave-uniform branch: no side work in there
+  // (a second copy of a slice is what makes hipcc give the accumulators a second register set), so the six
+  // slices of a stage sit in its six common slots, ten instructions behind each MFMA instead of five.
+  auto side_slice_upz = [&](int slot, int cur) {
+    if (WSC == 2) {
+      if (slot == 0) transform_read1(0, rbuf + (cur ^ 1) * RBUF);
+      if (slot == 1) raw_commit1(0, rbuf + cur * RBUF);
+      if (slot == 2) { transform_finish1(0, vbuf + (cur ^ 1) * VBUF); raw_load1(0); }
+      if (slot == 3) transform_read1(WSC - 1, rbuf + (cur ^ 1) * RBUF);
+      if (slot == 4) { raw_commit1(WSC - 1, rbuf + cur * RBUF); commit_done(); }
+      if (slot == 5) { transform_finish1(WSC - 1, vbuf + (cur ^ 1) * VBUF); raw_load1(WSC - 1); raw_load_done(); }
+    } else {
+      if (slot == 0) transform_read(rbuf + (cur ^ 1) * RBUF);
+      if (slot == 1) { raw_commit1(0, rbuf + cur * RBUF); commit_done(); }
+      if (slot == 2) { transform_finish1(0, vbuf + (cur ^ 1) * VBUF); raw_load1(0); raw_load_done(); }
+    }
+  };
   auto side_slice = [&](int slot, int g, int cur) {
     // Every slice runs in every trip (past the end of the stream it works on stale registers and writes LDS buffers nobody
     // reads; the loads stay inside this sample's planes): a slot is then ONE basic block, and the scheduler can place the
@@ -481,6 +565,44 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       const int c = st * WSC + sc;
       const f32x4* un = up + (size_t)(c + 1 < nch ? c + 1 : 0) * ustride;      // after a tile's last chunk: chunk 0 again
       const float* vb = vbuf + cur * VBUF + sc * 16 * VPOS + vrd;
+      if constexpr (UPZ) {
+        constexpr int CQ[3] = {0, 1, 3};                   // the blocks both halves run
+        f32x4 bq[3];                                       // their B fragments, one position ahead of the MFMAs
+        bq[0] = *reinterpret_cast<const f32x4*>(vb);
+        bq[1] = *reinterpret_cast<const f32x4*>(vb + VPOS);
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          if (i == 0) bq[2] = *reinterpret_cast<const f32x4*>(vb + 3 * VPOS);
+#pragma unroll
+          for (int s = 0; s < 4; ++s) acc[CQ[i]] = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[CQ[i]][s], bq[i][s], acc[CQ[i]], 0, 0, 0);
+          if (!no_u) ua[CQ[i]] = un[CQ[i] * 64];
+          side_slice_upz(sc * 3 + i, cur);
+          if (i == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x486, 2 * WINO_IL_K, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (sc * 3 + i == (WSC == 2 ? 5 : 2)) raw_load_next();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (hf == 0) {                                     // xi = 1: blocks 4, 5, 7 (wave-uniform; the hf = 1 waves' xi = 2 is dead)
+          constexpr int HQ[3] = {4, 5, 7};
+          f32x4 bh[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) bh[i] = *reinterpret_cast<const f32x4*>(vb + HQ[i] * VPOS);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc[HQ[i]] = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[HQ[i]][s], bh[i][s], acc[HQ[i]], 0, 0, 0);
+            if (!no_u) ua[HQ[i]] = un[HQ[i] * 64];
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
       f32x4 b4[2][2];                                      // B fragments of two positions, one pair ahead of the MFMAs
       b4[0][0] = *reinterpret_cast<const f32x4*>(vb);
       b4[0][1] = *reinterpret_cast<const f32x4*>(vb + VPOS);
@@ -520,6 +642,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
         __builtin_amdgcn_sched_barrier(0);
         WINO_SLOT(sc * 4 + qp + (WSC == 1 ? 0 : 0))
       }
+      }
     }
     WINO_STAMP(1)
     __syncthreads();
@@ -553,8 +676,10 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     for (int j = 0; j < 2; ++j) {                          // one pixel column at a time: fewer values live beside the accumulators
       const f32x16 t0 = j == 0 ? acc[0] + acc[1] + acc[2] : acc[1] - acc[2] - acc[3];
       const f32x16 t1 = j == 0 ? acc[4] + acc[5] + acc[6] : acc[5] - acc[6] - acc[7];
-      if (hf == 0) { keep[j] = t0 + t1; send[j] = t1; }
-      else         { keep[j] = -t0 - t1; send[j] = t0; }
+      // UPZ: the hf = 1 waves hold T3 in blocks 0 .. 3 (t0) and the dead T2 = +0 in blocks 4 .. 7 (t1): same expressions, roles swapped
+      if (hf == 0)  { keep[j] = t0 + t1; send[j] = t1; }
+      else if (UPZ) { keep[j] = -t1 - t0; send[j] = t1; }
+      else          { keep[j] = -t0 - t1; send[j] = t0; }
       __builtin_amdgcn_sched_barrier(0);
     }
     // (chunk 0's weights for the next tile came with the stream's reload at this tile's last chunk.  Fetching them AGAIN here --
@@ -695,6 +820,13 @@ static int wino_fold_env() {                                   // MCEDM_WINO_FOL
   if (env < 0) { const char* e = getenv("MCEDM_WINO_FOLD"); env = e ? atoi(e) : 1; }
   return variant_choice(KV_CONV_WINO_FOLD, g_wino_fold, env);
 }
+static int g_wino_upz = -1;  // -1: default (env MCEDM_WINO_UPZ, else on); 0 / 1: forced by mcedm_op_set_conv_wino_upz
+void set_conv_wino_upz(int enable) { g_wino_upz = enable; }
+static int wino_upz_env() {                                    // MCEDM_WINO_UPZ=0: the up-sampling convs run all sixteen positions
+  static int env = -1;
+  if (env < 0) { const char* e = getenv("MCEDM_WINO_UPZ"); env = e ? atoi(e) : 1; }
+  return variant_choice(KV_CONV_WINO_UPZ, g_wino_upz, env);
+}
 static int wino_mode_env() {                                   // MCEDM_WINO_MODE: ablation bits of the -DMCEDM_WINO_TIMELINE build (else unused)
   static int env = -1;                                         // | 256: the interleaved, XCD-aware tile map (MCEDM_WINO_MAP, default on)
   if (env < 0) {
@@ -795,6 +927,8 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
     MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if constexpr (!C::SKIP) {                              // the SKIP variant exists in the plain, activated form only
       MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true, true, WinoUp<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true, true, WinoUp<false>>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     attr_set[dev].store(true, std::memory_order_release);
@@ -805,8 +939,10 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   if (per_env > 0 && tiles_img % per_env == 0) per = per_env;
   char name[64] = "";
   const bool noact = a.resample != RS_UP && !a.act;
-  if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<Wino%sCfg<%d>, %s, %s>", C::SKIP ? "Skip" : "", C::MB, a.resample == RS_UP ? "true" : "false",
-                               noact ? "false" : "true");   // = rocprofv3's name
+  // the zero-position variant (WinoUp: same LDS footprint); 2: with the sixteen-position kernel's staging (the positions alone, A/B runs)
+  const int upz = !C::SKIP && a.resample == RS_UP ? wino_upz_env() : 0;
+  if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<Wino%sCfg<%d>, %s, %s%s>", C::SKIP ? "Skip" : "", C::MB, a.resample == RS_UP ? "true" : "false",
+                               noact ? "false" : "true", upz == 2 ? ", WinoUp<false>" : upz ? ", WinoUp<true>" : "");   // = rocprofv3's name
   const double px = (double)a.B * a.H * a.W;
   const double skc = C::SKIP ? (double)(a.sk_Ca + a.sk_Cb) : 0.0;      // folded 1x1 projection: its own flops, input read and weights
   // algorithmic cost = the direct convolution's (2 * MAC); the kernel issues 4 / 9 of these as matrix flops
@@ -814,6 +950,12 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
                4.0 * ((double)a.B * Cin * a.Hs * a.Ws + px * (a.Cout * (a.res ? 2 : 1) + skc) + (double)a.Cout * (Cin * 9 + skc)), stream);
   if constexpr (C::SKIP)
     hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
+                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+  else if (upz == 2)
+    hipLaunchKernelGGL((conv_wino_kernel<C, true, true, WinoUp<false>>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
+                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+  else if (upz)
+    hipLaunchKernelGGL((conv_wino_kernel<C, true, true, WinoUp<true>>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
                        tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
   else if (a.resample == RS_UP)
     hipLaunchKernelGGL((conv_wino_kernel<C, true>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,

@@ -38,6 +38,35 @@ struct WinoSkipCfg : WinoCfg<MB_> {
   static constexpr int SK_FLOATS = WinoCfg<MB_>::MT + 2 * SKBUF;        // the projection's bias row, two stage buffers
   static_assert(MB_ == 4, "the fold is built for the 128-channel workgroup (512 threads = 16 channels x 32 quads per stage)");
 };
+// The zero-position variant of the UP-SAMPLING kernel (UP == true only; WinoUp below).  The input is the nearest 2x up-sampling of the source and
+// tiles and patches start on even pixels, so the rows (and likewise the columns) of every 4 x 4 input patch are (a, b, b, c) in source
+// pixels -- zero padding is source row / column -1 or Hs / Ws, rows 1 and 2 are always both inside the image.  Under B^T the patch
+// gives xi = 0: a - b, xi = 1: b + b, xi = 2: b - b = +0, xi = 3: b - c, and the same along nu (the negated nu = 2 column is
+// c1 + (-1) c2 = +0): at the SEVEN positions with xi = 2 or nu = 2 V is exactly +0 for every channel, patch and sample.  Their
+// products are +-0, an accumulator that starts at +0 stays +0 under round-to-nearest, and the bias sits at (1, 1): the variant does
+// nothing for them (no weight load, no B-fragment read, no MFMA; nu = 2 is not written to the V tile either) and the epilogue
+// meets the same +0 blocks as before.  PRECONDITION: finite transformed weights (0 * Inf would have been NaN).
+// Blocks are ordered by liveness: hf = 1 keeps xi = 3 in acc[0..3] (xi = 2, dead, in acc[4..7]), so that blocks 0, 1, 3 are what
+// both halves run and blocks 4, 5, 7 (xi = 1) what only the hf = 0 waves run: 6 + 3 of 16 positions per SIMD.
+// SRC: the raw tile is staged at SOURCE resolution -- the 6 x 10 source pixels (4 x 8 plus a halo of one) under the tile's 10 x 18
+// patch: ONE dword load, one (x - mean) * scale + offset -> SiLU evaluation, one mask and one LDS store per lane and channel instead
+// of three -- and the transform reads source rows ty + {0, 1, 2} and columns tx + {0, 1, 2} of patch (ty, tx): patch row r is source
+// row (r + 1) >> 1 of the staged patch.  It evaluates the same expressions on the same values (Y - X, X + s Z down the rows;
+// c0 - c2, c1 + c2, c1 - c3 along the columns), hence the same bits.  SRC = false keeps the element-by-element staging of the
+// sixteen-position kernel (the positions alone: switch value 2, kept for A/B runs).
+// A TAG behind the kernel's own template arguments -- conv_wino_kernel<WinoCfg<MB>, true, true, WinoUp<SRC>> --: an instantiation and a
+// profiler name of its own (KV_CONV_WINO_UPZ picks it) that still reads as the up-sampling kernel of WinoCfg<MB>; without a tag (every
+// other instantiation) the kernel and its name are what they were.
+template <bool SRC>
+struct WinoUp {};
+template <class... Tag>
+struct WinoUpTraits { static constexpr bool UPZ = false, UPS = false; static_assert(sizeof...(Tag) == 0, "one tag at most: WinoUp<SRC>"); };
+template <bool SRC>
+struct WinoUpTraits<WinoUp<SRC>> { static constexpr bool UPZ = true, UPS = SRC; };
+constexpr int UROWS = WPH / 2 + 2, UCOLS = WPW / 2 + 2;   // source patch of a tile: 6 x 10
+constexpr int UPLANE = 68;                       // floats between its channels (60 used; lanes 60 .. 63 store into the pad); = 4 mod 32: the
+                                                 // transform's dword reads (eight channels x four patch columns per 32 lanes) cover the 32 banks once
+static_assert(UPLANE >= 64 && UPLANE % 32 == 4 && UPLANE <= 196, "LDS layout");
 constexpr int RROWS = WPH + 2, RPITCH = WPW + 2; // raw tile with halo: 10 x 18
 constexpr int RPLANE = 196;                      // floats between channels of the raw tile (180 used); = 4 mod 32: hipcc merges the transform's two
                                                  // adjacent 8-byte reads into ds_read2_b64, which banks at dword mod 32 over 16-lane groups = eight

@@ -79,6 +79,25 @@ extern "C" int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int 
   return launch_conv_wino(a, (hipStream_t)stream);
 }
 
+// mcedm_op_conv_wino with the fused GroupNorm records of `out` in gsum (4-channel blocks, as a plan's convs write them)
+extern "C" int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
+                                       int act, int resample, int H, int W, const float* wino, const float* bias, const float* res,
+                                       int res_mode, float* out, float* gsum, int Cout, int B, void* stream) {
+  MCEDM_REQUIRE((resample == RS_NONE || resample == RS_UP) && (res_mode == RS_NONE || res_mode == RS_UP || res_mode == RS_DOWN),
+                "op_conv_wino_sums: resample must be 0 (none) or 1 (nearest-2x up), res_mode 0, 1 or 2 (2x2-mean down)");
+  MCEDM_REQUIRE(gsum, "op_conv_wino_sums: gsum is null");
+  ConvArgs a{};
+  a.xa = xa; a.xb = xb; a.Ca = Ca; a.Cb = Cb;
+  a.coef = reinterpret_cast<const Coef*>(coef); a.coef_batch = coef_batch; a.act = act;
+  a.resample = resample; a.H = H; a.W = W;
+  a.Hs = resample == RS_UP ? H / 2 : H; a.Ws = resample == RS_UP ? W / 2 : W;
+  a.wino = wino; a.bias = bias; a.res = res; a.res_mode = res_mode;
+  SumTiles st;
+  a.out = out; a.Cout = Cout; a.B = B; a.gsum = gsum; a.gsum_tiles = &st;
+  MCEDM_REQUIRE(conv_wino_applicable(a, 9), "op_conv_wino_sums: needs Cout %% 64 == 0, H %% 8 == 0, W %% 16 == 0, Cin %% 8 == 0 and 16-byte aligned inputs / weight table");
+  return launch_conv_wino(a, (hipStream_t)stream);
+}
+
 // A 1x1 conv's weights [Cout][Cin] in the MFMA-fragment order of ConvArgs::sk_wfrag (cout_padded(Cout) * ceil8(Cin) floats)
 extern "C" int mcedm_op_pack_conv_frag(const float* w, int Cout, int Cin, float* wfrag, void* stream) {
   return launch_pack_conv_frag(w, wfrag, Cout, Cin, (hipStream_t)stream);
@@ -205,6 +224,11 @@ extern "C" int mcedm_op_set_conv_wino1(int enable) {
 
 extern "C" int mcedm_op_set_conv_wino_fold(int enable) {
   set_conv_wino_fold(enable);
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_op_set_conv_wino_upz(int enable) {
+  set_conv_wino_upz(enable);
   return MCEDM_OK;
 }
 

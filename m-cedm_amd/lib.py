@@ -53,7 +53,7 @@ SAMPLER_STEMS = {
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
 VARIANTS = {"conv_wino": 0, "conv_wino1": 1, "conv_resident": 2, "conv8": 3, "attn_fused": 4, "wgrad_wino": 5, "conv1x1_reg": 6,
-            "conv_wino_fold": 7}
+            "conv_wino_fold": 7, "conv_wino_upz": 8}
 
 
 class UNetDesc(C.Structure):
@@ -1311,6 +1311,7 @@ def _bind_ops():
     lib.mcedm_op_pack_conv_wino.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
+    lib.mcedm_op_conv_wino_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
     lib.mcedm_op_pack_conv_frag.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_skip.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]
     f32 = C.c_float
@@ -1320,7 +1321,7 @@ def _bind_ops():
                                                 i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
-              "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"):
+              "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1332,7 +1333,7 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
-              "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"]
+              "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1391,6 +1392,15 @@ def set_conv_wino_fold(enable: int = -1) -> None:
     lib = _bind_ops()
     lib.mcedm_op_set_conv_wino_fold.argtypes = [C.c_int]
     check(lib.mcedm_op_set_conv_wino_fold(int(enable)), "set_conv_wino_fold")
+
+
+def set_conv_wino_upz(enable: int = -1) -> None:
+    """The up-sampling Winograd convs skip the seven positions whose transformed input is exactly zero and stage their input at source
+    resolution (conv_wino.hip, WinoUp): 1 / 0 (all sixteen positions); 2 = the positions alone, on the sixteen-position kernel's
+    staging (A/B runs); -1 = default (on).  Same bits in every form."""
+    lib = _bind_ops()
+    lib.mcedm_op_set_conv_wino_upz.argtypes = [C.c_int]
+    check(lib.mcedm_op_set_conv_wino_upz(int(enable)), "set_conv_wino_upz")
 
 
 def set_wgrad_wino(enable: int = -1) -> None:
@@ -1481,13 +1491,19 @@ def op_pack_conv_wino(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
 
 
 def op_conv_wino(xa, xb, wino, bias, Cout, coef=None, coef_batch=1, act=0, resample=RS_NONE, res=None, res_mode=RS_NONE,
-                 out=None):
+                 out=None, want_sums=False):
+    """want_sums: -> (out, the fused GroupNorm records of out as a plan's convs write them)."""
     lib = _bind_ops()
     B, Ca, Hs, Ws = xa.shape
     Cb = xb.shape[1] if xb is not None else 0
     H, W = (Hs * 2, Ws * 2) if resample == RS_UP else (Hs, Ws)
     if out is None:
         out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=xa.device)
+    if want_sums:
+        gsum = torch.zeros(B * ((H + 3) // 4) * ((W + 7) // 8) * ((Cout + 3) // 4) * 2, dtype=torch.float32, device=xa.device)
+        check(lib.mcedm_op_conv_wino_sums(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, H, W, _ptr(wino),
+                                          _ptr(bias), _ptr(res), res_mode, _ptr(out), _ptr(gsum), Cout, B, _stream()), "op_conv_wino_sums")
+        return out, gsum
     check(lib.mcedm_op_conv_wino(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, H, W, _ptr(wino),
                                  _ptr(bias), _ptr(res), res_mode, _ptr(out), Cout, B, _stream()), "op_conv_wino")
     return out
