@@ -440,6 +440,13 @@ int mcedm_op_embedding(const float* labels, int n, int ch, const float* w0, cons
 /* a = softmax(q^T k / sqrt(64)) v per (sample, head) (models/adm_blocks.py:103-109,174-178);
  * qkv is [B][heads][3][64][T] (the packed qkv conv's output), out [B][heads*64][T]. */
 int mcedm_op_attention(const float* qkv, float* out, int B, int heads, int T, void* stream);
+/* The whole attention part of a 64-channel UNetBlock at 8 x 8 in one launch (models/adm_blocks.py:174-180):
+ * z = proj(attention(qkv(group_norm(y)))) + y, y and z [B][64][8][8], 16 groups, one head.  wq_pk / bq_pk: mcedm_op_pack_conv of
+ * qkv.weight / qkv.bias with qkv_heads = 1; wp_pk / bp_pk: the same of proj with qkv_heads = 0.  gsum: NULL, or B * 16 * 2 floats
+ * that receive the fused GroupNorm records (sum, M2 about the group mean) of z per 4-channel group.  Always the fused kernel:
+ * the plan's dispatch (MCEDM_ATTN_FUSED, mcedm_op_set_attn_fused) does not apply, as for mcedm_op_attention. */
+int mcedm_op_attn_block64(const float* y, const float* gamma, const float* beta, float eps, const float* wq_pk,
+                          const float* bq_pk, const float* wp_pk, const float* bp_pk, float* z, float* gsum, int B, void* stream);
 /* Backward building blocks.
  * conv weight / bias gradient: dw [Cout, Cin, k, k], db [Cout] (may be NULL) for the conv described as in mcedm_op_conv
  * (the transformed input is rebuilt into the scratch first); scratch holds mcedm_op_wgrad_scratch_floats() floats; qkv_heads > 0:

@@ -145,6 +145,15 @@ extern "C" int mcedm_op_attention(const float* qkv, float* out, int B, int heads
   return launch_attention(qkv, out, B, heads, T, (hipStream_t)stream);
 }
 
+// The fused 8 x 8 x 64 attention block (attn_fused.hip) on its own, whatever MCEDM_ATTN_FUSED / mcedm_op_set_attn_fused say
+extern "C" int mcedm_op_attn_block64(const float* y, const float* gamma, const float* beta, float eps, const float* wq_pk,
+                                     const float* bq_pk, const float* wp_pk, const float* bp_pk, float* z, float* gsum, int B,
+                                     void* stream) {
+  MCEDM_REQUIRE(y && z && gamma && beta && wq_pk && bq_pk && wp_pk && bp_pk, "op_attn_block64: null pointer");
+  MCEDM_REQUIRE(B > 0, "op_attn_block64: B = %d", B);
+  return launch_attn_block64(y, z, gamma, beta, eps, 16, wq_pk, bq_pk, wp_pk, bp_pk, gsum, nullptr, B, (hipStream_t)stream);
+}
+
 extern "C" int mcedm_op_set_conv_tile(int mt, int ph, int pw) {
   set_conv_tile_override(mt, ph, pw);
   return MCEDM_OK;

@@ -1296,6 +1296,7 @@ def _bind_ops():
     lib.mcedm_op_conv.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32,
                                   i32, i32, vp]
     lib.mcedm_op_attention.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.mcedm_op_attn_block64.argtypes = [vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.mcedm_op_embedding.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.mcedm_op_wgrad_scratch_floats.argtypes = [i32, i32, i32, i32, i32, i32]
     lib.mcedm_op_wgrad_scratch_floats.restype = sz
@@ -1321,7 +1322,8 @@ def _bind_ops():
                                                 i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
-              "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"):
+              "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
+              "mcedm_op_attn_block64"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1333,7 +1335,8 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
-              "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip"]
+              "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
+              "mcedm_op_attn_block64"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1551,6 +1554,21 @@ def op_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     out = torch.empty((B, C3 // 3, H, W), dtype=torch.float32, device=qkv.device)
     check(lib.mcedm_op_attention(_ptr(qkv), _ptr(out), B, heads, H * W, _stream()), "op_attention")
     return out
+
+
+def op_attn_block(y, gamma, beta, wq_pk, bq_pk, wp_pk, bp_pk, eps=1e-5, want_sums=False):
+    """The fused 8 x 8 x 64 attention block (attn_block64_kernel) on its own: z = proj(attention(qkv(group_norm(y)))) + y for
+    y [B, 64, 8, 8].  wq_pk, bq_pk = op_pack_conv(qkv.weight, qkv.bias, qkv_heads=1); wp_pk, bp_pk = op_pack_conv(proj.weight,
+    proj.bias).  want_sums: -> (z, gsum [B, 16, 2]), the fused GroupNorm records (sum, M2) of z per 4-channel group."""
+    lib = _bind_ops()
+    if y.dim() != 4 or tuple(y.shape[1:]) != (64, 8, 8):
+        raise RuntimeError(f"op_attn_block: y must be [B, 64, 8, 8], got {tuple(y.shape)}")
+    B = y.shape[0]
+    z = torch.empty_like(y)
+    gsum = torch.zeros((B, 16, 2), dtype=torch.float32, device=y.device) if want_sums else None
+    check(lib.mcedm_op_attn_block64(_ptr(y), _ptr(gamma), _ptr(beta), eps, _ptr(wq_pk), _ptr(bq_pk), _ptr(wp_pk), _ptr(bp_pk),
+                                    _ptr(z), _ptr(gsum), B, _stream()), "op_attn_block64")
+    return (z, gsum) if want_sums else z
 
 
 def op_conv_wgrad(dy, xa, xb, k, coef=None, coef_batch=1, act=0, resample=RS_NONE, qkv_heads=0):

@@ -13,6 +13,7 @@ import torch
 
 from oracle import fixtures as fx
 from oracle import mcedm_oracle as orc
+from tests._attn_block import dev, hip_block
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +27,6 @@ def lib():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     L.load()
     return L
-
-
-def dev(t):
-    return t.contiguous().cuda()
 
 
 def close(got, ref, rtol=RTOL, atol=ATOL, what=""):
@@ -404,37 +401,6 @@ def test_attention_online_softmax_rescale(lib):
 
 
 # ------------------------------------------------------------------ whole blocks out of the ops
-def hip_block(L, P, spec, x, emb):
-    """adm_blocks.py:159-181 composed from the kernel-level entry points (mirrors csrc/plan.hip run_block)."""
-    k = spec.key
-    g = lambda n: dev(P[f"{k}.{n}"])
-    n_emb = emb.shape[0]
-    film = dev(orc.linear(emb, P[f"{k}.affine.weight"], P[f"{k}.affine.bias"]))
-    rs = L.RS_UP if spec.up else (L.RS_DOWN if spec.down else L.RS_NONE)
-    xd = dev(x)
-    c0 = L.op_gn_coef(xd, None, g("norm0.weight"), g("norm0.bias"))
-    w0, b0 = L.op_pack_conv(g("conv0.weight"), g("conv0.bias"))
-    h = L.op_conv(xd, None, w0, b0, spec.cout, 3, coef=c0, act=1, resample=rs)
-    c1 = L.op_gn_coef(h, None, g("norm1.weight"), g("norm1.bias"), film=film, film_batch=int(n_emb > 1),
-                      film_stride=2 * spec.cout)
-    res, mode = xd, L.RS_NONE
-    if spec.skip_kernel == 1:
-        ws, bs = L.op_pack_conv(g("skip.weight"), g("skip.bias"))
-        res = L.op_conv(xd, None, ws, bs, spec.cout, 1, resample=rs)
-    elif spec.skip_kernel == 0:
-        mode = rs
-    w1, b1 = L.op_pack_conv(g("conv1.weight"), g("conv1.bias"))
-    y = L.op_conv(h, None, w1, b1, spec.cout, 3, coef=c1, act=1, res=res, res_mode=mode)
-    if not spec.attn:
-        return y
-    c2 = L.op_gn_coef(y, None, g("norm2.weight"), g("norm2.bias"))
-    wq, bq = L.op_pack_conv(g("qkv.weight"), g("qkv.bias"), qkv_heads=spec.heads)
-    qkv = L.op_conv(y, None, wq, bq, 3 * spec.cout, 1, coef=c2)
-    a = L.op_attention(qkv, spec.heads)
-    wp, bp = L.op_pack_conv(g("proj.weight"), g("proj.bias"))
-    return L.op_conv(a, None, wp, bp, spec.cout, 1, res=y)
-
-
 @pytest.mark.parametrize("tag", list(fx.BLOCK_CASES))
 @pytest.mark.parametrize("n_emb", [1, 2])
 def test_unet_block_golden(lib, golden, tag, n_emb):
@@ -513,6 +479,29 @@ def test_fused_groupnorm_statistics_with_large_means(lib):
     assert ratio > 40, ratio
     close(plan.forward(packed, dev(x), dev(lab), cond=dev(cond)), ref, what=f"large-mean fused GN (|mean|/std = {ratio:.0f})")
     close(plan.forward(packed, dev(x), dev(lab), cond=dev(cond), training=True), ref, what="large-mean GN, training layout")
+
+
+def test_fused_attention_block_with_large_means(lib):
+    """The same at 32 x 32, where the attention level is 8 x 8: the large means reach attn_block64_kernel (its GroupNorm in
+    registers, and the records of z it writes for the next conv0), which the 40 x 24 inputs above never launch."""
+    plan = make_plan(lib, fx.CFG_P)
+    P = {k: v.clone() for k, v in orc.make_params(fx.CFG_P, 7).items()}
+    P["enc.32x32_block0.conv1.bias"] = 30.0 + 0.05 * fx.randn("t/bigmean32/b0", 64)
+    P["dec.32x32_in0.conv1.bias"] = -25.0 + 0.05 * fx.randn("t/bigmean32/b1", 64)
+    packed = plan.pack({k: dev(v) for k, v in P.items()})
+    x, cond = fx.randn("t/bigmean32/x", 3, 2, 32, 32), fx.randn("t/bigmean32/c", 3, 2, 32, 32)
+    lab = torch.tensor([0.4])
+    with torch.no_grad():
+        ref = orc.unet_forward(P, fx.CFG_P, x, lab, cond)
+    lib.prof_enable(True)
+    try:
+        F = plan.forward(packed, dev(x), dev(lab), cond=dev(cond))
+        names = [r["name"] for r in lib.prof_report()]
+    finally:
+        lib.prof_enable(False)
+    assert "attn_block64_kernel" in names and "attention_kernel" not in names, names
+    close(F, ref, what="large means through the fused attention block")
+    close(plan.forward(packed, dev(x), dev(lab), cond=dev(cond), training=True), ref, what="large means, training layout (three launches)")
 
 
 def test_embedding_kernel_golden(lib, golden):
