@@ -705,41 +705,81 @@ static DHeader dheader(const mcedm_ddpm_plan& P, int B, int H, int W) {
   h.total = cur;
   return h;
 }
+static size_t state_floats(const mcedm_ddpm_plan& P, int B) {
+  return (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
+}
+static size_t map_bytes(const mcedm_ddpm_plan& P, int B) {
+  return (size_t)B * P.desc.ch * P.desc.resolution * P.desc.resolution * sizeof(float);
+}
 
-// Model.forward (ddim_blocks.py:410-470) with dx None; cond enters as cond_map (null: None) on a plan with the head, as cond_cat
-// [B, cat_channels, R, R] (null: None, zeros) on a cat_cond plan; the input is scaled by the rows of coef_in (null = identity)
-// while conv_in stages it.  `act` = start of the activation region.  Returns the peak bytes in *peak.
-static int ddpm_forward(const mcedm_ddpm_plan& P, bool dry, const float* pk, const float* x, const Coef* coef_in, float t,
-                        float* bias_table, float* out, char* act, int B, hipStream_t s, size_t* peak,
-                        const float* x_self_cond = nullptr, const float* cond_map = nullptr, const float* cond_cat = nullptr) {
+// One evaluation's inputs.  The input is scaled by the rows of coef_in (null = identity) while conv_in stages it; cond enters
+// as cond_map (null: None) on a plan with the head, as cond_cat [B, cat_channels, R, R] (null: None, zeros) on a cat_cond plan.
+struct DdpmIn {
+  const float* x = nullptr;
+  float t = 0.f;
+  const Coef* coef_in = nullptr;
+  const float* self_cond = nullptr;
+  const float* cond_map = nullptr;
+  const float* cond_cat = nullptr;
+};
+
+// A plan bound to its packed weights, its region of a workspace (header, then activations), a batch size and a stream
+struct DdpmNet {
+  const mcedm_ddpm_plan* plan = nullptr;
+  const float* pk = nullptr;
+  DHeader hd{};
+  char* ws = nullptr;         // start of the network's region
+  int B = 0;
+  hipStream_t s = nullptr;
+  int ddpm_forward(bool dry, const DdpmIn& in, float* out, size_t* peak) const;      // the schedule; dry: sizes only
+  int forward(const DdpmIn& in, float* out) const { return ddpm_forward(false, in, out, nullptr); }
+  // F <- the network on `in`; Fu (unless null) <- the same without its conditioning: the two passes of classifier-free guidance
+  int forward_cfg(DdpmIn in, float* F, float* Fu) const {
+    const int rc = forward(in, F);
+    if (rc || !Fu) return rc;
+    in.cond_map = in.cond_cat = nullptr;
+    return forward(in, Fu);
+  }
+  float* F() const { return at<float>(ws, hd.F); }
+  float* Fu() const { return at<float>(ws, hd.Fu); }
+  Coef* coef_in() const { return at<Coef>(ws, hd.coef_in); }
+  // the rows of coef_in <- c_in on the state channels, identity on what conv_in reads in front of them
+  int scale_input(float c_in) const { return launch_vp_coef(c_in, plan->in_total - plan->desc.in_channels, plan->desc.in_channels, coef_in(), s); }
+  size_t state() const { return state_floats(*plan, B); }
+};
+
+// Model.forward (ddim_blocks.py:410-470) with dx None.  Returns the peak bytes of the activation region in *peak.
+int DdpmNet::ddpm_forward(bool dry, const DdpmIn& in, float* out, size_t* peak) const {
+  const mcedm_ddpm_plan& P = *plan;
   const mcedm_ddpm_desc& d = P.desc;
   const int R = d.resolution, L = d.n_levels;
+  float* bias_table = dry ? nullptr : at<float>(ws, hd.bias);
   int rc;
   if (!dry) {
     int nsplit = P.rows / 32; if (nsplit < 1) nsplit = 1; if (nsplit > 64) nsplit = 64;
     const int ch = d.ch;
-    hipLaunchKernelGGL(ddpm_temb_kernel, dim3(nsplit), dim3(TEMB_NT), (size_t)(ch + 8 * ch) * sizeof(float), s, t, ch, pk + P.freqs,
+    hipLaunchKernelGGL(ddpm_temb_kernel, dim3(nsplit), dim3(TEMB_NT), (size_t)(ch + 8 * ch) * sizeof(float), s, in.t, ch, pk + P.freqs,
                        pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1, pk + P.tproj_w, pk + P.tproj_b, pk + P.c1bias, P.rows, bias_table);
     MCEDM_LAUNCH_CHECK("ddpm_temb_kernel");
   }
-  DExec E{P, dry, act, pk, s, B, Pool(), {}};
+  DExec E{P, dry, dry ? nullptr : at<char>(ws, hd.total), pk, s, B, Pool(), {}};
   E.t.reserve(4096);        // ConvArgs::gsum_tiles points into this vector during a launch
   // conv_in on cat(x_self_cond = zeros, x): the self-conditioning half is a null source (reads as zeros); on a cat_cond plan
   // (no self-conditioning there) the first source is the conditioning instead, cat(cond, x)
   const int n_self = P.in_total - d.in_channels;
-  const float* front = P.cat_channels > 0 ? cond_cat : x_self_cond;
+  const float* front = P.cat_channels > 0 ? in.cond_cat : in.self_cond;
   std::vector<int> hs;
   {
     const int h0 = E.act(d.ch, R, R, true);
     ConvArgs ci{};
-    ci.xa = front; ci.Ca = n_self; ci.xb = x; ci.Cb = d.in_channels;             // a null first source reads as zeros
-    if (n_self == 0) { ci.xa = x; ci.Ca = d.in_channels; ci.xb = nullptr; ci.Cb = 0; }
-    ci.coef = coef_in; ci.coef_batch = 0; ci.act = 0;
+    ci.xa = front; ci.Ca = n_self; ci.xb = in.x; ci.Cb = d.in_channels;          // a null first source reads as zeros
+    if (n_self == 0) { ci.xa = in.x; ci.Ca = d.in_channels; ci.xb = nullptr; ci.Cb = 0; }
+    ci.coef = in.coef_in; ci.coef_batch = 0; ci.act = 0;
     ci.Hs = R; ci.Ws = R; ci.H = R; ci.W = R;
     dst_of(E, ci, h0, P.conv_in, nullptr, true);
     // the head: conv_in holds the folded weights; with cond the map (which carries its own bias) enters as the residual, in
     // front of the statistics; without it (cond None: zero features, not cond_enc(0)) the folded bias Wx b_in + b_comb alone
-    if (cond_map) { ci.bias = nullptr; ci.res = cond_map; ci.res_mode = RS_NONE; }
+    if (in.cond_map) { ci.bias = nullptr; ci.res = in.cond_map; ci.res_mode = RS_NONE; }
     if ((rc = run_conv(E, ci, 9, h0))) return rc;
     hs.push_back(h0);
   }
@@ -810,24 +850,40 @@ static int ddpm_forward(const mcedm_ddpm_plan& P, bool dry, const float* pk, con
   return MCEDM_OK;
 }
 
-static int ddpm_sizes(const mcedm_ddpm_plan& P, int B, DHeader* hd, size_t* act_bytes) {
+// *net <- (P, B, header offsets), *bytes <- what the network needs of a workspace: header + peak of the activations
+static int ddpm_sizes(const mcedm_ddpm_plan& P, int B, DdpmNet* net, size_t* bytes) {
   MCEDM_REQUIRE(B > 0, "ddpm: empty batch");
-  *hd = dheader(P, B, P.desc.resolution, P.desc.resolution);
-  return ddpm_forward(P, true, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, B, nullptr, act_bytes);
+  *net = DdpmNet{&P, nullptr, dheader(P, B, P.desc.resolution, P.desc.resolution), nullptr, B, nullptr};
+  size_t act = 0;
+  const int rc = net->ddpm_forward(true, DdpmIn{}, nullptr, &act);
+  if (rc == MCEDM_OK) *bytes = net->hd.total + act;
+  return rc;
+}
+
+// The one place that knows the workspace layout: `front_bytes` of the caller's own buffers (a sampler's), then the network's
+// header and activations.  `who` names the entry in the message of a workspace that is too small.
+static int ddpm_bind(const char* who, const mcedm_ddpm_plan& P, const void* packed, void* workspace, size_t workspace_bytes,
+                     size_t front_bytes, int B, void* stream, DdpmNet* net) {
+  int rc;
+  size_t need = 0;
+  if ((rc = ddpm_sizes(P, B, net, &need))) return rc;
+  if ((rc = heun_check_workspace(who, workspace_bytes, front_bytes + need))) return rc;
+  net->pk = (const float*)packed; net->ws = at<char>(workspace, front_bytes); net->s = (hipStream_t)stream;
+  return MCEDM_OK;
 }
 
 // get_denoised (ddim.py:915-947): D = x + (-sigma) F(c_in x, c_noise), sigma and c_noise host scalars
-static int ddpm_denoise_impl(const mcedm_ddpm_plan& P, const DHeader& hd, const float* pk, const float* x, float sigma,
-                             float c_noise, float* D_out, float* F_out, void* ws, int B, hipStream_t s) {
+static int ddpm_denoise_impl(const DdpmNet& net, const float* x, float sigma, float c_noise, float* D_out, float* F_out) {
+  const mcedm_ddpm_plan& P = *net.plan;
   int rc;
   const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                 // 1 / (sigma ** 2 + 1).sqrt(), fp32
-  Coef* coef_in = at<Coef>(ws, hd.coef_in);
-  const int n_self = P.in_total - P.desc.in_channels;
-  if ((rc = launch_vp_coef(c_in, n_self, P.desc.in_channels, coef_in, s))) return rc;
-  float* F = F_out ? F_out : at<float>(ws, hd.F);
-  if ((rc = ddpm_forward(P, false, pk, x, coef_in, c_noise, at<float>(ws, hd.bias), F, at<char>(ws, hd.total), B, s, nullptr))) return rc;
-  const size_t total = (size_t)B * P.desc.out_channels * P.desc.resolution * P.desc.resolution;
-  return launch_vp_finish(x, F, sigma, total, D_out, s);
+  DdpmIn in{x, c_noise};
+  in.coef_in = net.coef_in();
+  if ((rc = net.scale_input(c_in))) return rc;
+  float* F = F_out ? F_out : net.F();
+  if ((rc = net.forward(in, F))) return rc;
+  const size_t total = (size_t)net.B * P.desc.out_channels * P.desc.resolution * P.desc.resolution;
+  return launch_vp_finish(x, F, sigma, total, D_out, net.s);
 }
 
 // round_sigma (ddim.py:949-957): nearest entry of edm_steps in fp32; ties resolve to the lower index like argmin
@@ -841,28 +897,36 @@ static int nearest_step(const float* steps, int n, float sigma) {
   return best;
 }
 
+
+// a size query: the caller's own buffers (bufs_of(plan, B).total bytes, a sampler's) in front of the network's workspace
+template <class BufsOf>
+static int workspace_query(const char* who, const mcedm_ddpm_plan* plan, int B, size_t* bytes, BufsOf bufs_of) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "%s: null argument", who);
+  DdpmNet net;
+  const int rc = ddpm_sizes(*plan, B, &net, bytes);
+  if (rc == MCEDM_OK) *bytes += bufs_of(*plan, B).total;
+  return rc;
+}
+
+// what the four forward entries do behind their own argument checks
+static int forward_entry(const char* who, const mcedm_ddpm_plan* plan, const void* packed, const DdpmIn& in, float* out,
+                         void* workspace, size_t workspace_bytes, int B, void* stream) {
+  DdpmNet net;
+  const int rc = ddpm_bind(who, *plan, packed, workspace, workspace_bytes, 0, B, stream, &net);
+  return rc ? rc : net.forward(in, out);
+}
 }  // namespace mcedm
 
 extern "C" int mcedm_ddpm_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "ddpm_workspace_bytes: null argument");
-  DHeader hd; size_t act = 0;
-  int rc = ddpm_sizes(*plan, B, &hd, &act);
-  if (rc) return rc;
-  *bytes = hd.total + act;
-  return MCEDM_OK;
+  return workspace_query("ddpm_workspace_bytes", plan, B, bytes, [](const mcedm_ddpm_plan&, int) { return HeunBufs{}; });
 }
 
 extern "C" int mcedm_ddpm_forward(const mcedm_ddpm_plan* plan, const void* packed, const float* x, float t, float* out,
                                   void* workspace, size_t workspace_bytes, int B, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward: null argument");
-  DHeader hd; size_t act = 0;
-  int rc = ddpm_sizes(*plan, B, &hd, &act);
-  if (rc) return rc;
-  if (hd.total + act > workspace_bytes) { set_error("ddpm_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, hd.total + act); return MCEDM_ERR_WORKSPACE; }
-  return ddpm_forward(*plan, false, (const float*)packed, x, nullptr, t, at<float>(workspace, hd.bias), out,
-                      at<char>(workspace, hd.total), B, (hipStream_t)stream, nullptr);
+  return forward_entry("ddpm_forward", plan, packed, DdpmIn{x, t}, out, workspace, workspace_bytes, B, stream);
 }
 
 extern "C" int mcedm_ddpm_forward_sc(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
@@ -870,29 +934,24 @@ extern "C" int mcedm_ddpm_forward_sc(const mcedm_ddpm_plan* plan, const void* pa
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_sc: null argument");
   MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_sc: the network was built without self-conditioning channels");
-  DHeader hd; size_t act = 0;
-  int rc = ddpm_sizes(*plan, B, &hd, &act);
-  if (rc) return rc;
-  if (hd.total + act > workspace_bytes) { set_error("ddpm_forward_sc: workspace too small (%zu < %zu bytes)", workspace_bytes, hd.total + act); return MCEDM_ERR_WORKSPACE; }
-  return ddpm_forward(*plan, false, (const float*)packed, x, nullptr, t, at<float>(workspace, hd.bias), out,
-                      at<char>(workspace, hd.total), B, (hipStream_t)stream, nullptr, x_self_cond);
+  DdpmIn in{x, t};
+  in.self_cond = x_self_cond;
+  return forward_entry("ddpm_forward_sc", plan, packed, in, out, workspace, workspace_bytes, B, stream);
 }
 
 extern "C" int mcedm_ddpm_denoise(const mcedm_ddpm_plan* plan, const void* packed, const float* x, float sigma, float c_noise,
                                   float* D_out, float* F_out, void* workspace, size_t workspace_bytes, int B, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && packed && x && D_out && workspace, "ddpm_denoise: null argument");
-  DHeader hd; size_t act = 0;
-  int rc = ddpm_sizes(*plan, B, &hd, &act);
-  if (rc) return rc;
-  if (hd.total + act > workspace_bytes) { set_error("ddpm_denoise: workspace too small (%zu < %zu bytes)", workspace_bytes, hd.total + act); return MCEDM_ERR_WORKSPACE; }
-  return ddpm_denoise_impl(*plan, hd, (const float*)packed, x, sigma, c_noise, D_out, F_out, workspace, B, (hipStream_t)stream);
+  DdpmNet net;
+  const int rc = ddpm_bind("ddpm_denoise", *plan, packed, workspace, workspace_bytes, 0, B, stream, &net);
+  return rc ? rc : ddpm_denoise_impl(net, x, sigma, c_noise, D_out, F_out);
 }
 
 namespace mcedm {
 struct RBufs : HeunBufs { size_t mask; };
 static RBufs rbufs(const mcedm_ddpm_plan& P, int B) {
-  const size_t n = (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
+  const size_t n = state_floats(P, B);
   RBufs r{heun_bufs(n), 0};
   r.mask = heun_take(r, n * 4);
   return r;
@@ -919,11 +978,7 @@ static int launch_repaint_mask(float* m, int C, int R, const Desc* sp, size_t to
 }  // namespace mcedm
 
 extern "C" int mcedm_repaint_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "repaint_workspace_bytes: null argument");
-  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
-  if (rc == MCEDM_OK) *bytes += rbufs(*plan, B).total;
-  return rc;
+  return workspace_query("repaint_workspace_bytes", plan, B, bytes, rbufs);
 }
 
 extern "C" int mcedm_repaint_schedule(const mcedm_repaint_desc* sp, double* t_steps) {
@@ -959,15 +1014,12 @@ static int repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, const m
   const int S = P.desc.resolution;
   std::vector<double> t(N + 1);
   if ((rc = mcedm_repaint_schedule(sp, t.data()))) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
   const RBufs rb = rbufs(P, B);
-  if ((rc = heun_check_workspace("repaint_sample", workspace_bytes, rb.total + hd.total + act))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
+  DdpmNet net;
+  if ((rc = ddpm_bind("repaint_sample", P, packed, workspace, workspace_bytes, rb.total, B, stream, &net))) return rc;
+  hipStream_t s = net.s;
   HeunState h = heun_state(workspace, rb, B, P.desc.in_channels, (size_t)S * S, N, return_last, out, s);
   float* mask = at<float>(workspace, rb.mask);
-  void* uws = at<char>(workspace, rb.total);
   const size_t total = h.total;
 
   auto alpha = [&](double tt) -> float {          // compute_alpha(t.long()) (ddim.py:700-704): the SIGMA is the index
@@ -980,7 +1032,7 @@ static int repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, const m
   auto denoise = [&](double sg, bool) -> int {    // get_denoised at a scalar sigma: c_noise = n - 1 - index(sigma)
     const float s32 = (float)sg;
     const float cn = (float)(n - 1 - nearest_step(sp->edm_steps, n, s32));
-    return ddpm_denoise_impl(P, hd, pk, h.x32, s32, cn, h.D, nullptr, uws, B, s);
+    return ddpm_denoise_impl(net, h.x32, s32, cn, h.D, nullptr);
   };
 
   if ((rc = launch_repaint_mask(mask, h.C, S, sp, total, s))) return rc;
@@ -1058,20 +1110,14 @@ namespace mcedm {
 struct DdimBufs { size_t xt, x0, et, mask, total; };
 static DdimBufs ddim_bufs(const mcedm_ddpm_plan& P, int B) {
   DdimBufs r{};
-  const size_t n = (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
+  const size_t n = state_floats(P, B);
   r.xt = heun_take(r, n * 4); r.x0 = heun_take(r, n * 4); r.et = heun_take(r, n * 4); r.mask = heun_take(r, n * 4);
   return r;
 }
 }  // namespace mcedm
 
 extern "C" int mcedm_ddim_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "ddim_workspace_bytes: null argument");
-  size_t u = 0;
-  int rc = mcedm_ddpm_workspace_bytes(plan, B, &u);
-  if (rc) return rc;
-  *bytes = ddim_bufs(*plan, B).total + u;
-  return MCEDM_OK;
+  return workspace_query("ddim_workspace_bytes", plan, B, bytes, ddim_bufs);
 }
 
 // (the timestep sequence itself, ddim_timestep_seq, is shared with the conditional sampler: edm.hpp)
@@ -1105,20 +1151,17 @@ static int ddim_repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, co
   // the timestep sequence (ddim.py:823-830) and its predecessor list (:845)
   std::vector<int> seq = ddim_timestep_seq(n, N, sp->skip_type);
   const int S = (int)seq.size();
-  DHeader hd; size_t act = 0;
   int rc;
-  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
   const DdimBufs db = ddim_bufs(P, B);
-  if ((rc = heun_check_workspace("ddim_repaint_sample", workspace_bytes, db.total + hd.total + act))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
+  DdpmNet net;
+  if ((rc = ddpm_bind("ddim_repaint_sample", P, packed, workspace, workspace_bytes, db.total, B, stream, &net))) return rc;
+  hipStream_t s = net.s;
   float* xt = at<float>(workspace, db.xt);
   float* x0 = at<float>(workspace, db.x0);
   float* et = at<float>(workspace, db.et);
   float* mask = at<float>(workspace, db.mask);
-  void* uws = at<char>(workspace, db.total);
   const int res = P.desc.resolution, C = P.desc.in_channels;
-  const size_t hw = (size_t)res * res, total = (size_t)B * C * hw;
+  const size_t hw = (size_t)res * res, total = net.state();
   const int Txs = return_last ? 1 : S + 1, Tx0 = return_last ? 1 : S;
   auto alpha = [&](int t) -> float { return sp->alphas_cumprod_ext[t + 1]; };      // compute_alpha(t): index t + 1 (ddim.py:700-704)
 
@@ -1134,8 +1177,9 @@ static int ddim_repaint_impl(const mcedm_ddpm_plan* plan, const void* packed, co
     const float a_t = alpha(i), at_next = alpha(j);
     const float s0 = sqrtf(a_t), s1 = sqrtf(1.0f - a_t);
     for (int k = 0; k < R; ++k) {
-      const float* sc = (sp->self_cond && have_x0) ? x0 : nullptr;      // x_self_cond = x0_t if self_condition else None (:863)
-      if ((rc = ddpm_forward(P, false, pk, xt, nullptr, (float)i, at<float>(uws, hd.bias), et, at<char>(uws, hd.total), B, s, nullptr, sc))) return rc;
+      DdpmIn in{xt, (float)i};
+      in.self_cond = (sp->self_cond && have_x0) ? x0 : nullptr;        // x_self_cond = x0_t if self_condition else None (:863)
+      if ((rc = net.forward(in, et))) return rc;
       if ((rc = launch_ddim_x0(xt, et, hu, mask, s0, s1, k < R - 1 ? 1 : 0, total, x0, s))) return rc;
       have_x0 = true;
     }
@@ -1196,12 +1240,9 @@ extern "C" int mcedm_ddpm_forward_cond(const mcedm_ddpm_plan* plan, const void* 
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_cond: null argument");
   MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_cond: the network was built without self-conditioning channels");
   MCEDM_REQUIRE(!cond_map || plan->cond_channels > 0, "ddpm_forward_cond: cond_map given to a plan built without the cond_enc head");
-  DHeader hd; size_t act = 0;
-  int rc = ddpm_sizes(*plan, B, &hd, &act);
-  if (rc) return rc;
-  if ((rc = heun_check_workspace("ddpm_forward_cond", workspace_bytes, hd.total + act))) return rc;
-  return ddpm_forward(*plan, false, (const float*)packed, x, nullptr, t, at<float>(workspace, hd.bias), out,
-                      at<char>(workspace, hd.total), B, (hipStream_t)stream, nullptr, x_self_cond, cond_map);
+  DdpmIn in{x, t};
+  in.self_cond = x_self_cond; in.cond_map = cond_map;
+  return forward_entry("ddpm_forward_cond", plan, packed, in, out, workspace, workspace_bytes, B, stream);
 }
 
 namespace mcedm {
@@ -1213,12 +1254,6 @@ static int cond_sampler_check(const char* who, const mcedm_ddpm_plan& P, const f
                 cond_channels, P.cond_channels);
   MCEDM_REQUIRE((cond != nullptr) == (cond_channels > 0), "%s: cond goes with cond_channels > 0 (and only with it)", who);
   return MCEDM_OK;
-}
-static size_t state_floats(const mcedm_ddpm_plan& P, int B) {
-  return (size_t)B * P.desc.in_channels * P.desc.resolution * P.desc.resolution;
-}
-static size_t map_bytes(const mcedm_ddpm_plan& P, int B) {
-  return (size_t)B * P.desc.ch * P.desc.resolution * P.desc.resolution * sizeof(float);
 }
 
 struct DVpBufs : HeunBufs { size_t map, Fu; };
@@ -1238,34 +1273,27 @@ static int dvp_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, cons
   int rc;
   if ((rc = cond_sampler_check("ddpm_vp_heun_sample", P, cond, sp->cond_channels, B))) return rc;
   if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
   const DVpBufs vb = dvp_bufs(P, B);
-  if ((rc = heun_check_workspace("ddpm_vp_heun_sample", workspace_bytes, vb.total + hd.total + act))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
+  DdpmNet net;
+  if ((rc = ddpm_bind("ddpm_vp_heun_sample", P, packed, workspace, workspace_bytes, vb.total, B, stream, &net))) return rc;
+  hipStream_t s = net.s;
   const int R = P.desc.resolution;
   HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)R * R, sp->timesteps, return_last, out, s);
-  void* uws = at<char>(workspace, vb.total);
   float* map = cond ? at<float>(workspace, vb.map) : nullptr;
-  if (map && (rc = launch_cond_map(P, pk, cond, map, B, s))) return rc;
+  if (map && (rc = launch_cond_map(P, net.pk, cond, map, B, s))) return rc;
   const bool guided = std::fabs(sp->w) >= 0.001 && map != nullptr;             // :937-942, the second evaluation without cond
-  float* F = at<float>(uws, hd.F);
   float* Fu = guided ? at<float>(workspace, vb.Fu) : nullptr;
-  Coef* coef_in = at<Coef>(uws, hd.coef_in);
-  const int n_self = P.in_total - P.desc.in_channels;
   // get_denoised (:915-947): D = x + (-sigma) F(c_in x, c_noise, cond); cond itself is NOT scaled (cat_condition False, :932),
   // so one map serves every noise level; x_self_cond is None (get_self_cond_edm, :1603-1605)
   return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma_d, float c_noise) -> int {
     int e;
     const float sigma = (float)sigma_d;                                   // t.to(torch.float32)
     const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                // 1 / (sigma ** 2 + 1).sqrt(), fp32
-    if ((e = launch_vp_coef(c_in, n_self, P.desc.in_channels, coef_in, s))) return e;
-    if ((e = ddpm_forward(P, false, pk, h.x32, coef_in, c_noise, at<float>(uws, hd.bias), F, at<char>(uws, hd.total), B, s, nullptr,
-                          nullptr, map))) return e;
-    if (guided && (e = ddpm_forward(P, false, pk, h.x32, coef_in, c_noise, at<float>(uws, hd.bias), Fu, at<char>(uws, hd.total), B, s,
-                                    nullptr, nullptr, nullptr))) return e;
-    return launch_vp_cfg_finish(h.x32, F, Fu, sp->w, sigma, h.total, h.D, s);
+    DdpmIn in{h.x32, c_noise};
+    in.coef_in = net.coef_in(); in.cond_map = map;
+    if ((e = net.scale_input(c_in))) return e;
+    if ((e = net.forward_cfg(in, net.F(), Fu))) return e;
+    return launch_vp_cfg_finish(h.x32, net.F(), Fu, sp->w, sigma, h.total, h.D, s);
   });
 }
 
@@ -1288,36 +1316,28 @@ static int dcond_ddim_impl(const mcedm_ddpm_plan* plan, const void* packed, cons
   if ((rc = cond_sampler_check("ddpm_cond_ddim_sample", P, cond, sp->cond_channels, B))) return rc;
   MCEDM_REQUIRE(!sp->self_cond || P.desc.self_cond, "ddpm_cond_ddim_sample: self-conditioning asked of a network built without it");
   if ((rc = cond_ddim_check_schedule(sp, eta_noise, rng_seed))) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
   const DCondDdimBufs cb = dcond_ddim_bufs(P, B);
-  if ((rc = heun_check_workspace("ddpm_cond_ddim_sample", workspace_bytes, cb.total + hd.total + act))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
-  void* uws = at<char>(workspace, cb.total);
+  DdpmNet net;
+  if ((rc = ddpm_bind("ddpm_cond_ddim_sample", P, packed, workspace, workspace_bytes, cb.total, B, stream, &net))) return rc;
+  hipStream_t s = net.s;
   const int R = P.desc.resolution, C = P.desc.in_channels;
   float* map = cond ? at<float>(workspace, cb.map) : nullptr;
-  if (map && (rc = launch_cond_map(P, pk, cond, map, B, s))) return rc;
+  if (map && (rc = launch_cond_map(P, net.pk, cond, map, B, s))) return rc;
   const bool guided = cond_ddim_guided(sp);
   // x_self_cond of the next step = this step's x0 prediction, written by the step kernel (:1490, 1505); both passes read it
   float* sc = sp->self_cond ? at<float>(workspace, cb.sc) : nullptr;
-  CondDdimLoop lp{C, (size_t)R * R, state_floats(P, B), at<float>(workspace, cb.xt), at<float>(workspace, cb.xtn),
+  CondDdimLoop lp{C, (size_t)R * R, net.state(), at<float>(workspace, cb.xt), at<float>(workspace, cb.xtn),
                   at<float>(workspace, cb.F), guided ? at<float>(workspace, cb.Fu) : nullptr, sc, nullptr, C, 0};
   return cond_ddim_loop(sp, lp, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, s, [&](const float* xt, float t, int step) -> int {
-    const float* xsc = step > 0 ? sc : nullptr;                           // None in the first step: zeros
-    int e = ddpm_forward(P, false, pk, xt, nullptr, t, at<float>(uws, hd.bias), lp.F, at<char>(uws, hd.total), B, s, nullptr, xsc, map);
-    if (e || !guided) return e;
-    return ddpm_forward(P, false, pk, xt, nullptr, t, at<float>(uws, hd.bias), lp.Fu, at<char>(uws, hd.total), B, s, nullptr, xsc, nullptr);
+    DdpmIn in{xt, t};
+    in.self_cond = step > 0 ? sc : nullptr; in.cond_map = map;            // x_self_cond None in the first step: zeros
+    return net.forward_cfg(in, lp.F, lp.Fu);
   });
 }
 }  // namespace mcedm
 
 extern "C" int mcedm_ddpm_vp_sampler_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "ddpm_vp_sampler_workspace_bytes: null argument");
-  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
-  if (rc == MCEDM_OK) *bytes += dvp_bufs(*plan, B).total;
-  return rc;
+  return workspace_query("ddpm_vp_sampler_workspace_bytes", plan, B, bytes, dvp_bufs);
 }
 extern "C" int mcedm_ddpm_vp_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
                                          const float* cond, const float* init_noise, const double* step_noise, double* out,
@@ -1334,11 +1354,7 @@ extern "C" int mcedm_ddpm_vp_heun_sample_rng(const mcedm_ddpm_plan* plan, const 
 }
 
 extern "C" int mcedm_ddpm_cond_ddim_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "ddpm_cond_ddim_workspace_bytes: null argument");
-  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
-  if (rc == MCEDM_OK) *bytes += dcond_ddim_bufs(*plan, B).total;
-  return rc;
+  return workspace_query("ddpm_cond_ddim_workspace_bytes", plan, B, bytes, dcond_ddim_bufs);
 }
 extern "C" int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
                                            const float* cond, const float* init_noise, const float* eta_noise, float* xs_out,
@@ -1372,26 +1388,19 @@ static int cat_check(const char* who, const mcedm_ddpm_plan& P, const float* con
 
 // get_denoised (:1745-1763) at one noise level, fp32 like the reference: c_in scales the state rows of conv_in only (cond is
 // concatenated unscaled), F = (1 + w) F(cond) - w F(None) for |w| >= 1e-3 with cond given, D = c_skip x + c_out F
-static int dedm_denoise_impl(const mcedm_ddpm_plan& P, const DHeader& hd, const float* pk, const float* x, const float* cond,
-                             float sigma, float c_noise, double w, float sigma_data, float* D_out, float* F_out, void* ws, int B,
-                             hipStream_t s) {
+static int dedm_denoise_impl(const DdpmNet& net, const float* x, const float* cond, float sigma, float c_noise, double w,
+                             float sigma_data, float* D_out, float* F_out) {
   int rc;
   const float sd2 = sigma_data * sigma_data, s2 = sigma * sigma;
   const float c_skip = sd2 / (s2 + sd2);
   const float c_out = sigma * sigma_data / sqrtf(s2 + sd2);
   const float c_in = 1.0f / sqrtf(sd2 + s2);
-  Coef* coef_in = at<Coef>(ws, hd.coef_in);
-  if ((rc = launch_vp_coef(c_in, P.in_total - P.desc.in_channels, P.desc.in_channels, coef_in, s))) return rc;
-  float* F = at<float>(ws, hd.F);
-  float* bias = at<float>(ws, hd.bias);
-  char* act = at<char>(ws, hd.total);
-  if ((rc = ddpm_forward(P, false, pk, x, coef_in, c_noise, bias, F, act, B, s, nullptr, nullptr, nullptr, cond))) return rc;
-  float* Fu = nullptr;
-  if (std::fabs(w) >= 0.001 && cond != nullptr) {
-    Fu = at<float>(ws, hd.Fu);
-    if ((rc = ddpm_forward(P, false, pk, x, coef_in, c_noise, bias, Fu, act, B, s, nullptr, nullptr, nullptr, nullptr))) return rc;
-  }
-  return launch_edm_cfg_finish(x, F, Fu, w, c_skip, c_out, state_floats(P, B), D_out, F_out, s);
+  DdpmIn in{x, c_noise};
+  in.coef_in = net.coef_in(); in.cond_cat = cond;
+  if ((rc = net.scale_input(c_in))) return rc;
+  float* Fu = std::fabs(w) >= 0.001 && cond != nullptr ? net.Fu() : nullptr;
+  if ((rc = net.forward_cfg(in, net.F(), Fu))) return rc;
+  return launch_edm_cfg_finish(x, net.F(), Fu, w, c_skip, c_out, net.state(), D_out, F_out, net.s);
 }
 
 struct DEdmBufs : HeunBufs { size_t dx, g; };
@@ -1419,22 +1428,19 @@ static int dedm_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, con
                 "ddpm_edm_heun_sample: PDE guidance is defined for the single-task sampler (state u, conditioning h in cond[:, 0]), "
                 "models/ddim.py:1532-1601");
   if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(P, B, &hd, &act))) return rc;
   const DEdmBufs eb = dedm_bufs(P, B);
-  if ((rc = heun_check_workspace("ddpm_edm_heun_sample", workspace_bytes, eb.total + hd.total + act))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
+  DdpmNet net;
+  if ((rc = ddpm_bind("ddpm_edm_heun_sample", P, packed, workspace, workspace_bytes, eb.total, B, stream, &net))) return rc;
+  hipStream_t s = net.s;
   const int R = P.desc.resolution;
   HeunState h = heun_state(workspace, eb, B, P.desc.in_channels, (size_t)R * R, sp->timesteps, return_last, out, s);
-  void* uws = at<char>(workspace, eb.total);
   float* dxg = gd ? at<float>(workspace, eb.dx) : nullptr;
   float* gscratch = at<float>(workspace, eb.g);
   const float sd = (float)sigma_data;
   // x_self_cond is None in every evaluation (no self-conditioning on a cat_cond plan); guidance: dx = get_dx_log_prob(h, D) after
   // each denoiser call (:1576, 1589)
   return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma_d, float c_noise) -> int {
-    int e = dedm_denoise_impl(P, hd, pk, h.x32, cond, (float)sigma_d, c_noise, sp->w, sd, h.D, nullptr, uws, B, s);      // t.to(torch.float32)
+    int e = dedm_denoise_impl(net, h.x32, cond, (float)sigma_d, c_noise, sp->w, sd, h.D, nullptr);      // t.to(torch.float32)
     if (e || !gd) return e;
     return guidance_dx(P.cat_channels, *gd, cond, h.D, dxg, gscratch, B, R, R, s);
   }, dxg, gd ? (float)gd->weight : 0.f);
@@ -1447,11 +1453,9 @@ extern "C" int mcedm_ddpm_forward_cat(const mcedm_ddpm_plan* plan, const void* p
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_cat: null argument");
   int rc;
   if ((rc = cat_check("ddpm_forward_cat", *plan, cond, B))) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(*plan, B, &hd, &act))) return rc;
-  if ((rc = heun_check_workspace("ddpm_forward_cat", workspace_bytes, hd.total + act))) return rc;
-  return ddpm_forward(*plan, false, (const float*)packed, x, nullptr, t, at<float>(workspace, hd.bias), out,
-                      at<char>(workspace, hd.total), B, (hipStream_t)stream, nullptr, nullptr, nullptr, cond);
+  DdpmIn in{x, t};
+  in.cond_cat = cond;
+  return forward_entry("ddpm_forward_cat", plan, packed, in, out, workspace, workspace_bytes, B, stream);
 }
 
 extern "C" int mcedm_ddpm_edm_denoise(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float sigma,
@@ -1462,19 +1466,13 @@ extern "C" int mcedm_ddpm_edm_denoise(const mcedm_ddpm_plan* plan, const void* p
   MCEDM_REQUIRE(sigma > 0.f && sigma_data > 0.0, "ddpm_edm_denoise: sigma %g and sigma_data %g must be positive", (double)sigma, sigma_data);
   int rc;
   if ((rc = cat_check("ddpm_edm_denoise", *plan, cond, B))) return rc;
-  DHeader hd; size_t act = 0;
-  if ((rc = ddpm_sizes(*plan, B, &hd, &act))) return rc;
-  if ((rc = heun_check_workspace("ddpm_edm_denoise", workspace_bytes, hd.total + act))) return rc;
-  return dedm_denoise_impl(*plan, hd, (const float*)packed, x, cond, sigma, c_noise, w, (float)sigma_data, D_out, F_out, workspace, B,
-                           (hipStream_t)stream);
+  DdpmNet net;
+  if ((rc = ddpm_bind("ddpm_edm_denoise", *plan, packed, workspace, workspace_bytes, 0, B, stream, &net))) return rc;
+  return dedm_denoise_impl(net, x, cond, sigma, c_noise, w, (float)sigma_data, D_out, F_out);
 }
 
 extern "C" int mcedm_ddpm_edm_sampler_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  MCEDM_REQUIRE(plan && bytes, "ddpm_edm_sampler_workspace_bytes: null argument");
-  const int rc = mcedm_ddpm_workspace_bytes(plan, B, bytes);
-  if (rc == MCEDM_OK) *bytes += dedm_bufs(*plan, B).total;
-  return rc;
+  return workspace_query("ddpm_edm_sampler_workspace_bytes", plan, B, bytes, dedm_bufs);
 }
 extern "C" int mcedm_ddpm_edm_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
                                           double sigma_data, const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,

@@ -1,7 +1,7 @@
 """CPU checks of PlCondDdim on the DDPM U-Net ``Model`` (reference models/ddim.py:43-46, configs/model/ddim_cond_h_res32.yaml) and of
 the cond_enc / combine_enc head of its plan: the parameter table and the module's state_dict against the reference's
 (tests/golden/ddpm_cond.npz), what still raises, the new C entries in header, binding and library, and their host-side
-rejections (which run before any launch, so without a GPU)."""
+rejections (which run before any launch, so without a GPU), with those of the unconditional entries and of the size queries."""
 import ctypes as C
 import os
 import re
@@ -142,3 +142,80 @@ def test_host_side_rejections():
     assert dm(noself, dd, one, need) == -1 and "built without it" in _last()
     assert lib.mcedm_ddpm_cond_ddim_sample_rng(plan._h, one, C.byref(dd), one, one, None, one, one, 1, one, need, B, None) == -1
     assert "rng_seed" in _last()
+
+
+def _samplers():
+    """Of the two unconditional samplers: the makers of their descriptions (each returns (desc, keepalive)) and
+    call(plan, packed, workspace, nbytes, B, made)."""
+    from oracle import ddpm_oracle as ddo
+    lib, one = L.load(), C.c_void_p(4096)
+    betas = ddo.betas_of(D.CFG)
+    ae = ddo.alphas_ext_of(betas)
+
+    def rp(**kw):
+        return L.repaint_desc(ddo.RepaintParams(timesteps=3, n_time_u=8, **kw), ddo.edm_steps_of(betas), ae, 1, 0)
+
+    def dd(self_cond):
+        return L.ddim_desc(ddo.DdimParams(timesteps=3, n_repeat=1, n_time_h=8), ae, 1, 0, self_cond)
+
+    def repaint(p, pk, ws, nbytes, b, made):
+        return lib.mcedm_repaint_sample(p, pk, C.byref(made[0]), one, one, None, one, one, 1, ws, nbytes, b, None)
+
+    def ddim(p, pk, ws, nbytes, b, made):
+        return lib.mcedm_ddim_repaint_sample(p, pk, C.byref(made[0]), one, one, None, one, one, 1, ws, nbytes, b, None)
+    return rp, dd, repaint, ddim
+
+
+def test_host_side_rejections_of_the_unconditional_entries():
+    """mcedm_ddpm_forward, _forward_sc, _denoise, mcedm_repaint_sample, mcedm_ddim_repaint_sample and the six size queries: a null
+    plan / packed / workspace, an empty batch, a workspace one byte short (the text names the bytes needed), x_self_cond on a plan
+    without self-conditioning, and which check speaks when two fail at once.  All on the host, before any launch."""
+    lib = L.load()
+    plan, noself = cond_plan(0), cond_plan(0, self_cond=False)
+    one = C.c_void_p(4096)
+    B = 3
+    rp, dd, repaint, ddim = _samplers()
+    rd, dsc, net = rp(), dd(True), plan.workspace_bytes(B)
+    entries = {
+        "ddpm_forward": (net, lambda p, pk, ws, n, b: lib.mcedm_ddpm_forward(p, pk, one, 500.0, one, ws, n, b, None)),
+        "ddpm_forward_sc": (net, lambda p, pk, ws, n, b: lib.mcedm_ddpm_forward_sc(p, pk, one, one, 500.0, one, ws, n, b, None)),
+        "ddpm_denoise": (net, lambda p, pk, ws, n, b: lib.mcedm_ddpm_denoise(p, pk, one, 1.5, 700.0, one, None, ws, n, b, None)),
+        "repaint_sample": (plan.repaint_workspace_bytes(B), lambda p, pk, ws, n, b: repaint(p, pk, ws, n, b, rd)),
+        "ddim_repaint_sample": (plan.ddim_workspace_bytes(B), lambda p, pk, ws, n, b: ddim(p, pk, ws, n, b, dsc)),
+    }
+    for who, (need, call) in entries.items():
+        for args in ((None, one, one), (plan._h, None, one), (plan._h, one, None)):
+            assert call(*args, need, B) == -1 and _last() == f"{who}: null argument", (who, args)
+        assert call(plan._h, one, one, need, 0) == -1 and _last() == "ddpm: empty batch", who
+        assert call(plan._h, one, one, need - 1, B) == -3, who
+        assert _last() == f"{who}: workspace too small ({need - 1} < {need} bytes)", who
+        # two at once: the empty batch speaks before the workspace
+        assert call(plan._h, one, one, 0, 0) == -1 and _last() == "ddpm: empty batch", who
+    # x_self_cond given to a plan built without self-conditioning (it speaks before the empty batch and the workspace)
+    need = noself.workspace_bytes(B)
+    assert lib.mcedm_ddpm_forward_sc(noself._h, one, one, one, 500.0, one, one, need, B, None) == -1
+    assert _last() == "ddpm_forward_sc: the network was built without self-conditioning channels"
+    assert lib.mcedm_ddpm_forward_sc(noself._h, one, one, one, 500.0, one, one, 0, 0, None) == -1 and "without self-conditioning" in _last()
+    assert lib.mcedm_ddpm_forward_sc(noself._h, one, one, None, 500.0, one, one, need - 1, B, None) == -3     # None: as mcedm_ddpm_forward
+    assert ddim(noself._h, one, one, noself.ddim_workspace_bytes(B), B, dsc) == -1
+    assert _last() == "ddim_repaint_sample: self-conditioning asked of a network built without it"
+    assert ddim(noself._h, one, one, noself.ddim_workspace_bytes(B) - 1, B, dd(False)) == -3
+    # two at once on the samplers: the schedule speaks before the workspace
+    assert repaint(plan._h, one, one, 0, B, rp(w=0.5)) == -1 and "classifier-free guidance needs a conditional network" in _last()
+    bad = rp()
+    bad[0].timesteps = 1
+    assert repaint(plan._h, one, one, 0, B, bad) == -1 and "timesteps=1 n_repeat=2 out of range" in _last()
+    bad = dd(True)
+    bad[0].skip_type = 2
+    assert ddim(plan._h, one, one, 0, B, bad) == -1 and "skip_type must be 0 (uniform) or 1 (quad)" in _last()
+    # the size queries
+    cat = cond_plan(1, self_cond=False, cat_cond=True)
+    sz = C.c_size_t()
+    for q in ("ddpm_workspace_bytes", "repaint_workspace_bytes", "ddim_workspace_bytes", "ddpm_vp_sampler_workspace_bytes",
+              "ddpm_cond_ddim_workspace_bytes", "ddpm_edm_sampler_workspace_bytes"):
+        fn = getattr(lib, "mcedm_" + q)
+        for pl in (plan, cat):
+            assert fn(None, B, C.byref(sz)) == -1 and _last() == f"{q}: null argument", q
+            assert fn(pl._h, B, None) == -1 and _last() == f"{q}: null argument", q
+            assert fn(pl._h, 0, C.byref(sz)) == -1 and _last() == "ddpm: empty batch", q
+            assert fn(pl._h, -2, C.byref(sz)) == -1 and _last() == "ddpm: empty batch", q
