@@ -769,6 +769,21 @@ int mcedm_ddpm_edm_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* pack
  * mcedm_darcy_residual   DarcyLoss.calculate_loss models/pde_loss.py:30-54 and the division / clamp of forward
  *                        (:80-86): two_dx = (float)(2 * D / s), denom = (s-4)^2; out (b, s-4, s-4) */
 int mcedm_swe_fv_step(const float* s, float* out, int B, int T, int X, float half_dt, float dx, void* stream);
+/* mcedm_swe_fv_unroll    SweFvLoss.unroll_from_init models/pde_loss.py:167-182 and, with gt / loss given, the residual of
+ *                        unroll_loss (:184-197): n_steps dependent steps of mcedm_swe_fv_step from one initial row per sample in
+ *                        ONE launch (one workgroup per sample, the row held in LDS), bit-identical to the n_steps launches.
+ *   ic    B rows of X (h, u) pairs, ic_sample_stride floats apart (>= 2 * X), so that pred[:, 0] of a (b, t, x, 2) tensor is read in
+ *         place; it must not overlap out.
+ *   out, gt, loss  (B, n_steps + 1, X, 2), contiguous; row 0 of out is ic, copied verbatim.
+ *   gt and loss are both NULL (scale2_* ignored) or both given: loss = (out - gt)^2 / scale2 on every row, row 0 included,
+ *         with neither the NaN -> 0 nor the clamp of mcedm_swe_fv_residual (the reference's unroll_loss has neither).
+ *   half_dt = (float)(0.5 * Tn / n_steps) (NOT Tn / (n_steps + 1): unroll_from_init divides by the step count, :176), dx as above.
+ * MCEDM_ERR_INVALID, before any launch, with a message that names the argument: ic or out NULL, only one of gt / loss, X outside
+ * [1, MCEDM_SWE_UNROLL_MAX_X], n_steps < 0, B < 0, ic_sample_stride < 2 * X.  B == 0 is MCEDM_OK without a launch; n_steps == 0
+ * copies ic (and fills loss).  Allocates nothing and does not synchronise. */
+#define MCEDM_SWE_UNROLL_MAX_X 4096   /* two rows of (h, u) pairs in 64 KB of LDS */
+int mcedm_swe_fv_unroll(const float* ic, size_t ic_sample_stride, float* out, const float* gt, float* loss,
+                        int B, int n_steps, int X, float half_dt, float dx, float scale2_h, float scale2_u, void* stream);
 /* The return_d=True branches (the guidance gradients; analytic adjoints of the stencils, models/pde_loss.py:231-242 and
  * :60-75): mcedm_swe_fv_guidance = d mean(calculate_loss(pred, gt)) / d pred, out (b, t, x, 2);
  * mcedm_darcy_guidance = d mean(L) / d pred or, calc_prob != 0, d mean(log(2 (1 - sigmoid(1e5 L)) + 1e-12)) / d pred,

@@ -2,9 +2,11 @@
 //
 //   swe_fv_*   SweFvLoss.f_t_swp1d / calculate_loss  (models/pde_loss.py:131-165, 211-225): FORCE finite-volume step
 //              along x for every (b, t) row; the residual compares step(pred[t-1]) with gt[t] (row 0: pred[0]).
+//   swe_unroll SweFvLoss.unroll_from_init / unroll_loss  (models/pde_loss.py:167-197): the same step applied n_steps times from
+//              one initial row, sequential in time; one workgroup per sample with the row in LDS.
 //   darcy_*    DarcyLoss.calculate_loss              (models/pde_loss.py:30-54): -div(a grad u) = 1, central differences.
 //
-// Pure streaming kernels (one thread per output cell, 3-point / 5x5 neighbourhoods served by L1/L2): HBM-bound at
+// Apart from the unroll, pure streaming kernels (one thread per output cell, 3-point / 5x5 neighbourhoods served by L1/L2): HBM-bound at
 // 16 B (SWE) / 12 B (Darcy) per cell.  Built with -ffp-contract=off and written in the reference's evaluation order,
 // so the results are bit-identical to the PyTorch CPU path (tests compare with torch.equal).
 #include "common.hpp"
@@ -75,6 +77,46 @@ __global__ __launch_bounds__(256) void swe_fv_residual_kernel(const float2* __re
   float lu = (vu - g.y) * (vu - g.y) / scale2_u;
   if (clamp) { lh = lh > 1.f ? 1.f : lh; lu = lu > 1.f ? 1.f : lu; }     // torch.clamp(max=1): NaN stays NaN
   out[i] = make_float2(lh, lu);
+}
+
+// SweFvLoss.unroll_from_init (+ the residual of unroll_loss) (models/pde_loss.py:167-197): n_steps dependent FORCE steps from
+// row 0.  One workgroup per sample; the current row lives in LDS as (h, u) pairs, double-buffered (2 * X float2 of dynamic
+// LDS), so a step reads one buffer, writes the other and needs one barrier.  Every cell is swe_force_cell of the previous
+// row -- a pure function of it -- so the result does not depend on the workgroup size and is bit-identical to n_steps launches
+// of swe_fv_step_kernel.  ic is read as scalars (any 4-byte aligned stride); out / gt / loss are (B, n_steps + 1, X) float2.
+// With gt / loss given, loss = (row - gt)^2 / scale2 for every row incl. row 0 (no NaN zeroing, no clamp, :191-193).
+__global__ __launch_bounds__(1024) void swe_unroll_kernel(const float* __restrict__ ic, size_t ic_sample_stride,
+                                                          float2* __restrict__ out, const float2* __restrict__ gt,
+                                                          float2* __restrict__ loss, int n_steps, int X, float half_dt, float dx,
+                                                          float scale2_h, float scale2_u) {
+  extern __shared__ float2 swe_rows[];       // [2][X]
+  const size_t b = blockIdx.x;
+  const float* src = ic + b * ic_sample_stride;
+  const size_t base = b * ((size_t)n_steps + 1) * X;
+  auto put = [&](size_t i, float2 v) {
+    out[i] = v;
+    if (loss) {
+      const float2 g = gt[i];
+      loss[i] = make_float2((v.x - g.x) * (v.x - g.x) / scale2_h, (v.y - g.y) * (v.y - g.y) / scale2_u);
+    }
+  };
+  for (int x = threadIdx.x; x < X; x += blockDim.x) {
+    const float2 v = make_float2(src[2 * (size_t)x], src[2 * (size_t)x + 1]);
+    swe_rows[x] = v;
+    put(base + x, v);
+  }
+  __syncthreads();
+  for (int t = 0; t < n_steps; ++t) {
+    const float2* cur = swe_rows + (size_t)(t & 1) * X;
+    float2* nxt = swe_rows + (size_t)((t + 1) & 1) * X;
+    for (int x = threadIdx.x; x < X; x += blockDim.x) {
+      const SweCell c = swe_force_cell(cur, x, X, half_dt, dx);
+      const float2 v = make_float2(c.h, c.u);
+      nxt[x] = v;
+      put(base + ((size_t)t + 1) * X + x, v);
+    }
+    __syncthreads();                         // nxt is complete and cur fully read: the next step overwrites cur
+  }
 }
 
 __global__ __launch_bounds__(256) void darcy_residual_kernel(const float2* __restrict__ pred, float* __restrict__ out, int S,
@@ -340,6 +382,26 @@ extern "C" int mcedm_swe_fv_step(const float* s, float* out, int B, int T, int X
   hipLaunchKernelGGL(swe_fv_step_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)s, (float2*)out, X, cells, half_dt, dx);
   MCEDM_LAUNCH_CHECK("swe_fv_step_kernel");
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_swe_fv_unroll(const float* ic, size_t ic_sample_stride, float* out, const float* gt, float* loss, int B,
+                                   int n_steps, int X, float half_dt, float dx, float scale2_h, float scale2_u, void* stream) {
+  MCEDM_REQUIRE(ic, "swe_fv_unroll: ic is null");
+  MCEDM_REQUIRE(out, "swe_fv_unroll: out is null");
+  MCEDM_REQUIRE((gt == nullptr) == (loss == nullptr), "swe_fv_unroll: gt and loss must both be given or both be null (%s is null)",
+                gt ? "loss" : "gt");
+  MCEDM_REQUIRE(X >= 1 && X <= MCEDM_SWE_UNROLL_MAX_X, "swe_fv_unroll: X = %d is outside [1, MCEDM_SWE_UNROLL_MAX_X = %d]", X,
+                MCEDM_SWE_UNROLL_MAX_X);
+  MCEDM_REQUIRE(n_steps >= 0, "swe_fv_unroll: n_steps = %d is negative", n_steps);
+  MCEDM_REQUIRE(B >= 0, "swe_fv_unroll: B = %d is negative", B);
+  MCEDM_REQUIRE(ic_sample_stride >= 2 * (size_t)X, "swe_fv_unroll: ic_sample_stride = %zu is smaller than 2 * X = %d floats",
+                ic_sample_stride, 2 * X);
+  if (B == 0) return MCEDM_OK;
+  const int threads = (X + 63) / 64 * 64 < 1024 ? (X + 63) / 64 * 64 : 1024;      // whole waves; cells beyond that are looped over
+  hipLaunchKernelGGL(swe_unroll_kernel, dim3((unsigned)B), dim3(threads), 2 * (size_t)X * sizeof(float2), (hipStream_t)stream, ic,
+                     ic_sample_stride, (float2*)out, (const float2*)gt, (float2*)loss, n_steps, X, half_dt, dx, scale2_h, scale2_u);
+  MCEDM_LAUNCH_CHECK("swe_unroll_kernel");
   return MCEDM_OK;
 }
 

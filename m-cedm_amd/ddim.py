@@ -42,8 +42,8 @@ from .pl_base import DotDict, _PlBase, _TrainLoss, _nchw, _opt, correlation, l1,
 
 class _SingleTask(_PlBase):
     """What the single-task models (h given, u generated) share -- in the reference PlCondEdm inherits it from PlCondDdim
-    (models/ddim.py:1053-1319): the conditioning input, the u-only inverse transform, the PDE residual of (h, u) and the
-    evaluation loops around ``sample_edm``."""
+    (models/ddim.py:1053-1386): the conditioning input, the u-only inverse transform, the PDE residual of (h, u), the
+    evaluation loops around ``sample_edm`` and the unroll metrics (``print_unroll_metrics``, ``get_x_unnorm``)."""
 
     def _adm_only(self, what):
         if self._on_ddpm_unet:
@@ -117,6 +117,48 @@ class _SingleTask(_PlBase):
         if noise_level is not None:
             err = err / (noise_level.reshape(-1, 1, 1, 1) + 1.0)
         return err.sum() if reduce else err
+
+    def get_x_unnorm(self, cond, x_denoised, do_rearrange=True):
+        """models/ddim.py:1378-1386: the un-normalised (h, u) state of a conditioning field and a denoised one."""
+        h, u = cond, x_denoised
+        if do_rearrange:
+            h, u = h.permute(0, 2, 3, 1), u.permute(0, 2, 3, 1)
+        return torch.cat(self.inverse_data_transform(h, u), dim=-1)
+
+    def print_unroll_metrics(self, xs, h_unnorm, u_unnorm, state_gt, n_samples):
+        """models/ddim.py:1321-1376: run the solver forward from the first row of every recovered state '(n b) t h w c' (its last
+        sampler step) and of the truth, and compare the runs.  The n samples go through ONE unroll_loss call (one launch); their
+        error sums are then accumulated sample by sample in the reference's order.  Like every PDE entry here the unroll computes
+        in fp32 whatever the dtype of xs.  Switches self.pde_loss to the simulator loss, as the reference does."""
+        self.pde_loss = self.pde_loss_simulator
+        h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
+        n, nb = n_samples, xs.shape[0] // n_samples
+        cond = state_gt[..., 0:h_ch]
+        pred_unnorm = self.get_x_unnorm(cond.repeat(n, 1, 1, 1), xs[:, -1], do_rearrange=False)
+        err, unroll_res = self.pde_loss.unroll_loss(pred_unnorm, pred_unnorm, self.normalizer_input, self.normalizer_target,
+                                                    return_unroll=True)
+        err = err.reshape(n, nb, *err.shape[1:])
+        err_h, err_u = 0.0, 0.0
+        for i in range(n):
+            err_h += torch.sum(err[i][..., 0:h_ch])
+            err_u += torch.sum(err[i][..., h_ch:u_ch + h_ch])
+        err_h /= n
+        err_u /= n
+        x_gt1 = torch.cat([h_unnorm, u_unnorm], dim=-1)
+        err_gt, unroll_res_gt = self.pde_loss.unroll_loss(x_gt1, x_gt1, self.normalizer_input, self.normalizer_target,
+                                                          return_unroll=True)
+        err_gt_h, err_gt_u = torch.sum(err_gt[..., 0:h_ch]), torch.sum(err_gt[..., h_ch:u_ch + h_ch])
+        self._log("test_pde_unroll_error", err_u)
+        print(f"Tests Unroll error h is {err_h}")
+        print(f"Tests Unroll error u is {err_u}")
+        self._log("test_pde_unroll_error_gt", err_gt_u)
+        print(f"Tests Unroll error gt h is {err_gt_h}")
+        print(f"Tests Unroll error gt u is {err_gt_u}")
+        gt_rep = unroll_res_gt.repeat(n, 1, 1, 1)
+        self._log("test_pde_unrolled_mae_h", l1(unroll_res[..., 0:h_ch], gt_rep[..., 0:h_ch]))
+        self._log("test_pde_unrolled_mae_u", l1(unroll_res[..., h_ch:u_ch + h_ch], gt_rep[..., h_ch:u_ch + h_ch]))
+        unroll_res = unroll_res.reshape(n, nb, *unroll_res.shape[1:]).permute(1, 2, 3, 0, 4).unsqueeze(1)   # 'b 1 h w n c'
+        return unroll_res, unroll_res_gt
 
     def validation_step(self, val_batch, batch_idx):
         if (self.current_epoch + 1) % 100 != 0 and self.current_epoch != 0:

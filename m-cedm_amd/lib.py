@@ -42,6 +42,7 @@ EXPORTS = [
     "mcedm_ddpm_cond_ddim_sample", "mcedm_ddpm_cond_ddim_sample_rng",
     "mcedm_ddpm_forward_cat", "mcedm_ddpm_edm_denoise", "mcedm_ddpm_edm_sampler_workspace_bytes", "mcedm_ddpm_edm_heun_sample",
     "mcedm_ddpm_edm_heun_sample_rng",
+    "mcedm_swe_fv_unroll",
 ]
 # The sampler entries _PlanBase._sample_call drives, with the number of materialised-noise pointers each takes; every one
 # has a "_rng" twin that takes ONE seed pointer in their place.  A new sampler is a row here and a method that names it.
@@ -67,6 +68,7 @@ class UNetDesc(C.Structure):
 DX_NONE, DX_CAT, DX_ENC = 0, 1, 2      # MCEDM_DX_* (include/mcedm_hip.h)
 ABI_VERSION = 4                        # MCEDM_ABI_VERSION
 REDUCE_SCRATCH_BYTES = 4096 * 8 + 64   # MCEDM_REDUCE_SCRATCH_BYTES
+SWE_UNROLL_MAX_X = 4096                # MCEDM_SWE_UNROLL_MAX_X
 
 
 class SamplerDesc(C.Structure):
@@ -178,6 +180,7 @@ def load() -> C.CDLL:
     lib.mcedm_adam_ema_step.argtypes = [f32p, f32p, f32p, f32p, f32p, sz, C.c_double, C.c_double, C.c_double,
                                         C.c_double, C.c_double, f64p, C.c_double, C.c_double, C.c_double, C.c_int64, vp]
     lib.mcedm_swe_fv_step.argtypes = [f32p, f32p, i32, i32, i32, C.c_float, C.c_float, vp]
+    lib.mcedm_swe_fv_unroll.argtypes = [f32p, sz, f32p, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     lib.mcedm_swe_fv_residual.argtypes = [f32p, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float,
                                           i32, vp]
     lib.mcedm_darcy_residual.argtypes = [f32p, f32p, i32, i32, C.c_float, C.c_float, i32, vp]
@@ -1228,6 +1231,40 @@ def swe_fv_step(s_t: torch.Tensor, half_dt: float, dx: float) -> torch.Tensor:
     out = torch.empty_like(s_t)
     check(load().mcedm_swe_fv_step(_ptr(s_t), _ptr(out), B, T, X, half_dt, dx, _stream()), "swe_fv_step")
     return out
+
+
+def swe_fv_unroll(ic: torch.Tensor, n_steps: int, half_dt: float, dx: float, gt: Optional[torch.Tensor] = None,
+                  scale2: Optional[Sequence[float]] = None):
+    """SweFvLoss.unroll_from_init on the initial rows ``ic`` (b, 1, x, 2) or (b, x, 2), fp32: ``out`` (b, n_steps + 1, x, 2) in one
+    launch.  With ``gt`` (the shape of ``out``) and ``scale2 = (scale2_h, scale2_u)`` also the residual of unroll_loss,
+    ``(out - gt) ** 2 / scale2``; returns ``(loss, out)`` then.  ``ic`` may be a view whose samples are strided (``pred[:, 0:1]``):
+    it is read in place; only its rows must be dense."""
+    if not ic.is_cuda:
+        raise RuntimeError("libmcedm_hip needs device tensors (got a CPU tensor); there is no CPU fallback")
+    if ic.dtype != torch.float32:
+        raise RuntimeError(f"expected dtype {torch.float32}, got {ic.dtype}")
+    rows = ic[:, 0] if ic.dim() == 4 else ic
+    if rows.dim() != 3 or rows.shape[2] != 2 or (ic.dim() == 4 and ic.shape[1] != 1):
+        raise RuntimeError(f"swe_fv_unroll: ic must be (b, 1, x, 2) or (b, x, 2), got {tuple(ic.shape)}")
+    B, X, _ = rows.shape
+    dense = rows.stride(2) == 1 and (X == 1 or rows.stride(1) == 2)
+    if not dense or (B > 1 and rows.stride(0) < 2 * X):
+        rows = rows.contiguous()
+    if (gt is None) != (scale2 is None):
+        raise RuntimeError("swe_fv_unroll: gt and scale2 go together")
+    n_steps = int(n_steps)
+    out = torch.empty((B, max(n_steps, 0) + 1, X, 2), dtype=torch.float32, device=ic.device)
+    loss, s2h, s2u = None, 1.0, 1.0
+    if gt is not None:
+        if tuple(gt.shape) != tuple(out.shape):
+            raise RuntimeError(f"swe_fv_unroll: gt must be {tuple(out.shape)}, got {tuple(gt.shape)}")
+        loss, (s2h, s2u) = torch.empty_like(out), scale2
+    stride = rows.stride(0) if B > 1 else 2 * X
+    if B == 0:                               # an empty tensor has no pointer to pass
+        return out if gt is None else (loss, out)
+    check(load().mcedm_swe_fv_unroll(rows.data_ptr(), stride, _ptr(out), _ptr(gt), _ptr(loss), B, n_steps, X, half_dt, dx,
+                                     float(s2h), float(s2u), _stream()), "swe_fv_unroll")
+    return out if gt is None else (loss, out)
 
 
 def swe_fv_residual(pred, gt, half_dt: float, dx: float, scale2_h: float, scale2_u: float, clamp: bool) -> torch.Tensor:

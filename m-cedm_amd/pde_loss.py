@@ -1,9 +1,12 @@
-"""Device-side PDE residual metrics: drop-in for the reference's ``models/pde_loss.py`` (forward residual only).
+"""Device-side PDE residual metrics: drop-in for the reference's ``models/pde_loss.py`` (``SweFvLoss``, ``DarcyLoss``).
 
 ``SweFvLoss`` / ``DarcyLoss`` keep the reference's constructor and ``forward(pred, gt, normalizer_h, normalizer_u,
 return_d=False, calc_prob=False, clamp_loss=False)`` signature and return bit-identical tensors; the stencil work runs
 in ``libmcedm_hip.so`` (csrc/pde.hip).  ``return_d=True`` (the guidance gradient) runs the stencils' analytic adjoints
-(csrc/pde.hip) and agrees with the reference's autograd result to rounding.  ``get_pde_loss_function`` mirrors ``models/loss_helper.py:16-38``.
+(csrc/pde.hip) and agrees with the reference's autograd result to rounding.  ``SweFvLoss.unroll_from_init`` / ``unroll_loss``
+(models/pde_loss.py:167-197) run the solver forward from an initial row: all steps in one launch (mcedm_swe_fv_unroll), bit-identical
+to repeated ``f_t_swp1d``; no gradient flows through them.  ``SweFvGtLoss`` is not built.  ``get_pde_loss_function`` mirrors
+``models/loss_helper.py:16-38``.
 """
 import numpy as np
 import torch
@@ -56,6 +59,23 @@ class SweFvLoss(nn.Module):
     def f_t_swp1d(self, s_t, dt):
         s = _f32(s_t)
         return lib.swe_fv_step(s, float(np.float32(0.5 * dt)), self._dx(s.shape[2]))
+
+    def _unroll(self, ic, n_steps, gt=None, scale2=None):
+        dt = self.Tn / n_steps                         # n_steps 0 (a one-row pred): ZeroDivisionError, as in the reference (:176)
+        ic = ic.to(torch.float32)                      # a strided view such as pred[:, 0:1] stays one: it is read in place
+        return lib.swe_fv_unroll(ic, n_steps, float(np.float32(0.5 * dt)), self._dx(ic.shape[2]), gt, scale2)
+
+    def unroll_from_init(self, ic, n_steps):
+        """models/pde_loss.py:167-182: ic (b, 1, w, 2) -> (b, n_steps + 1, w, 2), row 0 = ic; all steps in one launch."""
+        return self._unroll(ic, n_steps)
+
+    def unroll_loss(self, pred, gt, normalizer_h, normalizer_u, return_unroll=False):
+        """models/pde_loss.py:184-197: the solver run from pred[:, 0:1] over pred.shape[1] - 1 steps of Tn / (pred.shape[1] - 1)
+        (calculate_loss uses Tn / pred.shape[1]), compared with gt; no NaN zeroing and no clamp."""
+        if self.flip_xy:
+            pred, gt = flip_state(pred, gt, normalizer_h, normalizer_u)
+        loss, unrolled = self._unroll(pred[:, 0:1], pred.shape[1] - 1, _f32(gt), self._scales(normalizer_h, normalizer_u))
+        return (loss, unrolled) if return_unroll else loss
 
     def get_scaling(self, normalizer_h, normalizer_u):
         scale_h, scale_u = normalizer_h.divide, normalizer_u.divide
