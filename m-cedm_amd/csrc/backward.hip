@@ -148,11 +148,11 @@ struct Ctx;
 static GnBwdArgs with_sync(const Ctx& c, GnBwdArgs g);
 
 struct Ctx {
+  const AdmNet& net;        // the forward's network, bound to the same workspace: plan, weights, layout, activations
   const mcedm_plan& P;
   const Layout& L;
   const BwdScratch& S;
-  char* act;        // forward activations
-  char* scr;        // backward scratch
+  char* scr;        // backward scratch, behind the activations
   const float* pk;
   float* const* grads;
   int B, n_noise;
@@ -163,8 +163,11 @@ struct Ctx {
   const int32_t* bucket_first = nullptr;      // >= bucket_first[k] has its gradient enqueued
   void* const* bucket_events = nullptr;
 
-  float* T(int id) const { return id < 0 ? nullptr : reinterpret_cast<float*>(act + L.t[id].off); }
-  Coef* CF(int id) const { return id < 0 ? nullptr : reinterpret_cast<Coef*>(act + L.t[id].off); }
+  Ctx(const AdmNet& n, const BwdScratch& scratch, float* const* g)
+      : net(n), P(*n.plan), L(n.L), S(scratch), scr(n.act + n.L.total_bytes), pk(n.pk), grads(g), B(n.B), n_noise(n.n_noise),
+        s(n.s), have(n.L.t.size(), 0) {}
+  float* T(int id) const { return net.T(id); }
+  Coef* CF(int id) const { return net.CF(id); }
   float* G(int id) const { return id < 0 ? nullptr : reinterpret_cast<float*>(scr + S.g[id]); }
   float* X(size_t off) const { return reinterpret_cast<float*>(scr + off); }
 };
@@ -182,7 +185,7 @@ static int dgrad(const Ctx& c, const ConvP& cv, const float* dy, int H, int W, f
 }
 
 static int norm_param_grads(const Ctx& c, const NormP& nm, const float* film, int film_stride, float* dfilm) {
-  return launch_gn_param_grads(c.X(c.S.ab), c.pk + nm.gamma, c.pk + nm.beta, film, c.n_noise > 1 ? 1 : 0, film_stride,
+  return launch_gn_param_grads(c.X(c.S.ab), c.pk + nm.gamma, c.pk + nm.beta, film, c.net.coef_batch(), film_stride,
                                c.B, nm.C, c.grads[nm.w], c.grads[nm.b], dfilm, c.P.film_rows, c.s);
 }
 
@@ -217,9 +220,9 @@ static int block_backward(Ctx& c, const BlockP& b, const BlockLayout& bl) {
   }
   // y = conv1(silu(film(norm1(h)))) + skip(x)
   if ((rc = dgrad(c, b.conv1, dy, H, W, dact))) return rc;
-  const float* film = reinterpret_cast<const float*>(c.act + c.L.t[c.L.film].off) + b.film_row0;
+  const float* film = c.net.film() + b.film_row0;
   GnBwdArgs g1{dact, RS_NONE, c.T(bl.h), nullptr, b.cout, 0, H, W, B, b.norm1.groups, c.CF(bl.coef1), c.T(bl.stats1),
-               c.pk + b.norm1.gamma, film, c.n_noise > 1 ? 1 : 0, c.P.film_rows, 1, c.G(bl.h), nullptr, 0, nullptr, 0, 0,
+               c.pk + b.norm1.gamma, film, c.net.coef_batch(), c.P.film_rows, 1, c.G(bl.h), nullptr, 0, nullptr, 0, 0,
                c.X(c.S.ab), c.X(c.S.xact)};
   if ((rc = launch_gn_bwd(with_sync(c, g1), c.s))) return rc;
   if ((rc = norm_param_grads(c, b.norm1, film, c.P.film_rows, c.X(c.S.dfilm) + b.film_row0))) return rc;
@@ -339,20 +342,15 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   }
   for (size_t i = 0; i < P.params.size(); ++i)
     MCEDM_REQUIRE(grads[i] != nullptr, "denoise_backward: grads[%zu] (%s) is null", i, P.params[i].name.c_str());
-  Layout L;
-  int rc = build_layout(P, B, H, W, 1, n_sigma, &L);
+  AdmNet net;
+  BwdScratch S;
+  int rc = adm_bind("denoise_backward", P, packed, workspace, workspace_bytes, 0,
+                    [&](const AdmNet& n) { S = make_scratch(P, n.L, B, H, W); return S.total; }, B, H, W, 1, n_sigma, stream, &net);
   if (rc) return rc;
-  const Header hd = header_for(P, B, H, W);
-  const BwdScratch S = make_scratch(P, L, B, H, W);
-  if (hd.total + L.total_bytes + S.total > workspace_bytes) {
-    set_error("denoise_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, hd.total + L.total_bytes + S.total);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  char* act = at<char>(workspace, hd.total);
-  char* scr = act + L.total_bytes;
-  const float* pk = (const float*)packed;
-  Ctx c{P, L, S, act, scr, pk, grads, B, n_sigma, s, std::vector<char>(L.t.size(), 0)};
+  const Layout& L = net.L;
+  hipStream_t s = net.s;
+  const float* pk = net.pk;
+  Ctx c(net, S, grads);
   c.n_buckets = n_buckets; c.bucket_first = bucket_first; c.bucket_events = bucket_events;
   MCEDM_HIP_TRY(hipMemsetAsync(c.X(S.sync), 0, S.sync_bytes, s));      // zero once per pass; every GroupNorm backward leaves it zero
   const int ch = P.desc.ch;
@@ -366,7 +364,7 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   float* t1 = c.X(S.t1); float* t2 = c.X(S.t2); float* t3 = c.X(S.t3);
   float* emb = c.X(S.emb);
   hipLaunchKernelGGL(emb_save_kernel, dim3(n), dim3(256), 2 * ch * sizeof(float), s,
-                     from.dF ? from.noise_labels : at<float>(workspace, hd.c_noise),
+                     from.dF ? from.noise_labels : net.c_noise(),
                      pk + P.freqs, pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1, ch, pe, u1, u2);
   MCEDM_LAUNCH_CHECK("emb_save_kernel");
   const size_t ne = (size_t)n * ch;
@@ -378,7 +376,7 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   // dF = c_out * dD (EDM entries) or given
   const float* gF = from.dF;
   if (!gF) {
-    hipLaunchKernelGGL(scale_by_cout_kernel, dim3(grid_for(per * B)), dim3(256), 0, s, dD, at<float>(workspace, hd.coefs4),
+    hipLaunchKernelGGL(scale_by_cout_kernel, dim3(grid_for(per * B)), dim3(256), 0, s, dD, net.coefs4(),
                        n_sigma, per, per * B, c.X(S.gF));
     MCEDM_LAUNCH_CHECK("scale_by_cout_kernel");
     gF = c.X(S.gF);
@@ -430,9 +428,9 @@ static int denoise_backward_impl(const mcedm_plan* plan, const void* packed, con
   }
   // conv_in: weight / bias gradient only (its inputs carry no gradient)
   const bool catdx = P.desc.dx_mode == MCEDM_DX_CAT;
-  const Coef* coef_in = (from.dF && !from.x_scale) ? nullptr : at<Coef>(workspace, hd.coef_in);   // the forward's conv_in rows
+  const Coef* coef_in = (from.dF && !from.x_scale) ? nullptr : net.coef_in();   // the forward's conv_in rows
   WgradArgs wi{dy_in, cond, catdx ? c.T(L.xdx) : x, P.desc.cond_channels, P.desc.in_channels + (catdx ? P.desc.dx_channels : 0),
-               coef_in, n_sigma > 1 ? 1 : 0, 0, RS_NONE, H, W, H, W, P.conv_in.cout, B, c.X(S.wg), nullptr};
+               coef_in, net.coef_batch(), 0, RS_NONE, H, W, H, W, P.conv_in.cout, B, c.X(S.wg), nullptr};
   if ((rc = launch_wgrad(wi, 9, grads[P.conv_in.w], grads[P.conv_in.b], 0, c.X(c.S.xact), s))) return rc;
 
   // mapping MLP: film = emb Waff^T + baff, emb = silu(u2), u2 = W1 silu(u1) + b1, u1 = W0 pe + b0

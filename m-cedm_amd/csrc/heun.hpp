@@ -40,15 +40,6 @@ static inline HeunState heun_state(void* ws, const HeunBufs& b, int B, int C, si
                    C, hw, (size_t)B * C * hw, N, return_last ? 1 : N + 1, return_last, s, out};
 }
 
-// (the samplers' other entry checks are one statement each, in an order and with texts of their own: they stay with them)
-static inline int heun_check_workspace(const char* who, size_t have, size_t need) {
-  if (need > have) {
-    set_error("%s: workspace too small (%zu < %zu bytes)", who, have, need);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  return MCEDM_OK;
-}
-
 // trajectory slot `slot` <- x (0 after the init, i + 1 after step i); nothing with return_last, whose one store is the last
 static inline int heun_store_step(const HeunState& h, int slot) {
   return h.return_last ? MCEDM_OK : launch_heun_store(h.x, h.C, h.hw, slot, h.Tout, h.total, h.out, h.s);

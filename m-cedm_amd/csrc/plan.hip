@@ -554,6 +554,24 @@ Header header_for(const mcedm_plan& P, int B, int H, int W) {
   return h;
 }
 
+float* AdmNet::F() const { return at<float>(ws, hd.F); }
+float* AdmNet::Fu() const { return at<float>(ws, hd.Fu); }
+Coef* AdmNet::coef_in() const { return at<Coef>(ws, hd.coef_in); }
+float* AdmNet::c_noise() const { return at<float>(ws, hd.c_noise); }
+float* AdmNet::coefs4() const { return at<float>(ws, hd.coefs4); }
+
+void AdmNet::place(const void* packed, void* region, void* stream) {
+  pk = (const float*)packed; ws = (char*)region; act = ws + hd.total; s = (hipStream_t)stream;
+}
+
+int adm_sizes(const mcedm_plan& P, int B, int H, int W, int training, int n_noise, AdmNet* net, size_t* bytes) {
+  const int rc = build_layout(P, B, H, W, training, n_noise, &net->L);
+  if (rc) return rc;
+  net->plan = &P; net->hd = header_for(P, B, H, W);
+  net->B = B; net->H = H; net->W = W; net->n_noise = n_noise;
+  *bytes = net->hd.total + net->L.total_bytes;
+  return MCEDM_OK;
+}
 
 // ------------------------------------------------------------------------------------------
 // forward schedule (adm_blocks.py:364-404 and :159-181)
@@ -570,11 +588,22 @@ static int gn_for_conv(const GnArgs& g, ConvArgs& c, bool need_table, hipStream_
   return launch_gn_coef_from_sums(g, s);
 }
 
-static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl, const Layout& L, void* act,
-                     const float* pk, int B, int n_noise, hipStream_t s, std::vector<SumTiles>& st) {
-  auto T = [&](int id) -> float* { return id < 0 ? nullptr : at<float>(act, L.t[id].off); };
-  auto CF = [&](int id) -> Coef* { return id < 0 ? nullptr : at<Coef>(act, L.t[id].off); };
-  auto SUMS = [&](int id) -> float* { return (id < 0 || L.t[id].sums == NONE) ? nullptr : at<float>(act, L.t[id].sums); };
+// One conv of the schedule.  The caller then sets only what is particular to it: coef / act / resample, res / res_mode, the
+// sk_* fold fields.
+ConvArgs AdmNet::conv(const ConvP& cv, const float* xa, int Ca, const float* xb, int Cb, int Hs, int Ws, int H, int W, int dst,
+                      std::vector<SumTiles>& st) const {
+  ConvArgs c{};
+  c.xa = xa; c.Ca = Ca; c.xb = xb; c.Cb = Cb;
+  c.Hs = Hs; c.Ws = Ws; c.H = H; c.W = W;
+  c.wpk = pk + cv.wpk; c.bias = pk + cv.bias;
+  c.wino = cv.wino != NONE ? pk + cv.wino : nullptr;
+  c.out = T(dst); c.Cout = cv.cout; c.B = B;
+  c.gsum = SUMS(dst); c.gsum_tiles = c.gsum ? &st[dst] : nullptr;
+  return c;
+}
+
+int AdmNet::run_block(const BlockP& b, const BlockLayout& bl, std::vector<SumTiles>& st) const {
+  const mcedm_plan& P = *plan;
   auto TL = [&](int id) -> SumTiles { return id < 0 ? SumTiles{} : st[id]; };      // tiling of that tensor's statistics table
   const float* xa = T(bl.xa);
   const float* xb = T(bl.xb);
@@ -585,15 +614,9 @@ static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl
   GnArgs g0{xa, xb, Ca, Cb, bl.Hin * bl.Win, B, b.norm0.groups, pk + b.norm0.gamma, pk + b.norm0.beta,
             nullptr, 0, 0, eps, CF(bl.coef0), T(bl.stats0), SUMS(bl.xa), SUMS(bl.xb), TL(bl.xa), TL(bl.xb), bl.Win};
   // h = conv0(resample(silu(norm0(x))))
-  ConvArgs c0{};
-  c0.xa = xa; c0.xb = xb; c0.Ca = Ca; c0.Cb = Cb;
-  c0.coef = CF(bl.coef0); c0.coef_batch = 1; c0.act = 1;
   const int rs = b.up ? RS_UP : (b.down ? RS_DOWN : RS_NONE);
-  c0.resample = rs;
-  c0.Hs = bl.Hin; c0.Ws = bl.Win; c0.H = bl.H; c0.W = bl.W;
-  c0.wpk = pk + b.conv0.wpk; c0.bias = pk + b.conv0.bias;
-  c0.wino = b.conv0.wino != NONE ? pk + b.conv0.wino : nullptr;
-  c0.out = T(bl.h); c0.Cout = b.cout; c0.B = B; c0.gsum = SUMS(bl.h); c0.gsum_tiles = &st[bl.h];
+  ConvArgs c0 = conv(b.conv0, xa, Ca, xb, Cb, bl.Hin, bl.Win, bl.H, bl.W, bl.h, st);
+  c0.coef = CF(bl.coef0); c0.coef_batch = 1; c0.act = 1; c0.resample = rs;
   if ((rc = gn_for_conv(g0, c0, /*need_table=*/bl.xd >= 0, s))) return rc;
   if (bl.xd >= 0) {
     WgradArgs m{};
@@ -605,31 +628,23 @@ static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl
   }
   if ((rc = launch_conv(c0, 9, s))) return rc;
   // norm1 + FiLM -> transform table for conv1
-  const float* film = at<float>(act, L.t[L.film].off) + b.film_row0;
   GnArgs g1{T(bl.h), nullptr, b.cout, 0, bl.H * bl.W, B, b.norm1.groups, pk + b.norm1.gamma, pk + b.norm1.beta,
-            film, n_noise > 1 ? 1 : 0, P.film_rows, eps, CF(bl.coef1), T(bl.stats1), SUMS(bl.h), nullptr, TL(bl.h), SumTiles{}, bl.W};
+            film() + b.film_row0, coef_batch(), P.film_rows, eps, CF(bl.coef1), T(bl.stats1), SUMS(bl.h), nullptr, TL(bl.h), SumTiles{}, bl.W};
   // skip path
   const float* res = xa;
   int res_mode = RS_NONE;
   const bool fold_skip = b.skip_kernel == 1 && (bl.sk < 0 || bl.wfold);      // see build_layout
   if (b.skip_kernel == 1 && !fold_skip) {
-    ConvArgs cs{};
-    cs.xa = xa; cs.xb = xb; cs.Ca = Ca; cs.Cb = Cb;
-    cs.resample = rs; cs.Hs = bl.Hin; cs.Ws = bl.Win; cs.H = bl.H; cs.W = bl.W;
-    cs.wpk = pk + b.skip.wpk; cs.bias = pk + b.skip.bias;
-    cs.out = T(bl.sk); cs.Cout = b.cout; cs.B = B;
+    ConvArgs cs = conv(b.skip, xa, Ca, xb, Cb, bl.Hin, bl.Win, bl.H, bl.W, bl.sk, st);
+    cs.resample = rs;
     if ((rc = launch_conv(cs, 1, s))) return rc;
     res = T(bl.sk);
   } else if (b.skip_kernel == 0) {
     res_mode = rs;
   }
   // y = conv1(silu(film(norm1(h)))) + skip
-  ConvArgs c1{};
-  c1.xa = T(bl.h); c1.Ca = b.cout;
+  ConvArgs c1 = conv(b.conv1, T(bl.h), b.cout, nullptr, 0, bl.H, bl.W, bl.H, bl.W, bl.y, st);
   c1.coef = CF(bl.coef1); c1.coef_batch = 1; c1.act = 1;
-  c1.Hs = bl.H; c1.Ws = bl.W; c1.H = bl.H; c1.W = bl.W;
-  c1.wpk = pk + b.conv1.wpk; c1.bias = pk + b.conv1.bias;
-  c1.wino = b.conv1.wino != NONE ? pk + b.conv1.wino : nullptr;
   c1.res = res; c1.res_mode = res_mode;
   if (fold_skip) {            // y = conv1(...) + skip(orig): the projection rides on conv1 as extra K chunks
     c1.res = nullptr; c1.res_mode = RS_NONE;
@@ -637,7 +652,6 @@ static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl
     c1.sk_wpk = pk + b.skip.wpk; c1.sk_bias = pk + b.skip.bias;
     c1.sk_wfrag = b.skip.wfrag != NONE ? pk + b.skip.wfrag : nullptr;
   }
-  c1.out = T(bl.y); c1.Cout = b.cout; c1.B = B; c1.gsum = SUMS(bl.y); c1.gsum_tiles = &st[bl.y];
   if ((rc = gn_for_conv(g1, c1, false, s))) return rc;
   if ((rc = launch_conv(c1, 9, s))) return rc;
   if (!b.attn) return MCEDM_OK;
@@ -647,21 +661,13 @@ static int run_block(const mcedm_plan& P, const BlockP& b, const BlockLayout& bl
                                pk + b.qkv.bias, pk + b.proj.wpk, pk + b.proj.bias, SUMS(bl.z), &st[bl.z], B, s);
   GnArgs g2{T(bl.y), nullptr, b.cout, 0, bl.H * bl.W, B, b.norm2.groups, pk + b.norm2.gamma, pk + b.norm2.beta,
             nullptr, 0, 0, eps, CF(bl.coef2), T(bl.stats2), SUMS(bl.y), nullptr, TL(bl.y), SumTiles{}, bl.W};
-  ConvArgs cq{};
-  cq.xa = T(bl.y); cq.Ca = b.cout;
+  ConvArgs cq = conv(b.qkv, T(bl.y), b.cout, nullptr, 0, bl.H, bl.W, bl.H, bl.W, bl.qkv, st);
   cq.coef = CF(bl.coef2); cq.coef_batch = 1; cq.act = 0;
-  cq.Hs = bl.H; cq.Ws = bl.W; cq.H = bl.H; cq.W = bl.W;
-  cq.wpk = pk + b.qkv.wpk; cq.bias = pk + b.qkv.bias;
-  cq.out = T(bl.qkv); cq.Cout = 3 * b.cout; cq.B = B;
   if ((rc = gn_for_conv(g2, cq, false, s))) return rc;
   if ((rc = launch_conv(cq, 1, s))) return rc;
   if ((rc = launch_attention(T(bl.qkv), T(bl.a), B, b.heads, bl.H * bl.W, s))) return rc;
-  ConvArgs cp{};
-  cp.xa = T(bl.a); cp.Ca = b.cout;
-  cp.Hs = bl.H; cp.Ws = bl.W; cp.H = bl.H; cp.W = bl.W;
-  cp.wpk = pk + b.proj.wpk; cp.bias = pk + b.proj.bias;
+  ConvArgs cp = conv(b.proj, T(bl.a), b.cout, nullptr, 0, bl.H, bl.W, bl.H, bl.W, bl.z, st);
   cp.res = T(bl.y); cp.res_mode = RS_NONE;
-  cp.out = T(bl.z); cp.Cout = b.cout; cp.B = B; cp.gsum = SUMS(bl.z); cp.gsum_tiles = &st[bl.z];
   return launch_conv(cp, 1, s);
 }
 
@@ -690,81 +696,59 @@ int launch_gelu(const float* v, const float* g, float* out, size_t n, int mode, 
   return MCEDM_OK;
 }
 
-// act = start of the activation region (after the header)
-int forward_impl(const mcedm_plan& P, const Layout& L, const float* pk, const float* x, const float* dx, const float* cond,
-                 const Coef* coef_in, int coef_batch, const float* noise_labels, int n_noise, float* out,
-                 void* act, int B, int H, int W, hipStream_t s) {
+int AdmNet::forward(const AdmIn& in, float* out) const {
+  const mcedm_plan& P = *plan;
   const int ch = P.desc.ch;
   const int dxm = P.desc.dx_mode;
   int rc;
-  EmbArgs e{noise_labels, n_noise, ch, pk + P.freqs, pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1,
-            pk + P.waff, pk + P.baff, P.film_rows, nullptr, at<float>(act, L.t[L.film].off)};
+  EmbArgs e{in.noise_labels, n_noise, ch, pk + P.freqs, pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1,
+            pk + P.waff, pk + P.baff, P.film_rows, nullptr, T(L.film)};
   if ((rc = launch_embedding(e, s))) return rc;
   std::vector<SumTiles> st(L.t.size());     // tiling of each tensor's fused-statistics table
   // conv_in on cat(cond, x)  (cond FIRST, adm_blocks.py:332)
-  ConvArgs ci{};
-  ci.xa = cond; ci.Ca = P.desc.cond_channels;
-  ci.xb = x; ci.Cb = P.desc.in_channels;
+  const float* xb = in.x;
+  int Cb = P.desc.in_channels;
   if (dxm == MCEDM_DX_CAT) {         // cat(cond, x, dx): x and dx meet in one staging tensor (the kernels take two sources)
-    float* xdx = at<float>(act, L.t[L.xdx].off);
     const size_t hw = (size_t)H * W, total = (size_t)B * (P.desc.in_channels + P.desc.dx_channels) * hw;
     const size_t nb = (total + 255) / 256;
-    hipLaunchKernelGGL(concat_x_dx_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, s, x, dx, P.desc.in_channels,
-                       P.desc.dx_channels, hw, total, xdx);
+    hipLaunchKernelGGL(concat_x_dx_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, s, in.x, in.dx, P.desc.in_channels,
+                       P.desc.dx_channels, hw, total, T(L.xdx));
     MCEDM_LAUNCH_CHECK("concat_x_dx_kernel");
-    ci.xb = xdx; ci.Cb = P.desc.in_channels + P.desc.dx_channels;
+    xb = T(L.xdx); Cb = P.desc.in_channels + P.desc.dx_channels;
   }
-  ci.coef = coef_in; ci.coef_batch = coef_batch; ci.act = 0;
-  ci.Hs = H; ci.Ws = W; ci.H = H; ci.W = W;
-  ci.wpk = pk + P.conv_in.wpk; ci.bias = pk + P.conv_in.bias;
-  ci.out = at<float>(act, L.t[L.t0].off); ci.Cout = P.conv_in.cout; ci.B = B;
-  ci.gsum = at<float>(act, L.t[L.t0].sums); ci.gsum_tiles = &st[L.t0];
-  if (dxm == MCEDM_DX_ENC) { ci.out = at<float>(act, L.t[L.xf].off); ci.gsum = nullptr; ci.gsum_tiles = nullptr; }
+  // (conv_in and out_conv never take the Winograd kernel, whatever their channel counts)
+  ConvArgs ci = conv(P.conv_in, in.cond, P.desc.cond_channels, xb, Cb, H, W, H, W, dxm == MCEDM_DX_ENC ? L.xf : L.t0, st);
+  ci.wino = nullptr;
+  ci.coef = in.coef_in; ci.coef_batch = coef_batch(); ci.act = 0;
   if ((rc = launch_conv(ci, 9, s))) return rc;
   if (dxm == MCEDM_DX_ENC) {
     // x_feat = combine_enc(cat(conv_in(.), dx_enc(dx))), dx_enc = Conv3x3 -> GELU -> Conv3x3; dx None: zero features, NOT
     // dx_enc(0) (adm_blocks.py:352-362)
     const int c0 = P.conv_in.cout;
-    float* d2 = at<float>(act, L.t[L.d2].off);
-    auto plain = [&](const ConvP& cv, const float* xa, int Ca, const float* xb, int Cb, float* o) {
-      ConvArgs c{};
-      c.xa = xa; c.Ca = Ca; c.xb = xb; c.Cb = Cb;
-      c.Hs = H; c.Ws = W; c.H = H; c.W = W;
-      c.wpk = pk + cv.wpk; c.bias = pk + cv.bias;
-      c.wino = cv.wino != NONE ? pk + cv.wino : nullptr;
-      c.out = o; c.Cout = cv.cout; c.B = B;
-      return c;
-    };
-    if (dx) {
-      float* d1 = at<float>(act, L.t[L.d1].off);
-      float* g1 = at<float>(act, L.t[L.g1].off);
-      ConvArgs ca = plain(P.dx_enc0, dx, P.desc.dx_channels, nullptr, 0, d1);
+    if (in.dx) {
+      ConvArgs ca = conv(P.dx_enc0, in.dx, P.desc.dx_channels, nullptr, 0, H, W, H, W, L.d1, st);
       if ((rc = launch_conv(ca, 9, s))) return rc;
-      if ((rc = launch_gelu(d1, nullptr, g1, (size_t)B * c0 * H * W, 0, s))) return rc;
-      ConvArgs cb = plain(P.dx_enc2, g1, c0, nullptr, 0, d2);
+      if ((rc = launch_gelu(T(L.d1), nullptr, T(L.g1), (size_t)B * c0 * H * W, 0, s))) return rc;
+      ConvArgs cb = conv(P.dx_enc2, T(L.g1), c0, nullptr, 0, H, W, H, W, L.d2, st);
       if ((rc = launch_conv(cb, 9, s))) return rc;
     } else {
-      MCEDM_HIP_TRY(hipMemsetAsync(d2, 0, L.t[L.d2].bytes, s));
+      MCEDM_HIP_TRY(hipMemsetAsync(T(L.d2), 0, L.t[L.d2].bytes, s));
     }
-    ConvArgs cc = plain(P.combine, at<float>(act, L.t[L.xf].off), c0, d2, c0, at<float>(act, L.t[L.t0].off));
-    cc.gsum = at<float>(act, L.t[L.t0].sums); cc.gsum_tiles = &st[L.t0];
+    ConvArgs cc = conv(P.combine, T(L.xf), c0, T(L.d2), c0, H, W, H, W, L.t0, st);
     if ((rc = launch_conv(cc, 9, s))) return rc;
   }
   size_t bi = 0;
-  for (const BlockP& b : P.enc) if ((rc = run_block(P, b, L.blocks[bi++], L, act, pk, B, n_noise, s, st))) return rc;
-  for (const BlockP& b : P.dec) if ((rc = run_block(P, b, L.blocks[bi++], L, act, pk, B, n_noise, s, st))) return rc;
+  for (const BlockP& b : P.enc) if ((rc = run_block(b, L.blocks[bi++], st))) return rc;
+  for (const BlockP& b : P.dec) if ((rc = run_block(b, L.blocks[bi++], st))) return rc;
   // out = out_conv(silu(out_norm(x)))
   const TRef& last = L.t[L.last];
-  GnArgs go{at<float>(act, last.off), nullptr, last.C, 0, H * W, B, P.out_norm.groups, pk + P.out_norm.gamma,
-            pk + P.out_norm.beta, nullptr, 0, 0, 1e-5f, at<Coef>(act, L.t[L.coef_out].off),
-            L.stats_out >= 0 ? at<float>(act, L.t[L.stats_out].off) : nullptr,
-            last.sums != NONE ? at<float>(act, last.sums) : nullptr, nullptr, st[L.last], SumTiles{}, W};
-  ConvArgs co{};
-  co.xa = at<float>(act, last.off); co.Ca = last.C;
-  co.coef = at<Coef>(act, L.t[L.coef_out].off); co.coef_batch = 1; co.act = 1;
-  co.Hs = H; co.Ws = W; co.H = H; co.W = W;
-  co.wpk = pk + P.conv_out.wpk; co.bias = pk + P.conv_out.bias;
-  co.out = out; co.Cout = P.desc.out_channels; co.B = B;
+  GnArgs go{T(L.last), nullptr, last.C, 0, H * W, B, P.out_norm.groups, pk + P.out_norm.gamma,
+            pk + P.out_norm.beta, nullptr, 0, 0, 1e-5f, CF(L.coef_out), T(L.stats_out), SUMS(L.last), nullptr, st[L.last],
+            SumTiles{}, W};
+  ConvArgs co = conv(P.conv_out, T(L.last), last.C, nullptr, 0, H, W, H, W, -1, st);
+  co.wino = nullptr;
+  co.out = out;
+  co.coef = CF(L.coef_out); co.coef_batch = 1; co.act = 1;
   if ((rc = gn_for_conv(go, co, false, s))) return rc;
   return launch_conv(co, 9, s);
 }
@@ -776,31 +760,19 @@ __global__ void scale_to_coef_kernel(const float* __restrict__ x_scale, int n, i
   for (int c = 0; c < Ct; ++c) out[(size_t)i * Ct + c] = Coef{0.f, (c < cond_ch || c >= cond_ch + in_ch) ? 1.0f : x_scale[i], 0.f, 0.f};
 }
 
-// D = c_skip x + c_out F(c_in x; ln(sigma)/4; cond) with sigma from the device (n_sigma rows) or from the host
-int denoise_impl(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x, const float* dx,
-                 const float* sigma_dev, float sigma_host, int use_host, int n_sigma, const float* cond,
-                 float w, float* D_out, float* F_out, void* ws, int B, int H, int W, float sigma_data,
-                 hipStream_t s) {
+int denoise_impl(const AdmNet& net, const float* x, const float* dx, const float* cond, const float* sigma_dev, float sigma_host,
+                 float w, float sigma_data, float* D_out, float* F_out) {
+  const mcedm_unet_desc& d = net.plan->desc;
   int rc;
-  float* coefs4 = at<float>(ws, hd.coefs4);
-  float* c_noise = at<float>(ws, hd.c_noise);
-  Coef* coef_in = at<Coef>(ws, hd.coef_in);
-  float* Fbuf = at<float>(ws, hd.F);
-  void* act = at<char>(ws, hd.total);
-  if ((rc = launch_precond_prepare(sigma_dev, sigma_host, use_host, n_sigma, sigma_data, P.desc.cond_channels,
-                                   P.desc.in_channels, P.desc.dx_mode == MCEDM_DX_CAT ? P.desc.dx_channels : 0, coefs4, c_noise,
-                                   coef_in, s))) return rc;
-  if ((rc = forward_impl(P, L, pk, x, dx, cond, coef_in, n_sigma > 1 ? 1 : 0, c_noise, n_sigma, Fbuf, act, B, H, W, s))) return rc;
-  const float* Fu = nullptr;
+  if ((rc = launch_precond_prepare(sigma_dev, sigma_host, sigma_dev ? 0 : 1, net.n_noise, sigma_data, d.cond_channels, d.in_channels,
+                                   d.dx_mode == MCEDM_DX_CAT ? d.dx_channels : 0, net.coefs4(), net.c_noise(), net.coef_in(),
+                                   net.s))) return rc;
   // classifier-free branch, mcedm.py:453-458; models/ddim.py:1755-1760: taken when cond OR dx is given, and the
   // unconditional evaluation drops both
-  if (fabsf(w) >= 0.001f && (cond != nullptr || dx != nullptr)) {
-    float* Fubuf = at<float>(ws, hd.Fu);
-    if ((rc = forward_impl(P, L, pk, x, nullptr, nullptr, coef_in, n_sigma > 1 ? 1 : 0, c_noise, n_sigma, Fubuf, act, B, H, W, s))) return rc;
-    Fu = Fubuf;
-  }
-  const size_t per = (size_t)P.desc.out_channels * H * W;
-  return launch_precond_finish(x, Fbuf, Fu, w, coefs4, n_sigma, per, per * B, D_out, F_out, s);
+  float* Fu = fabsf(w) >= 0.001f && (cond != nullptr || dx != nullptr) ? net.Fu() : nullptr;
+  if ((rc = net.forward_cfg(AdmIn{x, dx, cond, net.coef_in(), net.c_noise()}, net.F(), Fu))) return rc;
+  const size_t per = (size_t)d.out_channels * net.H * net.W;
+  return launch_precond_finish(x, net.F(), Fu, w, net.coefs4(), net.n_noise, per, per * net.B, D_out, F_out, net.s);
 }
 
 }  // namespace mcedm
@@ -808,11 +780,10 @@ int denoise_impl(const mcedm_plan& P, const Layout& L, const Header& hd, const f
 extern "C" int mcedm_unet_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, int training, size_t* bytes) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && bytes, "workspace_bytes: null argument");
-  Layout L;
-  int rc = build_layout(*plan, B, H, W, training, B, &L);
-  if (rc) return rc;
-  *bytes = header_for(*plan, B, H, W).total + L.total_bytes + (training ? backward_scratch_bytes(*plan, L, B, H, W) : 0);
-  return MCEDM_OK;
+  AdmNet net;
+  const int rc = adm_sizes(*plan, B, H, W, training, B, &net, bytes);
+  if (rc == MCEDM_OK && training) *bytes += backward_scratch_bytes(*plan, net.L, B, H, W);
+  return rc;
 }
 
 extern "C" int mcedm_unet_forward_dx(const mcedm_plan* plan, const void* packed, const float* x, const float* dx, const float* cond,
@@ -822,26 +793,18 @@ extern "C" int mcedm_unet_forward_dx(const mcedm_plan* plan, const void* packed,
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && packed && x && noise_labels && out && workspace, "unet_forward: null argument");
   MCEDM_REQUIRE(dx == nullptr || plan->desc.dx_mode != MCEDM_DX_NONE, "unet_forward: dx given to a plan without dx_cond");
-  Layout L;
-  int rc = build_layout(*plan, B, H, W, training, n_noise, &L);
+  AdmNet net;
+  const int rc = adm_bind("unet_forward", *plan, packed, workspace, workspace_bytes, 0, no_extra, B, H, W, training, n_noise, stream, &net);
   if (rc) return rc;
-  const Header hd = header_for(*plan, B, H, W);
-  if (hd.total + L.total_bytes > workspace_bytes) {
-    set_error("unet_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, hd.total + L.total_bytes);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const Coef* coef_in = nullptr;
+  AdmIn in{x, dx, cond, nullptr, noise_labels};
   if (x_scale) {
-    Coef* c = at<Coef>(workspace, hd.coef_in);
-    hipLaunchKernelGGL(scale_to_coef_kernel, dim3(ceil_div(n_noise, 64)), dim3(64), 0, s, x_scale, n_noise,
+    hipLaunchKernelGGL(scale_to_coef_kernel, dim3(ceil_div(n_noise, 64)), dim3(64), 0, net.s, x_scale, n_noise,
                        plan->desc.cond_channels, plan->desc.in_channels,
-                       plan->desc.dx_mode == MCEDM_DX_CAT ? plan->desc.dx_channels : 0, c);
+                       plan->desc.dx_mode == MCEDM_DX_CAT ? plan->desc.dx_channels : 0, net.coef_in());
     MCEDM_LAUNCH_CHECK("scale_to_coef_kernel");
-    coef_in = c;
+    in.coef_in = net.coef_in();
   }
-  return forward_impl(*plan, L, (const float*)packed, x, dx, cond, coef_in, n_noise > 1 ? 1 : 0, noise_labels, n_noise, out,
-                      at<char>(workspace, hd.total), B, H, W, s);
+  return net.forward(in, out);
 }
 
 extern "C" int mcedm_unet_forward(const mcedm_plan* plan, const void* packed, const float* x, const float* cond,
@@ -860,16 +823,9 @@ extern "C" int mcedm_edm_denoise_dx(const mcedm_plan* plan, const void* packed, 
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && packed && x && sigma && D_out && workspace, "edm_denoise: null argument");
   MCEDM_REQUIRE(dx == nullptr || plan->desc.dx_mode != MCEDM_DX_NONE, "edm_denoise: dx given to a plan without dx_cond");
-  Layout L;
-  int rc = build_layout(*plan, B, H, W, training, n_sigma, &L);
-  if (rc) return rc;
-  const Header hd = header_for(*plan, B, H, W);
-  if (hd.total + L.total_bytes > workspace_bytes) {
-    set_error("edm_denoise: workspace too small (%zu < %zu bytes)", workspace_bytes, hd.total + L.total_bytes);
-    return MCEDM_ERR_WORKSPACE;
-  }
-  return denoise_impl(*plan, L, hd, (const float*)packed, x, dx, sigma, 0.f, 0, n_sigma, cond, 0.f, D_out, F_out, workspace,
-                      B, H, W, (float)sigma_data, (hipStream_t)stream);
+  AdmNet net;
+  const int rc = adm_bind("edm_denoise", *plan, packed, workspace, workspace_bytes, 0, no_extra, B, H, W, training, n_sigma, stream, &net);
+  return rc ? rc : denoise_impl(net, x, dx, cond, sigma, 0.f, 0.f, (float)sigma_data, D_out, F_out);
 }
 
 extern "C" int mcedm_edm_denoise(const mcedm_plan* plan, const void* packed, const float* x, const float* sigma,

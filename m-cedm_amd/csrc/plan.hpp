@@ -197,15 +197,90 @@ Header header_for(const mcedm_plan& P, int B, int H, int W);
 template <class T>
 static inline T* at(void* ws, size_t off) { return reinterpret_cast<T*>(reinterpret_cast<char*>(ws) + off); }
 
-// plan.hip's forward and EDM denoise, as the samplers (sampler.hip) call them.  act = start of the activation region
-// (after the header); ws = start of the header.
-int forward_impl(const mcedm_plan& P, const Layout& L, const float* pk, const float* x, const float* dx, const float* cond,
-                 const Coef* coef_in, int coef_batch, const float* noise_labels, int n_noise, float* out,
-                 void* act, int B, int H, int W, hipStream_t s);
-int denoise_impl(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x, const float* dx,
-                 const float* sigma_dev, float sigma_host, int use_host, int n_sigma, const float* cond,
-                 float w, float* D_out, float* F_out, void* ws, int B, int H, int W, float sigma_data,
-                 hipStream_t s);
+// the one text of a workspace that is too small, for every entry of either network; `who` names the entry
+static inline int heun_check_workspace(const char* who, size_t have, size_t need) {
+  if (need > have) {
+    set_error("%s: workspace too small (%zu < %zu bytes)", who, have, need);
+    return MCEDM_ERR_WORKSPACE;
+  }
+  return MCEDM_OK;
+}
+
+// One evaluation's inputs: conv_in reads cat(cond, x[, dx]) scaled by the rows of coef_in (null = identity); cond and dx are
+// optional (null: None).
+struct AdmIn {
+  const float* x = nullptr;
+  const float* dx = nullptr;
+  const float* cond = nullptr;
+  const Coef* coef_in = nullptr;
+  const float* noise_labels = nullptr;
+};
+
+// A plan bound to its packed weights, its region of a workspace (header, then activations), a shape and a stream.  The
+// schedule and the header's offsets are plan.hip's; the samplers (sampler.hip) and the backward (backward.hip) go through
+// the members.
+struct AdmNet {
+  const mcedm_plan* plan = nullptr;
+  const float* pk = nullptr;
+  Layout L;
+  Header hd{};
+  char* ws = nullptr;          // start of the network's region (its header)
+  char* act = nullptr;         // start of the activations behind the header
+  int B = 0, H = 0, W = 0, n_noise = 0;
+  hipStream_t s = nullptr;
+
+  int coef_batch() const { return n_noise > 1 ? 1 : 0; }      // per-sample rows (film, coef_in) with one label per sample
+  float* T(int id) const { return id < 0 ? nullptr : reinterpret_cast<float*>(act + L.t[id].off); }
+  Coef* CF(int id) const { return id < 0 ? nullptr : reinterpret_cast<Coef*>(act + L.t[id].off); }
+  float* SUMS(int id) const { return (id < 0 || L.t[id].sums == NONE) ? nullptr : reinterpret_cast<float*>(act + L.t[id].sums); }
+  const float* film() const { return T(L.film); }
+  // the header: network output with and without its conditioning, conv_in's rows, the noise labels and the EDM (c_skip, c_out, ..) rows
+  float* F() const;
+  float* Fu() const;
+  Coef* coef_in() const;
+  float* c_noise() const;
+  float* coefs4() const;
+
+  void place(const void* packed, void* region, void* stream);
+  // one conv of the schedule: weights `cv`, sources xa | xb at Hs x Ws, output tensor `dst` at H x W with that tensor's
+  // fused-statistics table if it has one (dst < 0: the caller sets `out`)
+  ConvArgs conv(const ConvP& cv, const float* xa, int Ca, const float* xb, int Cb, int Hs, int Ws, int H, int W, int dst,
+                std::vector<SumTiles>& st) const;
+  int run_block(const BlockP& b, const BlockLayout& bl, std::vector<SumTiles>& st) const;
+  int forward(const AdmIn& in, float* out) const;
+  // F <- the network on `in`; Fu (unless null) <- the same without cond and dx: the two passes of classifier-free guidance
+  int forward_cfg(AdmIn in, float* F, float* Fu) const {
+    const int rc = forward(in, F);
+    if (rc || !Fu) return rc;
+    in.cond = in.dx = nullptr;
+    return forward(in, Fu);
+  }
+};
+
+// *net <- (P, shape, layout, header offsets), *bytes <- what the network needs of a workspace: header + activations.
+// Three facts about who lays out how: the size queries lay out with n_noise = B; the samplers with n_noise = 1 and
+// training = 0; mcedm_unet_forward_dx and mcedm_edm_denoise_dx with their own n_noise / n_sigma and their training flag, and
+// they check header + activations only, not the backward's scratch (which the training size query adds and the backward checks).
+int adm_sizes(const mcedm_plan& P, int B, int H, int W, int training, int n_noise, AdmNet* net, size_t* bytes);
+
+// The one place that knows the workspace layout: `front_bytes` of the caller's own buffers (a sampler's), then the network's
+// header and activations, then extra_bytes(net) of the caller's behind them (the backward's scratch, sized from the layout).
+template <class Extra>
+static inline int adm_bind(const char* who, const mcedm_plan& P, const void* packed, void* workspace, size_t workspace_bytes,
+                           size_t front_bytes, Extra&& extra_bytes, int B, int H, int W, int training, int n_noise, void* stream,
+                           AdmNet* net) {
+  int rc;
+  size_t need = 0;
+  if ((rc = adm_sizes(P, B, H, W, training, n_noise, net, &need))) return rc;
+  if ((rc = heun_check_workspace(who, workspace_bytes, front_bytes + need + extra_bytes(*net)))) return rc;
+  net->place(packed, at<char>(workspace, front_bytes), stream);
+  return MCEDM_OK;
+}
+static inline size_t no_extra(const AdmNet&) { return 0; }
+
+// D = c_skip x + c_out F(c_in x; ln(sigma)/4; cond) with sigma from the device (net.n_noise rows) or, null, from the host
+int denoise_impl(const AdmNet& net, const float* x, const float* dx, const float* cond, const float* sigma_dev, float sigma_host,
+                 float w, float sigma_data, float* D_out, float* F_out);
 
 // bytes the backward needs behind the training-mode activations (gradient buffers + scratch)
 size_t backward_scratch_bytes(const mcedm_plan& P, const Layout& L, int B, int H, int W);

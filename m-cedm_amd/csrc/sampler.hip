@@ -66,15 +66,11 @@ static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mc
     gammas[i] = in_range ? std::min(sp->S_churn / N, std::sqrt(2.0) - 1.0) : 0.0;
     MCEDM_REQUIRE(gammas[i] == 0.0 || step_noise != nullptr || rng_seed != nullptr, "heun_sample: S_churn > 0 needs step_noise (or mcedm_heun_sample_rng)");
   }
-  Layout L;
-  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
-  const Header hd = header_for(P, B, H, W);
   const SamplerBufs sb = sampler_bufs(P, B, H, W);
-  if ((rc = heun_check_workspace("heun_sample", workspace_bytes, sb.total + hd.total + L.total_bytes))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
+  AdmNet net;
+  if ((rc = adm_bind("heun_sample", P, packed, workspace, workspace_bytes, sb.total, no_extra, B, H, W, 0, 1, stream, &net))) return rc;
+  hipStream_t s = net.s;
   HeunState h = heun_state(workspace, sb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, s);
-  void* uws = at<char>(workspace, sb.total);
   const float w = (float)sp->w;
   const float sd = (float)sp->sigma_data;
   float* gscratch = at<float>(workspace, sb.g);
@@ -86,7 +82,7 @@ static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mc
   auto denoise = [&](double sigma, bool) -> int {
     int e = dxc ? guidance_dx(P.desc.cond_channels, *dxc, cond, h.x32, dxin, gscratch, B, H, W, s) : MCEDM_OK;
     if (e) return e;
-    e = denoise_impl(P, L, hd, pk, h.x32, dxin, nullptr, (float)sigma, 1, 1, cond, w, h.D, nullptr, uws, B, H, W, sd, s);
+    e = denoise_impl(net, h.x32, dxin, cond, nullptr, (float)sigma, w, sd, h.D, nullptr);
     if (e) return e;
     return gd ? guidance_dx(P.desc.cond_channels, *gd, cond, h.D, dxg, gscratch, B, H, W, s) : MCEDM_OK;
   };
@@ -207,24 +203,15 @@ static VpBufs vp_bufs(const mcedm_plan& P, int B, int H, int W) {
 }
 
 // get_denoised (models/ddim.py:915-947) at one noise level: D = x + (-sigma) F(c_in cat(cond', x), c_noise)
-static int vp_denoise(const mcedm_plan& P, const Layout& L, const Header& hd, const float* pk, const float* x32, const float* condp,
-                      double sigma_d, float c_noise, double w, float* D, void* ws, int B, int H, int W, hipStream_t s) {
+static int vp_denoise(const AdmNet& net, const float* x32, const float* condp, double sigma_d, float c_noise, double w, float* D) {
+  const mcedm_unet_desc& d = net.plan->desc;
   int rc;
   const float sigma = (float)sigma_d;                                   // t.to(torch.float32)
   const float c_in = 1.0f / sqrtf(sigma * sigma + 1.0f);                // 1 / (sigma ** 2 + 1).sqrt(), fp32
-  Coef* coef_in = at<Coef>(ws, hd.coef_in);
-  float* label = at<float>(ws, hd.c_noise);
-  float* F = at<float>(ws, hd.F);
-  void* act = at<char>(ws, hd.total);
-  if ((rc = launch_vp_prepare(c_in, P.desc.cond_channels + P.desc.in_channels, c_noise, coef_in, label, s))) return rc;
-  if ((rc = forward_impl(P, L, pk, x32, nullptr, condp, coef_in, 0, label, 1, F, act, B, H, W, s))) return rc;
-  const float* Fu = nullptr;
-  if (std::fabs(w) >= 0.001 && condp != nullptr) {                     // :938-942, the second evaluation without cond
-    float* Fub = at<float>(ws, hd.Fu);
-    if ((rc = forward_impl(P, L, pk, x32, nullptr, nullptr, coef_in, 0, label, 1, Fub, act, B, H, W, s))) return rc;
-    Fu = Fub;
-  }
-  return launch_vp_cfg_finish(x32, F, Fu, w, sigma, (size_t)B * P.desc.out_channels * H * W, D, s);
+  if ((rc = launch_vp_prepare(c_in, d.cond_channels + d.in_channels, c_noise, net.coef_in(), net.c_noise(), net.s))) return rc;
+  float* Fu = std::fabs(w) >= 0.001 && condp != nullptr ? net.Fu() : nullptr;      // :938-942, the second evaluation without cond
+  if ((rc = net.forward_cfg(AdmIn{x32, nullptr, condp, net.coef_in(), net.c_noise()}, net.F(), Fu))) return rc;
+  return launch_vp_cfg_finish(x32, net.F(), Fu, w, sigma, (size_t)net.B * d.out_channels * net.H * net.W, D, net.s);
 }
 }  // namespace mcedm
 
@@ -250,15 +237,10 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
   MCEDM_REQUIRE(cond == nullptr || sp->cond_channels > 0, "vp_heun_sample: cond given with cond_channels 0");
   if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
   const int N = sp->timesteps;
-  Layout L;
-  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
-  const Header hd = header_for(P, B, H, W);
   const VpBufs vb = vp_bufs(P, B, H, W);
-  if ((rc = heun_check_workspace("vp_heun_sample", workspace_bytes, vb.total + hd.total + L.total_bytes))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
-  HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, s);
-  void* uws = at<char>(workspace, vb.total);
+  AdmNet net;
+  if ((rc = adm_bind("vp_heun_sample", P, packed, workspace, workspace_bytes, vb.total, no_extra, B, H, W, 0, 1, stream, &net))) return rc;
+  HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, net.s);
   // cond' once per call: cond in its channels, zeros in the self-conditioning ones (get_self_cond_edm returns None)
   const float* condp = cond;
   if (cond && sp->cond_channels < P.desc.cond_channels) {
@@ -268,7 +250,7 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
     condp = st;
   }
   return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma, float c_noise) {
-    return vp_denoise(P, L, hd, pk, h.x32, condp, sigma, c_noise, sp->w, h.D, uws, B, H, W, s);
+    return vp_denoise(net, h.x32, condp, sigma, c_noise, sp->w, h.D);
   });
 }
 
@@ -310,9 +292,9 @@ static CondDdimBufs cond_ddim_bufs(const mcedm_plan& P, int B, int H, int W) {
 extern "C" int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(plan && bytes, "cond_ddim_workspace_bytes: null argument");
-  Layout L;                              // one noise label for the whole batch, as the sampler lays its forward out
-  const int rc = build_layout(*plan, B, H, W, 0, 1, &L);
-  if (rc == MCEDM_OK) *bytes = cond_ddim_bufs(*plan, B, H, W).total + header_for(*plan, B, H, W).total + L.total_bytes;
+  AdmNet net;                            // one noise label for the whole batch, as the sampler lays its forward out
+  const int rc = adm_sizes(*plan, B, H, W, 0, 1, &net, bytes);
+  if (rc == MCEDM_OK) *bytes += cond_ddim_bufs(*plan, B, H, W).total;
   return rc;
 }
 
@@ -333,18 +315,11 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
                 cc, C, Cp);
   if ((rc = cond_ddim_check_schedule(sp, eta_noise, rng_seed))) return rc;
   const bool guided = cond_ddim_guided(sp);
-  Layout L;
-  if ((rc = build_layout(P, B, H, W, 0, 1, &L))) return rc;
-  const Header hd = header_for(P, B, H, W);
   const CondDdimBufs cb = cond_ddim_bufs(P, B, H, W);
-  if ((rc = heun_check_workspace("cond_ddim_sample", workspace_bytes, cb.total + hd.total + L.total_bytes))) return rc;
+  AdmNet net;
+  if ((rc = adm_bind("cond_ddim_sample", P, packed, workspace, workspace_bytes, cb.total, no_extra, B, H, W, 0, 1, stream, &net))) return rc;
   const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
-  hipStream_t s = (hipStream_t)stream;
-  const float* pk = (const float*)packed;
-  void* uws = at<char>(workspace, cb.total);
-  float* label = at<float>(uws, hd.c_noise);
-  Coef* coef_in = at<Coef>(uws, hd.coef_in);
-  void* act = at<char>(uws, hd.total);
+  hipStream_t s = net.s;
   // cond' once per call: cond in its channels, zeros in the others (x_self_cond is None in the first step); the step kernel
   // keeps the self-conditioning channels current from then on.  Guided: the twin with zeros for cond as well.
   float* condp = Cp > 0 ? at<float>(workspace, cb.condp) : nullptr;
@@ -358,9 +333,11 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
   // the network sees xt itself (no c_in on this path: conv_in rows scaled by 1) under the label t
   return cond_ddim_loop(sp, lp, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, s, [&](const float* xt, float t, int) -> int {
     int e;
-    if ((e = launch_vp_prepare(1.0f, Cp + C, t, coef_in, label, s))) return e;
-    if ((e = forward_impl(P, L, pk, xt, nullptr, condp, coef_in, 0, label, 1, lp.F, act, B, H, W, s))) return e;
-    return guided ? forward_impl(P, L, pk, xt, nullptr, condu, coef_in, 0, label, 1, lp.Fu, act, B, H, W, s) : MCEDM_OK;
+    if ((e = launch_vp_prepare(1.0f, Cp + C, t, net.coef_in(), net.c_noise(), s))) return e;
+    AdmIn in{xt, nullptr, condp, net.coef_in(), net.c_noise()};
+    if ((e = net.forward(in, lp.F)) || !guided) return e;
+    in.cond = condu;                  // (not forward_cfg: the twin keeps the self-conditioning channels, only cond is zeros)
+    return net.forward(in, lp.Fu);
   });
 }
 

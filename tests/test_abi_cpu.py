@@ -102,6 +102,155 @@ def test_host_side_argument_validation():
         plan.forward(torch.zeros(8), torch.zeros(1, 2, 32, 32), torch.zeros(1))
 
 
+def _last():
+    return L.load().mcedm_last_error().decode()
+
+
+def _up(nbytes):
+    return (nbytes + 255) // 256 * 256
+
+
+def test_host_side_rejections_of_the_adm_entries():
+    """mcedm_unet_forward(_dx), mcedm_edm_denoise(_dx), the Heun samplers (plain, _rng, _guided, _dxcond), mcedm_vp_heun_sample,
+    mcedm_cond_ddim_sample, mcedm_edm_denoise_backward(_dx), mcedm_unet_backward and the four size queries: the return code and
+    the exact text for a null plan / packed / workspace, B = 0, H off the plan's grid, n_noise neither 1 nor B, a workspace one
+    byte short (both byte counts named; the backward's include its scratch), dx on a plan without dx_cond, and which check speaks
+    when two fail at once.  All on the host, before any launch: the dummy pointers are never dereferenced.
+
+    The bytes an entry needs come from the size queries alone.  A query lays the network out with n_noise = B, the samplers with
+    one label for the batch, as mcedm_cond_ddim_workspace_bytes does: what that query reports minus the DDIM sampler's own six
+    buffers is the network at n_noise = 1, and a sampler's query minus mcedm_unet_workspace_bytes is that sampler's own buffers."""
+    from types import SimpleNamespace
+    lib = L.load()
+    mk = lambda c, **kw: L.Plan(c, c, c, 64, (1, 1, 1), 1, (32,), 128, **kw)      # noqa: E731
+    joint, single, dxp = mk(2), mk(1), mk(1, dx_channels=1, dx_mode=L.DX_ENC)
+    one = C.c_void_p(4096)
+    B, H, W = 3, 32, 32
+    vpp = C.POINTER(C.c_void_p)
+    ptrs = lambda p: C.cast((C.c_void_p * len(p.param_names))(*[4096] * len(p.param_names)), vpp)      # noqa: E731
+    mk_sd = lambda N: L.sampler_desc(orc.SamplerParams(timesteps=N))      # noqa: E731
+    gd = L.GuidanceDesc(1, 0.002, 0.03125, 0.0, 0.0, 1.0, 0.0, 1.0, 5.0)
+    def mk_vd(N, cc):             # two steps' tables, of which the sampler is told to walk N
+        d = L.vp_sampler_desc(2, cc, [5.0, 1.0, 0.0], [5.0, 1.0], [900.0, 800.0, 700.0, 0.0], 1.0, 0.0)
+        d.timesteps = N
+        return d
+    ae = torch.linspace(1.0, 0.1, 11)
+    mk_cd = lambda N, cc: L.cond_ddim_desc(SimpleNamespace(timesteps=N, skip_type="uniform", eta=0.0, w=0.0), ae, cc, False)      # noqa: E731
+
+    def net_bytes(p, n):          # header + activations of the inference layout with n noise labels
+        if n == B:
+            return p.workspace_bytes(B, H, W)
+        hw4 = H * W * 4
+        own = 2 * _up(B * p.in_channels * hw4) + 2 * _up(B * p.out_channels * hw4) + 2 * _up(B * p.cond_channels * hw4)
+        return p.cond_ddim_workspace_bytes(B, H, W) - own
+
+    for p in (joint, single, dxp):
+        state = B * p.in_channels * H * W
+        heun = 3 * _up(state * 8) + 2 * _up(state * 4)
+        assert net_bytes(p, 1) < net_bytes(p, B)
+        assert p.sampler_workspace_bytes(B, H, W) - p.workspace_bytes(B, H, W) == heun + 3 * _up(state * 4)
+        assert p.vp_sampler_workspace_bytes(B, H, W) - p.workspace_bytes(B, H, W) == heun + _up(B * p.cond_channels * H * W * 4)
+
+    def own_bytes(p, query):
+        return getattr(p, query)(B, H, W) - p.workspace_bytes(B, H, W)
+
+    # name -> (who in the shared texts, text of a null plan, plan, bytes needed with n labels, call(plan, packed, workspace, bytes, B, H, n))
+    guided_text = ("heun_sample_guided: PDE guidance is defined for the single-task sampler (state u, conditioning h in cond[:, 0]; "
+                   "mask NULL), models/ddim.py:1532-1601; the joint model's hook fails in the reference (models/mcedm.py:500-518)")
+    dxcond_text = ("heun_sample_dxcond: needs a dx_cond plan of the single-task model (state u, conditioning h in cond[:, 0], one dx "
+                   "channel), models/ddim.py:1424-1450, 1532-1601")
+    sd, vd2, vd1, cd2, cd1 = mk_sd(3), mk_vd(2, 2), mk_vd(2, 1), mk_cd(3, 2), mk_cd(3, 1)
+    heun_need = lambda p: lambda n: own_bytes(p, "sampler_workspace_bytes") + net_bytes(p, 1)      # noqa: E731
+    entries = {
+        "unet_forward": ("unet_forward", None, joint, lambda n: net_bytes(joint, n), lambda p, pk, ws, nb, b, h, n:
+                         lib.mcedm_unet_forward(p, pk, one, one, None, one, n, one, ws, nb, b, h, W, 0, None)),
+        "unet_forward_dx": ("unet_forward", None, dxp, lambda n: net_bytes(dxp, n), lambda p, pk, ws, nb, b, h, n:
+                            lib.mcedm_unet_forward_dx(p, pk, one, one, one, one, one, n, one, ws, nb, b, h, W, 0, None)),
+        "edm_denoise": ("edm_denoise", None, joint, lambda n: net_bytes(joint, n), lambda p, pk, ws, nb, b, h, n:
+                        lib.mcedm_edm_denoise(p, pk, one, one, n, one, one, None, ws, nb, b, h, W, 0, 0.5, None)),
+        "edm_denoise_dx": ("edm_denoise", None, dxp, lambda n: net_bytes(dxp, n), lambda p, pk, ws, nb, b, h, n:
+                           lib.mcedm_edm_denoise_dx(p, pk, one, one, one, n, one, one, None, ws, nb, b, h, W, 0, 0.5, None)),
+        "heun_sample": ("heun_sample", None, joint, heun_need(joint), lambda p, pk, ws, nb, b, h, n, d=sd:
+                        lib.mcedm_heun_sample(p, pk, C.byref(d), one, one, one, one, one, 1, ws, nb, b, h, W, None)),
+        "heun_sample_rng": ("heun_sample", None, joint, heun_need(joint), lambda p, pk, ws, nb, b, h, n, d=sd:
+                            lib.mcedm_heun_sample_rng(p, pk, C.byref(d), one, one, one, one, one, 1, ws, nb, b, h, W, None)),
+        "heun_sample_guided": ("heun_sample", guided_text, single, heun_need(single), lambda p, pk, ws, nb, b, h, n, d=sd:
+                               lib.mcedm_heun_sample_guided(p, pk, C.byref(d), C.byref(gd), one, None, one, one, one, 1, ws, nb, b,
+                                                            h, W, None)),
+        "heun_sample_dxcond": ("heun_sample", dxcond_text, dxp, heun_need(dxp), lambda p, pk, ws, nb, b, h, n, d=sd:
+                               lib.mcedm_heun_sample_dxcond(p, pk, C.byref(d), C.byref(gd), None, one, one, one, one, 1, ws, nb, b,
+                                                            h, W, None)),
+        "vp_heun_sample": ("vp_heun_sample", None, joint, lambda n: own_bytes(joint, "vp_sampler_workspace_bytes") + net_bytes(joint, 1),
+                           lambda p, pk, ws, nb, b, h, n, d=vd2:
+                           lib.mcedm_vp_heun_sample(p, pk, C.byref(d), one, one, None, one, 1, ws, nb, b, h, W, None)),
+        "cond_ddim_sample": ("cond_ddim_sample", None, joint, lambda n: joint.cond_ddim_workspace_bytes(B, H, W),
+                             lambda p, pk, ws, nb, b, h, n, d=cd2:
+                             lib.mcedm_cond_ddim_sample(p, pk, C.byref(d), one, one, None, one, one, 1, ws, nb, b, h, W, None)),
+        "edm_denoise_backward": ("denoise_backward", None, joint, lambda n: joint.workspace_bytes(B, H, W, True),
+                                 lambda p, pk, ws, nb, b, h, n, g=ptrs(joint):
+                                 lib.mcedm_edm_denoise_backward(p, pk, g, one, one, n, one, one, g, ws, nb, b, h, W, 0.5, None)),
+        "unet_backward": ("denoise_backward", None, joint, lambda n: joint.workspace_bytes(B, H, W, True),
+                          lambda p, pk, ws, nb, b, h, n, g=ptrs(joint):
+                          lib.mcedm_unet_backward(p, pk, g, one, one, None, one, n, one, g, ws, nb, b, h, W, None)),
+    }
+    samplers = [k for k in entries if "sample" in k]
+    for name, (who, null_plan, plan, need_of, call) in entries.items():
+        need = need_of(B)
+        assert call(None, one, one, need, B, H, B) == -1 and _last() == (null_plan or f"{who}: null argument"), name
+        for args in ((plan._h, None, one), (plan._h, one, None)):
+            assert call(*args, need, B, H, B) == -1 and _last() == f"{who}: null argument", (name, args)
+        assert call(plan._h, one, one, need, 0, H, 0) == -1 and _last() == f"layout: empty shape B=0 H={H} W={W}", name
+        assert call(plan._h, one, one, need, B, 30, B) == -1, name
+        assert _last() == f"layout: H=30 W={W} must be multiples of 4 (2^(levels-1))", name
+        for n in ((B,) if name in samplers or "backward" in name else (B, 1)):
+            need = need_of(n)
+            assert call(plan._h, one, one, need - 1, B, H, n) == -3, (name, n)
+            assert _last() == f"{who}: workspace too small ({need - 1} < {need} bytes)", (name, n)
+        if name not in samplers:        # (the samplers take no n_noise: one label for the batch)
+            assert call(plan._h, one, one, need, B, H, 2) == -1 and _last() == f"layout: n_noise=2 must be 1 or B={B}", name
+            # two at once: the shape speaks before n_noise, and both before the workspace
+            assert call(plan._h, one, one, 0, B, 30, 2) == -1 and "must be multiples of 4" in _last(), name
+            assert call(plan._h, one, one, 0, B, H, 2) == -1 and "n_noise=2 must be 1 or B=3" in _last(), name
+        assert call(plan._h, one, one, 0, 0, H, 0) == -1 and _last() == f"layout: empty shape B=0 H={H} W={W}", name
+    # the backward's bytes include its scratch behind the training-mode activations
+    assert joint.workspace_bytes(B, H, W, True) > joint.workspace_bytes(B, H, W)
+    # dx given to a plan without dx_cond: it speaks before the layout and the workspace
+    g = ptrs(single)
+    for who, call in (("unet_forward", lambda b, nb: lib.mcedm_unet_forward_dx(single._h, one, one, one, one, None, one, b, one, one,
+                                                                                nb, b, H, W, 0, None)),
+                      ("edm_denoise", lambda b, nb: lib.mcedm_edm_denoise_dx(single._h, one, one, one, one, b, one, one, None, one, nb, b,
+                                                                             H, W, 0, 0.5, None)),
+                      ("denoise_backward", lambda b, nb: lib.mcedm_edm_denoise_backward_dx(single._h, one, g, one, one, one, b, one, one,
+                                                                                           g, one, nb, b, H, W, 0.5, 0, None, None, None))):
+        for b, nb in ((B, 1 << 30), (0, 0)):
+            assert call(b, nb) == -1 and _last() == f"{who}: dx given to a plan without dx_cond", (who, b)
+    # two at once on the samplers: a bad schedule speaks before a zero-byte workspace.  The EDM schedule divides by timesteps - 1,
+    # so 1 is bad there; the VP and DDIM schedules hold from 1 step on (there the workspace speaks) and are bad at 0.
+    for name in ("heun_sample", "heun_sample_rng", "heun_sample_guided", "heun_sample_dxcond"):
+        plan, call = entries[name][2], entries[name][4]
+        assert call(plan._h, one, one, 0, B, H, B, mk_sd(1)) == -1 and _last() == "heun_sample: timesteps=1 out of range", name
+    plan, call = entries["vp_heun_sample"][2], entries["vp_heun_sample"][4]
+    assert call(plan._h, one, one, 0, B, H, B, mk_vd(1, 2)) == -3 and _last().startswith("vp_heun_sample: workspace too small (0 < ")
+    assert call(plan._h, one, one, 0, B, H, B, mk_vd(0, 2)) == -1 and _last() == "vp_heun_sample: timesteps=0 out of range"
+    assert call(plan._h, one, one, 0, B, H, B, vd1) == -3          # fewer conditioning channels than the plan's: a staged cond'
+    call = entries["cond_ddim_sample"][4]
+    assert call(plan._h, one, one, 0, B, H, B, mk_cd(1, 2)) == -3 and _last().startswith("cond_ddim_sample: workspace too small (0 < ")
+    assert call(plan._h, one, one, 0, B, H, B, mk_cd(0, 2)) == -1 and _last() == "cond_ddim_sample: bad schedule (timesteps=0 of 10)"
+    assert call(plan._h, one, one, 0, B, H, B, cd1) == -3
+    # the size queries
+    sz = C.c_size_t()
+    for q, extra in (("workspace_bytes", (0,)), ("workspace_bytes", (1,)), ("sampler_workspace_bytes", ()),
+                     ("vp_sampler_workspace_bytes", ()), ("cond_ddim_workspace_bytes", ())):
+        fn = getattr(lib, "mcedm_unet_workspace_bytes" if q == "workspace_bytes" else "mcedm_" + q)
+        for pl in (joint, dxp):
+            assert fn(None, B, H, W, *extra, C.byref(sz)) == -1 and _last() == f"{q}: null argument", q
+            assert fn(pl._h, B, H, W, *extra, None) == -1 and _last() == f"{q}: null argument", q
+            assert fn(pl._h, 0, H, W, *extra, C.byref(sz)) == -1 and _last() == f"layout: empty shape B=0 H={H} W={W}", q
+            assert fn(pl._h, B, 30, W, *extra, C.byref(sz)) == -1, q
+            assert _last() == f"layout: H=30 W={W} must be multiples of 4 (2^(levels-1))", q
+            assert fn(pl._h, B, H, W, *extra, C.byref(sz)) == 0 and sz.value > 0, q
+
+
 def test_dx_entry_points_validate_before_any_launch():
     """The dx_cond entry points reject a dx tensor / a dx-conditioned sampler on a plan built without dx_cond, and a wrong
     dx shape, on the host (no GPU in this container: the checks run before anything is enqueued)."""
