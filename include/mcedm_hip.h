@@ -425,6 +425,17 @@ int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int Cb, const m
 int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
                             int resample, int H, int W, const float* wino, const float* bias, const float* res, int res_mode,
                             float* out, float* gsum, int Cout, int B, void* stream);
+/* mcedm_op_conv and mcedm_op_conv_wino_sums with a bias row PER SAMPLE: the bias is [B][bias_batch], bias_batch >= Cout floats
+ * between the rows of consecutive samples (0: one row for the whole batch, the entries above).  Un-resampled 3x3 convolutions of
+ * more than 4 output channels only, in the Winograd form with act = 1 (the form the DDPM U-Net's conv1 launches: its own
+ * instantiation of the kernel); any other launch with bias_batch != 0 is MCEDM_ERR_INVALID, never a result without it.
+ * Sample b of the result equals, bit for bit, the single-row entry on sample b with row b. */
+int mcedm_op_conv_bias_batch(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                             int resample, int Hs, int Ws, int H, int W, const float* wpk, const float* bias_pk, int bias_batch,
+                             const float* res, int res_mode, float* out, int Cout, int B, int k, void* stream);
+int mcedm_op_conv_wino_sums_bias_batch(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
+                                       int act, int resample, int H, int W, const float* wino, const float* bias, int bias_batch,
+                                       const float* res, int res_mode, float* out, float* gsum, int Cout, int B, void* stream);
 /* The Winograd table of the DATA GRADIENT of that convolution (the backward of models/adm_blocks.py:57-82: du = conv3x3 of dy
  * with the weights transposed over the channels and mirrored over the taps).  w is the FORWARD weight [Cout][Cin][3][3]; wino
  * holds mcedm_op_conv_wino_packed_floats(Cin, Cout) floats and is used as mcedm_op_conv_wino(dy, .., wino, NULL bias, ..,
@@ -758,6 +769,36 @@ int mcedm_ddpm_edm_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* pack
                                    double sigma_data, const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
                                    const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes,
                                    int B, void* stream);
+
+/* ---- one timestep (noise level) per sample on the DDPM U-Net: the noising pass of training, forward only -------------------
+ * Training draws a t (PlDdim, PlCondDdim: models/ddim.py:276-278) or a sigma (PlCondEdm: :1717-1719) per sample.  The entries
+ * above evaluate the network at one timestep per call: the term temb_proj(swish(temb)) is folded into conv1's bias vector of every
+ * ResnetBlock.  These entries keep one such row set PER SAMPLE: a table [B][rows] in the workspace, of which the convolutions read
+ * row set b for sample b.  t and sigma are read from DEVICE memory, never by the host: a call can be captured in a graph and
+ * replayed after rewriting them in place.  Per sample the arithmetic and its order are those of the one-timestep entries: with
+ * every t[b] equal, mcedm_ddpm_forward_t returns the bits of mcedm_ddpm_forward / _sc / _cond / _cat at that t, and a sample's
+ * result does not depend on the rest of the batch.  There is no backward: these are for evaluation under no_grad.
+ * mcedm_ddpm_temb_row_count: rows = the sum of the output channels of the network's ResnetBlocks.
+ * mcedm_ddpm_temb_rows: rows_out [B][rows] (device), row r of sample b = temb_proj_r . swish(MLP(emb(t[b]))) + temb_proj.bias[r] +
+ *   conv1.bias[r]; the rows are ordered as the *.temb_proj.weight entries of the parameter table (mcedm_ddpm_param_info), each
+ *   block's output channels in order.
+ * mcedm_ddpm_forward_t: Model.forward(x, t [B], cond, x_self_cond) on any of the three kinds of plan.  x_self_cond NULL = zeros;
+ *   cond_map (of mcedm_ddpm_cond_map) belongs to a plan with the head, cond_cat [B, cond_channels, R, R] to a cat_cond plan, NULL =
+ *   cond None; a pointer the plan has no use for is MCEDM_ERR_INVALID before any launch.
+ * mcedm_ddpm_edm_denoise_t: PlCondEdm.model_precond (:1654-1666) with sigma [B] on the device; c_skip, c_out, c_in and
+ *   c_noise = ln(sigma) / 4 are computed there in fp32 with the reference's expressions, c_in scales the state channels only,
+ *   D = c_skip x + c_out F per sample; F_out (optional) receives F.  No guidance (training never uses it): for |w| >= 1e-3 use
+ *   mcedm_ddpm_edm_denoise at one noise level.
+ * mcedm_ddpm_workspace_bytes_t: what these two entries need (the table included); every other size query is unchanged. */
+int mcedm_ddpm_temb_row_count(const mcedm_ddpm_plan* plan, int* rows);
+int mcedm_ddpm_temb_rows(const mcedm_ddpm_plan* plan, const void* packed, const float* t, int B, float* rows_out, void* stream);
+int mcedm_ddpm_workspace_bytes_t(const mcedm_ddpm_plan* plan, int B, size_t* bytes);
+int mcedm_ddpm_forward_t(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
+                         const float* cond_map, const float* cond_cat, const float* t, float* out, void* workspace,
+                         size_t workspace_bytes, int B, void* stream);
+int mcedm_ddpm_edm_denoise_t(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, const float* sigma,
+                             double sigma_data, float* D_out, float* F_out, void* workspace, size_t workspace_bytes, int B,
+                             void* stream);
 
 /* ---- PDE residuals (forward) ----------------------------------------------
  * Replace the tensor-op bodies of models/pde_loss.py; results are bit-identical to the PyTorch CPU path.

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -144,6 +145,12 @@ struct ConvArgs {
   const float* bias; // [Cout] (packed order) or null
   const float* res;  // residual [B, Cout, Hr, Wr] or null
   int res_mode;      // Resample applied to the residual source
+  // floats between the bias rows of consecutive samples: sample n adds bias[n * bias_batch + c]; 0 = one row for the whole batch.
+  // Un-resampled 3x3 convs on the tiled, input-resident and Winograd kernels only: every other launcher refuses a non-zero value.
+  // It sits in what was the padding behind res_mode: every other member keeps its kernel-argument offset and the struct its size,
+  // so the kernel arguments behind it do not move either (a member appended at the end moved them, and that alone cost the
+  // Winograd kernel, at its 256 registers, its schedule: 1.5 % of the sampler)
+  int bias_batch;
   float* out;        // [B, Cout, H, W]
   int Cout;
   int B;
@@ -168,6 +175,8 @@ struct ConvArgs {
   // with sk_wpk runs on the direct / resident kernels.  (Last member: the other members keep their kernel-argument offsets.)
   const float* sk_wfrag;
 };
+static_assert(sizeof(ConvArgs) % 8 == 0 && offsetof(ConvArgs, bias_batch) + sizeof(int) == offsetof(ConvArgs, out),
+              "bias_batch fills the padding in front of `out`: no member moves and the struct does not grow");
 
 int launch_conv(const ConvArgs& a, int taps, hipStream_t stream);
 // conv_wino.hip: Winograd F(2x2, 3x3) kernel for un-resampled 3x3 convs with Cout % 128 == 0 on (8, 16)-divisible images

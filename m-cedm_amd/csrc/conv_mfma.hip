@@ -872,6 +872,10 @@ int launch_conv(const ConvArgs& a, int taps, hipStream_t stream) {
   if (a.res && a.res_mode == RS_UP) MCEDM_REQUIRE(a.H % 2 == 0 && a.W % 2 == 0, "conv: up residual needs even size");
   if (a.sk_wpk) MCEDM_REQUIRE(taps == 9 && a.resample == RS_NONE && a.sk_Ca + a.sk_Cb > 0 && (a.sk_xa || a.sk_xb) && a.Cout > 4,
                               "conv: a folded 1x1 projection rides on an un-resampled 3x3 conv with more than 4 output channels");
+  // a bias row per sample: the un-resampled 3x3 kernels (tiled, input-resident, Winograd) implement it; nobody may ignore it
+  MCEDM_REQUIRE(a.bias_batch == 0 || (a.bias && a.bias_batch >= a.Cout && (long long)a.B * a.bias_batch < (1ll << 31) && taps == 9 &&
+                                      a.resample == RS_NONE && a.Cout > 4),
+                "conv: a bias row per sample (bias_batch=%d) goes with an un-resampled 3x3 conv of more than 4 output channels", a.bias_batch);
   // 32-bit buffer offsets: one channel plane and the packed weight table must each stay below 4 GiB
   MCEDM_REQUIRE((unsigned long long)a.Hs * a.Ws * 4ull < (1ull << 32) &&
                 (unsigned long long)cout_padded(a.Cout) * (a.Ca + a.Cb + 16) * taps * 4ull < (1ull << 32),
@@ -888,7 +892,7 @@ int launch_conv(const ConvArgs& a, int taps, hipStream_t stream) {
   if (a.resample == RS_S2) return dispatch_s2(a, stream);
   // Winograd F(2x2, 3x3) kernel (conv_wino.hip) where the launch carries its weight table and the shape fits: chosen by shape
   // alone (never by the batch size), like every other tile choice here
-  if (!g_force_mt && taps == 9 && a.wino && conv_wino_preferred(a) && conv_wino_applicable(a, taps)) return launch_conv_wino(a, stream);
+  if (!g_force_mt && taps == 9 && a.wino && (a.bias_batch == 0 || a.act) && conv_wino_preferred(a) && conv_wino_applicable(a, taps)) return launch_conv_wino(a, stream);
   if (!g_force_mt && taps == 1) {     // un-transformed 1x1 convs at >= 32 x 32 (the decoder's skip projections): register-direct GEMM
     const int rc = try_launch_conv1x1_reg(a, taps, stream);
     if (rc != -1) return rc;

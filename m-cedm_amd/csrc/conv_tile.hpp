@@ -375,7 +375,7 @@ __device__ __forceinline__ void conv_init_acc(const ConvArgs& p, f32x16 (&acc)[C
   // channel step in the scalar offset (the launcher checks Cout * HWr * 4 < 4 GiB)
   __amdgpu_buffer_rsrc_t rs;
   if (MODE != 0) rs = make_rsrc(p.res + (size_t)n * p.Cout * HWr, 4u * (unsigned)p.Cout * HWr);
-  const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.bias, p.bias ? 4u * (unsigned)p.Cout : 0u);   // no bias: zero records
+  const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.bias + n * p.bias_batch, p.bias ? 4u * (unsigned)p.Cout : 0u);   // no bias: zero records
   const __amdgpu_buffer_rsrc_t rb2 = make_rsrc(p.sk_bias, p.sk_bias ? 4u * (unsigned)p.Cout : 0u);   // folded skip projection's bias
 #pragma unroll
   for (int i = 0; i < C::TM; ++i) {

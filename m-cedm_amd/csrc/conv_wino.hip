@@ -441,7 +441,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 
   // ---- prologue (once per workgroup): transform rows of the sample, stages 0 .. 2 of the stream
   stage_coef_rows<C::NT>(p, n, cfl, tid);
-  if (tid < C::MT) bias_l[tid] = p.bias ? p.bias[m0 + tid] : 0.f;
+  if (tid < C::MT) bias_l[tid] = p.bias ? p.bias[(WinoUpTraits<Tag...>::BROWS ? n * p.bias_batch : 0) + m0 + tid] : 0.f;
   if constexpr (SKIP) { if (tid < C::MT) skb_l[tid] = p.sk_bias ? p.sk_bias[m0 + tid] : 0.f; }
   raw_load();
   __syncthreads();
@@ -930,6 +930,7 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
       MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true, true, WinoUp<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true, true, WinoUp<false>>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, true, WinoBiasRows>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     attr_set[dev].store(true, std::memory_order_release);
   }
@@ -939,10 +940,13 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   if (per_env > 0 && tiles_img % per_env == 0) per = per_env;
   char name[64] = "";
   const bool noact = a.resample != RS_UP && !a.act;
+  // a bias row per sample: the un-resampled, activated kernel alone has that form (the DDPM U-Net's conv1)
+  MCEDM_REQUIRE(a.bias_batch == 0 || (!C::SKIP && a.resample == RS_NONE && a.act && a.bias),
+                "conv_wino: a bias row per sample (bias_batch=%d) goes with an un-resampled, activated conv without a folded projection", a.bias_batch);
   // the zero-position variant (WinoUp: same LDS footprint); 2: with the sixteen-position kernel's staging (the positions alone, A/B runs)
   const int upz = !C::SKIP && a.resample == RS_UP ? wino_upz_env() : 0;
   if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<Wino%sCfg<%d>, %s, %s%s>", C::SKIP ? "Skip" : "", C::MB, a.resample == RS_UP ? "true" : "false",
-                               noact ? "false" : "true", upz == 2 ? ", WinoUp<false>" : upz ? ", WinoUp<true>" : "");   // = rocprofv3's name
+                               noact ? "false" : "true", a.bias_batch ? ", WinoBiasRows" : upz == 2 ? ", WinoUp<false>" : upz ? ", WinoUp<true>" : "");   // = rocprofv3's name
   const double px = (double)a.B * a.H * a.W;
   const double skc = C::SKIP ? (double)(a.sk_Ca + a.sk_Cb) : 0.0;      // folded 1x1 projection: its own flops, input read and weights
   // algorithmic cost = the direct convolution's (2 * MAC); the kernel issues 4 / 9 of these as matrix flops
@@ -950,6 +954,9 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
                4.0 * ((double)a.B * Cin * a.Hs * a.Ws + px * (a.Cout * (a.res ? 2 : 1) + skc) + (double)a.Cout * (Cin * 9 + skc)), stream);
   if constexpr (C::SKIP)
     hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
+                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+  else if (a.bias_batch)
+    hipLaunchKernelGGL((conv_wino_kernel<C, false, true, WinoBiasRows>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
                        tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
   else if (upz == 2)
     hipLaunchKernelGGL((conv_wino_kernel<C, true, true, WinoUp<false>>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
@@ -983,7 +990,7 @@ int launch_conv_wino(const ConvArgs& a_in, hipStream_t stream) {
   // 128 output channels per workgroup where they divide (fewer passes over the input), else 64; the 128-channel shape runs on
   // the one-wave-per-SIMD kernel (conv_wino1.hip) only when that is switched on (MCEDM_WINO1=1; off by default)
   if (a.sk_wpk) return launch_wino_cfg<WinoSkipCfg<4>>(a, stream);      // the SKIP variant (conv_wino_fold_ok); never the one-wave kernel
-  if (a.Cout % 128 == 0) {
+  if (a.Cout % 128 == 0 && !a.bias_batch) {      // (the one-wave kernel has no form with a bias row per sample)
     const int rc = try_launch_conv_wino1(a, stream);
     if (rc != -1) return rc;
   }

@@ -60,9 +60,15 @@ struct WinoSkipCfg : WinoCfg<MB_> {
 template <bool SRC>
 struct WinoUp {};
 template <class... Tag>
-struct WinoUpTraits { static constexpr bool UPZ = false, UPS = false; static_assert(sizeof...(Tag) == 0, "one tag at most: WinoUp<SRC>"); };
+struct WinoUpTraits { static constexpr bool UPZ = false, UPS = false, BROWS = false; static_assert(sizeof...(Tag) == 0, "one tag at most: WinoUp<SRC> or WinoBiasRows"); };
 template <bool SRC>
-struct WinoUpTraits<WinoUp<SRC>> { static constexpr bool UPZ = true, UPS = SRC; };
+struct WinoUpTraits<WinoUp<SRC>> { static constexpr bool UPZ = true, UPS = SRC, BROWS = false; };
+// WinoBiasRows: the un-resampled, activated kernel with a bias row per sample (ConvArgs::bias_batch).  An instantiation of its own:
+// the kernel sits at 256 registers, and reading one more argument in the shared prologue cost the 128-channel form its schedule
+// (2 % of its time) although no resource count moved; without the tag the kernel is what it was, instruction for instruction.
+struct WinoBiasRows {};
+template <>
+struct WinoUpTraits<WinoBiasRows> { static constexpr bool UPZ = false, UPS = false, BROWS = true; };
 constexpr int UROWS = WPH / 2 + 2, UCOLS = WPW / 2 + 2;   // source patch of a tile: 6 x 10
 constexpr int UPLANE = 68;                       // floats between its channels (60 used; lanes 60 .. 63 store into the pad); = 4 mod 32: the
                                                  // transform's dword reads (eight channels x four patch columns per 32 lanes) cover the 32 banks once

@@ -12,7 +12,8 @@
 //   * q, k, v are one packed [3C x C] GEMM whose output is the attention kernel's [3][64][T] layout (C == 64);
 //   * the stride-2 conv is conv_s2_mfma_kernel (4-phase LDS tile), nearest-up is the RS_UP staging mode, the channel
 //     concat of the decoder is virtual (two source pointers).
-// Only what the samplers need is built: inference, one timestep per call.
+// Only the forward is built.  The samplers evaluate it at one timestep per call; the noising pass of training at one per sample
+// (the last section of this file): there the table of bias rows holds a row set per sample and conv1 reads its sample's.
 //   * the conditioning head of the single-task model (cond_enc / combine_enc, ddim_blocks.py:279-306, 401-421) is folded into
 //     conv_in at pack time (combine_enc is linear); what depends on cond is one map M [B, ch, R, R], computed by
 //     ddpm_cond_map_kernel once per sampler call and added by conv_in as its residual, in front of the fused statistics.
@@ -224,6 +225,15 @@ static int ddpm_plan_build(const mcedm_ddpm_desc* d, int cond_channels, int cat_
   }
   P.norm_out = dnorm(P, "norm_out", block_in);
   P.conv_out = dconv(P, "conv_out", block_in, d->out_channels, 3);
+  // the rows of the combined bias table in the order of the parameter table's temb_proj entries (mcedm_ddpm_temb_rows hands the
+  // table out); dres numbered the up path in the order it was built, deepest level first
+  {
+    int row = 0;
+    auto number = [&](DRes& r) { r.brow = row; row += r.cout; };
+    for (DLevel& lv : P.down) for (DRes& r : lv.blocks) number(r);
+    number(P.mid1); number(P.mid2);
+    for (DLevel& lv : P.up) for (DRes& r : lv.blocks) number(r);
+  }
 
   // every width that meets GroupNorm(32) must be a multiple of 32; attention is one head over all C channels and the
   // attention kernel is built for 64
@@ -422,12 +432,13 @@ __device__ __forceinline__ float swish_d(float v) { return v * (1.0f / (1.0f + e
 // grid = nsplit workgroups of 16 waves; each recomputes the small MLP (one wave per row, 16 rows in flight: the kernel is a
 // chain of three dependent mat-vec products and runs once per U-Net evaluation) and writes its slice of the rows.
 constexpr int TEMB_NT = 1024, TEMB_NW = TEMB_NT / 64;
-__global__ __launch_bounds__(TEMB_NT) void ddpm_temb_kernel(float t, int ch, const float* __restrict__ freqs,
-                                                            const float* __restrict__ w0, const float* __restrict__ b0,
-                                                            const float* __restrict__ w1, const float* __restrict__ b1,
-                                                            const float* __restrict__ wp, const float* __restrict__ bp,
-                                                            const float* __restrict__ c1b, int rows, float* __restrict__ out) {
-  extern __shared__ float sm[];
+// the rows of ONE timestep: workgroup blockIdx.x of gridDim.x writes its slice.  A row is one wave's sum in a fixed order, so its
+// bits depend on (t, weights) alone: not on the split, and not on which of the two kernels below runs this body.
+__device__ __forceinline__ void ddpm_temb_rows(float* sm, float t, int ch, const float* __restrict__ freqs,
+                                               const float* __restrict__ w0, const float* __restrict__ b0,
+                                               const float* __restrict__ w1, const float* __restrict__ b1,
+                                               const float* __restrict__ wp, const float* __restrict__ bp,
+                                               const float* __restrict__ c1b, int rows, float* __restrict__ out) {
   const int temb = 4 * ch, half = ch / 2;
   float* e0 = sm;              // [ch]
   float* e1 = sm + ch;         // [temb]
@@ -463,6 +474,41 @@ __global__ __launch_bounds__(TEMB_NT) void ddpm_temb_kernel(float t, int ch, con
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) out[r] = (s + bp[r]) + c1b[r];
   }
+}
+__global__ __launch_bounds__(TEMB_NT) void ddpm_temb_kernel(float t, int ch, const float* __restrict__ freqs,
+                                                            const float* __restrict__ w0, const float* __restrict__ b0,
+                                                            const float* __restrict__ w1, const float* __restrict__ b1,
+                                                            const float* __restrict__ wp, const float* __restrict__ bp,
+                                                            const float* __restrict__ c1b, int rows, float* __restrict__ out) {
+  extern __shared__ float sm[];
+  ddpm_temb_rows(sm, t, ch, freqs, w0, b0, w1, b1, wp, bp, c1b, rows, out);
+}
+// One timestep per sample (training draws them per sample, models/ddim.py:276-278): sample blockIdx.y reads t[blockIdx.y] from
+// device memory -- no host read, so the launch can be captured -- and writes row set blockIdx.y of out [B][rows].
+__global__ __launch_bounds__(TEMB_NT) void ddpm_temb_batch_kernel(const float* __restrict__ t, int ch, const float* __restrict__ freqs,
+                                                                  const float* __restrict__ w0, const float* __restrict__ b0,
+                                                                  const float* __restrict__ w1, const float* __restrict__ b1,
+                                                                  const float* __restrict__ wp, const float* __restrict__ bp,
+                                                                  const float* __restrict__ c1b, int rows, float* __restrict__ out) {
+  extern __shared__ float sm[];
+  ddpm_temb_rows(sm, t[blockIdx.y], ch, freqs, w0, b0, w1, b1, wp, bp, c1b, rows, out + (size_t)blockIdx.y * rows);
+}
+
+// rows_out [B][P.rows] <- the rows at t[b], both in device memory.  The rows are split over at most as many workgroups as the one-
+// timestep launch uses, fewer when the batch already fills the device (a row's bits do not depend on the split).
+static int launch_temb_rows(const mcedm_ddpm_plan& P, const float* pk, const float* t, int B, float* rows_out, hipStream_t s) {
+  MCEDM_REQUIRE(B > 0 && B <= 65535, "ddpm_temb_rows: batch %d outside [1, 65535]", B);
+  int nsplit = P.rows / 32; if (nsplit < 1) nsplit = 1; if (nsplit > 64) nsplit = 64;
+  const int fill = ceil_div(512, B);
+  if (nsplit > fill) nsplit = fill;
+  const int ch = P.desc.ch, temb = 4 * ch;
+  // per sample: every workgroup's copy of the MLP (ch x temb + temb x temb) and the rows once; the weights come from L2 after the first read
+  ProfScope ps("ddpm_temb_batch_kernel", 2.0 * B * ((double)nsplit * temb * (ch + temb) + (double)P.rows * temb),
+               4.0 * ((double)temb * (ch + temb) + (double)P.rows * (temb + B)), s);
+  hipLaunchKernelGGL(ddpm_temb_batch_kernel, dim3(nsplit, B), dim3(TEMB_NT), (size_t)(ch + 8 * ch) * sizeof(float), s, t, ch, pk + P.freqs,
+                     pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1, pk + P.tproj_w, pk + P.tproj_b, pk + P.c1bias, P.rows, rows_out);
+  MCEDM_LAUNCH_CHECK("ddpm_temb_batch_kernel");
+  return MCEDM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -557,6 +603,7 @@ struct DExec {
   int B;
   Pool pool;
   std::vector<DT> t;
+  int bias_batch = 0;         // floats between the samples' row sets of the timestep table (one timestep per sample), 0: one set
 
   int act(int C, int H, int W, bool with_sums) {
     DT d; d.C = C; d.H = H; d.W = W;
@@ -623,6 +670,7 @@ static int run_conv(DExec& E, ConvArgs& c, int taps, int out) {
 
 // ResnetBlock.forward (ddim_blocks.py:144-164) on cat(xa, xb); returns the output tensor id
 static int res_block(DExec& E, const DRes& r, int xa, int xb, const float* bias_table, int* out_id) {
+  const int bias_batch = E.bias_batch;                        // rows of bias_table per sample (0: one row set for the batch)
   int rc, tab;
   const int H = E.t[xa].H, W = E.t[xa].W;
   const int h = E.act(r.cout, H, W, true);
@@ -630,6 +678,7 @@ static int res_block(DExec& E, const DRes& r, int xa, int xb, const float* bias_
   src_of(E, c1, xa, xb);
   if ((rc = gn_into(E, r.n1, xa, xb, c1, &tab))) return rc;
   dst_of(E, c1, h, r.c1, bias_table + r.brow, true);          // bias = conv1.bias + temb_proj(swish(temb))
+  c1.bias_batch = bias_batch;
   if ((rc = run_conv(E, c1, 9, h))) return rc;
   E.release(tab);
   // y = conv2(swish(norm2(h))) + (nin_shortcut(x) | x).  The 1x1 shortcut is a GEMM onto conv2's output tile, so it rides on
@@ -718,6 +767,11 @@ struct DdpmIn {
   const float* x = nullptr;
   float t = 0.f;
   const Coef* coef_in = nullptr;
+  // one timestep per sample: t_dev [B] in device memory replaces t, and the rows go to rows_t [B][plan.rows] (the caller's, in front
+  // of the network's region: the header keeps its one row set); coef_batch 1: coef_in holds a row set per sample
+  const float* t_dev = nullptr;
+  float* rows_t = nullptr;
+  int coef_batch = 0;
   const float* self_cond = nullptr;
   const float* cond_map = nullptr;
   const float* cond_cat = nullptr;
@@ -753,9 +807,11 @@ int DdpmNet::ddpm_forward(bool dry, const DdpmIn& in, float* out, size_t* peak) 
   const mcedm_ddpm_plan& P = *plan;
   const mcedm_ddpm_desc& d = P.desc;
   const int R = d.resolution, L = d.n_levels;
-  float* bias_table = dry ? nullptr : at<float>(ws, hd.bias);
+  float* bias_table = dry ? nullptr : in.t_dev ? in.rows_t : at<float>(ws, hd.bias);
   int rc;
-  if (!dry) {
+  if (!dry && in.t_dev) {
+    if ((rc = launch_temb_rows(P, pk, in.t_dev, B, bias_table, s))) return rc;
+  } else if (!dry) {
     int nsplit = P.rows / 32; if (nsplit < 1) nsplit = 1; if (nsplit > 64) nsplit = 64;
     const int ch = d.ch;
     hipLaunchKernelGGL(ddpm_temb_kernel, dim3(nsplit), dim3(TEMB_NT), (size_t)(ch + 8 * ch) * sizeof(float), s, in.t, ch, pk + P.freqs,
@@ -764,6 +820,7 @@ int DdpmNet::ddpm_forward(bool dry, const DdpmIn& in, float* out, size_t* peak) 
   }
   DExec E{P, dry, dry ? nullptr : at<char>(ws, hd.total), pk, s, B, Pool(), {}};
   E.t.reserve(4096);        // ConvArgs::gsum_tiles points into this vector during a launch
+  E.bias_batch = in.t_dev ? P.rows : 0;
   // conv_in on cat(x_self_cond = zeros, x): the self-conditioning half is a null source (reads as zeros); on a cat_cond plan
   // (no self-conditioning there) the first source is the conditioning instead, cat(cond, x)
   const int n_self = P.in_total - d.in_channels;
@@ -774,7 +831,7 @@ int DdpmNet::ddpm_forward(bool dry, const DdpmIn& in, float* out, size_t* peak) 
     ConvArgs ci{};
     ci.xa = front; ci.Ca = n_self; ci.xb = in.x; ci.Cb = d.in_channels;          // a null first source reads as zeros
     if (n_self == 0) { ci.xa = in.x; ci.Ca = d.in_channels; ci.xb = nullptr; ci.Cb = 0; }
-    ci.coef = in.coef_in; ci.coef_batch = 0; ci.act = 0;
+    ci.coef = in.coef_in; ci.coef_batch = in.coef_batch; ci.act = 0;
     ci.Hs = R; ci.Ws = R; ci.H = R; ci.W = R;
     dst_of(E, ci, h0, P.conv_in, nullptr, true);
     // the head: conv_in holds the folded weights; with cond the map (which carries its own bias) enters as the residual, in
@@ -1490,4 +1547,80 @@ extern "C" int mcedm_ddpm_edm_heun_sample_rng(const mcedm_ddpm_plan* plan, const
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_edm_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return dedm_sample_impl(plan, packed, sp, sigma_data, gd, cond, init_noise, nullptr, rng_seed, out, return_last, workspace,
                           workspace_bytes, B, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// one timestep (noise level) per sample: what the noising pass of training evaluates (models/ddim.py:195-226, 1654-1694).  Every
+// ResnetBlock's conv1 reads its own row set of the timestep table (ConvArgs::bias_batch); the table [B][rows], and for the EDM entry
+// conv_in's transform rows [B][in_total] and c_noise [B], sit in front of the network's region, whose layout does not change.
+// ------------------------------------------------------------------------------------------
+namespace mcedm {
+struct DTBufs { size_t rows, coef, c_noise, total; };
+static DTBufs dt_bufs(const mcedm_ddpm_plan& P, int B) {
+  DTBufs b{};
+  b.rows = heun_take(b, (size_t)B * P.rows * sizeof(float));
+  b.coef = heun_take(b, (size_t)B * P.in_total * sizeof(Coef));
+  b.c_noise = heun_take(b, (size_t)B * sizeof(float));
+  return b;
+}
+}  // namespace mcedm
+
+extern "C" int mcedm_ddpm_temb_row_count(const mcedm_ddpm_plan* plan, int* rows) {
+  MCEDM_REQUIRE(plan && rows, "ddpm_temb_row_count: null argument");
+  *rows = plan->rows;
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_ddpm_temb_rows(const mcedm_ddpm_plan* plan, const void* packed, const float* t, int B, float* rows_out,
+                                    void* stream) {
+  MCEDM_REQUIRE(plan && packed && t && rows_out, "ddpm_temb_rows: null argument");
+  return launch_temb_rows(*plan, (const float*)packed, t, B, rows_out, (hipStream_t)stream);
+}
+
+extern "C" int mcedm_ddpm_workspace_bytes_t(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
+  return workspace_query("ddpm_workspace_bytes_t", plan, B, bytes, dt_bufs);
+}
+
+extern "C" int mcedm_ddpm_forward_t(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
+                                    const float* cond_map, const float* cond_cat, const float* t, float* out, void* workspace,
+                                    size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && x && t && out && workspace, "ddpm_forward_t: null argument");
+  MCEDM_REQUIRE(B > 0 && B <= 65535, "ddpm_forward_t: batch %d outside [1, 65535]", B);
+  MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_t: the network was built without self-conditioning channels");
+  MCEDM_REQUIRE(!cond_map || plan->cond_channels > 0, "ddpm_forward_t: cond_map given to a plan built without the cond_enc head");
+  MCEDM_REQUIRE(!cond_cat || plan->cat_channels > 0, "ddpm_forward_t: cond_cat given to a plan built without cat_cond channels (mcedm_ddpm_plan_create_cond)");
+  const DTBufs tb = dt_bufs(*plan, B);
+  DdpmNet net;
+  int rc;
+  if ((rc = ddpm_bind("ddpm_forward_t", *plan, packed, workspace, workspace_bytes, tb.total, B, stream, &net))) return rc;
+  DdpmIn in{x};
+  in.self_cond = x_self_cond; in.cond_map = cond_map; in.cond_cat = cond_cat;
+  in.t_dev = t; in.rows_t = at<float>(workspace, tb.rows);
+  return net.forward(in, out);
+}
+
+extern "C" int mcedm_ddpm_edm_denoise_t(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond,
+                                        const float* sigma, double sigma_data, float* D_out, float* F_out, void* workspace,
+                                        size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && packed && x && sigma && D_out && workspace, "ddpm_edm_denoise_t: null argument");
+  MCEDM_REQUIRE(B > 0 && B <= 65535, "ddpm_edm_denoise_t: batch %d outside [1, 65535]", B);
+  MCEDM_REQUIRE(sigma_data > 0.0, "ddpm_edm_denoise_t: sigma_data %g must be positive", sigma_data);
+  MCEDM_REQUIRE(plan->desc.in_channels == plan->desc.out_channels, "ddpm_edm_denoise_t: in_channels != out_channels");
+  int rc;
+  if ((rc = cat_check("ddpm_edm_denoise_t", *plan, cond, B))) return rc;
+  const DTBufs tb = dt_bufs(*plan, B);
+  DdpmNet net;
+  if ((rc = ddpm_bind("ddpm_edm_denoise_t", *plan, packed, workspace, workspace_bytes, tb.total, B, stream, &net))) return rc;
+  const mcedm_ddpm_plan& P = *plan;
+  Coef* coef = at<Coef>(workspace, tb.coef);
+  float* c_noise = at<float>(workspace, tb.c_noise);
+  const float sd = (float)sigma_data;
+  if ((rc = launch_edm_prepare_t(sigma, sd, P.in_total - P.desc.in_channels, P.desc.in_channels, B, coef, c_noise, net.s))) return rc;
+  DdpmIn in{x};
+  in.coef_in = coef; in.coef_batch = 1; in.cond_cat = cond;
+  in.t_dev = c_noise; in.rows_t = at<float>(workspace, tb.rows);
+  if ((rc = net.forward(in, net.F()))) return rc;
+  return launch_edm_finish_t(x, net.F(), sigma, sd, net.state() / B, net.state(), D_out, F_out, net.s);
 }

@@ -353,6 +353,46 @@ int launch_edm_cfg_finish(const float* x, const float* F, const float* Fu, doubl
   return MCEDM_OK;
 }
 
+// The same preconditioning with one noise level per sample (model_precond, models/ddim.py:1654-1666), every coefficient from
+// sigma [B] in device memory, fp32 with the reference's expressions: row set b of conv_in's transform table scales the state
+// channels by c_in(sigma_b) and leaves what conv_in reads in front of them alone; c_noise[b] = ln(sigma_b) / 4.
+__global__ void edm_prepare_t_kernel(const float* __restrict__ sigma, float sigma_data, int n_front, int n_in, int B,
+                                     Coef* __restrict__ coef, float* __restrict__ c_noise) {
+  const int rows = n_front + n_in;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * rows) return;
+  const int b = i / rows, c = i - b * rows;
+  const float sg = sigma[b];
+  const float c_in = 1.0f / sqrtf(sigma_data * sigma_data + sg * sg);
+  coef[i] = Coef{0.f, c < n_front ? 1.0f : c_in, 0.f, 0.f};
+  if (c == 0) c_noise[b] = logf(sg) / 4.0f;
+}
+int launch_edm_prepare_t(const float* sigma, float sigma_data, int n_front, int n_in, int B, Coef* coef, float* c_noise, hipStream_t s) {
+  const int total = B * (n_front + n_in);
+  hipLaunchKernelGGL(edm_prepare_t_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, sigma, sigma_data, n_front, n_in, B, coef, c_noise);
+  MCEDM_LAUNCH_CHECK("edm_prepare_t_kernel");
+  return MCEDM_OK;
+}
+// D = c_skip(sigma_b) x + c_out(sigma_b) F, `per` elements per sample; F_out (optional, not F itself) <- F
+__global__ void edm_finish_t_kernel(const float* __restrict__ x, const float* __restrict__ F, const float* __restrict__ sigma,
+                                    float sigma_data, size_t per, size_t total, float* __restrict__ D, float* __restrict__ F_out) {
+  const float sd2 = sigma_data * sigma_data;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const float sg = sigma[i / per], s2 = sg * sg;
+    const float c_skip = sd2 / (s2 + sd2);
+    const float c_out = sg * sigma_data / sqrtf(s2 + sd2);
+    const float f = F[i];
+    if (F_out) F_out[i] = f;
+    D[i] = c_skip * x[i] + c_out * f;
+  }
+}
+int launch_edm_finish_t(const float* x, const float* F, const float* sigma, float sigma_data, size_t per, size_t total, float* D,
+                        float* F_out, hipStream_t s) {
+  hipLaunchKernelGGL(edm_finish_t_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, F, sigma, sigma_data, per, total, D, F_out);
+  MCEDM_LAUNCH_CHECK("edm_finish_t_kernel");
+  return MCEDM_OK;
+}
+
 __global__ void repaint_init_kernel(const float* __restrict__ hu, const float* __restrict__ noise,
                                     const float* __restrict__ mask, float sa, float sb, double t0, size_t total,
                                     double* __restrict__ x, float* __restrict__ x32) {

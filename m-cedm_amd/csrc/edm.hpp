@@ -63,7 +63,13 @@ int launch_vp_cfg_finish(const float* x, const float* F, const float* Fu, double
 // D = c_skip * x + c_out * F with F = (w + 1) F - w Fu when Fu != NULL; F_out (optional, not F itself) <- the blended F
 int launch_edm_cfg_finish(const float* x, const float* F, const float* Fu, double w, float c_skip, float c_out, size_t total,
                           float* D, float* F_out, hipStream_t s);
-// x0 = ((hu*sa + nz*sb)*m + nz*(1-m)) [fp32] -> fp64, times t0        (ddim.py:989-994), m = 1 marks KNOWN entries
+// one noise level per sample, sigma [B] in device memory: coef [B][n_front + n_in] <- identity on the n_front channels in front of
+// the state, c_in(sigma_b) on the n_in state channels; c_noise [B] <- ln(sigma_b) / 4                     (models/ddim.py:1656-1661)
+int launch_edm_prepare_t(const float* sigma, float sigma_data, int n_front, int n_in, int B, Coef* coef, float* c_noise, hipStream_t s);
+// D = c_skip(sigma_b) x + c_out(sigma_b) F over `per` elements per sample; F_out (optional, not F itself) <- F        (:1665)
+int launch_edm_finish_t(const float* x, const float* F, const float* sigma, float sigma_data, size_t per, size_t total, float* D,
+                        float* F_out, hipStream_t s);
+// x0 = ((hu*sa + nz*sb)*m + nz*(1-m)) [fp32] -> fp64, times t0       (ddim.py:989-994), m = 1 marks KNOWN entries
 int launch_repaint_init(const float* hu, const float* noise, const float* mask, float sa, float sb, double t0, size_t total,
                         double* x, float* x32, hipStream_t s);
 // x = (sa*hu + sb*nz)*m [fp32] + x*(1-m) [fp64]                          (ddim.py:1029-1031); final: x = hu*m + x*(1-m) (:1041-1043)

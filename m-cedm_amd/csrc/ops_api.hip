@@ -37,10 +37,9 @@ extern "C" int mcedm_op_gn_coef(const float* xa, const float* xb, int Ca, int Cb
   return launch_gn_coef(a, (hipStream_t)stream);
 }
 
-extern "C" int mcedm_op_conv(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
-                             int act, int resample, int Hs, int Ws, int H, int W, const float* wpk,
-                             const float* bias_pk, const float* res, int res_mode, float* out, int Cout, int B, int k,
-                             void* stream) {
+static int op_conv(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act, int resample,
+                   int Hs, int Ws, int H, int W, const float* wpk, const float* bias_pk, int bias_batch, const float* res, int res_mode,
+                   float* out, int Cout, int B, int k, void* stream) {
   MCEDM_REQUIRE(k == 1 || k == 3, "op_conv: k must be 1 or 3");
   MCEDM_REQUIRE(resample >= 0 && resample <= 3 && res_mode >= 0 && res_mode <= 2, "op_conv: bad resample mode");
   ConvArgs a{};
@@ -48,8 +47,24 @@ extern "C" int mcedm_op_conv(const float* xa, const float* xb, int Ca, int Cb, c
   a.coef = reinterpret_cast<const Coef*>(coef); a.coef_batch = coef_batch; a.act = act;
   a.resample = resample; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W;
   a.wpk = wpk; a.bias = bias_pk; a.res = res; a.res_mode = res_mode;
-  a.out = out; a.Cout = Cout; a.B = B;
+  a.out = out; a.Cout = Cout; a.B = B; a.bias_batch = bias_batch;
   return launch_conv(a, k * k, (hipStream_t)stream);
+}
+extern "C" int mcedm_op_conv(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
+                             int act, int resample, int Hs, int Ws, int H, int W, const float* wpk,
+                             const float* bias_pk, const float* res, int res_mode, float* out, int Cout, int B, int k,
+                             void* stream) {
+  return op_conv(xa, xb, Ca, Cb, coef, coef_batch, act, resample, Hs, Ws, H, W, wpk, bias_pk, 0, res, res_mode, out, Cout, B, k, stream);
+}
+// mcedm_op_conv with a bias row per sample: bias_pk [B][bias_batch] (each row in packed order); a launcher whose kernel does not
+// implement it refuses a non-zero bias_batch
+extern "C" int mcedm_op_conv_bias_batch(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
+                                        int act, int resample, int Hs, int Ws, int H, int W, const float* wpk, const float* bias_pk,
+                                        int bias_batch, const float* res, int res_mode, float* out, int Cout, int B, int k,
+                                        void* stream) {
+  MCEDM_REQUIRE(bias_batch >= 0, "op_conv_bias_batch: bias_batch %d < 0", bias_batch);
+  return op_conv(xa, xb, Ca, Cb, coef, coef_batch, act, resample, Hs, Ws, H, W, wpk, bias_pk, bias_batch, res, res_mode, out, Cout, B, k,
+                 stream);
 }
 
 extern "C" size_t mcedm_op_conv_wino_packed_floats(int Cout, int Cin) { return conv_wino_packed_floats(Cout, Cin); }
@@ -80,9 +95,9 @@ extern "C" int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int 
 }
 
 // mcedm_op_conv_wino with the fused GroupNorm records of `out` in gsum (4-channel blocks, as a plan's convs write them)
-extern "C" int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
-                                       int act, int resample, int H, int W, const float* wino, const float* bias, const float* res,
-                                       int res_mode, float* out, float* gsum, int Cout, int B, void* stream) {
+static int op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                             int resample, int H, int W, const float* wino, const float* bias, int bias_batch, const float* res,
+                             int res_mode, float* out, float* gsum, int Cout, int B, void* stream) {
   MCEDM_REQUIRE((resample == RS_NONE || resample == RS_UP) && (res_mode == RS_NONE || res_mode == RS_UP || res_mode == RS_DOWN),
                 "op_conv_wino_sums: resample must be 0 (none) or 1 (nearest-2x up), res_mode 0, 1 or 2 (2x2-mean down)");
   MCEDM_REQUIRE(gsum, "op_conv_wino_sums: gsum is null");
@@ -94,8 +109,23 @@ extern "C" int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca,
   a.wino = wino; a.bias = bias; a.res = res; a.res_mode = res_mode;
   SumTiles st;
   a.out = out; a.Cout = Cout; a.B = B; a.gsum = gsum; a.gsum_tiles = &st;
+  MCEDM_REQUIRE(bias_batch == 0 || (bias && bias_batch >= Cout), "op_conv_wino_sums: bias_batch %d needs a bias of B rows of at least Cout floats", bias_batch);
+  a.bias_batch = bias_batch;
   MCEDM_REQUIRE(conv_wino_applicable(a, 9), "op_conv_wino_sums: needs Cout %% 64 == 0, H %% 8 == 0, W %% 16 == 0, Cin %% 8 == 0 and 16-byte aligned inputs / weight table");
   return launch_conv_wino(a, (hipStream_t)stream);
+}
+extern "C" int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
+                                       int act, int resample, int H, int W, const float* wino, const float* bias, const float* res,
+                                       int res_mode, float* out, float* gsum, int Cout, int B, void* stream) {
+  return op_conv_wino_sums(xa, xb, Ca, Cb, coef, coef_batch, act, resample, H, W, wino, bias, 0, res, res_mode, out, gsum, Cout, B, stream);
+}
+// mcedm_op_conv_wino_sums with a bias row per sample: bias [B][bias_batch]
+extern "C" int mcedm_op_conv_wino_sums_bias_batch(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef,
+                                                  int coef_batch, int act, int resample, int H, int W, const float* wino,
+                                                  const float* bias, int bias_batch, const float* res, int res_mode, float* out,
+                                                  float* gsum, int Cout, int B, void* stream) {
+  return op_conv_wino_sums(xa, xb, Ca, Cb, coef, coef_batch, act, resample, H, W, wino, bias, bias_batch, res, res_mode, out, gsum, Cout, B,
+                           stream);
 }
 
 // A 1x1 conv's weights [Cout][Cin] in the MFMA-fragment order of ConvArgs::sk_wfrag (cout_padded(Cout) * ceil8(Cin) floats)

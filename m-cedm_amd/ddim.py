@@ -20,8 +20,9 @@ sampling of ``PlCondEdm`` raises as in the reference (models/ddim.py:1739-1740),
 would feed ``denoised`` back).  With a ``name`` that does not start with ``adm`` (configs/model/edm_cond_h_res32.yaml: ``name:
 edm_cond_h``, ``cat_cond: True``, ``self_cond: False``) the network is the DDPM U-Net ``Model`` with the conditioning concatenated
 to its input, for EVALUATION: ``model_precond``, ``get_denoised``, ``sample_edm`` (with ``guide_dx``), ``validation_step`` and
-``test_step`` run on it (mcedm_ddpm_edm_denoise, mcedm_ddpm_edm_heun_sample[_rng]); ``training_step`` and ``forward`` raise, because
-``Model`` has no backward here, and so does ``dx_cond``.
+``test_step`` run on it (mcedm_ddpm_edm_denoise, mcedm_ddpm_edm_heun_sample[_rng]).  ``Model`` has no backward here: with gradients
+enabled ``training_step`` and ``forward`` raise; under ``torch.no_grad()`` they run with one noise level per sample
+(mcedm_ddpm_edm_denoise_t) and return the reference's ``(output, x0_t)`` and loss value.  ``dx_cond`` raises.
 
 ``PlCondDdim`` (bottom of this file) for ``models/ddim.py:1053-1605``: the single-task conditional DDPM on the ADM U-Net with
 self-conditioning (which it runs) -- epsilon-prediction ``training_step``, the VP-preconditioned ``sample_edm`` and the DDIM
@@ -46,9 +47,11 @@ class _SingleTask(_PlBase):
     evaluation loops around ``sample_edm`` and the unroll metrics (``print_unroll_metrics``, ``get_x_unnorm``)."""
 
     def _adm_only(self, what):
-        if self._on_ddpm_unet:
+        """With gradients enabled the DDPM U-Net refuses what training calls; under torch.no_grad() it runs (the forward only)."""
+        if self._on_ddpm_unet and torch.is_grad_enabled():
             raise NotImplementedError(f"{what} is not built on the DDPM U-Net (models/ddim.py:43-46, Model): it has no backward "
-                                      "here; only the ADM U-Net (hparams.name = 'adm*') trains")
+                                      "here; only the ADM U-Net (hparams.name = 'adm*') trains.  Under torch.no_grad() it runs: "
+                                      "the noising pass and the loss value, without gradients")
 
     def _edm_schedule(self, sparams, c_noise_of):
         """The schedule of sample_edm in the reference's own expressions on the host (models/ddim.py:1543-1553, 1566-1567), rounded by
@@ -249,6 +252,50 @@ class _DdpmSchedule:
             self.sigma_min = float(self.edm_steps[self.num_timesteps - 1])
             self.sigma_max = float(self.edm_steps[0])
 
+    def _noise_tables(self, device):
+        """sqrt(a) and sqrt(1 - a), a = (1 - betas).cumprod(0), on the module's device (models/ddim.py:195-197)."""
+        if getattr(self, "_tables", None) is None or self._tables[0].device != torch.device(device):
+            a = (1 - self.betas.to(device)).cumprod(dim=0)
+            self._tables = (a.sqrt().contiguous(), (1.0 - a).sqrt().contiguous())
+        return self._tables
+
+    def _ddpm_eps_forward(self, x, t, noise, cond):
+        """forward(x, t, noise, cond) of the epsilon-prediction modules (models/ddim.py:195-226) on the DDPM U-Net, without
+        gradients: (output, x0_t) at one timestep per sample (mcedm_ddpm_forward_t).  torch's generator is consumed as the
+        reference consumes it: the cond_p draw (:210), then -- on a self-conditioning network -- the draw of the pre-pass (:214),
+        whose estimate mcedm_eps_self_cond writes.  The conditioning map is computed once and serves both passes."""
+        net = self.model
+        with torch.no_grad():
+            x = x.to(torch.float32).contiguous()
+            noise = noise.to(torch.float32).contiguous()
+            t = torch.as_tensor(t).to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+            sa, sb = self._noise_tables(x.device)
+            x_noise, labels = _lib.eps_noise_inputs(x, noise, t, sa, sb)
+            if torch.rand(1) >= self.cond_p:
+                cond = None                                    # the conditioning switched off for this batch
+            pk = net.packed_weights()
+            cmap = None
+            if cond is not None:
+                if net.cond_enc is None:
+                    raise NotImplementedError("cond given to a network built without the cond_enc head")
+                cmap = net.plan.cond_map(pk, cond.to(torch.float32).contiguous())
+
+            def x0_of(F):                                      # (x_noise - F sqrt(1 - a)) / sqrt(a), :217 and :224
+                out = torch.empty_like(F)
+                return _lib.eps_self_cond(out, None, 0, F.shape[1], x_noise=x_noise, F0=F, t=t, sqrt_ab=sa, sqrt_1mab=sb)
+            x_sc = None
+            if net.self_condition and torch.rand(1) < 0.5:
+                x_sc = x0_of(net.plan.forward_t(pk, x_noise, labels, cond_map=cmap, ws=net._ws))
+            output = net.plan.forward_t(pk, x_noise, labels, x_self_cond=x_sc, cond_map=cmap, ws=net._ws)
+            return output, x0_of(output)
+
+    def _ddpm_eps_loss(self, output, noise):
+        """NoiseEstimationLoss (models/losses.py:39-59) of a forward on the DDPM U-Net, the value alone (mcedm_eps_loss)."""
+        with torch.no_grad():
+            loss = _lib.eps_loss(output, noise.to(torch.float32).contiguous(), want_grad=False)[0].reshape(())
+        self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
+        return loss
+
     def get_edm_steps(self):
         """models/ddim.py:131-137, evaluated on the CPU like the schedule buffers themselves."""
         b = self.betas.detach().cpu()
@@ -338,8 +385,17 @@ class PlCondEdm(_SingleTask):
         return 0 if return_index else sigma
 
     def forward(self, x, sigma, noise, cond=None):
+        """models/ddim.py:1668-1694 on the DDPM U-Net without gradients: (output, x0_t) with one noise level per sample."""
         self._adm_only("forward (the noising pass of training)")
-        return super().forward(x, sigma, noise, cond)          # not defined for the ADM U-Net either: training_step is the entry
+        if not self._on_ddpm_unet:
+            return super().forward(x, sigma, noise, cond)      # not defined for the ADM U-Net: training_step is the entry
+        with torch.no_grad():
+            sigma = torch.as_tensor(sigma).to(device=x.device, dtype=torch.float32)
+            x_noise = x.to(torch.float32) + noise.to(torch.float32) * sigma.reshape(-1, 1, 1, 1)
+            if torch.rand(1) >= self.cond_p:
+                cond = None                                    # the conditioning switched off for this batch (:1683-1684)
+            output = self.model_precond(x_noise, sigma, cond)  # no self-conditioning on this network: no pre-pass, no draw
+        return output, output
 
     # ---- HIP path -------------------------------------------------------------------------------------------
     def _dx_arg(self, net, dx):
@@ -356,8 +412,14 @@ class PlCondEdm(_SingleTask):
             raise NotImplementedError("dx_cond is not built on the DDPM U-Net")
         sig = torch.as_tensor(sigma).detach().to("cpu", torch.float32).reshape(-1)
         if sig.numel() != 1 and not bool((sig == sig[0]).all()):
-            raise NotImplementedError("one noise level for the whole batch (what sample_edm evaluates; per-sample levels need a "
-                                      "per-sample bias in every conv of the DDPM U-Net)")
+            guided = w is not None and abs(w) >= 0.001
+            if torch.is_grad_enabled() or guided or sig.numel() != xt.shape[0]:
+                raise NotImplementedError("one noise level for the whole batch (what sample_edm evaluates); a level per sample "
+                                          "runs under torch.no_grad(), without guidance (mcedm_ddpm_edm_denoise_t)")
+            return net.plan.edm_denoise_t(net.packed_weights(), xt.to(torch.float32).contiguous(),
+                                          torch.as_tensor(sigma).detach().to(xt.device, torch.float32).reshape(-1).contiguous(),
+                                          cond=None if cond is None else cond.to(torch.float32).contiguous(),
+                                          sigma_data=self.sigma_data, ws=net._ws, want_F=True)
         c_noise = float((sig[:1].log() / 4)[0])
         with torch.no_grad():
             return net.plan.edm_denoise(net.packed_weights(), xt.to(torch.float32).contiguous(), float(sig[0]), c_noise,
@@ -411,6 +473,11 @@ class PlCondEdm(_SingleTask):
             dx = self.get_dx_input(cond_in[:, 0:self.h_ch], u_noise)     # on the NOISED target; carries no gradient
         if torch.rand(1) >= self.cond_p:                         # models/ddim.py:1683-1684: conditioning off for this batch
             cond_in = None                                       # (the network then reads zeros, adm_blocks.py:328-331)
+        if self._on_ddpm_unet:                                   # under torch.no_grad() (see _adm_only): the loss value alone
+            D = self.model_precond(u_noise, sigma, cond_in)
+            loss = _lib.edm_loss(D, u.contiguous(), None, sigma, self.sigma_data, want_grad=False)[0].reshape(())
+            self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
+            return loss
         loss = _edm_train_loss(self, u, u_noise, sigma, cond_in, None, dx)
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
         return loss
@@ -520,7 +587,9 @@ class PlDdim(_DdpmSchedule, _PlBase):
     Constructor, buffers (``betas``, ``logvar``), attributes and the signatures of ``set_test_sampler_params``,
     ``get_edm_steps``, ``compute_alpha``, ``round_sigma``, ``get_denoised`` and ``sample_edm`` follow the reference.
     ``sample_with_repeat`` (the DDIM sampler with RePaint loops, the default ``diff_sampler: ddim_sampler``) runs on the device
-    too (round 3).  DDPM training, the h -> u ``sample`` loop and PDE guidance are not built and raise."""
+    too (round 3).  DDPM training (``Model`` has no backward: with gradients enabled ``training_step`` and ``forward`` raise; under
+    ``torch.no_grad()`` they run with one timestep per sample, mcedm_ddpm_forward_t, and return the reference's ``(output, x0_t)``
+    and loss value), the h -> u ``sample`` loop and PDE guidance are not built and raise."""
 
     def __init__(self, hparams):
         super().__init__()
@@ -540,6 +609,7 @@ class PlDdim(_DdpmSchedule, _PlBase):
         self.h_ch = self.u_ch = m.out_ch // 2
         self._init_common(hparams, self.h_ch, self.u_ch)
         self.edm_steps = self.sigma_min = self.sigma_max = None
+        self.pde_loss_lambda = _opt(_opt(hparams, "optimization", None), "pde_loss_lambda", 0.0)
 
     def compute_alpha(self, t):
         """models/ddim.py:700-704."""
@@ -739,9 +809,33 @@ class PlDdim(_DdpmSchedule, _PlBase):
                                                                      ws=self._sample_ws, device_noise=dev_noise),
                                 eager, hu, hu_noise, eta_noise, **kw)
 
+    def _no_backward(self):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("DDPM (epsilon-prediction) training is not built: SURVEY.md section 8 f1 covers EDM sampling "
+                                      "of a trained DDPM checkpoint (Model has no backward here).  Under torch.no_grad() forward and "
+                                      "training_step run: the noising pass and the loss value, without gradients")
+
+    def forward(self, x, t, noise, cond=None):
+        """models/ddim.py:195-226 without gradients: (output, x0_t), one timestep per sample."""
+        self._no_backward()
+        return self._ddpm_eps_forward(x, t, noise, cond)
+
     def training_step(self, *a, **k):
-        raise NotImplementedError("DDPM (epsilon-prediction) training is not built: SURVEY.md section 8 f1 covers EDM sampling "
-                                  "of a trained DDPM checkpoint")
+        """training_step(train_batch, batch_idx), models/ddim.py:264-292, under torch.no_grad(): the noise-estimation loss of the
+        batch (logged as train_loss), no gradients."""
+        self._no_backward()
+        train_batch = a[0] if a else k["train_batch"]
+        if self.pde_loss_lambda:
+            raise NotImplementedError("pde_loss_lambda > 0 (models/ddim.py:284-290) is not built")
+        h_unnorm, dx, dt, u_unnorm = train_batch
+        self.h_ch, self.u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
+        x = _nchw(self.data_transform(h_unnorm, u_unnorm)).float()
+        n = x.size(0)
+        noise = torch.randn_like(x)
+        t = torch.randint(low=0, high=self.num_timesteps, size=(n // 2 + 1,))       # antithetic sampling (:275-278)
+        t = t.to(x.device).long()
+        t = torch.cat([t, self.num_timesteps - t - 1], dim=0)[:n]
+        return self._ddpm_eps_loss(self.forward(x, t, noise)[0], noise)
 
 
 def _eps_train_loss(module, x_noise, labels, cond, noise):
@@ -772,8 +866,9 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     With a ``name`` that does not start with ``adm`` the network is the DDPM U-Net ``Model`` (:43-46;
     configs/model/ddim_cond_h_res32.yaml: ``name: ddim_cond_h``, ``cat_cond: False``, ``self_cond: True``) with its cond_enc head,
     for EVALUATION: ``get_denoised``, ``sample_edm``, ``sample``, ``validation_step`` and ``test_step`` run on it
-    (mcedm_ddpm_vp_heun_sample[_rng], mcedm_ddpm_cond_ddim_sample[_rng]); ``training_step`` and ``forward`` raise, because
-    ``Model`` has no backward here.  ``noise_source`` ("device" / "torch", from MCEDM_NOISE_SOURCE) says where the per-step draws of
+    (mcedm_ddpm_vp_heun_sample[_rng], mcedm_ddpm_cond_ddim_sample[_rng]).  ``Model`` has no backward here: with gradients enabled
+    ``training_step`` and ``forward`` raise; under ``torch.no_grad()`` they run with one timestep per sample (mcedm_ddpm_forward_t)
+    and return the reference's ``(output, x0_t)`` and loss value.  ``noise_source`` ("device" / "torch", from MCEDM_NOISE_SOURCE) says where the per-step draws of
     the two samplers come from: the sampler's own kernels, or torch tensors drawn up front."""
 
     def __init__(self, hparams):
@@ -807,13 +902,6 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         self.h_ch, self.u_ch = m.cond_channels - (1 if self.node_type else 0), m.out_ch
         self._tables = None
         self._stage = None
-
-    def _noise_tables(self, device):
-        """sqrt(a) and sqrt(1 - a), a = (1 - betas).cumprod(0), on the module's device (models/ddim.py:195-197)."""
-        if self._tables is None or self._tables[0].device != torch.device(device):
-            a = (1 - self.betas.to(device)).cumprod(dim=0)
-            self._tables = (a.sqrt().contiguous(), (1.0 - a).sqrt().contiguous())
-        return self._tables
 
     # ---- epsilon-prediction forward (models/ddim.py:195-226) --------------------------------------------------------------
     def _noised_inputs(self, x, t, noise, cond, ws):
@@ -850,6 +938,8 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     def forward(self, x, t, noise, cond=None):
         """models/ddim.py:195-226 without gradients: (output, x0_t)."""
         self._adm_only("forward (the noising pass of training)")
+        if self._on_ddpm_unet:
+            return self._ddpm_eps_forward(x, t, noise, cond)
         net = self.model
         with torch.no_grad():
             x_noise, labels, condp, t = self._noised_inputs(x, t, noise, cond, net._ws)
@@ -872,6 +962,8 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         t = torch.randint(low=0, high=self.num_timesteps, size=(n // 2 + 1,))       # antithetic sampling (:1134-1137)
         t = t.to(x.device).long()
         t = torch.cat([t, self.num_timesteps - t - 1], dim=0)[:n]
+        if self._on_ddpm_unet:                       # under torch.no_grad() (see _adm_only): the loss value alone
+            return self._ddpm_eps_loss(self._ddpm_eps_forward(u, t, noise, cond_in)[0], noise)
         x_noise, labels, condp, _ = self._noised_inputs(u, t, noise, cond_in, self._train_ws)
         loss = _eps_train_loss(self, x_noise, labels, condp, noise.contiguous())
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)

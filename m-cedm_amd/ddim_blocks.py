@@ -5,10 +5,11 @@ Same constructor (``Model(hparams)``), the same ``state_dict`` keys / shapes (``
 unchanged, and the same ``forward(x, t, cond=None, x_self_cond=None, dx=None)`` signature; the compute runs in
 libmcedm_hip.so (csrc/ddpm.hip).  The sub-modules only OWN parameters (plain torch layers, i.e. the reference's own
 default initialisation).  What the samplers of ``PlDdim`` and ``PlCondDdim`` evaluate is built: inference, one timestep for
-the whole batch, ``x_self_cond`` given or None, and -- with ``cond_channels > 0`` and ``cat_cond: False``
+the whole batch or (``t`` with one entry per sample, read on the device: mcedm_ddpm_forward_t) one per sample, ``x_self_cond``
+given or None, and -- with ``cond_channels > 0`` and ``cat_cond: False``
 (configs/model/ddim_cond_h_res32.yaml) -- ``cond`` through the ``cond_enc`` / ``combine_enc`` head, or -- with ``cat_cond: True``
 and ``self_cond: False`` (configs/model/edm_cond_h_res32.yaml) -- ``cond`` concatenated in front of the state by ``conv_in``.
-Everything else (cat_cond together with self_cond, dx conditioning, per-sample timesteps, autograd) raises instead of silently
+Everything else (cat_cond together with self_cond, dx conditioning, autograd) raises instead of silently
 computing something else.  There is no PyTorch fallback.
 """
 from __future__ import annotations
@@ -198,9 +199,15 @@ class Model(nn.Module):
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("the DDPM U-Net is built for inference (RePaint sampling); call it under torch.no_grad()")
         t = torch.as_tensor(t).reshape(-1)
-        if t.numel() != 1 and not bool((t == t[0]).all()):
-            raise NotImplementedError("one timestep for the whole batch (what the sampler evaluates)")
+        if t.numel() not in (1, x.shape[0]):
+            raise ValueError(f"t has {t.numel()} entries: one for the whole batch or one per sample ({x.shape[0]})")
         sc = None if x_self_cond is None else x_self_cond.to(torch.float32).contiguous()
+        if t.numel() != 1:                 # one timestep per sample, read on the device (never compared on the host)
+            pk = self.packed_weights()
+            c = None if cond is None else cond.to(torch.float32).contiguous()
+            cmap = self.plan.cond_map(pk, c) if (c is not None and self.cond_enc is not None) else None
+            return self.plan.forward_t(pk, x.to(torch.float32).contiguous(), t.to(device=x.device, dtype=torch.float32).contiguous(),
+                                       x_self_cond=sc, cond_map=cmap, cond=c if self.cat_condition else None, ws=self._ws)
         if self.cat_condition:             # cat(cond, x) by conv_in's two sources; cond None reads as zeros (ddim_blocks.py:386-391)
             c = None if cond is None else cond.to(torch.float32).contiguous()
             return self.plan.forward_cat(self.packed_weights(), x.to(torch.float32).contiguous(), float(t[0]), cond=c, ws=self._ws)

@@ -43,6 +43,8 @@ EXPORTS = [
     "mcedm_ddpm_forward_cat", "mcedm_ddpm_edm_denoise", "mcedm_ddpm_edm_sampler_workspace_bytes", "mcedm_ddpm_edm_heun_sample",
     "mcedm_ddpm_edm_heun_sample_rng",
     "mcedm_swe_fv_unroll",
+    "mcedm_ddpm_temb_row_count", "mcedm_ddpm_temb_rows", "mcedm_ddpm_workspace_bytes_t", "mcedm_ddpm_forward_t",
+    "mcedm_ddpm_edm_denoise_t",
 ]
 # The sampler entries _PlanBase._sample_call drives, with the number of materialised-noise pointers each takes; every one
 # has a "_rng" twin that takes ONE seed pointer in their place.  A new sampler is a row here and a method that names it.
@@ -247,6 +249,11 @@ def load() -> C.CDLL:
                                                f64p, i32, vp, sz, i32, vp]
     lib.mcedm_ddpm_edm_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), C.c_double, C.POINTER(GuidanceDesc), f32p, f32p, vp,
                                                    f64p, i32, vp, sz, i32, vp]
+    lib.mcedm_ddpm_temb_row_count.argtypes = [vp, C.POINTER(i32)]
+    lib.mcedm_ddpm_temb_rows.argtypes = [vp, vp, f32p, i32, f32p, vp]
+    lib.mcedm_ddpm_workspace_bytes_t.argtypes = [vp, i32, C.POINTER(sz)]
+    lib.mcedm_ddpm_forward_t.argtypes = [vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, vp, sz, i32, vp]
+    lib.mcedm_ddpm_edm_denoise_t.argtypes = [vp, vp, f32p, f32p, f32p, C.c_double, f32p, f32p, vp, sz, i32, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)          # AttributeError here == header/library drift
         if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
@@ -804,6 +811,71 @@ class DdpmPlan(_PlanBase):
     def edm_sampler_workspace_bytes(self, B: int) -> int:
         return self._bytes("mcedm_ddpm_edm_sampler_workspace_bytes", "ddpm_edm_sampler_workspace_bytes", B)
 
+    # ---- one timestep (noise level) per sample: the noising pass of training, forward only -------------------------------
+    @property
+    def temb_row_count(self) -> int:
+        """mcedm_ddpm_temb_row_count: rows of the timestep table per sample (the ResnetBlocks' output channels)."""
+        n = C.c_int32()
+        check(self._lib.mcedm_ddpm_temb_row_count(self._h, C.byref(n)), "ddpm_temb_row_count")
+        return int(n.value)
+
+    def workspace_bytes_t(self, B: int) -> int:
+        return self._bytes("mcedm_ddpm_workspace_bytes_t", "ddpm_workspace_bytes_t", B)
+
+    @staticmethod
+    def _check_levels(v, B: int, who: str, name: str):
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 1 or v.numel() != B:
+            raise RuntimeError(f"{who}: {name} must be a device fp32 tensor of shape [{B}] (one per sample; it is read on the device)")
+
+    def temb_rows(self, packed, t: torch.Tensor) -> torch.Tensor:
+        """mcedm_ddpm_temb_rows: [B, temb_row_count], per sample what the ResnetBlocks' conv1 add at t[b] (conv1.bias included),
+        ordered as the *.temb_proj.weight entries of the parameter table."""
+        if not torch.is_tensor(t) or t.dim() != 1 or t.numel() == 0:
+            raise RuntimeError("temb_rows: t must be a non-empty 1-D tensor")
+        B = t.numel()
+        self._check_levels(t, B, "temb_rows", "t")
+        out = torch.empty((B, self.temb_row_count), dtype=torch.float32, device=t.device)
+        check(self._lib.mcedm_ddpm_temb_rows(self._h, packed.data_ptr(), _ptr(t), B, _ptr(out), _stream()), "ddpm_temb_rows")
+        return out
+
+    def forward_t(self, packed, x, t: torch.Tensor, x_self_cond=None, cond_map=None, cond=None, ws: Optional[Workspace] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcedm_ddpm_forward_t: Model.forward(x, t [B], cond, x_self_cond), one timestep per sample, t a device tensor.  cond_map
+        (of cond_map()) goes with a plan that has the head, cond (raw) with a cat_cond plan; None: cond None."""
+        self._check_x(x)
+        B, R = x.shape[0], self.resolution
+        self._check_levels(t, B, "forward_t", "t")
+        if x_self_cond is not None and tuple(x_self_cond.shape) != tuple(x.shape):
+            raise RuntimeError("x_self_cond must have the shape of x")
+        if cond_map is not None and tuple(cond_map.shape) != (B, self.ch, R, R):
+            raise RuntimeError(f"forward_t: cond_map {tuple(cond_map.shape)} != {(B, self.ch, R, R)}")
+        if cond is not None and (not self.cat_cond or cond.shape[0] != B):
+            raise RuntimeError("forward_t: the raw conditioning [B, cond_channels, R, R] goes with a cat_cond plan (else pass cond_map)")
+        self._check_cond(cond, "forward_t")
+        buf = (ws or Workspace()).get(self.workspace_bytes_t(B), x.device)
+        if out is None:
+            out = torch.empty((B, self.out_channels, R, R), dtype=torch.float32, device=x.device)
+        check(self._lib.mcedm_ddpm_forward_t(self._h, packed.data_ptr(), _ptr(x), _ptr(x_self_cond), _ptr(cond_map), _ptr(cond), _ptr(t),
+                                             _ptr(out), buf.data_ptr(), buf.numel(), B, _stream()), "ddpm_forward_t")
+        return out
+
+    def edm_denoise_t(self, packed, x, sigma: torch.Tensor, cond=None, sigma_data: float = 1.0, ws: Optional[Workspace] = None,
+                      want_F: bool = False):
+        """mcedm_ddpm_edm_denoise_t: PlCondEdm.model_precond with one noise level per sample, sigma [B] a device tensor; every
+        coefficient is computed on the device.  No guidance (edm_denoise serves it at one noise level)."""
+        self._check_x(x)
+        B = x.shape[0]
+        self._check_levels(sigma, B, "edm_denoise_t", "sigma")
+        if cond is not None and cond.shape[0] != B:
+            raise RuntimeError("edm_denoise_t: cond must have the batch size of x")
+        self._check_cond(cond, "edm_denoise_t")
+        buf = (ws or Workspace()).get(self.workspace_bytes_t(B), x.device)
+        D = torch.empty((B, self.out_channels, self.resolution, self.resolution), dtype=torch.float32, device=x.device)
+        F = torch.empty_like(D) if want_F else None
+        check(self._lib.mcedm_ddpm_edm_denoise_t(self._h, packed.data_ptr(), _ptr(x), _ptr(cond), _ptr(sigma), float(sigma_data), _ptr(D),
+                                                 _ptr(F), buf.data_ptr(), buf.numel(), B, _stream()), "ddpm_edm_denoise_t")
+        return (D, F) if want_F else D
+
     def edm_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
                    ws: Optional[Workspace] = None, rng_seed: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                    sigma_data: float = 1.0, guidance: Optional["GuidanceDesc"] = None) -> torch.Tensor:
@@ -1350,6 +1422,10 @@ def _bind_ops():
     lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
     lib.mcedm_op_conv_wino_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
+    lib.mcedm_op_conv_bias_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32,
+                                             i32, i32, vp]
+    lib.mcedm_op_conv_wino_sums_bias_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32,
+                                                       i32, vp]
     lib.mcedm_op_pack_conv_frag.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_skip.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]
     f32 = C.c_float
@@ -1360,7 +1436,7 @@ def _bind_ops():
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
               "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
-              "mcedm_op_attn_block64"):
+              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1373,7 +1449,7 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
               "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
-              "mcedm_op_attn_block64"]
+              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1504,13 +1580,21 @@ def op_gn_coef(xa, xb, gamma, beta, film=None, film_batch=0, film_stride=0, eps=
 
 
 def op_conv(xa, xb, wpk, bias_pk, Cout, k, coef=None, coef_batch=1, act=0, resample=RS_NONE, res=None,
-            res_mode=RS_NONE, out=None):
+            res_mode=RS_NONE, out=None, bias_batch=0):
+    """bias_batch != 0: bias_pk is [B, bias_batch], a (packed) row per sample (mcedm_op_conv_bias_batch)."""
     lib = _bind_ops()
     B, Ca, Hs, Ws = xa.shape
     Cb = xb.shape[1] if xb is not None else 0
     H, W = (Hs * 2, Ws * 2) if resample == RS_UP else ((Hs // 2, Ws // 2) if resample in (RS_DOWN, RS_S2) else (Hs, Ws))
     if out is None:
         out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=xa.device)
+    if bias_batch:
+        if bias_pk is None or bias_pk.numel() < (B - 1) * bias_batch + Cout:
+            raise RuntimeError(f"op_conv: bias_batch={bias_batch} needs a bias of {B} rows")
+        check(lib.mcedm_op_conv_bias_batch(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, Hs, Ws, H, W, _ptr(wpk),
+                                           _ptr(bias_pk), int(bias_batch), _ptr(res), res_mode, _ptr(out), Cout, B, k, _stream()),
+              "op_conv_bias_batch")
+        return out
     check(lib.mcedm_op_conv(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, Hs, Ws, H, W, _ptr(wpk),
                             _ptr(bias_pk), _ptr(res), res_mode, _ptr(out), Cout, B, k, _stream()), "op_conv")
     return out
@@ -1531,16 +1615,24 @@ def op_pack_conv_wino(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
 
 
 def op_conv_wino(xa, xb, wino, bias, Cout, coef=None, coef_batch=1, act=0, resample=RS_NONE, res=None, res_mode=RS_NONE,
-                 out=None, want_sums=False):
-    """want_sums: -> (out, the fused GroupNorm records of out as a plan's convs write them)."""
+                 out=None, want_sums=False, bias_batch=0):
+    """want_sums: -> (out, the fused GroupNorm records of out as a plan's convs write them).  bias_batch != 0 (with want_sums):
+    bias is [B, bias_batch], a row per sample (mcedm_op_conv_wino_sums_bias_batch)."""
     lib = _bind_ops()
     B, Ca, Hs, Ws = xa.shape
     Cb = xb.shape[1] if xb is not None else 0
     H, W = (Hs * 2, Ws * 2) if resample == RS_UP else (Hs, Ws)
     if out is None:
         out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=xa.device)
+    if bias_batch and (not want_sums or bias is None or bias.numel() < (B - 1) * bias_batch + Cout):
+        raise RuntimeError(f"op_conv_wino: bias_batch={bias_batch} goes with want_sums and a bias of {B} rows")
     if want_sums:
         gsum = torch.zeros(B * ((H + 3) // 4) * ((W + 7) // 8) * ((Cout + 3) // 4) * 2, dtype=torch.float32, device=xa.device)
+        if bias_batch:
+            check(lib.mcedm_op_conv_wino_sums_bias_batch(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, H, W,
+                                                         _ptr(wino), _ptr(bias), int(bias_batch), _ptr(res), res_mode, _ptr(out),
+                                                         _ptr(gsum), Cout, B, _stream()), "op_conv_wino_sums_bias_batch")
+            return out, gsum
         check(lib.mcedm_op_conv_wino_sums(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, H, W, _ptr(wino),
                                           _ptr(bias), _ptr(res), res_mode, _ptr(out), _ptr(gsum), Cout, B, _stream()), "op_conv_wino_sums")
         return out, gsum
