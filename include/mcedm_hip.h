@@ -564,6 +564,32 @@ int mcedm_op_conv_skip(const float* x, int Cin, const mcedm_coef* coef, int act,
                        const float* bias, const float* res, const float* sk_xa, const float* sk_xb, int sk_Ca, int sk_Cb,
                        const float* sk_wpk, const float* sk_wfrag, const float* sk_bias, float* out, float* gsum, int Cout, int B,
                        void* stream);
+/* The fused GroupNorm chain at kernel level.  A conv that produces a normalised tensor writes, per sample, pixel tile and block of rc
+ * channels, a record (sum, M2 about the record's own mean); the next conv merges the records in fp64.  A tiling is five ints, the
+ * geometry of a table: {tiles per sample, tiles along W, tile height, tile width, rc}; a table is [B][tiles][C / rc][2] floats.
+ *
+ * mcedm_op_conv_sums: the conv of mcedm_op_conv_bias_batch through the same dispatcher (wino: mcedm_op_pack_conv_wino's table or NULL,
+ * with which the Winograd kernels may serve the launch as in a plan), with the records of out in gsum -- room for
+ * B * ceil(H / 4) * ceil(W / 8) * (Cout / rc) * 2 floats, rc = 2 for gsum_rc = 2 and 4 for gsum_rc = 0 or 4 -- and the tiling the
+ * launcher chose in tiling_out.  MCEDM_ERR_INVALID for a NULL gsum or tiling_out, any other gsum_rc, Cout % rc != 0 (no partial
+ * records), and a kernel that cannot write the record width asked for. */
+int mcedm_op_conv_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act, int resample,
+                       int Hs, int Ws, int H, int W, const float* wpk, const float* wino, const float* bias_pk, int bias_batch,
+                       const float* res, int res_mode, float* out, int Cout, int B, int k, float* gsum, int gsum_rc, int* tiling_out,
+                       void* stream);
+/* gn_coef_from_sums_kernel: coef_out [B][Ca + Cb] (and stats_out [B][groups][2] = (mean, rstd), or NULL) of GroupNorm(groups) (+ FiLM as in
+ * mcedm_op_gn_coef) over cat(a, b) [B, Ca + Cb, H, W] from the records suma / sumb with tilings tiling_a / tiling_b (sumb, tiling_b NULL
+ * iff Cb == 0).  MCEDM_ERR_INVALID unless each tiling covers H x W and every group is a whole number of records of each table it
+ * touches: this entry never falls back to a pass over the tensor. */
+int mcedm_op_gn_coef_from_sums(const float* suma, const float* sumb, const int* tiling_a, const int* tiling_b, int Ca, int Cb, int B, int H,
+                               int W, int groups, const float* gamma, const float* beta, const float* film, int film_batch,
+                               int film_stride, float eps, mcedm_coef* coef_out, float* stats_out, void* stream);
+/* mcedm_op_conv whose transform rows are derived inside the kernel from the records of its SOURCE cat(xa, xb) [B, Ca + Cb, Hs, Ws]
+ * (the inference path of both U-Nets: no GroupNorm kernel runs); arguments as in the two entries above. */
+int mcedm_op_conv_gn(const float* xa, const float* xb, int Ca, int Cb, const float* suma, const float* sumb, const int* tiling_a,
+                     const int* tiling_b, int groups, const float* gamma, const float* beta, const float* film, int film_batch,
+                     int film_stride, float eps, int act, int resample, int Hs, int Ws, int H, int W, const float* wpk, const float* wino,
+                     const float* bias_pk, const float* res, int res_mode, float* out, int Cout, int B, int k, void* stream);
 /* The single-launch attention part of a UNetBlock at 8 x 8 x 64 channels (attn_fused.hip; inference only): 1 on, 0 off
  * (qkv conv + attention kernel + proj conv), -1 back to the default (env MCEDM_ATTN_FUSED, else on).  Process-global. */
 int mcedm_op_set_attn_fused(int enable);

@@ -811,7 +811,8 @@ static int dispatch(const ConvArgs& a, hipStream_t stream) {
     MCEDM_REQUIRE(coutp % g_force_mt == 0, "conv: forced MT=%d does not divide padded Cout=%d", g_force_mt, coutp);
     switch (id) {
       case 1281632:
-        MCEDM_REQUIRE(TAPS == 9 && a.resample == RS_NONE && a.Ca + a.Cb <= 2048 && !a.sk_wpk, "conv: the 8-wave kernel is 3x3, not resampled, without a folded projection");
+        MCEDM_REQUIRE(TAPS == 9 && a.resample == RS_NONE && a.Ca + a.Cb <= 2048 && !a.sk_wpk && a.gsum_rc != 2,
+                      "conv: the 8-wave kernel is 3x3, not resampled, without a folded projection, and writes 4-channel statistics records only");
         return launch_conv8(a, stream);
       case 1280832: return launch_cfg<ConvCfg<128, 8, 32, 1, 4, TAPS, KC>>(a, stream);
       case 1280816: return launch_cfg<ConvCfg<128, 8, 16, 1, 4, TAPS, KC>>(a, stream);

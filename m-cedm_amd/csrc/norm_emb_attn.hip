@@ -174,6 +174,9 @@ int launch_gn_coef_from_sums(const GnArgs& a, hipStream_t stream) {
   MCEDM_REQUIRE(a.groups > 0 && C % a.groups == 0, "group_norm: C=%d not divisible by groups=%d", C, a.groups);
   if (!gn_sums_usable(a))
     return launch_gn_coef(a, stream);            // no fused statistics for this shape: one pass over the tensor
+  // reads the records (8 bytes per sample, tile and record), writes the table
+  const double recs = (double)a.B * ((double)a.ta.tiles * (a.Ca / a.ta.rc) + (a.Cb ? (double)a.tb.tiles * (a.Cb / a.tb.rc) : 0.0));
+  ProfScope ps("gn_coef_from_sums_kernel", 6.0 * recs, 8.0 * recs + 16.0 * a.B * (double)C, stream);
   hipLaunchKernelGGL(gn_coef_from_sums_kernel, dim3(ceil_div(a.B * a.groups, 4)), dim3(256), 0, stream, a);
   MCEDM_LAUNCH_CHECK("gn_coef_from_sums_kernel");
   return MCEDM_OK;

@@ -153,6 +153,102 @@ extern "C" int mcedm_op_conv_skip(const float* x, int Cin, const mcedm_coef* coe
   return launch_conv(a, 9, (hipStream_t)stream);
 }
 
+// The conv of mcedm_op_conv_bias_batch through the dispatcher (wino: optional Winograd table, as a plan's convs carry one), with what
+// the fused GroupNorm chain adds to a launch: the records of `out` (gsum / gsum_rc, the tiling the launcher chose in tiling_out)
+// and / or transform rows derived inside the kernel from a producer's records (gn).
+static void tiling_to_ints(const SumTiles& t, int* o) { o[0] = t.tiles; o[1] = t.tiles_x; o[2] = t.ph; o[3] = t.pw; o[4] = t.rc; }
+static SumTiles tiling_from_ints(const int* t) { return t ? SumTiles{t[0], t[1], t[2], t[3], t[4]} : SumTiles{}; }
+
+static int op_conv_chain(const char* who, const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch,
+                         const GnArgs* gn, int act, int resample, int Hs, int Ws, int H, int W, const float* wpk, const float* wino,
+                         const float* bias_pk, int bias_batch, const float* res, int res_mode, float* out, int Cout, int B, int k,
+                         float* gsum, int gsum_rc, int* tiling_out, void* stream) {
+  MCEDM_REQUIRE(k == 1 || k == 3, "%s: k must be 1 or 3", who);
+  MCEDM_REQUIRE(resample >= 0 && resample <= 3 && res_mode >= 0 && res_mode <= 2, "%s: bad resample mode", who);
+  MCEDM_REQUIRE(bias_batch >= 0, "%s: bias_batch %d < 0", who, bias_batch);
+  ConvArgs a{};
+  a.xa = xa; a.xb = xb; a.Ca = Ca; a.Cb = Cb;
+  a.coef = reinterpret_cast<const Coef*>(coef); a.coef_batch = coef_batch; a.act = act;
+  a.resample = resample; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W;
+  a.wpk = wpk; a.wino = wino; a.bias = bias_pk; a.res = res; a.res_mode = res_mode;
+  a.out = out; a.Cout = Cout; a.B = B; a.bias_batch = bias_batch;
+  SumTiles st;
+  if (gsum) { a.gsum = gsum; a.gsum_rc = gsum_rc; a.gsum_tiles = &st; }
+  if (gn) { a.gn = *gn; a.gn_on = 1; a.coef = nullptr; a.coef_batch = 1; }
+  const int rc = launch_conv(a, k * k, (hipStream_t)stream);
+  if (rc) return rc;
+  if (gsum) {
+    MCEDM_REQUIRE(st.tiles > 0 && st.rc == (gsum_rc == 2 ? 2 : 4), "%s: the launcher wrote no tiling, or records of %d channels where %d were asked for",
+                  who, st.rc, gsum_rc == 2 ? 2 : 4);
+    tiling_to_ints(st, tiling_out);
+  }
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_op_conv_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                                  int resample, int Hs, int Ws, int H, int W, const float* wpk, const float* wino, const float* bias_pk,
+                                  int bias_batch, const float* res, int res_mode, float* out, int Cout, int B, int k, float* gsum,
+                                  int gsum_rc, int* tiling_out, void* stream) {
+  MCEDM_REQUIRE(gsum && tiling_out, "op_conv_sums: gsum / tiling_out is null");
+  MCEDM_REQUIRE(gsum_rc == 0 || gsum_rc == 2 || gsum_rc == 4, "op_conv_sums: gsum_rc = %d, records hold 4 (0 / 4) or 2 channels", gsum_rc);
+  // a partial record's element count is not the rc * h * w the consumers assume (sum_tile_count); no plan asks for one
+  MCEDM_REQUIRE(Cout > 0 && Cout % (gsum_rc == 2 ? 2 : 4) == 0, "op_conv_sums: Cout = %d is not a whole number of %d-channel records", Cout,
+                gsum_rc == 2 ? 2 : 4);
+  return op_conv_chain("op_conv_sums", xa, xb, Ca, Cb, coef, coef_batch, nullptr, act, resample, Hs, Ws, H, W, wpk, wino, bias_pk, bias_batch,
+                       res, res_mode, out, Cout, B, k, gsum, gsum_rc, tiling_out, stream);
+}
+
+// The GnArgs of a consumer of records: cat(a, b) [B, Ca + Cb, H, W] described by its producers' tables alone (no tensor pointers)
+static int op_gn_from_records(const char* who, GnArgs& g, const float* suma, const float* sumb, const int* tiling_a, const int* tiling_b,
+                              int Ca, int Cb, int B, int H, int W, int groups, const float* gamma, const float* beta, const float* film,
+                              int film_batch, int film_stride, float eps) {
+  MCEDM_REQUIRE(suma && tiling_a && gamma && beta, "%s: null pointer", who);
+  MCEDM_REQUIRE(B > 0 && H > 0 && W > 0 && Ca > 0 && Cb >= 0 && groups > 0, "%s: bad shape", who);
+  MCEDM_REQUIRE(Cb == 0 || (sumb && tiling_b), "%s: Cb = %d without the second table", who, Cb);
+  MCEDM_REQUIRE((Ca + Cb) % groups == 0, "%s: C=%d not divisible by groups=%d", who, Ca + Cb, groups);
+  g = GnArgs{nullptr, nullptr, Ca, Cb, H * W, B, groups, gamma, beta, film, film_batch, film_stride, eps, nullptr, nullptr, suma,
+             Cb ? sumb : nullptr, tiling_from_ints(tiling_a), Cb ? tiling_from_ints(tiling_b) : SumTiles{}, W};
+  for (const SumTiles* t : {&g.ta, &g.tb}) {
+    if (t == &g.tb && !Cb) break;
+    MCEDM_REQUIRE(t->tiles > 0 && t->tiles_x > 0 && t->ph > 0 && t->pw > 0 && t->tiles_x == ceil_div(W, t->pw) &&
+                      t->tiles == t->tiles_x * ceil_div(H, t->ph),
+                  "%s: tiling (%d tiles, %d across, %d x %d pixels) does not cover a %d x %d image", who, t->tiles, t->tiles_x, t->ph, t->pw, H, W);
+  }
+  // never the pass over the tensor that launch_gn_coef_from_sums falls back to: the caller has to know which kernel ran
+  MCEDM_REQUIRE(gn_sums_usable(g), "%s: records of %d | %d channels (%d / %d per record) do not tile %d groups", who, Ca, Cb, g.ta.rc,
+                Cb ? g.tb.rc : g.ta.rc, groups);
+  return MCEDM_OK;
+}
+
+// gn_coef_from_sums_kernel on its own: the transform table (+ statistics) of GroupNorm(groups) (+ FiLM) from records alone
+extern "C" int mcedm_op_gn_coef_from_sums(const float* suma, const float* sumb, const int* tiling_a, const int* tiling_b, int Ca, int Cb,
+                                          int B, int H, int W, int groups, const float* gamma, const float* beta, const float* film,
+                                          int film_batch, int film_stride, float eps, mcedm_coef* coef_out, float* stats_out,
+                                          void* stream) {
+  MCEDM_REQUIRE(coef_out, "op_gn_coef_from_sums: null pointer");
+  GnArgs g;
+  const int rc = op_gn_from_records("op_gn_coef_from_sums", g, suma, sumb, tiling_a, tiling_b, Ca, Cb, B, H, W, groups, gamma, beta, film,
+                                    film_batch, film_stride, eps);
+  if (rc) return rc;
+  g.coef = reinterpret_cast<Coef*>(coef_out); g.stats = stats_out;
+  return launch_gn_coef_from_sums(g, (hipStream_t)stream);
+}
+
+// A conv whose transform rows come from records inside the kernel (ConvArgs::gn_on, stage_coef_rows): the records describe the
+// SOURCE cat(xa, xb) [B, Ca + Cb, Hs, Ws]
+extern "C" int mcedm_op_conv_gn(const float* xa, const float* xb, int Ca, int Cb, const float* suma, const float* sumb, const int* tiling_a,
+                                const int* tiling_b, int groups, const float* gamma, const float* beta, const float* film, int film_batch,
+                                int film_stride, float eps, int act, int resample, int Hs, int Ws, int H, int W, const float* wpk,
+                                const float* wino, const float* bias_pk, const float* res, int res_mode, float* out, int Cout, int B, int k,
+                                void* stream) {
+  GnArgs g;
+  const int rc = op_gn_from_records("op_conv_gn", g, suma, sumb, tiling_a, tiling_b, Ca, Cb, B, Hs, Ws, groups, gamma, beta, film, film_batch,
+                                    film_stride, eps);
+  if (rc) return rc;
+  return op_conv_chain("op_conv_gn", xa, xb, Ca, Cb, nullptr, 1, &g, act, resample, Hs, Ws, H, W, wpk, wino, bias_pk, 0, res, res_mode, out,
+                       Cout, B, k, nullptr, 0, nullptr, stream);
+}
+
 // freqs[k] = (1/10000)^(k/half) exactly as the plan packs them (adm_blocks.py:193-196, endpoint=False)
 __global__ void op_freqs_kernel(float* f, int half) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;

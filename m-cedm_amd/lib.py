@@ -1429,6 +1429,11 @@ def _bind_ops():
     lib.mcedm_op_pack_conv_frag.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_skip.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]
     f32 = C.c_float
+    lib.mcedm_op_conv_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32,
+                                       vp, i32, vp, vp]
+    lib.mcedm_op_gn_coef_from_sums.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, vp, vp]
+    lib.mcedm_op_conv_gn.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, i32, i32, vp, vp,
+                                     vp, vp, i32, vp, i32, i32, i32, vp]
     lib.mcedm_op_ddim_cond_step.argtypes = [vp, vp, vp, vp, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32,
                                             i32, vp, i32, i32, vp, i32, i32, vp]
     lib.mcedm_op_ddim_cond_step_rng.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32,
@@ -1436,7 +1441,8 @@ def _bind_ops():
     for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
               "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
-              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch"):
+              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
+              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1449,7 +1455,8 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
               "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
-              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch"]
+              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
+              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1662,6 +1669,66 @@ def op_conv_skip(x, wpk, wino, bias, Cout, coef=None, act=1, res=None, sk_xa=Non
                                  sk_xa.shape[1] if sk_xa is not None else 0, sk_xb.shape[1] if sk_xb is not None else 0, _ptr(sk_wpk),
                                  _ptr(sk_wfrag), _ptr(sk_bias), _ptr(out), _ptr(gsum), Cout, B, _stream()), "op_conv_skip")
     return (out, gsum) if want_sums else out
+
+
+def _conv_hw(xa, resample):
+    Hs, Ws = xa.shape[2:]
+    H, W = (Hs * 2, Ws * 2) if resample == RS_UP else ((Hs // 2, Ws // 2) if resample in (RS_DOWN, RS_S2) else (Hs, Ws))
+    return Hs, Ws, H, W
+
+
+def _tiling_arg(t):
+    return None if t is None else (C.c_int * 5)(*[int(v) for v in t])
+
+
+def op_conv_sums(xa, xb, wpk, bias_pk, Cout, k, rc=4, wino=None, coef=None, coef_batch=1, act=0, resample=RS_NONE, res=None,
+                 res_mode=RS_NONE, bias_batch=0):
+    """op_conv through the dispatcher with the fused GroupNorm records of its output (mcedm_op_conv_sums): rc channels per record
+    (4 or 2); wino: op_pack_conv_wino's table, with which the Winograd kernels may take the launch as in a plan.
+    -> (out, records [B, tiles, Cout / rc, 2] = (sum, M2), tiling = (tiles, tiles_x, ph, pw, rc) as the launcher chose it).
+    The table is filled with NaN before the launch: a record the kernel does not write shows."""
+    lib = _bind_ops()
+    B, Ca = xa.shape[:2]
+    Cb = xb.shape[1] if xb is not None else 0
+    Hs, Ws, H, W = _conv_hw(xa, resample)
+    out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=xa.device)
+    nrec = -(-Cout // (2 if rc == 2 else 4))
+    gsum = torch.full((B * ((H + 3) // 4) * ((W + 7) // 8) * nrec * 2,), float("nan"), dtype=torch.float32, device=xa.device)
+    tiling = (C.c_int * 5)()
+    check(lib.mcedm_op_conv_sums(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, Hs, Ws, H, W, _ptr(wpk), _ptr(wino),
+                                 _ptr(bias_pk), int(bias_batch), _ptr(res), res_mode, _ptr(out), Cout, B, k, _ptr(gsum), int(rc), tiling,
+                                 _stream()), "op_conv_sums")
+    tiling = tuple(tiling)
+    if tiling[0] > ((H + 3) // 4) * ((W + 7) // 8):
+        raise RuntimeError(f"op_conv_sums: the launcher reports {tiling[0]} tiles, beyond the table")
+    return out, gsum[:B * tiling[0] * nrec * 2].view(B, tiling[0], nrec, 2), tiling
+
+
+def op_gn_coef_from_sums(suma, tiling_a, Ca, H, W, groups, gamma, beta, sumb=None, tiling_b=None, Cb=0, film=None, film_batch=0,
+                         film_stride=0, eps=1e-5):
+    """gn_coef_from_sums_kernel on records alone (mcedm_op_gn_coef_from_sums) -> (coef [B, Ca + Cb, 4], stats [B, groups, 2])."""
+    lib = _bind_ops()
+    B = suma.shape[0]
+    coef = torch.empty((B, Ca + Cb, 4), dtype=torch.float32, device=suma.device)
+    stats = torch.empty((B, groups, 2), dtype=torch.float32, device=suma.device)
+    check(lib.mcedm_op_gn_coef_from_sums(_ptr(suma), _ptr(sumb), _tiling_arg(tiling_a), _tiling_arg(tiling_b), Ca, Cb, B, H, W, groups,
+                                         _ptr(gamma), _ptr(beta), _ptr(film), film_batch, film_stride, eps, _ptr(coef), _ptr(stats),
+                                         _stream()), "op_gn_coef_from_sums")
+    return coef, stats
+
+
+def op_conv_gn(xa, xb, suma, tiling_a, groups, gamma, beta, wpk, bias_pk, Cout, k, sumb=None, tiling_b=None, film=None, film_batch=0,
+               film_stride=0, eps=1e-5, act=1, wino=None, resample=RS_NONE, res=None, res_mode=RS_NONE):
+    """op_conv whose GroupNorm (+ FiLM) rows the kernel derives from the records of cat(xa, xb) (mcedm_op_conv_gn)."""
+    lib = _bind_ops()
+    B, Ca = xa.shape[:2]
+    Cb = xb.shape[1] if xb is not None else 0
+    Hs, Ws, H, W = _conv_hw(xa, resample)
+    out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=xa.device)
+    check(lib.mcedm_op_conv_gn(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(suma), _ptr(sumb), _tiling_arg(tiling_a), _tiling_arg(tiling_b), groups,
+                               _ptr(gamma), _ptr(beta), _ptr(film), film_batch, film_stride, eps, act, resample, Hs, Ws, H, W, _ptr(wpk),
+                               _ptr(wino), _ptr(bias_pk), _ptr(res), res_mode, _ptr(out), Cout, B, k, _stream()), "op_conv_gn")
+    return out
 
 
 def op_embedding(labels, w0, b0, w1, b1, waff, baff):

@@ -355,3 +355,74 @@ def test_plan_variants_are_per_plan_and_validated():
     lib.mcedm_unet_plan_set_variant.argtypes = [C.c_void_p, C.c_int, C.c_int]
     assert lib.mcedm_unet_plan_set_variant(pa._h, 99, 1) != 0 and b"unknown switch" in lib.mcedm_last_error()
     assert lib.mcedm_unet_plan_set_variant(pa._h, 0, 7) != 0
+
+
+def test_host_side_rejections_of_the_groupnorm_record_entries():
+    """mcedm_op_conv_sums, mcedm_op_gn_coef_from_sums and mcedm_op_conv_gn refuse on the host, before any launch: null pointers, a
+    record width other than 2 or 4, an output that is no whole number of records, and tables that cannot serve the GroupNorm asked
+    for (the tiling does not cover the image, groups that are no whole records, records across the concat boundary) -- the last
+    instead of the pass over the tensor that the plan's launcher falls back to."""
+    lib = L._bind_ops()
+    one = C.c_void_p(4096)
+    til = lambda *t: (C.c_int * 5)(*t)      # noqa: E731
+    out5 = til(0, 0, 0, 0, 0)
+
+    def conv_sums(Cout=64, rc=4, gsum=one, tiling=out5, k=3, out=one, wpk=one):
+        return lib.mcedm_op_conv_sums(one, None, 64, 0, None, 0, 0, 0, 16, 16, 16, 16, wpk, None, one, 0, None, 0, out, Cout, 2, k, gsum, rc,
+                                      tiling, None)
+
+    assert conv_sums(gsum=None) == -1 and _last() == "op_conv_sums: gsum / tiling_out is null"
+    assert conv_sums(tiling=None) == -1 and _last() == "op_conv_sums: gsum / tiling_out is null"
+    for rc in (3, 1, 8, -2):
+        assert conv_sums(rc=rc) == -1 and _last() == f"op_conv_sums: gsum_rc = {rc}, records hold 4 (0 / 4) or 2 channels", rc
+    assert conv_sums(Cout=66) == -1 and _last() == "op_conv_sums: Cout = 66 is not a whole number of 4-channel records"
+    assert conv_sums(Cout=66, rc=0) == -1 and "4-channel records" in _last()
+    assert conv_sums(Cout=65, rc=2) == -1 and _last() == "op_conv_sums: Cout = 65 is not a whole number of 2-channel records"
+    assert conv_sums(k=2) == -1 and _last() == "op_conv_sums: k must be 1 or 3"
+    assert conv_sums(out=None) == -1 and conv_sums(wpk=None) == -1 and _last() == "conv: null output / weights"
+    assert list(out5) == [0] * 5                         # nothing was written
+
+    t16 = til(4, 2, 8, 8, 4)                             # 16 x 16 in 8 x 8 tiles, quad records
+
+    def coef(suma=one, sumb=None, ta=t16, tb=None, Ca=64, Cb=0, H=16, W=16, groups=16, gamma=one, beta=one, coef_out=one, B=2):
+        return lib.mcedm_op_gn_coef_from_sums(suma, sumb, ta, tb, Ca, Cb, B, H, W, groups, gamma, beta, None, 0, 0, 1e-5, coef_out, None, None)
+
+    def conv_gn(suma=one, sumb=None, ta=t16, tb=None, Ca=64, Cb=0, H=16, W=16, groups=16, gamma=one, beta=one, B=2, k=3):
+        return lib.mcedm_op_conv_gn(one, one if Cb else None, Ca, Cb, suma, sumb, ta, tb, groups, gamma, beta, None, 0, 0, 1e-5, 1, 0, H, W,
+                                    H, W, one, None, one, None, 0, one, 64, B, k, None)
+
+    assert coef(coef_out=None) == -1 and _last() == "op_gn_coef_from_sums: null pointer"
+    for who, call in (("op_gn_coef_from_sums", coef), ("op_conv_gn", conv_gn)):
+        for kw in (dict(suma=None), dict(ta=None), dict(gamma=None), dict(beta=None)):
+            assert call(**kw) == -1 and _last() == f"{who}: null pointer", (who, kw)
+        assert call(B=0) == -1 and _last() == f"{who}: bad shape", who
+        assert call(Cb=64, groups=32) == -1 and _last() == f"{who}: Cb = 64 without the second table", who
+        assert call(Cb=64, groups=32, sumb=one) == -1 and "without the second table" in _last(), who
+        assert call(groups=24) == -1 and _last() == f"{who}: C=64 not divisible by groups=24", who
+        # tilings that do not cover the image: too few tiles, the wrong row length, a degenerate tile
+        for bad in (til(3, 2, 8, 8, 4), til(4, 1, 8, 8, 4), til(4, 2, 8, 0, 4), til(0, 0, 0, 0, 0)):
+            assert call(ta=bad) == -1 and "does not cover a 16 x 16 image" in _last(), (who, list(bad))
+        assert call(H=20) == -1 and "does not cover a 20 x 16 image" in _last(), who
+        # unusable records: rc = 3, 2-channel groups on quad records, a quad across the concat boundary, pairs | quads with 2-channel groups
+        assert call(ta=til(4, 2, 8, 8, 3)) == -1 and _last() == f"{who}: records of 64 | 0 channels (3 / 3 per record) do not tile 16 groups", who
+        assert call(groups=32) == -1 and _last() == f"{who}: records of 64 | 0 channels (4 / 4 per record) do not tile 32 groups", who
+        assert call(Ca=66, Cb=62, sumb=one, tb=t16, groups=32) == -1 and "records of 66 | 62 channels (4 / 4 per record) do not tile 32" in _last(), who
+        assert call(Cb=64, sumb=one, ta=til(4, 2, 8, 8, 2), tb=t16, groups=64) == -1 and "(2 / 4 per record) do not tile 64 groups" in _last(), who
+    assert conv_gn(k=5) == -1 and _last() == "op_conv_gn: k must be 1 or 3"
+
+
+def test_forced_8_wave_tile_refuses_pair_records():
+    """The 8-wave kernel writes 4-channel records only.  The size heuristic never gives it a launch that asks for pairs; the forced tile
+    (128, 16, 32) used to, and reported rc = 4 for a table the caller had sized, and would read, as pairs."""
+    lib = L._bind_ops()
+    one = C.c_void_p(4096)
+    tiling = (C.c_int * 5)()
+    L.set_conv_tile(128, 16, 32)
+    try:
+        rc = lib.mcedm_op_conv_sums(one, None, 128, 0, None, 0, 0, 0, 32, 32, 32, 32, one, None, one, 0, None, 0, one, 128, 2, 3, one, 2, tiling,
+                                    None)
+        msg = _last()
+    finally:
+        L.set_conv_tile()
+    assert rc == -1 and "8-wave kernel" in msg and "4-channel statistics records only" in msg, (rc, msg)
+    assert list(tiling) == [0] * 5
