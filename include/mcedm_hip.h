@@ -105,6 +105,7 @@ void mcedm_unet_plan_destroy(mcedm_plan* plan);
 #define MCEDM_VARIANT_CONV1X1_REG 6     /* register-direct GEMM for un-transformed 1x1 convs at >= 32 x 32 (env MCEDM_CONV1X1_REG, default 1) */
 #define MCEDM_VARIANT_CONV_WINO_FOLD 7  /* decoder skip projections computed in the Winograd conv1's epilogue (env MCEDM_WINO_FOLD, default 1); the workspace layout does not depend on it */
 #define MCEDM_VARIANT_CONV_WINO_UPZ 8   /* up-sampling Winograd convs skip the positions whose transformed input is exactly zero and stage their input at source resolution (env MCEDM_WINO_UPZ, default 1); bit-identical results, the workspace layout does not depend on it */
+#define MCEDM_VARIANT_CONV_WINO_SPLIT 9 /* 3x3 convs below 32 x 32 on the Winograd kernel with the positions split over the waves (env MCEDM_WINO_SPLIT, default 1); the workspace layout does not depend on it */
 int mcedm_unet_plan_set_variant(mcedm_plan* plan, int which, int value);
 
 /* Parameter table in DhariwalUNet.state_dict() order (parameters only, no buffers).
@@ -425,6 +426,16 @@ int mcedm_op_conv_wino(const float* xa, const float* xb, int Ca, int Cb, const m
 int mcedm_op_conv_wino_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
                             int resample, int H, int W, const float* wino, const float* bias, const float* res, int res_mode,
                             float* out, float* gsum, int Cout, int B, void* stream);
+/* The same conv on the SPLIT variant of the Winograd kernel (one 32-channel output block per workgroup, the sixteen positions split
+ * over its eight waves; see mcedm_op_set_conv_wino_split), whatever that switch says: un-resampled, images below 32 x 32 with
+ * H % 8 == 0 and W % 16 == 0, Cout % 32 == 0, Ca % 8 == 0, (Ca + Cb) % 8 == 0, res_mode 0 or 2, 16-byte aligned inputs and table.
+ * Outputs and records carry the bits of mcedm_op_conv_wino / mcedm_op_conv_wino_sums on a shape that both serve. */
+int mcedm_op_conv_wino_split(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                             int H, int W, const float* wino, const float* bias, const float* res, int res_mode, float* out, int Cout,
+                             int B, void* stream);
+int mcedm_op_conv_wino_split_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                                  int H, int W, const float* wino, const float* bias, const float* res, int res_mode, float* out,
+                                  float* gsum, int Cout, int B, void* stream);
 /* mcedm_op_conv and mcedm_op_conv_wino_sums with a bias row PER SAMPLE: the bias is [B][bias_batch], bias_batch >= Cout floats
  * between the rows of consecutive samples (0: one row for the whole batch, the entries above).  Un-resampled 3x3 convolutions of
  * more than 4 output channels only, in the Winograd form with act = 1 (the form the DDPM U-Net's conv1 launches: its own
@@ -552,6 +563,14 @@ int mcedm_op_set_conv_wino_fold(int enable);
  * on).  Bit-identical results in every form for finite transformed weights (a product with an exact zero is dropped instead of
  * yielding NaN).  Read at every launch; the workspace layout does not depend on it.  Process-global. */
 int mcedm_op_set_conv_wino_upz(int enable);
+/* The SPLIT variant of the Winograd kernel (conv_wino.hip, WinoSplitCfg) for the un-resampled 3x3 convs of images below 32 x 32 (the
+ * 16 x 16 level) that carry a Winograd table: a workgroup is one 32-channel output block x one 8 x 16-pixel tile x all sixteen
+ * positions, the positions split over its eight waves: 1 on, 0 off (the input-resident / tiled kernels, as before), -1 back to the
+ * default (env MCEDM_WINO_SPLIT, else on).  Launches with a folded skip projection, a bias row per sample, the 8 x 8 level and
+ * misaligned inputs keep their kernels, as does every launch while the input-resident switch or a tile is set explicitly, the
+ * training path and the DDPM U-Net.  Results differ from the direct form in the last bits, as the Winograd kernel's do.  Read at every launch; the
+ * workspace layout does not depend on it.  Process-global. */
+int mcedm_op_set_conv_wino_split(int enable);
 /* [Cout][Cin] weights of a 1x1 conv -> the MFMA-fragment order that mcedm_op_conv_skip's sk_wfrag expects;
  * wfrag holds ((Cout + 31) / 32 * 32) * ((Cin + 7) / 8 * 8) floats, 16-byte aligned. */
 int mcedm_op_pack_conv_frag(const float* w, int Cout, int Cin, float* wfrag, void* stream);

@@ -42,8 +42,8 @@ void set_error(const char* fmt, ...);
 // (mcedm_*_plan_set_variant; a field of the plan, so two plans in one process -- on two threads or two streams -- cannot flip each
 // other's kernels), the process-wide test hooks mcedm_op_set_* (kernel-level calls have no plan), the environment.
 enum KernelVariant { KV_CONV_WINO = 0, KV_CONV_WINO1 = 1, KV_CONV_RESIDENT = 2, KV_CONV8 = 3, KV_ATTN_FUSED = 4, KV_WGRAD_WINO = 5,
-                     KV_CONV1X1_REG = 6, KV_CONV_WINO_FOLD = 7, KV_CONV_WINO_UPZ = 8, KV_COUNT = 9 };
-struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1}; };
+                     KV_CONV1X1_REG = 6, KV_CONV_WINO_FOLD = 7, KV_CONV_WINO_UPZ = 8, KV_CONV_WINO_SPLIT = 9, KV_COUNT = 10 };
+struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1}; };
 const KernelVariants* current_variants();                 // of the executing plan-level call on this thread, or null
 struct VariantScope {                                      // first statement of every extern "C" function that takes a plan
   const KernelVariants* prev;
@@ -193,6 +193,13 @@ int launch_pack_conv_frag(const float* w, float* dst, int Cout, int Cin, hipStre
 void set_conv_wino(int enable);                          // 1 / 0, -1: default (env MCEDM_WINOGRAD, else on)
 bool conv_wino_preferred(const ConvArgs& a);              // env MCEDM_WINOGRAD (default on), MCEDM_WINO_MIN_HW (default 32 x 32)
 int launch_conv_wino(const ConvArgs& a, hipStream_t stream);
+// the SPLIT variant (conv_wino.hpp WinoSplitCfg): un-resampled 3x3 convs on images below the other variants' minimum size
+bool conv_wino_split_applicable(const ConvArgs& a, int taps);
+bool conv_wino_split_preferred();                        // the Winograd kernels are on and so is this one
+bool conv_wino_small(int H, int W);                      // an image below the minimum size of the other variants (MCEDM_WINO_MIN_HW)
+int launch_conv_wino_split(const ConvArgs& a, hipStream_t stream);
+void set_conv_wino_split(int enable);                    // 1 / 0, -1: default (env MCEDM_WINO_SPLIT, else on)
+bool conv_resident_explicit();                           // a plan or mcedm_op_set_conv_resident has set the input-resident switch, either way
 static inline int cout_padded(int Cout) { return (Cout + 31) / 32 * 32; }     // channel padding of the packed tables
 int conv_resolve_identity(ConvArgs& a);                  // points a missing transform table at the identity row
 unsigned long long* conv_debug_buffer();

@@ -894,6 +894,9 @@ int launch_conv(const ConvArgs& a, int taps, hipStream_t stream) {
   // Winograd F(2x2, 3x3) kernel (conv_wino.hip) where the launch carries its weight table and the shape fits: chosen by shape
   // alone (never by the batch size), like every other tile choice here
   if (!g_force_mt && taps == 9 && a.wino && (a.bias_batch == 0 || a.act) && conv_wino_preferred(a) && conv_wino_applicable(a, taps)) return launch_conv_wino(a, stream);
+  // ... and below that kernel's minimum size its SPLIT variant (one 32-channel block per workgroup, the positions split over the waves),
+  // again by shape alone; an explicit request for the input-resident kernels (either way) or for a tile wins
+  if (!g_force_mt && !conv_resident_explicit() && conv_wino_split_preferred() && conv_wino_split_applicable(a, taps)) return launch_conv_wino_split(a, stream);
   if (!g_force_mt && taps == 1) {     // un-transformed 1x1 convs at >= 32 x 32 (the decoder's skip projections): register-direct GEMM
     const int rc = try_launch_conv1x1_reg(a, taps, stream);
     if (rc != -1) return rc;

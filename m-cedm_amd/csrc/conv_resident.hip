@@ -577,6 +577,7 @@ static int resident_level() {     // 0: off, > 0: on
   if (env < 0) { const char* e = getenv("MCEDM_CONV_RESIDENT"); env = e ? atoi(e) : 1; }
   return variant_choice(KV_CONV_RESIDENT, g_resident, env);
 }
+bool conv_resident_explicit() { return variant_choice(KV_CONV_RESIDENT, g_resident, -1) >= 0; }
 
 static constexpr int LDS_MAX = 160 * 1024;
 // big-tile (>= 64 x 64 images) variants: MCEDM_RES_BIG=0 turns them off; MCEDM_RES_BIG_PASS = channels per pass (multiple of 8)

@@ -25,6 +25,8 @@
 //     partial through LDS; then bias, residual, stores (8-byte, two pixels of a row) and the fused GroupNorm statistics.
 //   * up-sampled input (UP): by default the zero-position variant WinoUp (conv_wino.hpp) -- 9 of the 16 positions, the raw tile
 //     staged and transformed at source resolution; bit-identical to the sixteen-position form, which MCEDM_WINO_UPZ=0 keeps.
+//   * images below 32 x 32 (the 16 x 16 level): the SPLIT variant WinoSplitCfg (conv_wino.hpp) -- one 32-channel block per workgroup, the sixteen
+//     positions split over the eight waves, the same input path and the same expression tree in the epilogue: the bits of WinoCfg<4> / <2>.
 // Results differ from the direct kernel in the last bits (a different, equally long fp32 sum: measured 1.5x its error
 // against fp64, 0.1 of the rtol 1e-4 / atol 1e-5 bar); they do not depend on the batch size or the grid.
 #include <atomic>
@@ -195,6 +197,8 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   constexpr bool UPS = WinoUpTraits<Tag...>::UPS;                 // ... and the raw tile is staged and transformed at source resolution
   static_assert(!UPS || UPZ, "source-resolution staging is part of the zero-position variant");
   static_assert(!UPZ || (UP && !SKIP), "the zero positions belong to the up-sampled input");
+  constexpr bool SPLIT = C::SPLIT;                                // WinoSplitCfg: one 32-channel block per workgroup, the positions split over the waves
+  static_assert(!SPLIT || (!UP && !SKIP && sizeof...(Tag) == 0 && MB == 4 && WSC == 2), "the split variant: plain input, WinoCfg<4>'s input path");
   extern __shared__ float lds[];
   const int Cin = p.Ca + p.Cb;
   float* const vbuf = lds;
@@ -217,12 +221,21 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   // 4 MB L2 long before the neighbouring tile asked for its overlap: 1.9x the input from HBM).  Same tiles, same sums: same bits.
   int gt0 = blockIdx.x * per, tstep = 1;
   int n = gt0 / tiles_img, tile0 = gt0 % tiles_img;
-  if (mode & 256) {
+  if (!SPLIT && (mode & 256)) {
     const int nwg = gridDim.x, wps = tiles_img / per;
     const int lid = (nwg % 8 == 0) ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
     n = lid / wps; tile0 = lid % wps; tstep = wps;
   }
-  const int m0 = blockIdx.y * C::MT;
+  // SPLIT: a 1-D grid of B x tiles x Cout / 32 workgroups, one tile each; the Cout / 32 workgroups of a tile are consecutive in `lid`,
+  // i.e. 8 apart in workgroup id: one XCD, so that they find the raw tile and the producers' statistics in one L2
+  int split_mb = 0;
+  if constexpr (SPLIT) {
+    const int nwg = gridDim.x, nmb = p.Cout / C::MT;
+    const int lid = (nwg % 8 == 0) ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+    split_mb = lid % nmb;
+    n = (lid / nmb) / tiles_img; tile0 = (lid / nmb) % tiles_img;
+  }
+  const int m0 = SPLIT ? split_mb * C::MT : blockIdx.y * C::MT;
   const size_t HW = (size_t)p.H * p.W, HWs = (size_t)p.Hs * p.Ws;
   const int nst = (nch + WSC - 1) / WSC;                           // stages per tile
   const int G = per * nst;                                        // stages of this workgroup
@@ -453,9 +466,18 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   const size_t ustride = (size_t)mblocks * 16 * 64;                  // f32x4 per chunk
   // UPZ: block q of the hf = 1 waves is position 12 + q (xi = 3 first; its blocks 4 .. 7, xi = 2, are never touched)
   constexpr int PHF = UPZ ? 12 : 8;                                  // first position of the hf = 1 waves' block 0
-  const f32x4* up = reinterpret_cast<const f32x4*>(p.wino) + ((size_t)(m0 / 32 + mb) * 16 + PHF * hf) * 64 + lane;
+  // SPLIT: the wave's two positions 2 wave, 2 wave + 1 of the workgroup's block
+  const f32x4* up = reinterpret_cast<const f32x4*>(p.wino) + (SPLIT ? ((size_t)(m0 / 32) * 16 + 2 * wave) : ((size_t)(m0 / 32 + mb) * 16 + PHF * hf)) * 64 + lane;
   f32x4 ua[8];                                                       // reloaded position by position right after its last use
-  if constexpr (UPZ) {
+  // SPLIT: [chunk of the stage][position]: the current stage's fragments; the next stage's are requested a whole stage ahead
+  // (registers are plentiful here) and past the last chunk of the tile comes chunk 0 again, as in the other variants
+  f32x4 wa[WSC][2];
+  if constexpr (SPLIT) {
+#pragma unroll
+    for (int sc = 0; sc < WSC; ++sc)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) wa[sc][q] = up[(size_t)(sc < nch ? sc : 0) * ustride + q * 64];
+  } else if constexpr (UPZ) {
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     ua[0] = up[0 * 64]; ua[1] = up[1 * 64]; ua[3] = up[3 * 64];
     ua[4] = zero4; ua[5] = zero4; ua[7] = zero4;
@@ -477,11 +499,16 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float z = 0.f;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
+    for (int q = 0; q < (SPLIT ? 2 : 8); ++q) {
       asm volatile("" : "+v"(z));                          // an opaque zero per block: eight matrix instructions, not one + 112 copies
       acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(z, z, zero16, 0, 0, 0);
     }
-    if (hf == 0) {
+    if constexpr (SPLIT) {                                 // position (1, 1) = 5 is block 1 of wave 2
+      if (wave == 2) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[1][r] = bias_l[4 * (lane >> 5) + (r & 3) + 8 * (r >> 2)];
+      }
+    } else if (hf == 0) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[5][r] = bias_l[32 * mb + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2)];
     }
@@ -490,7 +517,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   init_acc();
 
   // ---- the stream of stages: one trip = one stage of WSC chunks
-  const int vrd = (PHF * hf) * VPOS + (lane >> 5) * VH1 + (lane & 31) * 4;
+  const int vrd = (SPLIT ? 2 * wave : PHF * hf) * VPOS + (lane >> 5) * VH1 + (lane & 31) * 4;
   if (p.dbg && tid == 0) { p.dbg[blockIdx.x * 16 + 1] = __builtin_amdgcn_s_memrealtime(); p.dbg[blockIdx.x * 16 + 5] = __builtin_amdgcn_s_memtime(); }
 #ifdef MCEDM_WINO_TIMELINE      // cycle sums of waves 0 and MB (lane 0): MFMA stream, barrier, epilogue -> dbg[8..12] / dbg[13..15, 7] (diagnostic builds only)
   unsigned long long ph[5] = {0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -560,6 +587,47 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     const int cur = g & 1;
     WINO_STAMP(0)
     WINO_SLOT0
+    if constexpr (SPLIT) {
+      // SPLIT: a stage is 2 x 4 slots of TWO MFMAs -- k-step s of the wave's two positions, so that every position still sums its
+      // chunks ascending, four k-steps per chunk, from the matrix pipe's zero -- and behind each slot the same slice of side work as
+      // in the other variants (same slot numbers, one basic block per slot).  The stage's four B fragments are read right behind
+      // the barrier, the next stage's four weight fragments requested with them.
+      f32x4 bf[WSC][2], wn[WSC][2];
+#pragma unroll
+      for (int sc = 0; sc < WSC; ++sc) {
+        const float* vb = vbuf + cur * VBUF + sc * 16 * VPOS + vrd;
+        bf[sc][0] = *reinterpret_cast<const f32x4*>(vb);
+        bf[sc][1] = *reinterpret_cast<const f32x4*>(vb + VPOS);
+      }
+#pragma unroll
+      for (int sc = 0; sc < WSC; ++sc) {
+        const int cn = (st + 1) * WSC + sc;
+        const f32x4* un = up + (size_t)(cn < nch ? cn : 0) * ustride;
+        wn[sc][0] = un[0];
+        wn[sc][1] = un[64];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int sc = 0; sc < WSC; ++sc) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[sc][0][s], bf[sc][0][s], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[sc][1][s], bf[sc][1][s], acc[1], 0, 0, 0);
+          side_slice(sc * 4 + s, g, cur);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x486, 4 * WINO_IL_K, 0);       // VALU | SALU | DS | transcendental
+          }
+          __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (sc * 4 + s == 5) raw_load_next();                                   // the one conditional piece (tile geometry): a block of its own
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+#pragma unroll
+      for (int sc = 0; sc < WSC; ++sc) { wa[sc][0] = wn[sc][0]; wa[sc][1] = wn[sc][1]; }
+    } else {
 #pragma unroll
     for (int sc = 0; sc < WSC; ++sc) {
       const int c = st * WSC + sc;
@@ -644,6 +712,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       }
       }
     }
+    }
     WINO_STAMP(1)
     __syncthreads();
     WINO_STAMP(2)
@@ -652,6 +721,102 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 
     // ---- a tile is complete: output transform, bias, residual, stores, statistics; then the accumulators start over.
     // (The stream's LDS buffers already hold the first stages of the next tile: the exchange area is a region of its own.)
+    if constexpr (SPLIT) {
+      // SPLIT: the workgroup's one tile is complete and its stream has drained (the trip's barrier is behind every wave): the sixteen
+      // blocks go to LDS over the V buffers, [position][register][lane].  Then wave (ehf, gq) takes the part of the other variants'
+      // wave (mb, hf = ehf) that sits in registers 4 gq .. 4 gq + 3 -- channels 8 gq + 4 (lane >> 5) + {0 .. 3}, patch lane & 31, pixel
+      // row ehf -- and evaluates their expressions on it: T_xi over nu, keep + the partner's send over xi, then the residual.
+      const int y0 = (tile / tiles_x) * WPH, x0 = (tile % tiles_x) * WPW;
+      float* const dump = lds;
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dump[((2 * wave + q) * 16 + r) * 64 + lane] = acc[q][r];
+      const int ehf = wave >> 2, gq = wave & 3, pt = lane & 31;
+      const int oy = y0 + 2 * (pt >> 3) + ehf, ox = x0 + 2 * (pt & 7);
+      const int cbase = m0 + 8 * gq + 4 * (lane >> 5);
+      const size_t splane = (size_t)p.Cout * HW;
+      const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(p.out + (size_t)n * splane, 4u * (unsigned)splane);
+      const size_t rplane = p.res_mode == RS_DOWN ? splane << 2 : splane;
+      const __amdgpu_buffer_rsrc_t rs_res = make_rsrc(p.res ? p.res + (size_t)n * rplane : nullptr, p.res ? 4u * (unsigned)rplane : 0u);
+      const unsigned HWu = (unsigned)HW;
+      const unsigned voff = 4u * ((unsigned)cbase * HWu + (unsigned)oy * p.W + ox);
+      float2 rv[4];
+      if (p.res && p.res_mode == RS_DOWN) {               // the 2x2 mean of the source at double resolution, as in the other variants
+        const unsigned dvoff = 4u * ((unsigned)cbase * (HWu << 2) + (unsigned)(2 * oy) * (unsigned)(2 * p.W) + (unsigned)(2 * ox));
+        f32x4 ta[4], tb[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const unsigned so = 4u * (unsigned)k * (HWu << 2);
+          ta[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, dvoff, so, 0));
+          tb[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, dvoff + 8u * (unsigned)p.W, so, 0));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          rv[k] = make_float2(0.25f * ((ta[k][0] + ta[k][1]) + (tb[k][0] + tb[k][1])), 0.25f * ((ta[k][2] + ta[k][3]) + (tb[k][2] + tb[k][3])));
+      } else {                                             // no residual: a zero-sized descriptor reads zeros
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rv[k] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_res, voff, 4u * (unsigned)k * HWu, 0));
+      }
+      __syncthreads();
+      float v0[4], v1[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        // T[i][j]: the nu-reduced block xi = ehf + i for pixel column j (A^T = [[1,1,1,0],[0,1,-1,-1]])
+        float T[3][2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float* d = dump + ((4 * (ehf + i)) * 16 + 4 * gq + k) * 64 + lane;
+          const float a0 = d[0 * 16 * 64], a1 = d[1 * 16 * 64], a2 = d[2 * 16 * 64], a3 = d[3 * 16 * 64];
+          T[i][0] = a0 + a1 + a2;
+          T[i][1] = a1 - a2 - a3;
+        }
+        if (ehf == 0) {                                    // row 0: keep = T0 + T1, the partner sends T2
+          v0[k] = (T[0][0] + T[1][0]) + T[2][0] + rv[k].x;
+          v1[k] = (T[0][1] + T[1][1]) + T[2][1] + rv[k].y;
+        } else {                                           // row 1: keep = -T2 - T3, the partner sends T1
+          v0[k] = (-T[1][0] - T[2][0]) + T[0][0] + rv[k].x;
+          v1[k] = (-T[1][1] - T[2][1]) + T[0][1] + rv[k].y;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, make_float2(v0[k], v1[k])), rs_out, voff,
+                                              4u * (unsigned)k * HWu, 0);
+      if (p.gsum) {                                        // the records of the other variants' wave (mb, hf) for its group gq
+        const bool pairs = p.gsum_rc == 2;
+        float a[2], b[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) a[e] = half_sum32((v0[2 * e] + v1[2 * e]) + (v0[2 * e + 1] + v1[2 * e + 1]));
+        const float cnt = pairs ? 128.f : 256.f;
+        const float mean0 = pairs ? a[0] * (1.0f / 128.0f) : (a[0] + a[1]) * (1.0f / 256.0f);
+        const float mean1 = pairs ? a[1] * (1.0f / 128.0f) : mean0;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float mean = e ? mean1 : mean0;
+          float q = 0.f;
+#pragma unroll
+          for (int r = 2 * e; r < 2 * e + 2; ++r) { const float d0 = v0[r] - mean, d1 = v1[r] - mean; q = fmaf(d0, d0, q); q = fmaf(d1, d1, q); }
+          b[e] = half_sum32(q);
+        }
+        if ((lane & 31) == 0) {
+          const int quad = 2 * gq + (lane >> 5);
+          if (pairs) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              float* slot = red + (ehf * (C::MT / 2) + 2 * quad + e) * 3;
+              slot[0] = cnt; slot[1] = a[e]; slot[2] = b[e];
+            }
+          } else {
+            float* slot = red + (ehf * (C::MT / 4) + quad) * 3;
+            slot[0] = cnt; slot[1] = a[0] + a[1]; slot[2] = b[0] + b[1];
+          }
+        }
+        __syncthreads();
+        conv_stats_store<C, 2>(p, red, n, m0, tile, tiles_img, tid);
+      }
+      break;
+    }
     WINO_EP(0)
     const int y0 = (tile / tiles_x) * WPH, x0 = (tile % tiles_x) * WPW;
     const int pt = lane & 31;                             // this wave stores row hf of every patch: pixels
@@ -827,7 +992,14 @@ static int wino_upz_env() {                                    // MCEDM_WINO_UPZ
   if (env < 0) { const char* e = getenv("MCEDM_WINO_UPZ"); env = e ? atoi(e) : 1; }
   return variant_choice(KV_CONV_WINO_UPZ, g_wino_upz, env);
 }
-static int wino_mode_env() {                                   // MCEDM_WINO_MODE: ablation bits of the -DMCEDM_WINO_TIMELINE build (else unused)
+static int g_wino_split = -1; // -1: default (env MCEDM_WINO_SPLIT, else on); 0 / 1: forced by mcedm_op_set_conv_wino_split
+void set_conv_wino_split(int enable) { g_wino_split = enable; }
+static int wino_split_env() {                                  // MCEDM_WINO_SPLIT=0: the small images' 3x3 convs stay on the input-resident / tiled kernels
+  static int env = -1;
+  if (env < 0) { const char* e = getenv("MCEDM_WINO_SPLIT"); env = e ? atoi(e) : 1; }
+  return variant_choice(KV_CONV_WINO_SPLIT, g_wino_split, env);
+}
+static int wino_mode_env() {                                  // MCEDM_WINO_MODE: ablation bits of the -DMCEDM_WINO_TIMELINE build (else unused)
   static int env = -1;                                         // | 256: the interleaved, XCD-aware tile map (MCEDM_WINO_MAP, default on)
   if (env < 0) {
     const char* e = getenv("MCEDM_WINO_MODE");
@@ -1003,5 +1175,58 @@ bool conv_wino_shape_ok(int Cout, int Cin, int H, int W) {
 }
 // the dispatcher's choice: enabled, and an image large enough for the grid to fill the chip
 bool conv_wino_preferred(const ConvArgs& a) { return wino_env() != 0 && (long long)a.H * a.W >= wino_min_hw_env(); }
+
+// ---- the SPLIT variant (WinoSplitCfg): the images below that size
+bool conv_wino_small(int H, int W) { return (long long)H * W < wino_min_hw_env(); }
+bool conv_wino_split_preferred() { return wino_env() != 0 && wino_split_env() != 0; }
+// Un-resampled 3x3 convs with a Winograd table on whole 8 x 16 tiles, whole 32-channel output blocks and whole chunks out of either
+// source; residual absent, same-size or the 2x2 mean of a double-resolution source.  A folded skip projection, a bias row per
+// sample and anything misaligned stay with the direct kernels.
+bool conv_wino_split_applicable(const ConvArgs& a, int taps) {
+  const int Cin = a.Ca + a.Cb;
+  return taps == 9 && a.wino && a.resample == RS_NONE && !a.sk_wpk && a.bias_batch == 0 && conv_wino_small(a.H, a.W) && a.Cout % 32 == 0 &&
+         a.H % WPH == 0 && a.W % WPW == 0 && a.Ca > 0 && a.Cb >= 0 && Cin % WKC == 0 && a.Ca % WKC == 0 && Cin <= 1024 &&
+         (((size_t)a.xa | (size_t)a.xb | (size_t)a.wino) & 15) == 0 && (!a.res || a.res_mode == RS_NONE || a.res_mode == RS_DOWN);
+}
+
+int launch_conv_wino_split(const ConvArgs& a_in, hipStream_t stream) {
+  typedef WinoSplitCfg C;
+  ConvArgs a = a_in;
+  a.dbg = nullptr;                                         // the in-kernel stamps are the large kernels'
+  MCEDM_REQUIRE(conv_wino_split_applicable(a, 9), "conv_wino_split: shape not served by the split Winograd kernel");
+  MCEDM_REQUIRE(a.out && a.B > 0 && a.Hs == a.H && a.Ws == a.W, "conv_wino_split: bad arguments");
+  MCEDM_REQUIRE((unsigned long long)a.H * a.W * 4ull * a.Cout * (a.res && a.res_mode == RS_DOWN ? 4 : 1) < (1ull << 32),
+                "conv_wino_split: one sample of the output / residual exceeds the 4 GiB buffer range");
+  { const int rc = conv_resolve_identity(a); if (rc != MCEDM_OK) return rc; }
+  const int tiles_x = a.W / WPW, tiles_img = tiles_x * (a.H / WPH), nmb = a.Cout / C::MT;
+  const long long total = (long long)a.B * tiles_img * nmb;
+  MCEDM_REQUIRE(total > 0 && total <= 0x7fffffffLL, "conv_wino_split: grid out of range");
+  const int Cin = a.Ca + a.Cb, nch = Cin / WKC;
+  const int lds_bytes = (C::LDS_ROWS_OFF + 4 * Cin + C::XCH_FLOATS + C::RED_FLOATS) * 4;
+  MCEDM_REQUIRE(lds_bytes <= 160 * 1024, "conv_wino_split: %d input channels exceed the LDS row table", Cin);
+  static std::atomic<bool> attr_set[64];
+  int dev = 0;
+  MCEDM_HIP_TRY(hipGetDevice(&dev));
+  MCEDM_REQUIRE(dev >= 0 && dev < 64, "device index %d out of range", dev);
+  if (!attr_set[dev].load(std::memory_order_acquire)) {
+    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_set[dev].store(true, std::memory_order_release);
+  }
+  char name[64] = "";
+  if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<WinoSplitCfg, false, %s>", a.act ? "true" : "false");   // = rocprofv3's name
+  const double px = (double)a.B * a.H * a.W;
+  ProfScope ps(name, 2.0 * px * a.Cout * (double)Cin * 9,
+               4.0 * ((double)a.B * Cin * a.H * a.W + px * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * Cin * 9), stream);
+  if (a.act)
+    hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)total), dim3(C::NT), lds_bytes, stream, a, tiles_x, tiles_img, nch,
+                       cout_padded(a.Cout) / 32, 1, 0);
+  else
+    hipLaunchKernelGGL((conv_wino_kernel<C, false, false>), dim3((unsigned)total), dim3(C::NT), lds_bytes, stream, a, tiles_x, tiles_img, nch,
+                       cout_padded(a.Cout) / 32, 1, 0);
+  MCEDM_LAUNCH_CHECK("conv_wino_kernel");
+  if (a.gsum_tiles) *a.gsum_tiles = SumTiles{tiles_img, tiles_x, WPH, WPW, a.gsum_rc == 2 ? 2 : 4};
+  return MCEDM_OK;
+}
 
 }  // namespace mcedm

@@ -22,8 +22,26 @@ struct WinoCfg {
   static constexpr int XCH_FLOATS = NW * 16 * 64;                       // epilogue exchange: one round of 16 registers x 64 lanes per wave
   static constexpr int RED_FLOATS = 2 * (MT / 2) * 3 + MT;              // statistics records of the two halves (pairs at most) + the bias row
   static constexpr bool SKIP = false;                                   // see WinoSkipCfg
+  static constexpr bool SPLIT = false;                                  // see WinoSplitCfg
   static_assert(MB_ == 4 || MB_ == 2, "128 or 64 output channels per workgroup");
   static_assert(LDS_ROWS_OFF % 4 == 0, "LDS layout");
+};
+// The SPLIT variant, for images below the other variants' minimum size (16 x 16: at B = 32 a 128-channel workgroup per pixel tile
+// leaves three quarters of the chip idle): a workgroup is ONE 32-channel output block x one pixel tile x all sixteen positions,
+// and the POSITIONS are split over the eight waves -- wave w owns positions 2 w, 2 w + 1 (xi = w >> 1, nu = 2 (w & 1) + {0, 1}): two
+// accumulator blocks, eight MFMAs per chunk.  The input path is WinoCfg<4>'s, instruction for instruction (512 threads, two chunks
+// per stage, wave w stages channel w of a chunk, thread = (channel, patch, row half) in the transform); the epilogue passes all
+// sixteen blocks through LDS (64 KB over the drained V buffers) and evaluates the output transform in the expression tree of the
+// other variants -- over nu, then over xi, keep + the partner's send, residual -- on their lane layout (wave = row half x
+// four-register group), so outputs and GroupNorm records carry the bits of WinoCfg<4> / WinoCfg<2> on the same shape.
+// A configuration class of its own: an instantiation and a profiler name of its own, the other variants keep theirs.
+struct WinoSplitCfg : WinoCfg<4> {
+  static constexpr int MT = 32;                                         // output channels per workgroup
+  static constexpr int XCH_FLOATS = 0;                                  // no exchange area: the accumulator dump aliases the V buffers
+  static constexpr int RED_FLOATS = 2 * (MT / 2) * 3 + MT;
+  static constexpr int DUMP_FLOATS = 16 * 16 * 64;                      // sixteen blocks of 16 registers x 64 lanes
+  static constexpr bool SPLIT = true;
+  static_assert(DUMP_FLOATS <= 2 * VBUF, "the accumulator dump fits the two V buffers");
 };
 // The SKIP variant (ConvArgs::sk_wfrag): the epilogue COMPUTES the residual -- the decoder block's 1x1 skip projection of
 // cat(sk_xa, sk_xb), 32 channels x 64 pixels per wave -- on the matrix pipe instead of loading it.  A configuration class of its

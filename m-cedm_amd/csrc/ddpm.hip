@@ -657,7 +657,9 @@ static void src_of(const DExec& E, ConvArgs& c, int xa, int xb) {
 }
 static void dst_of(DExec& E, ConvArgs& c, int out, const DConv& cv, const float* bias, bool stats) {
   c.wpk = E.pk + cv.wpk; c.bias = bias ? bias : E.pk + cv.bias;
-  c.wino = cv.wino != NONE ? E.pk + cv.wino : nullptr;
+  // (below 32 x 32 the DDPM U-Net keeps its input-resident / tiled kernels: its conv1 has a bias row per sample in one entry and a
+  // shared row in the other, the two must agree bit for bit, and the Winograd kernel's split variant has no per-sample form)
+  c.wino = cv.wino != NONE && !conv_wino_small(E.t[out].H, E.t[out].W) ? E.pk + cv.wino : nullptr;
   c.out = E.ptr(out); c.Cout = cv.cout; c.B = E.B;
   if (stats && E.t[out].rc) { c.gsum = E.sums(out); c.gsum_rc = E.t[out].rc; c.gsum_tiles = &E.t[out].st; }
 }

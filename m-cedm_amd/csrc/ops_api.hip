@@ -128,6 +128,35 @@ extern "C" int mcedm_op_conv_wino_sums_bias_batch(const float* xa, const float* 
                            stream);
 }
 
+// The same conv on the SPLIT variant of the Winograd kernel (conv_wino.hpp WinoSplitCfg: images below 32 x 32, Cout % 32 == 0), whatever
+// the switch says; gsum: null, or the fused GroupNorm records of `out`.  Bit-identical to mcedm_op_conv_wino(_sums) on a shape both serve.
+static int op_conv_wino_split(const char* who, const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                              int H, int W, const float* wino, const float* bias, const float* res, int res_mode, float* out, float* gsum,
+                              int Cout, int B, void* stream) {
+  MCEDM_REQUIRE(res_mode == RS_NONE || res_mode == RS_DOWN, "%s: res_mode must be 0 or 2 (2x2-mean down)", who);
+  ConvArgs a{};
+  a.xa = xa; a.xb = xb; a.Ca = Ca; a.Cb = Cb;
+  a.coef = reinterpret_cast<const Coef*>(coef); a.coef_batch = coef_batch; a.act = act;
+  a.resample = RS_NONE; a.H = H; a.W = W; a.Hs = H; a.Ws = W;
+  a.wino = wino; a.bias = bias; a.res = res; a.res_mode = res_mode;
+  SumTiles st;
+  a.out = out; a.Cout = Cout; a.B = B; a.gsum = gsum; a.gsum_tiles = gsum ? &st : nullptr;
+  MCEDM_REQUIRE(conv_wino_split_applicable(a, 9),
+                "%s: needs an image below 32 x 32 with H %% 8 == 0 and W %% 16 == 0, Cout %% 32 == 0, Ca %% 8 == 0, Cin %% 8 == 0 and 16-byte aligned inputs / weight table", who);
+  return launch_conv_wino_split(a, (hipStream_t)stream);
+}
+extern "C" int mcedm_op_conv_wino_split(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                                        int H, int W, const float* wino, const float* bias, const float* res, int res_mode, float* out,
+                                        int Cout, int B, void* stream) {
+  return op_conv_wino_split("op_conv_wino_split", xa, xb, Ca, Cb, coef, coef_batch, act, H, W, wino, bias, res, res_mode, out, nullptr, Cout, B, stream);
+}
+extern "C" int mcedm_op_conv_wino_split_sums(const float* xa, const float* xb, int Ca, int Cb, const mcedm_coef* coef, int coef_batch, int act,
+                                             int H, int W, const float* wino, const float* bias, const float* res, int res_mode, float* out,
+                                             float* gsum, int Cout, int B, void* stream) {
+  MCEDM_REQUIRE(gsum, "op_conv_wino_split_sums: gsum is null");
+  return op_conv_wino_split("op_conv_wino_split_sums", xa, xb, Ca, Cb, coef, coef_batch, act, H, W, wino, bias, res, res_mode, out, gsum, Cout, B, stream);
+}
+
 // A 1x1 conv's weights [Cout][Cin] in the MFMA-fragment order of ConvArgs::sk_wfrag (cout_padded(Cout) * ceil8(Cin) floats)
 extern "C" int mcedm_op_pack_conv_frag(const float* w, int Cout, int Cin, float* wfrag, void* stream) {
   return launch_pack_conv_frag(w, wfrag, Cout, Cin, (hipStream_t)stream);
@@ -364,6 +393,11 @@ extern "C" int mcedm_op_set_conv_wino_fold(int enable) {
 
 extern "C" int mcedm_op_set_conv_wino_upz(int enable) {
   set_conv_wino_upz(enable);
+  return MCEDM_OK;
+}
+
+extern "C" int mcedm_op_set_conv_wino_split(int enable) {
+  set_conv_wino_split(enable);
   return MCEDM_OK;
 }
 

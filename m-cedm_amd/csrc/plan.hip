@@ -73,7 +73,8 @@ static void place_conv(Taker& t, ConvP& c, bool dgrad) {
   c.bias = t.take((size_t)(c.cout + 31) / 32 * 32);
   if (dgrad) c.wpk_dgrad = t.take(conv_packed_floats(c.cin, c.cout, c.taps));
   if (c.taps == 9 && c.qkv_heads == 0) {       // Winograd tables where the kernel's channel constraints can be met
-    if (c.cout % 64 == 0 && c.cin % 8 == 0) c.wino = t.take(conv_wino_packed_floats(c.cout, c.cin));
+    // (whole 32-channel blocks: the split variant of the kernel, which serves the images below 32 x 32; the others need 64)
+    if (c.cout % 32 == 0 && c.cin % 8 == 0) c.wino = t.take(conv_wino_packed_floats(c.cout, c.cin));
     if (dgrad && c.cin % 64 == 0 && c.cout % 8 == 0) c.wino_dgrad = t.take(conv_wino_packed_floats(c.cin, c.cout));
   }
 }
@@ -422,6 +423,7 @@ int build_layout(const mcedm_plan& P, int B, int H, int W, int training, int n_n
   MCEDM_REQUIRE(n_noise == 1 || n_noise == B, "layout: n_noise=%d must be 1 or B=%d", n_noise, B);
   Layout& L = *out;
   L = Layout();
+  L.training = training != 0;
   LayoutBuilder lb{L, Pool(), B};
   lb.pool.keep_all = training != 0;
   L.film = lb.make(P.film_rows, 1, 1, (size_t)n_noise * P.film_rows * sizeof(float));
@@ -596,7 +598,8 @@ ConvArgs AdmNet::conv(const ConvP& cv, const float* xa, int Ca, const float* xb,
   c.xa = xa; c.Ca = Ca; c.xb = xb; c.Cb = Cb;
   c.Hs = Hs; c.Ws = Ws; c.H = H; c.W = W;
   c.wpk = pk + cv.wpk; c.bias = pk + cv.bias;
-  c.wino = cv.wino != NONE ? pk + cv.wino : nullptr;
+  // (training keeps the kernels its backward was built on: below 32 x 32 its convs carry no Winograd table, so the split variant never takes them)
+  c.wino = cv.wino != NONE && !(L.training && conv_wino_small(H, W)) ? pk + cv.wino : nullptr;
   c.out = T(dst); c.Cout = cv.cout; c.B = B;
   c.gsum = SUMS(dst); c.gsum_tiles = c.gsum ? &st[dst] : nullptr;
   return c;

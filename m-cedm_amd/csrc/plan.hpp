@@ -164,6 +164,7 @@ struct Layout {
   int xdx = -1, xf = -1, d1 = -1, g1 = -1, d2 = -1;
   size_t sums_base = 0, sums_bytes = 0;   // arena of all fused-statistics tables
   size_t total_bytes = 0;
+  bool training = false;       // laid out for training (build_layout)
 };
 
 }  // namespace mcedm

@@ -56,7 +56,7 @@ SAMPLER_STEMS = {
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
 VARIANTS = {"conv_wino": 0, "conv_wino1": 1, "conv_resident": 2, "conv8": 3, "attn_fused": 4, "wgrad_wino": 5, "conv1x1_reg": 6,
-            "conv_wino_fold": 7, "conv_wino_upz": 8}
+            "conv_wino_fold": 7, "conv_wino_upz": 8, "conv_wino_split": 9}
 
 
 class UNetDesc(C.Structure):
@@ -1422,6 +1422,8 @@ def _bind_ops():
     lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
     lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
     lib.mcedm_op_conv_wino_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
+    lib.mcedm_op_conv_wino_split.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
+    lib.mcedm_op_conv_wino_split_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
     lib.mcedm_op_conv_bias_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32,
                                              i32, i32, vp]
     lib.mcedm_op_conv_wino_sums_bias_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32,
@@ -1442,7 +1444,7 @@ def _bind_ops():
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
               "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
               "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
-              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn"):
+              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn", "mcedm_op_conv_wino_split", "mcedm_op_conv_wino_split_sums"):
         getattr(lib, n).restype = C.c_int
     _OPS_BOUND = True
     return lib
@@ -1456,7 +1458,8 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
               "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
               "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
-              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn"]
+              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn", "mcedm_op_conv_wino_split", "mcedm_op_conv_wino_split_sums",
+              "mcedm_op_set_conv_wino_split"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1524,6 +1527,15 @@ def set_conv_wino_upz(enable: int = -1) -> None:
     lib = _bind_ops()
     lib.mcedm_op_set_conv_wino_upz.argtypes = [C.c_int]
     check(lib.mcedm_op_set_conv_wino_upz(int(enable)), "set_conv_wino_upz")
+
+
+def set_conv_wino_split(enable: int = -1) -> None:
+    """The un-resampled 3x3 convs of images below 32 x 32 (the 16 x 16 level) run on the Winograd kernel with one 32-channel block per
+    workgroup and the sixteen positions split over its waves (conv_wino.hip, WinoSplitCfg): 1 / 0 (the input-resident / tiled
+    kernels); -1 = default (on).  An explicit set_conv_resident / set_conv_tile wins."""
+    lib = _bind_ops()
+    lib.mcedm_op_set_conv_wino_split.argtypes = [C.c_int]
+    check(lib.mcedm_op_set_conv_wino_split(int(enable)), "set_conv_wino_split")
 
 
 def set_wgrad_wino(enable: int = -1) -> None:
@@ -1645,6 +1657,24 @@ def op_conv_wino(xa, xb, wino, bias, Cout, coef=None, coef_batch=1, act=0, resam
         return out, gsum
     check(lib.mcedm_op_conv_wino(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, resample, H, W, _ptr(wino),
                                  _ptr(bias), _ptr(res), res_mode, _ptr(out), Cout, B, _stream()), "op_conv_wino")
+    return out
+
+
+def op_conv_wino_split(xa, xb, wino, bias, Cout, coef=None, coef_batch=1, act=0, res=None, res_mode=RS_NONE, out=None, want_sums=False):
+    """op_conv_wino on the split variant of the kernel (mcedm_op_conv_wino_split / _sums): un-resampled, images below 32 x 32,
+    Cout % 32 == 0.  want_sums: -> (out, the fused GroupNorm records of out)."""
+    lib = _bind_ops()
+    B, Ca, H, W = xa.shape
+    Cb = xb.shape[1] if xb is not None else 0
+    if out is None:
+        out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=xa.device)
+    if want_sums:
+        gsum = torch.zeros(B * ((H + 3) // 4) * ((W + 7) // 8) * ((Cout + 3) // 4) * 2, dtype=torch.float32, device=xa.device)
+        check(lib.mcedm_op_conv_wino_split_sums(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, H, W, _ptr(wino), _ptr(bias),
+                                                _ptr(res), res_mode, _ptr(out), _ptr(gsum), Cout, B, _stream()), "op_conv_wino_split_sums")
+        return out, gsum
+    check(lib.mcedm_op_conv_wino_split(_ptr(xa), _ptr(xb), Ca, Cb, _ptr(coef), coef_batch, act, H, W, _ptr(wino), _ptr(bias), _ptr(res),
+                                       res_mode, _ptr(out), Cout, B, _stream()), "op_conv_wino_split")
     return out
 
 
