@@ -345,6 +345,20 @@ int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm
 int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
                              const float* init_noise, const uint64_t* rng_seed, double* out, int return_last, void* workspace,
                              size_t workspace_bytes, int B, int H, int W, void* stream);
+/* mcedm_vp_heun_sample / _rng in one signature (at most one of step_noise and rng_seed non-NULL, else MCEDM_ERR_INVALID) with
+ * PDE guidance (guide_dx=True): after each get_denoised, dx = get_dx_log_prob(h, D) on the fp32 D (models/ddim.py:1576, 1589 ->
+ * get_dx_pde :1424-1450; h = cond[:, 0] of the caller's unscaled cond, u = D) and
+ *   d_cur = (x_hat - D) / t_hat - weight * dx / t_hat,  d_prime = (x_next - D') / t_next - weight * dx' / t_hat   (:1576-1578, 1589-1590)
+ * -- both stages divide by t_hat.  gd: the description of mcedm_heun_sample_guided, weight 5.0 in the reference.  gd == NULL
+ * reproduces the unguided entry bit for bit.  gd != NULL requires in_channels == 1, cond != NULL, sp->cond_channels >= 1,
+ * gd->system in {1, 2} and, for Darcy, a square grid larger than 4 x 4: otherwise MCEDM_ERR_INVALID before any launch.  The workspace
+ * (mcedm_vp_guided_workspace_bytes) is the unguided one plus the gradient [B, 1, H, W] and the Darcy scratch; with gd == NULL the
+ * unguided size suffices. */
+int mcedm_vp_guided_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes);
+int mcedm_vp_heun_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const double* step_noise,
+                                const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes,
+                                int B, int H, int W, void* stream);
 
 /* PlCondDdim.sample (models/ddim.py:1452-1530): the DDIM sampler of the single-task conditional network, guide_dx False,
  * dx_cond False.  Everything is fp32 like the reference; one network evaluation per step, two with guidance, and one fused
@@ -382,6 +396,18 @@ int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mce
 int mcedm_cond_ddim_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
                                const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last,
                                void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
+/* mcedm_cond_ddim_sample / _rng in one signature (at most one of eta_noise and rng_seed non-NULL, else MCEDM_ERR_INVALID) with PDE
+ * guidance (guide_dx=True, models/ddim.py:1499-1503): per step, after the classifier-free blend of et,
+ *   dx = get_dx_log_prob(h, xt)  at the CURRENT NOISY STATE xt (:1501; h = cond[:, 0], u = xt, get_dx_pde :1424-1450)
+ *   et = et - weight * (1 - at).sqrt() * dx                                                                  (:1502-1503)
+ * in fp32 in that order (gw = fl(weight * s1), g = fl(gw * dx), et = fl(et - g)); the guided et feeds x0_t, the next step's
+ * x_self_cond and xt_next (:1505-1515).  The guidance launches of a step go in front of its network launches.  gd, its checks, the
+ * gd == NULL case and the workspace (mcedm_cond_ddim_guided_workspace_bytes): as for mcedm_vp_heun_sample_guided. */
+int mcedm_cond_ddim_guided_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes);
+int mcedm_cond_ddim_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                  const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const float* eta_noise,
+                                  const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last, void* workspace,
+                                  size_t workspace_bytes, int B, int H, int W, void* stream);
 
 /* ---- kernel-level entry points ----------------------------------------------------------
  * The building blocks the schedules above are made of, exported so that each kernel can be
@@ -516,6 +542,14 @@ int mcedm_op_ddim_cond_step_rng(const float* xt, const float* F, const float* Fu
                                 float s0, float s1, float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u,
                                 int cond_channels, int plan_cond_channels, int B, int C, int H, int W, float* xs, int T_xs,
                                 int t_xs, float* x0s, int T_x0, int t_x0, void* stream);
+/* Both forms in one signature (noise, or rng_seed and draw; at most one of the two pointers) plus the PDE-guidance term of
+ * mcedm_cond_ddim_sample_guided: et = et - gw * dx before x0 (models/ddim.py:1502-1503), dx [B, 1, H, W], gw = fl(5 * s1) formed by
+ * the caller.  dx given requires C == 1 (MCEDM_ERR_INVALID otherwise); dx NULL is the step above bit for bit and gw is not read. */
+int mcedm_op_ddim_cond_step_guided(const float* xt, const float* F, const float* Fu, const float* noise, const uint64_t* rng_seed,
+                                   uint64_t draw, const float* dx, float gw, double w, float s0, float s1, float sa_next, float c1,
+                                   float c2, float* xt_next, float* condp, float* condp_u, int cond_channels, int plan_cond_channels,
+                                   int B, int C, int H, int W, float* xs, int T_xs, int t_xs, float* x0s, int T_x0, int t_x0,
+                                   void* stream);
 /* Test hook: force the conv tile (channel tile mt in {32,64,128}, pixel tile ph x pw in {8x32,8x16,16x16,8x8};
  * (128,16,32) = the 8-wave kernel, 3x3 only);
  * (0,0,0) restores the size heuristic.  Process-global, not thread-safe. */
@@ -785,6 +819,20 @@ int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const void* packed,
 int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
                                     const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last,
                                     void* workspace, size_t workspace_bytes, int B, void* stream);
+/* mcedm_vp_heun_sample_guided and mcedm_cond_ddim_sample_guided on the DDPM U-Net with the head (guide_dx=True of
+ * PlCondDdim.sample_edm, models/ddim.py:1576-1578, 1589-1590, and of PlCondDdim.sample, :1499-1503; dx from get_dx_pde
+ * :1424-1450): the same description, checks, gd == NULL case and noise forms; h is plane 0 of cond, the guided workspaces are the
+ * unguided ones plus the gradient and the Darcy scratch.  H = W = the plan's resolution. */
+int mcedm_ddpm_vp_guided_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes);
+int mcedm_ddpm_vp_heun_sample_guided(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                     const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                     const double* step_noise, const uint64_t* rng_seed, double* out, int return_last,
+                                     void* workspace, size_t workspace_bytes, int B, void* stream);
+int mcedm_ddpm_cond_ddim_guided_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes);
+int mcedm_ddpm_cond_ddim_sample_guided(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                       const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                       const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
+                                       int return_last, void* workspace, size_t workspace_bytes, int B, void* stream);
 
 /* ---- the single-task EDM model on a cat_cond plan (PlCondEdm on Model, models/ddim.py:1608-1773) ------------------------
  * mcedm_ddpm_forward_cat: Model.forward(x, t, cond) with cond [B, cond_channels, R, R] concatenated in front of the state by

@@ -1315,33 +1315,41 @@ static int cond_sampler_check(const char* who, const mcedm_ddpm_plan& P, const f
   return MCEDM_OK;
 }
 
-struct DVpBufs : HeunBufs { size_t map, Fu; };
-static DVpBufs dvp_bufs(const mcedm_ddpm_plan& P, int B) {
-  DVpBufs v{heun_bufs(state_floats(P, B)), 0, 0};
+struct DVpBufs : HeunBufs { size_t map, Fu, dx, g; };
+static DVpBufs dvp_bufs_of(const mcedm_ddpm_plan& P, int B, bool pde) {
+  DVpBufs v{heun_bufs(state_floats(P, B)), 0, 0, 0, 0};
   v.map = heun_take(v, map_bytes(P, B));
   v.Fu = heun_take(v, state_floats(P, B) * 4);
+  if (pde) { v.dx = heun_take(v, state_floats(P, B) * 4); v.g = heun_take(v, state_floats(P, B) * 4); }      // PDE guidance: gradient, Darcy scratch
   return v;
 }
+static DVpBufs dvp_bufs(const mcedm_ddpm_plan& P, int B) { return dvp_bufs_of(P, B, false); }
+static DVpBufs dvp_guided_bufs(const mcedm_ddpm_plan& P, int B) { return dvp_bufs_of(P, B, true); }
 
-static int dvp_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
-                           const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
+// gd: PDE guidance, dx = get_dx_log_prob(h, D) after every get_denoised (:1576, 1589), h = plane 0 of cond
+static int dvp_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const mcedm_guidance_desc* gd,
+                           const float* cond, const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
                            int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
   MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "ddpm_vp_heun_sample: null argument");
+  MCEDM_REQUIRE(!(step_noise && rng_seed), "ddpm_vp_heun_sample: step_noise and rng_seed are both given (at most one of them)");
   MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "ddpm_vp_heun_sample: null schedule array");
   const mcedm_ddpm_plan& P = *plan;
   int rc;
   if ((rc = cond_sampler_check("ddpm_vp_heun_sample", P, cond, sp->cond_channels, B))) return rc;
+  const int R = P.desc.resolution;
+  if ((rc = guidance_check("ddpm_vp_heun_sample", gd, P.desc.in_channels, cond, sp->cond_channels, R, R))) return rc;
   if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
-  const DVpBufs vb = dvp_bufs(P, B);
+  const DVpBufs vb = dvp_bufs_of(P, B, gd != nullptr);
   DdpmNet net;
   if ((rc = ddpm_bind("ddpm_vp_heun_sample", P, packed, workspace, workspace_bytes, vb.total, B, stream, &net))) return rc;
   hipStream_t s = net.s;
-  const int R = P.desc.resolution;
   HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)R * R, sp->timesteps, return_last, out, s);
   float* map = cond ? at<float>(workspace, vb.map) : nullptr;
   if (map && (rc = launch_cond_map(P, net.pk, cond, map, B, s))) return rc;
   const bool guided = std::fabs(sp->w) >= 0.001 && map != nullptr;             // :937-942, the second evaluation without cond
   float* Fu = guided ? at<float>(workspace, vb.Fu) : nullptr;
+  float* dxg = gd ? at<float>(workspace, vb.dx) : nullptr;
+  float* gscratch = gd ? at<float>(workspace, vb.g) : nullptr;
   // get_denoised (:915-947): D = x + (-sigma) F(c_in x, c_noise, cond); cond itself is NOT scaled (cat_condition False, :932),
   // so one map serves every noise level; x_self_cond is None (get_self_cond_edm, :1603-1605)
   return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma_d, float c_noise) -> int {
@@ -1352,34 +1360,43 @@ static int dvp_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, cons
     in.coef_in = net.coef_in(); in.cond_map = map;
     if ((e = net.scale_input(c_in))) return e;
     if ((e = net.forward_cfg(in, net.F(), Fu))) return e;
-    return launch_vp_cfg_finish(h.x32, net.F(), Fu, sp->w, sigma, h.total, h.D, s);
-  });
+    if ((e = launch_vp_cfg_finish(h.x32, net.F(), Fu, sp->w, sigma, h.total, h.D, s)) || !gd) return e;
+    return guidance_dx(P.cond_channels, *gd, cond, h.D, dxg, gscratch, B, R, R, s);
+  }, dxg, gd ? (float)gd->weight : 0.f);
 }
 
-struct DCondDdimBufs { size_t xt, xtn, F, Fu, sc, map, total; };
-static DCondDdimBufs dcond_ddim_bufs(const mcedm_ddpm_plan& P, int B) {
+struct DCondDdimBufs { size_t xt, xtn, F, Fu, sc, map, total, dx, g; };
+static DCondDdimBufs dcond_ddim_bufs_of(const mcedm_ddpm_plan& P, int B, bool pde) {
   DCondDdimBufs b{};
   const size_t n = state_floats(P, B);
   b.xt = heun_take(b, n * 4); b.xtn = heun_take(b, n * 4); b.F = heun_take(b, n * 4); b.Fu = heun_take(b, n * 4);
   b.sc = heun_take(b, n * 4);
   b.map = heun_take(b, map_bytes(P, B));
+  if (pde) { b.dx = heun_take(b, n * 4); b.g = heun_take(b, n * 4); }      // PDE guidance: gradient, Darcy scratch
   return b;
 }
+static DCondDdimBufs dcond_ddim_bufs(const mcedm_ddpm_plan& P, int B) { return dcond_ddim_bufs_of(P, B, false); }
+static DCondDdimBufs dcond_ddim_guided_bufs(const mcedm_ddpm_plan& P, int B) { return dcond_ddim_bufs_of(P, B, true); }
 
-static int dcond_ddim_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
-                           const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
-                           int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
+// gd: PDE guidance, dx = get_dx_log_prob(h, xt) at every step's noisy state (:1501), h = plane 0 of cond
+static int dcond_ddim_impl(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const mcedm_guidance_desc* gd,
+                           const float* cond, const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out,
+                           float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
   MCEDM_REQUIRE(plan && packed && sp && init_noise && xs_out && x0_out && workspace, "ddpm_cond_ddim_sample: null argument");
+  MCEDM_REQUIRE(!(eta_noise && rng_seed), "ddpm_cond_ddim_sample: eta_noise and rng_seed are both given (at most one of them)");
   const mcedm_ddpm_plan& P = *plan;
   int rc;
   if ((rc = cond_sampler_check("ddpm_cond_ddim_sample", P, cond, sp->cond_channels, B))) return rc;
   MCEDM_REQUIRE(!sp->self_cond || P.desc.self_cond, "ddpm_cond_ddim_sample: self-conditioning asked of a network built without it");
+  const int R = P.desc.resolution, C = P.desc.in_channels;
+  if ((rc = guidance_check("ddpm_cond_ddim_sample", gd, C, cond, sp->cond_channels, R, R))) return rc;
   if ((rc = cond_ddim_check_schedule(sp, eta_noise, rng_seed))) return rc;
-  const DCondDdimBufs cb = dcond_ddim_bufs(P, B);
+  const DCondDdimBufs cb = dcond_ddim_bufs_of(P, B, gd != nullptr);
   DdpmNet net;
   if ((rc = ddpm_bind("ddpm_cond_ddim_sample", P, packed, workspace, workspace_bytes, cb.total, B, stream, &net))) return rc;
   hipStream_t s = net.s;
-  const int R = P.desc.resolution, C = P.desc.in_channels;
+  float* dxg = gd ? at<float>(workspace, cb.dx) : nullptr;
+  float* gscratch = gd ? at<float>(workspace, cb.g) : nullptr;
   float* map = cond ? at<float>(workspace, cb.map) : nullptr;
   if (map && (rc = launch_cond_map(P, net.pk, cond, map, B, s))) return rc;
   const bool guided = cond_ddim_guided(sp);
@@ -1391,6 +1408,8 @@ static int dcond_ddim_impl(const mcedm_ddpm_plan* plan, const void* packed, cons
     DdpmIn in{xt, t};
     in.self_cond = step > 0 ? sc : nullptr; in.cond_map = map;            // x_self_cond None in the first step: zeros
     return net.forward_cfg(in, lp.F, lp.Fu);
+  }, dxg, gd ? (float)gd->weight : 0.f, [&](const float* xt) -> int {
+    return guidance_dx(P.cond_channels, *gd, cond, xt, dxg, gscratch, B, R, R, s);
   });
 }
 }  // namespace mcedm
@@ -1402,14 +1421,27 @@ extern "C" int mcedm_ddpm_vp_heun_sample(const mcedm_ddpm_plan* plan, const void
                                          const float* cond, const float* init_noise, const double* step_noise, double* out,
                                          int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  return dvp_sample_impl(plan, packed, sp, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B, stream);
+  return dvp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B,
+                         stream);
 }
 extern "C" int mcedm_ddpm_vp_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
                                              const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
                                              int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
-  return dvp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, stream);
+  return dvp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B,
+                         stream);
+}
+extern "C" int mcedm_ddpm_vp_guided_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
+  return workspace_query("ddpm_vp_guided_workspace_bytes", plan, B, bytes, dvp_guided_bufs);
+}
+extern "C" int mcedm_ddpm_vp_heun_sample_guided(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                                const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                                const double* step_noise, const uint64_t* rng_seed, double* out, int return_last,
+                                                void* workspace, size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return dvp_sample_impl(plan, packed, sp, gd, cond, init_noise, step_noise, rng_seed, out, return_last, workspace, workspace_bytes, B,
+                         stream);
 }
 
 extern "C" int mcedm_ddpm_cond_ddim_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
@@ -1420,8 +1452,8 @@ extern "C" int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const vo
                                            float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
                                            void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  return dcond_ddim_impl(plan, packed, sp, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace, workspace_bytes,
-                         B, stream);
+  return dcond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
+                         workspace_bytes, B, stream);
 }
 extern "C" int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
                                                const float* cond, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
@@ -1429,8 +1461,19 @@ extern "C" int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, cons
                                                void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
-  return dcond_ddim_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace, workspace_bytes,
-                         B, stream);
+  return dcond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace,
+                         workspace_bytes, B, stream);
+}
+extern "C" int mcedm_ddpm_cond_ddim_guided_workspace_bytes(const mcedm_ddpm_plan* plan, int B, size_t* bytes) {
+  return workspace_query("ddpm_cond_ddim_guided_workspace_bytes", plan, B, bytes, dcond_ddim_guided_bufs);
+}
+extern "C" int mcedm_ddpm_cond_ddim_sample_guided(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                                  const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                                  const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
+                                                  int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return dcond_ddim_impl(plan, packed, sp, gd, cond, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, workspace,
+                         workspace_bytes, B, stream);
 }
 
 // ------------------------------------------------------------------------------------------

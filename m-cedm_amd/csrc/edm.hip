@@ -535,8 +535,10 @@ int launch_store_f32(const float* x, int C, size_t hw, int t, int T, size_t tota
 // takes four consecutive state elements (16-byte loads of xt / F / Fu / noise, 16-byte store of xt_next) and scatters x0
 // and xt_next to where their readers want them -- the self-conditioning channels of cond' and of its zero-cond twin
 // ([B, Cp, H, W]: the next forward's conv_in reads them there) and one slot each of the 'b t h w c' trajectories.
-__device__ __forceinline__ void ddim_cond_point(const DdimCondStep& a, float x, float f, float fu, float nz, float& x0, float& xn) {
-  const float et = a.Fu ? a.w1 * f - a.w * fu : f;                     // (w + 1) * model(cond) - w * model(None)   (:1497)
+// PDE guidance (dxg, C == 1): et = fl(et - fl(gw * dx)) in front of x0 (:1502-1503), dx at the state's own index.
+__device__ __forceinline__ void ddim_cond_point(const DdimCondStep& a, float x, float f, float fu, float nz, float dx, float& x0, float& xn) {
+  float et = a.Fu ? a.w1 * f - a.w * fu : f;                           // (w + 1) * model(cond) - w * model(None)   (:1497)
+  if (a.dxg) et = et - a.gw * dx;                                      // et - 5. * (1 - at).sqrt() * dx            (:1502-1503)
   x0 = (x - et * a.s1) / a.s0;                                         // (xt - et * (1 - at).sqrt()) / at.sqrt()   (:1505)
   xn = (a.noise || a.seed) ? (a.sa * x0 + a.c1 * nz) + a.c2 * et : a.sa * x0 + a.c2 * et;        // (:1512 / :1515)
 }
@@ -562,11 +564,12 @@ __global__ __launch_bounds__(256) void ddim_cond_step_kernel(DdimCondStep a, siz
     const float4 x = reinterpret_cast<const float4*>(a.xt)[g], f = reinterpret_cast<const float4*>(a.F)[g];
     const float4 fu = a.Fu ? reinterpret_cast<const float4*>(a.Fu)[g] : zero4;
     const float4 nz = a.seed ? uniform_group(seed, a.draw, g) : a.noise ? reinterpret_cast<const float4*>(a.noise)[g] : zero4;
+    const float4 dx = a.dxg ? reinterpret_cast<const float4*>(a.dxg)[g] : zero4;      // C == 1: the state's own index
     float4 x0, xn;
-    ddim_cond_point(a, x.x, f.x, fu.x, nz.x, x0.x, xn.x);
-    ddim_cond_point(a, x.y, f.y, fu.y, nz.y, x0.y, xn.y);
-    ddim_cond_point(a, x.z, f.z, fu.z, nz.z, x0.z, xn.z);
-    ddim_cond_point(a, x.w, f.w, fu.w, nz.w, x0.w, xn.w);
+    ddim_cond_point(a, x.x, f.x, fu.x, nz.x, dx.x, x0.x, xn.x);
+    ddim_cond_point(a, x.y, f.y, fu.y, nz.y, dx.y, x0.y, xn.y);
+    ddim_cond_point(a, x.z, f.z, fu.z, nz.z, dx.z, x0.z, xn.z);
+    ddim_cond_point(a, x.w, f.w, fu.w, nz.w, dx.w, x0.w, xn.w);
     reinterpret_cast<float4*>(a.xt_next)[g] = xn;
     const size_t i = 4 * g;
     // H * W % 4 == 0: the four elements share (b, c) and every destination offset is a multiple of four
@@ -596,14 +599,14 @@ __global__ __launch_bounds__(256) void ddim_cond_step_kernel(DdimCondStep a, siz
   for (size_t i = 4 * n4 + tid; i < a.n; i += stride) {                // scalar tail (everything, when a pointer is not 16-byte aligned)
     float x0, xn;
     const float nz = a.seed ? uniform_element(seed, a.draw, i) : a.noise ? a.noise[i] : 0.f;
-    ddim_cond_point(a, a.xt[i], a.F[i], a.Fu ? a.Fu[i] : 0.f, nz, x0, xn);
+    ddim_cond_point(a, a.xt[i], a.F[i], a.Fu ? a.Fu[i] : 0.f, nz, a.dxg ? a.dxg[i] : 0.f, x0, xn);
     a.xt_next[i] = xn;
     ddim_cond_scatter(a, i, x0, xn);
   }
 }
 int launch_ddim_cond_step(const DdimCondStep& a, hipStream_t s) {
   auto al16 = [](const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; };
-  const bool body = al16(a.xt) && al16(a.F) && al16(a.Fu) && al16(a.noise) && al16(a.xt_next);
+  const bool body = al16(a.xt) && al16(a.F) && al16(a.Fu) && al16(a.noise) && al16(a.dxg) && al16(a.xt_next);
   const size_t n4 = body ? a.n / 4 : 0;
   const int vec_sc = a.hw % 4 == 0 && al16(a.sc) && al16(a.sc_u);
   const int vec_tr = a.hw % 4 == 0 && a.C == 1 && al16(a.xs) && al16(a.x0s);

@@ -118,11 +118,14 @@ static inline std::vector<int> ddim_timestep_seq(int n, int N, int skip_type) {
 //   et = w1 * F - w * Fu (Fu != NULL) or F;  x0 = (xt - et * s1) / s0;  xt_next = sa * x0 [+ c1 * noise] + c2 * et   (:1497-1515)
 // in one pass that also puts x0 and xt_next where they are read next.  Every pointer but xt, F and xt_next may be NULL.
 // seed != NULL (then noise is NULL): the kernel generates `noise` itself, draw `draw` of launch_uniform_fill keyed by *seed.
+// dxg != NULL (C == 1): PDE guidance, et = et - gw * dxg before x0 (:1501-1503), gw = fl(5 * s1) formed by the caller.
 struct DdimCondStep {
   const float *xt, *F, *Fu, *noise;        // [B, C, H, W]
   const unsigned long long* seed;          // device memory, read when the kernel runs
   unsigned long long draw;
   float w1, w, s0, s1, sa, c1, c2;
+  const float* dxg;                        // [B, 1, H, W] get_dx_log_prob(h, xt), or NULL
+  float gw;
   float* xt_next;                          // [B, C, H, W]
   float *sc, *sc_u;                        // [B, Cp, H, W] cond' and its zero-cond twin: x0 -> channels [sc_off, sc_off + C)
   int C, Cp, sc_off;

@@ -172,10 +172,14 @@ struct CondDdimLoop {
   float *xt, *xtn, *F, *Fu;            // Fu null = no guidance pass
   float *sc, *sc_u; int Cp, sc_off;
 };
-// net(xt, t, step) runs the network on xt under the label t into b.F (and, guided, without cond into b.Fu)
-template <class Net>
+// net(xt, t, step) runs the network on xt under the label t into b.F (and, guided, without cond into b.Fu).
+// dxg / wgt / pde: the PDE-guidance term, et -= fl(wgt * sqrt(1 - a_t)) * dxg (:1501-1503); pde(xt) leaves
+// get_dx_log_prob(h, xt) of the CURRENT NOISY state in dxg.  xt of a step is known before its network runs, so the
+// guidance launches go in front of the network's and the step kernel reads dxg.
+template <class Net, class Pde>
 static inline int cond_ddim_loop(const mcedm_cond_ddim_desc* sp, const CondDdimLoop& b, const float* init_noise, const float* eta_noise,
-                                 const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last, hipStream_t s, Net&& net) {
+                                 const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last, hipStream_t s, Net&& net,
+                                 const float* dxg, float wgt, Pde&& pde) {
   int rc;
   const std::vector<int> seq = ddim_timestep_seq(sp->num_diffusion_timesteps, sp->timesteps, sp->skip_type);   // walked from its end, seq_next = [-1] + seq[:-1]
   const int S = (int)seq.size();
@@ -187,15 +191,18 @@ static inline int cond_ddim_loop(const mcedm_cond_ddim_desc* sp, const CondDdimL
   k.sc = b.sc; k.sc_u = b.sc_u;
   k.C = b.C; k.Cp = b.Cp; k.sc_off = b.sc_off; k.hw = b.hw; k.n = b.total;
   k.T_xs = return_last ? 1 : S + 1; k.T_x0 = return_last ? 1 : S;
+  k.dxg = dxg;
   const float* xt = init_noise;
   float* bufs[2] = {b.xtn, b.xt};
   auto alpha = [&](int t) -> float { return sp->alphas_cumprod_ext[t + 1]; };      // compute_alpha(t): index t + 1 (:700-704)
   for (int step = 0; step < S; ++step) {
     const int i = seq[S - 1 - step], j = (S - 1 - step) > 0 ? seq[S - 2 - step] : -1;
     const float a_t = alpha(i), at_next = alpha(j);
+    if (dxg && (rc = pde(xt))) return rc;
     if ((rc = net(xt, (float)i, step))) return rc;
     k.xt = xt; k.xt_next = bufs[step & 1];
     k.s0 = sqrtf(a_t); k.s1 = sqrtf(1.0f - a_t); k.sa = sqrtf(at_next);
+    k.gw = dxg ? wgt * k.s1 : 0.f;                                        // 5. * (1 - at).sqrt(), fp32 (:1502)
     const DdimNoiseCoefs nc = ddim_noise_coefs(stochastic, sp->eta, a_t, at_next);
     k.c1 = nc.c1; k.c2 = nc.c2;
     if (stochastic) {
@@ -210,6 +217,26 @@ static inline int cond_ddim_loop(const mcedm_cond_ddim_desc* sp, const CondDdimL
     if ((rc = launch_ddim_cond_step(k, s))) return rc;
     xt = k.xt_next;
   }
+  return MCEDM_OK;
+}
+template <class Net>
+static inline int cond_ddim_loop(const mcedm_cond_ddim_desc* sp, const CondDdimLoop& b, const float* init_noise, const float* eta_noise,
+                                 const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last, hipStream_t s, Net&& net) {
+  return cond_ddim_loop(sp, b, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, s, net, nullptr, 0.f,
+                        [](const float*) { return (int)MCEDM_OK; });
+}
+
+// What every guided entry of the single-task samplers checks before any launch (with guidance_dx's Darcy grid check)
+static inline int guidance_check(const char* who, const mcedm_guidance_desc* gd, int in_channels, const float* cond, int cond_channels,
+                                 int H, int W) {
+  if (!gd) return MCEDM_OK;
+  MCEDM_REQUIRE(gd->system == 1 || gd->system == 2, "%s: gd->system %d: guidance system must be 1 (SWE) or 2 (Darcy)", who, gd->system);
+  MCEDM_REQUIRE(in_channels == 1, "%s: gd given to a plan with in_channels %d: PDE guidance is defined for the single-task sampler "
+                "(state u, conditioning h in cond[:, 0]), models/ddim.py:1424-1450", who, in_channels);
+  MCEDM_REQUIRE(cond != nullptr && cond_channels >= 1, "%s: gd needs cond (h in cond[:, 0]) and sp->cond_channels >= 1 (got cond %s, "
+                "cond_channels %d)", who, cond ? "given" : "NULL", cond_channels);
+  MCEDM_REQUIRE(gd->system == 1 || (H == W && H > 4), "%s: gd: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)",
+                who, H, W);
   return MCEDM_OK;
 }
 

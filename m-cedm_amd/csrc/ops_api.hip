@@ -430,8 +430,11 @@ extern "C" int mcedm_op_set_conv_debug(unsigned long long* buf) {
 static int op_ddim_cond_step(const float* xt, const float* F, const float* Fu, const float* noise, const uint64_t* rng_seed,
                              uint64_t draw, double w, float s0, float s1, float sa_next, float c1, float c2, float* xt_next,
                              float* condp, float* condp_u, int cond_channels, int plan_cond_channels, int B, int C, int H, int W,
-                             float* xs, int T_xs, int t_xs, float* x0s, int T_x0, int t_x0, void* stream) {
+                             float* xs, int T_xs, int t_xs, float* x0s, int T_x0, int t_x0, void* stream, const float* dx = nullptr,
+                             float gw = 0.f) {
   MCEDM_REQUIRE(xt && F && xt_next, "op_ddim_cond_step: null pointer");
+  MCEDM_REQUIRE(!(noise && rng_seed), "op_ddim_cond_step: noise and rng_seed are both given (at most one of them)");
+  MCEDM_REQUIRE(!dx || C == 1, "op_ddim_cond_step: dx [B, 1, H, W] goes with C == 1 (got C = %d)", C);
   MCEDM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "op_ddim_cond_step: empty shape");
   MCEDM_REQUIRE(!condp_u || condp, "op_ddim_cond_step: the twin goes with cond'");
   MCEDM_REQUIRE(!condp || (cond_channels >= 0 && cond_channels + C <= plan_cond_channels),
@@ -444,6 +447,7 @@ static int op_ddim_cond_step(const float* xt, const float* F, const float* Fu, c
   k.xt_next = xt_next; k.sc = condp; k.sc_u = condp_u;
   k.C = C; k.Cp = plan_cond_channels; k.sc_off = cond_channels; k.hw = (size_t)H * W; k.n = (size_t)B * C * k.hw;
   k.xs = xs; k.x0s = x0s; k.T_xs = T_xs; k.t_xs = t_xs; k.T_x0 = T_x0; k.t_x0 = t_x0;
+  k.dxg = dx; k.gw = dx ? gw : 0.f;
   return launch_ddim_cond_step(k, (hipStream_t)stream);
 }
 extern "C" int mcedm_op_ddim_cond_step(const float* xt, const float* F, const float* Fu, const float* noise, double w, float s0,
@@ -462,4 +466,13 @@ extern "C" int mcedm_op_ddim_cond_step_rng(const float* xt, const float* F, cons
   MCEDM_REQUIRE(rng_seed != nullptr, "op_ddim_cond_step_rng: rng_seed (a 64-bit seed in device memory) is null");
   return op_ddim_cond_step(xt, F, Fu, nullptr, rng_seed, draw, w, s0, s1, sa_next, c1, c2, xt_next, condp, condp_u, cond_channels,
                            plan_cond_channels, B, C, H, W, xs, T_xs, t_xs, x0s, T_x0, t_x0, stream);
+}
+// both forms in one signature, with the PDE-guidance term et -= gw * dx (dx [B, 1, H, W], C == 1; NULL: the step above)
+extern "C" int mcedm_op_ddim_cond_step_guided(const float* xt, const float* F, const float* Fu, const float* noise,
+                                              const uint64_t* rng_seed, uint64_t draw, const float* dx, float gw, double w, float s0,
+                                              float s1, float sa_next, float c1, float c2, float* xt_next, float* condp, float* condp_u,
+                                              int cond_channels, int plan_cond_channels, int B, int C, int H, int W, float* xs,
+                                              int T_xs, int t_xs, float* x0s, int T_x0, int t_x0, void* stream) {
+  return op_ddim_cond_step(xt, F, Fu, noise, rng_seed, draw, w, s0, s1, sa_next, c1, c2, xt_next, condp, condp_u, cond_channels,
+                           plan_cond_channels, B, C, H, W, xs, T_xs, t_xs, x0s, T_x0, t_x0, stream, dx, gw);
 }

@@ -194,11 +194,13 @@ extern "C" int mcedm_heun_sample_dxcond_rng(const mcedm_plan* plan, const void* 
 // VP-preconditioned Heun sampler of an epsilon network (PlCondDdim.sample_edm, models/ddim.py:1532-1601)
 // ------------------------------------------------------------------------------------------
 namespace mcedm {
-struct VpBufs : HeunBufs { size_t condp; };
-static VpBufs vp_bufs(const mcedm_plan& P, int B, int H, int W) {
-  VpBufs v{heun_bufs((size_t)B * P.desc.in_channels * H * W), 0};
+struct VpBufs : HeunBufs { size_t condp, dx, g; };
+static VpBufs vp_bufs(const mcedm_plan& P, int B, int H, int W, bool pde = false) {
+  const size_t n = (size_t)B * P.desc.in_channels * H * W;
+  VpBufs v{heun_bufs(n), 0, 0, 0};
   // cond' = cat(cond, zeros) of a self-conditioning plan
   v.condp = heun_take(v, (size_t)B * P.desc.cond_channels * H * W * 4);
+  if (pde) { v.dx = heun_take(v, n * 4); v.g = heun_take(v, n * 4); }      // PDE guidance: gradient, Darcy scratch
   return v;
 }
 
@@ -223,10 +225,12 @@ extern "C" int mcedm_vp_sampler_workspace_bytes(const mcedm_plan* plan, int B, i
   return rc;
 }
 
-static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
-                          const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
+// gd: PDE guidance, dx = get_dx_log_prob(h, D) after every get_denoised (:1576, 1589), h = plane 0 of the caller's cond
+static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const mcedm_guidance_desc* gd,
+                          const float* cond, const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
                           int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
   MCEDM_REQUIRE(plan && packed && sp && init_noise && out && workspace, "vp_heun_sample: null argument");
+  MCEDM_REQUIRE(!(step_noise && rng_seed), "vp_heun_sample: step_noise and rng_seed are both given (at most one of them)");
   MCEDM_REQUIRE(sp->t_steps && sp->t_hat && sp->c_noise, "vp_heun_sample: null schedule array");
   const mcedm_plan& P = *plan;
   int rc;
@@ -235,9 +239,10 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
   MCEDM_REQUIRE(sp->cond_channels >= 0 && sp->cond_channels <= P.desc.cond_channels,
                 "vp_heun_sample: cond_channels %d outside [0, %d]", sp->cond_channels, P.desc.cond_channels);
   MCEDM_REQUIRE(cond == nullptr || sp->cond_channels > 0, "vp_heun_sample: cond given with cond_channels 0");
+  if ((rc = guidance_check("vp_heun_sample", gd, P.desc.in_channels, cond, sp->cond_channels, H, W))) return rc;
   if ((rc = vp_check_schedule(sp, step_noise, rng_seed))) return rc;
   const int N = sp->timesteps;
-  const VpBufs vb = vp_bufs(P, B, H, W);
+  const VpBufs vb = vp_bufs(P, B, H, W, gd != nullptr);
   AdmNet net;
   if ((rc = adm_bind("vp_heun_sample", P, packed, workspace, workspace_bytes, vb.total, no_extra, B, H, W, 0, 1, stream, &net))) return rc;
   HeunState h = heun_state(workspace, vb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, net.s);
@@ -249,17 +254,22 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
                                   P.desc.cond_channels - sp->cond_channels, B, H, W, st, stream))) return rc;
     condp = st;
   }
-  return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma, float c_noise) {
-    return vp_denoise(net, h.x32, condp, sigma, c_noise, sp->w, h.D);
-  });
+  float* dxg = gd ? at<float>(workspace, vb.dx) : nullptr;
+  float* gscratch = gd ? at<float>(workspace, vb.g) : nullptr;
+  // the guidance reads the caller's cond [B, sp->cond_channels, H, W], not cond'
+  return vp_heun_loop(h, sp, init_noise, step_noise, rng_seed, [&](double sigma, float c_noise) -> int {
+    int e = vp_denoise(net, h.x32, condp, sigma, c_noise, sp->w, h.D);
+    if (e || !gd) return e;
+    return guidance_dx(sp->cond_channels, *gd, cond, h.D, dxg, gscratch, B, H, W, net.s);
+  }, dxg, gd ? (float)gd->weight : 0.f);
 }
 
 extern "C" int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
                                     const float* init_noise, const double* step_noise, double* out, int return_last,
                                     void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  return vp_sample_impl(plan, packed, sp, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B, H,
-                        W, stream);
+  return vp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes,
+                        B, H, W, stream);
 }
 
 extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
@@ -268,8 +278,26 @@ extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* pack
                                         void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(rng_seed != nullptr, "vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
-  return vp_sample_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B, H,
-                        W, stream);
+  return vp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes,
+                        B, H, W, stream);
+}
+
+extern "C" int mcedm_vp_guided_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "vp_guided_workspace_bytes: null argument");
+  AdmNet net;                            // one noise label for the whole batch, as the sampler lays its forward out: exact
+  const int rc = adm_sizes(*plan, B, H, W, 0, 1, &net, bytes);
+  if (rc == MCEDM_OK) *bytes += vp_bufs(*plan, B, H, W, true).total;
+  return rc;
+}
+
+extern "C" int mcedm_vp_heun_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                           const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                           const double* step_noise, const uint64_t* rng_seed, double* out, int return_last,
+                                           void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return vp_sample_impl(plan, packed, sp, gd, cond, init_noise, step_noise, rng_seed, out, return_last, workspace, workspace_bytes, B,
+                        H, W, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -277,14 +305,15 @@ extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* pack
 // ------------------------------------------------------------------------------------------
 namespace mcedm {
 // the sampler's own buffers in front of the network's workspace, each 256-byte aligned
-struct CondDdimBufs { size_t xt, xtn, F, Fu, condp, condu, total; };
-static CondDdimBufs cond_ddim_bufs(const mcedm_plan& P, int B, int H, int W) {
+struct CondDdimBufs { size_t xt, xtn, F, Fu, condp, condu, total, dx, g; };
+static CondDdimBufs cond_ddim_bufs(const mcedm_plan& P, int B, int H, int W, bool pde = false) {
   CondDdimBufs b{};
   const size_t hw = (size_t)H * W, n = (size_t)B * P.desc.in_channels * hw;
   b.xt = heun_take(b, n * 4); b.xtn = heun_take(b, n * 4);
   b.F = heun_take(b, (size_t)B * P.desc.out_channels * hw * 4); b.Fu = heun_take(b, (size_t)B * P.desc.out_channels * hw * 4);
   // cond' = cat(cond, x0_t) and cat(0, x0_t), what the unconditional pass reads
   b.condp = heun_take(b, (size_t)B * P.desc.cond_channels * hw * 4); b.condu = heun_take(b, (size_t)B * P.desc.cond_channels * hw * 4);
+  if (pde) { b.dx = heun_take(b, n * 4); b.g = heun_take(b, n * 4); }      // PDE guidance: gradient, Darcy scratch
   return b;
 }
 }  // namespace mcedm
@@ -299,10 +328,12 @@ extern "C" int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, in
 }
 
 // eta_noise / rng_seed: the uniform draws of the stochastic steps, read from slice k or generated in the step kernel as draw k
-static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
-                          const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
-                          int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+// gd: PDE guidance, dx = get_dx_log_prob(h, xt) at every step's noisy state (:1501), h = plane 0 of the caller's cond
+static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const mcedm_guidance_desc* gd,
+                          const float* cond, const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out,
+                          float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
   MCEDM_REQUIRE(plan && packed && sp && init_noise && xs_out && x0_out && workspace, "cond_ddim_sample: null argument");
+  MCEDM_REQUIRE(!(eta_noise && rng_seed), "cond_ddim_sample: eta_noise and rng_seed are both given (at most one of them)");
   const mcedm_plan& P = *plan;
   int rc;
   MCEDM_REQUIRE(P.desc.in_channels == P.desc.out_channels, "cond_ddim_sample: in_channels != out_channels");
@@ -313,9 +344,10 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
   MCEDM_REQUIRE(!sp->self_cond || cc + C <= Cp,
                 "cond_ddim_sample: self-conditioning asked of a plan whose conditioning input is not widened (%d + %d > %d channels)",
                 cc, C, Cp);
+  if ((rc = guidance_check("cond_ddim_sample", gd, C, cond, cc, H, W))) return rc;
   if ((rc = cond_ddim_check_schedule(sp, eta_noise, rng_seed))) return rc;
   const bool guided = cond_ddim_guided(sp);
-  const CondDdimBufs cb = cond_ddim_bufs(P, B, H, W);
+  const CondDdimBufs cb = cond_ddim_bufs(P, B, H, W, gd != nullptr);
   AdmNet net;
   if ((rc = adm_bind("cond_ddim_sample", P, packed, workspace, workspace_bytes, cb.total, no_extra, B, H, W, 0, 1, stream, &net))) return rc;
   const size_t hw = (size_t)H * W, total = (size_t)B * C * hw;
@@ -330,6 +362,8 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
     return rc;
   CondDdimLoop lp{C, hw, total, at<float>(workspace, cb.xt), at<float>(workspace, cb.xtn), at<float>(workspace, cb.F),
                   guided ? at<float>(workspace, cb.Fu) : nullptr, sp->self_cond ? condp : nullptr, sp->self_cond ? condu : nullptr, Cp, cc};
+  float* dxg = gd ? at<float>(workspace, cb.dx) : nullptr;
+  float* gscratch = gd ? at<float>(workspace, cb.g) : nullptr;
   // the network sees xt itself (no c_in on this path: conv_in rows scaled by 1) under the label t
   return cond_ddim_loop(sp, lp, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, s, [&](const float* xt, float t, int) -> int {
     int e;
@@ -338,6 +372,8 @@ static int cond_ddim_impl(const mcedm_plan* plan, const void* packed, const mced
     if ((e = net.forward(in, lp.F)) || !guided) return e;
     in.cond = condu;                  // (not forward_cfg: the twin keeps the self-conditioning channels, only cond is zeros)
     return net.forward(in, lp.Fu);
+  }, dxg, gd ? (float)gd->weight : 0.f, [&](const float* xt) -> int {
+    return guidance_dx(cc, *gd, cond, xt, dxg, gscratch, B, H, W, s);      // the caller's cond [B, cc, H, W], not cond'
   });
 }
 
@@ -346,7 +382,7 @@ extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed
                                       int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
                                       void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
-  return cond_ddim_impl(plan, packed, sp, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
+  return cond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
                         workspace_bytes, B, H, W, stream);
 }
 
@@ -356,6 +392,25 @@ extern "C" int mcedm_cond_ddim_sample_rng(const mcedm_plan* plan, const void* pa
                                           int W, void* stream) {
   VariantScope variant_scope__(plan ? &plan->variants : nullptr);
   MCEDM_REQUIRE(rng_seed != nullptr, "cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
-  return cond_ddim_impl(plan, packed, sp, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace,
+  return cond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace,
+                        workspace_bytes, B, H, W, stream);
+}
+
+extern "C" int mcedm_cond_ddim_guided_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  MCEDM_REQUIRE(plan && bytes, "cond_ddim_guided_workspace_bytes: null argument");
+  AdmNet net;
+  const int rc = adm_sizes(*plan, B, H, W, 0, 1, &net, bytes);
+  if (rc == MCEDM_OK) *bytes += cond_ddim_bufs(*plan, B, H, W, true).total;
+  return rc;
+}
+
+extern "C" int mcedm_cond_ddim_sample_guided(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                             const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
+                                             const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
+                                             int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                             void* stream) {
+  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  return cond_ddim_impl(plan, packed, sp, gd, cond, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, workspace,
                         workspace_bytes, B, H, W, stream);
 }

@@ -860,8 +860,10 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     Constructor, buffers (``betas``, ``logvar``), state_dict keys and method signatures follow the reference.  The training
     step runs in the HIP library: noising (mcedm_eps_noise_inputs), the self-conditioning pre-pass and its estimate written into
     the network's widened conditioning input (mcedm_eps_self_cond), forward, loss (mcedm_eps_loss) and backward from dF
-    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The PDE loss term, ``guide_dx`` and ``dx_cond`` raise.
-    ``sample`` (the DDIM loop, :1452-1530) is mcedm_cond_ddim_sample[_rng].
+    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The PDE loss term and ``dx_cond`` raise.
+    ``sample`` (the DDIM loop, :1452-1530) is mcedm_cond_ddim_sample[_rng].  ``guide_dx=True`` (PDE guidance, :1499-1503 and
+    :1576-1590) runs in both samplers on both networks (mcedm_[ddpm_]cond_ddim_sample_guided, mcedm_[ddpm_]vp_heun_sample_guided) for
+    scalar gauss-normalised fields with h given on the device; every other form of it raises.
 
     With a ``name`` that does not start with ``adm`` the network is the DDPM U-Net ``Model`` (:43-46;
     configs/model/ddim_cond_h_res32.yaml: ``name: ddim_cond_h``, ``cat_cond: False``, ``self_cond: True``) with its cond_enc head,
@@ -1020,14 +1022,27 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             D = xt + (-c_in.new_tensor(s32).to(xt.device)) * F
         return D, F
 
+    def _guidance(self, h, guide_dx):
+        """The residual description of guide_dx=True (None without it), as PlCondEdm.sample_edm builds it; h 'b h w c'."""
+        if not guide_dx:
+            return None
+        if h is None or not getattr(h, "is_cuda", False):
+            raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1501-1503, 1576-1590) needs the conditioning field h on "
+                                      "the device: guidance without it, or off the device, is not built")
+        if self.pde_loss is None or not hasattr(self.pde_loss, "guidance_desc"):
+            raise NotImplementedError("guide_dx needs set_pde_loss_function('swe' | 'swe_per' | 'darcy')")
+        if self.rescaled or self.normalization == "min_max" or self.h_ch != 1 or self.u_ch != 1:
+            raise NotImplementedError("guide_dx is built for scalar gauss-normalised fields h, u")
+        return self.pde_loss.guidance_desc(self.normalizer_input, self.normalizer_target, h.shape[1], h.shape[2])
+
     def sample_edm(self, h, u_noise, sparams, return_last=True, guide_dx=False):
         """models/ddim.py:1532-1601; h, u_noise in the reference's 'b h w c' layout; returns [b, t, h, w, c] float64.  The
         schedule is rounded on the host (round_sigma, :1553, 1566); the loop runs in mcedm_vp_heun_sample_rng, whose churn kernel
         generates the per-step randn_like(x_cur) of :1567 from a seed drawn from torch's CPU generator (``noise_source =
         "device"``), or in mcedm_vp_heun_sample fed one torch.randn([N, B, C, H, W], float64) (``"torch"``).  Either way the call
-        replays from one HIP graph."""
-        if guide_dx:
-            raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1577-1579) is not built for PlCondDdim")
+        replays from one HIP graph.  guide_dx=True: after every denoiser call d -= 5 * dx / t_hat with dx the PDE-residual gradient
+        at the denoised state (:1576-1578, 1589-1590), evaluated on the device (mcedm_[ddpm_]vp_heun_sample_guided)."""
+        guidance = self._guidance(h, guide_dx)
         noise_source = self._noise_mode()
         if self.edm_steps is None:
             self.set_test_sampler_params(sparams)
@@ -1047,13 +1062,17 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         with torch.no_grad():
             packed = net.packed_weights()
             eager = lambda c, i, sn, seed=None: net.plan.vp_sample(      # noqa: E731
-                packed, vd, c, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device))
+                packed, vd, c, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device),
+                guidance=guidance)
+            # the residual description of guide_dx is a host-side struct: part of the key and of the capture
             B, _, H, W = init.shape
             key = ("vp", B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), init.device.index, N, net.cond_channels,
-                   tuple(t_steps.tolist()), tuple(t_hat), tuple(c_noise), float(sparams.S_noise), float(sparams.w))
+                   tuple(t_steps.tolist()), tuple(t_hat), tuple(c_noise), float(sparams.S_noise), float(sparams.w),
+                   None if guidance is None else _lib.desc_key(guidance))
             return self._replay(key, lambda: _lib.GraphedVpSampler(net.plan, packed, vd, B, H, W, cond is not None, churn,
                                                                    return_last=return_last, ws=self._sample_ws,
-                                                                   device_noise=dev_noise), eager, cond, init, step_noise, **kw)
+                                                                   device_noise=dev_noise, guidance=guidance),
+                                eager, cond, init, step_noise, **kw)
 
     def sample(self, *a, **k):
         """``sample(h, u_noise, sparams, return_last=True, guide_dx=False)`` of models/ddim.py:1452-1530 (the open signature is the
@@ -1066,9 +1085,10 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         per step one network pass (two with classifier-free guidance, |w| >= 0.001) and one fused kernel that also feeds the
         x0 prediction back as the next step's x_self_cond.  With eta != 0 the per-step torch.rand_like(x) of :1512 (a UNIFORM
         draw) is generated inside that kernel from a seed drawn from torch's CPU generator (``noise_source = "device"``), or made
-        up front as one torch.rand([S, B, C, H, W]) (``"torch"``)."""
-        if guide_dx:
-            raise NotImplementedError("guide_dx (PDE guidance, models/ddim.py:1501-1503) is not built for PlCondDdim")
+        up front as one torch.rand([S, B, C, H, W]) (``"torch"``).  guide_dx=True: et -= 5 * sqrt(1 - at) * dx with dx the
+        PDE-residual gradient at each step's noisy state xt (:1501-1503), evaluated on the device in front of the step's network
+        passes (mcedm_[ddpm_]cond_ddim_sample_guided)."""
+        guidance = self._guidance(h, guide_dx)
         if h is None:
             raise NotImplementedError("sampling without the conditioning field h (models/ddim.py:1452-1531 hands cond=h to the "
                                       "network in every step) is not built")
@@ -1087,11 +1107,12 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         with torch.no_grad():
             packed = net.packed_weights()
             eager = lambda c, i, en, seed=None: net.plan.cond_ddim_sample(      # noqa: E731
-                packed, dd, c, i, en, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device))
+                packed, dd, c, i, en, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device),
+                guidance=guidance)
             # the evaluation loops repeat the call: it replays from one HIP graph, like sample_edm of the sibling modules
             B, _, H, W = init.shape
             key = ("ddim", B, H, W, bool(return_last), stochastic, dev_noise, packed.data_ptr(), init.device.index, _table_key(ae),
-                   _lib.desc_key(dd, skip=("alphas_cumprod_ext",)))
+                   _lib.desc_key(dd, skip=("alphas_cumprod_ext",)), None if guidance is None else _lib.desc_key(guidance))
             return self._replay(key, lambda: _lib.GraphedCondDdim(net.plan, packed, dd, B, H, W, stochastic, return_last=return_last,
-                                                                  ws=self._sample_ws, device_noise=dev_noise),
+                                                                  ws=self._sample_ws, device_noise=dev_noise, guidance=guidance),
                                 eager, cond, init, eta_noise, **kw)

@@ -45,6 +45,9 @@ EXPORTS = [
     "mcedm_swe_fv_unroll",
     "mcedm_ddpm_temb_row_count", "mcedm_ddpm_temb_rows", "mcedm_ddpm_workspace_bytes_t", "mcedm_ddpm_forward_t",
     "mcedm_ddpm_edm_denoise_t",
+    "mcedm_vp_guided_workspace_bytes", "mcedm_vp_heun_sample_guided", "mcedm_cond_ddim_guided_workspace_bytes",
+    "mcedm_cond_ddim_sample_guided", "mcedm_ddpm_vp_guided_workspace_bytes", "mcedm_ddpm_vp_heun_sample_guided",
+    "mcedm_ddpm_cond_ddim_guided_workspace_bytes", "mcedm_ddpm_cond_ddim_sample_guided",
 ]
 # The sampler entries _PlanBase._sample_call drives, with the number of materialised-noise pointers each takes; every one
 # has a "_rng" twin that takes ONE seed pointer in their place.  A new sampler is a row here and a method that names it.
@@ -52,6 +55,12 @@ SAMPLER_STEMS = {
     "mcedm_heun_sample": 1, "mcedm_heun_sample_guided": 1, "mcedm_heun_sample_dxcond": 1,
     "mcedm_vp_heun_sample": 1, "mcedm_ddpm_vp_heun_sample": 1, "mcedm_cond_ddim_sample": 1, "mcedm_ddpm_cond_ddim_sample": 1,
     "mcedm_ddim_repaint_sample": 1, "mcedm_repaint_sample": 2, "mcedm_ddpm_edm_heun_sample": 1,
+}
+# The PDE-guided (guide_dx) entries of the single-task samplers take the materialised draws AND the seed pointer in one signature
+# (at most one of them non-NULL) behind a mcedm_guidance_desc*, and have no "_rng" twin: unguided stem -> guided entry.
+GUIDED_ENTRIES = {
+    "mcedm_vp_heun_sample": "mcedm_vp_heun_sample_guided", "mcedm_ddpm_vp_heun_sample": "mcedm_ddpm_vp_heun_sample_guided",
+    "mcedm_cond_ddim_sample": "mcedm_cond_ddim_sample_guided", "mcedm_ddpm_cond_ddim_sample": "mcedm_ddpm_cond_ddim_sample_guided",
 }
 # kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
 GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
@@ -242,6 +251,19 @@ def load() -> C.CDLL:
     lib.mcedm_ddpm_cond_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
     lib.mcedm_ddpm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
     lib.mcedm_ddpm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32, vp]
+    gdp = C.POINTER(GuidanceDesc)
+    lib.mcedm_vp_guided_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.mcedm_vp_heun_sample_guided.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), gdp, f32p, f32p, f64p, vp, f64p, i32, vp, sz, i32,
+                                                i32, i32, vp]
+    lib.mcedm_cond_ddim_guided_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.mcedm_cond_ddim_sample_guided.argtypes = [vp, vp, C.POINTER(CondDdimDesc), gdp, f32p, f32p, f32p, vp, f32p, f32p, i32, vp, sz,
+                                                  i32, i32, i32, vp]
+    lib.mcedm_ddpm_vp_guided_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
+    lib.mcedm_ddpm_vp_heun_sample_guided.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), gdp, f32p, f32p, f64p, vp, f64p, i32, vp, sz,
+                                                     i32, vp]
+    lib.mcedm_ddpm_cond_ddim_guided_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
+    lib.mcedm_ddpm_cond_ddim_sample_guided.argtypes = [vp, vp, C.POINTER(CondDdimDesc), gdp, f32p, f32p, f32p, vp, f32p, f32p, i32, vp,
+                                                       sz, i32, vp]
     lib.mcedm_ddpm_forward_cat.argtypes = [vp, vp, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
     lib.mcedm_ddpm_edm_denoise.argtypes = [vp, vp, f32p, f32p, C.c_float, C.c_float, C.c_double, C.c_double, f32p, f32p, vp, sz, i32, vp]
     lib.mcedm_ddpm_edm_sampler_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
@@ -381,12 +403,15 @@ class _PlanBase:
 
     # ---- the samplers ----------------------------------------------------------------------
     def _sample_call(self, who: str, stem: str, packed, head: Sequence, noise: Sequence[tuple], rng_seed, out, shapes: List[tuple],
-                     dtype, return_last: bool, ws: Optional["Workspace"], nbytes: int, dims: tuple, device):
+                     dtype, return_last: bool, ws: Optional["Workspace"], nbytes: int, dims: tuple, device,
+                     guidance: Optional["GuidanceDesc"] = None):
         """The call every sampler method makes: ``stem(plan, packed, *head, <draws>, <outputs>, return_last, workspace, bytes,
         *dims, stream)``.  noise: (name, tensor or None, dtype, shape) of each materialised draw ``stem`` takes; with rng_seed
         (device-side draws) ``stem + "_rng"`` runs instead, the one seed pointer in their place.  shapes: of the one or two
         ``dtype`` outputs, allocated here or checked against the caller's ``out`` (a graphed call's static tensors); returns
-        the tensor, or the pair.  Every check runs before anything is enqueued."""
+        the tensor, or the pair.  guidance: ``GUIDED_ENTRIES[stem]`` runs instead, the description behind the first entry of
+        ``head`` (the sampler's) and the draws AND the seed pointer in its one signature.  Every check runs before anything is
+        enqueued."""
         buf = (ws or Workspace()).get(nbytes, device)
         single = len(shapes) == 1
         if out is None:
@@ -408,6 +433,9 @@ class _PlanBase:
             stem, draws = stem + "_rng", [_seed_ptr(rng_seed, device, who)]
         else:
             draws = [_ptr(t, dt) for _, t, dt, _ in noise]
+        if guidance is not None:
+            stem, head = GUIDED_ENTRIES[stem[:-len("_rng")] if rng_seed is not None else stem], (head[0], C.byref(guidance)) + tuple(head[1:])
+            draws = [_ptr(t, dt) for _, t, dt, _ in noise] + [_seed_ptr(rng_seed, device, who) if rng_seed is not None else None]
         check(getattr(self._lib, stem)(self._h, packed.data_ptr(), *head, *draws, *[_ptr(o, dtype) for o in outs], int(return_last),
                                        buf.data_ptr(), buf.numel(), *dims, _stream()), stem[len("mcedm_"):])
         return outs[0] if single else (outs[0], outs[1])
@@ -416,23 +444,27 @@ class _PlanBase:
     # queries, the trailing size arguments of its entries (_dims) and its input checks with the state's (H, W) (_state_hw).
     def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
                   ws: Optional["Workspace"] = None, rng_seed: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, guidance: Optional["GuidanceDesc"] = None) -> torch.Tensor:
         """mcedm_[ddpm_]vp_heun_sample (rng_seed None) / its _rng form; returns [B, 1 or N+1, H, W, in] float64 (``out``, when
-        given: a graphed call's static tensor)."""
+        given: a graphed call's static tensor).  guidance: the PDE residual whose gradient at the denoised state corrects the
+        slope (guide_dx): mcedm_[ddpm_]vp_heun_sample_guided, with the guided workspace."""
         H, W = self._state_hw(init_noise, cond, "vp_sample")
         B, N = init_noise.shape[0], vd.timesteps
         return self._sample_call("vp_sample", f"mcedm_{self._WHAT}vp_heun_sample", packed,
                                  (C.byref(vd), _ptr(cond), _ptr(init_noise)),
                                  [("step_noise", step_noise, torch.float64, (N,) + tuple(init_noise.shape))], rng_seed, out,
                                  [(B, 1 if return_last else N + 1, H, W, self.in_channels)], torch.float64, return_last, ws,
-                                 self.vp_sampler_workspace_bytes(B, H, W), self._dims(B, H, W), init_noise.device)
+                                 self.vp_sampler_workspace_bytes(B, H, W, guided=guidance is not None), self._dims(B, H, W),
+                                 init_noise.device, guidance=guidance)
 
     def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
-                         ws: Optional["Workspace"] = None, out=None, rng_seed: Optional[torch.Tensor] = None):
+                         ws: Optional["Workspace"] = None, out=None, rng_seed: Optional[torch.Tensor] = None,
+                         guidance: Optional["GuidanceDesc"] = None):
         """mcedm_[ddpm_]cond_ddim_sample (PlCondDdim.sample on the device) -> (xs, x0_preds), both fp32 'b t h w c': S + 1 and S
         slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors).  rng_seed (int64 [1]
         on the device): the uniform draws of the eta != 0 steps are generated inside the step kernel (the _rng form, step k =
-        draw k of uniform_fill) instead of being read from eta_noise [S, B, C, H, W]."""
+        draw k of uniform_fill) instead of being read from eta_noise [S, B, C, H, W].  guidance: the PDE residual whose gradient at
+        each step's noisy state corrects et (guide_dx): mcedm_[ddpm_]cond_ddim_sample_guided, with the guided workspace."""
         H, W = self._state_hw(init_noise, cond, "cond_ddim_sample")
         B, Cc = init_noise.shape[0], self.in_channels
         S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
@@ -440,8 +472,8 @@ class _PlanBase:
                                  (C.byref(dd), _ptr(cond), _ptr(init_noise)),
                                  [("eta_noise", eta_noise, torch.float32, (S,) + tuple(init_noise.shape))], rng_seed, out,
                                  [(B, 1 if return_last else S + 1, H, W, Cc), (B, 1 if return_last else S, H, W, Cc)],
-                                 torch.float32, return_last, ws, self.cond_ddim_workspace_bytes(B, H, W), self._dims(B, H, W),
-                                 init_noise.device)
+                                 torch.float32, return_last, ws, self.cond_ddim_workspace_bytes(B, H, W, guided=guidance is not None),
+                                 self._dims(B, H, W), init_noise.device, guidance=guidance)
 
 
 class Plan(_PlanBase):
@@ -569,11 +601,13 @@ class Plan(_PlanBase):
                                                      _ptr(noise_labels), noise_labels.numel(), _ptr(dF), garr, buf.data_ptr(),
                                                      buf.numel(), B, H, W, nb, firsts, evs, _stream()), "unet_backward")
 
-    def vp_sampler_workspace_bytes(self, B: int, H: int, W: int) -> int:
-        return self._bytes("mcedm_vp_sampler_workspace_bytes", "vp_sampler_workspace_bytes", B, H, W)
+    def vp_sampler_workspace_bytes(self, B: int, H: int, W: int, guided: bool = False) -> int:
+        what = "vp_guided_workspace_bytes" if guided else "vp_sampler_workspace_bytes"
+        return self._bytes("mcedm_" + what, what, B, H, W)
 
-    def cond_ddim_workspace_bytes(self, B: int, H: int, W: int) -> int:
-        return self._bytes("mcedm_cond_ddim_workspace_bytes", "cond_ddim_workspace_bytes", B, H, W)
+    def cond_ddim_workspace_bytes(self, B: int, H: int, W: int, guided: bool = False) -> int:
+        what = "cond_ddim_guided_workspace_bytes" if guided else "cond_ddim_workspace_bytes"
+        return self._bytes("mcedm_" + what, what, B, H, W)
 
     def _dims(self, B: int, H: int, W: int) -> tuple:
         return B, H, W
@@ -768,11 +802,13 @@ class DdpmPlan(_PlanBase):
 
     # the size queries keep Plan's signatures (H, W: ignored, the state has the plan's resolution): GraphedVpSampler /
     # GraphedCondDdim and the Lightning module drive either network through them and through vp_sample / cond_ddim_sample
-    def vp_sampler_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> int:
-        return self._bytes("mcedm_ddpm_vp_sampler_workspace_bytes", "ddpm_vp_sampler_workspace_bytes", B)
+    def vp_sampler_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None, guided: bool = False) -> int:
+        what = "ddpm_vp_guided_workspace_bytes" if guided else "ddpm_vp_sampler_workspace_bytes"
+        return self._bytes("mcedm_" + what, what, B)
 
-    def cond_ddim_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> int:
-        return self._bytes("mcedm_ddpm_cond_ddim_workspace_bytes", "ddpm_cond_ddim_workspace_bytes", B)
+    def cond_ddim_workspace_bytes(self, B: int, H: Optional[int] = None, W: Optional[int] = None, guided: bool = False) -> int:
+        what = "ddpm_cond_ddim_guided_workspace_bytes" if guided else "ddpm_cond_ddim_workspace_bytes"
+        return self._bytes("mcedm_" + what, what, B)
 
     def _dims(self, B: int, H: Optional[int] = None, W: Optional[int] = None) -> tuple:
         return (B,)
@@ -1095,9 +1131,11 @@ class GraphedCondDdim(_GraphedCall):
     instance's static (xs, x0_preds), overwritten by the next call."""
 
     def __init__(self, plan: "Plan", packed: torch.Tensor, dd: CondDdimDesc, B: int, H: int, W: int, stochastic: bool,
-                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False):
+                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False,
+                 guidance: Optional["GuidanceDesc"] = None):
         dev = packed.device
         self.plan, self.packed, self.dd, self.return_last = plan, packed, dd, return_last
+        self.guidance = guidance      # host-side description (guide_dx), baked into the captured kernel arguments
         Cc, S = plan.in_channels, len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
         self.cond = torch.zeros((B, dd.cond_channels, H, W), device=dev) if dd.cond_channels > 0 else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
@@ -1105,11 +1143,11 @@ class GraphedCondDdim(_GraphedCall):
         self.out = (torch.empty((B, 1 if return_last else S + 1, H, W, Cc), device=dev),
                     torch.empty((B, 1 if return_last else S, H, W, Cc), device=dev))
         self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "eta_noise": self.eta_noise}, ws,
-                           plan.cond_ddim_workspace_bytes(B, H, W))
+                           plan.cond_ddim_workspace_bytes(B, H, W, guided=guidance is not None))
 
     def _run(self):
         self.plan.cond_ddim_sample(self.packed, self.dd, self.cond, self.init, self.eta_noise, self.return_last, self.ws, out=self.out,
-                                   rng_seed=self.seed)
+                                   rng_seed=self.seed, guidance=self.guidance)
 
     def __call__(self, cond, init_noise, eta_noise=None, seed=None):
         return self._replay(seed, cond, init_noise, eta_noise)
@@ -1150,20 +1188,22 @@ class GraphedVpSampler(_GraphedCall):
     ``self.seed``.  Returns the instance's static output tensor, overwritten by the next call."""
 
     def __init__(self, plan: "Plan", packed: torch.Tensor, vd: VpSamplerDesc, B: int, H: int, W: int, has_cond: bool, churn: bool,
-                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False):
+                 return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False,
+                 guidance: Optional["GuidanceDesc"] = None):
         dev = packed.device
         self.plan, self.packed, self.vd, self.return_last = plan, packed, vd, return_last
+        self.guidance = guidance      # host-side description (guide_dx), baked into the captured kernel arguments
         Cc = plan.in_channels
         self.cond = torch.zeros((B, vd.cond_channels, H, W), device=dev) if has_cond else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
         self.seed, self.step_noise = self._draws(dev, churn, device_noise, (vd.timesteps, B, Cc, H, W), torch.float64)
         self.out = torch.empty((B, 1 if return_last else vd.timesteps + 1, H, W, Cc), dtype=torch.float64, device=dev)
         self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "step_noise": self.step_noise}, ws,
-                           plan.vp_sampler_workspace_bytes(B, H, W))
+                           plan.vp_sampler_workspace_bytes(B, H, W, guided=guidance is not None))
 
     def _run(self):
         self.plan.vp_sample(self.packed, self.vd, self.cond, self.init, self.step_noise, self.return_last, self.ws,
-                            rng_seed=self.seed, out=self.out)
+                            rng_seed=self.seed, out=self.out, guidance=self.guidance)
 
     def __call__(self, cond, init_noise, step_noise=None, seed=None) -> torch.Tensor:
         return self._replay(seed, cond, init_noise, step_noise)
@@ -1440,7 +1480,9 @@ def _bind_ops():
                                             i32, vp, i32, i32, vp, i32, i32, vp]
     lib.mcedm_op_ddim_cond_step_rng.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32,
                                                 i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
-    for n in ("mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
+    lib.mcedm_op_ddim_cond_step_guided.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, f32, C.c_double, f32, f32, f32, f32, f32, vp, vp,
+                                                   vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
+    for n in ("mcedm_op_ddim_cond_step_guided", "mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
               "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
               "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
               "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
@@ -1459,7 +1501,7 @@ OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_
               "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
               "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
               "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn", "mcedm_op_conv_wino_split", "mcedm_op_conv_wino_split_sums",
-              "mcedm_op_set_conv_wino_split"]
+              "mcedm_op_set_conv_wino_split", "mcedm_op_ddim_cond_step_guided"]
 
 
 def prof_enable(on: bool) -> None:
@@ -1848,16 +1890,25 @@ def op_attention_bwd(qkv, a, da, heads):
 
 
 def op_ddim_cond_step(xt, F, s0, s1, sa_next, c2, Fu=None, w=0.0, noise=None, c1=0.0, condp=None, condp_u=None, cond_channels=0,
-                      xs=None, t_xs=0, x0s=None, t_x0=0, rng_seed=None, draw=0):
+                      xs=None, t_xs=0, x0s=None, t_x0=0, rng_seed=None, draw=0, dx=None, gw=None):
     """One elementwise step of the conditional DDIM sampler (mcedm_op_ddim_cond_step) -> xt_next.  x0 is written into channels
     [cond_channels, cond_channels + C) of condp / condp_u and into slot t_x0 of x0s, xt_next into slot t_xs of xs ('b t h w c').
-    rng_seed (int64 [1] on the device) with draw: the kernel generates the uniform noise itself (mcedm_op_ddim_cond_step_rng)."""
+    rng_seed (int64 [1] on the device) with draw: the kernel generates the uniform noise itself (mcedm_op_ddim_cond_step_rng).
+    dx [B, 1, H, W] and gw (or gw alone, dx None): mcedm_op_ddim_cond_step_guided, both noise forms in its one signature, with the
+    PDE-guidance term et -= gw * dx."""
     lib = _bind_ops()
     B, Cc, H, W = xt.shape
     xt_next = torch.empty_like(xt)
     args = (float(w), s0, s1, sa_next, c1, c2, _ptr(xt_next), _ptr(condp), _ptr(condp_u), int(cond_channels),
             0 if condp is None else condp.shape[1], B, Cc, H, W, _ptr(xs), 0 if xs is None else xs.shape[1], int(t_xs), _ptr(x0s),
             0 if x0s is None else x0s.shape[1], int(t_x0))
+    if dx is not None or gw is not None:
+        if dx is not None and tuple(dx.shape) != (B, 1, H, W):
+            raise RuntimeError(f"op_ddim_cond_step: dx must be {(B, 1, H, W)}, got {tuple(dx.shape)}")
+        seed = None if rng_seed is None else _seed_ptr(rng_seed, xt.device, "op_ddim_cond_step")
+        check(lib.mcedm_op_ddim_cond_step_guided(_ptr(xt), _ptr(F), _ptr(Fu), _ptr(noise), seed, int(draw), _ptr(dx), float(gw or 0.0),
+                                                 *args, _stream()), "op_ddim_cond_step_guided")
+        return xt_next
     if rng_seed is not None:
         if noise is not None:
             raise RuntimeError("op_ddim_cond_step: give noise or rng_seed, not both")
