@@ -31,7 +31,6 @@ int launch_wgrad_wino(const WgradArgs& a, const float* x, float* dw, float* db, 
 size_t wgrad_gemm1_scratch_floats(int Cout, int Cin, int taps);
 bool wgrad_gemm1_applicable(const WgradArgs& a, int taps, const float* x, bool in_place_concat);
 int launch_wgrad_gemm1(const WgradArgs& a, const float* x, float* dbp, int* nslices, hipStream_t s);
-void set_wgrad_wino(int enable);                                   // 1 / 0, -1: default (env MCEDM_WGRAD_WINO, else on)
 // the materialisation step alone: out[B, Ca+Cb, H, W] = resample(act(coef(cat(xa, xb)))); dy / Cout / dwp are not read
 int launch_act_materialize(const WgradArgs& a, float* out, hipStream_t s);
 

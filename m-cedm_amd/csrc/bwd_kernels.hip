@@ -372,17 +372,12 @@ __global__ __launch_bounds__(256) void gn_bwd_lds_kernel(GnBwdArgs a, int ppc, u
   }
 }
 
-static int gn_bwd_lds_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_GN_BWD_LDS"); env = e ? atoi(e) : 1; }
-  return env;
-}
-
 // does the LDS-resident kernel serve this call (shape, switch, counters)?  -> pieces per channel
 static bool gn_bwd_lds_plan(const GnBwdArgs& a, int* ppc_out) {
+  static const int env = env_int("MCEDM_GN_BWD_LDS", 1);
   const int C = a.Ca + a.Cb, cpg = C / a.groups;
   const size_t HW = (size_t)a.Hs * a.Ws;
-  if (!gn_bwd_lds_env() || !a.sync || HW % GNL_PIECE != 0 || (size_t)cpg * HW < 16384) return false;
+  if (!env || !a.sync || HW % GNL_PIECE != 0 || (size_t)cpg * HW < 16384) return false;
   if (a.resample != RS_NONE && (a.Ws % 4 != 0 || a.Hs % 2 != 0 || (a.resample != RS_UP && a.resample != RS_DOWN))) return false;
   const size_t k = (size_t)cpg * (HW / GNL_PIECE);
   if (k > GNL_KMAX) return false;
@@ -393,8 +388,7 @@ static bool gn_bwd_lds_plan(const GnBwdArgs& a, int* ppc_out) {
 }
 
 static int launch_gn_bwd_lds(const GnBwdArgs& a, int ppc, hipStream_t s) {
-  static int spin_us = -1;                                   // MCEDM_GN_BWD_SPIN_US: how long a workgroup waits for its partners (0: never)
-  if (spin_us < 0) { const char* e = getenv("MCEDM_GN_BWD_SPIN_US"); spin_us = e ? atoi(e) : 100; }
+  static const int spin_us = env_int("MCEDM_GN_BWD_SPIN_US", 100);   // how long a workgroup waits for its partners (0: never)
   const unsigned ticks = (unsigned)spin_us * 100u;           // s_memrealtime: 100 MHz
   const int k = (a.Ca + a.Cb) / a.groups * ppc;
   hipLaunchKernelGGL(gn_bwd_lds_kernel, dim3((unsigned)a.B * a.groups * k), dim3(256), 0, s, a, ppc, ticks);
@@ -507,8 +501,7 @@ __global__ __launch_bounds__(256) void gn_bwd_reg_kernel(GnBwdArgs a, int segshi
 
 // quads per thread (1, 2, 4, 8) when gn_bwd_reg_kernel serves the call, else 0; *segshift: log2 of the lanes that share a channel
 static int gn_bwd_reg_plan(const GnBwdArgs& a, int* segshift) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_GN_BWD_REG"); env = e ? atoi(e) : 1; }
+  static const int env = env_int("MCEDM_GN_BWD_REG", 1);
   const int C = a.Ca + a.Cb, cpg = C / a.groups;
   const size_t HW = (size_t)a.Hs * a.Ws;
   if (!env || a.resample != RS_NONE || HW % 4 != 0 || (size_t)cpg * HW > 8192) return 0;
@@ -548,8 +541,7 @@ int launch_gn_bwd(const GnBwdArgs& a, hipStream_t s) {
   ProfScope ps("gn_bwd_kernel", 20.0 * a.B * (double)C * a.Hs * a.Ws, 4.0 * 3 * a.B * (double)C * a.Hs * a.Ws, s);
   // slabs of >= 64 KB: 1024-thread workgroups (at most two per CU instead of eight, so that fewer slabs are between their two passes
   // at any time and more of pass 2 is served by the memory-side cache: 5.78 -> 5.43 ms per S128 step, 3.12 -> 2.77 ms on the ch = 64 network)
-  static int nt = -1;
-  if (nt < 0) { const char* e = getenv("MCEDM_GN_BWD_NT"); nt = e ? atoi(e) : 1024; }
+  static const int nt = env_int("MCEDM_GN_BWD_NT", 1024);
   if (nt == 1024 && (size_t)(C / a.groups) * a.Hs * a.Ws >= 16384)
     hipLaunchKernelGGL(gn_bwd_kernel<1024>, dim3(a.B * a.groups), dim3(1024), 0, s, a);
   else
@@ -1116,8 +1108,7 @@ int launch_attention_bwd(const float* qkv, const float* a, const float* da, floa
   const dim3 grid(ceil_div(T, 32), B * heads);
   ProfScope ps("attention_bwd", 10.0 * B * heads * (double)T * T * 64, 4.0 * 8 * B * heads * 64.0 * T, s);
   // split factor: a function of T only (never of the batch size)
-  static int lds_env = -1;                                 // MCEDM_ATTN_BWD_LDS=0: the direct-from-global kernels at every T (A/B runs)
-  if (lds_env < 0) { const char* e = getenv("MCEDM_ATTN_BWD_LDS"); lds_env = e ? atoi(e) : 1; }
+  static const int lds_env = env_int("MCEDM_ATTN_BWD_LDS", 1);   // 0: the direct-from-global kernels at every T (A/B runs)
   const bool lds_path = lds_env && T % 128 == 0 && ((reinterpret_cast<size_t>(qkv) | reinterpret_cast<size_t>(da)) & 15) == 0;
   if (!lds_path) {
     if (T >= 128) hipLaunchKernelGGL(attn_bwd_stats_kernel<4>, grid, dim3(256), 0, s, qkv, a, da, lse, T);
@@ -1127,8 +1118,7 @@ int launch_attention_bwd(const float* qkv, const float* a, const float* da, floa
   }
   if (lds_path) {
     const dim3 g4(T / 128, B * heads);
-    static int xmap = -1;
-    if (xmap < 0) { const char* e = getenv("MCEDM_ATTN_XCD"); xmap = e ? atoi(e) : 1; }
+    const int xmap = attn_xcd_env();
     hipLaunchKernelGGL(attn_bwd_dq_lds_kernel, g4, dim3(256), 0, s, qkv, a, da, lse, dqkv, T, xmap);
     MCEDM_LAUNCH_CHECK("attn_bwd_dq_lds_kernel");
     hipLaunchKernelGGL(attn_bwd_dkv_lds_kernel, g4, dim3(256), 0, s, qkv, da, lse, dqkv, T, xmap);

@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "mcedm_hip.h"
+#include "switches.hpp"
 
 namespace mcedm {
 
@@ -38,25 +39,6 @@ void set_error(const char* fmt, ...);
     }                                                                                         \
   } while (0)
 
-// Kernel-variant choices.  Three levels, first hit wins: the plan whose entry point is executing on this thread
-// (mcedm_*_plan_set_variant; a field of the plan, so two plans in one process -- on two threads or two streams -- cannot flip each
-// other's kernels), the process-wide test hooks mcedm_op_set_* (kernel-level calls have no plan), the environment.
-enum KernelVariant { KV_CONV_WINO = 0, KV_CONV_WINO1 = 1, KV_CONV_RESIDENT = 2, KV_CONV8 = 3, KV_ATTN_FUSED = 4, KV_WGRAD_WINO = 5,
-                     KV_CONV1X1_REG = 6, KV_CONV_WINO_FOLD = 7, KV_CONV_WINO_UPZ = 8, KV_CONV_WINO_SPLIT = 9, KV_COUNT = 10 };
-struct KernelVariants { int v[KV_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1}; };
-const KernelVariants* current_variants();                 // of the executing plan-level call on this thread, or null
-struct VariantScope {                                      // first statement of every extern "C" function that takes a plan
-  const KernelVariants* prev;
-  explicit VariantScope(const KernelVariants* kv);
-  ~VariantScope();
-};
-// value of switch `which`: the executing plan's if it set one, else `global` (an mcedm_op_set_* value) if >= 0, else env_default
-static inline int variant_choice(int which, int global, int env_default) {
-  const KernelVariants* kv = current_variants();
-  if (kv && kv->v[which] >= 0) return kv->v[which];
-  return global >= 0 ? global : env_default;
-}
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -76,6 +58,8 @@ __device__ __forceinline__ void xcd_group_map(int map, int& bx, int& by) {
   bx = i - (i / nx) * nx;
 }
 #endif
+// MCEDM_ATTN_XCD: the `map` of xcd_group_map in the attention forward and backward kernels
+inline int attn_xcd_env() { static const int v = env_int("MCEDM_ATTN_XCD", 1); return v; }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -186,11 +170,8 @@ bool conv_wino_applicable(const ConvArgs& a, int taps);
 bool conv_wino_shape_ok(int Cout, int Cin, int H, int W);
 // the SKIP variant: conv1 of an un-resampled block computes the block's 1x1 skip projection (sk_Ca + sk_Cb -> Cout) in its epilogue
 bool conv_wino_fold_shape_ok(int Cout, int sk_Ca, int sk_Cb, int H, int W);
-void set_conv_wino_fold(int enable);                     // 1 / 0, -1: default (env MCEDM_WINO_FOLD, else on)
-void set_conv_wino_upz(int enable);                      // 1 / 0, 2: the positions alone (A/B runs), -1: default (env MCEDM_WINO_UPZ, else on)
 size_t conv_frag_packed_floats(int Cout, int Cin);       // a 1x1 conv's weights in MFMA-fragment order (ConvArgs::sk_wfrag)
 int launch_pack_conv_frag(const float* w, float* dst, int Cout, int Cin, hipStream_t stream);   // w [Cout][Cin]
-void set_conv_wino(int enable);                          // 1 / 0, -1: default (env MCEDM_WINOGRAD, else on)
 bool conv_wino_preferred(const ConvArgs& a);              // env MCEDM_WINOGRAD (default on), MCEDM_WINO_MIN_HW (default 32 x 32)
 int launch_conv_wino(const ConvArgs& a, hipStream_t stream);
 // the SPLIT variant (conv_wino.hpp WinoSplitCfg): un-resampled 3x3 convs on images below the other variants' minimum size
@@ -198,19 +179,15 @@ bool conv_wino_split_applicable(const ConvArgs& a, int taps);
 bool conv_wino_split_preferred();                        // the Winograd kernels are on and so is this one
 bool conv_wino_small(int H, int W);                      // an image below the minimum size of the other variants (MCEDM_WINO_MIN_HW)
 int launch_conv_wino_split(const ConvArgs& a, hipStream_t stream);
-void set_conv_wino_split(int enable);                    // 1 / 0, -1: default (env MCEDM_WINO_SPLIT, else on)
 bool conv_resident_explicit();                           // a plan or mcedm_op_set_conv_resident has set the input-resident switch, either way
 static inline int cout_padded(int Cout) { return (Cout + 31) / 32 * 32; }     // channel padding of the packed tables
 int conv_resolve_identity(ConvArgs& a);                  // points a missing transform table at the identity row
 unsigned long long* conv_debug_buffer();
 int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream);   // conv_resident.hip; -1: not served there
 int try_launch_conv1x1_reg(const ConvArgs& a, int taps, hipStream_t stream);     // conv1x1_reg.hip (un-transformed 1x1 convs); -1: not served
-void set_conv1x1_reg(int enable);                        // 1 / 0, -1: default (env MCEDM_CONV1X1_REG, else on)
-void set_conv_resident(int enable);                      // 1 / 0, -1: default (env MCEDM_CONV_RESIDENT, else on)
 static inline int conv_max_tiles(int H, int W) { return ((H + 3) / 4) * ((W + 7) / 8); }   // smallest pixel tile is 4x8 (conv_resident.hip)
-void set_conv_tile_override(int mt, int ph, int pw);
-void set_conv8(int enable);   // 1 / 0, -1: default (env MCEDM_CONV8, else off)
-void set_conv_debug(unsigned long long* buf);   // test hook; (0,0,0) restores the heuristic
+void set_conv_tile_override(int mt, int ph, int pw);   // test hook; (0,0,0) restores the heuristic
+void set_conv_debug(unsigned long long* buf);
 // geometry the packer must use for a given (Cout, taps): tile height over Cout and K-chunk
 int conv_mt_for(int Cout);
 int conv_kc_for(int taps);
@@ -243,6 +220,5 @@ bool attn_block_fused_applicable(int C, int heads, int H, int W, int groups);
 int launch_attn_block64(const float* y, float* z, const float* gamma, const float* beta, float eps, int groups, const float* wq,
                         const float* bq, const float* wp, const float* bp, float* gsum, SumTiles* gsum_tiles, int B,
                         hipStream_t stream);
-void set_attn_fused(int enable);      // 1 / 0, -1: default (env MCEDM_ATTN_FUSED, else on)
 
 }  // namespace mcedm

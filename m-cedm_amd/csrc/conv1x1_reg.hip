@@ -165,19 +165,11 @@ __global__ __launch_bounds__(512, 1) void conv1x1_reg_kernel(const Conv1Args p) 
   }
 }
 
-static int g_c1 = -1;         // -1: default (env MCEDM_CONV1X1_REG, else on)
-void set_conv1x1_reg(int enable) { g_c1 = enable; }
-static int c1_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_CONV1X1_REG"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_CONV1X1_REG, g_c1, env);
-}
-
 // -1: not served here (shape, transform, switch); else the launch status
 int try_launch_conv1x1_reg(const ConvArgs& a, int taps, hipStream_t stream) {
   const int Cin = a.Ca + a.Cb;
   const unsigned long long HW = (unsigned long long)a.H * a.W;
-  if (!c1_env() || taps != 1 || a.resample != RS_NONE || a.coef || a.act || a.sk_wpk || a.gsum || a.gn_on) return -1;
+  if (!kernel_switch(KV_CONV1X1_REG) || taps != 1 || a.resample != RS_NONE || a.coef || a.act || a.sk_wpk || a.gsum || a.gn_on) return -1;
   if (a.res && a.res_mode != RS_NONE) return -1;
   const int MT = a.Cout % 128 == 0 ? 128 : 64;
   const int C1_MT = MT, C1_PX = c1_px(MT);
@@ -216,8 +208,8 @@ int try_launch_conv1x1_reg(const ConvArgs& a, int taps, hipStream_t stream) {
   }
   const double px = (double)a.B * (double)HW;
   ProfScope ps("conv1x1_reg_kernel", 2.0 * px * a.Cout * Cin, 4.0 * (px * (Cin + a.Cout * (a.res ? 2 : 1)) + (double)a.Cout * Cin), stream);
-  static int ni_env = -1;                                  // MCEDM_C1_NI: 2 or 4 (A/B runs; the two differ in the last bits of nothing: same sums)
-  if (ni_env < 0) { const char* e = getenv("MCEDM_C1_NI"); ni_env = e ? atoi(e) : 2; }      // NI = 4 measured 20 % slower (436 vs 364 us)
+  // MCEDM_C1_NI: 2 or 4 (A/B runs; the two differ in the last bits of nothing: same sums); NI = 4 measured 20 % slower (436 vs 364 us)
+  static const int ni_env = env_int("MCEDM_C1_NI", 2);
   if (MT == 64) hipLaunchKernelGGL((conv1x1_reg_kernel<2, 64>), dim3(wgs, mblocks), dim3(512), lds, stream, p);
   else if (ni_env == 2) hipLaunchKernelGGL(conv1x1_reg_kernel<2>, dim3(wgs, mblocks), dim3(512), lds, stream, p);
   else hipLaunchKernelGGL(conv1x1_reg_kernel<4>, dim3(wgs, mblocks), dim3(512), lds, stream, p);

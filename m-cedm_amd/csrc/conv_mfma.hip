@@ -646,8 +646,7 @@ static int launch_cfg(const ConvArgs& a_in, hipStream_t stream) {
   const double bytes = 4.0 * ((double)a.B * (a.Ca + a.Cb) * a.Hs * a.Ws + px * skc + px * a.Cout * (a.res ? 2 : 1) +
                               (double)a.Cout * ((a.Ca + a.Cb) * C::TAPS + skc));
   ProfScope ps(name, flops, bytes, stream);
-  static int extra_lds = -1;     // diagnostics: MCEDM_CONV_EXTRA_LDS bytes of unused dynamic LDS lower the occupancy
-  if (extra_lds < 0) { const char* e = getenv("MCEDM_CONV_EXTRA_LDS"); extra_lds = e ? atoi(e) : 0; }
+  static const int extra_lds = env_int("MCEDM_CONV_EXTRA_LDS", 0);   // diagnostics: bytes of unused dynamic LDS lower the occupancy
   const unsigned rows_bytes = (unsigned)(a.Ca + a.Cb) * (unsigned)sizeof(Coef);      // transform rows in dynamic LDS
   MCEDM_REQUIRE((C::XL + C::WL) * sizeof(float) + rows_bytes <= 64 * 1024, "conv: %d input channels exceed the LDS row table",
                 a.Ca + a.Cb);
@@ -712,8 +711,7 @@ static int dispatch_s2(const ConvArgs& a, hipStream_t stream) {
   return launch_cfg_s2<ConvCfg<64, 8, 16, 1, 4, 9, 8>>(a, stream);
 }
 
-typedef ConvCfg<128, 16, 32, 1, 8, 9, 8, 512> Conv8Cfg;
-static int g_conv8 = -1;     // MCEDM_CONV8=1 selects the 8-wave kernel for the large layers (off: it only ties)
+typedef ConvCfg<128, 16, 32, 1, 8, 9, 8, 512> Conv8Cfg;     // KV_CONV8 selects the 8-wave kernel for the large layers (off: it only ties)
 
 static int launch_conv8(const ConvArgs& a_in, hipStream_t stream) {
   typedef Conv8Cfg C;
@@ -756,8 +754,6 @@ static int launch_conv8(const ConvArgs& a_in, hipStream_t stream) {
   if (a.gsum_tiles) *a.gsum_tiles = SumTiles{tiles_x * ceil_div(a.H, 8), tiles_x, 8, C::PW};     // records are per 8 x 32 sub-tile
   return MCEDM_OK;
 }
-
-void set_conv8(int enable) { g_conv8 = enable; }
 
 static int launch_small_cout(const ConvArgs& a_in, hipStream_t stream) {
   struct C { enum { PH = 16, PW = 64, KC = 8 }; };      // the kernel's pixel tile and K chunk
@@ -845,10 +841,8 @@ static int dispatch(const ConvArgs& a, hipStream_t stream) {
     return launch_cfg<ConvCfg<32, 8, 32, 1, 4, TAPS, KC>>(a, stream);
   }
   if (a.W >= 24) {
-    static int conv8_env = -1;
-    if (conv8_env < 0) { const char* e = getenv("MCEDM_CONV8"); conv8_env = e ? atoi(e) : 0; }
     // experimental 8-wave kernel (needs about one workgroup per CU); results are bit-identical to <128, 8, 32>
-    if (variant_choice(KV_CONV8, g_conv8, conv8_env) && !a.sk_wpk && a.gsum_rc != 2 && TAPS == 9 && a.resample == RS_NONE && coutp % 128 == 0 && a.Ca + a.Cb <= 2048 &&
+    if (kernel_switch(KV_CONV8) && !a.sk_wpk && a.gsum_rc != 2 && TAPS == 9 && a.resample == RS_NONE && coutp % 128 == 0 && a.Ca + a.Cb <= 2048 &&
         blocks_for(128, 16, 32) >= 224)
       return launch_conv8(a, stream);
     if (coutp % 128 == 0 && blocks_for(128, 8, 32) >= want) return launch_cfg<ConvCfg<128, 8, 32, 1, 4, TAPS, KC>>(a, stream);

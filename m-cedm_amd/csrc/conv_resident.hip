@@ -570,36 +570,26 @@ __global__ __launch_bounds__(256, 2) void conv_resident_kernel(ConvArgs p, int t
 
 // -------------------------------------------------------------------------------------------
 // host side
-static int g_resident = -1;      // -1: default (env MCEDM_CONV_RESIDENT, else on); 0 / 1: forced by mcedm_op_set_conv_resident
-void set_conv_resident(int enable) { g_resident = enable; }
-static int resident_level() {     // 0: off, > 0: on
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_CONV_RESIDENT"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_CONV_RESIDENT, g_resident, env);
-}
-bool conv_resident_explicit() { return variant_choice(KV_CONV_RESIDENT, g_resident, -1) >= 0; }
+static int resident_level() { return kernel_switch(KV_CONV_RESIDENT); }     // 0: off, > 0: on
+bool conv_resident_explicit() { return kernel_switch_forced(KV_CONV_RESIDENT) >= 0; }
 
 static constexpr int LDS_MAX = 160 * 1024;
 // big-tile (>= 64 x 64 images) variants: MCEDM_RES_BIG=0 turns them off; MCEDM_RES_BIG_PASS = channels per pass (multiple of 8)
 static int big_level() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_RES_BIG"); env = e ? atoi(e) : 1; }
+  static const int env = env_int("MCEDM_RES_BIG", 1);
   return env;
 }
 static int db_level() {          // MCEDM_RES_DB=1: double-buffered short passes at <= 32 x 32 (experiment)
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_RES_DB"); env = e ? atoi(e) : 0; }
+  static const int env = env_int("MCEDM_RES_DB", 0);
   return env;
 }
 static int big128_level() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_RES_BIG128"); env = e ? atoi(e) : 0; }
+  static const int env = env_int("MCEDM_RES_BIG128", 0);
   return env;
 }
 static int big_pass() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_RES_BIG_PASS"); env = (e && atoi(e) >= 8) ? atoi(e) / 8 * 8 : 1 << 20; }
-  return env;
+  static const int v = env_int("MCEDM_RES_BIG_PASS", 0);
+  return v >= 8 ? v / 8 * 8 : 1 << 20;
 }
 
 // Launch plan of one conv: channels resident per pass (0: this conv is not served here), weight slabs in the ring.
@@ -726,8 +716,7 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
       }
       ResidentPlan pl = resident_plan<M, true>(a, half_cu, 32);
       if (!pl.pass_c || pl.nslab != 3) return -1;
-      static int pass_env = -1;      // experiments: MCEDM_RES_PASS = channels per pass (multiple of 16, <= the plan's)
-      if (pass_env < 0) { const char* e = getenv("MCEDM_RES_PASS"); pass_env = e ? atoi(e) : 0; }
+      static const int pass_env = env_int("MCEDM_RES_PASS", 0);      // experiments: channels per pass (multiple of 16, <= the plan's)
       if (pass_env >= 16 && pass_env % 16 == 0 && pass_env < pl.pass_c) pl.pass_c = pass_env;
       return a.resample == RS_UP ? launch_resident<M, RS_UP, true>(a, pl, stream) : launch_resident<M, RS_NONE, true>(a, pl, stream);
     }
@@ -739,8 +728,7 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
       // segments (6 instructions per wave and 16-channel pass), is transformed in place, and no staging registers exist, so
       // a wave can own EIGHT accumulator blocks (64 channels x 16 x 32 pixels per workgroup) at two workgroups per CU.
       // The pixel tile is a function of the image size only (batch-shard bit-identity).
-      static int b16_min = -1;      // MCEDM_RES_B16_MIN: smallest image (pixels) that takes the 16 x 32 tile (experiments)
-      if (b16_min < 0) { const char* e = getenv("MCEDM_RES_B16_MIN"); b16_min = e ? atoi(e) : 16384; }
+      static const int b16_min = env_int("MCEDM_RES_B16_MIN", 16384);      // smallest image (pixels) that takes the 16 x 32 tile (experiments)
       if ((long long)a.H * a.W >= b16_min) {
         typedef ResCfg<64, 16, 32, 1, 4, 9, 8> B16;
         ResidentPlan pl = resident_plan<B16, true>(a, half_cu, 8);
@@ -768,8 +756,8 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
   // ~32 x 32 images (the decoder's skip projections there, launched on their own since conv1 runs on the Winograd kernel):
   // 1024 tiles per 64 samples, two workgroups per CU.  conv_mfma_kernel's <32, 8, 32> tile walks 8-16 chunks of
   // load -> barrier -> MFMA -> barrier with one accumulator block per wave and sits at 28 TFLOP/s there.
-  static int p32 = -1;               // MCEDM_RES_1X1_32 (A/B runs): 0 keeps these convs on conv_mfma_kernel, 1: 8 x 8-pixel tiles, 2 (default): 8 x 16
-  if (p32 < 0) { const char* e = getenv("MCEDM_RES_1X1_32"); p32 = e ? atoi(e) : 2; }
+  // MCEDM_RES_1X1_32 (A/B runs): 0 keeps these convs on conv_mfma_kernel, 1: 8 x 8-pixel tiles, 2 (default): 8 x 16
+  static const int p32 = env_int("MCEDM_RES_1X1_32", 2);
   if (p32 > 0 && !small && a.W >= 24 && (long long)a.H * a.W <= 1024 && !a.sk_wpk && cout_padded(a.Cout) % 64 == 0) {
     if (p32 == 2) {              // 8 x 16-pixel tiles: 512 workgroups per 64 samples = ONE round of two per CU (S32 1750 -> 1781 states/s; 8 x 8: two rounds)
       typedef ResCfg<64, 8, 16, 1, 4, 1, 16> P16;

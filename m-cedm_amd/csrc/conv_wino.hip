@@ -971,47 +971,17 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 #endif
 }
 
-static int g_wino = -1;      // -1: default (env MCEDM_WINOGRAD, else on); 0 / 1: forced by mcedm_op_set_conv_wino
-void set_conv_wino(int enable) { g_wino = enable; }
-static int wino_env() {                                        // MCEDM_WINOGRAD=0: never take this kernel
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WINOGRAD"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_CONV_WINO, g_wino, env);            // the executing plan's choice, the process-wide hook, the environment
-}
-static int g_wino_fold = -1; // -1: default (env MCEDM_WINO_FOLD, else on); 0 / 1: forced by mcedm_op_set_conv_wino_fold
-void set_conv_wino_fold(int enable) { g_wino_fold = enable; }
-static int wino_fold_env() {                                   // MCEDM_WINO_FOLD=0: the skip projection stays a launch of its own
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WINO_FOLD"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_CONV_WINO_FOLD, g_wino_fold, env);
-}
-static int g_wino_upz = -1;  // -1: default (env MCEDM_WINO_UPZ, else on); 0 / 1: forced by mcedm_op_set_conv_wino_upz
-void set_conv_wino_upz(int enable) { g_wino_upz = enable; }
-static int wino_upz_env() {                                    // MCEDM_WINO_UPZ=0: the up-sampling convs run all sixteen positions
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WINO_UPZ"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_CONV_WINO_UPZ, g_wino_upz, env);
-}
-static int g_wino_split = -1; // -1: default (env MCEDM_WINO_SPLIT, else on); 0 / 1: forced by mcedm_op_set_conv_wino_split
-void set_conv_wino_split(int enable) { g_wino_split = enable; }
-static int wino_split_env() {                                  // MCEDM_WINO_SPLIT=0: the small images' 3x3 convs stay on the input-resident / tiled kernels
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WINO_SPLIT"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_CONV_WINO_SPLIT, g_wino_split, env);
-}
+// The switches of this file (switches.hpp) -- KV_CONV_WINO = 0: never take this kernel; KV_CONV_WINO_FOLD = 0: the skip projection stays
+// a launch of its own; KV_CONV_WINO_UPZ = 0: the up-sampling convs run all sixteen positions; KV_CONV_WINO_SPLIT = 0: the small images'
+// 3x3 convs stay on the input-resident / tiled kernels.
 static int wino_mode_env() {                                  // MCEDM_WINO_MODE: ablation bits of the -DMCEDM_WINO_TIMELINE build (else unused)
-  static int env = -1;                                         // | 256: the interleaved, XCD-aware tile map (MCEDM_WINO_MAP, default on)
-  if (env < 0) {
-    const char* e = getenv("MCEDM_WINO_MODE");
-    const char* m = getenv("MCEDM_WINO_MAP");
-    env = ((e ? atoi(e) : 0) & ~256) | ((m ? atoi(m) : 1) ? 256 : 0);
-  }
+  static const int env =                                       // | 256: the interleaved, XCD-aware tile map (MCEDM_WINO_MAP, default on)
+      (env_int("MCEDM_WINO_MODE", 0) & ~256) | (env_int("MCEDM_WINO_MAP", 1) ? 256 : 0);
   return env;
 }
 
 static int wino_min_hw_env() {                                 // MCEDM_WINO_MIN_HW: smallest image (pixels) served; below 32 x 32 the grid
-  static int env = -1;                                  // (B * H * W / 128 workgroups) no longer fills the chip
-  if (env < 0) { const char* e = getenv("MCEDM_WINO_MIN_HW"); env = e ? atoi(e) : 1024; }
+  static const int env = env_int("MCEDM_WINO_MIN_HW", 1024);   // (B * H * W / 128 workgroups) no longer fills the chip
   return env;
 }
 
@@ -1042,7 +1012,7 @@ int launch_pack_conv_wino(const float* w, float* dst, int Cout, int Cin, int tra
 static bool conv_wino_fold_ok(const ConvArgs& a) {
   const int Csk = a.sk_Ca + a.sk_Cb;
   const unsigned long long HW = (unsigned long long)a.H * a.W;
-  return wino_fold_env() != 0 && a.sk_wfrag && a.resample == RS_NONE && !a.res && a.act && a.Cout % 128 == 0 && a.sk_xa && a.sk_Ca > 0 &&
+  return kernel_switch(KV_CONV_WINO_FOLD) != 0 && a.sk_wfrag && a.resample == RS_NONE && !a.res && a.act && a.Cout % 128 == 0 && a.sk_xa && a.sk_Ca > 0 &&
          a.sk_Cb >= 0 && (a.sk_Cb > 0) == (a.sk_xb != nullptr) && a.sk_Ca % 16 == 0 && a.sk_Cb % 16 == 0 && Csk >= 32 && Csk <= 256 &&
          (((size_t)a.sk_xa | (size_t)a.sk_xb | (size_t)a.sk_wfrag) & 15) == 0 && HW * 4ull * (unsigned long long)a.sk_Ca < (1ull << 32) &&
          HW * 4ull * (unsigned long long)a.sk_Cb < (1ull << 32);
@@ -1050,7 +1020,7 @@ static bool conv_wino_fold_ok(const ConvArgs& a) {
 // plan-time question (build_layout): will conv1 of an un-resampled block (Csk -> Cout skip projection) take the fold?
 bool conv_wino_fold_shape_ok(int Cout, int sk_Ca, int sk_Cb, int H, int W) {
   const int Csk = sk_Ca + sk_Cb;
-  return wino_fold_env() != 0 && conv_wino_shape_ok(Cout, Cout, H, W) && Cout % 128 == 0 && sk_Ca > 0 && sk_Ca % 16 == 0 && sk_Cb % 16 == 0 &&
+  return kernel_switch(KV_CONV_WINO_FOLD) != 0 && conv_wino_shape_ok(Cout, Cout, H, W) && Cout % 128 == 0 && sk_Ca > 0 && sk_Ca % 16 == 0 && sk_Cb % 16 == 0 &&
          Csk >= 32 && Csk <= 256 && (unsigned long long)H * W * 4ull * (unsigned long long)(sk_Ca > sk_Cb ? sk_Ca : sk_Cb) < (1ull << 32);
 }
 
@@ -1106,8 +1076,7 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
     }
     attr_set[dev].store(true, std::memory_order_release);
   }
-  static int per_env = -1;                                 // MCEDM_WINO_PER: force the tiles per workgroup (A/B runs; must divide)
-  if (per_env < 0) { const char* e = getenv("MCEDM_WINO_PER"); per_env = e ? atoi(e) : 0; }
+  const int per_env = wino_per_env();
   int per = wino_tiles_per_wg(total, tiles_img, ncu[dev].load(std::memory_order_acquire) * (C::MB == 4 ? 1 : 2));
   if (per_env > 0 && tiles_img % per_env == 0) per = per_env;
   char name[64] = "";
@@ -1116,7 +1085,7 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   MCEDM_REQUIRE(a.bias_batch == 0 || (!C::SKIP && a.resample == RS_NONE && a.act && a.bias),
                 "conv_wino: a bias row per sample (bias_batch=%d) goes with an un-resampled, activated conv without a folded projection", a.bias_batch);
   // the zero-position variant (WinoUp: same LDS footprint); 2: with the sixteen-position kernel's staging (the positions alone, A/B runs)
-  const int upz = !C::SKIP && a.resample == RS_UP ? wino_upz_env() : 0;
+  const int upz = !C::SKIP && a.resample == RS_UP ? kernel_switch(KV_CONV_WINO_UPZ) : 0;
   if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<Wino%sCfg<%d>, %s, %s%s>", C::SKIP ? "Skip" : "", C::MB, a.resample == RS_UP ? "true" : "false",
                                noact ? "false" : "true", a.bias_batch ? ", WinoBiasRows" : upz == 2 ? ", WinoUp<false>" : upz ? ", WinoUp<true>" : "");   // = rocprofv3's name
   const double px = (double)a.B * a.H * a.W;
@@ -1171,14 +1140,14 @@ int launch_conv_wino(const ConvArgs& a_in, hipStream_t stream) {
 
 // plan-time question (build_layout): will an un-resampled Cin -> Cout conv on H x W images be served here?
 bool conv_wino_shape_ok(int Cout, int Cin, int H, int W) {
-  return wino_env() != 0 && Cout % 64 == 0 && Cin % WKC == 0 && H % WPH == 0 && W % WPW == 0 && (long long)H * W >= wino_min_hw_env();
+  return kernel_switch(KV_CONV_WINO) != 0 && Cout % 64 == 0 && Cin % WKC == 0 && H % WPH == 0 && W % WPW == 0 && (long long)H * W >= wino_min_hw_env();
 }
 // the dispatcher's choice: enabled, and an image large enough for the grid to fill the chip
-bool conv_wino_preferred(const ConvArgs& a) { return wino_env() != 0 && (long long)a.H * a.W >= wino_min_hw_env(); }
+bool conv_wino_preferred(const ConvArgs& a) { return kernel_switch(KV_CONV_WINO) != 0 && (long long)a.H * a.W >= wino_min_hw_env(); }
 
 // ---- the SPLIT variant (WinoSplitCfg): the images below that size
 bool conv_wino_small(int H, int W) { return (long long)H * W < wino_min_hw_env(); }
-bool conv_wino_split_preferred() { return wino_env() != 0 && wino_split_env() != 0; }
+bool conv_wino_split_preferred() { return kernel_switch(KV_CONV_WINO) != 0 && kernel_switch(KV_CONV_WINO_SPLIT) != 0; }
 // Un-resampled 3x3 convs with a Winograd table on whole 8 x 16 tiles, whole 32-channel output blocks and whole chunks out of either
 // source; residual absent, same-size or the 2x2 mean of a double-resolution source.  A folded skip projection, a bias row per
 // sample and anything misaligned stay with the direct kernels.

@@ -109,8 +109,9 @@ static_assert(RPLANE % 32 == 4 && VH1 % 32 == 16 && VH1 >= 128 && VPOS >= VH1 + 
 
 // conv_wino1.hip: the 128-channel shape with ONE wave per SIMD (see there); -1: not served (shape / switch), else the launch status
 int try_launch_conv_wino1(const ConvArgs& a, hipStream_t stream);
-void set_conv_wino1(int enable);                 // 1 / 0, -1: default (env MCEDM_WINO1, else off: measured 6-9 % slower)
 // tiles per persistent workgroup (a divisor of the tiles per image; conv_wino.hip)
 int wino_tiles_per_wg(long long total, int tiles_img, int slots);
+// MCEDM_WINO_PER: force the tiles per workgroup of both kernels (A/B runs; must divide the tiles per image)
+inline int wino_per_env() { static const int v = env_int("MCEDM_WINO_PER", 0); return v; }
 
 }  // namespace mcedm

@@ -419,18 +419,11 @@ __global__ __launch_bounds__(Wino1Cfg::NT, 1) void conv_wino1_kernel(const ConvA
   }
 }
 
-static int g_wino1 = -1;      // -1: default (env MCEDM_WINO1, else OFF: measured 9 % slower, see the header); 0 / 1: forced by mcedm_op_set_conv_wino1
-void set_conv_wino1(int enable) { g_wino1 = enable; }
-static int wino1_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WINO1"); env = e ? atoi(e) : 0; }
-  return variant_choice(KV_CONV_WINO1, g_wino1, env);
-}
-
 // a (already validated by launch_conv_wino) with Cout % 128 == 0: the one-wave-per-SIMD kernel; -1 when switched off
+// (KV_CONV_WINO1, default OFF: measured 9 % slower, see the header)
 int try_launch_conv_wino1(const ConvArgs& a, hipStream_t stream) {
   using C = Wino1Cfg;
-  if (!wino1_env() || a.Cout % C::MT != 0) return -1;
+  if (!kernel_switch(KV_CONV_WINO1) || a.Cout % C::MT != 0) return -1;
   const int tiles_x = a.W / WPW, tiles_img = tiles_x * (a.H / WPH);
   const long long total = (long long)a.B * tiles_img;
   MCEDM_REQUIRE(total > 0 && total <= 0x7fffffffLL, "conv_wino1: grid out of range");
@@ -450,8 +443,7 @@ int try_launch_conv_wino1(const ConvArgs& a, hipStream_t stream) {
     MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set[dev].store(true, std::memory_order_release);
   }
-  static int per_env = -1;
-  if (per_env < 0) { const char* e = getenv("MCEDM_WINO_PER"); per_env = e ? atoi(e) : 0; }
+  const int per_env = wino_per_env();
   int per = wino_tiles_per_wg(total, tiles_img, ncu[dev].load(std::memory_order_acquire));
   if (per_env > 0 && tiles_img % per_env == 0) per = per_env;
   char name[64] = "";

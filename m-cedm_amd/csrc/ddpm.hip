@@ -396,7 +396,7 @@ static int dpack_head(const mcedm_ddpm_plan& P, const float* const* params, floa
 
 extern "C" int mcedm_ddpm_pack_weights(const mcedm_ddpm_plan* plan, const float* const* params, const float* temb_freqs,
                                        void* packed, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && params && temb_freqs && packed, "ddpm_pack_weights: null argument");
   const mcedm_ddpm_plan& P = *plan;
   for (size_t i = 0; i < P.params.size(); ++i)
@@ -960,7 +960,7 @@ static int nearest_step(const float* steps, int n, float sigma) {
 // a size query: the caller's own buffers (bufs_of(plan, B).total bytes, a sampler's) in front of the network's workspace
 template <class BufsOf>
 static int workspace_query(const char* who, const mcedm_ddpm_plan* plan, int B, size_t* bytes, BufsOf bufs_of) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "%s: null argument", who);
   DdpmNet net;
   const int rc = ddpm_sizes(*plan, B, &net, bytes);
@@ -983,14 +983,14 @@ extern "C" int mcedm_ddpm_workspace_bytes(const mcedm_ddpm_plan* plan, int B, si
 
 extern "C" int mcedm_ddpm_forward(const mcedm_ddpm_plan* plan, const void* packed, const float* x, float t, float* out,
                                   void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward: null argument");
   return forward_entry("ddpm_forward", plan, packed, DdpmIn{x, t}, out, workspace, workspace_bytes, B, stream);
 }
 
 extern "C" int mcedm_ddpm_forward_sc(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
                                      float t, float* out, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_sc: null argument");
   MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_sc: the network was built without self-conditioning channels");
   DdpmIn in{x, t};
@@ -1000,7 +1000,7 @@ extern "C" int mcedm_ddpm_forward_sc(const mcedm_ddpm_plan* plan, const void* pa
 
 extern "C" int mcedm_ddpm_denoise(const mcedm_ddpm_plan* plan, const void* packed, const float* x, float sigma, float c_noise,
                                   float* D_out, float* F_out, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && D_out && workspace, "ddpm_denoise: null argument");
   DdpmNet net;
   const int rc = ddpm_bind("ddpm_denoise", *plan, packed, workspace, workspace_bytes, 0, B, stream, &net);
@@ -1139,14 +1139,14 @@ extern "C" int mcedm_repaint_sample(const mcedm_ddpm_plan* plan, const void* pac
                                     const float* hu, const float* init_noise, const double* step_noise,
                                     const double* repeat_noise, double* out, int return_last, void* workspace,
                                     size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return repaint_impl(plan, packed, sp, hu, init_noise, step_noise, repeat_noise, nullptr, out, return_last, workspace,
                       workspace_bytes, B, stream);
 }
 extern "C" int mcedm_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_repaint_desc* sp,
                                         const float* hu, const float* init_noise, const uint64_t* rng_seed, double* out,
                                         int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "repaint_sample_rng: rng_seed is null");
   return repaint_impl(plan, packed, sp, hu, init_noise, nullptr, nullptr, reinterpret_cast<const unsigned long long*>(rng_seed),
                       out, return_last, workspace, workspace_bytes, B, stream);
@@ -1265,7 +1265,7 @@ extern "C" int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void
                                          const float* hu, const float* init_noise, const float* eta_noise, float* xs_out,
                                          float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
                                          void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return ddim_repaint_impl(plan, packed, sp, hu, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
                            workspace_bytes, B, stream);
 }
@@ -1274,7 +1274,7 @@ extern "C" int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const 
                                              const float* hu, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
                                              float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
                                              void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "ddim_repaint_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return ddim_repaint_impl(plan, packed, sp, hu, init_noise, nullptr, reinterpret_cast<const unsigned long long*>(rng_seed), xs_out,
                            x0_out, return_last, workspace, workspace_bytes, B, stream);
@@ -1285,7 +1285,7 @@ extern "C" int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const 
 // ------------------------------------------------------------------------------------------
 extern "C" int mcedm_ddpm_cond_map(const mcedm_ddpm_plan* plan, const void* packed, const float* cond, float* map_out, int B,
                                    void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && map_out, "ddpm_cond_map: null argument");
   MCEDM_REQUIRE(plan->cond_channels > 0, "ddpm_cond_map: the plan was built without the cond_enc head (mcedm_ddpm_plan_create_cond)");
   MCEDM_REQUIRE(cond != nullptr, "ddpm_cond_map: cond is null on a plan with cond_channels=%d", plan->cond_channels);
@@ -1295,7 +1295,7 @@ extern "C" int mcedm_ddpm_cond_map(const mcedm_ddpm_plan* plan, const void* pack
 extern "C" int mcedm_ddpm_forward_cond(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
                                        const float* cond_map, float t, float* out, void* workspace, size_t workspace_bytes, int B,
                                        void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_cond: null argument");
   MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_cond: the network was built without self-conditioning channels");
   MCEDM_REQUIRE(!cond_map || plan->cond_channels > 0, "ddpm_forward_cond: cond_map given to a plan built without the cond_enc head");
@@ -1420,14 +1420,14 @@ extern "C" int mcedm_ddpm_vp_sampler_workspace_bytes(const mcedm_ddpm_plan* plan
 extern "C" int mcedm_ddpm_vp_heun_sample(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
                                          const float* cond, const float* init_noise, const double* step_noise, double* out,
                                          int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return dvp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B,
                          stream);
 }
 extern "C" int mcedm_ddpm_vp_heun_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
                                              const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
                                              int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return dvp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B,
                          stream);
@@ -1439,7 +1439,7 @@ extern "C" int mcedm_ddpm_vp_heun_sample_guided(const mcedm_ddpm_plan* plan, con
                                                 const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
                                                 const double* step_noise, const uint64_t* rng_seed, double* out, int return_last,
                                                 void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return dvp_sample_impl(plan, packed, sp, gd, cond, init_noise, step_noise, rng_seed, out, return_last, workspace, workspace_bytes, B,
                          stream);
 }
@@ -1451,7 +1451,7 @@ extern "C" int mcedm_ddpm_cond_ddim_sample(const mcedm_ddpm_plan* plan, const vo
                                            const float* cond, const float* init_noise, const float* eta_noise, float* xs_out,
                                            float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
                                            void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return dcond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
                          workspace_bytes, B, stream);
 }
@@ -1459,7 +1459,7 @@ extern "C" int mcedm_ddpm_cond_ddim_sample_rng(const mcedm_ddpm_plan* plan, cons
                                                const float* cond, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
                                                float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B,
                                                void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return dcond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace,
                          workspace_bytes, B, stream);
@@ -1471,7 +1471,7 @@ extern "C" int mcedm_ddpm_cond_ddim_sample_guided(const mcedm_ddpm_plan* plan, c
                                                   const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
                                                   const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
                                                   int return_last, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return dcond_ddim_impl(plan, packed, sp, gd, cond, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, workspace,
                          workspace_bytes, B, stream);
 }
@@ -1551,7 +1551,7 @@ static int dedm_sample_impl(const mcedm_ddpm_plan* plan, const void* packed, con
 
 extern "C" int mcedm_ddpm_forward_cat(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float t,
                                       float* out, void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && out && workspace, "ddpm_forward_cat: null argument");
   int rc;
   if ((rc = cat_check("ddpm_forward_cat", *plan, cond, B))) return rc;
@@ -1563,7 +1563,7 @@ extern "C" int mcedm_ddpm_forward_cat(const mcedm_ddpm_plan* plan, const void* p
 extern "C" int mcedm_ddpm_edm_denoise(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond, float sigma,
                                       float c_noise, double w, double sigma_data, float* D_out, float* F_out, void* workspace,
                                       size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && D_out && workspace, "ddpm_edm_denoise: null argument");
   MCEDM_REQUIRE(sigma > 0.f && sigma_data > 0.0, "ddpm_edm_denoise: sigma %g and sigma_data %g must be positive", (double)sigma, sigma_data);
   int rc;
@@ -1580,7 +1580,7 @@ extern "C" int mcedm_ddpm_edm_heun_sample(const mcedm_ddpm_plan* plan, const voi
                                           double sigma_data, const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
                                           const double* step_noise, double* out, int return_last, void* workspace,
                                           size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return dedm_sample_impl(plan, packed, sp, sigma_data, gd, cond, init_noise, step_noise, nullptr, out, return_last, workspace,
                           workspace_bytes, B, stream);
 }
@@ -1588,7 +1588,7 @@ extern "C" int mcedm_ddpm_edm_heun_sample_rng(const mcedm_ddpm_plan* plan, const
                                               double sigma_data, const mcedm_guidance_desc* gd, const float* cond,
                                               const float* init_noise, const uint64_t* rng_seed, double* out, int return_last,
                                               void* workspace, size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "ddpm_edm_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return dedm_sample_impl(plan, packed, sp, sigma_data, gd, cond, init_noise, nullptr, rng_seed, out, return_last, workspace,
                           workspace_bytes, B, stream);
@@ -1629,7 +1629,7 @@ extern "C" int mcedm_ddpm_workspace_bytes_t(const mcedm_ddpm_plan* plan, int B, 
 extern "C" int mcedm_ddpm_forward_t(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* x_self_cond,
                                     const float* cond_map, const float* cond_cat, const float* t, float* out, void* workspace,
                                     size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && t && out && workspace, "ddpm_forward_t: null argument");
   MCEDM_REQUIRE(B > 0 && B <= 65535, "ddpm_forward_t: batch %d outside [1, 65535]", B);
   MCEDM_REQUIRE(!x_self_cond || plan->desc.self_cond, "ddpm_forward_t: the network was built without self-conditioning channels");
@@ -1648,7 +1648,7 @@ extern "C" int mcedm_ddpm_forward_t(const mcedm_ddpm_plan* plan, const void* pac
 extern "C" int mcedm_ddpm_edm_denoise_t(const mcedm_ddpm_plan* plan, const void* packed, const float* x, const float* cond,
                                         const float* sigma, double sigma_data, float* D_out, float* F_out, void* workspace,
                                         size_t workspace_bytes, int B, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && sigma && D_out && workspace, "ddpm_edm_denoise_t: null argument");
   MCEDM_REQUIRE(B > 0 && B <= 65535, "ddpm_edm_denoise_t: batch %d outside [1, 65535]", B);
   MCEDM_REQUIRE(sigma_data > 0.0, "ddpm_edm_denoise_t: sigma_data %g must be positive", sigma_data);

@@ -659,22 +659,9 @@ static int launch_attention_lds(const float* qkv, float* out, int B, int heads, 
     MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)attention_lds_kernel<KH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
     attr_set[dev].store(true, std::memory_order_release);
   }
-  static int xmap = -1;                                    // MCEDM_ATTN_XCD=0: workgroups in dispatch order (A/B runs)
-  if (xmap < 0) { const char* e = getenv("MCEDM_ATTN_XCD"); xmap = e ? atoi(e) : 1; }
-  hipLaunchKernelGGL(attention_lds_kernel<KH>, dim3(ceil_div(T, 128), B * heads), dim3(256 * KH), lds_bytes, stream, qkv, out, T, xmap);
+  // MCEDM_ATTN_XCD=0: workgroups in dispatch order (A/B runs)
+  hipLaunchKernelGGL(attention_lds_kernel<KH>, dim3(ceil_div(T, 128), B * heads), dim3(256 * KH), lds_bytes, stream, qkv, out, T, attn_xcd_env());
   return MCEDM_OK;
-}
-
-static int attn_split_env() {          // MCEDM_ATTN_SPLIT=0: the one-wave-per-query-tile kernel everywhere (A/B runs)
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_ATTN_SPLIT"); env = e ? atoi(e) : 1; }
-  return env;
-}
-
-static int attn_lds_min_env() {        // MCEDM_ATTN_LDS_MIN: shortest sequence that takes the LDS-staged kernel (A/B runs)
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_ATTN_LDS_MIN"); env = e ? atoi(e) : 512; }
-  return env;
 }
 
 int launch_attention(const float* qkv, float* out, int B, int heads, int T, hipStream_t stream) {
@@ -687,13 +674,14 @@ int launch_attention(const float* qkv, float* out, int B, int heads, int T, hipS
   // the split kernel would: 91 vs 45 us at B = 8 -- accepted for the batch-sharding invariance).  MCEDM_ATTN_SPLIT=2: split
   // kernel for every T, 3: the four-wave variant of the LDS kernel (A/B switches)
   const bool aligned = (T % 4 == 0) && ((reinterpret_cast<size_t>(qkv) & 15) == 0);
-  const int mode = attn_split_env();
-  if (mode >= 1 && mode != 2 && T >= attn_lds_min_env() && aligned) {
+  static const int mode = env_int("MCEDM_ATTN_SPLIT", 1);         // 0: the one-wave-per-query-tile kernel everywhere (A/B runs)
+  static const int lds_min = env_int("MCEDM_ATTN_LDS_MIN", 512);  // shortest sequence that takes the LDS-staged kernel (A/B runs)
+  if (mode >= 1 && mode != 2 && T >= lds_min && aligned) {
     const int rc = mode == 3 ? launch_attention_lds<1>(qkv, out, B, heads, T, stream) : launch_attention_lds<2>(qkv, out, B, heads, T, stream);
     if (rc != MCEDM_OK) return rc;
   }
-  else if (attn_split_env() && T >= 256) hipLaunchKernelGGL(attention_split_kernel<4>, grid, dim3(256), 0, stream, qkv, out, T);
-  else if (attn_split_env() && T >= 128) hipLaunchKernelGGL(attention_split_kernel<2>, grid, dim3(128), 0, stream, qkv, out, T);
+  else if (mode && T >= 256) hipLaunchKernelGGL(attention_split_kernel<4>, grid, dim3(256), 0, stream, qkv, out, T);
+  else if (mode && T >= 128) hipLaunchKernelGGL(attention_split_kernel<2>, grid, dim3(128), 0, stream, qkv, out, T);
   else hipLaunchKernelGGL(attention_kernel, grid, dim3(64), 0, stream, qkv, out, T);
   MCEDM_LAUNCH_CHECK("attention_kernel");
   return MCEDM_OK;

@@ -371,55 +371,18 @@ extern "C" int mcedm_op_attention_bwd(const float* qkv, const float* a, const fl
   return launch_attention_bwd(qkv, a, da, dqkv, lse_scratch, B, heads, T, (hipStream_t)stream);
 }
 
-extern "C" int mcedm_op_set_conv8(int enable) {
-  set_conv8(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv_wino(int enable) {
-  set_conv_wino(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv_wino1(int enable) {
-  set_conv_wino1(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv_wino_fold(int enable) {
-  set_conv_wino_fold(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv_wino_upz(int enable) {
-  set_conv_wino_upz(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv_wino_split(int enable) {
-  set_conv_wino_split(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv1x1_reg(int enable) {
-  set_conv1x1_reg(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_wgrad_wino(int enable) {
-  set_wgrad_wino(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_conv_resident(int enable) {
-  set_conv_resident(enable);
-  return MCEDM_OK;
-}
-
-extern "C" int mcedm_op_set_attn_fused(int enable) {
-  set_attn_fused(enable);
-  return MCEDM_OK;
-}
+// the process-wide level of the kernel switches (switches.hpp): any integer, < 0 = not set
+static int set_switch(KernelVariant which, int value) { set_kernel_switch(which, value); return MCEDM_OK; }
+extern "C" int mcedm_op_set_conv8(int enable) { return set_switch(KV_CONV8, enable); }
+extern "C" int mcedm_op_set_conv_wino(int enable) { return set_switch(KV_CONV_WINO, enable); }
+extern "C" int mcedm_op_set_conv_wino1(int enable) { return set_switch(KV_CONV_WINO1, enable); }
+extern "C" int mcedm_op_set_conv_wino_fold(int enable) { return set_switch(KV_CONV_WINO_FOLD, enable); }
+extern "C" int mcedm_op_set_conv_wino_upz(int enable) { return set_switch(KV_CONV_WINO_UPZ, enable); }
+extern "C" int mcedm_op_set_conv_wino_split(int enable) { return set_switch(KV_CONV_WINO_SPLIT, enable); }
+extern "C" int mcedm_op_set_conv1x1_reg(int enable) { return set_switch(KV_CONV1X1_REG, enable); }
+extern "C" int mcedm_op_set_wgrad_wino(int enable) { return set_switch(KV_WGRAD_WINO, enable); }
+extern "C" int mcedm_op_set_conv_resident(int enable) { return set_switch(KV_CONV_RESIDENT, enable); }
+extern "C" int mcedm_op_set_attn_fused(int enable) { return set_switch(KV_ATTN_FUSED, enable); }
 
 extern "C" int mcedm_op_set_conv_debug(unsigned long long* buf) {
   set_conv_debug(buf);

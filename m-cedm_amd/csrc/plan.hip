@@ -344,7 +344,7 @@ static void pack_norm(const NormP& n, const float* const* params, float* pk, Cop
 }  // namespace mcedm
 
 extern "C" int mcedm_unet_pack_weights(const mcedm_plan* plan, const float* const* params, void* packed, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && params && packed, "pack_weights: null argument");
   const mcedm_plan& P = *plan;
   for (size_t i = 0; i < P.params.size(); ++i)
@@ -781,7 +781,7 @@ int denoise_impl(const AdmNet& net, const float* x, const float* dx, const float
 }  // namespace mcedm
 
 extern "C" int mcedm_unet_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, int training, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "workspace_bytes: null argument");
   AdmNet net;
   const int rc = adm_sizes(*plan, B, H, W, training, B, &net, bytes);
@@ -793,7 +793,7 @@ extern "C" int mcedm_unet_forward_dx(const mcedm_plan* plan, const void* packed,
                                      const float* x_scale, const float* noise_labels, int n_noise, float* out,
                                      void* workspace, size_t workspace_bytes, int B, int H, int W, int training,
                                      void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && noise_labels && out && workspace, "unet_forward: null argument");
   MCEDM_REQUIRE(dx == nullptr || plan->desc.dx_mode != MCEDM_DX_NONE, "unet_forward: dx given to a plan without dx_cond");
   AdmNet net;
@@ -814,7 +814,7 @@ extern "C" int mcedm_unet_forward(const mcedm_plan* plan, const void* packed, co
                                   const float* x_scale, const float* noise_labels, int n_noise, float* out,
                                   void* workspace, size_t workspace_bytes, int B, int H, int W, int training,
                                   void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return mcedm_unet_forward_dx(plan, packed, x, nullptr, cond, x_scale, noise_labels, n_noise, out, workspace, workspace_bytes, B, H,
                                W, training, stream);
 }
@@ -823,7 +823,7 @@ extern "C" int mcedm_edm_denoise_dx(const mcedm_plan* plan, const void* packed, 
                                     int n_sigma, const float* cond, float* D_out, float* F_out, void* workspace,
                                     size_t workspace_bytes, int B, int H, int W, int training, double sigma_data,
                                     void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && packed && x && sigma && D_out && workspace, "edm_denoise: null argument");
   MCEDM_REQUIRE(dx == nullptr || plan->desc.dx_mode != MCEDM_DX_NONE, "edm_denoise: dx given to a plan without dx_cond");
   AdmNet net;
@@ -835,7 +835,7 @@ extern "C" int mcedm_edm_denoise(const mcedm_plan* plan, const void* packed, con
                                  int n_sigma, const float* cond, float* D_out, float* F_out, void* workspace,
                                  size_t workspace_bytes, int B, int H, int W, int training, double sigma_data,
                                  void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return mcedm_edm_denoise_dx(plan, packed, x, nullptr, sigma, n_sigma, cond, D_out, F_out, workspace, workspace_bytes, B, H, W,
                               training, sigma_data, stream);
 }

@@ -92,7 +92,7 @@ int plan_param_info(const PlanT* plan, const char* who, int index, const char** 
 
 template <class PlanT>
 int plan_packed_bytes(const PlanT* plan, const char* who, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "%s: null argument", who);
   *bytes = plan->packed_floats * sizeof(float);
   return MCEDM_OK;

@@ -36,7 +36,7 @@ static SamplerBufs sampler_bufs(const mcedm_plan& P, int B, int H, int W) {
 }  // namespace mcedm
 
 extern "C" int mcedm_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "sampler_workspace_bytes: null argument");
   const int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, bytes);
   if (rc == MCEDM_OK) *bytes += sampler_bufs(*plan, B, H, W).total;
@@ -107,7 +107,7 @@ extern "C" int mcedm_heun_sample(const mcedm_plan* plan, const void* packed, con
                                  const float* cond, const float* mask, const float* init_noise,
                                  const double* step_noise, double* out, int return_last, void* workspace,
                                  size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, step_noise, out, return_last, workspace, workspace_bytes,
                           B, H, W, nullptr, stream, nullptr, nullptr);
 }
@@ -119,7 +119,7 @@ extern "C" int mcedm_heun_sample_rng(const mcedm_plan* plan, const void* packed,
                                      const float* cond, const float* mask, const float* init_noise, const uint64_t* rng_seed,
                                      double* out, int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
                                      void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return heun_sample_impl(plan, packed, sp, cond, mask, init_noise, nullptr, out, return_last, workspace, workspace_bytes,
                           B, H, W, nullptr, stream, nullptr, rng_seed);
@@ -142,7 +142,7 @@ extern "C" int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* pack
                                         const mcedm_guidance_desc* gd, const float* cond, const float* mask,
                                         const float* init_noise, const double* step_noise, double* out, int return_last,
                                         void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return heun_guided(plan, packed, sp, gd, cond, mask, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B,
                      H, W, stream);
 }
@@ -151,7 +151,7 @@ extern "C" int mcedm_heun_sample_guided_rng(const mcedm_plan* plan, const void* 
                                             const mcedm_guidance_desc* gd, const float* cond, const float* mask,
                                             const float* init_noise, const uint64_t* rng_seed, double* out, int return_last,
                                             void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_guided_rng: rng_seed (a 64-bit seed in device memory) is null");
   return heun_guided(plan, packed, sp, gd, cond, mask, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B,
                      H, W, stream);
@@ -175,7 +175,7 @@ extern "C" int mcedm_heun_sample_dxcond(const mcedm_plan* plan, const void* pack
                                         const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
                                         const float* init_noise, const double* step_noise, double* out, int return_last,
                                         void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return heun_dxcond(plan, packed, sp, dxc, gd, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes, B,
                      H, W, stream);
 }
@@ -184,7 +184,7 @@ extern "C" int mcedm_heun_sample_dxcond_rng(const mcedm_plan* plan, const void* 
                                             const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
                                             const float* init_noise, const uint64_t* rng_seed, double* out, int return_last,
                                             void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "heun_sample_dxcond_rng: rng_seed (a 64-bit seed in device memory) is null");
   return heun_dxcond(plan, packed, sp, dxc, gd, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes, B,
                      H, W, stream);
@@ -218,7 +218,7 @@ static int vp_denoise(const AdmNet& net, const float* x32, const float* condp, d
 }  // namespace mcedm
 
 extern "C" int mcedm_vp_sampler_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "vp_sampler_workspace_bytes: null argument");
   const int rc = mcedm_unet_workspace_bytes(plan, B, H, W, 0, bytes);
   if (rc == MCEDM_OK) *bytes += vp_bufs(*plan, B, H, W).total;
@@ -267,7 +267,7 @@ static int vp_sample_impl(const mcedm_plan* plan, const void* packed, const mced
 extern "C" int mcedm_vp_heun_sample(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp, const float* cond,
                                     const float* init_noise, const double* step_noise, double* out, int return_last,
                                     void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return vp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, step_noise, nullptr, out, return_last, workspace, workspace_bytes,
                         B, H, W, stream);
 }
@@ -276,14 +276,14 @@ extern "C" int mcedm_vp_heun_sample_rng(const mcedm_plan* plan, const void* pack
                                         const float* cond, const float* init_noise, const uint64_t* rng_seed, double* out,
                                         int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
                                         void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "vp_heun_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return vp_sample_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, out, return_last, workspace, workspace_bytes,
                         B, H, W, stream);
 }
 
 extern "C" int mcedm_vp_guided_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "vp_guided_workspace_bytes: null argument");
   AdmNet net;                            // one noise label for the whole batch, as the sampler lays its forward out: exact
   const int rc = adm_sizes(*plan, B, H, W, 0, 1, &net, bytes);
@@ -295,7 +295,7 @@ extern "C" int mcedm_vp_heun_sample_guided(const mcedm_plan* plan, const void* p
                                            const mcedm_guidance_desc* gd, const float* cond, const float* init_noise,
                                            const double* step_noise, const uint64_t* rng_seed, double* out, int return_last,
                                            void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return vp_sample_impl(plan, packed, sp, gd, cond, init_noise, step_noise, rng_seed, out, return_last, workspace, workspace_bytes, B,
                         H, W, stream);
 }
@@ -319,7 +319,7 @@ static CondDdimBufs cond_ddim_bufs(const mcedm_plan& P, int B, int H, int W, boo
 }  // namespace mcedm
 
 extern "C" int mcedm_cond_ddim_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "cond_ddim_workspace_bytes: null argument");
   AdmNet net;                            // one noise label for the whole batch, as the sampler lays its forward out
   const int rc = adm_sizes(*plan, B, H, W, 0, 1, &net, bytes);
@@ -381,7 +381,7 @@ extern "C" int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed
                                       const float* init_noise, const float* eta_noise, float* xs_out, float* x0_out,
                                       int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
                                       void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return cond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, eta_noise, nullptr, xs_out, x0_out, return_last, workspace,
                         workspace_bytes, B, H, W, stream);
 }
@@ -390,14 +390,14 @@ extern "C" int mcedm_cond_ddim_sample_rng(const mcedm_plan* plan, const void* pa
                                           const float* cond, const float* init_noise, const uint64_t* rng_seed, float* xs_out,
                                           float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B, int H,
                                           int W, void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(rng_seed != nullptr, "cond_ddim_sample_rng: rng_seed (a 64-bit seed in device memory) is null");
   return cond_ddim_impl(plan, packed, sp, nullptr, cond, init_noise, nullptr, rng_seed, xs_out, x0_out, return_last, workspace,
                         workspace_bytes, B, H, W, stream);
 }
 
 extern "C" int mcedm_cond_ddim_guided_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   MCEDM_REQUIRE(plan && bytes, "cond_ddim_guided_workspace_bytes: null argument");
   AdmNet net;
   const int rc = adm_sizes(*plan, B, H, W, 0, 1, &net, bytes);
@@ -410,7 +410,7 @@ extern "C" int mcedm_cond_ddim_sample_guided(const mcedm_plan* plan, const void*
                                              const float* eta_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,
                                              int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
                                              void* stream) {
-  VariantScope variant_scope__(plan ? &plan->variants : nullptr);
+  VariantScope variant_scope__(plan);
   return cond_ddim_impl(plan, packed, sp, gd, cond, init_noise, eta_noise, rng_seed, xs_out, x0_out, return_last, workspace,
                         workspace_bytes, B, H, W, stream);
 }

@@ -38,8 +38,7 @@ struct WgCfg {
 bool wgrad_thin_applicable(const WgradArgs& a, int taps, int qkv_heads);
 int launch_wgrad_thin(const WgradArgs& a, float* dw, float* db, hipStream_t s);
 static bool wgrad_thin_enabled() {                       // MCEDM_WGRAD_THIN=0: the MFMA block kernel for these shapes too (A/B runs)
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WGRAD_THIN"); env = e ? atoi(e) : 1; }
+  static const int env = env_int("MCEDM_WGRAD_THIN", 1);
   return env != 0;
 }
 

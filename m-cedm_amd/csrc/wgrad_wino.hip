@@ -747,17 +747,10 @@ __global__ __launch_bounds__(1024) void wgrad_wino_finish_kernel(const double* _
   wgw_taps(m, tid, cl, co, ci, Cin, dw);
 }
 
-static int g_wgw = -1;       // -1: default (env MCEDM_WGRAD_WINO, else on); 0 / 1: forced by mcedm_op_set_wgrad_wino
-void set_wgrad_wino(int enable) { g_wgw = enable; }
-static int wgw_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WGRAD_WINO"); env = e ? atoi(e) : 1; }
-  return variant_choice(KV_WGRAD_WINO, g_wgw, env);
-}
+static int wgw_env() { return kernel_switch(KV_WGRAD_WINO); }
 
 static int wgw64_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WGRAD_WINO64"); env = e ? atoi(e) : 1; }
+  static const int env = env_int("MCEDM_WGRAD_WINO64", 1);
   return env;
 }
 
@@ -815,9 +808,8 @@ static int wgw_form(const WgradArgs& a, int taps, int qkv_heads) {
   // the 64-channel form pays a fixed 16 x Cout x Cin floats per split (store + reduction): with fewer than 4 stages of 8 tiles
   // per split the direct kernel is as fast or faster (64 -> 64 at 32^2, B = 32: 4 stages, 47 against 46 us; tools/wgrad_wino_ab.py)
   // (a switch FORCED on -- mcedm_op_set_wgrad_wino(1) or the plan's variant -- serves every legal shape: the parity tests' small cases)
-  if (form == 2 && variant_choice(KV_WGRAD_WINO, g_wgw, -1) != 1) {
-    static int min_per = -1;
-    if (min_per < 0) { const char* e = getenv("MCEDM_WGRAD_WINO64_MIN"); min_per = e ? atoi(e) : 4; }
+  if (form == 2 && kernel_switch_forced(KV_WGRAD_WINO) != 1) {
+    static const int min_per = env_int("MCEDM_WGRAD_WINO64_MIN", 4);
     const long long total = (long long)a.B * (a.H / 2) * (a.W / 16);
     if (total < (long long)min_per * wgw_form_nsplit(2, a.Cout, Cin)) return 0;
   }
@@ -887,8 +879,7 @@ int launch_wgrad_wino(const WgradArgs& a, const float* x, float* dw, float* db, 
 
 // ---- the 1x1 GEMM form
 static int wgg_env() {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("MCEDM_WGRAD_GEMM1"); env = e ? atoi(e) : 1; }
+  static const int env = env_int("MCEDM_WGRAD_GEMM1", 1);
   return env;
 }
 static bool wgg_shape_ok(int Cout, int Cin, int taps) { return taps == 1 && Cout > 0 && Cin > 0 && Cout % GW_CB == 0 && Cin % GW_CB == 0; }

@@ -1488,6 +1488,8 @@ def _bind_ops():
               "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
               "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn", "mcedm_op_conv_wino_split", "mcedm_op_conv_wino_split_sums"):
         getattr(lib, n).restype = C.c_int
+    for n in VARIANTS:
+        getattr(lib, "mcedm_op_set_" + n).argtypes = [i32]
     _OPS_BOUND = True
     return lib
 
@@ -1525,80 +1527,40 @@ def set_conv_tile(mt: int = 0, ph: int = 0, pw: int = 0) -> None:
     lib = _bind_ops()
     lib.mcedm_op_set_conv_tile.argtypes = [C.c_int, C.c_int, C.c_int]
     check(lib.mcedm_op_set_conv_tile(mt, ph, pw), "set_conv_tile")
-def set_conv8(enable: int = -1) -> None:
-    """Select the experimental 8-wave conv kernel (1 / 0; -1 = default)."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv8.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv8(int(enable)), "set_conv8")
 
 
-def set_conv_wino(enable: int = -1) -> None:
-    """Winograd F(2x2, 3x3) kernels in the network paths: 1 / 0; -1 = default (on).  Set before the workspace is laid out."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv_wino.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv_wino(int(enable)), "set_conv_wino")
-
-
-def set_conv_wino1(enable: int = -1) -> None:
-    """Which Winograd kernel serves the 128-channel shapes: 1 = one wave per SIMD (conv_wino1.hip), 0 = two (conv_wino.hip);
-    -1 = default (0: the one-wave kernel is 6-9 % slower).  Bit-identical results either way."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv_wino1.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv_wino1(int(enable)), "set_conv_wino1")
-
-
-def set_conv1x1_reg(enable: int = -1) -> None:
-    """Register-direct GEMM kernel for un-transformed 1x1 convs (conv1x1_reg.hip): 1 / 0 (conv_mfma_kernel); -1 = default (on)."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv1x1_reg.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv1x1_reg(int(enable)), "set_conv1x1_reg")
-
-
-def set_conv_wino_fold(enable: int = -1) -> None:
-    """The Winograd conv1 of an un-resampled decoder block computes the block's 1x1 skip projection in its epilogue (conv_wino.hip,
-    the SKIP variant): 1 / 0 (a conv1x1_reg_kernel launch plus a residual read); -1 = default (on).  Same bits either way."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv_wino_fold.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv_wino_fold(int(enable)), "set_conv_wino_fold")
-
-
-def set_conv_wino_upz(enable: int = -1) -> None:
-    """The up-sampling Winograd convs skip the seven positions whose transformed input is exactly zero and stage their input at source
+# The process-wide form of the kernel switches, one set_<name>(enable=-1) each over mcedm_op_set_<name>: any integer, < 0 = not set (the
+# plan's own choice aside, the environment decides).  Rows in the order of VARIANTS and of the table in csrc/switches.hpp: (name, docstring)
+_SWITCH_SETTERS = (
+    ("conv_wino", """Winograd F(2x2, 3x3) kernels in the network paths: 1 / 0; -1 = default (on).  Set before the workspace is laid out."""),
+    ("conv_wino1", """Which Winograd kernel serves the 128-channel shapes: 1 = one wave per SIMD (conv_wino1.hip), 0 = two (conv_wino.hip);
+    -1 = default (0: the one-wave kernel is 6-9 % slower).  Bit-identical results either way."""),
+    ("conv_resident", """Input-resident conv kernels for <= 32 x 32 images: 1 / 0; -1 = default (on)."""),
+    ("conv8", """Select the experimental 8-wave conv kernel (1 / 0; -1 = default)."""),
+    ("attn_fused", """Single-launch attention block at 8 x 8 x 64 (inference): 1 / 0; -1 = default (on)."""),
+    ("wgrad_wino", """Winograd F(3x3, 2x2) weight-gradient kernel (wgrad_wino.hip): 1 / 0 (direct split-K kernel everywhere); -1 = default (on)."""),
+    ("conv1x1_reg", """Register-direct GEMM kernel for un-transformed 1x1 convs (conv1x1_reg.hip): 1 / 0 (conv_mfma_kernel); -1 = default (on)."""),
+    ("conv_wino_fold", """The Winograd conv1 of an un-resampled decoder block computes the block's 1x1 skip projection in its epilogue (conv_wino.hip,
+    the SKIP variant): 1 / 0 (a conv1x1_reg_kernel launch plus a residual read); -1 = default (on).  Same bits either way."""),
+    ("conv_wino_upz", """The up-sampling Winograd convs skip the seven positions whose transformed input is exactly zero and stage their input at source
     resolution (conv_wino.hip, WinoUp): 1 / 0 (all sixteen positions); 2 = the positions alone, on the sixteen-position kernel's
-    staging (A/B runs); -1 = default (on).  Same bits in every form."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv_wino_upz.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv_wino_upz(int(enable)), "set_conv_wino_upz")
-
-
-def set_conv_wino_split(enable: int = -1) -> None:
-    """The un-resampled 3x3 convs of images below 32 x 32 (the 16 x 16 level) run on the Winograd kernel with one 32-channel block per
+    staging (A/B runs); -1 = default (on).  Same bits in every form."""),
+    ("conv_wino_split", """The un-resampled 3x3 convs of images below 32 x 32 (the 16 x 16 level) run on the Winograd kernel with one 32-channel block per
     workgroup and the sixteen positions split over its waves (conv_wino.hip, WinoSplitCfg): 1 / 0 (the input-resident / tiled
-    kernels); -1 = default (on).  An explicit set_conv_resident / set_conv_tile wins."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv_wino_split.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv_wino_split(int(enable)), "set_conv_wino_split")
+    kernels); -1 = default (on).  An explicit set_conv_resident / set_conv_tile wins."""),
+)
 
 
-def set_wgrad_wino(enable: int = -1) -> None:
-    """Winograd F(3x3, 2x2) weight-gradient kernel (wgrad_wino.hip): 1 / 0 (direct split-K kernel everywhere); -1 = default (on)."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_wgrad_wino.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_wgrad_wino(int(enable)), "set_wgrad_wino")
+def _switch_setter(name: str, doc: str):
+    def setter(enable: int = -1) -> None:
+        check(getattr(_bind_ops(), "mcedm_op_set_" + name)(int(enable)), "set_" + name)
+    setter.__name__ = setter.__qualname__ = "set_" + name
+    setter.__doc__ = doc
+    return setter
 
 
-def set_conv_resident(enable: int = -1) -> None:
-    """Input-resident conv kernels for <= 32 x 32 images: 1 / 0; -1 = default (on)."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_conv_resident.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_conv_resident(int(enable)), "set_conv_resident")
-
-
-def set_attn_fused(enable: int = -1) -> None:
-    """Single-launch attention block at 8 x 8 x 64 (inference): 1 / 0; -1 = default (on)."""
-    lib = _bind_ops()
-    lib.mcedm_op_set_attn_fused.argtypes = [C.c_int]
-    check(lib.mcedm_op_set_attn_fused(int(enable)), "set_attn_fused")
+for _name, _doc in _SWITCH_SETTERS:
+    globals()["set_" + _name] = _switch_setter(_name, _doc)
 
 
 def set_conv_debug(buf: Optional[torch.Tensor] = None) -> None:
