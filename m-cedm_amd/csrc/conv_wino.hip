@@ -21,6 +21,9 @@
 //     turns (channel k, patch t, row half) of it into 8 Winograd-domain values (6 ds_read_b64, 16 adds, 8 ds_write_b32).
 //     Both LDS stages are double-buffered, a stage is two chunks, ONE barrier per stage, and all of this side work is
 //     issued in slices between the MFMAs of the same wave (see the K loop).
+//     A trip of the loop is TWO stages, buffer parity 0 and 1 as compile-time constants: every LDS address is a per-lane register
+//     computed once per workgroup plus an immediate offset, the weights come through one buffer descriptor with the chunk in the
+//     scalar offset -- no address arithmetic between the MFMAs (odd stage counts per tile: the one-stage form, WinoLoop1).
 //   * epilogue: the output transform is register-local over nu; over xi the two halves exchange one 2 x 32-register
 //     partial through LDS; then bias, residual, stores (8-byte, two pixels of a row) and the fused GroupNorm statistics.
 //   * up-sampled input (UP): by default the zero-position variant WinoUp (conv_wino.hpp) -- 9 of the 16 positions, the raw tile
@@ -183,11 +186,45 @@ struct SkipFold<C, true> {
   }
 };
 
+// LDS accesses of the K loop by byte address: a per-lane base that sits in a register through the loop plus an offset that is a
+// compile-time constant wherever the buffer parity is one (the two-stage trip): hipcc then puts it into the instruction's 16-bit
+// offset field instead of adding it to the lane index in front of every group of accesses.
+template <class T>
+__device__ __forceinline__ T lds_get(unsigned base, int off) {
+  return *reinterpret_cast<const __attribute__((address_space(3))) T*>(base + (unsigned)off);
+}
+template <class T>
+__device__ __forceinline__ void lds_put(unsigned base, int off, T v) {
+  *reinterpret_cast<__attribute__((address_space(3))) T*>(base + (unsigned)off) = v;
+}
+// The input transform's packed fp32 operations, written as instructions.  Behind an MFMA hipcc rewrites a v_pk_add / v_pk_fma_f32 into two
+// scalar instructions after register allocation (it takes the matrix instruction's shadow for free issue slots); on gfx950 vector and
+// fp32 matrix instructions do not overlap, so the rewrite doubles what the operation costs -- fifteen of the stage's sixteen were split.
+// Same operations on the same values: a + (-b) for a - b, and c1 + c2 | c1 - c2 for the fma with (1, -1), whose product is exact.
+__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
+  f32x2 d;
+  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
+  f32x2 d;
+  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+// (a.y + b.x, a.y - b.x)
+__device__ __forceinline__ f32x2 pk_hi_pm_lo(f32x2 a, f32x2 b) {
+  f32x2 d;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+// the largest immediate offset of an LDS access family (bytes; the last byte of the access) must fit the instruction's field
+#define WINO_LDS_IMM_OK(floats, bytes) static_assert(4 * (floats) + (bytes) <= 65536, "LDS offset beyond the 16-bit immediate field")
+
 // UP: the conv input is the nearest-neighbour 2x up-sampling of the (activated) source (adm_blocks.py:69-73)
 // ACT = false: the launch has no activation (p.act == 0: the data-gradient convs of training, whose input is a raw gradient): the
 // plain variant's branch-free "evaluate SiLU and select" is compiled out -- ~20 of the ~58 vector instructions per chunk and lane,
 // every one of them matrix time (round 5; the forward convs of inference all carry the activation)
-// Tag: empty, or WinoUp<SRC> (conv_wino.hpp): the zero-position variant of the up-sampling kernel
+// Tag: empty, or WinoUp<SRC> (conv_wino.hpp): the zero-position variant of the up-sampling kernel; WinoLoop1 in front: one stage per trip
 template <class C, bool UP, bool ACT = true, class... Tag>
 __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(const ConvArgs p, int tiles_x, int tiles_img, int nch, int mblocks,
                                                                           int per, int mode) {
@@ -195,14 +232,13 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   constexpr bool SKIP = C::SKIP;                                  // WinoSkipCfg: the epilogue computes the residual (the skip projection)
   constexpr bool UPZ = WinoUpTraits<Tag...>::UPZ;                 // WinoUp: nothing is done for the positions whose V is exactly +0
   constexpr bool UPS = WinoUpTraits<Tag...>::UPS;                 // ... and the raw tile is staged and transformed at source resolution
+  constexpr bool PAIR = !WinoUpTraits<Tag...>::LOOP1;             // two stages per trip, immediate LDS offsets, buffer descriptors (WinoLoop1: not)
   static_assert(!UPS || UPZ, "source-resolution staging is part of the zero-position variant");
   static_assert(!UPZ || (UP && !SKIP), "the zero positions belong to the up-sampled input");
   constexpr bool SPLIT = C::SPLIT;                                // WinoSplitCfg: one 32-channel block per workgroup, the positions split over the waves
-  static_assert(!SPLIT || (!UP && !SKIP && sizeof...(Tag) == 0 && MB == 4 && WSC == 2), "the split variant: plain input, WinoCfg<4>'s input path");
+  static_assert(!SPLIT || (!UP && !SKIP && !UPZ && !WinoUpTraits<Tag...>::BROWS && MB == 4 && WSC == 2), "the split variant: plain input, WinoCfg<4>'s input path");
   extern __shared__ float lds[];
   const int Cin = p.Ca + p.Cb;
-  float* const vbuf = lds;
-  float* const rbuf = lds + 2 * VBUF;
   Coef* const cfl = reinterpret_cast<Coef*>(lds + C::LDS_ROWS_OFF);
   float* const xch = lds + C::LDS_ROWS_OFF + 4 * Cin;            // epilogue exchange (one 16-register round), then the records
   float* const red = xch + C::XCH_FLOATS;
@@ -212,6 +248,9 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mb = wave % MB, hf = wave / MB;
+  // the K loop's LDS accesses: byte addresses (lds_get / lds_put); RB0: where rbuf starts
+  const unsigned lds0 = (unsigned)reinterpret_cast<size_t>((__attribute__((address_space(3))) float*)lds);
+  constexpr int RB0 = 4 * 2 * VBUF;
   if (p.dbg && tid == 0) { p.dbg[blockIdx.x * 16 + 0] = __builtin_amdgcn_s_memrealtime(); p.dbg[blockIdx.x * 16 + 4] = per; }
   // A workgroup takes `per` consecutive pixel tiles of ONE sample (the launcher picks a divisor of the tiles per image) and
   // runs their stages as one stream: the pipeline below never drains between tiles, only the accumulators are written out.
@@ -250,15 +289,24 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   //   UPS: element `lane` of the 6 x 10 source patch, one dword load.
   constexpr int NR = UPS ? 1 : UP ? RSUB : 4, NG = UPS ? 1 : UP ? RSUB : 1;   // raw registers / geometry entries per lane and channel
   unsigned roff[NG], rkeepL[NG], rkeepC[NG];
-  int lofs[4];                                                      // plain input: where the quad's four elements go in the LDS patch
+  // where this lane commits in the raw tile's LDS plane of the wave's first channel (byte addresses, opaque to the compiler: they stay
+  // in these registers through the loop).  Plain input: the quad's four elements; up-sampled input: element `lane`
+  constexpr int NCM = UP ? 1 : 4;
+  unsigned cm_a[NCM];
   if (!UP) {
     const int r = lane / 6, qd = lane % 6;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int col = 4 * qd + e - 3;                              // column inside the 18-wide patch; -3 .. -1 and 18 .. 20 are not part of it
-      lofs[e] = (lane < 60 && col >= 0 && col < RPITCH) ? r * RPITCH + col : RROWS * RPITCH + lane % (RPLANE - RROWS * RPITCH);
+      const int lofs = (lane < 60 && col >= 0 && col < RPITCH) ? r * RPITCH + col : RROWS * RPITCH + lane % (RPLANE - RROWS * RPITCH);
+      cm_a[e] = lds0 + RB0 + 4 * (wave * C::CPW * RPLANE + lofs);
     }
+  } else {
+    cm_a[0] = lds0 + RB0 + 4 * (wave * C::CPW * (UPS ? UPLANE : RPLANE) + lane);
   }
+#pragma unroll
+  for (int e = 0; e < NCM; ++e) asm volatile("" : "+v"(cm_a[e]));
+  WINO_LDS_IMM_OK(RBUF + ((WSC - 1) * WKC + C::CPW - 1) * RPLANE + (UP && !UPS ? 64 * (RSUB - 1) : 0), 4);      // the commit's stores
   auto set_geom = [&](int tile) {
     const int y0 = (tile / tiles_x) * WPH, x0 = (tile % tiles_x) * WPW;
     if (UPS) {     // zero padding = source row / column -1 or Hs / Ws (H = 2 Hs, W = 2 Ws, y0 and x0 even)
@@ -321,7 +369,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   // instruction) and the zero padding is folded into the lane's copy of the row -- (v - mean) * 0 + 0 --: vector instructions
   // do not overlap with the fp32 MFMAs of either wave of the SIMD, so every one removed from this loop is
   // matrix time.  Same operations in the same order as apply_coef(): bit-identical values.
-  auto raw_commit1 = [&](int sc, float* rb) {
+  auto raw_commit1 = [&](int sc, int rbo) {                         // rbo: byte offset of the raw buffer (parity * RBUF)
 #pragma unroll
     for (int cw = 0; cw < C::CPW; ++cw) {
       const int kl = wave * C::CPW + cw, ci = (cm_st * WSC + sc) * WKC + kl;
@@ -331,13 +379,13 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       if (UPS) {
         float v = apply_coef(raw[sc][cw][0], cf, p.act);
         v = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & (rkeepC[0] & ck));
-        rb[(sc * WKC + kl) * UPLANE + lane] = v;                     // lanes 60 .. 63: zeros into the plane's pad
+        lds_put(cm_a[0], rbo + 4 * (sc * WKC + cw) * UPLANE, v);     // lanes 60 .. 63: zeros into the plane's pad
       } else if (UP) {
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
           float v = apply_coef(raw[sc][cw][i], cf, p.act);
           v = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) & (rkeepC[i] & ck));
-          if (i + 1 < RSUB || lane + 64 * i < RROWS * RPITCH) rb[(sc * WKC + kl) * RPLANE + lane + 64 * i] = v;
+          if (i + 1 < RSUB || lane + 64 * i < RROWS * RPITCH) lds_put(cm_a[0], rbo + 4 * ((sc * WKC + cw) * RPLANE + 64 * i), v);
         }
       } else {
         // zero padding = (v - mean) * 0 + 0 on the lane's copy of the row.  PRECONDITION: finite activations -- an out-of-image
@@ -359,7 +407,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 #pragma unroll
         for (int h = 0; h < 2; ++h) { if constexpr (ACT) t[h] = silu_f2(t[h]); }       // ACT == (p.act != 0): the launcher's choice
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rb[(sc * WKC + kl) * RPLANE + lofs[i]] = t[i >> 1][i & 1];
+        for (int i = 0; i < 4; ++i) lds_put(cm_a[UP ? 0 : i], rbo + 4 * (sc * WKC + cw) * RPLANE, (float)t[i >> 1][i & 1]);
       }
     }
   };
@@ -373,26 +421,29 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   // (o0, o3) = (c0, c1) - (c2, c3) and (o1, -o2) = (c1, c1) + (c2, -c2): two packed additions per row; nu = 2 is stored negated
   // and the packed weights carry the same sign (wino_pack_kernel).  8 packed vector instructions per chunk and thread.
   const int tk = lane & 7, ttx = lane >> 3, tty = mb;
-  const int tr_yz = tk * RPLANE + (2 * tty + 2 * hf) * RPITCH + 2 * ttx;
-  const int tr_x = tk * RPLANE + (2 * tty + 2 - hf) * RPITCH + 2 * ttx;
+  // rows Y / Z and row X of this thread's patch in the raw tile, its first V element: byte addresses like cm_a
+  unsigned tr_yz = lds0 + RB0 + 4 * (UPS ? tk * UPLANE + (tty + hf) * UCOLS + ttx : tk * RPLANE + (2 * tty + 2 * hf) * RPITCH + 2 * ttx);
+  unsigned tr_x = lds0 + RB0 + 4 * (UPS ? tk * UPLANE + (tty + 1) * UCOLS + ttx : tk * RPLANE + (2 * tty + 2 - hf) * RPITCH + 2 * ttx);
   const float tsgn = hf ? -1.f : 1.f;
-  const f32x2 tpm = {1.f, -1.f};
-  const int tr_dst = (8 * hf) * VPOS + (tk & 1) * VH1 + (tty * WTX + ttx) * 4 + (tk >> 1);
+  const f32x2 tsgn2 = {tsgn, tsgn};
+  unsigned tr_dst = lds0 + 4 * ((8 * hf) * VPOS + (tk & 1) * VH1 + (tty * WTX + ttx) * 4 + (tk >> 1));
+  asm volatile("" : "+v"(tr_yz), "+v"(tr_x), "+v"(tr_dst));
+  WINO_LDS_IMM_OK(RBUF + (WSC - 1) * WKC * (UPS ? UPLANE : RPLANE) + (C::TI - 1) * MB * (UPS ? UCOLS : 2 * RPITCH) + (UPS ? UCOLS + 2 : RPITCH + 2), UPS ? 4 : 8);   // its reads
+  WINO_LDS_IMM_OK(VBUF + (WSC - 1) * 16 * VPOS + (C::TI - 1) * MB * WTX * 4 + 7 * VPOS, 4);                                                  // its stores
   f32x2 td[WSC][C::TI][3][2];                         // rows Y, Z, X; column pairs (c0, c1), (c2, c3)
   // UPS: the same rows out of the source patch -- patch row r = source row (r + 1) >> 1: Y = ty + hf, Z = ty + 1 + hf, X = ty + 1 -- and
   // the three source columns tx, tx + 1, tx + 2 = (c0, c1 = c2, c3)
-  const int us_yz = tk * UPLANE + (tty + hf) * UCOLS + ttx, us_x = tk * UPLANE + (tty + 1) * UCOLS + ttx;
   float tu[WSC][C::TI][3][3];
-  auto transform_read1 = [&](int sc, const float* rb) {
+  auto transform_read1 = [&](int sc, int rbo) {                     // rbo, vbo: byte offsets of the raw / V buffer (parity * RBUF, * VBUF)
     if constexpr (UPS) {
 #pragma unroll
       for (int ti = 0; ti < C::TI; ++ti) {
-        const float* b = rb + sc * WKC * UPLANE + MB * ti * UCOLS;
+        const int b = rbo + 4 * (sc * WKC * UPLANE + MB * ti * UCOLS);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          tu[sc][ti][0][c] = b[us_yz + c];
-          tu[sc][ti][1][c] = b[us_yz + UCOLS + c];
-          tu[sc][ti][2][c] = b[us_x + c];
+          tu[sc][ti][0][c] = lds_get<float>(tr_yz, b + 4 * c);
+          tu[sc][ti][1][c] = lds_get<float>(tr_yz, b + 4 * (UCOLS + c));
+          tu[sc][ti][2][c] = lds_get<float>(tr_x, b + 4 * c);
         }
       }
       return;
@@ -401,13 +452,13 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     for (int ti = 0; ti < C::TI; ++ti)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const float* b = rb + sc * WKC * RPLANE + 2 * MB * ti * RPITCH + 2 * j;
-        td[sc][ti][0][j] = *reinterpret_cast<const f32x2*>(b + tr_yz);
-        td[sc][ti][1][j] = *reinterpret_cast<const f32x2*>(b + tr_yz + RPITCH);
-        td[sc][ti][2][j] = *reinterpret_cast<const f32x2*>(b + tr_x);
+        const int b = rbo + 4 * (sc * WKC * RPLANE + 2 * MB * ti * RPITCH + 2 * j);
+        td[sc][ti][0][j] = lds_get<f32x2>(tr_yz, b);
+        td[sc][ti][1][j] = lds_get<f32x2>(tr_yz, b + 4 * RPITCH);
+        td[sc][ti][2][j] = lds_get<f32x2>(tr_x, b);
       }
   };
-  auto transform_finish1 = [&](int sc, float* vb) {
+  auto transform_finish1 = [&](int sc, int vbo) {
     if constexpr (UPS) {
 #pragma unroll
       for (int ti = 0; ti < C::TI; ++ti) {
@@ -420,10 +471,10 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 #pragma unroll
         for (int x = 0; x < 2; ++x) {
           if (x == 0 && hf != 0) continue;                 // xi = 2 of the hf = 1 waves is exactly +0 and nobody reads it
-          float* o = vb + sc * 16 * VPOS + tr_dst + MB * ti * WTX * 4 + 4 * x * VPOS;
-          o[0 * VPOS] = t[x][0] - t[x][1];                 // c0 - c2
-          o[1 * VPOS] = t[x][1] + 1.f * t[x][1];           // c1 + c2
-          o[3 * VPOS] = t[x][1] - t[x][2];                 // c1 - c3
+          const int o = vbo + 4 * (sc * 16 * VPOS + MB * ti * WTX * 4 + 4 * x * VPOS);
+          lds_put(tr_dst, o + 4 * 0 * VPOS, t[x][0] - t[x][1]);            // c0 - c2
+          lds_put(tr_dst, o + 4 * 1 * VPOS, t[x][1] + 1.f * t[x][1]);      // c1 + c2
+          lds_put(tr_dst, o + 4 * 3 * VPOS, t[x][1] - t[x][2]);            // c1 - c3
         }
       }
       return;
@@ -433,24 +484,23 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       f32x2 t[2][2];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        t[0][j] = td[sc][ti][0][j] - td[sc][ti][2][j];
-        t[1][j] = td[sc][ti][2][j] + tsgn * td[sc][ti][1][j];
+        t[0][j] = pk_sub(td[sc][ti][0][j], td[sc][ti][2][j]);
+        t[1][j] = pk_fma(tsgn2, td[sc][ti][1][j], td[sc][ti][2][j]);
       }
 #pragma unroll
       for (int x = 0; x < 2; ++x) {
-        const f32x2 o03 = t[x][0] - t[x][1];
-        const f32x2 c11 = {t[x][0].y, t[x][0].y}, c22 = {t[x][1].x, t[x][1].x};
-        const f32x2 o12 = c11 + tpm * c22;
-        float* o = vb + sc * 16 * VPOS + tr_dst + MB * ti * WTX * 4 + 4 * x * VPOS;
-        o[0 * VPOS] = o03.x;
-        o[1 * VPOS] = o12.x;
-        if constexpr (!UPZ) o[2 * VPOS] = o12.y;             // UPZ: nu = 2 is exactly +0 and nobody reads it
-        o[3 * VPOS] = o03.y;
+        const f32x2 o03 = pk_sub(t[x][0], t[x][1]);
+        const f32x2 o12 = pk_hi_pm_lo(t[x][0], t[x][1]);       // (c1 + c2, c1 - c2)
+        const int o = vbo + 4 * (sc * 16 * VPOS + MB * ti * WTX * 4 + 4 * x * VPOS);
+        lds_put(tr_dst, o + 4 * 0 * VPOS, (float)o03.x);
+        lds_put(tr_dst, o + 4 * 1 * VPOS, (float)o12.x);
+        if constexpr (!UPZ) lds_put(tr_dst, o + 4 * 2 * VPOS, (float)o12.y);   // UPZ: nu = 2 is exactly +0 and nobody reads it
+        lds_put(tr_dst, o + 4 * 3 * VPOS, (float)o03.y);
       }
     }
   };
-  auto transform_read = [&](const float* rb) { for (int sc = 0; sc < WSC; ++sc) transform_read1(sc, rb); };
-  auto transform_finish = [&](float* vb) { for (int sc = 0; sc < WSC; ++sc) transform_finish1(sc, vb); };
+  auto transform_read = [&](int rbo) { for (int sc = 0; sc < WSC; ++sc) transform_read1(sc, rbo); };
+  auto transform_finish = [&](int vbo) { for (int sc = 0; sc < WSC; ++sc) transform_finish1(sc, vbo); };
 
   // ---- prologue (once per workgroup): transform rows of the sample, stages 0 .. 2 of the stream
   stage_coef_rows<C::NT>(p, n, cfl, tid);
@@ -458,16 +508,34 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   if constexpr (SKIP) { if (tid < C::MT) skb_l[tid] = p.sk_bias ? p.sk_bias[m0 + tid] : 0.f; }
   raw_load();
   __syncthreads();
-  for (int sc = 0; sc < WSC; ++sc) raw_commit1(sc, rbuf);
+  for (int sc = 0; sc < WSC; ++sc) raw_commit1(sc, 0);
   commit_done();
-  if (G > 1) { raw_load(); for (int sc = 0; sc < WSC; ++sc) raw_commit1(sc, rbuf + RBUF); commit_done(); }
+  if (G > 1) { raw_load(); for (int sc = 0; sc < WSC; ++sc) raw_commit1(sc, 4 * RBUF); commit_done(); }
   if (G > 2) raw_load();                                             // stays in registers until trip 0 commits it
   // this wave's transformed weights: 8 positions x one 16-byte load per chunk
   const size_t ustride = (size_t)mblocks * 16 * 64;                  // f32x4 per chunk
   // UPZ: block q of the hf = 1 waves is position 12 + q (xi = 3 first; its blocks 4 .. 7, xi = 2, are never touched)
   constexpr int PHF = UPZ ? 12 : 8;                                  // first position of the hf = 1 waves' block 0
   // SPLIT: the wave's two positions 2 wave, 2 wave + 1 of the workgroup's block
-  const f32x4* up = reinterpret_cast<const f32x4*>(p.wino) + (SPLIT ? ((size_t)(m0 / 32) * 16 + 2 * wave) : ((size_t)(m0 / 32 + mb) * 16 + PHF * hf)) * 64 + lane;
+  const size_t upos = (SPLIT ? ((size_t)(m0 / 32) * 16 + 2 * wave) : ((size_t)(m0 / 32 + mb) * 16 + PHF * hf)) * 64 + lane;   // f32x4 index inside a chunk
+  const f32x4* up = reinterpret_cast<const f32x4*>(p.wino) + upos;
+  // PAIR: ONE descriptor over the table (the launcher checks < 4 GiB), the lane's offset fixed for the kernel, the chunk in the scalar
+  // offset operand: no 64-bit pointer arithmetic per chunk.  The instruction's offset field is 12 bits, blocks 4 .. 7 lie 4096 ..
+  // 7168 bytes behind block 0: uw[1] = uw[0] + 4096 (the register the pointer's high half had) serves them.
+  const unsigned ustride_b = 16u * (unsigned)ustride;                // bytes per chunk
+  const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(PAIR ? p.wino : nullptr, PAIR ? (unsigned)nch * ustride_b : 0u);
+  unsigned uw[2] = {16u * (unsigned)upos, 16u * (unsigned)upos + 4096u};
+  if constexpr (PAIR) asm volatile("" : "+v"(uw[0]), "+v"(uw[1]));
+  auto wfrag = [&](int chunk, int q) -> f32x4 {                      // block q of this wave's positions, of chunk `chunk` (wave-uniform)
+    if constexpr (PAIR) {
+      // the lane offset is "redefined" in front of every load (no instruction): lane offset + block stays ONE use of a fresh value, which the
+      // load takes as register + immediate -- left loop-invariant, hipcc keeps a register per block through the loop (six more, and spills)
+      asm("" : "+v"(uw[q >> 2]));
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, uw[q >> 2] + (unsigned)(q & 3) * 1024u, (unsigned)chunk * ustride_b, 0));
+    } else {
+      return up[(size_t)chunk * ustride + q * 64];
+    }
+  };
   f32x4 ua[8];                                                       // reloaded position by position right after its last use
   // SPLIT: [chunk of the stage][position]: the current stage's fragments; the next stage's are requested a whole stage ahead
   // (registers are plentiful here) and past the last chunk of the tile comes chunk 0 again, as in the other variants
@@ -476,19 +544,19 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 #pragma unroll
     for (int sc = 0; sc < WSC; ++sc)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) wa[sc][q] = up[(size_t)(sc < nch ? sc : 0) * ustride + q * 64];
+      for (int q = 0; q < 2; ++q) wa[sc][q] = wfrag(sc < nch ? sc : 0, q);
   } else if constexpr (UPZ) {
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    ua[0] = up[0 * 64]; ua[1] = up[1 * 64]; ua[3] = up[3 * 64];
+    ua[0] = wfrag(0, 0); ua[1] = wfrag(0, 1); ua[3] = wfrag(0, 3);
     ua[4] = zero4; ua[5] = zero4; ua[7] = zero4;
-    if (hf == 0) { ua[4] = up[4 * 64]; ua[5] = up[5 * 64]; ua[7] = up[7 * 64]; }
+    if (hf == 0) { ua[4] = wfrag(0, 4); ua[5] = wfrag(0, 5); ua[7] = wfrag(0, 7); }
   } else {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) ua[q] = up[q * 64];
+    for (int q = 0; q < 8; ++q) ua[q] = wfrag(0, q);
   }
   __syncthreads();
-  transform_read(rbuf);
-  transform_finish(vbuf);
+  transform_read(0);
+  transform_finish(0);
   // Accumulators start at zero, except Winograd position (xi, nu) = (1, 1) -- block 5 of the hf = 0 waves --, which starts at
   // the bias: A^T has ones in column 1 of both rows, so a constant there comes out as that constant in all four pixels.
   // Zeroing is done by the matrix pipe itself -- D = 0 * 0 + 0 with the inline constant as C: eight instructions (512 cycles)
@@ -517,7 +585,9 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   init_acc();
 
   // ---- the stream of stages: one trip = one stage of WSC chunks
-  const int vrd = (SPLIT ? 2 * wave : PHF * hf) * VPOS + (lane >> 5) * VH1 + (lane & 31) * 4;
+  unsigned vrd = lds0 + 4 * ((SPLIT ? 2 * wave : PHF * hf) * VPOS + (lane >> 5) * VH1 + (lane & 31) * 4);   // this lane's B fragment of block 0: a byte address like cm_a
+  asm volatile("" : "+v"(vrd));
+  WINO_LDS_IMM_OK(VBUF + (WSC - 1) * 16 * VPOS + 7 * VPOS, 16);
   if (p.dbg && tid == 0) { p.dbg[blockIdx.x * 16 + 1] = __builtin_amdgcn_s_memrealtime(); p.dbg[blockIdx.x * 16 + 5] = __builtin_amdgcn_s_memtime(); }
 #ifdef MCEDM_WINO_TIMELINE      // cycle sums of waves 0 and MB (lane 0): MFMA stream, barrier, epilogue -> dbg[8..12] / dbg[13..15, 7] (diagnostic builds only)
   unsigned long long ph[5] = {0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
@@ -548,16 +618,16 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
   // slices of a stage sit in its six common slots, ten instructions behind each MFMA instead of five.
   auto side_slice_upz = [&](int slot, int cur) {
     if (WSC == 2) {
-      if (slot == 0) transform_read1(0, rbuf + (cur ^ 1) * RBUF);
-      if (slot == 1) raw_commit1(0, rbuf + cur * RBUF);
-      if (slot == 2) { transform_finish1(0, vbuf + (cur ^ 1) * VBUF); raw_load1(0); }
-      if (slot == 3) transform_read1(WSC - 1, rbuf + (cur ^ 1) * RBUF);
-      if (slot == 4) { raw_commit1(WSC - 1, rbuf + cur * RBUF); commit_done(); }
-      if (slot == 5) { transform_finish1(WSC - 1, vbuf + (cur ^ 1) * VBUF); raw_load1(WSC - 1); raw_load_done(); }
+      if (slot == 0) transform_read1(0, 4 * (cur ^ 1) * RBUF);
+      if (slot == 1) raw_commit1(0, 4 * cur * RBUF);
+      if (slot == 2) { transform_finish1(0, 4 * (cur ^ 1) * VBUF); raw_load1(0); }
+      if (slot == 3) transform_read1(WSC - 1, 4 * (cur ^ 1) * RBUF);
+      if (slot == 4) { raw_commit1(WSC - 1, 4 * cur * RBUF); commit_done(); }
+      if (slot == 5) { transform_finish1(WSC - 1, 4 * (cur ^ 1) * VBUF); raw_load1(WSC - 1); raw_load_done(); }
     } else {
-      if (slot == 0) transform_read(rbuf + (cur ^ 1) * RBUF);
-      if (slot == 1) { raw_commit1(0, rbuf + cur * RBUF); commit_done(); }
-      if (slot == 2) { transform_finish1(0, vbuf + (cur ^ 1) * VBUF); raw_load1(0); raw_load_done(); }
+      if (slot == 0) transform_read(4 * (cur ^ 1) * RBUF);
+      if (slot == 1) { raw_commit1(0, 4 * cur * RBUF); commit_done(); }
+      if (slot == 2) { transform_finish1(0, 4 * (cur ^ 1) * VBUF); raw_load1(0); raw_load_done(); }
     }
   };
   auto side_slice = [&](int slot, int g, int cur) {
@@ -568,23 +638,28 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       // a chunk's raw registers are requested again in the slot right behind their commit: the tile data (HBM) then has seven
       // slots = 7 / 8 of a stage to arrive (both chunks requested together in slot 6 left the first one three slots, ~1.5 us,
       // and its commit waited ~800 cycles for it: in-kernel slot stamps)
-      if (slot == 0) transform_read1(0, rbuf + (cur ^ 1) * RBUF);
-      if (slot == 1) raw_commit1(0, rbuf + cur * RBUF);
-      if (slot == 2) { transform_finish1(0, vbuf + (cur ^ 1) * VBUF); raw_load1(0); }
-      if (slot == 3) transform_read1(WSC - 1, rbuf + (cur ^ 1) * RBUF);
-      if (slot == 4) { raw_commit1(WSC - 1, rbuf + cur * RBUF); commit_done(); }
-      if (slot == 5) { transform_finish1(WSC - 1, vbuf + (cur ^ 1) * VBUF); raw_load1(WSC - 1); raw_load_done(); }
+      if (slot == 0) transform_read1(0, 4 * (cur ^ 1) * RBUF);
+      if (slot == 1) raw_commit1(0, 4 * cur * RBUF);
+      if (slot == 2) { transform_finish1(0, 4 * (cur ^ 1) * VBUF); raw_load1(0); }
+      if (slot == 3) transform_read1(WSC - 1, 4 * (cur ^ 1) * RBUF);
+      if (slot == 4) { raw_commit1(WSC - 1, 4 * cur * RBUF); commit_done(); }
+      if (slot == 5) { transform_finish1(WSC - 1, 4 * (cur ^ 1) * VBUF); raw_load1(WSC - 1); raw_load_done(); }
     } else {
-      if (slot == 0) transform_read(rbuf + (cur ^ 1) * RBUF);
-      if (slot == 1) { raw_commit1(0, rbuf + cur * RBUF); commit_done(); }
+      if (slot == 0) transform_read(4 * (cur ^ 1) * RBUF);
+      if (slot == 1) { raw_commit1(0, 4 * cur * RBUF); commit_done(); }
       if (slot == 2) { raw_load1(0); raw_load_done(); }
-      if (slot == 3) transform_finish1(0, vbuf + (cur ^ 1) * VBUF);
+      if (slot == 3) transform_finish1(0, 4 * (cur ^ 1) * VBUF);
     }
   };
   (void)mode;
   int st = 0, tile = tile0;                                        // stage within the tile, tile of the accumulators
-  for (int g = 0; g < G; ++g) {
-    const int cur = g & 1;
+  // PAIR: a trip is TWO stages, buffer parity 0 then 1, each with its barrier: the parity is a compile-time constant in either half
+  // and with it every LDS offset.  The tile-end check follows the second half only -- the launcher takes this form for even stage
+  // counts per tile -- so that the epilogue and init_acc() exist once in the loop.
+  for (int g = 0; g < G; g += PAIR ? 2 : 1) {
+#pragma unroll
+    for (int half = 0; half < (PAIR ? 2 : 1); ++half) {
+    const int cur = PAIR ? half : g & 1;
     WINO_STAMP(0)
     WINO_SLOT0
     if constexpr (SPLIT) {
@@ -595,16 +670,15 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       f32x4 bf[WSC][2], wn[WSC][2];
 #pragma unroll
       for (int sc = 0; sc < WSC; ++sc) {
-        const float* vb = vbuf + cur * VBUF + sc * 16 * VPOS + vrd;
-        bf[sc][0] = *reinterpret_cast<const f32x4*>(vb);
-        bf[sc][1] = *reinterpret_cast<const f32x4*>(vb + VPOS);
+        const int vbo = 4 * (cur * VBUF + sc * 16 * VPOS);
+        bf[sc][0] = lds_get<f32x4>(vrd, vbo);
+        bf[sc][1] = lds_get<f32x4>(vrd, vbo + 4 * VPOS);
       }
 #pragma unroll
       for (int sc = 0; sc < WSC; ++sc) {
         const int cn = (st + 1) * WSC + sc;
-        const f32x4* un = up + (size_t)(cn < nch ? cn : 0) * ustride;
-        wn[sc][0] = un[0];
-        wn[sc][1] = un[64];
+        wn[sc][0] = wfrag(cn < nch ? cn : 0, 0);
+        wn[sc][1] = wfrag(cn < nch ? cn : 0, 1);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -631,20 +705,20 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 #pragma unroll
     for (int sc = 0; sc < WSC; ++sc) {
       const int c = st * WSC + sc;
-      const f32x4* un = up + (size_t)(c + 1 < nch ? c + 1 : 0) * ustride;      // after a tile's last chunk: chunk 0 again
-      const float* vb = vbuf + cur * VBUF + sc * 16 * VPOS + vrd;
+      const int cn = c + 1 < nch ? c + 1 : 0;                                 // after a tile's last chunk: chunk 0 again
+      const int vbo = 4 * (cur * VBUF + sc * 16 * VPOS);
       if constexpr (UPZ) {
         constexpr int CQ[3] = {0, 1, 3};                   // the blocks both halves run
         f32x4 bq[3];                                       // their B fragments, one position ahead of the MFMAs
-        bq[0] = *reinterpret_cast<const f32x4*>(vb);
-        bq[1] = *reinterpret_cast<const f32x4*>(vb + VPOS);
+        bq[0] = lds_get<f32x4>(vrd, vbo);
+        bq[1] = lds_get<f32x4>(vrd, vbo + 4 * VPOS);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          if (i == 0) bq[2] = *reinterpret_cast<const f32x4*>(vb + 3 * VPOS);
+          if (i == 0) bq[2] = lds_get<f32x4>(vrd, vbo + 4 * 3 * VPOS);
 #pragma unroll
           for (int s = 0; s < 4; ++s) acc[CQ[i]] = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[CQ[i]][s], bq[i][s], acc[CQ[i]], 0, 0, 0);
-          if (!no_u) ua[CQ[i]] = un[CQ[i] * 64];
+          if (!no_u) ua[CQ[i]] = wfrag(cn, CQ[i]);
           side_slice_upz(sc * 3 + i, cur);
           if (i == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
 #pragma unroll
@@ -661,26 +735,26 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
           constexpr int HQ[3] = {4, 5, 7};
           f32x4 bh[3];
 #pragma unroll
-          for (int i = 0; i < 3; ++i) bh[i] = *reinterpret_cast<const f32x4*>(vb + HQ[i] * VPOS);
+          for (int i = 0; i < 3; ++i) bh[i] = lds_get<f32x4>(vrd, vbo + 4 * HQ[i] * VPOS);
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) acc[HQ[i]] = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[HQ[i]][s], bh[i][s], acc[HQ[i]], 0, 0, 0);
-            if (!no_u) ua[HQ[i]] = un[HQ[i] * 64];
+            if (!no_u) ua[HQ[i]] = wfrag(cn, HQ[i]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
       } else {
       f32x4 b4[2][2];                                      // B fragments of two positions, one pair ahead of the MFMAs
-      b4[0][0] = *reinterpret_cast<const f32x4*>(vb);
-      b4[0][1] = *reinterpret_cast<const f32x4*>(vb + VPOS);
+      b4[0][0] = lds_get<f32x4>(vrd, vbo);
+      b4[0][1] = lds_get<f32x4>(vrd, vbo + 4 * VPOS);
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #pragma unroll
       for (int qp = 0; qp < 4; ++qp) {
         const int cb = qp & 1;
         if (qp < 3) {
-          b4[cb ^ 1][0] = *reinterpret_cast<const f32x4*>(vb + (2 * qp + 2) * VPOS);
-          b4[cb ^ 1][1] = *reinterpret_cast<const f32x4*>(vb + (2 * qp + 3) * VPOS);
+          b4[cb ^ 1][0] = lds_get<f32x4>(vrd, vbo + 4 * (2 * qp + 2) * VPOS);
+          b4[cb ^ 1][1] = lds_get<f32x4>(vrd, vbo + 4 * (2 * qp + 3) * VPOS);
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -691,8 +765,8 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
         // issued together right behind the barrier -- 64 KB per CU at once -- back up the vector memory path and every
         // wave stalls in their issue for 1000-3000 cycles per chunk.)
         if (!no_u) {
-          ua[2 * qp] = un[(2 * qp) * 64];
-          ua[2 * qp + 1] = un[(2 * qp + 1) * 64];
+          ua[2 * qp] = wfrag(cn, 2 * qp);
+          ua[2 * qp + 1] = wfrag(cn, 2 * qp + 1);
         }
         // The slice's instructions go BETWEEN the slot's MFMAs, up to WINO_IL_K behind each: its dependent chains (LDS read ->
         // arithmetic -> transcendental -> LDS write) then wait under matrix instructions instead of in front of the next slot
@@ -716,7 +790,9 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
     WINO_STAMP(1)
     __syncthreads();
     WINO_STAMP(2)
-    if (++st < nst) continue;
+    ++st;
+    }
+    if (st < nst) continue;
     st = 0;
 
     // ---- a tile is complete: output transform, bias, residual, stores, statistics; then the accumulators start over.
@@ -1047,6 +1123,39 @@ int wino_tiles_per_wg(long long total, int tiles_img, int slots) {
   return best;
 }
 
+// The two forms of every instantiation (conv_wino.hpp WinoLoop1): the two-stage trip with immediate LDS offsets and buffer descriptors
+// serves the launches whose tiles have an EVEN number of stages (it ends a tile behind the second stage of a trip only) and whose
+// Winograd table lies inside a descriptor's 4 GiB range; everything else keeps the one-stage trip.  Three instantiations stay on the
+// one-stage trip for every shape, because hipcc spills more in the two-stage form than their present code does:
+// the sixteen-position up-sampling kernels (KV_CONV_WINO_UPZ = 0) and the 64-channel kernel without activation.
+template <class C, bool UP, bool ACT, class... Tag>
+constexpr bool wino_pair_form = !(UP && sizeof...(Tag) == 0) && !(C::MB == 2 && !UP && !ACT);
+static bool wino_loop1(const ConvArgs& a, int chunks_per_stage) {
+  const unsigned long long Cin = (unsigned long long)(a.Ca + a.Cb);
+  const int nst = ceil_div((int)Cin / WKC, chunks_per_stage);
+  const unsigned long long table = 16ull * Cin * (unsigned long long)cout_padded(a.Cout) * 4ull;
+  return nst % 2 != 0 || table >= (1ull << 32);
+}
+template <class C, bool UP, bool ACT, class... Tag>
+static void wino_launch(bool loop1, dim3 grid, int lds_bytes, hipStream_t stream, const ConvArgs& a, int tiles_x, int tiles_img, int nch, int mblocks, int per,
+                        int mode) {
+  if constexpr (wino_pair_form<C, UP, ACT, Tag...>) {
+    if (!loop1) {
+      hipLaunchKernelGGL((conv_wino_kernel<C, UP, ACT, Tag...>), grid, dim3(C::NT), lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((conv_wino_kernel<C, UP, ACT, WinoLoop1, Tag...>), grid, dim3(C::NT), lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
+}
+template <class C, bool UP, bool ACT, class... Tag>
+static hipError_t wino_lds_attr() {
+  if constexpr (wino_pair_form<C, UP, ACT, Tag...>) {
+    const hipError_t e = hipFuncSetAttribute((const void*)conv_wino_kernel<C, UP, ACT, Tag...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+  }
+  return hipFuncSetAttribute((const void*)conv_wino_kernel<C, UP, ACT, WinoLoop1, Tag...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
 template <class C>
 static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   const int tiles_x = a.W / WPW, tiles_img = tiles_x * (a.H / WPH);
@@ -1066,13 +1175,13 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
     int n_cu = 0;
     MCEDM_HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     ncu[dev].store(n_cu > 0 ? n_cu : 256, std::memory_order_release);
-    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MCEDM_HIP_TRY((wino_lds_attr<C, false, true>()));
     if constexpr (!C::SKIP) {                              // the SKIP variant exists in the plain, activated form only
-      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true, true, WinoUp<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, true, true, WinoUp<false>>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, true, WinoBiasRows>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MCEDM_HIP_TRY((wino_lds_attr<C, true, true>()));
+      MCEDM_HIP_TRY((wino_lds_attr<C, true, true, WinoUp<true>>()));
+      MCEDM_HIP_TRY((wino_lds_attr<C, true, true, WinoUp<false>>()));
+      MCEDM_HIP_TRY((wino_lds_attr<C, false, false>()));
+      MCEDM_HIP_TRY((wino_lds_attr<C, false, true, WinoBiasRows>()));
     }
     attr_set[dev].store(true, std::memory_order_release);
   }
@@ -1087,33 +1196,29 @@ static int launch_wino_cfg(const ConvArgs& a, hipStream_t stream) {
   // the zero-position variant (WinoUp: same LDS footprint); 2: with the sixteen-position kernel's staging (the positions alone, A/B runs)
   const int upz = !C::SKIP && a.resample == RS_UP ? kernel_switch(KV_CONV_WINO_UPZ) : 0;
   if (prof_enabled()) snprintf(name, sizeof(name), "conv_wino_kernel<Wino%sCfg<%d>, %s, %s%s>", C::SKIP ? "Skip" : "", C::MB, a.resample == RS_UP ? "true" : "false",
-                               noact ? "false" : "true", a.bias_batch ? ", WinoBiasRows" : upz == 2 ? ", WinoUp<false>" : upz ? ", WinoUp<true>" : "");   // = rocprofv3's name
+                               noact ? "false" : "true", a.bias_batch ? ", WinoBiasRows" : upz == 2 ? ", WinoUp<false>" : upz ? ", WinoUp<true>" : "");   // = rocprofv3's name (less the WinoLoop1 tag of the one-stage form)
   const double px = (double)a.B * a.H * a.W;
   const double skc = C::SKIP ? (double)(a.sk_Ca + a.sk_Cb) : 0.0;      // folded 1x1 projection: its own flops, input read and weights
   // algorithmic cost = the direct convolution's (2 * MAC); the kernel issues 4 / 9 of these as matrix flops
   ProfScope ps(name, 2.0 * px * a.Cout * ((double)Cin * 9 + skc),
                4.0 * ((double)a.B * Cin * a.Hs * a.Ws + px * (a.Cout * (a.res ? 2 : 1) + skc) + (double)a.Cout * (Cin * 9 + skc)), stream);
+  const dim3 grid((unsigned)(total / per), a.Cout / C::MT);
+  const int mblocks = cout_padded(a.Cout) / 32, mode = wino_mode_env();
+  const bool loop1 = wino_loop1(a, C::SC);
   if constexpr (C::SKIP)
-    hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, false, true>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   else if (a.bias_batch)
-    hipLaunchKernelGGL((conv_wino_kernel<C, false, true, WinoBiasRows>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, false, true, WinoBiasRows>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   else if (upz == 2)
-    hipLaunchKernelGGL((conv_wino_kernel<C, true, true, WinoUp<false>>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, true, true, WinoUp<false>>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   else if (upz)
-    hipLaunchKernelGGL((conv_wino_kernel<C, true, true, WinoUp<true>>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, true, true, WinoUp<true>>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   else if (a.resample == RS_UP)
-    hipLaunchKernelGGL((conv_wino_kernel<C, true>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, true, true>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   else if (noact)
-    hipLaunchKernelGGL((conv_wino_kernel<C, false, false>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, false, false>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   else
-    hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)(total / per), a.Cout / C::MT), dim3(C::NT), lds_bytes, stream, a, tiles_x,
-                       tiles_img, nch, cout_padded(a.Cout) / 32, per, wino_mode_env());
+    wino_launch<C, false, true>(loop1, grid, lds_bytes, stream, a, tiles_x, tiles_img, nch, mblocks, per, mode);
   MCEDM_LAUNCH_CHECK("conv_wino_kernel");
   if (a.gsum_tiles) *a.gsum_tiles = SumTiles{tiles_img, tiles_x, WPH, WPW, a.gsum_rc == 2 ? 2 : 4};
   return MCEDM_OK;
@@ -1178,8 +1283,8 @@ int launch_conv_wino_split(const ConvArgs& a_in, hipStream_t stream) {
   MCEDM_HIP_TRY(hipGetDevice(&dev));
   MCEDM_REQUIRE(dev >= 0 && dev < 64, "device index %d out of range", dev);
   if (!attr_set[dev].load(std::memory_order_acquire)) {
-    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MCEDM_HIP_TRY(hipFuncSetAttribute((const void*)conv_wino_kernel<C, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MCEDM_HIP_TRY((wino_lds_attr<C, false, true>()));
+    MCEDM_HIP_TRY((wino_lds_attr<C, false, false>()));
     attr_set[dev].store(true, std::memory_order_release);
   }
   char name[64] = "";
@@ -1187,12 +1292,11 @@ int launch_conv_wino_split(const ConvArgs& a_in, hipStream_t stream) {
   const double px = (double)a.B * a.H * a.W;
   ProfScope ps(name, 2.0 * px * a.Cout * (double)Cin * 9,
                4.0 * ((double)a.B * Cin * a.H * a.W + px * a.Cout * (a.res ? 2 : 1) + (double)a.Cout * Cin * 9), stream);
+  const bool loop1 = wino_loop1(a, C::SC);
   if (a.act)
-    hipLaunchKernelGGL((conv_wino_kernel<C, false>), dim3((unsigned)total), dim3(C::NT), lds_bytes, stream, a, tiles_x, tiles_img, nch,
-                       cout_padded(a.Cout) / 32, 1, 0);
+    wino_launch<C, false, true>(loop1, dim3((unsigned)total), lds_bytes, stream, a, tiles_x, tiles_img, nch, cout_padded(a.Cout) / 32, 1, 0);
   else
-    hipLaunchKernelGGL((conv_wino_kernel<C, false, false>), dim3((unsigned)total), dim3(C::NT), lds_bytes, stream, a, tiles_x, tiles_img, nch,
-                       cout_padded(a.Cout) / 32, 1, 0);
+    wino_launch<C, false, false>(loop1, dim3((unsigned)total), lds_bytes, stream, a, tiles_x, tiles_img, nch, cout_padded(a.Cout) / 32, 1, 0);
   MCEDM_LAUNCH_CHECK("conv_wino_kernel");
   if (a.gsum_tiles) *a.gsum_tiles = SumTiles{tiles_img, tiles_x, WPH, WPW, a.gsum_rc == 2 ? 2 : 4};
   return MCEDM_OK;

@@ -78,15 +78,25 @@ struct WinoSkipCfg : WinoCfg<MB_> {
 template <bool SRC>
 struct WinoUp {};
 template <class... Tag>
-struct WinoUpTraits { static constexpr bool UPZ = false, UPS = false, BROWS = false; static_assert(sizeof...(Tag) == 0, "one tag at most: WinoUp<SRC> or WinoBiasRows"); };
+struct WinoUpTraits { static constexpr bool UPZ = false, UPS = false, BROWS = false, LOOP1 = false; static_assert(sizeof...(Tag) == 0, "one tag at most: WinoUp<SRC> or WinoBiasRows"); };
 template <bool SRC>
-struct WinoUpTraits<WinoUp<SRC>> { static constexpr bool UPZ = true, UPS = SRC, BROWS = false; };
+struct WinoUpTraits<WinoUp<SRC>> { static constexpr bool UPZ = true, UPS = SRC, BROWS = false, LOOP1 = false; };
 // WinoBiasRows: the un-resampled, activated kernel with a bias row per sample (ConvArgs::bias_batch).  An instantiation of its own:
 // the kernel sits at 256 registers, and reading one more argument in the shared prologue cost the 128-channel form its schedule
 // (2 % of its time) although no resource count moved; without the tag the kernel is what it was, instruction for instruction.
 struct WinoBiasRows {};
 template <>
-struct WinoUpTraits<WinoBiasRows> { static constexpr bool UPZ = false, UPS = false, BROWS = true; };
+struct WinoUpTraits<WinoBiasRows> { static constexpr bool UPZ = false, UPS = false, BROWS = true, LOOP1 = false; };
+// WinoLoop1, in FRONT of the other tag: the K loop with one stage per trip and run-time addresses -- the LDS buffer parity added to a
+// lane index in front of every group of accesses, the weights through a 64-bit pointer per lane.  Without it (the default, every
+// launch of the benchmark workloads) a trip is TWO stages with the parity a compile-time constant: every LDS address is a per-lane
+// register computed once per workgroup plus an immediate offset, and the weights go through one buffer descriptor with the chunk in
+// the scalar offset -- no address arithmetic between the MFMAs.  That form ends a tile only behind the
+// second stage of a trip (the epilogue exists once in the loop), so the launcher keeps WinoLoop1 for the shapes with an odd
+// number of stages per tile and for a Winograd table beyond a descriptor's 4 GiB range.  Same operations in the same order: same bits.
+struct WinoLoop1 {};
+template <class... Tag>
+struct WinoUpTraits<WinoLoop1, Tag...> : WinoUpTraits<Tag...> { static constexpr bool LOOP1 = true; };
 constexpr int UROWS = WPH / 2 + 2, UCOLS = WPW / 2 + 2;   // source patch of a tile: 6 x 10
 constexpr int UPLANE = 68;                       // floats between its channels (60 used; lanes 60 .. 63 store into the pad); = 4 mod 32: the
                                                  // transform's dword reads (eight channels x four patch columns per 32 lanes) cover the 32 banks once
