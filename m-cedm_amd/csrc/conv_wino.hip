@@ -34,6 +34,7 @@
 // against fp64, 0.1 of the rtol 1e-4 / atol 1e-5 bar); they do not depend on the batch size or the grid.
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include "conv_wino.hpp"
 #include "pack.hpp"
@@ -216,6 +217,23 @@ __device__ __forceinline__ f32x2 pk_hi_pm_lo(f32x2 a, f32x2 b) {
   f32x2 d;
   asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
+}
+// half_sum32 (conv_tile.hpp: the sum over the 32 lanes of a half-wave, in every lane) with its last step in registers: behind the four
+// DPP steps every lane of a 16-lane row holds its row's sum, and v_permlane16_swap_b32 exchanges the odd rows of one copy with the even
+// rows of another -- row pair (0, 1) | (2, 3): a = (s0, s0, s2, s2), b = (s1, s1, s3, s3) -- so a + b adds the same two partial sums as
+// v + __shfl_xor(v, 16) did (s0 + s1 in row 0, s1 + s0 in row 1: the same bits) without the ds_bpermute_b32 round trip through the
+// LDS pipe and its wait.  Written as an instruction with BOTH operands read-write (the builtin lost its second result here,
+// DESIGN.md section 3); the two wait states a vector write of either operand needs in front of it are inside the string.
+__device__ __forceinline__ float half_sum32_swap(float v) {
+#define MCEDM_DPP(x, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
+  v += MCEDM_DPP(v, 0xB1);       // quad_perm [1, 0, 3, 2]
+  v += MCEDM_DPP(v, 0x4E);       // quad_perm [2, 3, 0, 1]
+  v += MCEDM_DPP(v, 0x141);      // row_half_mirror
+  v += MCEDM_DPP(v, 0x140);      // row_mirror
+#undef MCEDM_DPP
+  float a = v, b = v;
+  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return a + b;
 }
 // the largest immediate offset of an LDS access family (bytes; the last byte of the access) must fit the instruction's field
 #define WINO_LDS_IMM_OK(floats, bytes) static_assert(4 * (floats) + (bytes) <= 65536, "LDS offset beyond the 16-bit immediate field")
@@ -863,7 +881,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
         const bool pairs = p.gsum_rc == 2;
         float a[2], b[2];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) a[e] = half_sum32((v0[2 * e] + v1[2 * e]) + (v0[2 * e + 1] + v1[2 * e + 1]));
+        for (int e = 0; e < 2; ++e) a[e] = half_sum32_swap((v0[2 * e] + v1[2 * e]) + (v0[2 * e + 1] + v1[2 * e + 1]));
         const float cnt = pairs ? 128.f : 256.f;
         const float mean0 = pairs ? a[0] * (1.0f / 128.0f) : (a[0] + a[1]) * (1.0f / 256.0f);
         const float mean1 = pairs ? a[1] * (1.0f / 128.0f) : mean0;
@@ -873,7 +891,7 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
           float q = 0.f;
 #pragma unroll
           for (int r = 2 * e; r < 2 * e + 2; ++r) { const float d0 = v0[r] - mean, d1 = v1[r] - mean; q = fmaf(d0, d0, q); q = fmaf(d1, d1, q); }
-          b[e] = half_sum32(q);
+          b[e] = half_sum32_swap(q);
         }
         if ((lane & 31) == 0) {
           const int quad = 2 * gq + (lane >> 5);
@@ -933,10 +951,17 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       sk.run(xch, skb_l + 32 * mb + 4 * (lane >> 5), wave, wave ^ MB, lane, keep, send, v0, v1);
       WINO_EP(2)                                          // 2: the projection with the two exchange rounds inside it
     } else {
-    float2 rv[16];                                        // residual: in flight during the rest of the transform and the exchange
-    if (p.res && p.res_mode == RS_DOWN) {
+    // residual: in flight during the rest of the transform and the exchange.  ONE wave-uniform dispatch on its mode, every arm
+    // straight-line: rx / ry = what is added to the left / right pixel of the pair; nothing behind the arms knows the mode.
+    // RS_UP: both pixels share a source, and each asks for it with a load of its own -- a copy behind the load (rx = ry = q) had put
+    // a wait for the whole round trip between every two loads; one register for both, added where v1 is formed, lives through both
+    // exchange rounds and costs every instantiation spills.  The second load hits the line the first fetched.
+    float rx[16], ry[16];
+    const int rmode = p.res ? p.res_mode : RS_NONE;
+    if (rmode == RS_DOWN) {
       // residual at double resolution: the 2x2 mean of the source (adm_blocks.py:75-77), two 16-byte loads per channel and
-      // pixel pair, four channels in flight at a time (all sixteen would need 128 registers)
+      // pixel pair, four channels in flight at a time.  (Eight, as a rolling window -- the accumulators are dead here -- spill nothing
+      // and change nothing: the tile's 256 KB per CU arrive at the rate the memory system has for them)
       const unsigned dvoff = 4u * ((unsigned)cbase * (HWu << 2) + (unsigned)(2 * oy) * (unsigned)(2 * p.W) + (unsigned)(2 * ox));
 #pragma unroll
       for (int r0 = 0; r0 < 16; r0 += 4) {
@@ -948,19 +973,25 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
           tb[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, dvoff + 8u * (unsigned)p.W, so, 0));
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-          rv[r0 + k] = make_float2(0.25f * ((ta[k][0] + ta[k][1]) + (tb[k][0] + tb[k][1])), 0.25f * ((ta[k][2] + ta[k][3]) + (tb[k][2] + tb[k][3])));
+        for (int k = 0; k < 4; ++k) {
+          rx[r0 + k] = 0.25f * ((ta[k][0] + ta[k][1]) + (tb[k][0] + tb[k][1]));
+          ry[r0 + k] = 0.25f * ((ta[k][2] + ta[k][3]) + (tb[k][2] + tb[k][3]));
+        }
       }
-    } else {
+    } else if (rmode == RS_UP) {                           // residual at half resolution: 2 x 16 loads back to back, no copy, no wait
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        rx[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_res, rvoff, 4u * (unsigned)((r & 3) + 8 * (r >> 2)) * (HWu >> 2), 0));
+      unsigned rvoff_y = rvoff;                            // opaque: or the two loads of a channel become one and the copy is back
+      asm volatile("" : "+v"(rvoff_y));
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        ry[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_res, rvoff_y, 4u * (unsigned)((r & 3) + 8 * (r >> 2)) * (HWu >> 2), 0));
+    } else {                                               // same resolution; no residual: a zero-sized descriptor reads zeros
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int dr = (r & 3) + 8 * (r >> 2);
-        if (p.res && p.res_mode == RS_UP) {                // residual at half resolution: both pixels of the pair share a source
-          const float q = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_res, rvoff, 4u * (unsigned)dr * (HWu >> 2), 0));
-          rv[r] = make_float2(q, q);
-        } else {                                           // no residual: a zero-sized descriptor reads zeros
-          rv[r] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_res, voff, 4u * (unsigned)dr * HWu, 0));
-        }
+        const float2 q = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs_res, voff, 4u * (unsigned)((r & 3) + 8 * (r >> 2)) * HWu, 0));
+        rx[r] = q.x; ry[r] = q.y;
       }
     }
     WINO_EP(1)                                            // 1: output transform over nu, weight + residual requests
@@ -973,11 +1004,13 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float got = xch[(pw * 16 + r) * 64 + lane];
-        if (j == 0) v0[r] = keep[0][r] + got + rv[r].x;
-        else        v1[r] = keep[1][r] + got + rv[r].y;
+        if (j == 0) v0[r] = keep[0][r] + got + rx[r];
+        else        v1[r] = keep[1][r] + got;
       }
       if (j == 0) __syncthreads();
     }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v1[r] = v1[r] + ry[r];     // (keep + got) + residual, as for v0
     WINO_EP(2)                                            // 2: the two exchange rounds (incl. the wait for the residual)
     }
 #pragma unroll
@@ -990,39 +1023,48 @@ __global__ __launch_bounds__(C::NT, C::MB == 4 ? 1 : 2) void conv_wino_kernel(co
       // registers 4 g .. 4 g + 3 of the 32 lanes that share lane >> 5 (or per 2-channel block, gsum_rc == 2: their two
       // halves); this wave holds one pixel row of every patch, its partner wave the other: (count, sum, M2 about the wave's
       // own mean) per wave, merged in a fixed order by conv_stats_store.
-      const bool pairs = p.gsum_rc == 2;
+      // The record width is tested ONCE, in front of the four groups, and the slots in `red` are addressed from an opaque copy of
+      // the thread index: nothing of this phase is computed ahead of the K loop and kept (or spilled) through it.
+      int ol = tid;
+      asm volatile("" : "+v"(ol));
+      const int half = (ol >> 5) & 1;
+      const bool first = (ol & 31) == 0;
+      auto stats = [&](auto PAIRS) {
+        constexpr bool pairs = decltype(PAIRS)::value;
+        constexpr float cnt = pairs ? 128.f : 256.f;
+        float* const slot0 = red + (pairs ? hf * (C::MT / 2) + 2 * (8 * mb + half) : hf * (C::MT / 4) + 8 * mb + half) * 3;
 #pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        float a[2], b[2];
+        for (int gq = 0; gq < 4; ++gq) {
+          float a[2], b[2];
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          a[e] = half_sum32((v0[4 * gq + 2 * e] + v1[4 * gq + 2 * e]) + (v0[4 * gq + 2 * e + 1] + v1[4 * gq + 2 * e + 1]));
-        }
-        const float cnt = pairs ? 128.f : 256.f;
-        const float mean0 = pairs ? a[0] * (1.0f / 128.0f) : (a[0] + a[1]) * (1.0f / 256.0f);
-        const float mean1 = pairs ? a[1] * (1.0f / 128.0f) : mean0;
+          for (int e = 0; e < 2; ++e) {
+            a[e] = half_sum32_swap((v0[4 * gq + 2 * e] + v1[4 * gq + 2 * e]) + (v0[4 * gq + 2 * e + 1] + v1[4 * gq + 2 * e + 1]));
+          }
+          const float mean0 = pairs ? a[0] * (1.0f / 128.0f) : (a[0] + a[1]) * (1.0f / 256.0f);
+          const float mean1 = pairs ? a[1] * (1.0f / 128.0f) : mean0;
 #pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const float mean = e ? mean1 : mean0;
-          float q = 0.f;
+          for (int e = 0; e < 2; ++e) {
+            const float mean = e ? mean1 : mean0;
+            float q = 0.f;
 #pragma unroll
-          for (int r = 4 * gq + 2 * e; r < 4 * gq + 2 * e + 2; ++r) { const float d0 = v0[r] - mean, d1 = v1[r] - mean; q = fmaf(d0, d0, q); q = fmaf(d1, d1, q); }
-          b[e] = half_sum32(q);
-        }
-        if ((lane & 31) == 0) {
-          const int quad = 8 * mb + 2 * gq + (lane >> 5);
-          if (pairs) {
+            for (int r = 4 * gq + 2 * e; r < 4 * gq + 2 * e + 2; ++r) { const float d0 = v0[r] - mean, d1 = v1[r] - mean; q = fmaf(d0, d0, q); q = fmaf(d1, d1, q); }
+            b[e] = half_sum32_swap(q);
+          }
+          if (first) {                                     // quad = 8 mb + 2 gq + half: slot 2 quad + e (pairs) or quad
+            if constexpr (pairs) {
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              float* slot = red + (hf * (C::MT / 2) + 2 * quad + e) * 3;
-              slot[0] = cnt; slot[1] = a[e]; slot[2] = b[e];
+              for (int e = 0; e < 2; ++e) {
+                float* slot = slot0 + (4 * gq + e) * 3;
+                slot[0] = cnt; slot[1] = a[e]; slot[2] = b[e];
+              }
+            } else {
+              float* slot = slot0 + 2 * gq * 3;
+              slot[0] = cnt; slot[1] = a[0] + a[1]; slot[2] = b[0] + b[1];
             }
-          } else {
-            float* slot = red + (hf * (C::MT / 4) + quad) * 3;
-            slot[0] = cnt; slot[1] = a[0] + a[1]; slot[2] = b[0] + b[1];
           }
         }
-      }
+      };
+      if (p.gsum_rc == 2) stats(std::true_type{}); else stats(std::false_type{});
       __syncthreads();
       conv_stats_store<C, 2>(p, red, n, m0, tile, tiles_img, tid);
       // the next epilogue writes `red` only after a whole tile of barriers

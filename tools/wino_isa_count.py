@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Instruction classes per K-loop stage of the Winograd conv kernels (device-only compile to assembly, no GPU needed).
+"""Instruction classes per K-loop stage, and of the epilogue, of the Winograd conv kernels (device-only compile to assembly, no GPU needed).
 
-    python tools/wino_isa_count.py [substring-filter ...]
+    python tools/wino_isa_count.py [--epilogue] [substring-filter ...]
 
 conv_wino.hip is compiled for gfx950 with the flags of m-cedm_amd/build.py plus --cuda-device-only -S into a temporary
 directory.  In every conv_wino_kernel instantiation a STAGE is the run of basic blocks in front of an s_barrier that hold
@@ -16,6 +16,13 @@ them (the tile geometry of raw_load_next, taken once per tile) are not part of i
     vmem   global_* / buffer_* / flat_*
     scratch  scratch_* (spill code inside the stage)
     other  any other vector instruction (v_*)
+--epilogue: the EPILOGUE instead -- everything behind the last stage barrier of the loop in program order: the epilogue with all arms of
+its branches (hipcc lays some of them out behind the kernel's end), init_acc() and the kernel's few closing instructions:
+    valu   vector instructions other than MFMAs        mfma   v_mfma_* (init_acc's; the SKIP variant: its projection's too)
+    lds    ds_*          vmem   global_* / buffer_* / flat_*          scratch   scratch_*
+    wait   s_waitcnt     branch   s_cbranch_* / s_branch             barrier   s_barrier
+    vm0_between_loads    s_waitcnt with vmcnt(0) between the first and the last buffer_load of the epilogue: a wait for every load in
+                         flight in front of a further residual load
 It counts instruction classes only.
 """
 import os
@@ -147,6 +154,81 @@ def stages(blocks, want):
     return found
 
 
+EPI_CLASSES = ("valu", "mfma", "lds", "vmem", "scratch", "wait", "branch", "barrier", "vm0_between_loads")
+
+
+def instructions(asm):
+    """{demangled kernel name: [(mnemonic, operands)]} in program order"""
+    funcs, name = {}, None
+    for line in asm.splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            name = m.group(1)
+            funcs[name] = []
+            continue
+        if name is None:
+            continue
+        if re.match(r"^\.Lfunc_end", line):
+            name = None
+            continue
+        m = re.match(r"^\s+([a-z]\w+)\s*([^;]*)", line)
+        if m:
+            funcs[name].append((m.group(1), m.group(2).strip()))
+    mangled = [n for n in funcs if "conv_wino_kernel" in n]
+    if not mangled:
+        return {}
+    dem = subprocess.run(["c++filt"], input="\n".join(mangled), capture_output=True, text=True, check=True).stdout.split("\n")
+    out = {}
+    for n, d in zip(mangled, dem):
+        d = re.sub(r"^void mcedm::", "", d.strip())
+        out[re.sub(r"\(.*$", "", d).replace("mcedm::", "")] = funcs[n]
+    return out
+
+
+def epilogue_of(ins, want):
+    """{class: count} of one kernel's epilogue, or None if the kernel has no stage"""
+    last, prev, n = None, -1, 0
+    for i, (op, _) in enumerate(ins):
+        if classify(op) == "mfma":
+            n += 1
+        if op == "s_barrier":
+            if n == want:
+                last = i
+            prev, n = i, 0
+    if last is None:
+        return None
+    region = ins[last + 1:]
+    c = dict.fromkeys(EPI_CLASSES, 0)
+    loads = [i for i, (op, _) in enumerate(region) if op.startswith("buffer_load")]
+    for i, (op, args) in enumerate(region):
+        k = classify(op)
+        if k == "mfma":
+            c["mfma"] += 1
+        elif k in ("lds", "vmem", "scratch"):
+            c[k] += 1
+        elif k is not None:
+            c["valu"] += 1
+        elif op.startswith("s_waitcnt"):
+            c["wait"] += 1
+            if loads and loads[0] < i < loads[-1] and "vmcnt(0)" in args:
+                c["vm0_between_loads"] += 1
+        elif op.startswith("s_cbranch") or op == "s_branch":
+            c["branch"] += 1
+        elif op == "s_barrier":
+            c["barrier"] += 1
+    return c
+
+
+def epilogues(asm=None):
+    """{kernel name: epilogue counts} of every conv_wino_kernel instantiation that has a stage"""
+    out = {}
+    for name, ins in instructions(asm if asm is not None else compile_asm()).items():
+        c = epilogue_of(ins, stage_mfmas(name))
+        if c:
+            out[name] = c
+    return out
+
+
 def count(asm=None):
     """{kernel name: [stage counts]} of every conv_wino_kernel instantiation that has a stage"""
     out = {}
@@ -158,6 +240,14 @@ def count(asm=None):
 
 
 def main(argv):
+    if "--epilogue" in argv:
+        argv = [a for a in argv if a != "--epilogue"]
+        src = os.environ.get("MCEDM_WINO_SRC")               # another copy of the file (a parent commit's, for comparison)
+        res = epilogues(compile_asm(src) if src else None)
+        for name in sorted(res):
+            if not argv or any(a in name for a in argv):
+                print(f"{name[:76]:76s} epilogue: " + " ".join(f"{k} {res[name][k]}" for k in EPI_CLASSES))
+        return 0
     res = count()
     for name in sorted(res):
         if argv and not any(a in name for a in argv):
