@@ -186,7 +186,7 @@ int mcedm_heun_sample_guided(const mcedm_plan* plan, const void* packed, const m
                              void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
 /* mcedm_heun_sample_guided with rng_seed in place of step_noise: the churn draws are generated on the device exactly as in
  * mcedm_heun_sample_rng (draw index = step index; mcedm_normal_fill's tensors fed to mcedm_heun_sample_guided reproduce the call
- * bit for bit).  A NULL rng_seed is MCEDM_ERR_ARGUMENT; every other check is mcedm_heun_sample_guided's. */
+ * bit for bit).  A NULL rng_seed is MCEDM_ERR_INVALID; every other check is mcedm_heun_sample_guided's. */
 int mcedm_heun_sample_guided_rng(const mcedm_plan* plan, const void* packed, const mcedm_sampler_desc* sp,
                                  const mcedm_guidance_desc* gd, const float* cond, const float* mask, const float* init_noise,
                                  const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes,
@@ -392,7 +392,7 @@ int mcedm_cond_ddim_sample(const mcedm_plan* plan, const void* packed, const mce
  * load, no [S, B, in, H, W] tensor, and a captured HIP graph replays with fresh noise once the host has rewritten the seed.
  * Bit-for-bit contract: mcedm_uniform_fill(slice k of eta_noise, B * in * H * W, rng_seed, k) for every k, handed to
  * mcedm_cond_ddim_sample, reproduces this call.  With |eta| <= 1e-10 the seed is never read.  A NULL rng_seed is
- * MCEDM_ERR_ARGUMENT; every other check is mcedm_cond_ddim_sample's. */
+ * MCEDM_ERR_INVALID; every other check is mcedm_cond_ddim_sample's. */
 int mcedm_cond_ddim_sample_rng(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp, const float* cond,
                                const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last,
                                void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
@@ -770,7 +770,7 @@ int mcedm_ddim_repaint_sample(const mcedm_ddpm_plan* plan, const void* packed, c
                               void* workspace, size_t workspace_bytes, int B, void* stream);
 /* The same with rng_seed in place of eta_noise: step k (in the order the steps are walked) uses draw k of mcedm_uniform_fill,
  * generated inside the step kernel; feeding mcedm_ddim_repaint_sample the tensors mcedm_uniform_fill writes reproduces the call
- * bit for bit.  With |eta| <= 1e-10 the seed is never read.  A NULL rng_seed is MCEDM_ERR_ARGUMENT; every other check is
+ * bit for bit.  With |eta| <= 1e-10 the seed is never read.  A NULL rng_seed is MCEDM_ERR_INVALID; every other check is
  * mcedm_ddim_repaint_sample's. */
 int mcedm_ddim_repaint_sample_rng(const mcedm_ddpm_plan* plan, const void* packed, const mcedm_ddim_desc* sp, const float* hu,
                                   const float* init_noise, const uint64_t* rng_seed, float* xs_out, float* x0_out,

@@ -11,44 +11,32 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCEDM_LIB") or os.path.join(_HERE, "libmcedm_hip.so")   # MCEDM_LIB: A/B builds
-MAX_LEVELS = 8
-
-# every symbol include/mcedm_hip.h declares
-EXPORTS = [
-    "mcedm_version", "mcedm_last_error", "mcedm_unet_plan_create", "mcedm_unet_plan_destroy",
-    "mcedm_unet_param_count", "mcedm_unet_param_info", "mcedm_unet_packed_bytes", "mcedm_unet_pack_weights",
-    "mcedm_unet_workspace_bytes", "mcedm_unet_forward", "mcedm_edm_denoise", "mcedm_sampler_workspace_bytes",
-    "mcedm_heun_sample", "mcedm_edm_t_steps", "mcedm_edm_loss", "mcedm_edm_noise_inputs",
-    "mcedm_edm_denoise_backward", "mcedm_edm_denoise_backward_bucketed", "mcedm_unet_grad_buckets", "mcedm_sqnorm",
-    "mcedm_adam_ema_step",
-    "mcedm_swe_fv_step", "mcedm_swe_fv_residual", "mcedm_darcy_residual", "mcedm_swe_fv_guidance", "mcedm_darcy_guidance",
-    "mcedm_heun_sample_guided",
-    "mcedm_ddpm_plan_create", "mcedm_ddpm_plan_destroy", "mcedm_ddpm_param_count", "mcedm_ddpm_param_info",
-    "mcedm_ddpm_packed_bytes", "mcedm_ddpm_pack_weights", "mcedm_ddpm_workspace_bytes", "mcedm_ddpm_forward",
-    "mcedm_ddpm_denoise", "mcedm_repaint_schedule", "mcedm_repaint_workspace_bytes", "mcedm_repaint_sample",
-    "mcedm_repaint_sample_rng", "mcedm_normal_fill", "mcedm_ddpm_forward_sc", "mcedm_ddim_workspace_bytes",
-    "mcedm_ddim_repaint_sample", "mcedm_ddim_timesteps",
-    "mcedm_unet_forward_dx", "mcedm_edm_denoise_dx", "mcedm_edm_denoise_backward_dx", "mcedm_heun_sample_dxcond",
-    "mcedm_unet_plan_set_variant", "mcedm_ddpm_plan_set_variant", "mcedm_heun_sample_rng",
-    "mcedm_eps_noise_inputs", "mcedm_eps_self_cond", "mcedm_eps_loss", "mcedm_unet_backward", "mcedm_unet_backward_bucketed",
-    "mcedm_vp_sampler_workspace_bytes", "mcedm_vp_heun_sample", "mcedm_vp_heun_sample_rng",
-    "mcedm_cond_ddim_workspace_bytes", "mcedm_cond_ddim_sample",
-    "mcedm_uniform_fill", "mcedm_cond_ddim_sample_rng", "mcedm_ddim_repaint_sample_rng", "mcedm_heun_sample_guided_rng",
-    "mcedm_heun_sample_dxcond_rng",
-    "mcedm_ddpm_plan_create_cond", "mcedm_ddpm_cond_map", "mcedm_ddpm_forward_cond", "mcedm_ddpm_vp_sampler_workspace_bytes",
-    "mcedm_ddpm_vp_heun_sample", "mcedm_ddpm_vp_heun_sample_rng", "mcedm_ddpm_cond_ddim_workspace_bytes",
-    "mcedm_ddpm_cond_ddim_sample", "mcedm_ddpm_cond_ddim_sample_rng",
-    "mcedm_ddpm_forward_cat", "mcedm_ddpm_edm_denoise", "mcedm_ddpm_edm_sampler_workspace_bytes", "mcedm_ddpm_edm_heun_sample",
-    "mcedm_ddpm_edm_heun_sample_rng",
-    "mcedm_swe_fv_unroll",
-    "mcedm_ddpm_temb_row_count", "mcedm_ddpm_temb_rows", "mcedm_ddpm_workspace_bytes_t", "mcedm_ddpm_forward_t",
-    "mcedm_ddpm_edm_denoise_t",
-    "mcedm_vp_guided_workspace_bytes", "mcedm_vp_heun_sample_guided", "mcedm_cond_ddim_guided_workspace_bytes",
-    "mcedm_cond_ddim_sample_guided", "mcedm_ddpm_vp_guided_workspace_bytes", "mcedm_ddpm_vp_heun_sample_guided",
-    "mcedm_ddpm_cond_ddim_guided_workspace_bytes", "mcedm_ddpm_cond_ddim_sample_guided",
-]
+# Every symbol, struct and constant of include/mcedm_hip.h, as abi.py reads them from the header itself: a new entry point is a
+# prototype there, its definition, and a Python method here.  OP_EXPORTS: the kernel-level and measurement entries.
+OP_EXPORTS = [n for n in abi.PROTOS if n.startswith(("mcedm_op_", "mcedm_prof_"))]
+EXPORTS = [n for n in abi.PROTOS if n not in OP_EXPORTS]
+ABI_VERSION, MAX_LEVELS = abi.CONSTS["MCEDM_ABI_VERSION"], abi.CONSTS["MCEDM_MAX_LEVELS"]
+DX_NONE, DX_CAT, DX_ENC = abi.CONSTS["MCEDM_DX_NONE"], abi.CONSTS["MCEDM_DX_CAT"], abi.CONSTS["MCEDM_DX_ENC"]
+GN_SYNC_WORDS, REDUCE_SCRATCH_BYTES = abi.CONSTS["MCEDM_GN_SYNC_WORDS"], abi.CONSTS["MCEDM_REDUCE_SCRATCH_BYTES"]
+SWE_UNROLL_MAX_X = abi.CONSTS["MCEDM_SWE_UNROLL_MAX_X"]
+# kernel families that exist in two forms (MCEDM_VARIANT_*), in index order
+VARIANTS = {k[len("MCEDM_VARIANT_"):].lower(): v for k, v in sorted(abi.CONSTS.items(), key=lambda kv: kv[1])
+            if k.startswith("MCEDM_VARIANT_")}
+# The header's argument structs under the binding's names.  The host arrays behind a pointer field must outlive every call that
+# reads the struct; who keeps them alive is noted with each.
+UNetDesc = abi.STRUCTS["mcedm_unet_desc"]
+SamplerDesc = abi.STRUCTS["mcedm_sampler_desc"]
+GuidanceDesc = abi.STRUCTS["mcedm_guidance_desc"]
+DdpmDesc = abi.STRUCTS["mcedm_ddpm_desc"]
+DdpmCondDesc = abi.STRUCTS["mcedm_ddpm_cond_desc"]
+RepaintDesc = abi.STRUCTS["mcedm_repaint_desc"]            # the caller, with the tensors repaint_desc returns next to the struct
+DdimDesc = abi.STRUCTS["mcedm_ddim_desc"]                  # the caller, likewise (ddim_desc)
+VpSamplerDesc = abi.STRUCTS["mcedm_vp_sampler_desc"]       # the Python object that built the struct (vp_sampler_desc)
+CondDdimDesc = abi.STRUCTS["mcedm_cond_ddim_desc"]         # the Python object that built the struct (cond_ddim_desc)
 # The sampler entries _PlanBase._sample_call drives, with the number of materialised-noise pointers each takes; every one
 # has a "_rng" twin that takes ONE seed pointer in their place.  A new sampler is a row here and a method that names it.
 SAMPLER_STEMS = {
@@ -62,75 +50,6 @@ GUIDED_ENTRIES = {
     "mcedm_vp_heun_sample": "mcedm_vp_heun_sample_guided", "mcedm_ddpm_vp_heun_sample": "mcedm_ddpm_vp_heun_sample_guided",
     "mcedm_cond_ddim_sample": "mcedm_cond_ddim_sample_guided", "mcedm_ddpm_cond_ddim_sample": "mcedm_ddpm_cond_ddim_sample_guided",
 }
-# kernel families that exist in two forms (include/mcedm_hip.h MCEDM_VARIANT_*)
-GN_SYNC_WORDS = 130          # MCEDM_GN_SYNC_WORDS
-VARIANTS = {"conv_wino": 0, "conv_wino1": 1, "conv_resident": 2, "conv8": 3, "attn_fused": 4, "wgrad_wino": 5, "conv1x1_reg": 6,
-            "conv_wino_fold": 7, "conv_wino_upz": 8, "conv_wino_split": 9}
-
-
-class UNetDesc(C.Structure):
-    _fields_ = [("in_channels", C.c_int32), ("cond_channels", C.c_int32), ("out_channels", C.c_int32),
-                ("ch", C.c_int32), ("n_levels", C.c_int32), ("ch_mult", C.c_int32 * MAX_LEVELS),
-                ("num_res_blocks", C.c_int32), ("resolution", C.c_int32), ("n_attn_resolutions", C.c_int32),
-                ("attn_resolutions", C.c_int32 * MAX_LEVELS), ("channels_per_head", C.c_int32), ("eps", C.c_float),
-                ("dx_channels", C.c_int32), ("dx_mode", C.c_int32)]
-
-
-DX_NONE, DX_CAT, DX_ENC = 0, 1, 2      # MCEDM_DX_* (include/mcedm_hip.h)
-ABI_VERSION = 4                        # MCEDM_ABI_VERSION
-REDUCE_SCRATCH_BYTES = 4096 * 8 + 64   # MCEDM_REDUCE_SCRATCH_BYTES
-SWE_UNROLL_MAX_X = 4096                # MCEDM_SWE_UNROLL_MAX_X
-
-
-class SamplerDesc(C.Structure):
-    _fields_ = [("timesteps", C.c_int32), ("sigma_min", C.c_double), ("sigma_max", C.c_double), ("rho", C.c_double),
-                ("S_churn", C.c_double), ("S_min", C.c_double), ("S_max", C.c_double), ("S_noise", C.c_double),
-                ("w", C.c_double), ("sigma_data", C.c_double), ("net_sigma_min", C.c_double),
-                ("net_sigma_max", C.c_double)]
-
-
-class GuidanceDesc(C.Structure):
-    _fields_ = [("system", C.c_int32), ("half_dt", C.c_float), ("dx", C.c_float), ("two_dx", C.c_float), ("sub_h", C.c_float),
-                ("div_h", C.c_float), ("sub_u", C.c_float), ("div_u", C.c_float), ("weight", C.c_double)]
-
-
-class DdpmDesc(C.Structure):
-    _fields_ = [("in_channels", C.c_int32), ("out_channels", C.c_int32), ("ch", C.c_int32), ("n_levels", C.c_int32),
-                ("ch_mult", C.c_int32 * MAX_LEVELS), ("num_res_blocks", C.c_int32), ("resolution", C.c_int32),
-                ("n_attn_resolutions", C.c_int32), ("attn_resolutions", C.c_int32 * MAX_LEVELS), ("self_cond", C.c_int32),
-                ("eps", C.c_float)]
-
-
-class DdpmCondDesc(C.Structure):
-    _fields_ = [("cond_channels", C.c_int32), ("cat_cond", C.c_int32)]
-
-
-class RepaintDesc(C.Structure):
-    _fields_ = [("timesteps", C.c_int32), ("sigma_min", C.c_double), ("sigma_max", C.c_double), ("rho", C.c_double),
-                ("S_churn", C.c_double), ("S_min", C.c_double), ("S_max", C.c_double), ("S_noise", C.c_double),
-                ("w", C.c_double), ("n_repeat", C.c_int32), ("n_time_h", C.c_int32), ("n_time_u", C.c_int32),
-                ("h_ch", C.c_int32), ("u_ch", C.c_int32), ("num_diffusion_timesteps", C.c_int32),
-                ("edm_steps", C.POINTER(C.c_float)), ("alphas_cumprod_ext", C.POINTER(C.c_float))]
-
-
-class DdimDesc(C.Structure):
-    _fields_ = [("timesteps", C.c_int32), ("skip_type", C.c_int32), ("eta", C.c_double), ("n_repeat", C.c_int32),
-                ("n_time_h", C.c_int32), ("n_time_u", C.c_int32), ("h_ch", C.c_int32), ("u_ch", C.c_int32),
-                ("num_diffusion_timesteps", C.c_int32), ("self_cond", C.c_int32), ("alphas_cumprod_ext", C.POINTER(C.c_float))]
-
-
-class VpSamplerDesc(C.Structure):
-    """mcedm_vp_sampler_desc: the host arrays are kept alive by the Python object that built the struct (vp_sampler_desc)."""
-    _fields_ = [("timesteps", C.c_int32), ("cond_channels", C.c_int32), ("t_steps", C.POINTER(C.c_double)),
-                ("t_hat", C.POINTER(C.c_double)), ("c_noise", C.POINTER(C.c_float)), ("S_noise", C.c_double), ("w", C.c_double)]
-
-
-class CondDdimDesc(C.Structure):
-    """mcedm_cond_ddim_desc: the schedule table is kept alive by the Python object that built the struct (cond_ddim_desc)."""
-    _fields_ = [("timesteps", C.c_int32), ("skip_type", C.c_int32), ("eta", C.c_double), ("w", C.c_double),
-                ("cond_channels", C.c_int32), ("self_cond", C.c_int32), ("num_diffusion_timesteps", C.c_int32),
-                ("alphas_cumprod_ext", C.POINTER(C.c_float))]
-
 
 _lib = None
 
@@ -144,142 +63,12 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} not found: build it with `python m-cedm_amd/build.py` "
                            "(hipcc --offload-arch=gfx950); there is no CPU/PyTorch fallback")
     lib = C.CDLL(LIB_PATH)
-    vp, i32, f32p, f64p, sz = C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t
-    lib.mcedm_version.restype = C.c_int
-    if lib.mcedm_version() != ABI_VERSION:           # struct layouts below are those of include/mcedm_hip.h at this version
+    if lib.mcedm_version() != ABI_VERSION:           # the signatures and struct layouts applied below are those of this version
         raise RuntimeError(f"{LIB_PATH} implements ABI {lib.mcedm_version()}, this binding ABI {ABI_VERSION}: rebuild it with "
                            "`python m-cedm_amd/build.py`")
-    lib.mcedm_last_error.restype = C.c_char_p
-    lib.mcedm_unet_plan_create.argtypes = [C.POINTER(UNetDesc), C.POINTER(vp)]
-    lib.mcedm_unet_plan_destroy.argtypes = [vp]
-    lib.mcedm_unet_plan_destroy.restype = None
-    lib.mcedm_unet_param_count.argtypes = [vp]
-    lib.mcedm_unet_param_info.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                          C.POINTER(C.c_int64 * 4)]
-    lib.mcedm_unet_packed_bytes.argtypes = [vp, C.POINTER(sz)]
-    lib.mcedm_unet_pack_weights.argtypes = [vp, C.POINTER(vp), vp, vp]
-    lib.mcedm_unet_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, C.POINTER(sz)]
-    lib.mcedm_unet_forward.argtypes = [vp, vp, f32p, f32p, f32p, f32p, i32, f32p, vp, sz, i32, i32, i32, i32, vp]
-    lib.mcedm_edm_denoise.argtypes = [vp, vp, f32p, f32p, i32, f32p, f32p, f32p, vp, sz, i32, i32, i32, i32,
-                                      C.c_double, vp]
-    lib.mcedm_sampler_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
-    lib.mcedm_heun_sample.argtypes = [vp, vp, C.POINTER(SamplerDesc), f32p, f32p, f32p, f64p, f64p, i32, vp, sz,
-                                      i32, i32, i32, vp]
-    lib.mcedm_heun_sample_rng.argtypes = [vp, vp, C.POINTER(SamplerDesc), f32p, f32p, f32p, vp, f64p, i32, vp, sz,
-                                          i32, i32, i32, vp]
-    lib.mcedm_unet_plan_set_variant.argtypes = [vp, i32, i32]
-    lib.mcedm_ddpm_plan_set_variant.argtypes = [vp, i32, i32]
-    lib.mcedm_edm_t_steps.argtypes = [C.POINTER(SamplerDesc), C.POINTER(C.c_double)]
-    lib.mcedm_edm_loss.argtypes = [f32p, f32p, f32p, f32p, i32, i32, i32, i32, C.c_double, f32p, f32p, vp, sz, vp]
-    lib.mcedm_edm_noise_inputs.argtypes = [f32p, f32p, f32p, f32p, i32, i32, i32, i32, C.c_double, C.c_double, f32p,
-                                           f32p, vp]
-    lib.mcedm_edm_denoise_backward.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, i32, f32p, f32p, C.POINTER(vp), vp,
-                                               sz, i32, i32, i32, C.c_double, vp]
-    lib.mcedm_edm_denoise_backward_bucketed.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, i32, f32p, f32p, C.POINTER(vp),
-                                                        vp, sz, i32, i32, i32, C.c_double, i32, C.POINTER(C.c_int32),
-                                                        C.POINTER(vp), vp]
-    lib.mcedm_unet_grad_buckets.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
-    lib.mcedm_unet_forward_dx.argtypes = [vp, vp, f32p, f32p, f32p, f32p, f32p, i32, f32p, vp, sz, i32, i32, i32, i32, vp]
-    lib.mcedm_edm_denoise_dx.argtypes = [vp, vp, f32p, f32p, f32p, i32, f32p, f32p, f32p, vp, sz, i32, i32, i32, i32,
-                                         C.c_double, vp]
-    lib.mcedm_edm_denoise_backward_dx.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, f32p, i32, f32p, f32p, C.POINTER(vp),
-                                                  vp, sz, i32, i32, i32, C.c_double, i32, C.POINTER(C.c_int32),
-                                                  C.POINTER(vp), vp]
-    lib.mcedm_heun_sample_dxcond.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), C.POINTER(GuidanceDesc),
-                                             f32p, f32p, f64p, f64p, i32, vp, sz, i32, i32, i32, vp]
-    lib.mcedm_sqnorm.argtypes = [f32p, sz, f64p, vp, sz, vp]
-    lib.mcedm_adam_ema_step.argtypes = [f32p, f32p, f32p, f32p, f32p, sz, C.c_double, C.c_double, C.c_double,
-                                        C.c_double, C.c_double, f64p, C.c_double, C.c_double, C.c_double, C.c_int64, vp]
-    lib.mcedm_swe_fv_step.argtypes = [f32p, f32p, i32, i32, i32, C.c_float, C.c_float, vp]
-    lib.mcedm_swe_fv_unroll.argtypes = [f32p, sz, f32p, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp]
-    lib.mcedm_swe_fv_residual.argtypes = [f32p, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float,
-                                          i32, vp]
-    lib.mcedm_darcy_residual.argtypes = [f32p, f32p, i32, i32, C.c_float, C.c_float, i32, vp]
-    lib.mcedm_swe_fv_guidance.argtypes = [f32p, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp]
-    lib.mcedm_darcy_guidance.argtypes = [f32p, f32p, f32p, i32, i32, C.c_float, i32, vp]
-    lib.mcedm_heun_sample_guided.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), f32p, f32p, f32p, f64p,
-                                             f64p, i32, vp, sz, i32, i32, i32, vp]
-    lib.mcedm_heun_sample_guided_rng.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), f32p, f32p, f32p, vp,
-                                                 f64p, i32, vp, sz, i32, i32, i32, vp]
-    lib.mcedm_heun_sample_dxcond_rng.argtypes = [vp, vp, C.POINTER(SamplerDesc), C.POINTER(GuidanceDesc), C.POINTER(GuidanceDesc),
-                                                 f32p, f32p, vp, f64p, i32, vp, sz, i32, i32, i32, vp]
-    lib.mcedm_ddpm_plan_create.argtypes = [C.POINTER(DdpmDesc), C.POINTER(vp)]
-    lib.mcedm_ddpm_plan_destroy.argtypes = [vp]
-    lib.mcedm_ddpm_plan_destroy.restype = None
-    lib.mcedm_ddpm_param_count.argtypes = [vp]
-    lib.mcedm_ddpm_param_info.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
-                                          C.POINTER(C.c_int64 * 4)]
-    lib.mcedm_ddpm_packed_bytes.argtypes = [vp, C.POINTER(sz)]
-    lib.mcedm_ddpm_pack_weights.argtypes = [vp, C.POINTER(vp), f32p, vp, vp]
-    lib.mcedm_ddpm_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_forward.argtypes = [vp, vp, f32p, C.c_float, f32p, vp, sz, i32, vp]
-    lib.mcedm_ddpm_denoise.argtypes = [vp, vp, f32p, C.c_float, C.c_float, f32p, f32p, vp, sz, i32, vp]
-    lib.mcedm_repaint_schedule.argtypes = [C.POINTER(RepaintDesc), C.POINTER(C.c_double)]
-    lib.mcedm_repaint_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_repaint_sample.argtypes = [vp, vp, C.POINTER(RepaintDesc), f32p, f32p, f64p, f64p, f64p, i32, vp, sz, i32, vp]
-    lib.mcedm_repaint_sample_rng.argtypes = [vp, vp, C.POINTER(RepaintDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, vp]
-    lib.mcedm_normal_fill.argtypes = [f64p, sz, vp, C.c_uint64, vp]
-    lib.mcedm_uniform_fill.argtypes = [f32p, sz, vp, C.c_uint64, vp]
-    lib.mcedm_ddpm_forward_sc.argtypes = [vp, vp, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
-    lib.mcedm_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddim_repaint_sample.argtypes = [vp, vp, C.POINTER(DdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddim_repaint_sample_rng.argtypes = [vp, vp, C.POINTER(DdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddim_timesteps.argtypes = [i32, i32, i32, C.POINTER(C.c_int), i32, C.POINTER(C.c_int)]
-    lib.mcedm_eps_noise_inputs.argtypes = [f32p, f32p, vp, f32p, f32p, i32, i32, i32, i32, i32, f32p, f32p, vp]
-    lib.mcedm_eps_self_cond.argtypes = [f32p, f32p, vp, f32p, f32p, i32, f32p, i32, i32, i32, i32, i32, f32p, vp]
-    lib.mcedm_eps_loss.argtypes = [f32p, f32p, i32, i32, i32, i32, f32p, f32p, vp, sz, vp]
-    lib.mcedm_unet_backward.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, f32p, f32p, i32, f32p, C.POINTER(vp), vp, sz, i32,
-                                        i32, i32, vp]
-    lib.mcedm_unet_backward_bucketed.argtypes = [vp, vp, C.POINTER(vp), f32p, f32p, f32p, f32p, i32, f32p, C.POINTER(vp), vp,
-                                                 sz, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(vp), vp]
-    lib.mcedm_vp_sampler_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
-    lib.mcedm_vp_heun_sample.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, f64p, f64p, i32, vp, sz, i32, i32, i32,
-                                         vp]
-    lib.mcedm_vp_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, i32,
-                                             i32, vp]
-    lib.mcedm_cond_ddim_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
-    lib.mcedm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, i32,
-                                           i32, vp]
-    lib.mcedm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32,
-                                               i32, i32, vp]
-    lib.mcedm_ddpm_plan_create_cond.argtypes = [C.POINTER(DdpmDesc), C.POINTER(DdpmCondDesc), C.POINTER(vp)]
-    lib.mcedm_ddpm_cond_map.argtypes = [vp, vp, f32p, f32p, i32, vp]
-    lib.mcedm_ddpm_forward_cond.argtypes = [vp, vp, f32p, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
-    lib.mcedm_ddpm_vp_sampler_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_vp_heun_sample.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, f64p, f64p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddpm_vp_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), f32p, f32p, vp, f64p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddpm_cond_ddim_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_cond_ddim_sample.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, f32p, f32p, f32p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddpm_cond_ddim_sample_rng.argtypes = [vp, vp, C.POINTER(CondDdimDesc), f32p, f32p, vp, f32p, f32p, i32, vp, sz, i32, vp]
-    gdp = C.POINTER(GuidanceDesc)
-    lib.mcedm_vp_guided_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
-    lib.mcedm_vp_heun_sample_guided.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), gdp, f32p, f32p, f64p, vp, f64p, i32, vp, sz, i32,
-                                                i32, i32, vp]
-    lib.mcedm_cond_ddim_guided_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
-    lib.mcedm_cond_ddim_sample_guided.argtypes = [vp, vp, C.POINTER(CondDdimDesc), gdp, f32p, f32p, f32p, vp, f32p, f32p, i32, vp, sz,
-                                                  i32, i32, i32, vp]
-    lib.mcedm_ddpm_vp_guided_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_vp_heun_sample_guided.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), gdp, f32p, f32p, f64p, vp, f64p, i32, vp, sz,
-                                                     i32, vp]
-    lib.mcedm_ddpm_cond_ddim_guided_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_cond_ddim_sample_guided.argtypes = [vp, vp, C.POINTER(CondDdimDesc), gdp, f32p, f32p, f32p, vp, f32p, f32p, i32, vp,
-                                                       sz, i32, vp]
-    lib.mcedm_ddpm_forward_cat.argtypes = [vp, vp, f32p, f32p, C.c_float, f32p, vp, sz, i32, vp]
-    lib.mcedm_ddpm_edm_denoise.argtypes = [vp, vp, f32p, f32p, C.c_float, C.c_float, C.c_double, C.c_double, f32p, f32p, vp, sz, i32, vp]
-    lib.mcedm_ddpm_edm_sampler_workspace_bytes.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_edm_heun_sample.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), C.c_double, C.POINTER(GuidanceDesc), f32p, f32p, f64p,
-                                               f64p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddpm_edm_heun_sample_rng.argtypes = [vp, vp, C.POINTER(VpSamplerDesc), C.c_double, C.POINTER(GuidanceDesc), f32p, f32p, vp,
-                                                   f64p, i32, vp, sz, i32, vp]
-    lib.mcedm_ddpm_temb_row_count.argtypes = [vp, C.POINTER(i32)]
-    lib.mcedm_ddpm_temb_rows.argtypes = [vp, vp, f32p, i32, f32p, vp]
-    lib.mcedm_ddpm_workspace_bytes_t.argtypes = [vp, i32, C.POINTER(sz)]
-    lib.mcedm_ddpm_forward_t.argtypes = [vp, vp, f32p, f32p, f32p, f32p, f32p, f32p, vp, sz, i32, vp]
-    lib.mcedm_ddpm_edm_denoise_t.argtypes = [vp, vp, f32p, f32p, f32p, C.c_double, f32p, f32p, vp, sz, i32, vp]
-    for name in EXPORTS:
+    for name, (restype, argtypes) in abi.PROTOS.items():
         fn = getattr(lib, name)          # AttributeError here == header/library drift
-        if name not in ("mcedm_last_error", "mcedm_unet_plan_destroy", "mcedm_ddpm_plan_destroy"):
-            fn.restype = C.c_int
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -1429,86 +1218,13 @@ def adam_ema_step(param, grad, exp_avg, exp_avg_sq, ema, step, lr=2e-4, beta1=0.
 
 
 # ---- kernel-level ops (tests, per-kernel timing) ---------------------------------------------------
-_OPS_BOUND = False
-
-
-def _bind_ops():
-    global _OPS_BOUND
-    lib = load()
-    if _OPS_BOUND:
-        return lib
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    lib.mcedm_op_conv_packed_floats.argtypes = [i32, i32, i32]
-    lib.mcedm_op_conv_packed_floats.restype = sz
-    lib.mcedm_op_pack_conv.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.mcedm_op_gn_coef.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp]
-    lib.mcedm_op_conv.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32,
-                                  i32, i32, vp]
-    lib.mcedm_op_attention.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.mcedm_op_attn_block64.argtypes = [vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.mcedm_op_embedding.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.mcedm_op_wgrad_scratch_floats.argtypes = [i32, i32, i32, i32, i32, i32]
-    lib.mcedm_op_wgrad_scratch_floats.restype = sz
-    lib.mcedm_op_conv_wgrad.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                                        vp, vp, vp, vp]
-    lib.mcedm_op_gn_bwd.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
-                                    i32, vp, i32, vp, vp, vp, vp, i32, vp]
-    lib.mcedm_op_gn_bwd_sync.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
-                                         i32, vp, i32, vp, vp, vp, vp, i32, vp, vp]
-    lib.mcedm_op_attention_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp]
-    lib.mcedm_op_conv_wino_packed_floats.argtypes = [i32, i32]
-    lib.mcedm_op_conv_wino_packed_floats.restype = sz
-    lib.mcedm_op_pack_conv_wino.argtypes = [vp, i32, i32, vp, vp]
-    lib.mcedm_op_pack_conv_wino_dgrad.argtypes = [vp, i32, i32, vp, vp]
-    lib.mcedm_op_conv_wino.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
-    lib.mcedm_op_conv_wino_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
-    lib.mcedm_op_conv_wino_split.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp]
-    lib.mcedm_op_conv_wino_split_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
-    lib.mcedm_op_conv_bias_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32,
-                                             i32, i32, vp]
-    lib.mcedm_op_conv_wino_sums_bias_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32,
-                                                       i32, vp]
-    lib.mcedm_op_pack_conv_frag.argtypes = [vp, i32, i32, vp, vp]
-    lib.mcedm_op_conv_skip.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]
-    f32 = C.c_float
-    lib.mcedm_op_conv_sums.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32,
-                                       vp, i32, vp, vp]
-    lib.mcedm_op_gn_coef_from_sums.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp, vp, vp]
-    lib.mcedm_op_conv_gn.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, i32, i32, vp, vp,
-                                     vp, vp, i32, vp, i32, i32, i32, vp]
-    lib.mcedm_op_ddim_cond_step.argtypes = [vp, vp, vp, vp, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32, i32, i32, i32,
-                                            i32, vp, i32, i32, vp, i32, i32, vp]
-    lib.mcedm_op_ddim_cond_step_rng.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_double, f32, f32, f32, f32, f32, vp, vp, vp, i32, i32,
-                                                i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
-    lib.mcedm_op_ddim_cond_step_guided.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, vp, f32, C.c_double, f32, f32, f32, f32, f32, vp, vp,
-                                                   vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]
-    for n in ("mcedm_op_ddim_cond_step_guided", "mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv", "mcedm_op_attention", "mcedm_op_embedding", "mcedm_op_conv_wgrad",
-              "mcedm_op_gn_bwd", "mcedm_op_gn_bwd_sync", "mcedm_op_attention_bwd", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino",
-              "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_wino_dgrad", "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
-              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
-              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn", "mcedm_op_conv_wino_split", "mcedm_op_conv_wino_split_sums"):
-        getattr(lib, n).restype = C.c_int
-    for n in VARIANTS:
-        getattr(lib, "mcedm_op_set_" + n).argtypes = [i32]
-    _OPS_BOUND = True
-    return lib
-
-
-OP_EXPORTS = ["mcedm_op_conv_packed_floats", "mcedm_op_pack_conv", "mcedm_op_gn_coef", "mcedm_op_conv",
-              "mcedm_op_attention", "mcedm_op_set_conv_tile", "mcedm_prof_enable", "mcedm_prof_report",
-              "mcedm_op_wgrad_scratch_floats", "mcedm_op_conv_wgrad", "mcedm_op_gn_bwd", "mcedm_op_attention_bwd",
-              "mcedm_op_set_conv_debug", "mcedm_op_set_conv8", "mcedm_op_set_conv_resident", "mcedm_op_set_attn_fused", "mcedm_op_embedding",
-              "mcedm_op_conv_wino_packed_floats", "mcedm_op_pack_conv_wino", "mcedm_op_conv_wino", "mcedm_op_set_conv_wino", "mcedm_op_set_conv_wino1",
-              "mcedm_op_set_wgrad_wino", "mcedm_op_set_conv1x1_reg", "mcedm_op_gn_bwd_sync", "mcedm_op_pack_conv_wino_dgrad",
-              "mcedm_op_ddim_cond_step", "mcedm_op_ddim_cond_step_rng", "mcedm_op_set_conv_wino_fold", "mcedm_op_set_conv_wino_upz", "mcedm_op_conv_wino_sums", "mcedm_op_pack_conv_frag", "mcedm_op_conv_skip",
-              "mcedm_op_attn_block64", "mcedm_op_conv_bias_batch", "mcedm_op_conv_wino_sums_bias_batch", "mcedm_op_conv_sums",
-              "mcedm_op_gn_coef_from_sums", "mcedm_op_conv_gn", "mcedm_op_conv_wino_split", "mcedm_op_conv_wino_split_sums",
-              "mcedm_op_set_conv_wino_split", "mcedm_op_ddim_cond_step_guided"]
+def _bind_ops() -> C.CDLL:
+    """The loaded library; load() binds the kernel-level entries with every other one."""
+    return load()
 
 
 def prof_enable(on: bool) -> None:
     lib = load()
-    lib.mcedm_prof_enable.argtypes = [C.c_int]
     check(lib.mcedm_prof_enable(int(on)), "prof_enable")
 
 
@@ -1516,7 +1232,6 @@ def prof_report() -> list:
     """Kernel-level timing rows collected since prof_enable(True) (synchronises the recorded events)."""
     import json
     lib = load()
-    lib.mcedm_prof_report.argtypes = [C.c_char_p, C.c_size_t]
     buf = C.create_string_buffer(1 << 16)
     check(lib.mcedm_prof_report(buf, len(buf)), "prof_report")
     return json.loads(buf.value.decode())
@@ -1525,7 +1240,6 @@ def prof_report() -> list:
 def set_conv_tile(mt: int = 0, ph: int = 0, pw: int = 0) -> None:
     """Test hook: force the conv tile configuration; () restores the heuristic."""
     lib = _bind_ops()
-    lib.mcedm_op_set_conv_tile.argtypes = [C.c_int, C.c_int, C.c_int]
     check(lib.mcedm_op_set_conv_tile(mt, ph, pw), "set_conv_tile")
 
 
@@ -1568,7 +1282,6 @@ def set_conv_debug(buf: Optional[torch.Tensor] = None) -> None:
     64-bit words, 16 per blockIdx.x workgroup of the launches that follow; the Winograd kernels put their tiles per workgroup
     into word 4.  None switches the records off.  The caller keeps buf alive, and large enough, until it has cleared the hook."""
     lib = _bind_ops()
-    lib.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
     if buf is not None and (not buf.is_cuda or buf.element_size() != 8 or not buf.is_contiguous() or buf.numel() % 16):
         raise ValueError("set_conv_debug: buf must be a contiguous device tensor of 64-bit words, 16 per workgroup")
     check(lib.mcedm_op_set_conv_debug(buf.data_ptr() if buf is not None else None), "set_conv_debug")

@@ -4,12 +4,15 @@ schedule, argument validation) behave as documented."""
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
+import sys
 
 import pytest
 import torch
 
 import mcedm_amd  # noqa: F401
+from mcedm_amd import abi
 from mcedm_amd import lib as L
 from oracle import mcedm_oracle as orc
 
@@ -17,9 +20,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "mcedm_hip.h")
 
 
-def declared_symbols():
+def declared_symbols(with_args=False):
+    """The names the header declares (or name -> argument text), by a regex of this file's own: independent of mcedm_amd.abi."""
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    if with_args:
+        return dict(re.findall(r"\b(mcedm_[a-z0-9_]+)\s*\(([^)]*)\)", src))
     return sorted(set(re.findall(r"\b(mcedm_[a-z0-9_]+)\s*\(", src)))
 
 
@@ -27,8 +33,13 @@ def test_library_exports_every_declared_symbol():
     lib = L.load()
     names = declared_symbols()
     assert len(names) >= 36
-    for n in names:
-        getattr(lib, n)                                  # AttributeError == header / library drift
+    assert set(abi.PROTOS) == set(names), set(abi.PROTOS) ^ set(names)
+    for n, args in declared_symbols(with_args=True).items():
+        fn = getattr(lib, n)                             # AttributeError == header / library drift
+        void = args.strip() == "void"
+        assert fn.argtypes or void, n                    # bound, with its argument types
+        assert len(fn.argtypes) == (0 if void else args.count(",") + 1), n
+    assert len(declared_symbols(with_args=True)) == len(names)
     nm = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(set(re.findall(r"\bT (mcedm_[a-z0-9_]+)$", nm, flags=re.M)))
     assert exported == names, (set(exported) ^ set(names))
@@ -41,6 +52,89 @@ def test_library_exports_every_declared_symbol():
     assert consts["MCEDM_GN_SYNC_WORDS"] == L.GN_SYNC_WORDS
     for name, idx in L.VARIANTS.items():
         assert consts["MCEDM_VARIANT_" + name.upper()] == idx, name
+
+
+# The C spelling of each scalar class, this file's own (size_t and uint64_t are one class to ctypes and one type to the compiler on
+# LP64).  A scalar that mcedm_amd.abi misread is spelled wrongly below, and the compiler refuses it.
+_C_SCALAR = {C.c_int: "int", C.c_int64: "int64_t", C.c_uint64: "uint64_t", C.c_float: "float", C.c_double: "double"}
+
+
+def _c_type(ctype, text):
+    """How the generated C spells one parsed type: a scalar by its ctypes class, a pointer as abi.DECLS gives it."""
+    if ctype is None:
+        return "void"
+    if ctype in _C_SCALAR:
+        return _C_SCALAR[ctype]
+    assert "*" in text or "[" in text, (ctype, text)
+    if ctype not in (C.c_void_p, C.c_char_p):            # POINTER(struct): the struct the header names
+        assert text == f"const {ctype._type_.__name__}*" and abi.STRUCTS[ctype._type_.__name__] is ctype._type_, text
+    else:
+        assert (ctype is C.c_char_p) == (text.replace("const ", "") == "char*"), text
+    return text
+
+
+def _prototypes_c(protos):
+    lines = ['#include "mcedm_hip.h"']
+    for n, (ret, args) in protos.items():
+        rtext, atexts = abi.DECLS[n]
+        assert len(args) == len(atexts), n
+        lines.append(f"{_c_type(ret, rtext)} (*p_{n})({', '.join(map(_c_type, args, atexts)) or 'void'}) = &{n};")
+    return "\n".join(lines) + "\n"
+
+
+def test_parsed_abi_agrees_with_a_c_compiler(tmp_path):
+    """What mcedm_amd.abi read from the header, handed back to a C compiler next to the header itself.  Every prototype: its address
+    initialises a function pointer whose type is spelled from abi.PROTOS (compiled, not linked), so a miscounted or misread argument
+    or return type is an incompatible-pointer error.  Every struct: sizeof, each field's offset and a pointer of the parsed type to
+    each field, against the ctypes classes."""
+    cc = next(filter(None, map(shutil.which, ("cc", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang")))), None)
+    assert cc, "no C compiler found (cc, or ROCm's clang): m-cedm_amd/build.py needs one as well"
+
+    def compile_c(name, text, *flags):
+        (tmp_path / name).write_text(text)
+        return subprocess.run([cc, "-std=c11", "-I" + os.path.dirname(HEADER), "-Werror=incompatible-pointer-types", "-Werror=int-conversion",
+                               *flags, name], cwd=tmp_path, capture_output=True, text=True)
+
+    r = compile_c("protos.c", _prototypes_c(abi.PROTOS), "-c")
+    assert r.returncode == 0, r.stderr[-3000:]
+    # the check has teeth: size_t read as int, and double read as float, are refused
+    ret, args = abi.PROTOS["mcedm_sqnorm"]
+    assert args[1] is C.c_size_t
+    assert compile_c("bad0.c", _prototypes_c({"mcedm_sqnorm": (ret, [args[0], C.c_int] + args[2:])}), "-c").returncode != 0
+    ret, args = abi.PROTOS["mcedm_edm_denoise"]
+    assert args[-2] is C.c_double
+    assert compile_c("bad1.c", _prototypes_c({"mcedm_edm_denoise": (ret, args[:-2] + [C.c_float, args[-1]])}), "-c").returncode != 0
+
+    assert len(abi.STRUCTS) == 10
+    lines, want = ["#include <stdio.h>", '#include "mcedm_hip.h"', "int main(void) {"], {}
+    for s, cls in abi.STRUCTS.items():
+        lines += [f"  static {s} v_{s};", f'  printf("{s} %zu\\n", sizeof({s}));']
+        want[s] = C.sizeof(cls)
+        for f, t in cls._fields_:
+            if hasattr(t, "_length_"):
+                spelled = f"{_C_SCALAR[t._type_]} (*q)[{t._length_}]"
+            elif t in _C_SCALAR:
+                spelled = f"{_C_SCALAR[t]} *q"
+            else:                                        # (every pointer field of the header points at const)
+                spelled = f"const {_C_SCALAR[t._type_]} **q"
+            lines += [f'  printf("{s}.{f} %zu\\n", offsetof({s}, {f}));', f"  {{ {spelled} = &v_{s}.{f}; (void)q; }}"]
+            want[f"{s}.{f}"] = getattr(cls, f).offset
+    r = compile_c("sizes.c", "\n".join(lines + ["  return 0;", "}"]) + "\n", "-o", "sizes")
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = subprocess.run([str(tmp_path / "sizes")], capture_output=True, text=True, check=True).stdout
+    assert {k: int(v) for k, v in (line.split() for line in out.splitlines())} == want
+
+
+@pytest.mark.parametrize("line,text", [(3, "typedef union { int a; float b; } mcedm_u;"), (2, "#define MCEDM_TWICE(x) (2 * (x))"),
+                                       (3, "int mcedm_f(unsigned int flags);"), (3, "int mcedm_g(int (*callback)(void));"),
+                                       (4, "}")])
+def test_header_parser_refuses_what_it_does_not_know(tmp_path, line, text):
+    """A construct outside the header's own grammar is an error that names the file and line, never skipped: a by-value type with no
+    ctypes class here, a union, a function-like macro, a callback, a stray brace.  MCEDM_HEADER selects the header read."""
+    hdr = tmp_path / "other.h"
+    hdr.write_text("\n" * (line - 1) + text + "\n")
+    r = subprocess.run([sys.executable, abi.__file__], env=dict(os.environ, MCEDM_HEADER=str(hdr)), capture_output=True, text=True)
+    assert r.returncode != 0 and f"ValueError: {hdr}:{line}: " in r.stderr, r.stderr[-2000:]
 
 
 def test_plan_parameter_table_matches_state_dict_order():
@@ -352,7 +446,6 @@ def test_plan_variants_are_per_plan_and_validated():
     pa.set_variant("conv_wino", -1)
     assert pa.workspace_bytes(2, 64, 64) == base
     lib = L.load()
-    lib.mcedm_unet_plan_set_variant.argtypes = [C.c_void_p, C.c_int, C.c_int]
     assert lib.mcedm_unet_plan_set_variant(pa._h, 99, 1) != 0 and b"unknown switch" in lib.mcedm_last_error()
     assert lib.mcedm_unet_plan_set_variant(pa._h, 0, 7) != 0
 

@@ -1,6 +1,6 @@
 """In-kernel phase counters of the 1x1 conv at 128^2 (decoder skip projection 256 -> 128): needs the -DMCEDM_CONV_TIMELINE build
     tools/build_ab.sh ctl "-DMCEDM_CONV_TIMELINE" conv_mfma.hip;  MCEDM_LIB=m-cedm_amd/_ab/ctl.so python tools/conv1x1_timeline.py [cin cout hw]"""
-import os, sys, ctypes as C
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mcedm_amd  # noqa
@@ -21,7 +21,7 @@ us = e0.elapsed_time(e1) / 10 * 1e3
 print(f"{cin}->{cout} 1x1 @{hw}^2 B={B}: {us:.1f} us = {2.0 * B * hw * hw * cin * cout / us / 1e6:.1f} TFLOP/s, {4.0 * B * hw * hw * (cin + cout) / us / 1e6:.2f} TB/s")
 nb = B * (hw // 8) * (hw // 32) * max(1, cout // 128)
 dbg = torch.zeros(nb * 16 * 4, dtype=torch.int64, device="cuda")
-l = lib._bind_ops(); l.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
+l = lib._bind_ops()
 l.mcedm_op_set_conv_debug(dbg.data_ptr())
 for _ in range(4): run()
 torch.cuda.synchronize()

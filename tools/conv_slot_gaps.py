@@ -5,7 +5,6 @@ start in the same resident slot is summed.
     python tools/conv_slot_gaps.py B cin cout hw [res]
 """
 import collections
-import ctypes as C
 import os
 import sys
 
@@ -32,7 +31,6 @@ torch.cuda.synchronize()
 nb = 8192
 dbg = torch.zeros(nb * 16, dtype=torch.int64, device="cuda")
 l = lib._bind_ops()
-l.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
 l.mcedm_op_set_conv_debug(dbg.data_ptr())
 run()
 torch.cuda.synchronize()

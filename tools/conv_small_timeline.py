@@ -2,7 +2,6 @@
 
     python tools/conv_small_timeline.py B cin cout hw k [res] [gn]
 """
-import ctypes as C
 import os
 import sys
 
@@ -36,7 +35,6 @@ us = e0.elapsed_time(e1) / 50 * 1e3
 nb = 8192
 dbg = torch.zeros(nb * 16, dtype=torch.int64, device="cuda")
 l = lib._bind_ops()
-l.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
 l.mcedm_op_set_conv_debug(dbg.data_ptr())
 for _ in range(5):
     run()

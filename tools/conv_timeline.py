@@ -1,5 +1,5 @@
 """Diagnostic: per-workgroup timeline of the dominant conv (timestamps written by the kernel itself)."""
-import os, sys, ctypes as C
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mcedm_amd  # noqa
@@ -12,7 +12,7 @@ wpk, bpk = lib.op_pack_conv(w, b); out = torch.empty(B, cout, hw, hw, device="cu
 for _ in range(3): lib.op_conv(x, None, wpk, bpk, cout, 3, coef=coef, act=1, res=res, out=out)
 nb = B * (hw // 8) * (hw // 32)
 dbg = torch.zeros(nb * 16, dtype=torch.int64, device="cuda")
-l = lib._bind_ops(); l.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
+l = lib._bind_ops()
 l.mcedm_op_set_conv_debug(dbg.data_ptr())
 for _ in range(12):   # steady state (clocks, caches): every launch overwrites the records, the last one is read
     lib.op_conv(x, None, wpk, bpk, cout, 3, coef=coef, act=1, res=res, out=out)

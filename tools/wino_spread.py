@@ -1,6 +1,6 @@
 """Finish-time spread of the persistent Winograd workgroups (one per CU): how much of a launch its fastest CUs idle.
     python tools/wino_spread.py [B cin hw]"""
-import ctypes as C, importlib, os, sys
+import importlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lib = importlib.import_module("m-cedm_amd.lib")
@@ -19,7 +19,6 @@ for _ in range(5):
 torch.cuda.synchronize()
 nb = B * (hw // 8) * (hw // 16)
 l = lib._bind_ops()
-l.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
 for rep in range(3):
     dbg = torch.zeros(nb * 16, dtype=torch.int64, device="cuda")
     l.mcedm_op_set_conv_debug(dbg.data_ptr())

@@ -7,7 +7,7 @@ every conv of the sampler but out_conv writes them (0, the default: the statisti
 sk > 0: conv1 of a decoder block with its 1x1 skip projection of sk channels (two sources of sk / 2) folded in -- the SKIP variant
 (MCEDM_WINO_FOLD=0: the same conv on the direct kernels) -- instead of a residual; with MCEDM_WINO_MODE=32 the second epilogue
 phase is then the projection with the exchange rounds inside it (budget: 48 k cycles per tile at 256 channels)."""
-import ctypes as C, importlib, os, sys
+import importlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lib = importlib.import_module("m-cedm_amd.lib")
@@ -55,7 +55,6 @@ us = e0.elapsed_time(e1) / 10 * 1e3
 nb = B * (hw // 8) * (hw // 16)
 dbg = torch.zeros(nb * 16, dtype=torch.int64, device="cuda")
 l = lib._bind_ops()
-l.mcedm_op_set_conv_debug.argtypes = [C.c_void_p]
 l.mcedm_op_set_conv_debug(dbg.data_ptr())
 run()
 torch.cuda.synchronize()
