@@ -180,6 +180,25 @@ extern "C" int mcedm_unet_plan_create(const mcedm_unet_desc* d, mcedm_plan** out
         delete Pp;
         return MCEDM_ERR_UNSUPPORTED;
       }
+  // GroupNorm(C) has min(32, C / 4) groups (adm_blocks.py:89), which must divide C: a width or a concat of 128 channels or more
+  // that is not a multiple of 32 (144 = 96 + 48) is no network of the reference's either, and is refused here, not at the first forward
+  {
+    std::vector<std::pair<std::string, const NormP*>> norms;
+    for (auto* v : {&P.enc, &P.dec})
+      for (const BlockP& b : *v) {
+        norms.push_back({b.key + ".norm0", &b.norm0});
+        norms.push_back({b.key + ".norm1", &b.norm1});
+        if (b.attn) norms.push_back({b.key + ".norm2", &b.norm2});
+      }
+    norms.push_back({"out_norm", &P.out_norm});
+    for (const auto& kn : norms)
+      if (kn.second->groups <= 0 || kn.second->C % kn.second->groups != 0) {
+        set_error("plan_create: GroupNorm %s has %d channels, not a multiple of its %d groups (min(32, C / 4))", kn.first.c_str(),
+                  kn.second->C, kn.second->groups);
+        delete Pp;
+        return MCEDM_ERR_UNSUPPORTED;
+      }
+  }
 
   // packed-buffer layout
   Taker t;

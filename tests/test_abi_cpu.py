@@ -183,6 +183,18 @@ def test_attention_width_not_a_multiple_of_64_is_rejected(ch, mult, attn):
         L.Plan(2, 2, 2, ch, mult, 1, attn, 128)
 
 
+@pytest.mark.parametrize("ch,mult,name,C", [(48, (2, 1), "dec.8x8_block1.norm0", 144), (72, (2, 8), "enc.16x16_block0.norm0", 144)])
+def test_groupnorm_width_its_groups_do_not_divide_is_rejected(ch, mult, name, C):
+    """GroupNorm(C) has min(32, C / 4) groups (adm_blocks.py:89): a level width or a concat of 128 channels or more that is not a
+    multiple of 32 (144 = 96 + 48; a 144-wide level) has no GroupNorm in the reference either; plan_create names the first such
+    norm instead of leaving it to the first forward.  The neighbours the kernels do serve -- 120 = 80 + 40 (30 groups), 160 =
+    80 + 80, 72 = 48 + 24 -- still build."""
+    with pytest.raises(RuntimeError, match=rf"GroupNorm {name} has {C} channels, not a multiple of its 32 groups"):
+        L.Plan(2, 2, 2, ch, mult, 1, (), 16)
+    L.Plan(2, 2, 2, 40, (2, 1), 1, (), 16)
+    L.Plan(1, 0, 3, 24, (1, 2, 2), 1, (), 16)
+
+
 def test_host_side_argument_validation():
     with pytest.raises(RuntimeError, match="multiple of 8"):
         L.Plan(2, 2, 2, 12, (1,), 1, (), 128)
