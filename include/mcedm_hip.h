@@ -929,6 +929,30 @@ int mcedm_darcy_guidance(const float* pred, float* out, float* scratch, int B, i
 int mcedm_swe_fv_residual(const float* pred, const float* gt, float* out, int B, int T, int X, float half_dt, float dx,
                           float scale2_h, float scale2_u, int clamp, void* stream);
 int mcedm_darcy_residual(const float* pred, float* out, int B, int S, float two_dx, float denom, int clamp, void* stream);
+/* The PDE term of training (PlCondEdm.training_step with pde_loss_lambda > 0, models/ddim.py:1726-1731 -> get_pde_loss
+ * :1388-1422 with clamp_loss=True): value and gradient of
+ *   pde_loss = sum_{b,t,x} w_b * sum_fields clamp(residual(x_unnorm, gt), max=1),   x_unnorm = (h * div_h + sub_h, D * div_u + sub_u)
+ * with the residual of mcedm_swe_fv_residual (gd->system 1; H = time rows, W = cells) or mcedm_darcy_residual (system 2; one field).
+ *   gd        system, half_dt, dx / two_dx, sub_*, div_* as for the guided sampler (scale2_* = div_*^2); weight = pde_loss_lambda
+ *   D         [B, 1, H, W], the denoised output of the network
+ *   h         the NORMALISED conditioning field: element (b, t, x) at h[b * h_sb + t * h_st + x * h_sx]
+ *   gt        NULL: the state itself (x_gt_unnorm = x_unnorm, :1402-1403), so the gradient also flows through the target; or
+ *             un-normalised channel-last (B, H, W, 2) data without a gradient (use_gt_pde).  Darcy ignores it like the reference.
+ *   w         [B] in device memory or NULL (= 1): the factor on sample b's residual, in the value and the gradient alike.  With
+ *             pde_loss_prop_t the reference's division (:1415-1416) broadcasts to (b, b, t, x): w_b = sum_i 1 / (sigma_i + 1) for every b.
+ *   loss_out  1 fp32 (device): pde_loss, NOT multiplied by weight; summed in a fixed order through `scratch`
+ *             (MCEDM_REDUCE_SCRATCH_BYTES, as for mcedm_edm_loss): no floating-point atomics, bitwise reproducible
+ *   dD        [B, 1, H, W] or NULL (value only): dD += weight * d pde_loss / d D in place (on the buffer mcedm_edm_loss wrote),
+ *             the div_u of the un-normalisation included.  Every thread owns its cell.  The gradient's NaNs are not zeroed (the
+ *             reference zeroes them only in the return_d branch); the clamp passes the gradient at L <= 1 and blocks it at L > 1 / NaN.
+ *   pde_scratch  Darcy with dD: mcedm_pde_train_scratch_bytes(gd, B, H, W) = B * (H-4)^2 floats; otherwise unused (may be NULL)
+ * MCEDM_ERR_INVALID before any launch, with a message that names the argument: gd / D / h / loss_out NULL, an unknown gd->system,
+ * an empty shape, a short or misaligned scratch, Darcy with H != W or H <= 4 or a short pde_scratch.  Allocates nothing and does
+ * not synchronise. */
+size_t mcedm_pde_train_scratch_bytes(const mcedm_guidance_desc* gd, int B, int H, int W);
+int mcedm_pde_train_loss(const mcedm_guidance_desc* gd, const float* D, const float* h, int64_t h_sb, int64_t h_st, int64_t h_sx,
+                         const float* gt, const float* w, int B, int H, int W, float* loss_out, float* dD, void* pde_scratch,
+                         size_t pde_scratch_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- measurement ---------------------------------------------------------------------------
  * Per-launch timing with HIP event pairs recorded on the launch stream (bench.py's roofline leg).

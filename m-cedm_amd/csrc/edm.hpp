@@ -135,4 +135,45 @@ struct DdimCondStep {
 };
 int launch_ddim_cond_step(const DdimCondStep& a, hipStream_t s);
 
+// ---- deterministic grid-wide sums (loss, gradient norm) ---------------------------------------------------------
+// Every block stores its partial sum (fp64) in a slot of a scratch array, takes a ticket, and the block that draws the LAST
+// ticket adds the slots in index order: the value does not depend on the order the blocks ran in (an atomicAdd of the
+// partials would make the loss, the clip factor and with them the whole training run differ in the last bits from run to
+// run).  The array and the ticket live in CALLER-owned scratch (ABI 3: MCEDM_REDUCE_SCRATCH_BYTES per concurrent call), so
+// two plans on two streams of one device never share state; the entry point zeroes the ticket on the stream in front of
+// the kernel.  Layout: [RED_MAX] fp64 partials, then the 32-bit ticket.
+constexpr int RED_MAX = 4096;
+static_assert(MCEDM_REDUCE_SCRATCH_BYTES >= RED_MAX * 8 + 4, "mcedm_hip.h: MCEDM_REDUCE_SCRATCH_BYTES too small for the reduction");
+struct RedScratch { double* part; unsigned* ticket; };
+static inline RedScratch red_scratch(void* scratch) {
+  return RedScratch{reinterpret_cast<double*>(scratch), reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch) + (size_t)RED_MAX * 8)};
+}
+
+// block_sum: this block's partial in thread 0.  Returns true in every thread of the LAST block, with the total in *total
+// (thread 0 only).
+__device__ __forceinline__ bool grid_sum_fixed_order(RedScratch rs, double block_sum, unsigned bid, unsigned nblocks, double* total) {
+  __shared__ unsigned s_last;
+  __shared__ double s_red[4];
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(&rs.part[bid], block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    s_last = (atomicAdd(rs.ticket, 1u) == nblocks - 1) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last) return false;
+  __threadfence();
+  double t = 0.0;
+  for (unsigned i = threadIdx.x; i < nblocks; i += blockDim.x)      // fixed assignment of slots to threads
+    t += __hip_atomic_load(&rs.part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *total = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    *rs.ticket = 0u;
+  }
+  return true;
+}
+
 }  // namespace mcedm

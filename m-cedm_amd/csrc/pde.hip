@@ -5,12 +5,15 @@
 //   swe_unroll SweFvLoss.unroll_from_init / unroll_loss  (models/pde_loss.py:167-197): the same step applied n_steps times from
 //              one initial row, sequential in time; one workgroup per sample with the row in LDS.
 //   darcy_*    DarcyLoss.calculate_loss              (models/pde_loss.py:30-54): -div(a grad u) = 1, central differences.
+//   *_train_*  the clamped, summed residual of the denoised state as a term of the training loss, with its gradient
+//              (PlCondEdm.training_step, models/ddim.py:1726-1731).
 //
 // Apart from the unroll, pure streaming kernels (one thread per output cell, 3-point / 5x5 neighbourhoods served by L1/L2): HBM-bound at
 // 16 B (SWE) / 12 B (Darcy) per cell.  Built with -ffp-contract=off and written in the reference's evaluation order,
 // so the results are bit-identical to the PyTorch CPU path (tests compare with torch.equal).
 #include "common.hpp"
 #include "edm.hpp"
+#include "prof.hpp"
 
 namespace mcedm {
 
@@ -350,6 +353,163 @@ int launch_darcy_guidance(const GuideIO& io, float* scratch, int B, int S, float
   return MCEDM_OK;
 }
 
+// ---- the PDE term of training: PlCondEdm.training_step, models/ddim.py:1726-1731 -----------------------------------------
+//   pde_loss = sum(clamp(residual(x_unnorm, gt), max=1) [summed over the two fields] * w_b),  x_unnorm = (h, D) un-normalised
+// and dD += lambda * d pde_loss / d D.  What differs from the guidance gradients above (derivation: DESIGN.md):
+//   * sum of the CLAMPED residual, not the mean: the upstream of a cell is w_b where L <= 1 and 0 where L > 1 or L is NaN
+//     (torch.clamp's backward);
+//   * gt == NULL is get_pde_loss's `x_gt_unnorm = x_unnorm` (:1402-1403), the SAME autograd tensor: every cell also receives
+//     -2 (with_ic - gt) / scale2 directly, and row 0 (with_ic = gt there) cancels to an exact 0;
+//   * the NaNs of with_ic are zeroed (models/pde_loss.py:220), which zeroes the upstream of the step there, but the gradient itself
+//     is returned as it is (dloss[isnan] = 0 exists only in the return_d branch);
+//   * only u = D carries a gradient: h is data.
+// h is read through element strides (training_step holds it as a channel slice of the normalised batch), D is [B, 1, H, W].
+struct TrainView {
+  const float* h; long h_sb, h_st, h_sx;
+  const float* D;
+  const float* gt;               // NULL, or un-normalised (B, H, W, 2) data without a gradient (use_gt_pde)
+  const float* w;                // [B] factor on the residual of sample b, or NULL
+  int H, W;
+  float sub[2], div[2];
+  __device__ __forceinline__ float get(long b, int t, int x, int c) const {
+    return c == 0 ? h[b * h_sb + t * h_st + x * h_sx] * div[0] + sub[0] : D[(b * H + t) * W + x] * div[1] + sub[1];
+  }
+  __device__ __forceinline__ float target(long b, int t, int x, int c) const {
+    return gt ? gt[((b * H + t) * W + x) * 2 + c] : get(b, t, x, c);
+  }
+};
+
+// this block's partial of the loss (fp64) -> the fixed-order grid sum -> *loss
+__device__ __forceinline__ void train_loss_reduce(double t, RedScratch rs, float* __restrict__ loss) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+  __syncthreads();
+  double total;
+  if (grid_sum_fixed_order(rs, (red[0] + red[1]) + (red[2] + red[3]), blockIdx.x, gridDim.x, &total) && threadIdx.x == 0)
+    *loss = (float)total;
+}
+
+// One thread per cell (t, x) of a sample (grid-stride beyond RED_MAX blocks): its own clamped residual goes into the loss; its
+// gradient is its share of the VJPs of the (at most three) updates of row t + 1 that read it, plus the with_ic / gt terms of
+// its own entry.  No thread writes another thread's cell.
+__global__ __launch_bounds__(256) void swe_train_loss_kernel(TrainView v, int T, int X, size_t cells, float half_dt, float dx,
+                                                             float scale2_h, float scale2_u, float lambda,
+                                                             float* __restrict__ dD, float* __restrict__ loss, RedScratch rs) {
+  double acc = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (size_t)gridDim.x * 256) {
+    const size_t r = i / X;
+    const int x = (int)(i - r * X);
+    const long b = (long)(r / T);
+    const int t = (int)(r % T);
+    const float wb = v.w ? v.w[b] : 1.0f;
+    // the update of cell xo of row tt from row tt - 1 (row 0: the cell itself), its residual against the target, and the upstream
+    // of the (h, u) entry of with_ic
+    auto load3 = [&](int tt, int xo, int (&xi)[3], float (&hin)[3], float (&uin)[3]) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        int q = xo + k - 1;
+        q = q < 0 ? 0 : (q > X - 1 ? X - 1 : q);        // replicate padding
+        xi[k] = q;
+        hin[k] = v.get(b, tt, q, 0);
+        uin[k] = v.get(b, tt, q, 1);
+      }
+    };
+    int xi[3];
+    float hin[3], uin[3];
+    float vh, vu;
+    if (t == 0) {
+      vh = v.get(b, 0, x, 0); vu = v.get(b, 0, x, 1);
+    } else {
+      load3(t - 1, x, xi, hin, uin);
+      const float2 row3[3] = {make_float2(hin[0], uin[0]), make_float2(hin[1], uin[1]), make_float2(hin[2], uin[2])};
+      const SweCell o = swe_force_cell(row3, 1, 3, half_dt, dx);
+      vh = o.h; vu = o.u;
+    }
+    const bool nan_u = vu != vu;
+    if (vh != vh) vh = 0.f;                              // pred_next_with_ic[isnan] = 0 (models/pde_loss.py:220)
+    if (nan_u) vu = 0.f;
+    const float dfh = vh - v.target(b, t, x, 0), dfu = vu - v.target(b, t, x, 1);
+    const float lh = dfh * dfh / scale2_h, lu = dfu * dfu / scale2_u;
+    const float cell = (lh > 1.f ? 1.f : lh) + (lu > 1.f ? 1.f : lu);       // torch.clamp(max=1) keeps NaN; sum over the fields
+    acc += (double)(v.w ? cell * wb : cell);
+    if (!dD) continue;
+    // d / d u of this cell.  Its own entry: +au through with_ic (row 0 only: later rows are functions of row t - 1) and -au
+    // through gt when gt is the state itself.
+    float g = 0.f;
+    const float au = (lu <= 1.f ? wb : 0.f) / scale2_u * (2.0f * dfu);
+    if (t == 0 && !nan_u) g += au;
+    if (!v.gt) g -= au;
+    if (t + 1 < T) {
+      for (int xo = x - 1; xo <= x + 1; ++xo) {
+        if (xo < 0 || xo >= X) continue;
+        load3(t, xo, xi, hin, uin);
+        const float2 row3[3] = {make_float2(hin[0], uin[0]), make_float2(hin[1], uin[1]), make_float2(hin[2], uin[2])};
+        const SweCell o = swe_force_cell(row3, 1, 3, half_dt, dx);
+        const float eh = (o.h == o.h ? o.h : 0.f) - v.target(b, t + 1, xo, 0);
+        const float eu = (o.u == o.u ? o.u : 0.f) - v.target(b, t + 1, xo, 1);
+        const float gh = (o.h == o.h && eh * eh / scale2_h <= 1.f) ? wb / scale2_h * (2.0f * eh) : 0.f;
+        const float gu = (o.u == o.u && eu * eu / scale2_u <= 1.f) ? wb / scale2_u * (2.0f * eu) : 0.f;
+        const Swe6 d = swe_force_cell_vjp(hin, uin, half_dt, dx, gh, gu);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (xi[k] == x) g += d.du[k];
+      }
+    }
+    dD[i] += lambda * (g * v.div[1]);
+  }
+  train_loss_reduce(acc, rs, loss);
+}
+
+// Darcy: l = (Du - 1)^2 / (S-4)^2 clamped at 1 (models/pde_loss.py:80-84).  G = d pde_loss / d Du with the clamp mask and the
+// sample's factor; the same launch sums the loss.  G == NULL: the value alone.
+__global__ __launch_bounds__(256) void darcy_train_g_kernel(TrainView v, float* __restrict__ G, int S, size_t cells, float two_dx,
+                                                            float denom, float* __restrict__ loss, RedScratch rs) {
+  double acc = 0.0;
+  const int n = S - 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (size_t)gridDim.x * 256) {
+    const long b = (long)(i / ((size_t)n * n));
+    const int rem = (int)(i - (size_t)b * n * n);
+    const int oi = rem / n, oj = rem - oi * n;
+    const float wb = v.w ? v.w[b] : 1.0f;
+    auto A = [&](int p, int q) { return v.get(b, p, q, 0); };
+    auto U = [&](int p, int q) { return v.get(b, p, q, 1); };
+    auto aux = [&](int p, int q) { return A(p + 1, q + 1) * ((U(p + 2, q + 1) - U(p, q + 1)) / two_dx); };
+    auto auy = [&](int p, int q) { return A(p + 1, q + 1) * ((U(p + 1, q + 2) - U(p + 1, q)) / two_dx); };
+    const float auxx = (aux(oi + 2, oj + 1) - aux(oi, oj + 1)) / two_dx;
+    const float auyy = (auy(oi + 1, oj + 2) - auy(oi + 1, oj)) / two_dx;
+    const float Du = -(auxx + auyy);
+    const float l = (Du - 1.f) * (Du - 1.f) / denom;
+    const float lc = l > 1.f ? 1.f : l;
+    acc += (double)(v.w ? lc * wb : lc);
+    if (G) G[i] = (l <= 1.f ? wb : 0.f) / denom * (2.0f * (Du - 1.f));
+  }
+  train_loss_reduce(acc, rs, loss);
+}
+
+// dD += lambda * div_u * d pde_loss / d u, gathered from G as in darcy_guidance_gather_kernel (no d a: the coefficient is data;
+// no NaN zeroing: that belongs to the return_d branch)
+__global__ __launch_bounds__(256) void darcy_train_gather_kernel(TrainView v, const float* __restrict__ G, float* __restrict__ dD,
+                                                                 int S, size_t cells, float two_dx, float lambda) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= cells) return;
+  const long b = (long)(i / ((size_t)S * S));
+  const int rem = (int)(i - (size_t)b * S * S);
+  const int p = rem / S, q = rem - p * S;
+  const int n = S - 4, m2 = S - 2;
+  const float* Gb = G + (size_t)b * n * n;
+  auto g = [&](int a, int c) -> float { return (a >= 0 && a < n && c >= 0 && c < n) ? Gb[(size_t)a * n + c] : 0.f; };
+  auto dux = [&](int a, int c) -> float {
+    return (a >= 0 && a < m2 && c >= 0 && c < m2) ? (g(a, c - 1) - g(a - 2, c - 1)) / two_dx * v.get(b, a + 1, c + 1, 0) : 0.f;
+  };
+  auto duy = [&](int a, int c) -> float {
+    return (a >= 0 && a < m2 && c >= 0 && c < m2) ? (g(a - 1, c) - g(a - 1, c - 2)) / two_dx * v.get(b, a + 1, c + 1, 0) : 0.f;
+  };
+  const float du = (dux(p - 2, q - 1) - dux(p, q - 1)) / two_dx + (duy(p - 1, q - 2) - duy(p - 1, q)) / two_dx;
+  dD[i] += lambda * (du * v.div[1]);
+}
+
 }  // namespace mcedm
 
 using namespace mcedm;
@@ -422,5 +582,63 @@ extern "C" int mcedm_darcy_residual(const float* pred, float* out, int B, int S,
   hipLaunchKernelGGL(darcy_residual_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)pred, out, S, cells, two_dx, denom, clamp);
   MCEDM_LAUNCH_CHECK("darcy_residual_kernel");
+  return MCEDM_OK;
+}
+
+extern "C" size_t mcedm_pde_train_scratch_bytes(const mcedm_guidance_desc* gd, int B, int H, int W) {
+  if (!gd || gd->system != 2 || B <= 0 || H <= 4 || W != H) return 0;
+  return (size_t)B * (H - 4) * (H - 4) * sizeof(float);
+}
+
+extern "C" int mcedm_pde_train_loss(const mcedm_guidance_desc* gd, const float* D, const float* h, int64_t h_sb, int64_t h_st,
+                                    int64_t h_sx, const float* gt, const float* w, int B, int H, int W, float* loss_out, float* dD,
+                                    void* pde_scratch, size_t pde_scratch_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  MCEDM_REQUIRE(gd, "pde_train_loss: gd is null");
+  MCEDM_REQUIRE(D, "pde_train_loss: D is null");
+  MCEDM_REQUIRE(h, "pde_train_loss: h is null");
+  MCEDM_REQUIRE(loss_out, "pde_train_loss: loss_out is null");
+  MCEDM_REQUIRE(gd->system == 1 || gd->system == 2, "pde_train_loss: gd->system = %d is unknown (1 = SWE, 2 = Darcy)", gd->system);
+  MCEDM_REQUIRE(B > 0 && H > 0 && W > 0, "pde_train_loss: empty shape (B = %d, H = %d, W = %d)", B, H, W);
+  MCEDM_REQUIRE(scratch && scratch_bytes >= MCEDM_REDUCE_SCRATCH_BYTES && ((size_t)scratch & 7) == 0,
+                "pde_train_loss: scratch needs %d bytes of 8-byte aligned device memory (MCEDM_REDUCE_SCRATCH_BYTES)",
+                MCEDM_REDUCE_SCRATCH_BYTES);
+  const hipStream_t s = (hipStream_t)stream;
+  const float lambda = (float)gd->weight;
+  const TrainView v{h, (long)h_sb, (long)h_st, (long)h_sx, D, gd->system == 1 ? gt : nullptr, w, H, W,
+                    {gd->sub_h, gd->sub_u}, {gd->div_h, gd->div_u}};
+  const RedScratch rs = red_scratch(scratch);
+  // at most two workgroups per compute unit, the rest by grid stride: every block ends on one ticket of the fixed-order sum
+  auto blocks = [](size_t n) { const size_t g = (n + 255) / 256; return (unsigned)(g < 512 ? g : 512); };
+  static_assert(512 <= RED_MAX, "one slot of the reduction per block");
+  if (gd->system == 1) {
+    const size_t cells = (size_t)B * H * W;
+    MCEDM_HIP_TRY(hipMemsetAsync(rs.ticket, 0, sizeof(unsigned), s));
+    ProfScope ps("swe_train_loss_kernel", 700.0 * cells, (dD ? 20.0 : 8.0) * cells, s);
+    hipLaunchKernelGGL(swe_train_loss_kernel, dim3(blocks(cells)), dim3(256), 0, s, v, H, W, cells, gd->half_dt, gd->dx,
+                       gd->div_h * gd->div_h, gd->div_u * gd->div_u, lambda, dD, loss_out, rs);
+    MCEDM_LAUNCH_CHECK("swe_train_loss_kernel");
+    return MCEDM_OK;
+  }
+  MCEDM_REQUIRE(H == W, "pde_train_loss: Darcy needs a square grid (H = %d, W = %d)", H, W);
+  MCEDM_REQUIRE(H > 4, "pde_train_loss: Darcy needs a grid larger than 4 x 4 (S = %d)", H);
+  const int S = H;
+  const size_t inner = (size_t)B * (S - 4) * (S - 4), cells = (size_t)B * S * S;
+  MCEDM_REQUIRE(!dD || (pde_scratch && pde_scratch_bytes >= inner * sizeof(float)),
+                "pde_train_loss: pde_scratch needs %zu bytes (mcedm_pde_train_scratch_bytes), got %zu", inner * sizeof(float),
+                pde_scratch ? pde_scratch_bytes : (size_t)0);
+  float* G = dD ? (float*)pde_scratch : nullptr;
+  MCEDM_HIP_TRY(hipMemsetAsync(rs.ticket, 0, sizeof(unsigned), s));
+  {
+    ProfScope ps("darcy_train_g_kernel", 40.0 * inner, 4.0 * (2.0 * cells + inner), s);
+    hipLaunchKernelGGL(darcy_train_g_kernel, dim3(blocks(inner)), dim3(256), 0, s, v, G, S, inner, gd->two_dx,
+                       (float)((S - 4) * (S - 4)), loss_out, rs);
+    MCEDM_LAUNCH_CHECK("darcy_train_g_kernel");
+  }
+  if (dD) {
+    ProfScope ps("darcy_train_gather_kernel", 30.0 * cells, 4.0 * (3.0 * cells + inner), s);
+    hipLaunchKernelGGL(darcy_train_gather_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, v, G, dD, S, cells,
+                       gd->two_dx, lambda);
+    MCEDM_LAUNCH_CHECK("darcy_train_gather_kernel");
+  }
   return MCEDM_OK;
 }

@@ -347,8 +347,10 @@ class PlCondEdm(_SingleTask):
             from .ddim_blocks import Model
         self.model = Model(hparams) if self._on_ddpm_unet else DhariwalUNet(hparams)
         self.ema_model = EmaModel(self.model, beta=m.ema_rate) if m.ema else None
-        if _opt(o, "pde_loss_lambda", 0.0):
-            raise NotImplementedError("pde_loss_lambda != 0 is outside the hot path")
+        # models/ddim.py:68-72: the PDE residual term of training_step (mcedm_pde_train_loss)
+        self.pde_loss_lambda = _opt(o, "pde_loss_lambda", 0.0)
+        self.pde_loss_prop_t = _opt(o, "pde_loss_prop_t", False)
+        self.use_gt_pde = _opt(o, "use_gt_pde", False)
         self._init_common(hparams, m.in_channels, m.out_ch, default_sampler=self.get_edm_sampler_params)
         self.P_mean, self.P_std, self.sigma_data = -1.2, 1.2, 1.0
         self.sigma_min, self.sigma_max = 0.002, 80
@@ -461,6 +463,8 @@ class PlCondEdm(_SingleTask):
         self._adm_only("training_step")
         h_unnorm, dx, dt, u_unnorm = train_batch
         self.h_ch, self.u_ch = h_ch, u_ch = h_unnorm.shape[-1], u_unnorm.shape[-1]
+        if self.pde_loss_lambda > 0.:
+            self._pde_train_check()
         x = self.data_transform(h_unnorm, u_unnorm)
         h, u = x[..., 0:h_ch], x[..., h_ch:h_ch + u_ch]
         cond_in = _nchw(self.get_cond_in(h, u, dx, dt)).float()
@@ -473,14 +477,57 @@ class PlCondEdm(_SingleTask):
             dx = self.get_dx_input(cond_in[:, 0:self.h_ch], u_noise)     # on the NOISED target; carries no gradient
         if torch.rand(1) >= self.cond_p:                         # models/ddim.py:1683-1684: conditioning off for this batch
             cond_in = None                                       # (the network then reads zeros, adm_blocks.py:328-331)
+        # models/ddim.py:1726-1731: pde_loss_lambda * get_pde_loss(h, x0_t, ..., clamp_loss=True) on top of the EDM loss.  h is
+        # the normalised data (not cond_in: the cond_p draw does not remove it), read in place as a channel slice of x.  The
+        # reference's own call raises (:1729 passes the channel-last h with do_rearrange=True; :1396 scrambles it, :1400 cannot
+        # concatenate): this is the residual of (h, x0_t) in one layout, as validation_step / test_step form it
+        pde = self._pde_train_args(h_unnorm, u_unnorm, sigma) if self.pde_loss_lambda > 0. else None
+        parts = {}
+
+        def pde_term(D, dD, edm):
+            """pde_loss of the denoised D, its gradient accumulated into the EDM loss's dD; edm + lambda * pde in fp32."""
+            parts["edm"] = edm.reshape(())
+            parts["pde"] = _lib.pde_train_loss(pde[0], D, h, gt=pde[1], w=pde[2], dD=dD)[0].reshape(())
+            return parts["edm"] + self.pde_loss_lambda * parts["pde"]
+
         if self._on_ddpm_unet:                                   # under torch.no_grad() (see _adm_only): the loss value alone
             D = self.model_precond(u_noise, sigma, cond_in)
             loss = _lib.edm_loss(D, u.contiguous(), None, sigma, self.sigma_data, want_grad=False)[0].reshape(())
-            self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
-            return loss
-        loss = _edm_train_loss(self, u, u_noise, sigma, cond_in, None, dx)
-        self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
+            if pde is not None:
+                loss = pde_term(D, None, loss)
+        else:
+            loss = _edm_train_loss(self, u, u_noise, sigma, cond_in, None, dx, pde_term if pde is not None else None)
+        # train_loss is the EDM part: the reference logs it before it adds the PDE term (:1724)
+        self.log("train_loss", parts["edm"].detach() if pde is not None else loss, prog_bar=True, on_epoch=True, on_step=False,
+                 sync_dist=True)
+        if pde is not None:
+            self.log("train_pde_loss", parts["pde"], prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
         return loss
+
+    def _pde_train_check(self):
+        """The PDE term is built for what the guided sampler is built for: one gauss-normalised channel per field, no flip."""
+        if self.pde_loss is None or not hasattr(self.pde_loss, "guidance_desc"):
+            raise RuntimeError("pde_loss_lambda > 0 needs set_pde_loss_function('swe' | 'swe_per' | 'darcy') before training_step")
+        if self.pde_loss.flip_xy:
+            raise NotImplementedError("pde_loss_lambda > 0 with flip_xy (flip_state, models/pde_loss.py:6-16, 228-229) is not built")
+        if self.rescaled:
+            raise NotImplementedError("pde_loss_lambda > 0 with data.rescaled (inverse_data_transform, models/ddim.py:251-262) is not built")
+        if self.normalization == "min_max":
+            raise NotImplementedError("pde_loss_lambda > 0 with min_max normalisation (the clamp of inverse_data_transform, "
+                                      "models/ddim.py:251-262) is not built")
+        if self.h_ch != 1 or self.u_ch != 1:
+            raise NotImplementedError("pde_loss_lambda > 0 with more than one channel per field (models/ddim.py:1390-1400) is not built")
+
+    def _pde_train_args(self, h_unnorm, u_unnorm, sigma):
+        """(description, gt, w) of mcedm_pde_train_loss for this batch."""
+        gd = self.pde_loss.guidance_desc(self.normalizer_input, self.normalizer_target, h_unnorm.shape[1], h_unnorm.shape[2],
+                                         weight=float(self.pde_loss_lambda))
+        # use_gt_pde (:1728): the data as the residual's target, without a gradient; otherwise the denoised state itself
+        gt = torch.cat([h_unnorm, u_unnorm], dim=-1).to(torch.float32).contiguous() if self.use_gt_pde else None
+        # pde_loss_prop_t (:1727, 1413-1416): the (b, t, x) matrix divided by noise_level.reshape(-1, 1, 1, 1) + 1 broadcasts to
+        # (b, b, t, x), so every sample's residual meets every noise level: the factor is sum_i 1 / (sigma_i + 1) for all of them
+        w = (1.0 / (sigma + 1.0)).sum().expand(sigma.numel()).contiguous() if self.pde_loss_prop_t else None
+        return gd, gt, w
 
     def get_dx_pde(self, cond, x_denoised, calc_prob=False):
         """models/ddim.py:1424-1450: gradient of the PDE residual of (h from cond, u = x_denoised), un-normalised, w.r.t. that

@@ -1125,6 +1125,37 @@ def edm_loss(D, x, mask, sigma, sigma_data=1.0, want_grad=True, scratch: Optiona
     return loss, dD
 
 
+def pde_train_loss(gd: GuidanceDesc, D, h, gt=None, w=None, dD=None, scratch: Optional[torch.Tensor] = None):
+    """The PDE term of PlCondEdm.training_step (mcedm_pde_train_loss): ``(pde_loss, dD)`` with ``pde_loss`` one fp32 (not multiplied
+    by ``gd.weight`` = pde_loss_lambda) and ``dD += gd.weight * d pde_loss / d D`` in place; ``dD=None``: the value alone.
+    ``D`` [B, 1, H, W]; ``h`` the normalised conditioning field as (B, H, W) or (B, H, W, 1), any strides (read in place);
+    ``gt`` None (the state itself) or un-normalised (B, H, W, 2); ``w`` [B] per-sample factors or None."""
+    B, Cc, H, W = D.shape
+    if Cc != 1:
+        raise RuntimeError(f"pde_train_loss: D must be [B, 1, H, W], got {tuple(D.shape)}")
+    hv = h[..., 0] if h.dim() == 4 else h
+    if tuple(hv.shape) != (B, H, W) or h.dim() == 4 and h.shape[3] != 1:
+        raise RuntimeError(f"pde_train_loss: h must be {(B, H, W)} or {(B, H, W, 1)}, got {tuple(h.shape)}")
+    if not hv.is_cuda or hv.dtype != torch.float32:
+        raise RuntimeError("pde_train_loss: h must be an fp32 device tensor")
+    if gt is not None and tuple(gt.shape) != (B, H, W, 2):
+        raise RuntimeError(f"pde_train_loss: gt must be {(B, H, W, 2)}, got {tuple(gt.shape)}")
+    if w is not None and w.numel() != B:
+        raise RuntimeError(f"pde_train_loss: w must hold {B} factors, got {w.numel()}")
+    if dD is not None and tuple(dD.shape) != tuple(D.shape):
+        raise RuntimeError(f"pde_train_loss: dD must be {tuple(D.shape)}, got {tuple(dD.shape)}")
+    loss = torch.empty(1, dtype=torch.float32, device=D.device)
+    scratch = reduce_scratch(D.device) if scratch is None else scratch
+    lib = load()
+    nbytes = lib.mcedm_pde_train_scratch_bytes(C.byref(gd), B, H, W) if dD is not None else 0
+    pde_scratch = torch.empty(nbytes, dtype=torch.uint8, device=D.device) if nbytes else None
+    check(lib.mcedm_pde_train_loss(C.byref(gd), _ptr(D), hv.data_ptr(), hv.stride(0), hv.stride(1), hv.stride(2), _ptr(gt),
+                                   _ptr(w), B, H, W, _ptr(loss), _ptr(dD), None if pde_scratch is None else pde_scratch.data_ptr(),
+                                   nbytes, scratch.data_ptr(), scratch.numel() * scratch.element_size(), _stream()),
+          "pde_train_loss")
+    return loss, dD
+
+
 # ---- PDE residuals (models/pde_loss.py; SURVEY.md section 8 f3) -------------------------------------------------------
 def swe_fv_step(s_t: torch.Tensor, half_dt: float, dx: float) -> torch.Tensor:
     """SweFvLoss.f_t_swp1d on (b, t, x, 2) fp32 states."""

@@ -30,16 +30,20 @@ from .pl_base import (DotDict, Normalizer, _Base, _PlBase, _TrainLoss, _ddim_sam
                       masked_l1)
 
 
-def _edm_train_loss(module, x, x_noise, sigma, cond, mask, dx):
+def _edm_train_loss(module, x, x_noise, sigma, cond, mask, dx, extra=None):
     """loss = mean_b sum_chw w(sigma_b) (D*m - x*m)^2 with D = model_precond(x_noise, sigma, cond): forward and
     backward both run in the HIP library (mcedm_edm_denoise / mcedm_edm_loss / mcedm_edm_denoise_backward).
-    dx: the network's PDE-gradient input of dx_cond models (PlCondEdm.training_step) or None; no gradient flows into it."""
+    dx: the network's PDE-gradient input of dx_cond models (PlCondEdm.training_step) or None; no gradient flows into it.
+    extra(D, dD, loss) -> loss: a further term of the loss in D (the PDE residual of PlCondEdm.training_step); it adds its
+    gradient to dD in place and returns the total, and the backward from dD is the same."""
     net: DhariwalUNet = module.model
 
     def run():
         D = net.plan.denoise(net.packed_weights(), x_noise, sigma, cond=cond, ws=module._train_ws, training=True,
                              sigma_data=module.sigma_data, dx=dx)
         loss, dD = _lib.edm_loss(D, x, mask, sigma, sigma_data=module.sigma_data, want_grad=True)
+        if extra is not None:
+            loss = extra(D, dD, loss)
         return loss, lambda grads: net.plan.denoise_backward(
             net.packed_weights(), net.named_param_dict(), x_noise, sigma, cond, dD, grads, ws=module._train_ws,
             sigma_data=module.sigma_data, dx=dx)
@@ -73,9 +77,11 @@ class PlMcedm(_PlBase):
         self.P_mean, self.P_std, self.sigma_data = -1.2, 1.2, 1.0
         self.sigma_min, self.sigma_max = 0.002, 80
         self.factor, self.step_size, self.loss = o.factor, o.step_size, o.loss
+        # models/mcedm.py:72-76 reads the three knobs and the joint model's training_step (:254-281) never uses them: accepted and
+        # ignored here as well
         self.pde_loss_lambda = _opt(o, "pde_loss_lambda", 0.0)
-        if self.pde_loss_lambda:
-            raise NotImplementedError("pde_loss_lambda != 0 is outside the hot path")
+        self.pde_loss_prop_t = _opt(o, "pde_loss_prop_t", False)
+        self.use_gt_pde = _opt(o, "use_gt_pde", False)
         self.h_ch = self.u_ch = m.out_ch // 2
         self._init_common(hparams, self.h_ch, self.u_ch)
         # where the sampler's per-step churn noise (models/mcedm.py:608) comes from: "device" = generated inside the kernel that
