@@ -50,23 +50,24 @@ int launch_precond_prepare(const float* sigma_dev, float sigma_host, int use_hos
 }
 
 // ---- K7b: D = c_skip*x + c_out*F  (mcedm.py:210 / 460); optional classifier-free blend
-// F = (w+1)*F - w*F_uncond first (mcedm.py:457-458).
+// F = (w+1)*F - w*F_uncond first (mcedm.py:457-458), w1 = fl32(w + 1) with the sum formed in double like the reference's
+// Python scalar (fl32(fl32(w) + 1) is another number for one w in eight).
 __global__ void precond_finish_kernel(const float* __restrict__ x, const float* __restrict__ F,
-                                      const float* __restrict__ Fu, float w, const float* __restrict__ coefs4,
+                                      const float* __restrict__ Fu, float w1, float w, const float* __restrict__ coefs4,
                                       int n_sigma, size_t per_sample, size_t total, float* __restrict__ D,
                                       float* __restrict__ F_out) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = n_sigma == 1 ? 0 : i / per_sample;
     float f = F[i];
-    if (Fu) f = (w + 1.0f) * f - w * Fu[i];
+    if (Fu) f = w1 * f - w * Fu[i];
     if (F_out) F_out[i] = f;
     D[i] = coefs4[4 * b] * x[i] + coefs4[4 * b + 1] * f;
   }
 }
 
-int launch_precond_finish(const float* x, const float* F, const float* Fu, float w, const float* coefs4, int n_sigma,
+int launch_precond_finish(const float* x, const float* F, const float* Fu, double w, const float* coefs4, int n_sigma,
                           size_t per_sample, size_t total, float* D, float* F_out, hipStream_t stream) {
-  hipLaunchKernelGGL(precond_finish_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, F, Fu, w, coefs4, n_sigma,
+  hipLaunchKernelGGL(precond_finish_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, F, Fu, (float)(w + 1.0), (float)w, coefs4, n_sigma,
                      per_sample, total, D, F_out);
   MCEDM_LAUNCH_CHECK("precond_finish_kernel");
   return MCEDM_OK;

@@ -783,7 +783,7 @@ __global__ void scale_to_coef_kernel(const float* __restrict__ x_scale, int n, i
 }
 
 int denoise_impl(const AdmNet& net, const float* x, const float* dx, const float* cond, const float* sigma_dev, float sigma_host,
-                 float w, float sigma_data, float* D_out, float* F_out) {
+                 double w, float sigma_data, float* D_out, float* F_out) {
   const mcedm_unet_desc& d = net.plan->desc;
   int rc;
   if ((rc = launch_precond_prepare(sigma_dev, sigma_host, sigma_dev ? 0 : 1, net.n_noise, sigma_data, d.cond_channels, d.in_channels,
@@ -791,7 +791,7 @@ int denoise_impl(const AdmNet& net, const float* x, const float* dx, const float
                                    net.s))) return rc;
   // classifier-free branch, mcedm.py:453-458; models/ddim.py:1755-1760: taken when cond OR dx is given, and the
   // unconditional evaluation drops both
-  float* Fu = fabsf(w) >= 0.001f && (cond != nullptr || dx != nullptr) ? net.Fu() : nullptr;
+  float* Fu = std::fabs(w) >= 0.001 && (cond != nullptr || dx != nullptr) ? net.Fu() : nullptr;
   if ((rc = net.forward_cfg(AdmIn{x, dx, cond, net.coef_in(), net.c_noise()}, net.F(), Fu))) return rc;
   const size_t per = (size_t)d.out_channels * net.H * net.W;
   return launch_precond_finish(x, net.F(), Fu, w, net.coefs4(), net.n_noise, per, per * net.B, D_out, F_out, net.s);
@@ -847,7 +847,7 @@ extern "C" int mcedm_edm_denoise_dx(const mcedm_plan* plan, const void* packed, 
   MCEDM_REQUIRE(dx == nullptr || plan->desc.dx_mode != MCEDM_DX_NONE, "edm_denoise: dx given to a plan without dx_cond");
   AdmNet net;
   const int rc = adm_bind("edm_denoise", *plan, packed, workspace, workspace_bytes, 0, no_extra, B, H, W, training, n_sigma, stream, &net);
-  return rc ? rc : denoise_impl(net, x, dx, cond, sigma, 0.f, 0.f, (float)sigma_data, D_out, F_out);
+  return rc ? rc : denoise_impl(net, x, dx, cond, sigma, 0.f, 0.0, (float)sigma_data, D_out, F_out);
 }
 
 extern "C" int mcedm_edm_denoise(const mcedm_plan* plan, const void* packed, const float* x, const float* sigma,

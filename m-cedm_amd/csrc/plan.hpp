@@ -281,7 +281,7 @@ static inline size_t no_extra(const AdmNet&) { return 0; }
 
 // D = c_skip x + c_out F(c_in x; ln(sigma)/4; cond) with sigma from the device (net.n_noise rows) or, null, from the host
 int denoise_impl(const AdmNet& net, const float* x, const float* dx, const float* cond, const float* sigma_dev, float sigma_host,
-                 float w, float sigma_data, float* D_out, float* F_out);
+                 double w, float sigma_data, float* D_out, float* F_out);
 
 // bytes the backward needs behind the training-mode activations (gradient buffers + scratch)
 size_t backward_scratch_bytes(const mcedm_plan& P, const Layout& L, int B, int H, int W);

@@ -71,7 +71,7 @@ static int heun_sample_impl(const mcedm_plan* plan, const void* packed, const mc
   if ((rc = adm_bind("heun_sample", P, packed, workspace, workspace_bytes, sb.total, no_extra, B, H, W, 0, 1, stream, &net))) return rc;
   hipStream_t s = net.s;
   HeunState h = heun_state(workspace, sb, B, P.desc.in_channels, (size_t)H * W, N, return_last, out, s);
-  const float w = (float)sp->w;
+  const double w = sp->w;
   const float sd = (float)sp->sigma_data;
   float* gscratch = at<float>(workspace, sb.g);
   float* dxin = dxc ? at<float>(workspace, sb.dxin) : nullptr;

@@ -335,17 +335,21 @@ def model_precond(P, cfg, x_noise: Tensor, sigma: Tensor, cond: Optional[Tensor]
 
 
 def get_denoised(P, cfg, xt: Tensor, t: Tensor, cond: Optional[Tensor] = None, w: Optional[float] = None,
-                 dx: Optional[Tensor] = None):
+                 dx: Optional[Tensor] = None, sigma_data: float = SIGMA_DATA, net=None):
     """PlMcedm.get_denoised, mcedm.py:443-461 including the classifier-free branch (models/ddim.py:1745-1763 with dx: the
-    branch is taken when cond OR dx is given, and its unconditional evaluation drops both)."""
+    branch is taken when cond OR dx is given, and its unconditional evaluation drops both).  ``sigma_data``: the module's
+    attribute (mcedm.py:47).  ``net(x, noise_labels, cond, dx) -> F`` stands in for the U-Net (default: unet_forward on P)."""
+    if net is None:
+        def net(x, labels, c, dx=None):
+            return unet_forward(P, cfg, x, labels, c, dx=dx)
     xt = xt.to(torch.float32)
     sigma = t.to(torch.float32).reshape(-1, 1, 1, 1)
-    c_skip, c_out, c_in, c_noise = precond_coeffs(sigma)
+    c_skip, c_out, c_in, c_noise = precond_coeffs(sigma, sigma_data)
     if w is None or abs(w) < 0.001 or (cond is None and dx is None):
-        F_x = unet_forward(P, cfg, c_in * xt, c_noise.flatten(), cond, dx=dx)
+        F_x = net(c_in * xt, c_noise.flatten(), cond, dx)
     else:
-        F_x = (w + 1) * unet_forward(P, cfg, c_in * xt, c_noise.flatten(), cond, dx=dx) \
-            - w * unet_forward(P, cfg, c_in * xt, c_noise.flatten(), None)
+        F_x = (w + 1) * net(c_in * xt, c_noise.flatten(), cond, dx) \
+            - w * net(c_in * xt, c_noise.flatten(), None, None)
     D_x = c_skip * xt + c_out * F_x
     return D_x, F_x
 
@@ -425,14 +429,18 @@ def guidance_dx_cond(system: str, h: Tensor, denoised: Tensor, norm_stats) -> Te
 
 def sample_edm_cond(P, cfg, h: Tensor, sp: SamplerParams, init_noise: Tensor,
                     step_noise: Optional[Sequence[Tensor]] = None, return_last: bool = True, guidance=None,
-                    dx_input=None) -> Tensor:
+                    dx_input=None, sigma_data: float = SIGMA_DATA, t_steps: Optional[Tensor] = None, net=None,
+                    trace: Optional[list] = None) -> Tensor:
     """PlCondEdm.sample_edm, models/ddim.py:1532-1601 (guide_dx False, no self-conditioning): the unmasked Heun
     sampler; ``h`` [B, cond_ch, H, W] is pure conditioning, ``init_noise`` [B, out_ch, H, W].
     ``guidance`` (guide_dx=True): callable (h, denoised[f64]) -> dx [B, 1, H, W] fp32, see guidance_dx_cond.
     ``dx_input`` (dx_cond models, ddim.py:1571, 1584): callable (h, x[f64]) -> the network's dx input, evaluated on the
-    current NOISY state before each denoiser call (get_dx_input with dx_norm='prob' == guidance_dx_cond)."""
+    current NOISY state before each denoiser call (get_dx_input with dx_norm='prob' == guidance_dx_cond).
+    ``sigma_data``, ``net``: as for get_denoised.  ``t_steps``: the float64 schedule [N + 1] to walk instead of edm_t_steps'
+    (a caller's own evaluation of the same expression).  ``trace``: a list that receives one dict of intermediates per step."""
     N = sp.timesteps
-    t_steps = edm_t_steps(N, sp.sigma_min, sp.sigma_max, sp.rho)
+    t_steps = edm_t_steps(N, sp.sigma_min, sp.sigma_max, sp.rho) if t_steps is None else torch.as_tensor(t_steps, dtype=torch.float64)
+    kw = dict(sigma_data=sigma_data, net=net)
     x_next = init_noise.to(torch.float64) * t_steps[0]
     xs = [x_next]
     for i in range(N):
@@ -442,33 +450,40 @@ def sample_edm_cond(P, cfg, h: Tensor, sp: SamplerParams, init_noise: Tensor,
         eps_i = step_noise[i] if step_noise is not None else torch.zeros_like(x_next)
         x_hat = x_next + (t_hat ** 2 - t_cur ** 2).sqrt() * sp.S_noise * eps_i
         dxi = None if dx_input is None else dx_input(h, x_hat)
-        denoised = get_denoised(P, cfg, x_hat, t_hat, cond=h, w=sp.w, dx=dxi)[0].to(torch.float64)
+        denoised = get_denoised(P, cfg, x_hat, t_hat, cond=h, w=sp.w, dx=dxi, **kw)[0].to(torch.float64)
         d_cur = (x_hat - denoised) / t_hat
         if guidance is not None:                 # guide_dx: - weight * dx / t_hat, weight = 5 (ddim.py:1577-1579)
             d_cur = d_cur - 5. * guidance(h, denoised) / t_hat
         x_next = x_hat + (t_next - t_hat) * d_cur
+        step = dict(t_hat=t_hat, x_hat=x_hat, D=denoised, d_cur=d_cur, x_euler=x_next)
         if i < N - 1:
             dxi = None if dx_input is None else dx_input(h, x_next)
-            denoised = get_denoised(P, cfg, x_next, t_next, cond=h, w=sp.w, dx=dxi)[0].to(torch.float64)
+            denoised = get_denoised(P, cfg, x_next, t_next, cond=h, w=sp.w, dx=dxi, **kw)[0].to(torch.float64)
             d_prime = (x_next - denoised) / t_next
             if guidance is not None:             # the reference divides by t_hat here too (ddim.py:1590-1591)
                 d_prime = d_prime - 5. * guidance(h, denoised) / t_hat
             x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime)
+            step.update(D2=denoised, d_prime=d_prime)
+        if trace is not None:
+            trace.append(dict(step, x_next=x_next))
         xs = [x_next] if return_last else xs + [x_next]
     return torch.stack(xs, dim=0).permute(1, 0, 3, 4, 2).contiguous()
 
 
 def sample_edm(P, cfg, cond: Tensor, hu_mask: Tensor, sp: SamplerParams, init_noise: Tensor,
                step_noise: Optional[Sequence[Tensor]] = None, n_state: int = 2,
-               return_last: bool = True) -> Tensor:
+               return_last: bool = True, sigma_data: float = SIGMA_DATA, t_steps: Optional[Tensor] = None, net=None,
+               trace: Optional[list] = None) -> Tensor:
     """PlMcedm.sample_edm, mcedm.py:570-638 with guide_dx False / dx_cond False.
 
     ``init_noise`` replaces ``randn_like(hu)`` (:576) and ``step_noise[i]`` the
     per-step ``randn_like(x_cur)`` (:608); when ``step_noise`` is None the churn
     term is taken as zero noise (only valid for S_churn == 0 where its factor is 0).
+    ``sigma_data``, ``t_steps``, ``net``, ``trace``: as for sample_edm_cond.
     Returns [B, T, H, W, C] float64 like the reference."""
     N = sp.timesteps
-    t_steps = edm_t_steps(N, sp.sigma_min, sp.sigma_max, sp.rho)
+    t_steps = edm_t_steps(N, sp.sigma_min, sp.sigma_max, sp.rho) if t_steps is None else torch.as_tensor(t_steps, dtype=torch.float64)
+    kw = dict(sigma_data=sigma_data, net=net)
     hu_known = cond[:, 0:n_state]
     x_next = init_noise.to(torch.float64) * t_steps[0]
     x_next = hu_known * (1 - hu_mask) + x_next * hu_mask
@@ -480,21 +495,141 @@ def sample_edm(P, cfg, cond: Tensor, hu_mask: Tensor, sp: SamplerParams, init_no
         t_hat = t_cur + gamma * t_cur
         eps_i = step_noise[i] if step_noise is not None else torch.zeros_like(x_cur)
         x_hat = x_cur + (t_hat ** 2 - t_cur ** 2).sqrt() * sp.S_noise * eps_i * hu_mask
-        denoised, _ = get_denoised(P, cfg, x_hat, t_hat, cond=cond, w=sp.w)
+        denoised, _ = get_denoised(P, cfg, x_hat, t_hat, cond=cond, w=sp.w, **kw)
         denoised = denoised.to(torch.float64)
         d_cur = (x_hat - denoised) / t_hat
         x_next = x_hat + (t_next - t_hat) * d_cur * hu_mask
+        step = dict(t_hat=t_hat, x_hat=x_hat, D=denoised, d_cur=d_cur, x_euler=x_next)
         if i < N - 1:
-            denoised, _ = get_denoised(P, cfg, x_next, t_next, cond=cond, w=sp.w)
+            denoised, _ = get_denoised(P, cfg, x_next, t_next, cond=cond, w=sp.w, **kw)
             denoised = denoised.to(torch.float64)
             d_prime = (x_next - denoised) / t_next
             x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime) * hu_mask
+            step.update(D2=denoised, d_prime=d_prime)
+        if trace is not None:
+            trace.append(dict(step, x_next=x_next))
         if return_last:
             xs = [x_next]
         else:
             xs.append(x_next)
     xs = torch.stack(xs, dim=0)
     return xs.permute(1, 0, 3, 4, 2).contiguous()      # 't b c h w -> b t h w c'
+
+
+# --------------------------------------------------------------------------- #
+# the epsilon-prediction single-task model (PlCondDdim, models/ddim.py:1053-1605): VP Heun sampler and DDIM sampler
+# --------------------------------------------------------------------------- #
+def self_cond_net(P, cfg: UNetConfig):
+    """DhariwalUNet.forward of a self-conditioning model as ``net(x, labels, cond, x_self_cond) -> F``: cat_conditioning
+    (adm_blocks.py:319-333) builds cat(cond, x_self_cond, x), zeros standing in for whichever is None, so cfg.cond_channels
+    counts the channels of cond AND of x_self_cond (= in_channels)."""
+    def net(x, labels, cond=None, x_self_cond=None):
+        sc = torch.zeros_like(x) if x_self_cond is None else x_self_cond
+        n_cond = cfg.cond_channels - x.shape[1]
+        c = torch.zeros((x.shape[0], n_cond) + tuple(x.shape[2:]), dtype=x.dtype) if cond is None else cond
+        return unet_forward(P, cfg, x, labels, torch.cat([c, sc], dim=1))
+    return net
+
+
+def get_denoised_vp(net, xt: Tensor, t: Tensor, c_noise, cond: Optional[Tensor] = None, x_self_cond: Optional[Tensor] = None,
+                    w: Optional[float] = None, scale_cond: bool = True):
+    """PlDdim.get_denoised as PlCondDdim inherits it, models/ddim.py:915-947 with dx None.  ``net(x, labels, cond,
+    x_self_cond) -> F``; ``c_noise``: the label num_timesteps - 1 - round_sigma(sigma, return_index=True) (:925), which the
+    caller derives from its own table; ``scale_cond``: model.cat_condition (:932: True on the ADM U-Net, False with cond_enc)."""
+    xt = xt.to(torch.float32)
+    sigma = t.to(torch.float32).reshape(-1, 1, 1, 1)
+    c_skip = 1
+    c_out = -sigma
+    c_in = 1 / (sigma ** 2 + 1).sqrt()
+    labels = torch.as_tensor(c_noise, dtype=torch.float32).reshape(-1)
+    x_self_cond = (c_in * x_self_cond).to(torch.float32) if x_self_cond is not None else None
+    if cond is not None:
+        cond = (c_in * cond).to(torch.float32) if scale_cond else cond
+    if w is None or abs(w) < 0.001 or cond is None:
+        F_x = net(c_in * xt, labels, cond, x_self_cond)
+    else:
+        F_x = (w + 1) * net(c_in * xt, labels, cond, x_self_cond) - w * net(c_in * xt, labels, None, x_self_cond)
+    D_x = c_skip * xt + c_out * F_x
+    return D_x, F_x
+
+
+def sample_vp_heun(net, h: Optional[Tensor], t_steps, t_hat, c_noise, init_noise: Tensor,
+                   step_noise: Optional[Sequence[Tensor]] = None, S_noise: float = 1.0, w: Optional[float] = 0.0, guidance=None,
+                   return_last: bool = True, scale_cond: bool = True, trace: Optional[list] = None) -> Tensor:
+    """PlCondDdim.sample_edm, models/ddim.py:1532-1601, from its ROUNDED schedule on: ``t_steps`` [N + 1] float64 (:1553, last 0),
+    ``t_hat`` [N] = round_sigma(t_cur + gamma t_cur) (:1566-1567) and ``c_noise`` [2 N], the network's label at t_hat[i] and at
+    t_steps[i + 1] -- what mcedm_vp_sampler_desc carries.  ``h`` [B, cond_ch, H, W], ``init_noise`` [B, C, H, W] replaces u_noise,
+    ``step_noise[i]`` the randn_like(x_cur) of :1568 (None: zeros, exact where t_hat == t_cur).  x_self_cond is None throughout
+    (get_self_cond_edm, :1603-1605).  ``guidance`` (guide_dx=True): callable (h, denoised[f64]) -> dx [B, 1, H, W] fp32; both
+    stages divide it by t_hat (:1578, 1590).  ``trace``: a list that receives one dict of intermediates per step.
+    Returns [B, T, H, W, C] float64."""
+    t_steps = torch.as_tensor(t_steps, dtype=torch.float64)
+    t_hats = torch.as_tensor(t_hat, dtype=torch.float64)
+    N = len(t_hats)
+    x_next = init_noise.to(torch.float64) * t_steps[0]
+    xs = [x_next]
+    for i in range(N):
+        t_cur, t_next, t_hat_i = t_steps[i], t_steps[i + 1], t_hats[i]
+        x_cur = x_next
+        eps_i = step_noise[i] if step_noise is not None else torch.zeros_like(x_cur)
+        x_hat = x_cur + (t_hat_i ** 2 - t_cur ** 2).sqrt() * S_noise * eps_i
+        denoised = get_denoised_vp(net, x_hat, t_hat_i, c_noise[2 * i], cond=h, w=w, scale_cond=scale_cond)[0].to(torch.float64)
+        d_cur = (x_hat - denoised) / t_hat_i
+        if guidance is not None:
+            d_cur = d_cur - 5. * guidance(h, denoised) / t_hat_i
+        x_next = x_hat + (t_next - t_hat_i) * d_cur
+        step = dict(t_hat=t_hat_i, x_hat=x_hat, D=denoised, d_cur=d_cur, x_euler=x_next)
+        if i < N - 1:
+            denoised = get_denoised_vp(net, x_next, t_next, c_noise[2 * i + 1], cond=h, w=w, scale_cond=scale_cond)[0].to(torch.float64)
+            d_prime = (x_next - denoised) / t_next
+            if guidance is not None:
+                d_prime = d_prime - 5. * guidance(h, denoised) / t_hat_i
+            x_next = x_hat + (t_next - t_hat_i) * (0.5 * d_cur + 0.5 * d_prime)
+            step.update(D2=denoised, d_prime=d_prime)
+        if trace is not None:
+            trace.append(dict(step, x_next=x_next))
+        xs = [x_next] if return_last else xs + [x_next]
+    return torch.stack(xs, dim=0).permute(1, 0, 3, 4, 2).contiguous()
+
+
+def sample_cond_ddim(net, h: Optional[Tensor], alphas_ext: Tensor, seq: Sequence[int], init_noise: Tensor, eta: float = 0.0,
+                     w: Optional[float] = 0.0, eta_noise: Optional[Sequence[Tensor]] = None, self_cond: bool = True,
+                     return_last: bool = True, trace: Optional[list] = None) -> Tuple[Tensor, Tensor]:
+    """PlCondDdim.sample, models/ddim.py:1452-1530 with guide_dx False and dx_cond False, fp32 like the reference.  ``seq``: the
+    timestep sequence of :1463-1470; ``alphas_ext``: the table compute_alpha indexes with t + 1 (:700-704); ``eta_noise[k]``
+    replaces the torch.rand_like of :1512 in the k-th step walked; ``self_cond``: model.self_condition (:1490).
+    Returns (xs, x0_preds) 'b t h w c'."""
+    n = init_noise.shape[0]
+    seq = list(seq)
+    seq_next = [-1] + seq[:-1]
+    xs, x0_preds, x0_t = [init_noise], [], None
+    for k, (i, j) in enumerate(zip(reversed(seq), reversed(seq_next))):
+        t = torch.ones(n) * i
+        at = alphas_ext.index_select(0, t.long() + 1).view(-1, 1, 1, 1)
+        at_next = alphas_ext.index_select(0, (torch.ones(n) * j).long() + 1).view(-1, 1, 1, 1)
+        xt = xs[-1]
+        x_sc = x0_t if self_cond else None
+        if w is None or abs(w) < 0.001:
+            et = net(xt, t, h, x_sc)
+        else:
+            et = (w + 1) * net(xt, t, h, x_sc) - w * net(xt, t, None, x_sc)
+        x0_t = (xt - et * (1 - at).sqrt()) / at.sqrt()
+        if abs(eta) > 1e-10:
+            c1 = eta * ((1 - at / at_next) * (1 - at_next) / (1 - at)).sqrt()
+            c2 = ((1 - at_next) - c1 ** 2).sqrt()
+            xt_next = at_next.sqrt() * x0_t + c1 * eta_noise[k] + c2 * et
+        else:
+            c2 = (1 - at_next).sqrt()
+            xt_next = at_next.sqrt() * x0_t + c2 * et
+        if trace is not None:
+            trace.append(dict(t=i, xt=xt, et=et, x0=x0_t, xt_next=xt_next))
+        if return_last:
+            x0_preds, xs = [x0_t], [xt_next]
+        else:
+            x0_preds.append(x0_t)
+            xs.append(xt_next)
+    return (torch.stack(xs, dim=0).permute(1, 0, 3, 4, 2).contiguous(),
+            torch.stack(x0_preds, dim=0).permute(1, 0, 3, 4, 2).contiguous())
 
 
 # --------------------------------------------------------------------------- #
