@@ -318,6 +318,13 @@ int mcedm_unet_backward_bucketed(const mcedm_plan* plan, const void* packed, con
                                  const float* dF, float* const* grads, void* workspace, size_t workspace_bytes, int B, int H,
                                  int W, int n_buckets, const int32_t* bucket_first_param, void* const* bucket_events,
                                  void* stream);
+/* mcedm_unet_backward_bucketed for a dx_cond plan, after mcedm_unet_forward_dx(..., training = 1): dx [B, dx_channels, H, W] is
+ * that forward's (NULL: None -- the gradients of dx_enc.* are then exactly zero, those of combine_enc.* are not).  n_buckets == 0
+ * records no events, as in mcedm_edm_denoise_backward_dx.  The two entries above keep refusing dx_cond plans. */
+int mcedm_unet_backward_dx(const mcedm_plan* plan, const void* packed, const float* const* params, const float* x,
+                           const float* dx, const float* cond, const float* x_scale, const float* noise_labels, int n_noise,
+                           const float* dF, float* const* grads, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                           int n_buckets, const int32_t* bucket_first_param, void* const* bucket_events, void* stream);
 
 /* VP-preconditioned Heun sampler of an epsilon network (PlCondDdim.sample_edm, models/ddim.py:1532-1601, around get_denoised
  * :915-947): D = x + (-sigma) F(c_in x, c_noise, c_in cond), c_in = 1 / sqrt(sigma^2 + 1) in fp32, state fp64.  The host
@@ -359,6 +366,23 @@ int mcedm_vp_heun_sample_guided(const mcedm_plan* plan, const void* packed, cons
                                 const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const double* step_noise,
                                 const uint64_t* rng_seed, double* out, int return_last, void* workspace, size_t workspace_bytes,
                                 int B, int H, int W, void* stream);
+/* PlCondDdim.sample_edm of a dx_cond model (hparams.model.dx_cond with dx_norm 'prob'): mcedm_vp_heun_sample_guided's signature
+ * with dxc in front of gd.  In front of EACH of the two get_denoised calls of a step, dx_in = get_dx_input(h, x) (:1571, 1584 ->
+ * get_dx_pde :1424-1450 with calc_prob: the mean of the two field gradients, [B, 1, H, W]) at the current state x cast to fp32
+ * (x_hat, then the Euler x_next), h = cond[:, 0] of the caller's unscaled cond; the network reads fl(c_in * dx_in) (:933-934:
+ * here dx IS scaled, unlike mcedm_heun_sample_dxcond) -- one fp32 rounding of the finished mean, formed where the gradient
+ * kernel stores it.  With |sp->w| >= 0.001 the second evaluation reads neither cond nor dx (:938-942).  dxc: the description of
+ * mcedm_heun_sample_dxcond (weight unused); gd: PDE guidance on top, NULL = none, with a gradient buffer of its own.  Before any
+ * launch, MCEDM_ERR_INVALID unless: the plan has dx_mode != MCEDM_DX_NONE, in_channels == 1 and dx_channels == 1; dxc != NULL with
+ * system 1 or 2; cond != NULL with sp->cond_channels >= 1; for Darcy H == W > 4; gd passes mcedm_vp_heun_sample_guided's checks;
+ * at most one of step_noise and rng_seed is given.  mcedm_vp_dxcond_workspace_bytes sizes the call with dxc AND gd (exact);
+ * without gd one gradient buffer less is needed.  There is no _rng twin.  mcedm_vp_heun_sample[_rng|_guided] keep refusing dx_cond
+ * plans. */
+int mcedm_vp_dxcond_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes);
+int mcedm_vp_heun_sample_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_vp_sampler_desc* sp,
+                                const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+                                const float* init_noise, const double* step_noise, const uint64_t* rng_seed, double* out,
+                                int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream);
 
 /* PlCondDdim.sample (models/ddim.py:1452-1530): the DDIM sampler of the single-task conditional network, guide_dx False,
  * dx_cond False.  Everything is fp32 like the reference; one network evaluation per step, two with guidance, and one fused
@@ -408,6 +432,19 @@ int mcedm_cond_ddim_sample_guided(const mcedm_plan* plan, const void* packed, co
                                   const mcedm_guidance_desc* gd, const float* cond, const float* init_noise, const float* eta_noise,
                                   const uint64_t* rng_seed, float* xs_out, float* x0_out, int return_last, void* workspace,
                                   size_t workspace_bytes, int B, int H, int W, void* stream);
+/* PlCondDdim.sample of a dx_cond model: mcedm_cond_ddim_sample_guided's signature with dxc in front of gd.  At every step
+ * dx_in = get_dx_input(h, xt) (:1492) at the step's CURRENT noisy state xt (the first step's is init_noise), UNSCALED, is the dx
+ * input of model(xt, t, cond=h, x_self_cond, dx=dx_in); its launches go in front of the step's network launches.  With
+ * |sp->w| >= 0.001 the second pass keeps the self-conditioning channels and reads neither cond nor dx (:1495-1497).  The first
+ * step has dx but no x_self_cond.  dxc, gd, the checks, the missing _rng twin and the workspace
+ * (mcedm_cond_ddim_dxcond_workspace_bytes): as for mcedm_vp_heun_sample_dxcond.  mcedm_cond_ddim_sample[_rng|_guided] keep refusing
+ * dx_cond plans. */
+int mcedm_cond_ddim_dxcond_workspace_bytes(const mcedm_plan* plan, int B, int H, int W, size_t* bytes);
+int mcedm_cond_ddim_sample_dxcond(const mcedm_plan* plan, const void* packed, const mcedm_cond_ddim_desc* sp,
+                                  const mcedm_guidance_desc* dxc, const mcedm_guidance_desc* gd, const float* cond,
+                                  const float* init_noise, const float* eta_noise, const uint64_t* rng_seed, float* xs_out,
+                                  float* x0_out, int return_last, void* workspace, size_t workspace_bytes, int B, int H, int W,
+                                  void* stream);
 
 /* ---- kernel-level entry points ----------------------------------------------------------
  * The building blocks the schedules above are made of, exported so that each kernel can be

@@ -8,7 +8,8 @@ models/adm_blocks.py:10-15,221-222); the network is executed as one fused schedu
 not module by module.  ``dx_cond`` (the network conditioned on the PDE-residual gradient, models/adm_blocks.py:233-280,
 334-362) is built in both of the reference's forms: ``cat_dx=True`` (dx concatenated to conv_in's input) and
 ``cat_dx=False`` (``dx_enc`` = Conv3x3 -> GELU -> Conv3x3 and ``combine_enc``).  ``self_cond`` (adm_blocks.py:227-238,
-318-331) runs as the cat_cond network whose conditioning input is cat(cond, x_self_cond).  Configurations outside the hot path
+318-331) runs as the cat_cond network whose conditioning input is cat(cond, x_self_cond), with or without dx_cond: the input
+order is cat(cond, x_self_cond, x, dx).  Configurations outside the hot path
 (cond_enc / class or augment labels / dropout) raise NotImplementedError instead of silently computing
 something else.  There is no PyTorch fallback: without the HIP library or on a CPU tensor, forward raises.
 """
@@ -105,8 +106,6 @@ class DhariwalUNet(nn.Module):
         cond_channels = _get(m, "cond_channels", 0)
         if cond_channels > 0 and not _get(m, "cat_cond", False):
             unsupported.append("cond_enc (cat_cond=False)")
-        if self_cond and _get(m, "dx_cond", False):
-            unsupported.append("self_cond with dx_cond")
         ch, mult = m.ch, tuple(m.ch_mult)
         # attention widths: the bottleneck 'in0' block always, plus every level named in attn_resolutions; the
         # kernels are built for head_dim 64, the reference's head_dim is C / (C // 64) (adm_blocks.py:135,175)

@@ -500,6 +500,20 @@ extern "C" int mcedm_unet_backward_bucketed(const mcedm_plan* plan, const void* 
                                n_buckets, bucket_first_param, bucket_events, stream, BwdFrom{dF, noise_labels, x_scale});
 }
 
+// the same for a dx_cond plan (PlCondDdim.training_step with hparams.model.dx_cond): dx is the forward's (NULL: None, the
+// gradients of dx_enc.* are then zero); n_buckets == 0 records no events
+extern "C" int mcedm_unet_backward_dx(const mcedm_plan* plan, const void* packed, const float* const* params, const float* x,
+                                      const float* dx, const float* cond, const float* x_scale, const float* noise_labels,
+                                      int n_noise, const float* dF, float* const* grads, void* workspace, size_t workspace_bytes,
+                                      int B, int H, int W, int n_buckets, const int32_t* bucket_first_param,
+                                      void* const* bucket_events, void* stream) {
+  VariantScope variant_scope__(plan);
+  MCEDM_REQUIRE(dF != nullptr, "unet_backward_dx: null dF");
+  MCEDM_REQUIRE(n_buckets >= 0, "unet_backward_dx: n_buckets must be >= 0");
+  return denoise_backward_impl(plan, packed, params, x, dx, n_noise, cond, nullptr, grads, workspace, workspace_bytes, B, H, W,
+                               n_buckets, bucket_first_param, bucket_events, stream, BwdFrom{dF, noise_labels, x_scale});
+}
+
 extern "C" int mcedm_unet_backward(const mcedm_plan* plan, const void* packed, const float* const* params, const float* x,
                                    const float* cond, const float* x_scale, const float* noise_labels, int n_noise,
                                    const float* dF, float* const* grads, void* workspace, size_t workspace_bytes, int B, int H,

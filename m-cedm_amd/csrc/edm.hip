@@ -307,13 +307,15 @@ int launch_vp_coef(float c_in, int n_self, int n_in, Coef* out, hipStream_t s) {
 // VP sampler of the ADM U-Net (PlCondDdim.sample_edm, models/ddim.py:1532-1601): one row set of conv_in transforms for
 // cat(cond', x), every channel scaled by c_in (get_denoised scales x, cond and x_self_cond, :921-935), and the network's
 // noise label c_noise written where the forward reads it
-__global__ void vp_prepare_kernel(float c_in, int n_rows, float c_noise, Coef* __restrict__ coef, float* __restrict__ label) {
+__global__ void vp_prepare_kernel(float c_in, int n_rows, int n_plain, float c_noise, Coef* __restrict__ coef,
+                                  float* __restrict__ label) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < n_rows) coef[c] = Coef{0.f, c_in, 0.f, 0.f};
+  if (c < n_rows + n_plain) coef[c] = Coef{0.f, c < n_rows ? c_in : 1.0f, 0.f, 0.f};
   if (c == 0) *label = c_noise;
 }
-int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* label, hipStream_t s) {
-  hipLaunchKernelGGL(vp_prepare_kernel, dim3(ceil_div(n_rows, 64)), dim3(64), 0, s, c_in, n_rows, c_noise, coef, label);
+int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* label, hipStream_t s, int n_plain) {
+  hipLaunchKernelGGL(vp_prepare_kernel, dim3(ceil_div(n_rows + n_plain, 64)), dim3(64), 0, s, c_in, n_rows, n_plain, c_noise, coef,
+                     label);
   MCEDM_LAUNCH_CHECK("vp_prepare_kernel");
   return MCEDM_OK;
 }

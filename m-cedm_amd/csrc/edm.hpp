@@ -43,6 +43,7 @@ struct GuideIO {
   float* out[2]; long out_sb[2], out_st, out_sx;
   float sub[2], div[2];                       // un-normalisation x * div + sub applied while reading
   int mean;                                   // 1: write the mean of the two field gradients to out[0] only
+  float scale = 1.f;                          // mean form only: out[0] = fl(scale * mean), one fp32 rounding on the finished mean
 };
 int launch_swe_guidance(const GuideIO& io, int B, int T, int X, float half_dt, float dx, float scale2_h, float scale2_u,
                         hipStream_t s);
@@ -54,8 +55,9 @@ int launch_vp_finish(const float* x, const float* F, float sigma, size_t total, 
 // conv_in transform rows of the VP network input: n_self zero/self-conditioning channels pass, the state is scaled by c_in
 int launch_vp_coef(float c_in, int n_self, int n_in, Coef* out, hipStream_t s);
 // ---- VP sampler of the ADM U-Net (PlCondDdim.sample_edm, models/ddim.py:1532-1601)
-// conv_in rows: all n_rows channels of cat(cond', x) scaled by c_in; *label = c_noise
-int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* label, hipStream_t s);
+// conv_in rows: all n_rows channels of cat(cond', x) scaled by c_in, n_plain rows behind them (the dx channels of a cat_dx
+// plan, which arrive scaled) by 1; *label = c_noise
+int launch_vp_prepare(float c_in, int n_rows, float c_noise, Coef* coef, float* label, hipStream_t s, int n_plain = 0);
 // D = x + (-sigma) * F with F = (w + 1) F - w Fu when Fu != NULL                  (get_denoised, ddim.py:940-945)
 int launch_vp_cfg_finish(const float* x, const float* F, const float* Fu, double w, float sigma, size_t total, float* D,
                          hipStream_t s);

@@ -80,9 +80,11 @@ static inline int heun_update(HeunState& h, int i, double t_hat, double t_next, 
 // MEAN over the two field gradients (calc_prob=True) -> [B, 1, H, W].  cond [B, cond_channels, H, W] of either network: its
 // first plane is h.
 // (the same call on the current noisy state instead of D is get_dx_input(h, x) with dx_norm == 'prob', ddim.py:601-613)
+// scale: the stored value is fl(scale * dx), what PlCondDdim.get_denoised hands its network (c_in * dx, ddim.py:933-934)
 static inline int guidance_dx(int cond_channels, const mcedm_guidance_desc& g, const float* cond, const float* D, float* dx,
-                              float* scratch, int B, int H, int W, hipStream_t s) {
+                              float* scratch, int B, int H, int W, hipStream_t s, float scale = 1.f) {
   GuideIO io{};
+  io.scale = scale;
   const long hw = (long)H * W;
   io.in[0] = cond; io.in[1] = D; io.gt[0] = cond; io.gt[1] = D;
   io.in_sb[0] = (long)cond_channels * hw; io.in_sb[1] = hw; io.st = W; io.sx = 1;
@@ -236,6 +238,25 @@ static inline int guidance_check(const char* who, const mcedm_guidance_desc* gd,
   MCEDM_REQUIRE(cond != nullptr && cond_channels >= 1, "%s: gd needs cond (h in cond[:, 0]) and sp->cond_channels >= 1 (got cond %s, "
                 "cond_channels %d)", who, cond ? "given" : "NULL", cond_channels);
   MCEDM_REQUIRE(gd->system == 1 || (H == W && H > 4), "%s: gd: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)",
+                who, H, W);
+  return MCEDM_OK;
+}
+
+
+// What the dx_cond entries of the epsilon model's samplers check before any launch (mcedm_vp_heun_sample_dxcond,
+// mcedm_cond_ddim_sample_dxcond): the plan, the description of the dx residual and the conditioning field it reads
+static inline int dxcond_check(const char* who, const mcedm_plan* plan, const mcedm_guidance_desc* dxc, const float* cond,
+                               int cond_channels, int H, int W) {
+  MCEDM_REQUIRE(plan != nullptr, "%s: null plan", who);
+  const mcedm_unet_desc& d = plan->desc;
+  MCEDM_REQUIRE(d.dx_mode != MCEDM_DX_NONE && d.in_channels == 1 && d.dx_channels == 1,
+                "%s: needs a dx_cond plan of the single-task model (dx_mode %d, in_channels %d, dx_channels %d; state u, one dx "
+                "channel), models/ddim.py:1424-1450", who, d.dx_mode, d.in_channels, d.dx_channels);
+  MCEDM_REQUIRE(dxc != nullptr, "%s: dxc (the residual whose gradient is the network's dx input) is null", who);
+  MCEDM_REQUIRE(dxc->system == 1 || dxc->system == 2, "%s: dxc->system %d: dx system must be 1 (SWE) or 2 (Darcy)", who, dxc->system);
+  MCEDM_REQUIRE(cond != nullptr && cond_channels >= 1, "%s: dxc needs cond (h in cond[:, 0]) and sp->cond_channels >= 1 (got cond %s, "
+                "cond_channels %d)", who, cond ? "given" : "NULL", cond_channels);
+  MCEDM_REQUIRE(dxc->system == 1 || (H == W && H > 4), "%s: dxc: the Darcy residual needs a square grid larger than 4 x 4 (got %d x %d)",
                 who, H, W);
   return MCEDM_OK;
 }

@@ -281,7 +281,7 @@ extern "C" int mcedm_op_conv_gn(const float* xa, const float* xb, int Ca, int Cb
 // freqs[k] = (1/10000)^(k/half) exactly as the plan packs them (adm_blocks.py:193-196, endpoint=False)
 __global__ void op_freqs_kernel(float* f, int half) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < half) f[k] = powf(1.0f / 10000.0f, (float)k / (float)half);
+  if (k < half) f[k] = (float)pow((double)(1.0f / 10000.0f), (double)((float)k / (float)half));
 }
 
 extern "C" int mcedm_op_embedding(const float* labels, int n, int ch, const float* w0, const float* b0, const float* w1,

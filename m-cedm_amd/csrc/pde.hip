@@ -161,8 +161,13 @@ struct GradView {
   float* p[2];
   long sb[2], st, sx;
   int mean;
+  float scale;                   // mean form: the stored value is fl(scale * mean); 1 leaves the mean bit for bit
   __device__ __forceinline__ void put(long b, int t, int x, float g0, float g1) const {
-    if (mean) { p[0][b * sb[0] + t * st + x * sx] = (g0 + g1) / 2.0f; return; }
+    if (mean) {
+      const float m = (g0 + g1) / 2.0f;
+      p[0][b * sb[0] + t * st + x * sx] = scale * m;      // (two roundings, as torch forms c_in * dx from the fp32 dx)
+      return;
+    }
     p[0][b * sb[0] + t * st + x * sx] = g0;
     p[1][b * sb[1] + t * st + x * sx] = g1;
   }
@@ -331,7 +336,7 @@ int launch_swe_guidance(const GuideIO& io, int B, int T, int X, float half_dt, f
                         hipStream_t s) {
   FieldView pv{{io.in[0], io.in[1]}, {io.in_sb[0], io.in_sb[1]}, io.st, io.sx, {io.sub[0], io.sub[1]}, {io.div[0], io.div[1]}};
   FieldView gv{{io.gt[0], io.gt[1]}, {io.in_sb[0], io.in_sb[1]}, io.st, io.sx, {io.sub[0], io.sub[1]}, {io.div[0], io.div[1]}};
-  GradView ov{{io.out[0], io.out[1]}, {io.out_sb[0], io.out_sb[1]}, io.out_st, io.out_sx, io.mean};
+  GradView ov{{io.out[0], io.out[1]}, {io.out_sb[0], io.out_sb[1]}, io.out_st, io.out_sx, io.mean, io.scale};
   const size_t cells = (size_t)B * T * X;
   const float inv_n = 1.0f / (float)(2.0 * (double)cells);
   hipLaunchKernelGGL(swe_fv_guidance_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, pv, gv, ov, T, X, cells,
@@ -342,7 +347,7 @@ int launch_swe_guidance(const GuideIO& io, int B, int T, int X, float half_dt, f
 
 int launch_darcy_guidance(const GuideIO& io, float* scratch, int B, int S, float two_dx, int calc_prob, hipStream_t s) {
   FieldView pv{{io.in[0], io.in[1]}, {io.in_sb[0], io.in_sb[1]}, io.st, io.sx, {io.sub[0], io.sub[1]}, {io.div[0], io.div[1]}};
-  GradView ov{{io.out[0], io.out[1]}, {io.out_sb[0], io.out_sb[1]}, io.out_st, io.out_sx, io.mean};
+  GradView ov{{io.out[0], io.out[1]}, {io.out_sb[0], io.out_sb[1]}, io.out_st, io.out_sx, io.mean, io.scale};
   const size_t inner = (size_t)B * (S - 4) * (S - 4), cells = (size_t)B * S * S;
   hipLaunchKernelGGL(darcy_guidance_g_kernel, dim3((unsigned)((inner + 255) / 256)), dim3(256), 0, s, pv, scratch, S, inner, two_dx,
                      calc_prob, 1.0f / (float)inner);

@@ -259,10 +259,13 @@ __global__ void batched_copy_kernel(CopyBatch b) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < b.n[j]; i += gridDim.x * blockDim.x) d[i] = s[i];
 }
 
-// freqs[k] = (1/10000)^(k/half)   (adm_blocks.py:193-196, endpoint=False), fp32
+// freqs[k] = (1/10000)^(k/half)   (adm_blocks.py:193-196, endpoint=False): the fp32 power of the fp32 operands, correctly rounded
+// (evaluated in fp64).  The device's powf is 1 ulp off that for 7 of the 32 frequencies at ch = 64, where torch's CPU pow is not;
+// at a DDPM label of ~1000 one ulp of a frequency is 3e-5 in cos / sin(t * freq) (500 ulp), which the gradient of
+// map_layer0.weight shows at 1e-5 of its maximum.
 __global__ void freqs_kernel(float* f, int half) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < half) f[k] = powf(1.0f / 10000.0f, (float)k / (float)half);
+  if (k < half) f[k] = (float)pow((double)(1.0f / 10000.0f), (double)((float)k / (float)half));
 }
 
 // Every conv weight of a plan is re-laid per optimisation step (direct form, its data-gradient mirror, both again in

@@ -105,6 +105,31 @@ class _SingleTask(_PlBase):
             cond_in = torch.cat([cond_in, node], dim=-1)
         return cond_in
 
+    # ---- the PDE-residual gradient of (h, u): dx_cond's network input and guide_dx's correction, shared by both models ----
+    def get_dx_pde(self, cond, x_denoised, calc_prob=False):
+        """models/ddim.py:1424-1450: gradient of the PDE residual of (h from cond, u = x_denoised), un-normalised, w.r.t. that
+        state; mean (calc_prob) or sum over the two field gradients."""
+        h = cond[:, :self.h_ch].to(torch.float32).permute(0, 2, 3, 1)
+        u = x_denoised.to(torch.float32).permute(0, 2, 3, 1)
+        h_un = self.normalizer_input((h + 1.0) / 2.0 if self.rescaled else h, inverse=True)
+        u_un = self.inverse_data_transform_u(u)
+        x_un = torch.cat([h_un, u_un], dim=-1).contiguous()
+        d = self.pde_loss(x_un, x_un, self.normalizer_input, self.normalizer_target, True, calc_prob).permute(0, 3, 1, 2)
+        return torch.mean(d, dim=1, keepdim=True) if calc_prob else torch.sum(d, dim=1)
+
+    def get_dx_input(self, cond, x_denoised):
+        """models/ddim.py:601-639 with dx_norm == 'prob' (see the modules' __init__): the log-probability residual gradient itself.  The
+        reference's NaN test never fires: both residual classes zero the NaNs of the gradient they return."""
+        if not self.dx_cond:
+            return None
+        return self.get_dx_pde(cond, x_denoised, calc_prob=True).contiguous()
+
+    def get_dx_log_prob(self, cond, x_denoised, guide_dx):
+        """models/ddim.py:641-650 (the residual classes already zero the NaNs of the gradient)."""
+        if not guide_dx:
+            return torch.zeros_like(x_denoised)
+        return self.get_dx_pde(cond, x_denoised, calc_prob=True)
+
     # ---- evaluation loops (models/ddim.py:1154-1319): sampling on the device, metric bookkeeping on the host ----------
     def get_pde_loss(self, cond, x_denoised, x_gt_unnorm=None, noise_level=None, clamp_loss=True, do_rearrange=True,
                      reduce=True):
@@ -529,30 +554,6 @@ class PlCondEdm(_SingleTask):
         w = (1.0 / (sigma + 1.0)).sum().expand(sigma.numel()).contiguous() if self.pde_loss_prop_t else None
         return gd, gt, w
 
-    def get_dx_pde(self, cond, x_denoised, calc_prob=False):
-        """models/ddim.py:1424-1450: gradient of the PDE residual of (h from cond, u = x_denoised), un-normalised, w.r.t. that
-        state; mean (calc_prob) or sum over the two field gradients."""
-        h = cond[:, :self.h_ch].to(torch.float32).permute(0, 2, 3, 1)
-        u = x_denoised.to(torch.float32).permute(0, 2, 3, 1)
-        h_un = self.normalizer_input((h + 1.0) / 2.0 if self.rescaled else h, inverse=True)
-        u_un = self.inverse_data_transform_u(u)
-        x_un = torch.cat([h_un, u_un], dim=-1).contiguous()
-        d = self.pde_loss(x_un, x_un, self.normalizer_input, self.normalizer_target, True, calc_prob).permute(0, 3, 1, 2)
-        return torch.mean(d, dim=1, keepdim=True) if calc_prob else torch.sum(d, dim=1)
-
-    def get_dx_input(self, cond, x_denoised):
-        """models/ddim.py:601-639 with dx_norm == 'prob' (see __init__): the log-probability residual gradient itself.  The
-        reference's NaN test never fires: both residual classes zero the NaNs of the gradient they return."""
-        if not self.dx_cond:
-            return None
-        return self.get_dx_pde(cond, x_denoised, calc_prob=True).contiguous()
-
-    def get_dx_log_prob(self, cond, x_denoised, guide_dx):
-        """models/ddim.py:641-650 (the residual classes already zero the NaNs of the gradient)."""
-        if not guide_dx:
-            return torch.zeros_like(x_denoised)
-        return self.get_dx_pde(cond, x_denoised, calc_prob=True)
-
     def sample(self, h, u_noise, sparams, return_last=True, guide_dx=False):
         raise NotImplementedError("Only EDM sampler is supported for the model with EDM pre-conditioning")      # models/ddim.py:1739-1740
 
@@ -885,17 +886,18 @@ class PlDdim(_DdpmSchedule, _PlBase):
         return self._ddpm_eps_loss(self.forward(x, t, noise)[0], noise)
 
 
-def _eps_train_loss(module, x_noise, labels, cond, noise):
+def _eps_train_loss(module, x_noise, labels, cond, noise, dx=None):
     """NoiseEstimationLoss of PlCondDdim.training_step (models/ddim.py:1118-1152, models/losses.py:39-59):
     loss = mean_b sum_chw (F - noise)^2 with F = model(x_noise, t.float(), cond').  Forward and backward run in the HIP library
-    (mcedm_unet_forward, mcedm_eps_loss, mcedm_unet_backward)."""
+    (mcedm_unet_forward, mcedm_eps_loss, mcedm_unet_backward; with dx_cond mcedm_unet_forward_dx and mcedm_unet_backward_dx, dx
+    being the network's dx input of this batch or None)."""
     net: DhariwalUNet = module.model
 
     def run():
-        F = net.plan.forward(net.packed_weights(), x_noise, labels, cond=cond, ws=module._train_ws, training=True)
+        F = net.plan.forward(net.packed_weights(), x_noise, labels, cond=cond, ws=module._train_ws, training=True, dx=dx)
         loss, dF = _lib.eps_loss(F, noise, want_grad=True)
         return loss, lambda grads: net.plan.unet_backward(net.packed_weights(), net.named_param_dict(), x_noise, labels, cond, dF,
-                                                          grads, ws=module._train_ws)
+                                                          grads, ws=module._train_ws, dx=dx)
     return _TrainLoss.apply(module, run, *net.parameters())
 
 
@@ -907,7 +909,12 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
     Constructor, buffers (``betas``, ``logvar``), state_dict keys and method signatures follow the reference.  The training
     step runs in the HIP library: noising (mcedm_eps_noise_inputs), the self-conditioning pre-pass and its estimate written into
     the network's widened conditioning input (mcedm_eps_self_cond), forward, loss (mcedm_eps_loss) and backward from dF
-    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The PDE loss term and ``dx_cond`` raise.
+    (mcedm_unet_backward); ``sample_edm`` is mcedm_vp_heun_sample[_rng].  The PDE loss term raises.  ``dx_cond`` (with ``dx_norm:
+    prob``, the one normalisation the reference can run; ``cat_dx`` True or False) runs on the ADM U-Net: training draws the dx
+    switch first, evaluates the residual gradient on the noised target from the cond before the ``cond_p`` drop and feeds it to the
+    pre-pass and the main pass (mcedm_unet_forward_dx / mcedm_unet_backward_dx); ``sample`` and ``sample_edm`` evaluate it on the
+    device at every network evaluation (mcedm_cond_ddim_sample_dxcond: unscaled; mcedm_vp_heun_sample_dxcond: scaled by c_in), with
+    ``guide_dx`` on top if asked; it refuses what ``guide_dx`` refuses.
     ``sample`` (the DDIM loop, :1452-1530) is mcedm_cond_ddim_sample[_rng].  ``guide_dx=True`` (PDE guidance, :1499-1503 and
     :1576-1590) runs in both samplers on both networks (mcedm_[ddpm_]cond_ddim_sample_guided, mcedm_[ddpm_]vp_heun_sample_guided) for
     scalar gauss-normalised fields with h given on the device; every other form of it raises.
@@ -925,11 +932,17 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         self.save_hyperparameters()
         m, o = hparams.model, hparams.optimization
         self._on_ddpm_unet = not str(hparams.name).startswith("adm")                    # models/ddim.py:43-46
-        if _opt(m, "dx_cond", False):
-            raise NotImplementedError("dx_cond (models/ddim.py:33-35, 199-204) is not built for PlCondDdim")
+        # dx_cond (models/ddim.py:33-35, 199-204): as for PlCondEdm only dx_norm == 'prob' can run in the reference (pinned:
+        # tests/golden/cond_ddim_dx_cat.npz 'dx_norm_l2_raises'), so the other normalisations raise here as well
+        self.dx_cond = bool(_opt(m, "dx_cond", False))
+        self.dx_norm, self.dx_detach = _opt(m, "dx_norm", "l2"), _opt(m, "dx_detach", False)
+        if self.dx_cond and self.dx_norm != "prob":
+            raise NotImplementedError(f"dx_cond with dx_norm={self.dx_norm!r}: PlCondDdim.get_dx_input raises in the reference for "
+                                      "every dx_norm other than 'prob' (models/ddim.py:608-611, 1445-1448)")
+        if self.dx_cond and self._on_ddpm_unet:
+            raise NotImplementedError("dx_cond (models/ddim.py:33-35) is not built on the DDPM U-Net")
         if _opt(o, "pde_loss_lambda", 0.0):
             raise NotImplementedError("pde_loss_lambda > 0 (models/ddim.py:1144-1150) is not built")
-        self.dx_norm, self.dx_detach, self.dx_cond = _opt(m, "dx_norm", "l2"), _opt(m, "dx_detach", False), False
         self.node_type = bool(_opt(m, "node_type", False))
         if self.node_type:
             m.cond_channels = m.cond_channels + 1
@@ -954,20 +967,24 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
 
     # ---- epsilon-prediction forward (models/ddim.py:195-226) --------------------------------------------------------------
     def _noised_inputs(self, x, t, noise, cond, ws):
-        """x_noise, labels and the network's conditioning input of one forward, consuming torch's generator as the reference
-        does: the cond_p draw (:202), then the self-conditioning draw (:205) whose pre-pass runs in `ws` before anything
-        else uses it."""
+        """x_noise, labels, the network's conditioning input, t and dx of one forward, consuming torch's generator as the reference
+        does: with dx_cond the dx draw first (:199, only then), the cond_p draw (:202), then the self-conditioning draw (:205)
+        whose pre-pass runs in `ws` before anything else uses it.  dx = get_dx_input(cond[:, 0:h_ch], x_noise) is taken from the
+        cond BEFORE the cond_p drop, on the noised target, and goes to the pre-pass and the main pass alike (:216, :220)."""
         net = self.model
         x = x.to(torch.float32).contiguous()
         noise = noise.to(torch.float32).contiguous()
         t = torch.as_tensor(t).to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
         sa, sb = self._noise_tables(x.device)
         x_noise, labels = _lib.eps_noise_inputs(x, noise, t, sa, sb)
+        dx = None
+        if self.dx_cond and torch.rand(1) > 0.1:           # dx off with a small probability; it carries no gradient
+            dx = self._dx_train_input(cond, x_noise)
         if torch.rand(1) >= self.cond_p:
             cond = None                                    # the conditioning switched off for this batch
         cond = None if cond is None else cond.to(torch.float32).contiguous()
         if not net.self_condition:
-            return x_noise, labels, cond, t
+            return x_noise, labels, cond, t, dx
         B, _, H, W = x.shape
         shape = (B, net.plan_cond_channels, H, W)
         if self._stage is None or tuple(self._stage.shape) != shape or self._stage.device != x.device:
@@ -976,13 +993,21 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         if torch.rand(1) < 0.5:                            # no-grad pre-pass: F0 = model(x_noise, t, cond)
             pk = net.packed_weights()
             pre_cond = _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels) if cond is not None else None
-            F0 = net.plan.forward(pk, x_noise, labels, cond=pre_cond, ws=ws)
+            F0 = net.plan.forward(pk, x_noise, labels, cond=pre_cond, ws=ws, dx=dx)
             _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels, x_noise=x_noise, F0=F0, t=t, sqrt_ab=sa,
                                sqrt_1mab=sb)
-            return x_noise, labels, stage, t
+            return x_noise, labels, stage, t, dx
         if cond is None:
-            return x_noise, labels, None, t
-        return x_noise, labels, _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels), t
+            return x_noise, labels, None, t, dx
+        return x_noise, labels, _lib.eps_self_cond(stage, cond, net.cond_channels, net.state_channels), t, dx
+
+    def _dx_train_input(self, cond, x_noise):
+        """get_dx_input(cond[:, 0:h_ch], x_noise) of forward (:200-201) under the refusals of the samplers' dx path."""
+        if cond is None:
+            raise NotImplementedError("dx_cond needs the conditioning field: forward without cond is not built")
+        self._dx_check()
+        with torch.no_grad():
+            return self.get_dx_input(cond[:, 0:self.h_ch], x_noise)
 
     def forward(self, x, t, noise, cond=None):
         """models/ddim.py:195-226 without gradients: (output, x0_t)."""
@@ -991,8 +1016,8 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             return self._ddpm_eps_forward(x, t, noise, cond)
         net = self.model
         with torch.no_grad():
-            x_noise, labels, condp, t = self._noised_inputs(x, t, noise, cond, net._ws)
-            output = net.plan.forward(net.packed_weights(), x_noise, labels, cond=condp, ws=net._ws)
+            x_noise, labels, condp, t, dx = self._noised_inputs(x, t, noise, cond, net._ws)
+            output = net.plan.forward(net.packed_weights(), x_noise, labels, cond=condp, ws=net._ws, dx=dx)
             sa, sb = self._noise_tables(x.device)
             x0_t = torch.empty_like(output)
             _lib.eps_self_cond(x0_t, None, 0, output.shape[1], x_noise=x_noise, F0=output, t=t, sqrt_ab=sa, sqrt_1mab=sb)
@@ -1013,8 +1038,8 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         t = torch.cat([t, self.num_timesteps - t - 1], dim=0)[:n]
         if self._on_ddpm_unet:                       # under torch.no_grad() (see _adm_only): the loss value alone
             return self._ddpm_eps_loss(self._ddpm_eps_forward(u, t, noise, cond_in)[0], noise)
-        x_noise, labels, condp, _ = self._noised_inputs(u, t, noise, cond_in, self._train_ws)
-        loss = _eps_train_loss(self, x_noise, labels, condp, noise.contiguous())
+        x_noise, labels, condp, _, dx_in = self._noised_inputs(u, t, noise, cond_in, self._train_ws)
+        loss = _eps_train_loss(self, x_noise, labels, condp, noise.contiguous(), dx_in)
         self.log("train_loss", loss, prog_bar=True, on_epoch=True, on_step=False, sync_dist=True)
         return loss
 
@@ -1030,11 +1055,12 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         """models/ddim.py:915-947 at one noise level (the sampler's case): one VP-preconditioned Heun step's denoiser call,
         run as a single-step mcedm_vp_heun_sample would; here through the network directly: D = x - sigma F(c_in x, c_noise,
         c_in cond)."""
-        if dx is not None:
-            raise NotImplementedError("dx_cond is not built for PlCondDdim (models/ddim.py:933-934)")
         if self.edm_steps is None:
             raise RuntimeError("call set_test_sampler_params(params) with params.type == 'edm' first (models/ddim.py:122-129)")
         net = self._net(model)
+        if dx is not None and (self._on_ddpm_unet or not net.dx_cond):
+            raise NotImplementedError("dx given to a network built without dx_cond (models/ddim.py:933-934); dx_cond is not built "
+                                      "on the DDPM U-Net")
         sig = torch.as_tensor(t).reshape(-1)
         if sig.numel() != 1:
             raise NotImplementedError("one noise level for the whole batch (what sample_edm evaluates)")
@@ -1056,15 +1082,17 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
                     F = (w + 1) * F - w * net.plan.forward_cond(pk, x_in, t_lab, x_self_cond=xsc, ws=net._ws)
                 return xt + (-c_in.new_tensor(s32).to(xt.device)) * F, F
 
-            def evaluate(c, sc):
-                # the conv_in rows scale every input channel by c_in: x, cond and x_self_cond (:921-935)
+            def evaluate(c, sc, d=None):
+                # the conv_in rows scale every input channel by c_in: x, cond, x_self_cond and dx (:921-935)
                 cp = net.stage_self_cond(None if c is None else (c_in_dev * c).contiguous(),
                                          None if sc is None else (c_in_dev * sc).contiguous(), xt) \
                     if net.self_condition else (None if c is None else (c_in_dev * c).contiguous())
-                return net.plan.forward(pk, (c_in_dev * xt).contiguous(), labels, cond=cp, ws=net._ws)
+                return net.plan.forward(pk, (c_in_dev * xt).contiguous(), labels, cond=cp, ws=net._ws,
+                                        dx=None if d is None else (c_in_dev * d).to(torch.float32).contiguous())
             c32 = None if cond is None else cond.to(torch.float32)
-            F = evaluate(c32, x_self_cond)
-            if not (w is None or abs(w) < 0.001 or cond is None):
+            F = evaluate(c32, x_self_cond, dx)
+            # :938-942: the branch is taken when cond OR dx is given; its second evaluation drops both
+            if not (w is None or abs(w) < 0.001 or (cond is None and dx is None)):
                 F = (w + 1) * F - w * evaluate(None, x_self_cond)
             D = xt + (-c_in.new_tensor(s32).to(xt.device)) * F
         return D, F
@@ -1082,6 +1110,24 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
             raise NotImplementedError("guide_dx is built for scalar gauss-normalised fields h, u")
         return self.pde_loss.guidance_desc(self.normalizer_input, self.normalizer_target, h.shape[1], h.shape[2])
 
+    def _dx_check(self):
+        """What dx_cond refuses, in training and in both samplers: what the guided path refuses."""
+        if self.pde_loss is None or not hasattr(self.pde_loss, "guidance_desc"):
+            raise NotImplementedError("dx_cond needs set_pde_loss_function('swe' | 'swe_per' | 'darcy')")
+        if self.rescaled or self.normalization == "min_max" or self.h_ch != 1 or self.u_ch != 1:
+            raise NotImplementedError("dx_cond is built for scalar gauss-normalised fields h, u")
+
+    def _dx_input(self, h):
+        """The description of the residual whose gradient at the sampler's current state is the network's dx input (None for a
+        module without dx_cond); h 'b h w c'."""
+        if not self.dx_cond:
+            return None
+        if h is None or not getattr(h, "is_cuda", False):
+            raise NotImplementedError("dx_cond (models/ddim.py:1492, 1571, 1584) needs the conditioning field h on the device: "
+                                      "sampling without it, or off the device, is not built")
+        self._dx_check()
+        return self.pde_loss.guidance_desc(self.normalizer_input, self.normalizer_target, h.shape[1], h.shape[2])
+
     def sample_edm(self, h, u_noise, sparams, return_last=True, guide_dx=False):
         """models/ddim.py:1532-1601; h, u_noise in the reference's 'b h w c' layout; returns [b, t, h, w, c] float64.  The
         schedule is rounded on the host (round_sigma, :1553, 1566); the loop runs in mcedm_vp_heun_sample_rng, whose churn kernel
@@ -1089,7 +1135,7 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         "device"``), or in mcedm_vp_heun_sample fed one torch.randn([N, B, C, H, W], float64) (``"torch"``).  Either way the call
         replays from one HIP graph.  guide_dx=True: after every denoiser call d -= 5 * dx / t_hat with dx the PDE-residual gradient
         at the denoised state (:1576-1578, 1589-1590), evaluated on the device (mcedm_[ddpm_]vp_heun_sample_guided)."""
-        guidance = self._guidance(h, guide_dx)
+        guidance, dx_input = self._guidance(h, guide_dx), self._dx_input(h)
         noise_source = self._noise_mode()
         if self.edm_steps is None:
             self.set_test_sampler_params(sparams)
@@ -1106,19 +1152,22 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
                 step_noise = None                  # nothing reads it
         kw = dict(seed=self._draw_seed()) if dev_noise else {}
         cond = h if net.cond_channels > 0 else None
+        # dx_cond: dx_in = get_dx_input(h, x) in front of every get_denoised (:1571, 1584), inside mcedm_vp_heun_sample_dxcond
+        dxkw = {} if dx_input is None else dict(dx_input=dx_input)
+        dxkey = () if dx_input is None else (_lib.desc_key(dx_input),)
         with torch.no_grad():
             packed = net.packed_weights()
             eager = lambda c, i, sn, seed=None: net.plan.vp_sample(      # noqa: E731
                 packed, vd, c, i, sn, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device),
-                guidance=guidance)
-            # the residual description of guide_dx is a host-side struct: part of the key and of the capture
+                guidance=guidance, **dxkw)
+            # the residual descriptions of guide_dx and dx_cond are host-side structs: part of the key and of the capture
             B, _, H, W = init.shape
             key = ("vp", B, H, W, bool(return_last), churn, dev_noise, packed.data_ptr(), init.device.index, N, net.cond_channels,
                    tuple(t_steps.tolist()), tuple(t_hat), tuple(c_noise), float(sparams.S_noise), float(sparams.w),
-                   None if guidance is None else _lib.desc_key(guidance))
+                   None if guidance is None else _lib.desc_key(guidance)) + dxkey
             return self._replay(key, lambda: _lib.GraphedVpSampler(net.plan, packed, vd, B, H, W, cond is not None, churn,
                                                                    return_last=return_last, ws=self._sample_ws,
-                                                                   device_noise=dev_noise, guidance=guidance),
+                                                                   device_noise=dev_noise, guidance=guidance, **dxkw),
                                 eager, cond, init, step_noise, **kw)
 
     def sample(self, *a, **k):
@@ -1136,6 +1185,7 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
         PDE-residual gradient at each step's noisy state xt (:1501-1503), evaluated on the device in front of the step's network
         passes (mcedm_[ddpm_]cond_ddim_sample_guided)."""
         guidance = self._guidance(h, guide_dx)
+        dx_input = None if h is None else self._dx_input(h)
         if h is None:
             raise NotImplementedError("sampling without the conditioning field h (models/ddim.py:1452-1531 hands cond=h to the "
                                       "network in every step) is not built")
@@ -1151,15 +1201,19 @@ class PlCondDdim(_DdpmSchedule, _SingleTask):
                      if stochastic and not dev_noise else None)
         kw = dict(seed=self._draw_seed()) if dev_noise else {}
         cond = h if net.cond_channels > 0 else None
+        # dx_cond: dx_in = get_dx_input(h, xt) at every step's noisy state (:1492), inside mcedm_cond_ddim_sample_dxcond
+        dxkw = {} if dx_input is None else dict(dx_input=dx_input)
+        dxkey = () if dx_input is None else (_lib.desc_key(dx_input),)
         with torch.no_grad():
             packed = net.packed_weights()
             eager = lambda c, i, en, seed=None: net.plan.cond_ddim_sample(      # noqa: E731
                 packed, dd, c, i, en, return_last=return_last, ws=self._sample_ws, rng_seed=self._seed_tensor(seed, i.device),
-                guidance=guidance)
+                guidance=guidance, **dxkw)
             # the evaluation loops repeat the call: it replays from one HIP graph, like sample_edm of the sibling modules
             B, _, H, W = init.shape
             key = ("ddim", B, H, W, bool(return_last), stochastic, dev_noise, packed.data_ptr(), init.device.index, _table_key(ae),
-                   _lib.desc_key(dd, skip=("alphas_cumprod_ext",)), None if guidance is None else _lib.desc_key(guidance))
+                   _lib.desc_key(dd, skip=("alphas_cumprod_ext",)), None if guidance is None else _lib.desc_key(guidance)) + dxkey
             return self._replay(key, lambda: _lib.GraphedCondDdim(net.plan, packed, dd, B, H, W, stochastic, return_last=return_last,
-                                                                  ws=self._sample_ws, device_noise=dev_noise, guidance=guidance),
+                                                                  ws=self._sample_ws, device_noise=dev_noise, guidance=guidance,
+                                                                  **dxkw),
                                 eager, cond, init, eta_noise, **kw)

@@ -50,6 +50,9 @@ GUIDED_ENTRIES = {
     "mcedm_vp_heun_sample": "mcedm_vp_heun_sample_guided", "mcedm_ddpm_vp_heun_sample": "mcedm_ddpm_vp_heun_sample_guided",
     "mcedm_cond_ddim_sample": "mcedm_cond_ddim_sample_guided", "mcedm_ddpm_cond_ddim_sample": "mcedm_ddpm_cond_ddim_sample_guided",
 }
+# The dx_cond entries of PlCondDdim's samplers on the ADM U-Net: the guided signature with the description of the dx residual
+# (the network's dx input at the current state) in front of the guidance description, which may be NULL; no "_rng" twin either.
+DXCOND_ENTRIES = {"mcedm_vp_heun_sample": "mcedm_vp_heun_sample_dxcond", "mcedm_cond_ddim_sample": "mcedm_cond_ddim_sample_dxcond"}
 
 _lib = None
 
@@ -193,14 +196,17 @@ class _PlanBase:
     # ---- the samplers ----------------------------------------------------------------------
     def _sample_call(self, who: str, stem: str, packed, head: Sequence, noise: Sequence[tuple], rng_seed, out, shapes: List[tuple],
                      dtype, return_last: bool, ws: Optional["Workspace"], nbytes: int, dims: tuple, device,
-                     guidance: Optional["GuidanceDesc"] = None):
+                     guidance: Optional["GuidanceDesc"] = None, dx_input: Optional["GuidanceDesc"] = None):
         """The call every sampler method makes: ``stem(plan, packed, *head, <draws>, <outputs>, return_last, workspace, bytes,
         *dims, stream)``.  noise: (name, tensor or None, dtype, shape) of each materialised draw ``stem`` takes; with rng_seed
         (device-side draws) ``stem + "_rng"`` runs instead, the one seed pointer in their place.  shapes: of the one or two
         ``dtype`` outputs, allocated here or checked against the caller's ``out`` (a graphed call's static tensors); returns
         the tensor, or the pair.  guidance: ``GUIDED_ENTRIES[stem]`` runs instead, the description behind the first entry of
-        ``head`` (the sampler's) and the draws AND the seed pointer in its one signature.  Every check runs before anything is
-        enqueued."""
+        ``head`` (the sampler's) and the draws AND the seed pointer in its one signature.  dx_input (dx_cond plans, with or
+        without guidance): ``DXCOND_ENTRIES[stem]`` runs, both descriptions behind the sampler's (guidance NULL when absent).  Every
+        check runs before anything is enqueued."""
+        if dx_input is not None and stem not in DXCOND_ENTRIES:
+            raise RuntimeError(f"{who}: dx_input (dx_cond) is not built for {stem}")
         buf = (ws or Workspace()).get(nbytes, device)
         single = len(shapes) == 1
         if out is None:
@@ -222,8 +228,10 @@ class _PlanBase:
             stem, draws = stem + "_rng", [_seed_ptr(rng_seed, device, who)]
         else:
             draws = [_ptr(t, dt) for _, t, dt, _ in noise]
-        if guidance is not None:
-            stem, head = GUIDED_ENTRIES[stem[:-len("_rng")] if rng_seed is not None else stem], (head[0], C.byref(guidance)) + tuple(head[1:])
+        if guidance is not None or dx_input is not None:
+            base = stem[:-len("_rng")] if rng_seed is not None else stem
+            descs = (C.byref(guidance),) if dx_input is None else (C.byref(dx_input), None if guidance is None else C.byref(guidance))
+            stem, head = (GUIDED_ENTRIES if dx_input is None else DXCOND_ENTRIES)[base], (head[0],) + descs + tuple(head[1:])
             draws = [_ptr(t, dt) for _, t, dt, _ in noise] + [_seed_ptr(rng_seed, device, who) if rng_seed is not None else None]
         check(getattr(self._lib, stem)(self._h, packed.data_ptr(), *head, *draws, *[_ptr(o, dtype) for o in outs], int(return_last),
                                        buf.data_ptr(), buf.numel(), *dims, _stream()), stem[len("mcedm_"):])
@@ -233,27 +241,32 @@ class _PlanBase:
     # queries, the trailing size arguments of its entries (_dims) and its input checks with the state's (H, W) (_state_hw).
     def vp_sample(self, packed, vd: "VpSamplerDesc", cond, init_noise, step_noise=None, return_last: bool = True,
                   ws: Optional["Workspace"] = None, rng_seed: Optional[torch.Tensor] = None,
-                  out: Optional[torch.Tensor] = None, guidance: Optional["GuidanceDesc"] = None) -> torch.Tensor:
+                  out: Optional[torch.Tensor] = None, guidance: Optional["GuidanceDesc"] = None,
+                  dx_input: Optional["GuidanceDesc"] = None) -> torch.Tensor:
         """mcedm_[ddpm_]vp_heun_sample (rng_seed None) / its _rng form; returns [B, 1 or N+1, H, W, in] float64 (``out``, when
         given: a graphed call's static tensor).  guidance: the PDE residual whose gradient at the denoised state corrects the
-        slope (guide_dx): mcedm_[ddpm_]vp_heun_sample_guided, with the guided workspace."""
+        slope (guide_dx): mcedm_[ddpm_]vp_heun_sample_guided, with the guided workspace.  dx_input (dx_cond plans of the ADM
+        U-Net): the residual whose gradient at the current state, scaled by c_in, is the network's dx input:
+        mcedm_vp_heun_sample_dxcond."""
         H, W = self._state_hw(init_noise, cond, "vp_sample")
         B, N = init_noise.shape[0], vd.timesteps
         return self._sample_call("vp_sample", f"mcedm_{self._WHAT}vp_heun_sample", packed,
                                  (C.byref(vd), _ptr(cond), _ptr(init_noise)),
                                  [("step_noise", step_noise, torch.float64, (N,) + tuple(init_noise.shape))], rng_seed, out,
                                  [(B, 1 if return_last else N + 1, H, W, self.in_channels)], torch.float64, return_last, ws,
-                                 self.vp_sampler_workspace_bytes(B, H, W, guided=guidance is not None), self._dims(B, H, W),
-                                 init_noise.device, guidance=guidance)
+                                 self.vp_sampler_workspace_bytes(B, H, W, guided=guidance is not None, **self._dx_kw(dx_input)),
+                                 self._dims(B, H, W), init_noise.device, guidance=guidance, dx_input=dx_input)
 
     def cond_ddim_sample(self, packed, dd: "CondDdimDesc", cond, init_noise, eta_noise=None, return_last: bool = True,
                          ws: Optional["Workspace"] = None, out=None, rng_seed: Optional[torch.Tensor] = None,
-                         guidance: Optional["GuidanceDesc"] = None):
+                         guidance: Optional["GuidanceDesc"] = None, dx_input: Optional["GuidanceDesc"] = None):
         """mcedm_[ddpm_]cond_ddim_sample (PlCondDdim.sample on the device) -> (xs, x0_preds), both fp32 'b t h w c': S + 1 and S
         slots, or one each with return_last.  out: the pair to write into (a graphed call's static tensors).  rng_seed (int64 [1]
         on the device): the uniform draws of the eta != 0 steps are generated inside the step kernel (the _rng form, step k =
         draw k of uniform_fill) instead of being read from eta_noise [S, B, C, H, W].  guidance: the PDE residual whose gradient at
-        each step's noisy state corrects et (guide_dx): mcedm_[ddpm_]cond_ddim_sample_guided, with the guided workspace."""
+        each step's noisy state corrects et (guide_dx): mcedm_[ddpm_]cond_ddim_sample_guided, with the guided workspace.  dx_input
+        (dx_cond plans of the ADM U-Net): the residual whose gradient at each step's noisy state is the network's dx input:
+        mcedm_cond_ddim_sample_dxcond."""
         H, W = self._state_hw(init_noise, cond, "cond_ddim_sample")
         B, Cc = init_noise.shape[0], self.in_channels
         S = len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
@@ -261,8 +274,14 @@ class _PlanBase:
                                  (C.byref(dd), _ptr(cond), _ptr(init_noise)),
                                  [("eta_noise", eta_noise, torch.float32, (S,) + tuple(init_noise.shape))], rng_seed, out,
                                  [(B, 1 if return_last else S + 1, H, W, Cc), (B, 1 if return_last else S, H, W, Cc)],
-                                 torch.float32, return_last, ws, self.cond_ddim_workspace_bytes(B, H, W, guided=guidance is not None),
-                                 self._dims(B, H, W), init_noise.device, guidance=guidance)
+                                 torch.float32, return_last, ws,
+                                 self.cond_ddim_workspace_bytes(B, H, W, guided=guidance is not None, **self._dx_kw(dx_input)),
+                                 self._dims(B, H, W), init_noise.device, guidance=guidance, dx_input=dx_input)
+
+    @staticmethod
+    def _dx_kw(dx_input) -> dict:
+        """The size queries' ``dxcond=True`` for a dx_cond call; nothing otherwise (the DDPM plan's queries have no such form)."""
+        return {} if dx_input is None else {"dxcond": True}
 
 
 class Plan(_PlanBase):
@@ -378,24 +397,33 @@ class Plan(_PlanBase):
 
     def unet_backward(self, packed, params: Dict[str, torch.Tensor], x, noise_labels, cond, dF, grads: Sequence[torch.Tensor],
                       ws: Workspace, bucket_first: Optional[Sequence[int]] = None,
-                      bucket_events: Optional[Sequence[torch.cuda.Event]] = None) -> None:
+                      bucket_events: Optional[Sequence[torch.cuda.Event]] = None, dx=None) -> None:
         """Backward of forward(..., training=True) (x_scale None) on the SAME workspace, from dF = dLoss/d out:
-        grads[i] <- dLoss/dparam_i (overwritten); bucket events as in denoise_backward."""
+        grads[i] <- dLoss/dparam_i (overwritten); bucket events as in denoise_backward.  dx: that forward's (dx_cond plans, which
+        go through mcedm_unet_backward_dx whether or not this batch had a dx)."""
+        self._check_dx(x, dx)
         B, _, H, W = x.shape
         buf = ws.get(self.workspace_bytes(B, H, W, True), x.device)
         parr = (C.c_void_p * len(self.param_names))(*[_ptr(params[n].detach()) for n in self.param_names])
         garr = (C.c_void_p * len(self.param_names))(*[_ptr(g) for g in grads])
         nb, firsts, evs = _bucket_args(bucket_first, bucket_events, "unet_backward")
+        if self.dx_mode != DX_NONE:
+            check(self._lib.mcedm_unet_backward_dx(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(dx), _ptr(cond), None,
+                                                   _ptr(noise_labels), noise_labels.numel(), _ptr(dF), garr, buf.data_ptr(),
+                                                   buf.numel(), B, H, W, nb, firsts, evs, _stream()), "unet_backward_dx")
+            return
         check(self._lib.mcedm_unet_backward_bucketed(self._h, packed.data_ptr(), parr, _ptr(x), _ptr(cond), None,
                                                      _ptr(noise_labels), noise_labels.numel(), _ptr(dF), garr, buf.data_ptr(),
                                                      buf.numel(), B, H, W, nb, firsts, evs, _stream()), "unet_backward")
 
-    def vp_sampler_workspace_bytes(self, B: int, H: int, W: int, guided: bool = False) -> int:
-        what = "vp_guided_workspace_bytes" if guided else "vp_sampler_workspace_bytes"
+    def vp_sampler_workspace_bytes(self, B: int, H: int, W: int, guided: bool = False, dxcond: bool = False) -> int:
+        """dxcond: the size of mcedm_vp_heun_sample_dxcond, with or without guidance on top."""
+        what = "vp_dxcond_workspace_bytes" if dxcond else "vp_guided_workspace_bytes" if guided else "vp_sampler_workspace_bytes"
         return self._bytes("mcedm_" + what, what, B, H, W)
 
-    def cond_ddim_workspace_bytes(self, B: int, H: int, W: int, guided: bool = False) -> int:
-        what = "cond_ddim_guided_workspace_bytes" if guided else "cond_ddim_workspace_bytes"
+    def cond_ddim_workspace_bytes(self, B: int, H: int, W: int, guided: bool = False, dxcond: bool = False) -> int:
+        what = ("cond_ddim_dxcond_workspace_bytes" if dxcond else
+                "cond_ddim_guided_workspace_bytes" if guided else "cond_ddim_workspace_bytes")
         return self._bytes("mcedm_" + what, what, B, H, W)
 
     def _dims(self, B: int, H: int, W: int) -> tuple:
@@ -921,10 +949,10 @@ class GraphedCondDdim(_GraphedCall):
 
     def __init__(self, plan: "Plan", packed: torch.Tensor, dd: CondDdimDesc, B: int, H: int, W: int, stochastic: bool,
                  return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False,
-                 guidance: Optional["GuidanceDesc"] = None):
+                 guidance: Optional["GuidanceDesc"] = None, dx_input: Optional["GuidanceDesc"] = None):
         dev = packed.device
         self.plan, self.packed, self.dd, self.return_last = plan, packed, dd, return_last
-        self.guidance = guidance      # host-side description (guide_dx), baked into the captured kernel arguments
+        self.guidance, self.dx_input = guidance, dx_input      # host-side descriptions (guide_dx, dx_cond), baked into the captured kernel arguments
         Cc, S = plan.in_channels, len(ddim_timesteps(dd.num_diffusion_timesteps, dd.timesteps, dd.skip_type))
         self.cond = torch.zeros((B, dd.cond_channels, H, W), device=dev) if dd.cond_channels > 0 else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
@@ -932,11 +960,11 @@ class GraphedCondDdim(_GraphedCall):
         self.out = (torch.empty((B, 1 if return_last else S + 1, H, W, Cc), device=dev),
                     torch.empty((B, 1 if return_last else S, H, W, Cc), device=dev))
         self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "eta_noise": self.eta_noise}, ws,
-                           plan.cond_ddim_workspace_bytes(B, H, W, guided=guidance is not None))
+                           plan.cond_ddim_workspace_bytes(B, H, W, guided=guidance is not None, **plan._dx_kw(dx_input)))
 
     def _run(self):
         self.plan.cond_ddim_sample(self.packed, self.dd, self.cond, self.init, self.eta_noise, self.return_last, self.ws, out=self.out,
-                                   rng_seed=self.seed, guidance=self.guidance)
+                                   rng_seed=self.seed, guidance=self.guidance, dx_input=self.dx_input)
 
     def __call__(self, cond, init_noise, eta_noise=None, seed=None):
         return self._replay(seed, cond, init_noise, eta_noise)
@@ -978,21 +1006,21 @@ class GraphedVpSampler(_GraphedCall):
 
     def __init__(self, plan: "Plan", packed: torch.Tensor, vd: VpSamplerDesc, B: int, H: int, W: int, has_cond: bool, churn: bool,
                  return_last: bool = True, ws: Optional[Workspace] = None, device_noise: bool = False,
-                 guidance: Optional["GuidanceDesc"] = None):
+                 guidance: Optional["GuidanceDesc"] = None, dx_input: Optional["GuidanceDesc"] = None):
         dev = packed.device
         self.plan, self.packed, self.vd, self.return_last = plan, packed, vd, return_last
-        self.guidance = guidance      # host-side description (guide_dx), baked into the captured kernel arguments
+        self.guidance, self.dx_input = guidance, dx_input      # host-side descriptions (guide_dx, dx_cond), baked into the captured kernel arguments
         Cc = plan.in_channels
         self.cond = torch.zeros((B, vd.cond_channels, H, W), device=dev) if has_cond else None
         self.init = torch.zeros((B, Cc, H, W), device=dev)
         self.seed, self.step_noise = self._draws(dev, churn, device_noise, (vd.timesteps, B, Cc, H, W), torch.float64)
         self.out = torch.empty((B, 1 if return_last else vd.timesteps + 1, H, W, Cc), dtype=torch.float64, device=dev)
         self._capture_call(dev, {"cond": self.cond, "init_noise": self.init, "step_noise": self.step_noise}, ws,
-                           plan.vp_sampler_workspace_bytes(B, H, W, guided=guidance is not None))
+                           plan.vp_sampler_workspace_bytes(B, H, W, guided=guidance is not None, **plan._dx_kw(dx_input)))
 
     def _run(self):
         self.plan.vp_sample(self.packed, self.vd, self.cond, self.init, self.step_noise, self.return_last, self.ws,
-                            rng_seed=self.seed, out=self.out, guidance=self.guidance)
+                            rng_seed=self.seed, out=self.out, guidance=self.guidance, dx_input=self.dx_input)
 
     def __call__(self, cond, init_noise, step_noise=None, seed=None) -> torch.Tensor:
         return self._replay(seed, cond, init_noise, step_noise)
