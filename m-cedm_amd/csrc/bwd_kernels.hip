@@ -657,6 +657,20 @@ int launch_small_gemm(const float* A, const float* Bm, float* Cm, int M, int N, 
 //   (1) lse_q, delta_q          (2) dq (query on the lanes)          (3) dk, dv (key on the lanes)
 // =========================================================================================================
 #define MCEDM_KEY_OF(r, h) ((r & 3) + 8 * (r >> 2) + 4 * (h))
+constexpr float ATT_LOG2E = 1.4426950408889634f;
+
+// The scores are formed the way the FORWARD kernel of the same T forms them (norm_emb_attn.hip launch_attention): natural units,
+// q / 8, expf below 128 tokens (attention_kernel); units of log 2, q log2(e) / 8, v_exp_f32 from 128 tokens on
+// (attention_split_kernel, attention_lds_kernel) -- the four-wave kernels here and the LDS kernels below.  delta = sum_c da a
+// carries the forward's probabilities, and dS = P o (dP - delta) cancels only as far as the P recomputed here equals them: at
+// scores of +-150 one rounding of q log2(e) / 8 moves a probability by 1e-5, which through |dP - delta| of 100 and more was
+// 2x the bar (rtol 1e-4, atol 1e-5 max) on dq where the forward passed it (tests/test_hip_attn_bwd.py, the x6 inputs).
+template <int KW> struct AttnBwdUnits {
+  static constexpr bool base2 = KW == 4;
+  static constexpr float qscale = base2 ? 0.125f * ATT_LOG2E : 0.125f;
+  static __device__ __forceinline__ float exp(float x) { return base2 ? __builtin_amdgcn_exp2f(x) : expf(x); }
+  static __device__ __forceinline__ float log(float x) { return base2 ? __builtin_amdgcn_logf(x) : logf(x); }      // v_log_f32 is log2
+};
 
 // KW waves per workgroup take the key tiles w, w + KW, ... of the SAME 32-query tile and their (running max, sum) pairs meet in
 // LDS, merged by wave 0 in wave order (round 5: one wave per tile was 512 waves per launch at T = 256, B = 32, two heads -- half a
@@ -671,12 +685,13 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_stats_kernel(const float* __
   const float* Q = qkv + (bh * 3 + 0) * 64 * (size_t)T;
   const float* K = qkv + (bh * 3 + 1) * 64 * (size_t)T;
   const int q = q0 + l31, qc = q < T ? q : T - 1;
+  using U = AttnBwdUnits<KW>;
   float qreg[32];
   float delta = 0.f;
 #pragma unroll
   for (int s = 0; s < 32; ++s) {
     const size_t o = (size_t)(2 * s + h) * T + qc;
-    qreg[s] = Q[o] * 0.125f;
+    qreg[s] = Q[o] * U::qscale;
     if (wave == 0) delta += da[bh * 64 * (size_t)T + o] * a[bh * 64 * (size_t)T + o];
   }
   delta += __shfl_xor(delta, 32);
@@ -699,9 +714,9 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_stats_kernel(const float* __
     const float mn = fmaxf(m, mx);
     float rs = 0.f;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) rs += expf(sc[r] - mn);
+    for (int r = 0; r < 16; ++r) rs += U::exp(sc[r] - mn);
     rs += __shfl_xor(rs, 32);
-    l = l * expf(m - mn) + rs;
+    l = l * U::exp(m - mn) + rs;
     m = mn;
   }
   if (KW > 1) {
@@ -713,12 +728,12 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_stats_kernel(const float* __
     for (int w = 0; w < KW; ++w) {                          // wave order: a fixed order (a wave without key tiles holds (-inf, 0))
       const float mw = ml[w][0][l31], lw = ml[w][1][l31];
       const float mn = fmaxf(m, mw);
-      if (mn > -INFINITY) l = l * expf(m - mn) + lw * expf(mw - mn);
+      if (mn > -INFINITY) l = l * U::exp(m - mn) + lw * U::exp(mw - mn);
       m = mn;
     }
   }
   if (q < T && h == 0) {
-    lse[(bh * T + q) * 2] = m + logf(l);
+    lse[(bh * T + q) * 2] = m + U::log(l);      // in the units of the scores
     lse[(bh * T + q) * 2 + 1] = delta;
   }
 }
@@ -757,10 +772,11 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const float* V = qkv + (bh * 3 + 2) * 64 * (size_t)T;
   const float* dA = da + bh * 64 * (size_t)T;
   const int q = q0 + l31, qc = q < T ? q : T - 1;
+  using U = AttnBwdUnits<KW>;
   float qreg[32], dareg[32];
 #pragma unroll
   for (int s = 0; s < 32; ++s) {
-    qreg[s] = Q[(size_t)(2 * s + h) * T + qc] * 0.125f;
+    qreg[s] = Q[(size_t)(2 * s + h) * T + qc] * U::qscale;
     dareg[s] = dA[(size_t)(2 * s + h) * T + qc];
   }
   const float L = lse[(bh * T + qc) * 2], delta = lse[(bh * T + qc) * 2 + 1];
@@ -786,7 +802,7 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const bool ok = k0 + MCEDM_KEY_OF(r, h) < T;
-      const float pv = ok ? expf(sc[r] - L) : 0.f;
+      const float pv = ok ? U::exp(sc[r] - L) : 0.f;
       ds[r] = pv * (dp[r] - delta);
     }
     // dq[c][q] += sum_key K[c][key] * dS[key][q]
@@ -827,6 +843,7 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_dkv_kernel(const float* __re
   const float* V = qkv + (bh * 3 + 2) * 64 * (size_t)T;
   const float* dA = da + bh * 64 * (size_t)T;
   const int key = k0 + l31, kc = key < T ? key : T - 1;
+  using U = AttnBwdUnits<KW>;
   float kreg[32], vreg[32];
 #pragma unroll
   for (int s = 0; s < 32; ++s) {
@@ -846,7 +863,7 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_dkv_kernel(const float* __re
     for (int r = 0; r < 16; ++r) { sc[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
     for (int st = 0; st < 32; ++st) {
-      sc = __builtin_amdgcn_mfma_f32_32x32x2f32(Q[(size_t)(2 * st + h) * T + qc] * 0.125f, kreg[st], sc, 0, 0, 0);
+      sc = __builtin_amdgcn_mfma_f32_32x32x2f32(Q[(size_t)(2 * st + h) * T + qc] * U::qscale, kreg[st], sc, 0, 0, 0);
       dp = __builtin_amdgcn_mfma_f32_32x32x2f32(dA[(size_t)(2 * st + h) * T + qc], vreg[st], dp, 0, 0, 0);
     }
     float pr[16], ds[16];
@@ -855,7 +872,7 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_dkv_kernel(const float* __re
       const int qi = q0 + MCEDM_KEY_OF(r, h);
       const int qj = qi < T ? qi : T - 1;
       const float L = lse[(bh * T + qj) * 2], delta = lse[(bh * T + qj) * 2 + 1];
-      pr[r] = qi < T ? expf(sc[r] - L) : 0.f;
+      pr[r] = qi < T ? U::exp(sc[r] - L) : 0.f;
       ds[r] = pr[r] * (dp[r] - delta);
     }
 #pragma unroll
@@ -901,7 +918,6 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_dkv_kernel(const float* __re
 // MFMA operands are LDS dwords.  Same sums in the same order per output element as the kernels above except that a wave now
 // walks ALL chunks in ascending order instead of every fourth (no cross-wave merge): deterministic, batch independent.
 constexpr int ATP = 65;                    // pitch of the transposed chunk images
-constexpr float ATT_LOG2E = 1.4426950408889634f;
 
 // The dq kernel also produces the softmax statistics the dk / dv kernel needs (no attn_bwd_stats_kernel launch on this path: its
 // S = K^T Q product is the one computed here anyway; 164 of 496 us at T = 1024): the scores are normalised ONLINE -- running
@@ -1106,10 +1122,12 @@ int launch_attention_bwd(const float* qkv, const float* a, const float* da, floa
   MCEDM_REQUIRE(qkv && a && da && dqkv && lse, "attention_bwd: null pointer");
   MCEDM_REQUIRE(B > 0 && heads > 0 && T > 0 && (long long)B * heads <= 65535, "attention_bwd: bad shape");
   const dim3 grid(ceil_div(T, 32), B * heads);
-  ProfScope ps("attention_bwd", 10.0 * B * heads * (double)T * T * 64, 4.0 * 8 * B * heads * 64.0 * T, s);
   // split factor: a function of T only (never of the batch size)
   static const int lds_env = env_int("MCEDM_ATTN_BWD_LDS", 1);   // 0: the direct-from-global kernels at every T (A/B runs)
   const bool lds_path = lds_env && T % 128 == 0 && ((reinterpret_cast<size_t>(qkv) | reinterpret_cast<size_t>(da)) & 15) == 0;
+  // the profiler row names the branch taken (tests/_attn_bwd.py branch() restates the choice)
+  const char* row = lds_path ? "attention_bwd_lds" : T >= 128 ? "attention_bwd_direct<4>" : T >= 64 ? "attention_bwd_direct<2>" : "attention_bwd_direct<1>";
+  ProfScope ps(row, 10.0 * B * heads * (double)T * T * 64, 4.0 * 8 * B * heads * 64.0 * T, s);
   if (!lds_path) {
     if (T >= 128) hipLaunchKernelGGL(attn_bwd_stats_kernel<4>, grid, dim3(256), 0, s, qkv, a, da, lse, T);
     else if (T >= 64) hipLaunchKernelGGL(attn_bwd_stats_kernel<2>, grid, dim3(128), 0, s, qkv, a, da, lse, T);

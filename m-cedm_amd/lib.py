@@ -1613,10 +1613,13 @@ def op_gn_bwd(dact, xa, xb, coef, stats, gamma, beta, film=None, film_batch=0, f
     return dxa, dxb, dg, dbt, dfilm
 
 
-def op_attention_bwd(qkv, a, da, heads):
+def op_attention_bwd(qkv, a, da, heads, out=None):
+    """-> dqkv; out: a caller-owned contiguous tensor of qkv's shape, dtype and device to write it into (every element is written)."""
     lib = _bind_ops()
     B, C3, H, W = qkv.shape
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.empty_like(qkv) if out is None else out
+    if dqkv.shape != qkv.shape or dqkv.device != qkv.device:
+        raise ValueError("op_attention_bwd: out must have qkv's shape and device")
     lse = torch.empty(B * heads * H * W * 2, dtype=torch.float32, device=qkv.device)
     check(lib.mcedm_op_attention_bwd(_ptr(qkv), _ptr(a), _ptr(da), _ptr(dqkv), _ptr(lse), B, heads, H * W, _stream()),
           "op_attention_bwd")

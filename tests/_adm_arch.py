@@ -55,6 +55,10 @@ ARCHS = {
     "c192": (_cfg(32, 192, (1,), attn=(32,)), 2, 32, 32),
     # attention at two levels; 256 -> 128 un-resampled skip projections that the folded Winograd epilogue takes; odd batch
     "c128a": (_cfg(32, 128, (1, 1), attn=(32, 16)), 3, 32, 32),
+    # attention at token counts that are no multiple of 128 nor of 32: T = 400 (one head, three blocks) and T = 100 (two heads,
+    # four blocks) -- in training the direct-from-global backward kernels with four and with two waves per tile (tests/_attn_bwd.py),
+    # in inference a ragged attention_split_kernel<4> and attention_kernel; 20 x 20 and 10 x 10: no Winograd form anywhere
+    "attn_rag": (_cfg(20, 64, (1, 2), attn=(20, 10)), 2, 20, 20),
 }
 # out_ch != in_channels: the EDM skip term c_skip x has no meaning; this row runs through forward / unet_backward under sum(w F^2)
 PLAIN = ("ch24",)
@@ -72,7 +76,7 @@ PLAIN = ("ch24",)
 #          decoder blocks at 32 x 32 alone (rect, wide3: Cout 64; c192: Cout 192 and Cin 384).
 #   table  any full-pass gn_coef_kernel launch.  gn_for_conv / launch_gn_coef_from_sums fall back to it where gn_sums_usable fails:
 #          the ADM executor's records hold 4 channels, so a GroupNorm whose groups are not whole records -- 5 channels per group at
-#          160, 6 at 192 -- has none.  192 = 128 + 64 (rect, ragged, deep, nrb3) or a level width (wide3, c192); 160 = 80 + 80
+#          160, 6 at 192 -- has none.  192 = 128 + 64 (rect, ragged, deep, nrb3, attn_rag) or a level width (wide3, c192); 160 = 80 + 80
 #          (narrow).  one (64, 128), ch24 (24, 48, 72, 96: 4 per group) and c128a (128, 256) never need it.
 PATHS = {
     "one": dict(wino=False, split=False, fold=False, table=False),
@@ -85,6 +89,7 @@ PATHS = {
     "nrb3": dict(wino=False, split=True, fold=False, table=True),
     "c192": dict(wino=True, split=False, fold=False, table=True),
     "c128a": dict(wino=True, split=True, fold=True, table=False),
+    "attn_rag": dict(wino=False, split=False, fold=False, table=True),
 }
 # attention: launch_attention (attention_kernel) once per attention block, except where run_block takes
 # attn_block_fused_applicable (C == 64, one head, 8 x 8, inference: `one`): then attn_block64_kernel, and attention_kernel 0

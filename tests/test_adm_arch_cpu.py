@@ -11,6 +11,7 @@ import torch
 import mcedm_amd  # noqa: F401
 from mcedm_amd import lib as L
 from tests import _adm_arch as A
+from tests import _attn_bwd as AB
 
 
 @pytest.fixture
@@ -101,14 +102,18 @@ def test_the_table_reaches_what_it_claims():
     assert cpg["deep"] == {32: 4, 64: 4, 96: 4, 128: 4, 192: 6, 256: 8}
     assert cpg["nrb3"] == {64: 4, 128: 4, 192: 6, 256: 8}
     assert cpg["c192"] == {192: 6, 384: 12}
+    assert cpg["attn_rag"] == {64: 4, 128: 4, 192: 6, 256: 8}
     # the ADM executor's statistics records hold 4 channels: a row needs the full-pass table exactly where some group is not whole records
     assert {t: any(v % 4 for v in cpg[t].values()) for t in A.ARCHS} == {t: A.PATHS[t]["table"] for t in A.ARCHS}
     # attention blocks and their token counts
     # (narrow and ch24 have none: their deepest level is narrower than one head, and dec.*_in0 then has no attention, adm_blocks.py:135)
     tokens = {t: sorted(A.attention_tokens(t)) for t in A.ARCHS}
     assert tokens == dict(one=[64] * 4, rect=[384], ragged=[15] * 4, narrow=[], ch24=[], wide3=[256] * 4, deep=[4] + [16] * 5,
-                          nrb3=[128] + [512] * 7, c192=[1024] * 4, c128a=[256] * 4 + [1024] * 3)
-    assert {4, 15, 16, 128, 256, 512, 1024} <= {n for v in tokens.values() for n in v}
+                          nrb3=[128] + [512] * 7, c192=[1024] * 4, c128a=[256] * 4 + [1024] * 3, attn_rag=[100] * 4 + [400] * 3)
+    assert {4, 15, 16, 100, 128, 256, 400, 512, 1024} <= {n for v in tokens.values() for n in v}
+    # every branch of the attention backward (tests/_attn_bwd.py) in some training step
+    assert {AB.branch(n) for v in tokens.values() for n in v} == {"direct<1>", "direct<2>", "direct<4>", "lds"}
+    assert sorted(AB.branch(n) for n in tokens["attn_rag"]) == ["direct<2>"] * 4 + ["direct<4>"] * 3
     for t in A.ARCHS:
         assert len(tokens[t]) == sum(n.endswith(".qkv.weight") for n, _ in A.orc.param_shapes(A.cfg_of(t)))
     # a level on whole 8 x 16 tiles with at least 1024 pixels and a width the large Winograd kernel serves (Cout % 64 == 0) ...
@@ -123,8 +128,9 @@ def test_the_table_reaches_what_it_claims():
     assert {t for t, v in small.items() if v} == {"wide3", "deep", "nrb3", "c128a"} == {t for t in A.ARCHS if A.PATHS[t]["split"]}
     assert small["nrb3"] == [(16, 32, 128), (8, 16, 64)]
     # rows with neither
-    assert {t for t in A.ARCHS if not big[t] and not small[t]} == {"one", "ragged", "narrow", "ch24"}
+    assert {t for t in A.ARCHS if not big[t] and not small[t]} == {"one", "ragged", "narrow", "ch24", "attn_rag"}
     assert A.level_sizes("rect")[1] == (16, 24, 128) and A.level_sizes("ragged") == [(12, 20, 64), (6, 10, 64), (3, 5, 128)]
+    assert A.level_sizes("attn_rag") == [(20, 20, 64), (10, 10, 128)]
     # parameter counts, the skip stack (num_res_blocks + 1 decoder blocks per level), the channel counts of the plain row
     assert len(A.orc.param_shapes(A.cfg_of("deep"))) == 432
     spec = A.orc.build_spec(A.cfg_of("deep"))

@@ -20,9 +20,14 @@ gradient against the reference's run is the worst of the three stored tensors, a
     nrb3    0.0440       0.0003  0.2782 dec.8x8_in0.norm2.weight          0.1046 | 0.0969   0.0000 | 0.0003  0.3297 | 0.9793 dec.8x8_in0.norm2.weight
     c192    0.0421       0.0001  0.0702 enc.32x32_conv.weight             0.0902 | 0.0736   0.0000 | 0.0001  0.0238 | 0.0881 enc.32x32_conv.weight
     c128a   0.0560       0.0004  0.1255 dec.16x16_in0.norm0.weight        0.1216 | 0.1035   0.0000 | 0.0004  0.0718 | 0.2422 dec.16x16_in1.conv0.weight
+    attn_rag 0.0578      0.0005  0.2145 enc.20x20_block0.conv1.weight    0.1638 | 0.1919   0.0000 | 0.0005  0.2449 | 0.3641 enc.10x10_block0.conv1.weight
+
+In the training step every row's attention_bwd_* profiler rows are those tests/_attn_bwd.py branch() predicts from its token counts:
+the LDS kernels at 128, 256, 384, 512 and 1024 tokens, direct<1> at 4, 15, 16, direct<2> at 64 and (attn_rag) 100, direct<4> at 400.
 
 With a kernel family switched off the forward stays below 0.22 | 0.19 (rect, conv_wino = 0) and the gradients where they were.
 """
+import collections
 import functools
 import math
 
@@ -30,6 +35,7 @@ import pytest
 import torch
 
 from tests import _adm_arch as A
+from tests import _attn_bwd as AB
 
 pytestmark = pytest.mark.gpu
 
@@ -166,7 +172,8 @@ def test_inference_golden_and_fp64(golden, tag):
 @pytest.mark.parametrize("tag", list(A.ARCHS))
 def test_training_step_golden_and_fp64(golden, tag):
     """forward(training) -> loss -> backward; gradients pre-filled with NaN; a second step gives the same bits.  What the backward
-    is expected to launch: one attention_kernel per attention block (the fused 8 x 8 block is inference only), no split Winograd
+    is expected to launch: one attention_kernel per attention block (the fused 8 x 8 block is inference only), one attention_bwd_*
+    row per block on the branch tests/_attn_bwd.py branch() predicts from its token count, no split Winograd
     kernel (AdmNet::conv: training carries no Winograd table below 32 x 32), the thin weight-gradient kernels of the plain row."""
     g = golden("adm_arch.npz")
     L, plan, params, packed = net(tag)
@@ -175,6 +182,11 @@ def test_training_step_golden_and_fp64(golden, tag):
     loss2, grads2 = training_step(tag, L, plan, params, packed)
     assert torch.equal(loss, loss2) and all(torch.equal(grads[n], grads2[n]) for n in grads)
     assert count(rows, "attn_block64") == 0 and rows.get("attention_kernel", 0) == len(A.attention_tokens(tag)), rows
+    # the attention backward, one launch per block on the branch its token count selects (the workspace is 16-byte aligned)
+    want = collections.Counter("attention_bwd_" + AB.branch(T) for T in A.attention_tokens(tag))
+    assert {k: v for k, v in rows.items() if k.startswith("attention_bwd")} == dict(want), (rows, want)
+    if tag == "attn_rag":
+        assert want == {"attention_bwd_direct<4>": 3, "attention_bwd_direct<2>": 4}
     assert count(rows, "conv_wino_kernel<WinoSplitCfg") == 0 and count(rows, "conv_wino_kernel<WinoSkipCfg") == 0, sorted(rows)
     if tag in A.THIN_WGRADS:
         assert count(rows, "wgrad_thin_kernel") + count(rows, "wgrad_thin4_kernel") == A.THIN_WGRADS[tag], rows

@@ -362,11 +362,12 @@ def test_attention_backward_golden(lib, golden, T):
 @pytest.mark.parametrize("B,heads,hw", [(1, 1, (6, 6)), (2, 1, (32, 32)), (1, 2, (2, 2)),
                                         (2, 2, (16, 16)), (1, 1, (8, 16)), (3, 1, (16, 24))])      # T = 256, 128 (LDS-staged kernels), 384
 def test_attention_backward_vs_oracle(lib, B, heads, hw):
-    qkv = fx.randn(f"t/bwd/attn/{B}{heads}{hw}", B, heads * 192, *hw).requires_grad_(True)
+    """Against fp64 autograd through the oracle (every launch branch, ragged tiles and misaligned callers: test_hip_attn_bwd.py)."""
+    qkv = fx.randn(f"t/bwd/attn/{B}{heads}{hw}", B, heads * 192, *hw)
     da = fx.randn(f"t/bwd/attn/da/{B}{heads}{hw}", B, heads * 64, *hw)
-    a = orc.attention(qkv, heads)
-    (ref,) = torch.autograd.grad(a, qkv, da)
-    pq = dev(packed_qkv(qkv.detach(), heads))
+    q64 = qkv.double().requires_grad_(True)
+    (ref,) = torch.autograd.grad(orc.attention(q64, heads), q64, da.double())
+    pq = dev(packed_qkv(qkv, heads))
     dqkv = lib.op_attention_bwd(pq, lib.op_attention(pq, heads), dev(da), heads)
     close(unpacked_qkv(dqkv.cpu(), heads), ref, what="dqkv")
 
