@@ -538,11 +538,12 @@ int launch_gn_bwd(const GnBwdArgs& a, hipStream_t s) {
     MCEDM_LAUNCH_CHECK("gn_bwd_reg_kernel");
     return MCEDM_OK;
   }
-  ProfScope ps("gn_bwd_kernel", 20.0 * a.B * (double)C * a.Hs * a.Ws, 4.0 * 3 * a.B * (double)C * a.Hs * a.Ws, s);
   // slabs of >= 64 KB: 1024-thread workgroups (at most two per CU instead of eight, so that fewer slabs are between their two passes
   // at any time and more of pass 2 is served by the memory-side cache: 5.78 -> 5.43 ms per S128 step, 3.12 -> 2.77 ms on the ch = 64 network)
   static const int nt = env_int("MCEDM_GN_BWD_NT", 1024);
-  if (nt == 1024 && (size_t)(C / a.groups) * a.Hs * a.Ws >= 16384)
+  const bool big = nt == 1024 && (size_t)(C / a.groups) * a.Hs * a.Ws >= 16384;
+  ProfScope ps("gn_bwd_kernel", 20.0 * a.B * (double)C * a.Hs * a.Ws, 4.0 * 3 * a.B * (double)C * a.Hs * a.Ws, s, big ? "<1024>" : "<256>");
+  if (big)
     hipLaunchKernelGGL(gn_bwd_kernel<1024>, dim3(a.B * a.groups), dim3(1024), 0, s, a);
   else
     hipLaunchKernelGGL(gn_bwd_kernel<256>, dim3(a.B * a.groups), dim3(256), 0, s, a);
@@ -659,14 +660,17 @@ int launch_small_gemm(const float* A, const float* Bm, float* Cm, int M, int N, 
 #define MCEDM_KEY_OF(r, h) ((r & 3) + 8 * (r >> 2) + 4 * (h))
 constexpr float ATT_LOG2E = 1.4426950408889634f;
 
-// The scores are formed the way the FORWARD kernel of the same T forms them (norm_emb_attn.hip launch_attention): natural units,
-// q / 8, expf below 128 tokens (attention_kernel); units of log 2, q log2(e) / 8, v_exp_f32 from 128 tokens on
-// (attention_split_kernel, attention_lds_kernel) -- the four-wave kernels here and the LDS kernels below.  delta = sum_c da a
-// carries the forward's probabilities, and dS = P o (dP - delta) cancels only as far as the P recomputed here equals them: at
-// scores of +-150 one rounding of q log2(e) / 8 moves a probability by 1e-5, which through |dP - delta| of 100 and more was
-// 2x the bar (rtol 1e-4, atol 1e-5 max) on dq where the forward passed it (tests/test_hip_attn_bwd.py, the x6 inputs).
-template <int KW> struct AttnBwdUnits {
-  static constexpr bool base2 = KW == 4;
+// The scores are formed the way the FORWARD kernel of the same call forms them (common.hpp attn_fwd_kernel, asked by
+// launch_attention_bwd with the same T and qkv): natural units, q / 8, expf where that is attention_kernel (below 128 tokens, and
+// at every T under MCEDM_ATTN_SPLIT=0); units of log 2, q log2(e) / 8, v_exp_f32 where it is attention_split_kernel or
+// attention_lds_kernel.  delta = sum_c da a carries the forward's probabilities, and dS = P o (dP - delta) cancels only as far
+// as the P recomputed here equals them: a score of +-150 carries the fp32 rounding of its 64-term sum, 1e-5 on a probability;
+// summed in the SAME units on both sides that error is in delta too and cancels, summed in two unit systems it meets
+// |dP - delta| of 100 and more and was 2x the bar (rtol 1e-4, atol 1e-5 max) on dq where the forward passed it.  (The one extra
+// rounding of q log2(e) / 8 alone is 0.04 to 0.16 of the bar: tests/test_knobs_cpu.py.)  tests/test_hip_attn_bwd.py, the x6
+// inputs; tests/test_hip_knobs.py for the knobs.
+template <bool B2> struct AttnBwdUnits {
+  static constexpr bool base2 = B2;
   static constexpr float qscale = base2 ? 0.125f * ATT_LOG2E : 0.125f;
   static __device__ __forceinline__ float exp(float x) { return base2 ? __builtin_amdgcn_exp2f(x) : expf(x); }
   static __device__ __forceinline__ float log(float x) { return base2 ? __builtin_amdgcn_logf(x) : logf(x); }      // v_log_f32 is log2
@@ -675,7 +679,7 @@ template <int KW> struct AttnBwdUnits {
 // KW waves per workgroup take the key tiles w, w + KW, ... of the SAME 32-query tile and their (running max, sum) pairs meet in
 // LDS, merged by wave 0 in wave order (round 5: one wave per tile was 512 waves per launch at T = 256, B = 32, two heads -- half a
 // wave per SIMD with every K load and every exp chain exposed: 107 us for 0.5 GFLOP)
-template <int KW>
+template <int KW, bool B2>
 __global__ __launch_bounds__(64 * KW) void attn_bwd_stats_kernel(const float* __restrict__ qkv, const float* __restrict__ a,
                                                                  const float* __restrict__ da, float* __restrict__ lse, int T) {
   __shared__ float ml[KW][2][32];
@@ -685,7 +689,7 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_stats_kernel(const float* __
   const float* Q = qkv + (bh * 3 + 0) * 64 * (size_t)T;
   const float* K = qkv + (bh * 3 + 1) * 64 * (size_t)T;
   const int q = q0 + l31, qc = q < T ? q : T - 1;
-  using U = AttnBwdUnits<KW>;
+  using U = AttnBwdUnits<B2>;
   float qreg[32];
   float delta = 0.f;
 #pragma unroll
@@ -760,7 +764,7 @@ __device__ __forceinline__ bool merge_wave_partials(float (&v)[NREG], float* par
   return true;
 }
 
-template <int KW>
+template <int KW, bool B2>
 __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
                                                               const float* __restrict__ lse, float* __restrict__ dqkv, int T) {
   __shared__ float part[KW > 1 ? (KW - 1) * 32 * 64 : 1];
@@ -772,7 +776,7 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const float* V = qkv + (bh * 3 + 2) * 64 * (size_t)T;
   const float* dA = da + bh * 64 * (size_t)T;
   const int q = q0 + l31, qc = q < T ? q : T - 1;
-  using U = AttnBwdUnits<KW>;
+  using U = AttnBwdUnits<B2>;
   float qreg[32], dareg[32];
 #pragma unroll
   for (int s = 0; s < 32; ++s) {
@@ -831,7 +835,7 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 
-template <int KW>
+template <int KW, bool B2>
 __global__ __launch_bounds__(64 * KW) void attn_bwd_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
                                                                const float* __restrict__ lse, float* __restrict__ dqkv, int T) {
   __shared__ float part[KW > 1 ? (KW - 1) * 64 * 64 : 1];
@@ -843,7 +847,7 @@ __global__ __launch_bounds__(64 * KW) void attn_bwd_dkv_kernel(const float* __re
   const float* V = qkv + (bh * 3 + 2) * 64 * (size_t)T;
   const float* dA = da + bh * 64 * (size_t)T;
   const int key = k0 + l31, kc = key < T ? key : T - 1;
-  using U = AttnBwdUnits<KW>;
+  using U = AttnBwdUnits<B2>;
   float kreg[32], vreg[32];
 #pragma unroll
   for (int s = 0; s < 32; ++s) {
@@ -923,11 +927,13 @@ constexpr int ATP = 65;                    // pitch of the transposed chunk imag
 // S = K^T Q product is the one computed here anyway; 164 of 496 us at T = 1024): the scores are normalised ONLINE -- running
 // maximum m and sum l per query as in the forward kernel, dq accumulated unnormalised and rescaled when m moves, divided by l at
 // the end -- and (m + log l, delta = sum_c dA A) go to `lse` for the second kernel.
+template <bool B2>
 __global__ __launch_bounds__(256) void attn_bwd_dq_lds_kernel(const float* __restrict__ qkv, const float* __restrict__ a,
                                                               const float* __restrict__ da, float* __restrict__ lse,
                                                               float* __restrict__ dqkv, int T, int xmap) {
   __shared__ float Kc[2][64 * 32], Vc[2][64 * 32], Kt[2][32 * ATP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
+  using U = AttnBwdUnits<B2>;
   int bx_, by_;
   xcd_group_map(xmap, bx_, by_);
   const size_t bh = by_;
@@ -940,7 +946,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_lds_kernel(const float* __res
   float delta = 0.f;
 #pragma unroll
   for (int s = 0; s < 32; ++s) {
-    qreg[s] = Q[(size_t)(2 * s + h) * T + q] * (0.125f * ATT_LOG2E);      // scores in units of log 2: v_exp_f32 is 2^x
+    qreg[s] = Q[(size_t)(2 * s + h) * T + q] * U::qscale;      // B2: scores in units of log 2 (v_exp_f32 is 2^x)
     dareg[s] = dA[(size_t)(2 * s + h) * T + q];
     delta += dareg[s] * a[bh * 64 * (size_t)T + (size_t)(2 * s + h) * T + q];
   }
@@ -992,12 +998,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_lds_kernel(const float* __res
     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float mn = fmaxf(m, mx);
-    const float alpha = __builtin_amdgcn_exp2f(m - mn);   // 0 on the first chunk (m = -inf)
+    const float alpha = U::exp(m - mn);   // 0 on the first chunk (m = -inf)
     float ds[16];
     float rs = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float pr = __builtin_amdgcn_exp2f(sc[r] - mn);
+      const float pr = U::exp(sc[r] - mn);
       rs += pr;
       ds[r] = pr * (dp[r] - delta);
     }
@@ -1022,15 +1028,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_lds_kernel(const float* __res
 #pragma unroll
     for (int r = 0; r < 16; ++r) dQ[(size_t)(32 * i + MCEDM_KEY_OF(r, h)) * T + q] = o[i][r] * sc_out;
   if (h == 0) {
-    lse[(bh * T + q) * 2] = m + __builtin_amdgcn_logf(l);      // base 2, as attn_bwd_dkv_lds_kernel expects it (v_log_f32 is log2)
+    lse[(bh * T + q) * 2] = m + U::log(l);      // in the units of the scores, as attn_bwd_dkv_lds_kernel<B2> expects it
     lse[(bh * T + q) * 2 + 1] = delta;
   }
 }
 
+template <bool B2>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_lds_kernel(const float* __restrict__ qkv, const float* __restrict__ da,
                                                                const float* __restrict__ lse, float* __restrict__ dqkv, int T, int xmap) {
   __shared__ float Qc[2][64 * 32], Ac[2][64 * 32], Qt[2][32 * ATP], At[2][32 * ATP], Ls[2][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
+  using U = AttnBwdUnits<B2>;
   int bx_, by_;
   xcd_group_map(xmap, bx_, by_);
   const size_t bh = by_;
@@ -1065,7 +1073,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_lds_kernel(const float* _
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int idx = tid + 256 * j, c = idx >> 3, qq = idx & 7;
-      *reinterpret_cast<f32x4*>(&Qc[buf][c * 32 + 4 * qq]) = rq[j] * (0.125f * ATT_LOG2E);
+      *reinterpret_cast<f32x4*>(&Qc[buf][c * 32 + 4 * qq]) = rq[j] * U::qscale;
       *reinterpret_cast<f32x4*>(&Ac[buf][c * 32 + 4 * qq]) = ra[j];
 #pragma unroll
       for (int e = 0; e < 4; ++e) { Qt[buf][(4 * qq + e) * ATP + c] = rq[j][e]; At[buf][(4 * qq + e) * ATP + c] = ra[j][e]; }
@@ -1091,7 +1099,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_lds_kernel(const float* _
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int qi = MCEDM_KEY_OF(r, h);
-      pr[r] = __builtin_amdgcn_exp2f(sc[r] - Ls[buf][2 * qi]);
+      pr[r] = U::exp(sc[r] - Ls[buf][2 * qi]);
       ds[r] = pr[r] * (dp[r] - Ls[buf][2 * qi + 1]);
     }
 #pragma unroll
@@ -1128,31 +1136,32 @@ int launch_attention_bwd(const float* qkv, const float* a, const float* da, floa
   // the profiler row names the branch taken (tests/_attn_bwd.py branch() restates the choice)
   const char* row = lds_path ? "attention_bwd_lds" : T >= 128 ? "attention_bwd_direct<4>" : T >= 64 ? "attention_bwd_direct<2>" : "attention_bwd_direct<1>";
   ProfScope ps(row, 10.0 * B * heads * (double)T * T * 64, 4.0 * 8 * B * heads * 64.0 * T, s);
-  if (!lds_path) {
-    if (T >= 128) hipLaunchKernelGGL(attn_bwd_stats_kernel<4>, grid, dim3(256), 0, s, qkv, a, da, lse, T);
-    else if (T >= 64) hipLaunchKernelGGL(attn_bwd_stats_kernel<2>, grid, dim3(128), 0, s, qkv, a, da, lse, T);
-    else hipLaunchKernelGGL(attn_bwd_stats_kernel<1>, grid, dim3(64), 0, s, qkv, a, da, lse, T);
-    MCEDM_LAUNCH_CHECK("attn_bwd_stats_kernel");
-  }
+  // the units of the scores are the forward's (common.hpp attn_fwd_kernel, AttnBwdUnits above), whatever the knobs make it
+  const bool b2 = attn_fwd_base2(attn_fwd_kernel(T, qkv));
+#define MCEDM_ATTN_BWD_DIRECT(KW, B2)                                                                         \
+  do {                                                                                                        \
+    hipLaunchKernelGGL((attn_bwd_stats_kernel<KW, B2>), grid, dim3(64 * KW), 0, s, qkv, a, da, lse, T);       \
+    MCEDM_LAUNCH_CHECK("attn_bwd_stats_kernel");                                                              \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<KW, B2>), grid, dim3(64 * KW), 0, s, qkv, da, lse, dqkv, T);       \
+    MCEDM_LAUNCH_CHECK("attn_bwd_dq_kernel");                                                                 \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<KW, B2>), grid, dim3(64 * KW), 0, s, qkv, da, lse, dqkv, T);      \
+  } while (0)
   if (lds_path) {
     const dim3 g4(T / 128, B * heads);
     const int xmap = attn_xcd_env();
-    hipLaunchKernelGGL(attn_bwd_dq_lds_kernel, g4, dim3(256), 0, s, qkv, a, da, lse, dqkv, T, xmap);
+    if (b2) hipLaunchKernelGGL(attn_bwd_dq_lds_kernel<true>, g4, dim3(256), 0, s, qkv, a, da, lse, dqkv, T, xmap);
+    else hipLaunchKernelGGL(attn_bwd_dq_lds_kernel<false>, g4, dim3(256), 0, s, qkv, a, da, lse, dqkv, T, xmap);
     MCEDM_LAUNCH_CHECK("attn_bwd_dq_lds_kernel");
-    hipLaunchKernelGGL(attn_bwd_dkv_lds_kernel, g4, dim3(256), 0, s, qkv, da, lse, dqkv, T, xmap);
+    if (b2) hipLaunchKernelGGL(attn_bwd_dkv_lds_kernel<true>, g4, dim3(256), 0, s, qkv, da, lse, dqkv, T, xmap);
+    else hipLaunchKernelGGL(attn_bwd_dkv_lds_kernel<false>, g4, dim3(256), 0, s, qkv, da, lse, dqkv, T, xmap);
   } else if (T >= 128) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<4>, grid, dim3(256), 0, s, qkv, da, lse, dqkv, T);
-    MCEDM_LAUNCH_CHECK("attn_bwd_dq_kernel");
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<4>, grid, dim3(256), 0, s, qkv, da, lse, dqkv, T);
+    if (b2) MCEDM_ATTN_BWD_DIRECT(4, true); else MCEDM_ATTN_BWD_DIRECT(4, false);
   } else if (T >= 64) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, grid, dim3(128), 0, s, qkv, da, lse, dqkv, T);
-    MCEDM_LAUNCH_CHECK("attn_bwd_dq_kernel");
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, grid, dim3(128), 0, s, qkv, da, lse, dqkv, T);
+    if (b2) MCEDM_ATTN_BWD_DIRECT(2, true); else MCEDM_ATTN_BWD_DIRECT(2, false);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<1>, grid, dim3(64), 0, s, qkv, da, lse, dqkv, T);
-    MCEDM_LAUNCH_CHECK("attn_bwd_dq_kernel");
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<1>, grid, dim3(64), 0, s, qkv, da, lse, dqkv, T);
+    if (b2) MCEDM_ATTN_BWD_DIRECT(1, true); else MCEDM_ATTN_BWD_DIRECT(1, false);
   }
+#undef MCEDM_ATTN_BWD_DIRECT
   MCEDM_LAUNCH_CHECK("attn_bwd_dkv_kernel");
   return MCEDM_OK;
 }

@@ -61,6 +61,28 @@ __device__ __forceinline__ void xcd_group_map(int map, int& bx, int& by) {
 // MCEDM_ATTN_XCD: the `map` of xcd_group_map in the attention forward and backward kernels
 inline int attn_xcd_env() { static const int v = env_int("MCEDM_ATTN_XCD", 1); return v; }
 
+// Which forward attention kernel serves T tokens (norm_emb_attn.hip launch_attention), a function of T, the two knobs and the
+// alignment of qkv only -- never of the batch size: results are identical under batch sharding.
+//   MCEDM_ATTN_SPLIT  0: the one-wave-per-query-tile kernel at every T; 1: split<2> from 128, split<4> from 256 tokens, the
+//                     LDS-staged kernel from MCEDM_ATTN_LDS_MIN; 2: never the LDS-staged kernel; 3: its four-wave variant (A/B runs)
+//   MCEDM_ATTN_LDS_MIN  shortest sequence that takes the LDS-staged kernel (A/B runs)
+// The backward (bwd_kernels.hip launch_attention_bwd) asks the same function for the units in which the forward formed its scores,
+// with ITS qkv pointer: the two calls must see the same buffer (as the plan's do).  With MCEDM_ATTN_LDS_MIN below 128 a qkv that is
+// 16-byte aligned in only one of the two calls gives `one` there and `lds<2>` here, i.e. two unit systems; at the default knobs
+// the alignment decides between kernels of the same units only.
+enum AttnFwd { ATTN_FWD_ONE = 0, ATTN_FWD_SPLIT2, ATTN_FWD_SPLIT4, ATTN_FWD_LDS1, ATTN_FWD_LDS2 };
+inline AttnFwd attn_fwd_kernel(int T, const void* qkv) {
+  static const int mode = env_int("MCEDM_ATTN_SPLIT", 1);
+  static const int lds_min = env_int("MCEDM_ATTN_LDS_MIN", 512);
+  const bool aligned = (T % 4 == 0) && ((reinterpret_cast<size_t>(qkv) & 15) == 0);
+  if (mode >= 1 && mode != 2 && T >= lds_min && aligned) return mode == 3 ? ATTN_FWD_LDS1 : ATTN_FWD_LDS2;
+  if (mode && T >= 256) return ATTN_FWD_SPLIT4;
+  if (mode && T >= 128) return ATTN_FWD_SPLIT2;
+  return ATTN_FWD_ONE;
+}
+// attention_kernel forms its scores in natural units (q / 8, expf), every other forward kernel in units of log 2
+inline bool attn_fwd_base2(AttnFwd k) { return k != ATTN_FWD_ONE; }
+
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------------------

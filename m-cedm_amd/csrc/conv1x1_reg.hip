@@ -207,9 +207,11 @@ int try_launch_conv1x1_reg(const ConvArgs& a, int taps, hipStream_t stream) {
     attr_set[dev].store(true, std::memory_order_release);
   }
   const double px = (double)a.B * (double)HW;
-  ProfScope ps("conv1x1_reg_kernel", 2.0 * px * a.Cout * Cin, 4.0 * (px * (Cin + a.Cout * (a.res ? 2 : 1)) + (double)a.Cout * Cin), stream);
   // MCEDM_C1_NI: 2 or 4 (A/B runs; the two differ in the last bits of nothing: same sums); NI = 4 measured 20 % slower (436 vs 364 us)
   static const int ni_env = env_int("MCEDM_C1_NI", 2);
+  // the profiler row names the instantiation <NI, MT> as its variant
+  ProfScope ps("conv1x1_reg_kernel", 2.0 * px * a.Cout * Cin, 4.0 * (px * (Cin + a.Cout * (a.res ? 2 : 1)) + (double)a.Cout * Cin), stream,
+               MT == 64 ? "<2, 64>" : ni_env == 2 ? "<2, 128>" : "<4, 128>");
   if (MT == 64) hipLaunchKernelGGL((conv1x1_reg_kernel<2, 64>), dim3(wgs, mblocks), dim3(512), lds, stream, p);
   else if (ni_env == 2) hipLaunchKernelGGL(conv1x1_reg_kernel<2>, dim3(wgs, mblocks), dim3(512), lds, stream, p);
   else hipLaunchKernelGGL(conv1x1_reg_kernel<4>, dim3(wgs, mblocks), dim3(512), lds, stream, p);

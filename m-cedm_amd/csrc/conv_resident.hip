@@ -574,22 +574,10 @@ static int resident_level() { return kernel_switch(KV_CONV_RESIDENT); }     // 0
 bool conv_resident_explicit() { return kernel_switch_forced(KV_CONV_RESIDENT) >= 0; }
 
 static constexpr int LDS_MAX = 160 * 1024;
-// big-tile (>= 64 x 64 images) variants: MCEDM_RES_BIG=0 turns them off; MCEDM_RES_BIG_PASS = channels per pass (multiple of 8)
+// big-tile (>= 64 x 64 images) variants: MCEDM_RES_BIG=0 turns them off
 static int big_level() {
   static const int env = env_int("MCEDM_RES_BIG", 1);
   return env;
-}
-static int db_level() {          // MCEDM_RES_DB=1: double-buffered short passes at <= 32 x 32 (experiment)
-  static const int env = env_int("MCEDM_RES_DB", 0);
-  return env;
-}
-static int big128_level() {
-  static const int env = env_int("MCEDM_RES_BIG128", 0);
-  return env;
-}
-static int big_pass() {
-  static const int v = env_int("MCEDM_RES_BIG_PASS", 0);
-  return v >= 8 ? v / 8 * 8 : 1 << 20;
 }
 
 // Launch plan of one conv: channels resident per pass (0: this conv is not served here), weight slabs in the ring.
@@ -691,11 +679,6 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
     }
     if (small) {          // <= 256 workgroups per 64 samples: one per CU, the whole LDS
       if (cout_padded(a.Cout) % 64 != 0) return -1;
-      if (db_level() > 0 && a.resample == RS_NONE) {     // short double-buffered passes: the K loop starts after 32 channels
-        typedef ResCfg<64, 8, 8, 2, 2, 9, 8, 1, 1> SD;
-        ResidentPlan pd = resident_plan<SD, false>(a, whole_cu, 32);
-        if (pd.pass_c && pd.nslab == 3) { if (pd.pass_c > 32) pd.pass_c = 32; return launch_resident<SD, RS_NONE>(a, pd, stream); }
-      }
       const ResidentPlan pl = resident_plan<S, false>(a, whole_cu, 64);
       if (!pl.pass_c) return -1;
       return a.resample == RS_UP ? launch_resident<S, RS_UP>(a, pl, stream) : launch_resident<S, RS_NONE>(a, pl, stream);
@@ -709,15 +692,8 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
         if (!p32.pass_c || p32.nslab != 3 || a.resample != RS_NONE) return -1;
         return launch_resident<M32, RS_NONE, true>(a, p32, stream);
       }
-      if (db_level() > 0 && a.resample == RS_NONE) {     // 16-channel double-buffered passes
-        typedef ResCfg<64, 8, 16, 1, 4, 9, 8, 1, 1> MD;
-        ResidentPlan pd = resident_plan<MD, true>(a, half_cu, 16);
-        if (pd.pass_c && pd.nslab == 3 && pd.wide) { if (pd.pass_c > 16) pd.pass_c = 16; return launch_resident<MD, RS_NONE, true>(a, pd, stream); }
-      }
-      ResidentPlan pl = resident_plan<M, true>(a, half_cu, 32);
+      const ResidentPlan pl = resident_plan<M, true>(a, half_cu, 32);
       if (!pl.pass_c || pl.nslab != 3) return -1;
-      static const int pass_env = env_int("MCEDM_RES_PASS", 0);      // experiments: channels per pass (multiple of 16, <= the plan's)
-      if (pass_env >= 16 && pass_env % 16 == 0 && pass_env < pl.pass_c) pl.pass_c = pass_env;
       return a.resample == RS_UP ? launch_resident<M, RS_UP, true>(a, pl, stream) : launch_resident<M, RS_NONE, true>(a, pl, stream);
     }
     if ((long long)a.H * a.W >= 4096 && big_level() > 0 && a.resample == RS_NONE && cout_padded(a.Cout) == 64) {
@@ -728,23 +704,16 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
       // segments (6 instructions per wave and 16-channel pass), is transformed in place, and no staging registers exist, so
       // a wave can own EIGHT accumulator blocks (64 channels x 16 x 32 pixels per workgroup) at two workgroups per CU.
       // The pixel tile is a function of the image size only (batch-shard bit-identity).
-      static const int b16_min = env_int("MCEDM_RES_B16_MIN", 16384);      // smallest image (pixels) that takes the 16 x 32 tile (experiments)
+      constexpr int b16_min = 16384;      // smallest image (pixels) that takes the 16 x 32 tile
       if ((long long)a.H * a.W >= b16_min) {
         typedef ResCfg<64, 16, 32, 1, 4, 9, 8> B16;
-        ResidentPlan pl = resident_plan<B16, true>(a, half_cu, 8);
-        if (pl.pass_c && pl.nslab == 3 && pl.wide) { if (pl.pass_c > big_pass()) pl.pass_c = big_pass(); return launch_resident<B16, RS_NONE, true>(a, pl, stream); }
+        const ResidentPlan pl = resident_plan<B16, true>(a, half_cu, 8);
+        if (pl.pass_c && pl.nslab == 3 && pl.wide) return launch_resident<B16, RS_NONE, true>(a, pl, stream);
       } else {
         typedef ResCfg<64, 8, 32, 1, 4, 9, 8> B8;
-        ResidentPlan pl = resident_plan<B8, true>(a, half_cu, 8);
-        if (pl.pass_c && pl.nslab == 3 && pl.wide) { if (pl.pass_c > big_pass()) pl.pass_c = big_pass(); return launch_resident<B8, RS_NONE, true>(a, pl, stream); }
+        const ResidentPlan pl = resident_plan<B8, true>(a, half_cu, 8);
+        if (pl.pass_c && pl.nslab == 3 && pl.wide) return launch_resident<B8, RS_NONE, true>(a, pl, stream);
       }
-    }
-    if ((long long)a.H * a.W >= 4096 && big128_level() > 0 && a.resample == RS_NONE && cout_padded(a.Cout) % 128 == 0 && !a.sk_wpk) {
-      // the same for 128-channel output tiles (ch = 128 networks: BASELINE config 3), 8 x 32 pixels, eight accumulator
-      // blocks per wave.  MCEDM_RES_BIG128: 0 off, 1 on
-      typedef ResCfg<128, 8, 32, 1, 4, 9, 8> B128;
-      ResidentPlan pl = resident_plan<B128, true>(a, half_cu, 8);
-      if (pl.pass_c && pl.wide) { if (pl.pass_c > big_pass()) pl.pass_c = big_pass(); return launch_resident<B128, RS_NONE, true>(a, pl, stream); }
     }
     return -1;
   }
@@ -756,10 +725,8 @@ int try_launch_conv_resident(const ConvArgs& a, int taps, hipStream_t stream) {
   // ~32 x 32 images (the decoder's skip projections there, launched on their own since conv1 runs on the Winograd kernel):
   // 1024 tiles per 64 samples, two workgroups per CU.  conv_mfma_kernel's <32, 8, 32> tile walks 8-16 chunks of
   // load -> barrier -> MFMA -> barrier with one accumulator block per wave and sits at 28 TFLOP/s there.
-  // MCEDM_RES_1X1_32 (A/B runs): 0 keeps these convs on conv_mfma_kernel, 1: 8 x 8-pixel tiles, 2 (default): 8 x 16
-  static const int p32 = env_int("MCEDM_RES_1X1_32", 2);
-  if (p32 > 0 && !small && a.W >= 24 && (long long)a.H * a.W <= 1024 && !a.sk_wpk && cout_padded(a.Cout) % 64 == 0) {
-    if (p32 == 2) {              // 8 x 16-pixel tiles: 512 workgroups per 64 samples = ONE round of two per CU (S32 1750 -> 1781 states/s; 8 x 8: two rounds)
+  if (!small && a.W >= 24 && (long long)a.H * a.W <= 1024 && !a.sk_wpk && cout_padded(a.Cout) % 64 == 0) {
+    {                            // 8 x 16-pixel tiles: 512 workgroups per 64 samples = ONE round of two per CU (S32 1750 -> 1781 states/s; 8 x 8: two rounds)
       typedef ResCfg<64, 8, 16, 1, 4, 1, 16> P16;
       const ResidentPlan pl = resident_plan<P16, false>(a, half_cu, 64);
       if (pl.pass_c && pl.wide) return launch_resident<P16, RS_NONE>(a, pl, stream);

@@ -667,21 +667,20 @@ static int launch_attention_lds(const float* qkv, float* out, int B, int heads, 
 int launch_attention(const float* qkv, float* out, int B, int heads, int T, hipStream_t stream) {
   MCEDM_REQUIRE(B > 0 && heads > 0 && T > 0, "attention: empty shape");
   MCEDM_REQUIRE((long long)B * heads <= 65535, "attention: B*heads too large for grid.y");
-  ProfScope ps("attention_kernel", 4.0 * B * heads * (double)T * T * 64, 4.0 * 4 * B * heads * 64.0 * T, stream);
-  // the split factor is a function of T only (never of the batch size): results are identical under batch sharding
+  // the kernel is a function of T, the knobs and the alignment only (common.hpp attn_fwd_kernel), never of the batch size: results
+  // are identical under batch sharding.  The LDS-staged kernel for long sequences is chosen by T alone like the split factor (at
+  // B * heads < 24 it fills fewer CUs than the split kernel would: 91 vs 45 us at B = 8 -- accepted for that invariance).
+  const AttnFwd kind = attn_fwd_kernel(T, qkv);
+  // the profiler row says which kernel was taken, as its variant (tests/_knobs.py attn_fwd_row restates the choice)
+  static const char* const variants[] = {"one", "split<2>", "split<4>", "lds<1>", "lds<2>"};
+  ProfScope ps("attention_kernel", 4.0 * B * heads * (double)T * T * 64, 4.0 * 4 * B * heads * 64.0 * T, stream, variants[kind]);
   const dim3 grid(ceil_div(T, 32), B * heads);
-  // LDS-staged kernel for long sequences, chosen by T alone like the split factor (at B * heads < 24 it fills fewer CUs than
-  // the split kernel would: 91 vs 45 us at B = 8 -- accepted for the batch-sharding invariance).  MCEDM_ATTN_SPLIT=2: split
-  // kernel for every T, 3: the four-wave variant of the LDS kernel (A/B switches)
-  const bool aligned = (T % 4 == 0) && ((reinterpret_cast<size_t>(qkv) & 15) == 0);
-  static const int mode = env_int("MCEDM_ATTN_SPLIT", 1);         // 0: the one-wave-per-query-tile kernel everywhere (A/B runs)
-  static const int lds_min = env_int("MCEDM_ATTN_LDS_MIN", 512);  // shortest sequence that takes the LDS-staged kernel (A/B runs)
-  if (mode >= 1 && mode != 2 && T >= lds_min && aligned) {
-    const int rc = mode == 3 ? launch_attention_lds<1>(qkv, out, B, heads, T, stream) : launch_attention_lds<2>(qkv, out, B, heads, T, stream);
+  if (kind == ATTN_FWD_LDS1 || kind == ATTN_FWD_LDS2) {
+    const int rc = kind == ATTN_FWD_LDS1 ? launch_attention_lds<1>(qkv, out, B, heads, T, stream) : launch_attention_lds<2>(qkv, out, B, heads, T, stream);
     if (rc != MCEDM_OK) return rc;
   }
-  else if (mode && T >= 256) hipLaunchKernelGGL(attention_split_kernel<4>, grid, dim3(256), 0, stream, qkv, out, T);
-  else if (mode && T >= 128) hipLaunchKernelGGL(attention_split_kernel<2>, grid, dim3(128), 0, stream, qkv, out, T);
+  else if (kind == ATTN_FWD_SPLIT4) hipLaunchKernelGGL(attention_split_kernel<4>, grid, dim3(256), 0, stream, qkv, out, T);
+  else if (kind == ATTN_FWD_SPLIT2) hipLaunchKernelGGL(attention_split_kernel<2>, grid, dim3(128), 0, stream, qkv, out, T);
   else hipLaunchKernelGGL(attention_kernel, grid, dim3(64), 0, stream, qkv, out, T);
   MCEDM_LAUNCH_CHECK("attention_kernel");
   return MCEDM_OK;

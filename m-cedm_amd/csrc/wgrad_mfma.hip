@@ -37,10 +37,6 @@ struct WgCfg {
 
 bool wgrad_thin_applicable(const WgradArgs& a, int taps, int qkv_heads);
 int launch_wgrad_thin(const WgradArgs& a, float* dw, float* db, hipStream_t s);
-static bool wgrad_thin_enabled() {                       // MCEDM_WGRAD_THIN=0: the MFMA block kernel for these shapes too (A/B runs)
-  static const int env = env_int("MCEDM_WGRAD_THIN", 1);
-  return env != 0;
-}
 
 __device__ __forceinline__ float silu_w(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
@@ -454,7 +450,7 @@ int launch_wgrad(const WgradArgs& a, int taps, float* dw, float* db, int qkv_hea
   // an un-transformed single-source input (the attention projection's) IS the operand: no copy -- except for the Winograd
   // kernel, which reads the 4 bytes in front of its operand (and discards them): it only ever sees act_tmp, a scratch region
   // that is never the start of an allocation
-  if (!have_act && wgrad_thin_applicable(a, taps, qkv_heads) && wgrad_thin_enabled()) return launch_wgrad_thin(a, dw, db, s);
+  if (!have_act && wgrad_thin_applicable(a, taps, qkv_heads)) return launch_wgrad_thin(a, dw, db, s);
   const bool wino = wgrad_wino_applicable(a, taps, qkv_heads);
   const bool plain = !wino && !have_act && !a.coef && !a.act && a.resample == RS_NONE && a.xa && (a.Cb == 0 || a.xb);
   const float* xact = plain ? (a.Cb == 0 ? a.xa : nullptr) : act_tmp;      // nullptr: the kernel reads cat(xa, xb) in place

@@ -749,10 +749,7 @@ __global__ __launch_bounds__(1024) void wgrad_wino_finish_kernel(const double* _
 
 static int wgw_env() { return kernel_switch(KV_WGRAD_WINO); }
 
-static int wgw64_env() {
-  static const int env = env_int("MCEDM_WGRAD_WINO64", 1);
-  return env;
-}
+static int wgw64_env() { return 1; }      // the 64-channel form (its A/B knob went with the other untested ones)
 
 // splits of the K range: one round of one workgroup per CU over the siblings of a split (4 * cib * cob in the 128-channel form,
 // cib * cob in the 64-channel form), a multiple of 8 (XCD mapping).  A function of the channel counts only, so that the scratch
@@ -809,7 +806,7 @@ static int wgw_form(const WgradArgs& a, int taps, int qkv_heads) {
   // per split the direct kernel is as fast or faster (64 -> 64 at 32^2, B = 32: 4 stages, 47 against 46 us; tools/wgrad_wino_ab.py)
   // (a switch FORCED on -- mcedm_op_set_wgrad_wino(1) or the plan's variant -- serves every legal shape: the parity tests' small cases)
   if (form == 2 && kernel_switch_forced(KV_WGRAD_WINO) != 1) {
-    static const int min_per = env_int("MCEDM_WGRAD_WINO64_MIN", 4);
+    constexpr int min_per = 4;
     const long long total = (long long)a.B * (a.H / 2) * (a.W / 16);
     if (total < (long long)min_per * wgw_form_nsplit(2, a.Cout, Cin)) return 0;
   }
@@ -878,10 +875,7 @@ int launch_wgrad_wino(const WgradArgs& a, const float* x, float* dw, float* db, 
 }
 
 // ---- the 1x1 GEMM form
-static int wgg_env() {
-  static const int env = env_int("MCEDM_WGRAD_GEMM1", 1);
-  return env;
-}
+static int wgg_env() { return 1; }
 static bool wgg_shape_ok(int Cout, int Cin, int taps) { return taps == 1 && Cout > 0 && Cin > 0 && Cout % GW_CB == 0 && Cin % GW_CB == 0; }
 // slices ([co][ci] blocks + bias rows) of the LARGEST split count these channel counts can get
 size_t wgrad_gemm1_scratch_floats(int Cout, int Cin, int taps) {

@@ -1288,7 +1288,8 @@ def prof_enable(on: bool) -> None:
 
 
 def prof_report() -> list:
-    """Kernel-level timing rows collected since prof_enable(True) (synchronises the recorded events)."""
+    """Kernel-level timing rows collected since prof_enable(True) (synchronises the recorded events).  A row whose launcher chooses
+    among kernels or template instantiations under one name also has "variants": {variant: launches}."""
     import json
     lib = load()
     buf = C.create_string_buffer(1 << 16)

@@ -11,8 +11,8 @@ The launcher picks its kernels from the token count T = H W and the alignment of
     direct<2>  64 <= T < 128                               the streamed axis on wave w, partial results merged through LDS in
     direct<1>  T < 64                                      wave order; a ragged last tile is loaded clamped and masked
 
-lds and direct<4> form their scores in units of log 2 and direct<2>, direct<1> in natural units, each as the forward kernel of the
-same T does (AttnBwdUnits): delta = sum_c da a carries the forward's probabilities, and the x6 inputs notice a backward whose
+With the knobs at their defaults lds and direct<4> form their scores in units of log 2 and direct<2>, direct<1> in natural units:
+each as the forward kernel of the same T and knobs does (common.hpp attn_fwd_kernel, AttnBwdUnits; tests/_knobs.py): delta = sum_c da a carries the forward's probabilities, and the x6 inputs notice a backward whose
 recomputed probabilities differ from them by one rounding of the scaled query.
 
 Layouts: the oracle takes qkv [B, heads 3 64, H, W] in the reference's channel order (head, c, {q, k, v}); the kernels take the
@@ -49,9 +49,9 @@ class Case(collections.namedtuple("Case", "B heads H W misalign")):
 
 
 def branch(T, aligned=True):
-    """The branch launch_attention_bwd takes, as the suffix of its profiler row "attention_bwd_<branch>".  bwd_kernels.hip:1127:
-    lds_path = T % 128 == 0 && ((qkv | da) & 15) == 0 (with MCEDM_ATTN_BWD_LDS at its default 1); :1129, and the launches at
-    :1132-1134 and :1137-1155: otherwise T >= 128 -> <4>, T >= 64 -> <2>, else <1>."""
+    """The branch launch_attention_bwd takes, as the suffix of its profiler row "attention_bwd_<branch>".  bwd_kernels.hip:1133:
+    lds_path = T % 128 == 0 && ((qkv | da) & 15) == 0 (with MCEDM_ATTN_BWD_LDS at its default 1); :1135, and the launches at
+    :1147-1161: otherwise T >= 128 -> <4>, T >= 64 -> <2>, else <1>."""
     if T % 128 == 0 and aligned:
         return "lds"
     return "direct<4>" if T >= 128 else ("direct<2>" if T >= 64 else "direct<1>")

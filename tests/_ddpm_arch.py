@@ -104,6 +104,16 @@ def oracle_forward(tag, P, key_run):
                                  cond=cond if use_cond else None)
 
 
+def attention_tokens(cfg):
+    """Tokens of every attention block: down.L / up.L blocks work at resolution >> L, the middle block at the last level."""
+    out = []
+    for n, _ in ddo.param_shapes(cfg):
+        if n.endswith(".q.weight"):
+            level = len(cfg.ch_mult) - 1 if n.startswith("mid.") else int(n.split(".")[1])
+            out.append((cfg.resolution >> level) ** 2)
+    return out
+
+
 def n_attention_blocks(cfg):
     return sum(n.endswith(".q.weight") for n, _ in ddo.param_shapes(cfg))
 

@@ -36,6 +36,7 @@ import torch
 
 from tests import _adm_arch as A
 from tests import _attn_bwd as AB
+from tests import _knobs as K
 
 pytestmark = pytest.mark.gpu
 
@@ -106,16 +107,29 @@ def training_step(tag, L, plan, params, packed):
 
 
 def profiled(L, fn):
-    """fn() with the profiler on -> (its result, kernel name -> launches)."""
+    """fn() with the profiler on -> (its result, kernel name -> launches; .variants: kernel name -> {variant: launches} for the
+    rows whose launches name the kernel or instantiation they took)."""
     torch.cuda.synchronize()
     L.prof_enable(True)
     try:
         out = fn()
         torch.cuda.synchronize()
-        rows = {r["name"]: int(r["launches"]) for r in L.prof_report()}
+        report = L.prof_report()
     finally:
         L.prof_enable(False)
+    rows = Rows((r["name"], int(r["launches"])) for r in report)
+    rows.variants = {r["name"]: r["variants"] for r in report if r.get("variants")}
     return out, rows
+
+
+class Rows(dict):
+    variants = None
+
+
+def fwd_variants(tag):
+    """One launch_attention per attention block, on the kernel its token count selects (tests/_knobs.py attn_fwd_variant; the
+    workspace is 16-byte aligned): variant -> launches."""
+    return dict(collections.Counter(K.attn_fwd_variant(T) for T in A.attention_tokens(tag)))
 
 
 def count(rows, prefix):
@@ -182,6 +196,7 @@ def test_training_step_golden_and_fp64(golden, tag):
     loss2, grads2 = training_step(tag, L, plan, params, packed)
     assert torch.equal(loss, loss2) and all(torch.equal(grads[n], grads2[n]) for n in grads)
     assert count(rows, "attn_block64") == 0 and rows.get("attention_kernel", 0) == len(A.attention_tokens(tag)), rows
+    assert rows.variants.get("attention_kernel", {}) == fwd_variants(tag), (rows.variants, fwd_variants(tag))
     # the attention backward, one launch per block on the branch its token count selects (the workspace is 16-byte aligned)
     want = collections.Counter("attention_bwd_" + AB.branch(T) for T in A.attention_tokens(tag))
     assert {k: v for k, v in rows.items() if k.startswith("attention_bwd")} == dict(want), (rows, want)
@@ -213,6 +228,7 @@ def test_the_intended_kernels_ran(tag):
         assert count(rows, "attn_block64") == n_attn == 4 and rows.get("attention_kernel", 0) == 0, rows
     else:
         assert count(rows, "attn_block64") == 0 and rows.get("attention_kernel", 0) == n_attn, rows
+        assert rows.variants.get("attention_kernel", {}) == fwd_variants(tag), (rows.variants, fwd_variants(tag))
 
 
 # ---- 4. batch independence, repeatability -----------------------------------------------------------------------------------------------
@@ -242,9 +258,11 @@ def test_kernel_family_switched_off_stays_within_the_bar(golden, which, tag):
     held_forward(tag, f"{tag}::F_sigma", got, g, what=f" [{which} = 0]")
     if which == "attn_fused":
         assert rows.get("attention_kernel", 0) == len(A.attention_tokens(tag)), rows
+        assert rows.variants.get("attention_kernel", {}) == fwd_variants(tag), (rows.variants, fwd_variants(tag))
     if which == "conv_wino_fold":
         # the projections the fold served run as their own launches: try_launch_conv1x1_reg (128 output channels, 1024 pixels)
         assert rows.get("conv1x1_reg_kernel", 0) > 0, sorted(rows)
+        assert rows.variants["conv1x1_reg_kernel"] == {"<2, 128>": rows["conv1x1_reg_kernel"]}, rows.variants
 
 
 def test_fold_and_register_gemm_both_off(golden):

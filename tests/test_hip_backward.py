@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from oracle import fixtures as fx
 from oracle import mcedm_oracle as orc
+from tests import _knobs as K
 
 pytestmark = pytest.mark.gpu
 
@@ -200,71 +201,32 @@ def test_wgrad_reads_an_untransformed_concat_in_place(lib, B, Ca, Cb, Cout, H, W
     (1, 128, 0, 64, 64, 2, 1, False, 1, False, "sync"),
 ])
 def test_gn_film_silu_backward(lib, case):
+    """Inputs, reference and device run are tests/_knobs.py's (shared with the knob tests, which run the two-pass kernel on the
+    shapes that take the other two here)."""
     use_sync = len(case) > 10
     B, Ca, Cb, Hs, Ws, rs, act, use_film, add_mode, accumulate = case[:10]
-    tag = "t/bwd/gn/" + "_".join(map(str, case))
     C = Ca + Cb
-    Hc, Wc = (Hs * 2, Ws * 2) if rs == 1 else ((Hs // 2, Ws // 2) if rs == 2 else (Hs, Ws))
-    xa = (fx.randn(tag + "/xa", B, Ca, Hs, Ws) * 1.3 + 0.4).requires_grad_(True)
-    xb = (fx.randn(tag + "/xb", B, Cb, Hs, Ws) * 0.7).requires_grad_(True) if Cb else None
-    gamma = fx.param(tag, "norm.weight", (C,)).requires_grad_(True)
-    beta = fx.param(tag, "norm.bias", (C,)).requires_grad_(True)
-    film = (fx.randn(tag + "/film", B, 2 * C) * 0.3).requires_grad_(True) if use_film else None
-    dact = fx.randn(tag + "/dact", B, C, Hc, Wc)
-    add = None
-    if add_mode == 1:
-        add = fx.randn(tag + "/add", B, C, Hs, Ws)
-    elif add_mode == 2:
-        add = fx.randn(tag + "/add", B, C, Hc, Wc)
-    init = (fx.randn(tag + "/ia", B, Ca, Hs, Ws), fx.randn(tag + "/ib", B, Cb, Hs, Ws) if Cb else None) if accumulate else None
-    # reference
-    x = torch.cat([xa, xb], 1) if Cb else xa
-    t = orc.group_norm(x, gamma, beta)
-    if use_film:
-        t = torch.addcmul(film[:, C:, None, None], t, film[:, :C, None, None] + 1)
-    u = F.silu(t) if act else t
-    res = (lambda v: orc.resample_up(v)) if rs == 1 else ((lambda v: orc.resample_down(v)) if rs == 2 else (lambda v: v))
-    loss = (res(u) * dact).sum()
-    if add_mode == 1:
-        loss = loss + (x * add).sum()
-    elif add_mode == 2:
-        loss = loss + (res(x) * add).sum()
-    ins = [xa, gamma, beta] + ([xb] if Cb else []) + ([film] if use_film else [])
-    gr = torch.autograd.grad(loss, ins)
-    gxa, gg, gb = gr[0], gr[1], gr[2]
-    gxb = gr[3] if Cb else None
-    gfilm = gr[-1] if use_film else None
-    if accumulate:
-        gxa = gxa + init[0]
-        gxb = gxb + init[1] if Cb else None
-    # HIP
-    coef, stats = lib.op_gn_coef(dev(xa), dev(xb) if Cb else None, dev(gamma), dev(beta), film=dev(film) if use_film else None,
-                                 film_batch=1, film_stride=2 * C, want_stats=True)
-    sync = torch.zeros(lib.GN_SYNC_WORDS * B * min(32, C // 4), dtype=torch.int32, device="cuda") if use_sync else None
-    lib.prof_enable(True)
-    dxa, dxb, dg, dbt, dfilm = lib.op_gn_bwd(dev(dact), dev(xa), dev(xb) if Cb else None, coef, stats, dev(gamma), dev(beta),
-                                             film=dev(film) if use_film else None, film_batch=1, film_stride=2 * C, act=act,
-                                             resample=rs, add=dev(add) if add is not None else None, add_mode=add_mode,
-                                             dx_init=(dev(init[0]), dev(init[1]) if Cb else None) if accumulate else None,
-                                             sync=sync)
-    torch.cuda.synchronize()
-    names = {r["name"] for r in lib.prof_report()}
-    lib.prof_enable(False)
+    t = K.gn_inputs(case)
+    ref = K.gn_reference(case, t)
+    got, names, sync_left = K.run_gn(lib, case, t)
     on_chip = use_sync and (rs == 0 or Ws % 4 == 0) and (Hs * Ws) % 4096 == 0 and (C // min(32, C // 4)) * Hs * Ws >= 16384
     cpg, hw = C // min(32, C // 4), Hs * Ws
     in_regs = (not on_chip and rs == 0 and hw % 4 == 0 and cpg * hw <= 8192
                and ((hw // 4) % 64 == 0 or (16 <= hw // 4 < 64 and (hw // 4) & (hw // 4 - 1) == 0)))
+    # the two-pass kernel: 1024 threads on slabs of >= 16384 elements, else 256
     want = "gn_bwd_lds_kernel" if on_chip else "gn_bwd_reg_kernel" if in_regs else "gn_bwd_kernel"
-    assert {n_ for n_ in names if n_.startswith("gn_bwd")} == {want}, (names, want, case)
+    if want == "gn_bwd_kernel":      # the two-pass kernel names its instantiation: 1024 threads on slabs of >= 16384 elements, else 256
+        want += "[<1024>]" if cpg * hw >= 16384 else "[<256>]"
+    assert {n_ for n_ in names if n_.startswith("gn_bwd")} == {want} and want == K.gn_bwd_row(case), (names, want, case)
     if use_sync:
-        assert int(sync.abs().sum()) == 0, "the exchange area must be left zero"
-    close(dxa, gxa, what="dxa")
+        assert sync_left == 0, "the exchange area must be left zero"
+    close(got["dxa"], ref["dxa"], what="dxa")
     if Cb:
-        close(dxb, gxb, what="dxb")
-    close(dg, gg, what="dgamma")
-    close(dbt, gb, what="dbeta")
+        close(got["dxb"], ref["dxb"], what="dxb")
+    close(got["dgamma"], ref["dgamma"], what="dgamma")
+    close(got["dbeta"], ref["dbeta"], what="dbeta")
     if use_film:
-        close(dfilm, gfilm, what="dfilm")
+        close(got["dfilm"], ref["dfilm"], what="dfilm")
 
 
 def test_gn_backward_partner_wait_timeout_gives_the_same_bits(lib, tmp_path):

@@ -6,6 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import fixtures as fx
+from tests import _knobs as K
 
 pytestmark = pytest.mark.gpu
 
@@ -45,30 +46,19 @@ def run(L, fn):
     (2, 64, 0, 192, 64, 64, False),         # three 64-channel blocks
 ])
 def test_conv1x1_reg_vs_fp64_and_tiled_kernel(lib, B, Ca, Cb, Cout, H, W, use_res):
-    tag = f"c1/{B}_{Ca}_{Cb}_{Cout}_{H}_{W}"
-    Cin = Ca + Cb
-    xa = fx.randn(tag + "/xa", B, Ca, H, W)
-    xb = fx.randn(tag + "/xb", B, Cb, H, W) if Cb else None
-    w = fx.randn(tag + "/w", Cout, Cin, 1, 1) / Cin ** 0.5
-    b = fx.randn(tag + "/b", Cout) * 0.1
-    res = fx.randn(tag + "/r", B, Cout, H, W) if use_res else None
-    x = torch.cat([xa, xb], 1) if Cb else xa
-    ref = F.conv2d(x.double(), w.double(), b.double())
-    if use_res:
-        ref = ref + res.double()
-    wpk, bpk = lib.op_pack_conv(dev(w), dev(b))
-    args = (dev(xa), dev(xb) if Cb else None, wpk, bpk, Cout, 1)
-    kw = dict(res=dev(res)) if use_res else {}
-    lib.set_conv1x1_reg(1)
-    got, names = run(lib, lambda: lib.op_conv(*args, **kw))
-    assert "conv1x1_reg_kernel" in names, names
+    shape = (B, Ca, Cb, Cout, H, W, use_res)
+    t = K.c1_inputs(shape)                      # inputs, reference and run shared with the knob tests (tests/_knobs.py)
+    ref = K.c1_reference(t)
+    got, names, (wpk, bpk) = K.run_c1(lib, shape, t, reg=1)
+    # the row names the instantiation as its variant: two 32-channel blocks per wave, 128- or 64-channel workgroups
+    assert K.c1_row(Cout) == f"conv1x1_reg_kernel[<2, {128 if Cout % 128 == 0 else 64}>]" and K.c1_row(Cout) in names, names
+    assert [n for n in names if n.startswith("conv1x1_reg_kernel")] == [K.c1_row(Cout)], names
     torch.testing.assert_close(got.cpu().double(), ref, rtol=1e-4, atol=1e-5)
-    lib.set_conv1x1_reg(0)
-    old, names = run(lib, lambda: lib.op_conv(*args, **kw))
-    lib.set_conv1x1_reg(-1)
-    assert "conv1x1_reg_kernel" not in names, names
+    old, names, _ = K.run_c1(lib, shape, t, reg=0)
+    assert not any(n.startswith("conv1x1_reg_kernel") for n in names), names
     torch.testing.assert_close(got, old, rtol=1e-5, atol=2e-6)
     # a sample's bits do not depend on the batch it is computed in
+    xa, xb, res = t["xa"], t["xb"], t["res"]
     one = lib.op_conv(dev(xa[B - 1:]), dev(xb[B - 1:]) if Cb else None, wpk, bpk, Cout, 1, **(dict(res=dev(res[B - 1:])) if use_res else {}))
     assert torch.equal(one[0], got[B - 1])
 
@@ -83,7 +73,7 @@ def test_conv1x1_reg_leaves_other_shapes_alone(lib):
             wpk, bpk = lib.op_pack_conv(dev(w), None)
             cf = torch.tensor([0.1, 1.2, -0.1, 0.0]).repeat(2, Cin, 1) if coef else None
             y, names = run(lib, lambda: lib.op_conv(dev(x), None, wpk, None, Cout, 1, coef=dev(cf) if coef else None))
-            assert "conv1x1_reg_kernel" not in names, (names, Cin, Cout, H, W)
+            assert not any(n.startswith("conv1x1_reg_kernel") for n in names), (names, Cin, Cout, H, W)
             xr = (x - 0.1) * 1.2 - 0.1 if coef else x
             torch.testing.assert_close(y.cpu().double(), F.conv2d(xr.double(), w.double()), rtol=1e-4, atol=1e-5)
     finally:

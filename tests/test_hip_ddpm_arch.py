@@ -4,12 +4,14 @@ levels, one to three blocks per level, several attention blocks per level, both 
 atol 1e-5 max|ref|), with proof from the profiler rows that the intended path ran (the gn_coef_kernel table path or the fused
 statistics; one attention launch per attention block), batch independence, repeatability on one workspace, and the Winograd /
 input-resident kernel families switched off per plan."""
+import collections
 import functools
 
 import pytest
 import torch
 
 from tests import _ddpm_arch as A
+from tests import _knobs as K
 from tests._ddpm_cond import check_cond_map
 
 pytestmark = pytest.mark.gpu
@@ -89,11 +91,18 @@ def test_the_intended_kernels_ran(tag):
     try:
         call(tag, plan, packed, run)
         torch.cuda.synchronize()
-        rows = {r["name"]: r["launches"] for r in L.prof_report()}
+        report = L.prof_report()
     finally:
         L.prof_enable(False)
+    rows = {r["name"]: r["launches"] for r in report}
     assert ("gn_coef_kernel" in rows) == A.TABLE_PATH[tag], (tag, sorted(rows))
     assert rows.get("attention_kernel", 0) == A.n_attention_blocks(A.ALL[tag]), (tag, rows.get("attention_kernel"))
+    # ... each on the kernel its token count selects (the row's variants; tests/_knobs.py attn_fwd_variant)
+    tokens = A.attention_tokens(A.ALL[tag])
+    assert len(tokens) == A.n_attention_blocks(A.ALL[tag])
+    want = dict(collections.Counter(K.attn_fwd_variant(T) for T in tokens))
+    got = {r["name"]: r.get("variants") for r in report}.get("attention_kernel")
+    assert got == want, (tag, got, want)
     if tag in A.SWITCHED:
         assert any(n.startswith("conv_wino") for n in rows), sorted(rows)
 
