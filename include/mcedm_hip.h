@@ -108,6 +108,23 @@ void mcedm_unet_plan_destroy(mcedm_plan* plan);
 #define MCEDM_VARIANT_CONV_WINO_SPLIT 9 /* 3x3 convs below 32 x 32 on the Winograd kernel with the positions split over the waves (env MCEDM_WINO_SPLIT, default 1); the workspace layout does not depend on it */
 int mcedm_unet_plan_set_variant(mcedm_plan* plan, int which, int value);
 
+/* Dropout of the ADM U-Net's training step (models/adm_blocks.py:170: conv1 reads F.dropout(silu(film(norm1(h))), p, training)).
+ * A setting of the plan, honoured by every training entry -- mcedm_unet_forward[_dx] and mcedm_edm_denoise[_dx] with
+ * training != 0, and every backward entry -- and ignored by training = 0 calls and by every sampler.  0 <= p < 1; p = 0 is "off"
+ * (the state of a new plan; rng_seed is then not kept); p >= 1, negative or NaN, and p > 0 with rng_seed NULL, are
+ * MCEDM_ERR_INVALID.  rng_seed: DEVICE memory, one 64-bit seed, read by the kernels when the forward runs (like every `_rng`
+ * entry's); the forward copies the value it used into the workspace, on the stream, and the backward regenerates its masks from
+ * that copy, so the host may rewrite *rng_seed between the two.
+ * The mask contract.  Block j is the 0-based position of a block in the order the network runs them (encoder blocks, then decoder
+ * blocks); its mask covers conv1's input [B, cout, H, W].  With u = what mcedm_uniform_fill(u, B * cout * H * W, rng_seed,
+ * draw = j) writes, element e = ((b * cout + c) * H + y) * W + x is KEPT iff u[e] >= (float)p; a kept value is multiplied by
+ * 1.0f / (1.0f - (float)p) in fp32, a dropped value is exactly 0.0f (also where the activation is NaN or Inf: torch multiplies by
+ * zero there and keeps the NaN).  The kernels generate u in registers, one Philox block per four consecutive elements, and never
+ * read a mask tensor.  The training workspace grows by one conv1-input-sized tensor per block (256-byte aligned) and a 256-byte
+ * seed slot while p > 0: mcedm_unet_workspace_bytes(training = 1) reports it; at p = 0, and for training = 0 at any p, every size
+ * is what it was. */
+int mcedm_unet_plan_set_dropout(mcedm_plan* plan, double p, const uint64_t* rng_seed);
+
 /* Parameter table in DhariwalUNet.state_dict() order (parameters only, no buffers).
  * name is owned by the plan. */
 int mcedm_unet_param_count(const mcedm_plan* plan);
@@ -587,6 +604,14 @@ int mcedm_op_ddim_cond_step_guided(const float* xt, const float* F, const float*
                                    float c2, float* xt_next, float* condp, float* condp_u, int cond_channels, int plan_cond_channels,
                                    int B, int C, int H, int W, float* xs, int T_xs, int t_xs, float* x0s, int T_x0, int t_x0,
                                    void* stream);
+/* The two kernels of the training step's dropout (mcedm_unet_plan_set_dropout states the mask contract) on caller-owned tensors:
+ *   out = mask * s * silu((h - mean) * scale + offset)   h, out [B, C, H, W]; coef [coef_batch ? B : 1][C] rows (mean, scale,
+ *                                                        offset, pad), NULL = identity rows
+ *   g   = mask * s * g                                   in place, g [B, C, H, W]
+ * with mask and s = 1 / (1 - p) of draw `draw` keyed by *rng_seed (device memory).  0 < p < 1. */
+int mcedm_op_dropout_act(const float* h, const mcedm_coef* coef, int coef_batch, float* out, int B, int C, int H, int W, double p,
+                         const uint64_t* rng_seed, uint64_t draw, void* stream);
+int mcedm_op_dropout_scale(float* g, int B, int C, int H, int W, double p, const uint64_t* rng_seed, uint64_t draw, void* stream);
 /* Test hook: force the conv tile (channel tile mt in {32,64,128}, pixel tile ph x pw in {8x32,8x16,16x16,8x8};
  * (128,16,32) = the 8-wave kernel, 3x3 only);
  * (0,0,0) restores the size heuristic.  Process-global, not thread-safe. */

@@ -10,8 +10,10 @@ not module by module.  ``dx_cond`` (the network conditioned on the PDE-residual 
 ``cat_dx=False`` (``dx_enc`` = Conv3x3 -> GELU -> Conv3x3 and ``combine_enc``).  ``self_cond`` (adm_blocks.py:227-238,
 318-331) runs as the cat_cond network whose conditioning input is cat(cond, x_self_cond), with or without dx_cond: the input
 order is cat(cond, x_self_cond, x, dx).  Configurations outside the hot path
-(cond_enc / class or augment labels / dropout) raise NotImplementedError instead of silently computing
-something else.  There is no PyTorch fallback: without the HIP library or on a CPU tensor, forward raises.
+(cond_enc / class or augment labels) raise NotImplementedError instead of silently computing
+something else.  ``hparams.model.dropout`` (adm_blocks.py:170) acts in the fused training losses while the module is in ``train()``
+mode: the masks are generated on the device from a seed the loss draws once per step (``arm_dropout``); ``forward``, the samplers,
+the EMA copy and a module in ``eval()`` never drop.  There is no PyTorch fallback: without the HIP library or on a CPU tensor, forward raises.
 """
 from __future__ import annotations
 
@@ -101,8 +103,10 @@ class DhariwalUNet(nn.Module):
         self_cond = bool(_get(m, "self_cond", False))
         if m.augment_dim or m.label_dim:
             unsupported.append("augment_dim/label_dim")
-        if m.dropout:
-            unsupported.append("dropout")
+        # adm_blocks.py:170: every UNetBlock drops conv1's input with probability p while the module is in train() mode
+        p = float(m.dropout or 0.0)
+        if not (0.0 <= p < 1.0):                           # also NaN
+            raise ValueError(f"hparams.model.dropout must lie in [0, 1), got {m.dropout}")
         cond_channels = _get(m, "cond_channels", 0)
         if cond_channels > 0 and not _get(m, "cat_cond", False):
             unsupported.append("cond_enc (cat_cond=False)")
@@ -127,6 +131,7 @@ class DhariwalUNet(nn.Module):
         self.cat_condition = True
         self.self_condition = self_cond
         self.label_dropout = m.label_dropout
+        self.dropout = p
         # conv_in reads cat(cond, x_self_cond, x) (adm_blocks.py:318-331): to the HIP plan that is the cat_cond network with
         # cond' = cat(cond, x_self_cond), cond_channels + in_channels wide -- the same parameter table
         self.plan_cond_channels = cond_channels + (m.in_channels if self_cond else 0)
@@ -176,6 +181,7 @@ class DhariwalUNet(nn.Module):
         self._packed: Optional[torch.Tensor] = None
         self._packed_key = None
         self._ws = _lib.Workspace()
+        self._drop_seed: Optional[torch.Tensor] = None      # int64 [1] on the device: the key of this step's dropout masks
 
     # ---- HIP plumbing -------------------------------------------------------------------------------
     @property
@@ -186,6 +192,22 @@ class DhariwalUNet(nn.Module):
             if names != self._plan.param_names:
                 raise RuntimeError("parameter table of the HIP plan and of the module disagree")
         return self._plan
+
+    def arm_dropout(self, draw_seed) -> None:
+        """Called by a training loss right before its forward, after the step's other random draws.  Dropout is on iff
+        ``self.dropout > 0`` and the module is in ``train()`` mode (the reference's ``training=self.training``): then
+        ``draw_seed()`` -- one draw from torch's CPU generator -- keys this step's masks, and the plan is told when what it holds
+        (``Plan.dropout``, its seed tensor) differs.  With dropout off nothing is drawn."""
+        on = self.dropout > 0.0 and self.training
+        if on:
+            dev = next(self.parameters()).device
+            if self._drop_seed is None or self._drop_seed.device != dev:
+                self._drop_seed = torch.zeros(1, dtype=torch.int64, device=dev)
+            _lib._write_seed(self._drop_seed, draw_seed())
+        want = (self.dropout, self._drop_seed) if on else (0.0, None)
+        plan = self.plan
+        if plan.dropout != want[0] or plan._dropout_seed is not want[1]:
+            plan.set_dropout(*want)
 
     def named_param_dict(self) -> Dict[str, torch.Tensor]:
         return dict(self.named_parameters())

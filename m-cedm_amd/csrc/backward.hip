@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "bwd.hpp"
+#include "edm.hpp"
 #include "plan.hpp"
 
 namespace mcedm {
@@ -220,14 +221,21 @@ static int block_backward(Ctx& c, const BlockP& b, const BlockLayout& bl) {
   }
   // y = conv1(silu(film(norm1(h)))) + skip(x)
   if ((rc = dgrad(c, b.conv1, dy, H, W, dact))) return rc;
+  // dropout: conv1 read xd1 = mask * s * silu(.), so its data gradient passes the same mask and scale (regenerated from the seed the
+  // forward left in the workspace) on its way to the GroupNorm backward, which differentiates the undropped silu as ever
+  const bool drop = bl.xd1 >= 0;
+  if (drop && (rc = launch_dropout_scale(dact, (size_t)B * b.cout * H * W, c.P.dropout_p, c.net.seed_slot(),
+                                         (unsigned long long)bl.draw, c.s))) return rc;
   const float* film = c.net.film() + b.film_row0;
   GnBwdArgs g1{dact, RS_NONE, c.T(bl.h), nullptr, b.cout, 0, H, W, B, b.norm1.groups, c.CF(bl.coef1), c.T(bl.stats1),
                c.pk + b.norm1.gamma, film, c.net.coef_batch(), c.P.film_rows, 1, c.G(bl.h), nullptr, 0, nullptr, 0, 0,
-               c.X(c.S.ab), c.X(c.S.xact)};
+               c.X(c.S.ab), drop ? nullptr : c.X(c.S.xact)};
   if ((rc = launch_gn_bwd(with_sync(c, g1), c.s))) return rc;
   if ((rc = norm_param_grads(c, b.norm1, film, c.P.film_rows, c.X(c.S.dfilm) + b.film_row0))) return rc;
+  // conv1's weight gradient: its operand is what the GroupNorm backward just wrote, or -- dropout -- the forward's saved xd1, which
+  // stands in the same place (a materialised input that is not the start of an allocation; nothing is written to it)
   WgradArgs w1{dy, c.T(bl.h), nullptr, b.cout, 0, c.CF(bl.coef1), 1, 1, RS_NONE, H, W, H, W, b.cout, B, wg, nullptr};
-  if ((rc = launch_wgrad(w1, 9, c.grads[b.conv1.w], c.grads[b.conv1.b], 0, c.X(c.S.xact), c.s, true))) return rc;
+  if ((rc = launch_wgrad(w1, 9, c.grads[b.conv1.w], c.grads[b.conv1.b], 0, drop ? c.T(bl.xd1) : c.X(c.S.xact), c.s, true))) return rc;
   // skip path -> extra gradient for x
   const float* add = dy;
   int add_mode = 1;

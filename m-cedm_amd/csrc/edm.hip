@@ -6,6 +6,7 @@
 // term, so this file is compiled with -ffp-contract=off (see build.py).
 #include "common.hpp"
 #include "edm.hpp"
+#include "prof.hpp"
 
 namespace mcedm {
 
@@ -278,6 +279,94 @@ int launch_uniform_fill(float* out, const unsigned long long* seed_dev, unsigned
   const size_t n4 = (reinterpret_cast<size_t>(out) & 15) == 0 ? total / 4 : 0;
   hipLaunchKernelGGL(uniform_fill_kernel, dim3(grid_for(n4 ? n4 : total)), dim3(256), 0, s, out, seed_dev, draw, n4, total);
   MCEDM_LAUNCH_CHECK("uniform_fill_kernel");
+  return MCEDM_OK;
+}
+
+// ---- training-step dropout of the ADM U-Net (models/adm_blocks.py:170; the contract: mcedm_unet_plan_set_dropout) -------------
+// keep iff u >= p; kept values times s = 1 / (1 - p), dropped values exactly zero.  Both kernels generate u themselves: one Philox
+// block per 16-byte group, uniform_element for whatever a scalar path touches -- the value of an element never depends on the path.
+__device__ __forceinline__ float drop_keep(float v, float u, float p, float s) { return u >= p ? v * s : 0.0f; }
+__device__ __forceinline__ float drop_silu(float v, const Coef& c) {      // apply_coef's operations (conv_tile.hpp), SiLU on
+  const float t = (v - c.mean) * c.scale + c.offset;
+  return t * __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+}
+// out = mask * s * silu(coef(h)): conv1's input of a dropout block.  grid = (planes, chunks of a plane) as act_materialize_kernel:
+// one transform row per workgroup and 32-bit index arithmetic; plane (n, c) starts at element (n C + c) HW of the mask.  vec: HW % 4
+// == 0 and 16-byte aligned tensors -- every group of four lies inside one plane; otherwise (15-pixel planes) element by element.
+__global__ __launch_bounds__(256) void dropout_act_kernel(const float* __restrict__ h, const Coef* __restrict__ coef, int coef_batch,
+                                                          int C, unsigned HW, float p, float s,
+                                                          const unsigned long long* __restrict__ seed_dev, unsigned long long draw,
+                                                          float* __restrict__ out, int vec) {
+  const unsigned long long seed = *seed_dev;
+  const int n = blockIdx.x / C, c = blockIdx.x - n * C;
+  Coef cf{0.f, 1.f, 0.f, 0.f};
+  if (coef) cf = coef[(coef_batch ? (size_t)n * C : 0) + c];
+  const size_t e0 = (size_t)blockIdx.x * HW;
+  const float* src = h + e0;
+  float* dst = out + e0;
+  if (vec) {
+    const unsigned nq = HW / 4;
+    const size_t g0 = e0 / 4;
+    for (unsigned q = blockIdx.y * 256u + threadIdx.x; q < nq; q += gridDim.y * 256u) {
+      const float4 v = reinterpret_cast<const float4*>(src)[q], u = uniform_group(seed, draw, g0 + q);
+      float4 r;
+      r.x = drop_keep(drop_silu(v.x, cf), u.x, p, s);
+      r.y = drop_keep(drop_silu(v.y, cf), u.y, p, s);
+      r.z = drop_keep(drop_silu(v.z, cf), u.z, p, s);
+      r.w = drop_keep(drop_silu(v.w, cf), u.w, p, s);
+      reinterpret_cast<float4*>(dst)[q] = r;
+    }
+  } else {
+    for (unsigned i = blockIdx.y * 256u + threadIdx.x; i < HW; i += gridDim.y * 256u)
+      dst[i] = drop_keep(drop_silu(src[i], cf), uniform_element(seed, draw, e0 + i), p, s);
+  }
+}
+static int dropout_check_p(const char* who, double p) {
+  MCEDM_REQUIRE(p > 0.0 && (float)p < 1.0f, "%s: p=%g must lie in (0, 1)", who, p);
+  return MCEDM_OK;
+}
+int launch_dropout_act(const float* h, const Coef* coef, int coef_batch, float* out, int B, int C, int H, int W, double p,
+                       const unsigned long long* seed_dev, unsigned long long draw, hipStream_t s) {
+  MCEDM_REQUIRE(h && out && seed_dev && B > 0 && C > 0 && H > 0 && W > 0, "dropout_act: bad arguments");
+  if (const int rc = dropout_check_p("dropout_act", p)) return rc;
+  MCEDM_REQUIRE((size_t)B * C < (1ull << 31) && (size_t)H * W < (1ull << 31), "dropout_act: shape out of range");
+  const unsigned HW = (unsigned)H * (unsigned)W;
+  const int vec = HW % 4 == 0 && ((reinterpret_cast<size_t>(h) | reinterpret_cast<size_t>(out)) & 15) == 0;
+  const unsigned per = vec ? HW / 4 : HW;
+  int by = (int)((per + 1023) / 1024);                        // four trips per thread
+  if (by < 1) by = 1;
+  if (by > 64) by = 64;
+  const float pf = (float)p;
+  const double total = (double)B * C * HW;
+  ProfScope ps("dropout_act_kernel", 14.0 * total, 8.0 * total, s);
+  hipLaunchKernelGGL(dropout_act_kernel, dim3((unsigned)(B * C), (unsigned)by), dim3(256), 0, s, h, coef, coef_batch, C, HW, pf,
+                     1.0f / (1.0f - pf), seed_dev, draw, out, vec);
+  MCEDM_LAUNCH_CHECK("dropout_act_kernel");
+  return MCEDM_OK;
+}
+// g = mask * s * g in place (the data gradient of conv1 on its way to the GroupNorm backward): n4 full groups as float4 (g 16-byte
+// aligned), the rest element by element
+__global__ __launch_bounds__(256) void dropout_scale_kernel(float* __restrict__ g, float p, float s,
+                                                            const unsigned long long* __restrict__ seed_dev, unsigned long long draw,
+                                                            size_t n4, size_t total) {
+  const unsigned long long seed = *seed_dev;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t q = tid; q < n4; q += stride) {
+    const float4 v = reinterpret_cast<const float4*>(g)[q], u = uniform_group(seed, draw, q);
+    reinterpret_cast<float4*>(g)[q] = make_float4(drop_keep(v.x, u.x, p, s), drop_keep(v.y, u.y, p, s), drop_keep(v.z, u.z, p, s),
+                                                  drop_keep(v.w, u.w, p, s));
+  }
+  for (size_t i = 4 * n4 + tid; i < total; i += stride) g[i] = drop_keep(g[i], uniform_element(seed, draw, i), p, s);
+}
+int launch_dropout_scale(float* g, size_t total, double p, const unsigned long long* seed_dev, unsigned long long draw, hipStream_t s) {
+  MCEDM_REQUIRE(g && seed_dev && total > 0, "dropout_scale: bad arguments");
+  if (const int rc = dropout_check_p("dropout_scale", p)) return rc;
+  const size_t n4 = (reinterpret_cast<size_t>(g) & 15) == 0 ? total / 4 : 0;
+  const float pf = (float)p;
+  ProfScope ps("dropout_scale_kernel", 12.0 * (double)total, 8.0 * (double)total, s);
+  hipLaunchKernelGGL(dropout_scale_kernel, dim3(grid_for(n4 ? n4 : total)), dim3(256), 0, s, g, pf, 1.0f / (1.0f - pf), seed_dev, draw,
+                     n4, total);
+  MCEDM_LAUNCH_CHECK("dropout_scale_kernel");
   return MCEDM_OK;
 }
 

@@ -24,6 +24,13 @@ int launch_normal_fill(double* out, const unsigned long long* seed_dev, unsigned
 // out[e] = U[0, 1) in fp32, (word >> 8) * 2^-24 with word e % 4 of the Philox block at counter (e / 4, draw | 2^63): the draws of
 // the DDIM step kernels (launch_ddim_next_rng, DdimCondStep::seed), disjoint from the normal generator's blocks
 int launch_uniform_fill(float* out, const unsigned long long* seed_dev, unsigned long long draw, size_t total, hipStream_t s);
+// Training-step dropout (mcedm_unet_plan_set_dropout): element e of [B, C, H, W] is kept iff u[e] >= (float)p, u = draw `draw` of
+// launch_uniform_fill; kept values times 1.0f / (1.0f - (float)p), dropped values exactly 0.0f.
+//   out = mask * s * silu((h - mean) * scale + offset), one coef row per (sample, channel) (coef_batch) or per channel; null = identity
+int launch_dropout_act(const float* h, const Coef* coef, int coef_batch, float* out, int B, int C, int H, int W, double p,
+                       const unsigned long long* seed_dev, unsigned long long draw, hipStream_t s);
+//   g = mask * s * g in place
+int launch_dropout_scale(float* g, size_t total, double p, const unsigned long long* seed_dev, unsigned long long draw, hipStream_t s);
 // dxg / wgt / gdiv: optional PDE-guidance term of the single-task sampler, d -= (double)((wgt * dxg) / gdiv) formed in fp32
 // (models/ddim.py:1577-1579, 1590-1591: `weight * dx / t_hat`, with t_hat in BOTH stages)
 int launch_heun_euler(const double* x_hat, const float* D, const float* mask, double t_hat, double dt, size_t total,

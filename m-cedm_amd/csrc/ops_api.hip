@@ -439,3 +439,16 @@ extern "C" int mcedm_op_ddim_cond_step_guided(const float* xt, const float* F, c
   return op_ddim_cond_step(xt, F, Fu, noise, rng_seed, draw, w, s0, s1, sa_next, c1, c2, xt_next, condp, condp_u, cond_channels,
                            plan_cond_channels, B, C, H, W, xs, T_xs, t_xs, x0s, T_x0, t_x0, stream, dx, gw);
 }
+
+// the two kernels of the training step's dropout (edm.hip) on caller-owned tensors
+extern "C" int mcedm_op_dropout_act(const float* h, const mcedm_coef* coef, int coef_batch, float* out, int B, int C, int H, int W,
+                                    double p, const uint64_t* rng_seed, uint64_t draw, void* stream) {
+  return launch_dropout_act(h, reinterpret_cast<const Coef*>(coef), coef_batch, out, B, C, H, W, p,
+                            reinterpret_cast<const unsigned long long*>(rng_seed), draw, (hipStream_t)stream);
+}
+extern "C" int mcedm_op_dropout_scale(float* g, int B, int C, int H, int W, double p, const uint64_t* rng_seed, uint64_t draw,
+                                      void* stream) {
+  MCEDM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "op_dropout_scale: empty shape");
+  return launch_dropout_scale(g, (size_t)B * C * H * W, p, reinterpret_cast<const unsigned long long*>(rng_seed), draw,
+                              (hipStream_t)stream);
+}

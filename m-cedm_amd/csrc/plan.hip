@@ -93,6 +93,14 @@ extern "C" int mcedm_version(void) { return MCEDM_ABI_VERSION; }
 extern "C" int mcedm_unet_plan_set_variant(mcedm_plan* plan, int which, int value) {
   return plan_set_variant(plan, "plan_set_variant", which, value);
 }
+extern "C" int mcedm_unet_plan_set_dropout(mcedm_plan* plan, double p, const uint64_t* rng_seed) {
+  MCEDM_REQUIRE(plan, "plan_set_dropout: null plan");
+  MCEDM_REQUIRE(p >= 0.0 && (float)p < 1.0f, "plan_set_dropout: p=%g must lie in [0, 1)", p);      // (NaN fails the first test)
+  MCEDM_REQUIRE(p == 0.0 || rng_seed, "plan_set_dropout: p=%g > 0 needs the device address of a seed", p);
+  plan->dropout_p = p;
+  plan->dropout_seed = p > 0.0 ? reinterpret_cast<const unsigned long long*>(rng_seed) : nullptr;
+  return MCEDM_OK;
+}
 extern "C" const char* mcedm_last_error(void) { return g_err; }
 
 extern "C" int mcedm_unet_plan_create(const mcedm_unet_desc* d, mcedm_plan** out) {
@@ -559,6 +567,18 @@ int build_layout(const mcedm_plan& P, int B, int H, int W, int training, int n_n
   L.last = cur;
   L.coef_out = lb.coef(P.out_norm.C);
   if (training) L.stats_out = lb.stats(P.out_norm.groups);
+  // dropout (mcedm_unet_plan_set_dropout): every block's conv1 reads a materialised input, kept for its weight gradient, and the
+  // backward finds the forward's seed in a slot of its own.  Behind every other tensor: with the plan's p = 0 nothing moves.
+  if (training && P.dropout_p > 0.0) {
+    size_t j = 0;
+    for (auto* v : {&P.enc, &P.dec})
+      for (const BlockP& b : *v) {
+        BlockLayout& bl = L.blocks[j];
+        bl.draw = (int)j++;
+        bl.xd1 = lb.act(b.cout, bl.H, bl.W);
+      }
+    L.seed = lb.make(1, 1, 1, sizeof(unsigned long long));
+  }
   L.total_bytes = lb.pool.peak;
   return MCEDM_OK;
 }
@@ -677,7 +697,12 @@ int AdmNet::run_block(const BlockP& b, const BlockLayout& bl, std::vector<SumTil
     c1.sk_wpk = pk + b.skip.wpk; c1.sk_bias = pk + b.skip.bias;
     c1.sk_wfrag = b.skip.wfrag != NONE ? pk + b.skip.wfrag : nullptr;
   }
-  if ((rc = gn_for_conv(g1, c1, false, s))) return rc;
+  if ((rc = gn_for_conv(g1, c1, /*need_table=*/bl.xd1 >= 0, s))) return rc;
+  if (bl.xd1 >= 0) {          // dropout: xd1 = mask * s * silu(film(norm1(h))) by one pass, and conv1 on it as conv0 on a down block's xd
+    if ((rc = launch_dropout_act(T(bl.h), c1.coef, 1, T(bl.xd1), B, b.cout, bl.H, bl.W, P.dropout_p, seed_slot(),
+                                 (unsigned long long)bl.draw, s))) return rc;
+    c1.xa = T(bl.xd1); c1.coef = nullptr; c1.act = 0;
+  }
   if ((rc = launch_conv(c1, 9, s))) return rc;
   if (!b.attn) return MCEDM_OK;
   // attention: z = proj(attn(qkv(norm2(y)))) + y
@@ -729,6 +754,9 @@ int AdmNet::forward(const AdmIn& in, float* out) const {
   EmbArgs e{in.noise_labels, n_noise, ch, pk + P.freqs, pk + P.w0, pk + P.b0, pk + P.w1, pk + P.b1,
             pk + P.waff, pk + P.baff, P.film_rows, nullptr, T(L.film)};
   if ((rc = launch_embedding(e, s))) return rc;
+  // dropout: the seed of this pass goes into the workspace, on the stream; this pass's kernels and the backward's read it there
+  if (dropout())
+    MCEDM_HIP_TRY(hipMemcpyAsync(act + L.t[L.seed].off, P.dropout_seed, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
   std::vector<SumTiles> st(L.t.size());     // tiling of each tensor's fused-statistics table
   // conv_in on cat(cond, x)  (cond FIRST, adm_blocks.py:332)
   const float* xb = in.x;

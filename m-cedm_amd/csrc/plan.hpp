@@ -151,6 +151,8 @@ struct BlockLayout {
   int stats0 = -1, stats1 = -1, stats2 = -1;
   int xd = -1;                 // down blocks: the activated, 2x2-averaged input of conv0 (temporary)
   int out = -1;                // y or z
+  int xd1 = -1;                // dropout (training, plan->dropout_p > 0): conv1's materialised input mask * s * silu(film(norm1(h)))
+  int draw = 0;                // 0-based position in the order the blocks run (enc then dec): the draw index of the block's mask
   int wfold = 0;               // conv1 (Winograd kernel, SKIP variant) computes the 1x1 skip projection itself; `sk` stays reserved
   int Hin = 0, Win = 0, H = 0, W = 0;
 };
@@ -165,6 +167,7 @@ struct Layout {
   size_t sums_base = 0, sums_bytes = 0;   // arena of all fused-statistics tables
   size_t total_bytes = 0;
   bool training = false;       // laid out for training (build_layout)
+  int seed = -1;               // dropout: the 8-byte seed the forward used, kept for the backward (behind every other tensor)
 };
 
 }  // namespace mcedm
@@ -184,6 +187,9 @@ struct mcedm_plan {
   size_t packed_floats = 0;
   int levels_div = 1;          // 2^(n_levels-1)
   mcedm::KernelVariants variants;   // per-plan kernel choices (mcedm_unet_plan_set_variant); -1 = process default
+  // training-step dropout (mcedm_unet_plan_set_dropout): probability, 0 = off, and the DEVICE address of the 64-bit seed
+  double dropout_p = 0.0;
+  const unsigned long long* dropout_seed = nullptr;
 };
 
 namespace mcedm {
@@ -231,6 +237,8 @@ struct AdmNet {
   hipStream_t s = nullptr;
 
   int coef_batch() const { return n_noise > 1 ? 1 : 0; }      // per-sample rows (film, coef_in) with one label per sample
+  bool dropout() const { return L.seed >= 0; }                // this layout carries the dropout tensors (training, p > 0)
+  const unsigned long long* seed_slot() const { return reinterpret_cast<const unsigned long long*>(act + L.t[L.seed].off); }
   float* T(int id) const { return id < 0 ? nullptr : reinterpret_cast<float*>(act + L.t[id].off); }
   Coef* CF(int id) const { return id < 0 ? nullptr : reinterpret_cast<Coef*>(act + L.t[id].off); }
   float* SUMS(int id) const { return (id < 0 || L.t[id].sums == NONE) ? nullptr : reinterpret_cast<float*>(act + L.t[id].sums); }

@@ -892,6 +892,7 @@ def _eps_train_loss(module, x_noise, labels, cond, noise, dx=None):
     (mcedm_unet_forward, mcedm_eps_loss, mcedm_unet_backward; with dx_cond mcedm_unet_forward_dx and mcedm_unet_backward_dx, dx
     being the network's dx input of this batch or None)."""
     net: DhariwalUNet = module.model
+    net.arm_dropout(module._draw_seed)      # dropout in train() mode: this step's seed, after the reference's own draws
 
     def run():
         F = net.plan.forward(net.packed_weights(), x_noise, labels, cond=cond, ws=module._train_ws, training=True, dx=dx)

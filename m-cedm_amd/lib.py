@@ -311,6 +311,24 @@ class Plan(_PlanBase):
         check(lib.mcedm_unet_plan_create(C.byref(d), C.byref(h)), "plan_create")
         self._adopt(lib, h)
         self.in_channels, self.cond_channels, self.out_channels = in_channels, cond_channels, out_channels
+        self.dropout, self._dropout_seed = 0.0, None           # what set_dropout last told the plan
+
+    def set_dropout(self, p: float, rng_seed: Optional[torch.Tensor] = None) -> None:
+        """Dropout of this plan's training entries (mcedm_unet_plan_set_dropout): 0 <= p < 1, p = 0 switches it off.  rng_seed: a
+        one-element int64 DEVICE tensor the kernels read when the forward runs; the plan keeps a reference to it.  training=False
+        calls and every sampler ignore the setting.  ``self.dropout`` / ``self._dropout_seed`` hold what the plan was last told."""
+        p = float(p)
+        if not (0.0 <= p < 1.0):                       # also NaN
+            raise ValueError(f"dropout must lie in [0, 1), got {p}")
+        if p > 0.0 and rng_seed is None:
+            raise ValueError("dropout > 0 needs rng_seed, a one-element int64 tensor on the device")
+        ptr = None
+        if p > 0.0:
+            if rng_seed.dtype != torch.int64 or rng_seed.numel() != 1:
+                raise RuntimeError("set_dropout: rng_seed must be a one-element int64 tensor on the device")
+            ptr = _ptr(rng_seed, torch.int64)
+        check(self._lib.mcedm_unet_plan_set_dropout(self._h, p, ptr), "plan_set_dropout")
+        self.dropout, self._dropout_seed = p, (rng_seed if p > 0.0 else None)
 
     # ---- derived weights ---------------------------------------------------------------
     def pack(self, params: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1655,3 +1673,24 @@ def op_ddim_cond_step(xt, F, s0, s1, sa_next, c2, Fu=None, w=0.0, noise=None, c1
         return xt_next
     check(lib.mcedm_op_ddim_cond_step(_ptr(xt), _ptr(F), _ptr(Fu), _ptr(noise), *args, _stream()), "op_ddim_cond_step")
     return xt_next
+
+
+def op_dropout_act(h, p, rng_seed, draw, coef=None, coef_batch=1):
+    """out = mask * s * silu((h - mean) * scale + offset) (mcedm_op_dropout_act): h [B, C, H, W]; coef [B or 1, C, 4] rows (mean, scale,
+    offset, pad) or None (identity); the mask and s = 1 / (1 - p) of draw ``draw`` of the uniform generator keyed by rng_seed
+    (int64 [1] on the device), as mcedm_unet_plan_set_dropout states them."""
+    lib = _bind_ops()
+    B, Cc, H, W = h.shape
+    out = torch.empty_like(h)
+    check(lib.mcedm_op_dropout_act(_ptr(h), _ptr(coef), int(coef_batch), _ptr(out), B, Cc, H, W, float(p),
+                                   _seed_ptr(rng_seed, h.device, "op_dropout_act"), int(draw), _stream()), "op_dropout_act")
+    return out
+
+
+def op_dropout_scale(g, p, rng_seed, draw):
+    """g <- mask * s * g in place (mcedm_op_dropout_scale), g [B, C, H, W]; returns g."""
+    lib = _bind_ops()
+    B, Cc, H, W = g.shape
+    check(lib.mcedm_op_dropout_scale(_ptr(g), B, Cc, H, W, float(p), _seed_ptr(rng_seed, g.device, "op_dropout_scale"), int(draw),
+                                     _stream()), "op_dropout_scale")
+    return g

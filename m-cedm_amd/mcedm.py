@@ -37,6 +37,9 @@ def _edm_train_loss(module, x, x_noise, sigma, cond, mask, dx, extra=None):
     extra(D, dD, loss) -> loss: a further term of the loss in D (the PDE residual of PlCondEdm.training_step); it adds its
     gradient to dD in place and returns the total, and the backward from dD is the same."""
     net: DhariwalUNet = module.model
+    # hparams.model.dropout in train() mode: one seed per step, drawn AFTER the reference's own draws of the step (noise,
+    # rnd_normal, the dx / cond_p torch.rand's), so a dropout = 0 run with the same torch.manual_seed sees the same data noise
+    net.arm_dropout(module._draw_seed)
 
     def run():
         D = net.plan.denoise(net.packed_weights(), x_noise, sigma, cond=cond, ws=module._train_ws, training=True,

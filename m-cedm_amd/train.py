@@ -2,6 +2,7 @@
 
 One process per GPU.  Per step (models/mcedm.py:254-281 + Lightning's DDP / clip / Adam / EmaModel.update):
 
+    dropout seed        <- one draw of torch's CPU generator   (only with dropout > 0 in training mode; written to the device)
     x_noise, sigma      <- mcedm_edm_noise_inputs            (HIP)
     D                   <- mcedm_edm_denoise(training)        (HIP, activations kept in the workspace)
     loss, dD            <- mcedm_edm_loss                     (HIP)
@@ -18,6 +19,12 @@ Reproducibility: no kernel of the step uses atomics -- the weight-gradient kerne
 split and reduced in a fixed order (csrc/wgrad_mfma.hip) -- so the same inputs give the same bits, run after run
 (tests/test_hip_backward.py::test_training_step_is_bitwise_reproducible); inference / sampling is additionally
 bit-identical under batch sharding (tests/test_hip_fullsize.py).
+
+Dropout (``hparams.model.dropout`` > 0): the masks are a function of (seed, block, element index) alone, generated inside the
+kernels (mcedm_unet_plan_set_dropout).  Under DDP each rank draws the step's seed from its OWN torch generator, after the data noise
+of the step: ranks seeded identically (``seed_everything`` with one value) get identical masks on their different shards, ranks
+seeded apart get different ones -- exactly what torch's dropout does in the reference under the same seeding.  The EMA copy and
+every evaluation path never drop.
 """
 from __future__ import annotations
 
@@ -172,8 +179,12 @@ class FlatTrainState:
 
     def __init__(self, plan: "_lib.Plan", params: Dict[str, torch.Tensor], packed: Optional[torch.Tensor] = None,
                  ema: Optional[Dict[str, torch.Tensor]] = None, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
-                 clip=1.0, ema_beta=0.999, P_mean=-1.2, P_std=1.2, sigma_data=1.0, max_buckets: int = 4):
+                 clip=1.0, ema_beta=0.999, P_mean=-1.2, P_std=1.2, sigma_data=1.0, max_buckets: int = 4, dropout: float = 0.0):
         self.plan = plan
+        # dropout of the training forward (Plan.set_dropout): on while ``self.training``; one seed per step in ``drop_seed``
+        if not (0.0 <= float(dropout) < 1.0):
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
+        self.dropout, self.training = float(dropout), True
         names = plan.param_names
         tens = [params[n] for n in names]
         self.hp = dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, max_norm=clip, ema_beta=ema_beta)
@@ -193,6 +204,7 @@ class FlatTrainState:
         self.red_scratch = (torch.empty(_lib.REDUCE_SCRATCH_BYTES, dtype=torch.uint8, device=self.flat_p.device)
                             if self.flat_p.is_cuda else None)
         self.step_count = 0
+        self.drop_seed = torch.zeros(1, dtype=torch.int64, device=self.flat_p.device) if self.dropout > 0 else None
         self.ws = _lib.Workspace()
         self.packed = packed
         self.world = _world()
@@ -302,11 +314,28 @@ class FlatTrainState:
             raise RuntimeError(f"optimizer state: parameters disagree on the step count ({sorted(steps)})")
         self.step_count = steps.pop()
 
+    @staticmethod
+    def _draw_seed():
+        """The key of one step's dropout masks, from torch's CPU generator (pl_base._PlBase._draw_seed)."""
+        return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+    def _arm_dropout(self) -> None:
+        """Before the step's forward: with dropout on, draw this step's seed into the device scalar the kernels read (a captured
+        step replays with it); tell the plan when what it holds differs (a captured step is then captured again)."""
+        on = self.dropout > 0.0 and self.training
+        if on:
+            _lib._write_seed(self.drop_seed, self._draw_seed())
+        want = (self.dropout, self.drop_seed) if on else (0.0, None)
+        if getattr(self.plan, "dropout", 0.0) != want[0] or getattr(self.plan, "_dropout_seed", None) is not want[1]:
+            self.plan.set_dropout(*want)
+            self._graph = None
+
     def step(self, x, cond_in, mask, noise, rnd_normal, dx_fn=None, exchange: bool = True):
         """One optimisation step on this rank's shard (all tensors NCHW fp32 on the device). Returns the local loss (a
         tensor that the next step overwrites when the step is graph-replayed).  dx_fn: see _forward_backward (such steps are
         launched eagerly: the callable is the caller's code).  exchange=False skips the gradient all-reduce (measurement
         only -- bench.py separates compute from exchange with it; the replicas then drift apart)."""
+        self._arm_dropout()
         if self.use_graph and self.world == 1 and x.is_cuda and dx_fn is None:
             loss = self._graphed_forward_backward(x, cond_in, mask, noise, rnd_normal)
         else:
@@ -327,6 +356,7 @@ class EdmTrainer(FlatTrainState):
 
     def __init__(self, module, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, clip=1.0, ema_beta=0.999,
                  P_mean=-1.2, P_std=1.2, sigma_data=1.0, max_buckets: int = 4):
+        """The network's ``dropout`` is taken over; it acts while ``module.model`` is in ``train()`` mode."""
         self.module = module
         self.net = module.model
         net = self.net
@@ -335,7 +365,7 @@ class EdmTrainer(FlatTrainState):
         ema = dict(ema_net.named_parameters()) if ema_net is not None else None
         super().__init__(net.plan, params, packed=None, ema=ema, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
                          weight_decay=weight_decay, clip=clip, ema_beta=ema_beta, P_mean=P_mean, P_std=P_std,
-                         sigma_data=sigma_data, max_buckets=max_buckets)
+                         sigma_data=sigma_data, max_buckets=max_buckets, dropout=getattr(net, "dropout", 0.0))
         with torch.no_grad():
             for n, p in params.items():
                 p.data = self.pviews[n]
@@ -344,6 +374,7 @@ class EdmTrainer(FlatTrainState):
                     p.data = v
 
     def step(self, x, cond_in, mask, noise, rnd_normal, dx_fn=None):
+        self.training = bool(self.net.training)
         loss = super().step(x, cond_in, mask, noise, rnd_normal, dx_fn)
         # the kernel wrote parameters (and the EMA copy) in place behind autograd's back: drop the modules' packed copies
         self.net.invalidate_packed()
